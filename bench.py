@@ -15,6 +15,9 @@ Passes (all after the warm-up, each bracketed by barrier + synchronize):
   1. the TIMED region: K steps, per-kernel event profiling OFF            -> value, ms_per_step
   2. a profiled pass: the same K steps with a HIP event pair around every launch (on the launch's stream) -> roofline
   3. (full workload) K steps with the OptimizeActiveMap solve on 1 frame in 6 (the reference's key-frame cadence) -> full_solve_cadence6
+A plain run (`--gpus N --steps K --warmup W`) does pass 1 only: set-up, warm-up, the K timed steps, the line.  Everything else (the repeat regions and the
+clock probes, passes 2 onward, the rooflines, the oracle parity sample, the CPU baseline, the live-stream children) runs under --full.
+--dump-outputs DIR writes what the last timed step computed (bench/dump.py).
 Prints ONE JSON line (rank 0).  PyTorch is used for device memory, streams and torch.distributed only.
 
 This file is the entry point and the timed schedule (set-up, the step functions, passes 1-6, the verification steps, the JSON line).  Everything
@@ -75,6 +78,7 @@ from __graft_entry__ import load_package  # noqa: E402
 from bench.args import parse  # noqa: E402
 from bench.config import H, SYMBOL, W  # noqa: E402
 from bench.cpu_baseline import cpu_baseline  # noqa: E402
+from bench.dump import sample_frames, write as write_outputs  # noqa: E402
 from bench.parity_sample import parity_sample  # noqa: E402
 from bench.report import ba_solve_roofline, rooflines  # noqa: E402
 from bench.passes_multirank import db_exchange  # noqa: E402
@@ -487,7 +491,7 @@ def main():
 
     # ---- pass 1: the timed region (no per-kernel events) ----
     api.prof_enable(False)
-    clock_mhz = [api.shader_clock_mhz(stream)]          # the shader clock, measured on the device: before the warm-up and the timed region, between the repeats, after them
+    clock_mhz = [api.shader_clock_mhz(stream)] if args.full else None      # --full: the shader clock, measured on the device: before the warm-up and the timed region, between the repeats, after them
     if not args.gap_before_timed:
         for _ in range(args.warmup):                     # the contract's W untimed warm-up steps, of the timed region's own kind; timed() opens with barrier + synchronize
             step()
@@ -501,7 +505,34 @@ def main():
     for _ in range(0 if args.no_repeats else 2):
         clock_mhz.append(api.shader_clock_mhz(stream))
         repeats_ms.append(timed(args.steps, lead=0) / args.steps * 1e3)
-    clock_mhz.append(api.shader_clock_mhz(stream))
+    if clock_mhz is not None:
+        clock_mhz.append(api.shader_clock_mhz(stream))
+    if args.dump_outputs and rank == 0:
+        # what the last timed step computed (the repeat regions run the same steps on the same inputs): the per-frame outputs of a fixed sample of frames
+        fr = sample_frames(P)
+        d_fr = torch.from_numpy(fr).to(dev)
+        d_im = torch.cat([d_fr, d_fr + P])                    # their left, then their right images
+        if use_graph:
+            lo = lanes[(step_no[0] - 1) % len(lanes)]["o"]
+            o_kps, o_desc, o_cnt, o_midx, o_mdist, o_xyz, o_ok = (lo[k] for k in ("kps", "desc", "cnt", "midx", "mdist", "xyz", "ok"))
+            o_lcd = (lo["descr"], lo["best"], lo["max"], lo["dbcnt"]) if use_lcd else None
+            o_ba = lo["ba"] if use_ba else None
+        else:
+            p_last = (step_no[0] - 1) % NB
+            o_kps, o_desc, o_cnt = d_kps_b[p_last], d_desc_b[p_last], d_cnt_b[p_last]
+            o_midx, o_mdist, o_xyz, o_ok = d_midx, d_mdist, d_xyz, d_ok
+            o_lcd = (d_descr, d_best, d_max, d_dbcnt) if use_lcd else None
+            o_ba = b_out if use_ba else None
+        host = lambda t: t.cpu().numpy()
+        n_fr = len(fr)
+        write_outputs(args.dump_outputs, P, cap,
+                      kps=host(o_kps.view(2 * P, cap * 28)[d_im]).view(api.KP_DTYPE).reshape(2, n_fr, cap).transpose(1, 0, 2),
+                      desc=host(o_desc.view(2 * P, cap, 32)[d_im]).reshape(2, n_fr, cap, 32).transpose(1, 0, 2, 3),
+                      cnt=host(o_cnt[d_im]).reshape(2, n_fr).T,
+                      midx=host(o_midx.view(P, cap)[d_fr]), mdist=host(o_mdist.view(P, cap)[d_fr]),
+                      xyz=host(o_xyz.view(P, cap, 3)[d_fr]), ok=host(o_ok.view(P, cap)[d_fr]),
+                      lcd=None if o_lcd is None else [host(t) for t in o_lcd],
+                      ba=None if o_ba is None else [host(t[d_fr]) for t in o_ba])
     if args.block_trace:                # profiling builds only: which kernel's blocks sit on which CU of XCD 0 at what time (tools/block_trace_report.py)
         import ctypes
         fn = getattr(api.lib(), "myslam_debug_block_trace")        # AttributeError = this library was not built with -DMYSLAM_BLOCK_TRACE
@@ -522,7 +553,7 @@ def main():
         del d_bt
     # ---- multi-rank runs: the loop-database exchange timed stage by stage on an otherwise idle chip (bench/passes_multirank.py) ----
     collective = None
-    if world > 1 and use_lcd:
+    if world > 1 and use_lcd and args.full:
         collective = db_exchange(api, D, world, via_cpu, dev, side_stream, d_allq, d_descr, d_cand, d_best, d_max, d_dbcnt, cur_ids, NQ, P, n_db_local)
         barrier()
     frame_latency = None
@@ -894,7 +925,9 @@ def main():
     if rank == 0:
         ms_step = dt / args.steps * 1e3
         value = world * P * args.steps / dt
-        roof, roof_valu, mf, busy, peaks = rooflines(prof, alone, args.steps, P, lcd.conv2_products() if use_lcd else 3, build_id=api.build_id())
+        roof, roof_valu, mf, busy, peaks = None, None, None, {}, None
+        if args.full:
+            roof, roof_valu, mf, busy, peaks = rooflines(prof, alone, args.steps, P, lcd.conv2_products() if use_lcd else 3, build_id=api.build_id())
         n_internal = S if args.orb_internal_stream else 0        # every extractor handle runs its Gaussian pyramid on an internal stream
         out = {
             "metric": "stereo frames/sec (ORB+match+LCD+BA-build) @1241x376",

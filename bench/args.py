@@ -89,7 +89,22 @@ def parse():
                     "steps with the block trace on and write the records (npy, 2 x u64 per block that ran on XCD 0) to this file; tools/block_trace_report.py reads it")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo = debugging aid: several ranks share GPU 0 and the collectives go through host memory")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the two repeat regions and the clock probes, the extra passes (profiled, solve cadence, "
+                         "streamed input, sparse scene, extractor alone, other launch mode, growing database), the roofline objects, the oracle parity sample, "
+                         "the CPU baseline, the live-stream children and, at N > 1, the loop-database exchange stage by stage.  Without it a run sets up, "
+                         "warms up, times --steps steps and prints the line; --no-extra-passes, --no-repeats, --no-cpu-baseline, --parity-frames, "
+                         "--stream-input and --stream-mode then only take passes away from --full")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / float64; the per-frame outputs of a "
+                         "fixed, seeded sample of the batch's frames, at most 64 MB in all): two builds run with the same arguments can be compared output for output")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload == "latency":
+        ap.error("--dump-outputs: the latency workload has no timed step whose outputs could be written")
+    if not args.full:
+        args.no_extra_passes = args.no_repeats = args.no_cpu_baseline = True
+        args.parity_frames = 0
+        args.stream_mode = ""
     if args.pipeline < 0:
         args.pipeline = 1 if (args.streams == 2 and args.orb_split != 1) else 0
     if args.side_blocks_per_cu < 0:

@@ -21,6 +21,12 @@ def test_command_line_defaults(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "8", "--steps", "20", "--warmup", "3"])
     a = parse()
     assert (a.gpus, a.steps, a.warmup) == (8, 20, 3)
+    # a plain run is the timed region only; --full adds every other pass with today's defaults
+    assert not a.full and a.dump_outputs == "" and a.no_extra_passes and a.no_repeats and a.no_cpu_baseline and a.parity_frames == 0 and a.stream_mode == ""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = parse()
+    assert a.full and a.dump_outputs == "out" and not (a.no_extra_passes or a.no_repeats or a.no_cpu_baseline)
+    assert a.parity_frames == 8 and a.stream_input == 4 and a.stream_mode == "1x16,1x4,2x16,4x16"
 
 
 def test_roofline_objects_from_event_times():
@@ -64,3 +70,37 @@ def test_committed_profiles_are_the_newest_of_their_kind():
     assert abs(pmc["calibration"]["fetch_scale"] - 1.93) < 0.05                # gfx950 counts 128-byte requests as 64 bytes (MI355X_MICROARCH.md)
     peaks, ppath = peaks_file()
     assert peaks and os.path.exists(os.path.join(ROOT, ppath)) and 5500 < peaks["hbm_copy_GBps"] < 8000
+
+
+def test_dump_outputs_layout(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 arrays only, slots past an image's count zeroed (the step never writes them), the sample fixed by its seed."""
+    from bench.dump import sample_frames, write
+    api_dtype = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
+    P, cap = 512, 40
+    fr = sample_frames(P)
+    assert len(fr) == 16 and list(fr) == sorted(set(fr)) and np.array_equal(fr, sample_frames(P)) and list(sample_frames(8)) == list(range(8))
+    n = len(fr)
+    rng = np.random.default_rng(1)
+    kps = np.zeros((n, 2, cap), api_dtype)
+    for f in api_dtype.names:
+        kps[f] = rng.integers(1, 100, kps.shape)
+    desc = rng.integers(1, 256, (n, 2, cap, 32)).astype(np.uint8)
+    cnt = rng.integers(0, cap + 1, (n, 2)).astype(np.int32)
+    midx = rng.integers(1, 100, (n, cap)).astype(np.int32); xyz = rng.standard_normal((n, cap, 3)) + 5
+    ok = np.ones((n, cap), np.uint8)
+    lcd = (rng.random((P, 1064), dtype=np.float32), np.arange(P, dtype=np.int64), rng.random(P, dtype=np.float32), np.ones(P, np.int32))
+    ba = [rng.standard_normal((n, m)) for m in (36, 9, 18, 6, 3, 1)]
+    names = write(str(tmp_path), P, cap, kps, desc, cnt, midx, midx, xyz, ok, lcd=lcd, ba=ba)
+    got = {m: np.load(os.path.join(tmp_path, m + ".npy")) for m in names}
+    assert sorted(f[:-4] for f in os.listdir(tmp_path)) == names and all(a.dtype in (np.float32, np.float64) for a in got.values())
+    k = got["orb_keypoints"]
+    assert k.shape == (n, 2, cap, 7) and got["orb_descriptors"].shape == (n, 2, cap, 32) and got["triangulated_xyz"].shape == (n, cap, 3)
+    for i in range(n):
+        for s in range(2):
+            c = cnt[i, s]
+            assert np.array_equal(k[i, s, :c, 5], kps[i, s]["octave"][:c]) and not k[i, s, c:].any() and not got["orb_descriptors"][i, s, c:].any()
+        c = cnt[i, 0]
+        assert np.array_equal(got["match_index"][i, :c], midx[i, :c]) and not got["match_index"][i, c:].any() and not got["triangulated_xyz"][i, c:].any()
+    assert np.array_equal(got["db_best_id"], np.arange(P)) and got["ba_Hpp"].shape == (n, 36) and np.array_equal(got["sample_frames"], fr)
+    with pytest.raises(AssertionError):           # the 64 MB bound
+        write(str(tmp_path / "big"), P, cap, kps, desc, cnt, midx, midx, xyz, ok, lcd=(np.zeros((P, 40000), np.float32),) + lcd[1:])

@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 
 @pytest.mark.parametrize("extra", [["--cpu-pairs", "2", "--verify"], ["--no-cpu-baseline", "--workload", "orb_match", "--streams", "1"]])
 def test_bench_json_contract(extra):
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--pairs", "16"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--pairs", "16", "--full"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -95,7 +95,7 @@ def test_bench_two_ranks_on_one_gpu():
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--pairs", "16",
-           "--backend", "gloo", "--verify"]
+           "--backend", "gloo", "--verify", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
@@ -133,7 +133,7 @@ def test_bench_self_launch_eight_ranks():
     shards, check_shard_order, NQ = 8 P queries per shard scan, two all-gathers per step, the 8-way candidate merge) so that the first real
     8-GPU run cannot fail on something two ranks never exercised."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--pairs", "8", "--backend", "gloo",
-           "--db", "640", "--stream-input", "2"]
+           "--db", "640", "--stream-input", "2", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -145,3 +145,37 @@ def test_bench_self_launch_eight_ranks():
     assert "x8" in d["config"]["parallelism"] and "5120-KF" in d["config"]["workload"]
     assert d["streamed"]["value"] > 0 and d["full_solve_cadence6"]["value"] > 0
     assert len(d["per_rank_ms_per_step"]) == 8 and len(d["db_exchange"]["shard_scan_ms"]) == 8 and d["db_exchange"]["shard_rows"] == 640
+
+
+@pytest.mark.parametrize("graph", ["1", "0"])
+def test_bench_plain_line_and_dumped_outputs(graph, tmp_path, synth, oracle):
+    """The plain command (no --full) times its steps and prints the line, nothing measured by a pass of its own; --dump-outputs writes what the last timed
+    step computed (float32 / float64, at most 64 MB), the sampled frames' key-points bit-exact with the oracle on those frames' images.  graph 1 = the
+    recorded steps on lanes (the small-batch default), graph 0 = the pipelined eager schedule (the default at 512 pairs)."""
+    import numpy as np
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--pairs", "16", "--graph", graph,
+           "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["metric"].startswith("stereo frames/sec") and d["unit"] == "stereo frames/s" and d["higher_is_better"] is True and d["dtype"]
+    assert d["steps"] == 3 and d["warmup"] == 1 and abs(d["value"] - 16 * 3 / (d["ms_per_step"] * 3e-3)) < 1e-6 * d["value"]
+    assert d["repeats_ms_per_step"] == [d["ms_per_step"]] and d["clock_mhz"] is None
+    for k in ("roofline", "profiled_pass", "full_solve_cadence6", "streamed", "parity_sample", "cpu_baseline", "stream_mode", "db_grow", "extractor_alone"):
+        assert not d[k], k
+    files = {f[:-4]: np.load(os.path.join(tmp_path, f)) for f in os.listdir(tmp_path)}
+    assert {"sample_frames", "orb_count", "orb_keypoints", "orb_descriptors", "match_index", "triangulated_xyz", "lcd_descriptor", "db_best_id", "ba_Hpp"} <= set(files)
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values()) and sum(a.nbytes for a in files.values()) <= 64 << 20
+    fr = files["sample_frames"].astype(int)
+    assert list(fr) == list(range(16)) and files["orb_count"].shape == (16, 2) and files["lcd_descriptor"].shape == (16, 1064)
+    frames = synth.stereo_batch(16, stream_id=0, n_rect=6000)
+    for side in range(2):
+        kp, desc = oracle.detect_and_compute(oracle.params(2000), frames[fr[5], side])
+        n = int(files["orb_count"][5, side])
+        assert n == len(kp) > 1000
+        got = files["orb_keypoints"][5, side]
+        ref = np.stack([kp[f].astype(np.float32) for f in ("x", "y", "size", "angle", "response", "octave", "class_id")], -1)
+        assert np.array_equal(got[:n], ref) and not got[n:].any()
+        assert np.array_equal(files["orb_descriptors"][5, side, :n], desc.astype(np.float32))

@@ -1,13 +1,14 @@
 #!/bin/bash
 # descriptor kernel, direct-to-LDS form: blocks per CU of its limited grid swept further (2 / 3 windows per wave in flight); same box, 2 rounds
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"      # where the runs' lines and logs go
 P=a-simple-stereo-slam-system-with-deep-loop-closing_amd
 cp $P/libmyslam_hip.so /tmp/orig_lib.so
 run() { # name lib extra-args
   cp $2 $P/libmyslam_hip.so
-  python bench.py --no-cpu-baseline --parity-frames 0 --stream-input 0 --stream-mode "" --no-extra-passes --steps 60 $3 > gpurun_out/gk2_$1_$rep.json 2> gpurun_out/gk2_$1_$rep.err
+  python bench.py --full --no-cpu-baseline --parity-frames 0 --stream-input 0 --stream-mode "" --no-extra-passes --steps 60 $3 > $OUT/gk2_$1_$rep.json 2> $OUT/gk2_$1_$rep.err
   python -c "
 import json
-d = json.load(open('gpurun_out/gk2_$1_$rep.json')); print('$1', $rep, [round(x, 3) for x in d['repeats_ms_per_step']])"
+d = json.load(open('$OUT/gk2_$1_$rep.json')); print('$1', $rep, [round(x, 3) for x in d['repeats_ms_per_step']])"
 }
 for rep in 1 2; do
   run glds0_side2 tools/build/ab/libglds0.so ""

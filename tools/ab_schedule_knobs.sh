@@ -1,11 +1,12 @@
 #!/bin/bash
 # schedule knobs re-measured after the descriptor kernel's direct-to-LDS form (build v69): extractor handles per step, DeepLCD chain split, internal blur stream; same box, 2 rounds
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"      # where the runs' lines and logs go
 run() { # name args
-  python bench.py --no-cpu-baseline --parity-frames 0 --stream-input 0 --stream-mode "" --no-extra-passes --steps 60 $2 > gpurun_out/sk_$1_$rep.json 2> gpurun_out/sk_$1_$rep.err
+  python bench.py --full --no-cpu-baseline --parity-frames 0 --stream-input 0 --stream-mode "" --no-extra-passes --steps 60 $2 > $OUT/sk_$1_$rep.json 2> $OUT/sk_$1_$rep.err
   python -c "
 import json
 try:
-    d = json.load(open('gpurun_out/sk_$1_$rep.json')); print('$1', $rep, [round(x, 3) for x in d['repeats_ms_per_step']])
+    d = json.load(open('$OUT/sk_$1_$rep.json')); print('$1', $rep, [round(x, 3) for x in d['repeats_ms_per_step']])
 except Exception as e: print('$1 failed', e)"
 }
 for rep in 1 2; do

@@ -1,16 +1,17 @@
 #!/bin/bash
 # Per-rank compute of an N-GPU job measured on ONE GPU (bench.py --emulate-world N, no collective): N = 1 (the plain bench step), 2, 4, 8, same box, back to back.
-#   tools/emulated_world.sh <tag>  -> gpurun_out/r06_emulated_world_<tag>.json
+#   tools/emulated_world.sh <tag>  -> $OUT/r06_emulated_world_<tag>.json
+OUT=${OUT:-bench_out}; mkdir -p "$OUT"      # where the runs' lines and logs go
 TAG=${1:-x}
 for n in 1 2 4 8; do
-  timeout 600 python bench.py --no-cpu-baseline --parity-frames 8 --stream-input 0 --stream-mode "" --steps 100 --emulate-world $n > gpurun_out/emu_${TAG}_$n.json 2> gpurun_out/emu_${TAG}_$n.err; echo "N=$n rc=$?"
+  timeout 600 python bench.py --full --no-cpu-baseline --parity-frames 8 --stream-input 0 --stream-mode "" --steps 100 --emulate-world $n > $OUT/emu_${TAG}_$n.json 2> $OUT/emu_${TAG}_$n.err; echo "N=$n rc=$?"
 done
 python - <<PY
 import json
 out = {"build": "$TAG", "points": []}
 for n in (1, 2, 4, 8):
     try:
-        d = json.load(open(f"gpurun_out/emu_${TAG}_{n}.json"))
+        d = json.load(open(f"$OUT/emu_${TAG}_{n}.json"))
     except Exception as e:
         print(n, "failed", e); continue
     e = d.get("emulated_world") or {}
@@ -23,5 +24,5 @@ for n in (1, 2, 4, 8):
                           "clock_mhz": d.get("clock_mhz")})
     print(out["points"][-1])
 out["note"] = "bench.py --emulate-world N on one MI355X, same box, back to back; N = 1 is the plain 10 000-row step.  No collective ran: a real N-GPU job adds two all-gathers per step"
-json.dump(out, open("gpurun_out/r06_emulated_world_$TAG.json", "w"), indent=1)
+json.dump(out, open("$OUT/r06_emulated_world_$TAG.json", "w"), indent=1)
 PY

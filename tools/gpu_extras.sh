@@ -1,11 +1,12 @@
 #!/bin/bash
 # Secondary bench lines of a round: the sparse stream (the two-phase FAST path's regime), the other workloads, the joined one-stream
 # run whose profiled pass gives clean per-kernel times.   tools/gpu_extras.sh <tag>
-TAG=${1:-x}; mkdir -p gpurun_out
-run() { name=$1; shift; timeout 900 python bench.py --no-cpu-baseline "$@" > gpurun_out/bench_${name}_$TAG.json 2> gpurun_out/bench_${name}_$TAG.err; python - <<PY
+OUT=${OUT:-bench_out}      # where the runs' lines and logs go
+TAG=${1:-x}; mkdir -p "$OUT"
+run() { name=$1; shift; timeout 900 python bench.py --full --no-cpu-baseline "$@" > $OUT/bench_${name}_$TAG.json 2> $OUT/bench_${name}_$TAG.err; python - <<PY
 import json
 try:
-    d = json.load(open("gpurun_out/bench_${name}_$TAG.json"))
+    d = json.load(open("$OUT/bench_${name}_$TAG.json"))
     print("$name: fps", round(d["value"]), "ms/step", round(d["ms_per_step"], 3), {k: round(v, 3) for k, v in ((d.get("profiled_pass") or {}).get("kernel_ms_per_step") or {}).items()})
 except Exception as e:
     print("$name failed:", e)
