@@ -557,10 +557,15 @@ int myslam_lk_track_batch(myslam_lk* h, const uint8_t* d_prev, const uint8_t* d_
  * mRelativePoseToLoopKF :590-601), information I6, error log(meas^-1 * T[v0] * T[v1]^-1) (include/myslam/g2o_types.h:157-167),
  * Jacobians by g2o's central differences (delta 1e-9; the analytic linearizeOplus is commented out at g2o_types.h:168-182).
  * Runs g2o's Levenberg for max_iters (20, :606) iterations.  *final_chi2 = sum of e^T e at the returned poses, *iters = iterations
- * done.  Host pointers; uploads, runs and downloads synchronously on the null stream.
+ * done.  Host pointers; uploads, runs and downloads synchronously on the calling thread's own non-blocking stream (never the
+ * legacy null stream).
  * Solver structure: key-frames in index order form the chain; every edge that does not join neighbouring free key-frames adds
- * one separator key-frame to a dense Schur block (at most 96 separators: MYSLAM_ERR_UNSUPPORTED beyond, i.e. graphs far from
- * chain + loops); long chain runs are cut by further separators so that the serial block-tridiagonal sweeps run in parallel.
+ * one separator key-frame to a dense Schur block; long chain runs are cut by further separators so that the serial
+ * block-tridiagonal sweeps run in parallel.  Up to 96 separators in all, the fast path keeps the Schur pivots in LDS; graphs
+ * whose natural separators fit 96 stay on it (their cuts are coarsened until they fit).  Beyond that the general path takes up
+ * to 1024 separators, cuts included (MYSLAM_ERR_UNSUPPORTED beyond), with pivots and right-hand side in device memory: about
+ * (32 ntile 256 + 2 ldz^2 + 2 rowsPad ldz) * 8 bytes for the call, ldz = 6 |S| + 1 rounded up to 16, ntile = (ldz/16)(ldz/16 + 1)/2,
+ * rowsPad = 6 (chain key-frames) rounded up to 4 — ~6 GB near the limit (1012 separators), where one Levenberg iteration takes ~7.3 s on an MI355X.
  * ------------------------------------------------------------------------------------------ */
 int myslam_pose_graph_optimize(double* poses, int n, const uint8_t* fixed, const int32_t* edge_v0, const int32_t* edge_v1,
                                const double* meas, int n_edges, int max_iters, double* final_chi2, int* iters);

@@ -18,6 +18,8 @@ The error function itself is checked sharply: the oracle's chi2 at the device's 
 import numpy as np
 import pytest
 
+from pgo_structure import PG_MAXS, PG_MAXS_BIG, pg_structure
+
 pytestmark = pytest.mark.gpu
 
 def _cmp(got, ref, tol=None, rerun=None):
@@ -114,13 +116,14 @@ def test_pose_graph_rejects_bad_input(api, synth):
         api.pose_graph_optimize(poses, fixed, e1, e1, meas)           # self edges
 
 
-def _dense_graph(oracle, n=240, noise=0.02, seed=3):
-    """a graph that is nowhere near a chain: every key-frame of the upper half linked to up to 120 of the lower half (7 260 edges, no chain edge at all)"""
+def _dense_graph(oracle, n=240, noise=0.02, seed=3, complete=False):
+    """a graph that is nowhere near a chain: every key-frame of the upper half linked to up to 120 of the lower half (7 260 edges, no chain edge at all);
+    complete: every pair of key-frames linked"""
     rng = np.random.default_rng(seed)
     gt = np.tile(np.array([0, 0, 0, 1, 0, 0, 0.0]), (n, 1)); gt[:, 4] = np.arange(n)
     for i in range(n):                                               # a gently turning drive
         gt[i] = oracle.se3_compose(oracle.se3_exp(np.array([0.0, 0.02 * np.sin(i / 9.0), 0.0, 0.0, 0.004 * i, 0.0])), gt[i])
-    a, b = np.meshgrid(np.arange(n), np.arange(n)); m = (a - b) >= n // 2
+    a, b = np.meshgrid(np.arange(n), np.arange(n)); m = (a > b) if complete else (a - b) >= n // 2
     ea, eb = a[m].astype(np.int32), b[m].astype(np.int32)
     ms = np.stack([oracle.se3_compose(oracle.se3_compose(gt[i], gt[j], invert_b=True), oracle.se3_exp(noise * rng.standard_normal(6) * np.array([1, 1, 1, 0.1, 0.1, 0.1])))
                    for i, j in zip(ea, eb)])
@@ -146,7 +149,213 @@ def test_pose_graph_with_more_separators_than_the_fast_path(api, oracle):
     chk = oracle.pose_graph_optimize(got[0], fixed, ea, eb, ms, iters=0)[1]
     assert abs(chk - got[1]) <= 1e-9 * got[1]
     assert np.abs(got[0][0] - ref[0][0]).max() < 1e-15
-    # a chain of 900 with 130 loops: more separators than the fast path AND long chain runs between them (sweeps + general Schur together)
+
+
+# ---- the general Schur path (more than PG_MAXS = 96 separators) at its sizes and its limits -------------------------------------------
+# Every graph below states the regime it drives the library into through tests/pgo_structure.py (the host's separator rule restated) and
+# is held to bars that do not scale with its size:
+#   chi2 to 1e-6 relative — or to 10x the oracle's own chi2 spread where that is wider: after one or two iterations of a graph that takes a
+#   large first step, the oracle's chi2 itself moves by up to 3e-5 relative when its input moves by one ulp — and the same iteration count;
+#   the oracle's chi2 at the device's poses equal to the device's to 1e-9 (the error
+#   function, sharply); fixed key-frames to 1e-15; poses within 10x the oracle's own one-ulp spread on that graph at the same iteration
+#   count (the oracle re-run on poses moved by 1e-13 relative, as _cmp's rerun measures it) — at iters = 1 this exposes the linear solve
+#   before the soft modes drift.
+
+def _noisy_relative(oracle, gt, ea, eb, rng, noise=0.003):
+    """edges (ea, eb) at their true relative pose times a small random motion (the extra edges of tools/gpu_fuzz_round6.py)"""
+    return np.stack([oracle.se3_compose(oracle.se3_compose(gt[i], gt[j], invert_b=True), oracle.se3_exp(noise * rng.standard_normal(6)))
+                     for i, j in zip(ea, eb)])
+
+
+def _skip2_graph(synth, oracle, n, seed=11):
+    """synth's drive (odometry chain, drifted poses) without its loops, plus an edge (i, i-2) for every i >= 2; key-frame 0 fixed.
+    Separators: 96 at n = 287 ... 289, 97 (+ 4 cuts) at 290, 999 (+ 13) at 3000, more than 1024 at 3100 (tests/test_pgo_structure.py)."""
+    poses, _, e0, e1, meas, gt = synth.pose_graph(n, 0, seed=seed)
+    rng = np.random.default_rng(seed)
+    ea = np.arange(2, n); eb = ea - 2
+    fixed = np.zeros(n, np.uint8); fixed[0] = 1
+    return (poses, fixed, np.r_[e0, ea].astype(np.int32), np.r_[e1, eb].astype(np.int32), np.r_[meas, _noisy_relative(oracle, gt, ea, eb, rng)])
+
+
+def _clustered_loops_graph(synth, oracle, n=900, n_extra=129, lo=300, span=40, seed=4):
+    """synth's drive with its one loop (the current key-frame back one lap) plus n_extra short loops (3 .. span key-frames back) from
+    distinct key-frames in [lo, n - 20): the loops sit in one part of the drive, so the first ~lo key-frames form one long chain run
+    that the host cuts into sweeps of ~75 (loops spread uniformly, as synth places them, leave runs of a few key-frames)"""
+    poses, fixed, e0, e1, meas, gt = synth.pose_graph(n, 1, seed=seed)
+    rng = np.random.default_rng(seed)
+    ea = np.sort(rng.choice(np.arange(lo, n - 20), n_extra, replace=False)); eb = ea - rng.integers(3, span + 1, n_extra)
+    return (poses, fixed, np.r_[e0, ea].astype(np.int32), np.r_[e1, eb].astype(np.int32), np.r_[meas, _noisy_relative(oracle, gt, ea, eb, rng)])
+
+
+def _sharp(api, oracle, G, its, tag):
+    """the bars above for one graph at one iteration count; returns (pose deviation, oracle pose spread)"""
+    poses, fixed, e0, e1, meas = G
+    ref = oracle.pose_graph_optimize(poses, fixed, e0, e1, meas, iters=its)
+    got = api.pose_graph_optimize(poses, fixed, e0, e1, meas, iters=its)
+    rng = np.random.default_rng(0)
+    reruns = [oracle.pose_graph_optimize(poses * (1 + 1e-13 * rng.standard_normal(poses.shape)), fixed, e0, e1, meas, iters=its) for _ in range(4)]
+    spread = max(np.abs(r[0] - ref[0]).max() for r in reruns)
+    chi_spread = max(abs(r[1] - ref[1]) for r in reruns) / ref[1]
+    assert got[2] == ref[2], (tag, its, got[2], ref[2])
+    assert abs(got[1] - ref[1]) <= max(1e-6, 10 * chi_spread) * ref[1], (tag, its, got[1], ref[1], chi_spread)
+    chk = oracle.pose_graph_optimize(got[0], fixed, e0, e1, meas, iters=0)[1]
+    assert abs(chk - got[1]) <= 1e-9 * got[1], (tag, its, chk, got[1])
+    fx = fixed.astype(bool)
+    assert np.abs(got[0][fx] - ref[0][fx]).max() < 1e-15, tag
+    s = np.sign(np.sum(got[0][:, :4] * ref[0][:, :4], axis=1))[:, None]
+    dev = max(np.abs(got[0][:, :4] * s - ref[0][:, :4]).max(), np.abs(got[0][:, 4:] - ref[0][:, 4:]).max())
+    print(f"PGO-SHARP {tag} iters={its} chi2={got[1]:.9g} rel={abs(got[1] - ref[1]) / ref[1]:.2e} chi-spread={chi_spread:.2e} dev={dev:.3g} "
+          f"spread={spread:.3g}")
+    assert dev < 10 * spread, (tag, its, dev, spread)
+    return dev, spread
+
+
+def test_pose_graph_general_path_with_long_chain_runs(api, oracle, synth):
+    """A chain of 900 with 130 loops: more separators than the fast path AND long chain runs between them, so the general Schur system
+    (k_pg_schur<true>) runs together with real sweeps: runs cut by the host, a non-trivial Z^T Z (k_pg_syrk) subtracted, and k_pg_y
+    reading xS from device memory.  103 natural separators + 3 cuts, the longest run into the sweep 75 key-frames.
+    Measured at iters = 1 / 2 / 20: poses 3.7e-4 / 3.3e-4 / 2.2e-3 from the oracle, its own spread 6.1e-4 / 3.8e-4 / 2.9e-3; chi2 1.0e-5 /
+    4.3e-6 / 9.2e-8 relative, the oracle's own chi2 spread 1.8e-5 / 5.5e-6 / 3.7e-7."""
+    G = _clustered_loops_graph(synth, oracle)
+    st = pg_structure(len(G[0]), G[1], G[2], G[3])
+    assert st.path == "general" and st.natural > PG_MAXS and st.cuts >= 1 and st.longest_run >= 64, st
+    chi0 = oracle.pose_graph_optimize(*G, iters=0)[1]
+    for its in (1, 2, 20):
+        _sharp(api, oracle, G, its, "clustered-900")
+    assert oracle.pose_graph_optimize(*G)[1] < 0.5 * chi0
+
+
+@pytest.mark.parametrize("case", ["fast-full", "first-general", "lmax-doubles"])
+def test_pose_graph_fast_general_boundary(api, oracle, synth, case):
+    """The switch between the two paths.  fast-full: exactly 96 separators (mS = 576 fills the fast path's LDS pivots, k_pg_y's sx[576]
+    and the PER = 9 register back substitution; the fast budget leaves no room for a cut, lmax doubles until none remains);
+    first-general: the same family one key-frame longer, 97 natural separators + 4 cuts (sepBudget and bigS flip, k_pg_y's big branch);
+    lmax-doubles: 95 natural separators whose first cuts do not fit the fast budget: lmax doubles and one cut stays.
+    Measured poses from the oracle at iters = 1 / 2 / 20 (the oracle's own spread in brackets): fast-full 1.5e-4 / 2.8e-4 / 4.5e-2
+    (3.5e-4 / 5.8e-4 / 4.0e-2), first-general 1.8e-4 / 3.7e-4 / 3.4e-2 (2.8e-4 / 5.9e-4 / 4.5e-2), lmax-doubles 4.0e-4 / 2.8e-4 / 3.9e-3
+    (6.9e-4 / 3.0e-4 / 3.4e-3); chi2 within 9e-7 relative on the skip-2 chains, 1.3e-5 / 1.9e-6 / 4.4e-7 on lmax-doubles (the oracle's
+    own chi2 spread 2.0e-5 / 5.2e-6 / 4.8e-7)."""
+    if case == "lmax-doubles":
+        G = _clustered_loops_graph(synth, oracle, lo=330, span=30)
+    else:
+        G = _skip2_graph(synth, oracle, 289 if case == "fast-full" else 290)
+    st = pg_structure(len(G[0]), G[1], G[2], G[3])
+    want = {"fast-full": (96, 0, "fast"), "first-general": (97, 4, "general"), "lmax-doubles": (95, 1, "fast")}[case]
+    assert (st.natural, st.cuts, st.path) == want, st
+    assert st.doublings >= 1 or case == "first-general"
+    for its in (1, 2, 20):
+        _sharp(api, oracle, G, its, case)
+
+
+def test_pose_graph_near_the_separator_limit(api, oracle, synth):
+    """999 natural separators + 13 cuts (the skip-2 chain of 3000 key-frames): ldz = 6080, ntile = 72 390, the Z^T Z partials
+    d_P = 32 * ntile * 256 doubles = 4.7 GB, the 6072 x 6072 factorisation in one 1024-thread workgroup.  One Levenberg iteration takes ~7.3 s on the MI355X (measured:
+    7.4 s for iters = 1, 14.7 s for 2), so the reference's 20 would cost ~150 s on their own: run at iters = 1, 2 and 5.
+    Measured at iters = 1 / 2 / 5: poses 1.7e-3 / 4.1e-3 / 9.1e-3 from the oracle, its own spread 8.7e-3 / 8.1e-3 / 1.7e-2; chi2 within
+    1.8e-7 relative.  The call allocates ~6 GB and must give all of it back."""
+    import time
+    import torch
+    G = _skip2_graph(synth, oracle, 3000)
+    st = pg_structure(len(G[0]), G[1], G[2], G[3])
+    assert (st.natural, st.cuts, st.path) == (999, 13, "general") and st.separators <= PG_MAXS_BIG, st
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    for its in (1, 2, 5):
+        t0 = time.perf_counter()
+        _sharp(api, oracle, G, its, "skip2-3000")
+        print(f"PGO-TIME skip2-3000 iters={its} {time.perf_counter() - t0:.2f} s with the oracle")
+        free1 = torch.cuda.mem_get_info()[0]
+        assert abs(free1 - free0) <= 64 << 20, (free0, free1)
+
+
+def test_pose_graph_refuses_more_than_1024_separators(api, oracle, synth):
+    """1025 separators (the skip-2 chain of 3100 key-frames): MYSLAM_ERR_UNSUPPORTED, the caller's poses untouched, and the next graph
+    (the first general one of the boundary test) still solves to the oracle's result"""
+    import ctypes as C
+    poses, fixed, e0, e1, meas = _skip2_graph(synth, oracle, 3100)
+    assert pg_structure(len(poses), fixed, e0, e1).path == "refused"
+    with pytest.raises(api.MyslamError) as ei:
+        api.pose_graph_optimize(poses, fixed, e0, e1, meas)
+    assert ei.value.code == api.ERR_UNSUPPORTED
+    mine = np.ascontiguousarray(poses, np.float64).copy(); before = mine.copy()
+    chi = C.c_double(-1.0); it = C.c_int(-1)
+    rc = api.lib().myslam_pose_graph_optimize(mine.ctypes.data_as(C.c_void_p), len(mine), fixed.ctypes.data_as(C.c_void_p), e0.ctypes.data_as(C.c_void_p),
+                                              e1.ctypes.data_as(C.c_void_p), np.ascontiguousarray(meas).ctypes.data_as(C.c_void_p), len(e0), 20,
+                                              C.byref(chi), C.byref(it))
+    assert rc == api.ERR_UNSUPPORTED
+    assert mine.tobytes() == before.tobytes()
+    _sharp(api, oracle, _skip2_graph(synth, oracle, 290), 20, "after-refusal")
+
+
+def test_pose_graph_general_structure_on_the_general_path(api, oracle, synth):
+    """test_pose_graph_general_structure's mutations on a graph that takes the general path: edges in either orientation, a duplicated
+    chain edge and a duplicated loop, two loops into one key-frame, fixed key-frames inside the chain and among the loops.
+    Measured at iters = 1 / 2 / 20: poses 2.5e-4 / 3.9e-4 / 1.6e-3 from the oracle, its own spread 5.9e-4 / 6.1e-4 / 1.8e-3."""
+    poses, fixed, e0, e1, meas = _clustered_loops_graph(synth, oracle)
+    rng = np.random.default_rng(0)
+    flip = rng.uniform(size=len(e0)) < 0.4
+    inv = np.stack([oracle.se3_compose(np.array([0, 0, 0, 1, 0, 0, 0.0]), m, invert_b=True) for m in meas])
+    e0f = np.where(flip, e1, e0); e1f = np.where(flip, e0, e1); mf = np.where(flip[:, None], inv, meas)
+    lp = 899                                                           # synth's loop edge: the current key-frame back one lap
+    a, b = max(e0[lp], e1[lp]) - 3, min(e0[lp], e1[lp])
+    extra = oracle.se3_compose(poses[a], poses[b], invert_b=True)
+    e0f = np.concatenate([e0f, e0f[10:11], e0f[-5:-4], [a]]).astype(np.int32); e1f = np.concatenate([e1f, e1f[10:11], e1f[-5:-4], [b]]).astype(np.int32)
+    mf = np.concatenate([mf, mf[10:11], mf[-5:-4], extra[None]])
+    fixed = fixed.copy(); fixed[[40, 41, 600]] = 1
+    G = (poses, fixed, e0f, e1f, mf)
+    st = pg_structure(len(poses), fixed, e0f, e1f)
+    assert st.path == "general" and st.longest_run >= 64, st
+    for its in (1, 2, 20):
+        _sharp(api, oracle, G, its, "mutated-900")
+
+
+def test_pose_graph_nearly_complete_graph(api, oracle):
+    """111 key-frames, every pair linked, key-frame 0 fixed: 108 of the 110 free key-frames become separators and 2 remain in the chain
+    (a 648 x 648 general Schur system over a 2-key-frame sweep).  Measured at iters = 1 / 2 / 20: poses 2.5e-7 / 5.2e-8 / 2.1e-6 from the
+    oracle, its own spread 4.5e-7 / 8.0e-8 / 2.7e-6; chi2 within 3.3e-8 relative."""
+    G = _dense_graph(oracle, n=111, complete=True)
+    st = pg_structure(111, G[1], G[2], G[3])
+    assert (st.natural, st.cuts, st.n_chain, st.path) == (108, 0, 2, "general"), st
+    for its in (1, 2, 20):
+        _sharp(api, oracle, G, its, "complete-111")
+
+
+def test_correct_map_points_device_on_a_caller_stream(api, oracle, synth):
+    """myslam_correct_map_points_device: device buffers, the caller's stream, errors through d_status"""
+    import ctypes as C
+    import torch
+    L = api.lib()
+    poses, fixed, e0, e1, meas, _ = synth.pose_graph(80, 1, seed=8)
+    new = oracle.pose_graph_optimize(poses, fixed, e0, e1, meas)[0]
+    rng = np.random.default_rng(2)
+    n = 4999                                                           # not a whole number of 256-thread blocks
+    kf = rng.integers(-3, 80, n).astype(np.int32); kf[:3] = [0, 79, -1]
+    pts = rng.normal(0, 30, (n, 3))
+    ref = oracle.correct_map_points(poses, new, kf, pts)
+    st = torch.cuda.Stream()
+    d_old, d_new = torch.from_numpy(poses).cuda(), torch.from_numpy(new).cuda()
+
+    def run(kf_, n_):
+        d_kf = torch.from_numpy(kf_[:n_].copy()).cuda(); d_pts = torch.from_numpy(pts[:n_].copy()).cuda()
+        d_status = torch.zeros(1, dtype=torch.int32, device="cuda")
+        st.wait_stream(torch.cuda.current_stream())
+        rc = L.myslam_correct_map_points_device(d_old.data_ptr(), d_new.data_ptr(), 80, d_kf.data_ptr(), d_pts.data_ptr(), n_, d_status.data_ptr(),
+                                                C.c_void_p(st.cuda_stream))
+        st.synchronize()
+        return rc, d_pts.cpu().numpy(), int(d_status.cpu().item())
+
+    rc, got, status = run(kf, n)
+    assert rc == api.OK and status == api.OK
+    assert np.abs(got - ref).max() < 1e-10
+    assert got[kf < 0].tobytes() == pts[kf < 0].tobytes()             # first_kf < 0: bit-identical
+    assert np.linalg.norm(got - pts, axis=1)[kf >= 0].max() > 1e-3
+    bad = kf.copy(); bad[[5, 4998]] = [80, 1 << 20]
+    rc, got, status = run(bad, n)
+    assert rc == api.OK and status == api.ERR_INVALID                 # an index >= n_poses: reported through d_status
+    ok = np.ones(n, bool); ok[[5, 4998]] = False
+    assert np.abs(got[ok] - ref[ok]).max() < 1e-10 and got[~ok].tobytes() == pts[~ok].tobytes()
+    assert L.myslam_correct_map_points_device(None, None, 80, None, None, 0, None, C.c_void_p(st.cuda_stream)) == api.OK
+    assert run(kf, 0)[0] == api.OK
 
 
 def test_correct_map_points(api, oracle, synth):
