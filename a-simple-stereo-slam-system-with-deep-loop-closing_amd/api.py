@@ -757,6 +757,51 @@ class LKTracker:
                                            C.c_void_p(d_status), C.c_void_p(d_err or None)), "myslam_lk_track_batch")
 
 
+# ---------------------------------------------------------------------------------- lens undistortion
+class Undistorter:
+    """Camera::UndistortImage (src/camera.cpp:36-48) = cv::undistort(src, dst, K, D) for one camera at one image size, as
+    Frontend::GrabStereoImage runs it when Camera.bNeedUndistortion is 1 (src/frontend.cpp:47-51).  K = (fx, fy, cx, cy),
+    D = (k1, k2, p1, p2), both passed as float."""
+
+    def __init__(self, rows, cols, K, D, stream=None):
+        self.rows, self.cols = int(rows), int(cols)
+        k = np.ascontiguousarray(K, np.float32).reshape(4); d = np.ascontiguousarray(D, np.float32).reshape(4)
+        self._h = C.c_void_p()
+        _check(lib().myslam_undistort_create(C.byref(self._h), self.rows, self.cols, _p(k), _p(d)), "myslam_undistort_create")
+        if stream is not None:
+            _check(lib().myslam_undistort_set_stream(self._h, C.c_void_p(stream)), "myslam_undistort_set_stream")
+
+    def __del__(self):
+        if getattr(self, "_h", None) and self._h.value and _lib is not None:
+            lib().myslam_undistort_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def set_stream(self, stream):
+        _check(lib().myslam_undistort_set_stream(self._h, C.c_void_p(stream)), "myslam_undistort_set_stream")
+
+    def UndistortImage(self, src, dst=None):
+        """host arrays (rows x cols uint8, any row pitch); dst=None returns a new array, dst=src undistorts in place"""
+        if src.dtype != np.uint8 or src.shape != (self.rows, self.cols) or src.strides[1] != 1:
+            raise ValueError(f"expected a {self.rows} x {self.cols} uint8 image with unit column stride")
+        if dst is None:
+            dst = np.empty((self.rows, self.cols), np.uint8)
+        if dst.dtype != np.uint8 or dst.shape != (self.rows, self.cols) or dst.strides[1] != 1:
+            raise ValueError(f"expected a {self.rows} x {self.cols} uint8 output with unit column stride")
+        _check(lib().myslam_undistort_image(self._h, _p(src), src.strides[0], _p(dst), dst.strides[0]), "myslam_undistort_image")
+        return dst
+
+    def batch(self, d_src, batch, src_step, src_stride, d_dst, dst_step, dst_stride):
+        """device pointers, asynchronous on the handle's stream"""
+        _check(lib().myslam_undistort_batch(self._h, C.c_void_p(d_src), int(batch), int(src_step), C.c_size_t(src_stride), C.c_void_p(d_dst),
+                                            int(dst_step), C.c_size_t(dst_stride)), "myslam_undistort_batch")
+
+    def get_map(self):
+        """OpenCV's maps: xy (rows, cols, 2) int16 (CV_16SC2) and frac (rows, cols) uint16 (CV_16UC1)"""
+        xy = np.empty((self.rows, self.cols, 2), np.int16); frac = np.empty((self.rows, self.cols), np.uint16)
+        _check(lib().myslam_undistort_get_map(self._h, _p(xy), _p(frac)), "myslam_undistort_get_map")
+        return xy, frac
+
+
 # ---------------------------------------------------------------------------------- pose-only optimisation
 def pose_only_optimize(pose, pts3d, obs, K, chi2_th=5.991, rounds=4, iters=10, pre_optimize=0):
     """The g2o part of Frontend::EstimateCurrentPose (src/frontend.cpp:176-276).  Returns (pose7, outlier flags, inlier count)."""

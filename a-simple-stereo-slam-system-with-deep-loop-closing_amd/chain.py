@@ -136,10 +136,16 @@ IDENT = np.array([0, 0, 0, 1, 0, 0, 0], float)
 
 def camera_from_config(cfg):
     """System::GetCamera (system.cpp:101-146): BOTH cameras take the Camera.right.* keys (reference quirk 8), every value passes through a
-    float, baseline = bf / fx in float"""
+    float, baseline = bf / fx in float.  Camera.bNeedUndistortion != 0 (system.cpp:34; an absent key reads 0) adds "undistort": True and the
+    distortion of each camera, "dist_left" = Camera.left.{k1,k2,p1,p2} and "dist_right" = Camera.right.{k1,k2,p1,p2} (system.cpp:118-138)"""
     f = lambda k: np.float32(float(cfg[k]))
     fx, fy, cx, cy, bf = f("Camera.right.fx"), f("Camera.right.fy"), f("Camera.right.cx"), f("Camera.right.cy"), f("Camera.bf")
-    return {"fx": float(fx), "fy": float(fy), "cx": float(cx), "cy": float(cy), "bf": float(bf), "baseline": float(np.float32(bf / fx))}
+    K = {"fx": float(fx), "fy": float(fy), "cx": float(cx), "cy": float(cy), "bf": float(bf), "baseline": float(np.float32(bf / fx))}
+    if int(float(cfg.get("Camera.bNeedUndistortion", 0))) != 0:
+        K["undistort"] = True
+        for side in ("left", "right"):
+            K["dist_" + side] = tuple(float(f(f"Camera.{side}.{n}")) for n in ("k1", "k2", "p1", "p2"))
+    return K
 
 
 # ---- the map's objects ------------------------------------------------------------------------------------------------------------
@@ -198,6 +204,19 @@ class HipBackend:
         self.lk = api.LKTracker()
         self.lcd = lcd if lcd is not None else api.DeepLCD(weights)
         self.db = api.LoopDatabase(64)                                # grows like the std::map
+        self.cfg = c
+        self.undist = [None, None]                                    # Camera::UndistortImage of the left / right camera, made on first use
+
+    def undistort(self, img, which):
+        """Camera::UndistortImage (camera.cpp:36-48) of camera `which` (0 = left, 1 = right) with the config's Camera.* keys; a new image"""
+        u = self.undist[which]
+        if u is None or (u.rows, u.cols) != img.shape:
+            K = camera_from_config(self.cfg)
+            if not K.get("undistort"):
+                raise ValueError("undistort() needs Camera.bNeedUndistortion = 1 and the Camera.{left,right}.{k1,k2,p1,p2} keys in the config")
+            u = self.undist[which] = self.api.Undistorter(img.shape[0], img.shape[1], (K["fx"], K["fy"], K["cx"], K["cy"]),
+                                                          K["dist_right" if which else "dist_left"])
+        return u.UndistortImage(np.ascontiguousarray(img, np.uint8))
 
     def detect(self, img, mask, init):
         return (self.det_init if init else self.orb).Detect(img, mask)
@@ -308,8 +327,11 @@ class Chain:
 
     # ---------------------------------------------------------------- Frontend
     def grab(self, t, ts=None):
-        """Frontend::GrabStereoImage (frontend.cpp:41-80); False = the tracker is LOST (the reference quits)"""
+        """Frontend::GrabStereoImage (frontend.cpp:41-80); False = the tracker is LOST (the reference quits).  With Camera.bNeedUndistortion the
+        two images are undistorted before anything else (:47-51) through the back end's undistort(img, which): only then is it called"""
         L, R = self.frame_images(t)
+        if self.K.get("undistort"):
+            L, R = self.be.undistort(L, 0), self.be.undistort(R, 1)
         self.cur = Frame(self.next_frame_id, float(ts if ts is not None else (self.ts[t] if self.ts is not None else t)), L, R)
         self.next_frame_id += 1
         if self.status == INITING:

@@ -13,6 +13,7 @@
 //   myslam::KeyFrameFeatures / MatchFeatures          KeyFrame::{mvPyramidKeyPoints, mORBDescriptors} + LoopClosing::ProcessNewKF /
 //                                                     MatchFeatures bookkeeping                   src/loopclosing.cpp:83-121, 163-203
 //   myslam::LoopLocalFusion                           arithmetic of LoopClosing::LoopLocalFusion  src/loopclosing.cpp:466-507
+//   myslam::Camera::UndistortImage                    cv::undistort of Frontend::GrabStereoImage  src/camera.cpp:36-48, frontend.cpp:47-51
 //
 // No OpenCV / Eigen / g2o: images are (data, rows, cols, step) views, cv::KeyPoint is the layout-compatible
 // myslam_keypoint, DescrVector is std::array<float,1064>.  Errors the reference reports by logging + return keep
@@ -360,6 +361,31 @@ public:
     }
     // asynchronous upload + pyramid of the image the next cached call will name by `token` (it must stay valid and unchanged until then)
     void Prefetch(const ImageView& img, uint64_t token) { check(myslam_lk_prefetch(h_, img.data, token, img.rows, img.cols, img.step), "myslam_lk_prefetch"); }
+};
+
+// Camera::UndistortImage (include/myslam/camera.h, src/camera.cpp:36-48): cv::undistort(src, dst, K, distCoef) for one camera at one image
+// size, as Frontend::GrabStereoImage calls it on both images when Camera.bNeedUndistortion is 1 (src/frontend.cpp:47-51).  K = fx fy cx cy,
+// D = k1 k2 p1 p2.  src and dst may be the same image (the reference's in-place call).
+class Camera {
+    myslam_undistort* h_ = nullptr;
+    int rows_ = 0, cols_ = 0;
+public:
+    Camera(int rows, int cols, const float K[4], const float D[4]) : rows_(rows), cols_(cols) {
+        check(myslam_undistort_create(&h_, rows, cols, K, D), "myslam_undistort_create");
+    }
+    ~Camera() { if (h_) myslam_undistort_destroy(h_); }
+    Camera(const Camera&) = delete; Camera& operator=(const Camera&) = delete;
+    int rows() const { return rows_; }
+    int cols() const { return cols_; }
+    void UndistortImage(const ImageView& src, ImageView& dst) {
+        if (src.rows != rows_ || src.cols != cols_ || dst.rows != rows_ || dst.cols != cols_) throw std::runtime_error("Camera::UndistortImage: image size");
+        check(myslam_undistort_image(h_, src.data, src.step, dst.data, dst.step), "myslam_undistort_image");
+    }
+    // OpenCV's CV_16SC2 / CV_16UC1 maps (rows x cols x 2 / rows x cols)
+    void GetMap(std::vector<int16_t>& xy, std::vector<uint16_t>& frac) const {
+        xy.resize((size_t)rows_ * cols_ * 2); frac.resize((size_t)rows_ * cols_);
+        check(myslam_undistort_get_map(h_, xy.data(), frac.data()), "myslam_undistort_get_map");
+    }
 };
 
 // the g2o stage of Frontend::EstimateCurrentPose (src/frontend.cpp:176-276); returns features.size() - cntOutliers.

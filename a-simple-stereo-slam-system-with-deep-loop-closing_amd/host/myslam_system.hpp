@@ -146,17 +146,28 @@ inline double se3_log_norm(const Mat4& T) {
 }
 
 // System::GetCamera (system.cpp:101-146): BOTH cameras take the Camera.right.* keys (reference quirk 8), every value passes through a
-// float, baseline = bf / fx in float
+// float, baseline = bf / fx in float.  Camera.bNeedUndistortion != 0 (system.cpp:34, an absent key reads 0): the left camera's distortion is
+// Camera.left.{k1,k2,p1,p2}, the right camera's Camera.right.{k1,k2,p1,p2} (system.cpp:118-138)
 struct StereoCamera {
     double fx = 0, fy = 0, cx = 0, cy = 0, bf = 0, baseline = 0;
+    bool needUndistortion = false;
+    float distLeft[4] = {0, 0, 0, 0}, distRight[4] = {0, 0, 0, 0};
     template <class Cfg>
     static StereoCamera FromConfig(const Cfg& cfg) {
         auto f = [&](const char* k) { return (float)cfg.template Get<double>(k); };
         const float fx = f("Camera.right.fx"), fy = f("Camera.right.fy"), cx = f("Camera.right.cx"), cy = f("Camera.right.cy"), bf = f("Camera.bf");
         StereoCamera c;
         c.fx = fx; c.fy = fy; c.cx = cx; c.cy = cy; c.bf = bf; c.baseline = (double)(float)(bf / fx);
+        c.needUndistortion = cfg.Has("Camera.bNeedUndistortion") && cfg.template Get<int>("Camera.bNeedUndistortion") != 0;
+        if (c.needUndistortion) {
+            const char* kl[4] = {"Camera.left.k1", "Camera.left.k2", "Camera.left.p1", "Camera.left.p2"};
+            const char* kr[4] = {"Camera.right.k1", "Camera.right.k2", "Camera.right.p1", "Camera.right.p2"};
+            for (int i = 0; i < 4; i++) { c.distLeft[i] = f(kl[i]); c.distRight[i] = f(kr[i]); }
+        }
         return c;
     }
+    // K of Camera::UndistortImage (camera.cpp:36-48): the float members fx_ fy_ cx_ cy_ — the Camera.right.* values for both cameras
+    void Intrinsics(float K[4]) const { K[0] = (float)fx; K[1] = (float)fy; K[2] = (float)cx; K[3] = (float)cy; }
 };
 
 // the reference's config/stereo/gray/KITTI00-02.yaml values; the YAML given on the command line overrides them
@@ -186,6 +197,7 @@ struct SystemConfig {
 struct Image {                              // cv::Mat CV_8UC1; shared_ptr<Image> copies share pixels as cv::Mat copies do
     std::vector<uint8_t> px; int rows = 0, cols = 0;
     uint64_t token = 0;                     // names these BYTES for the tracker's image cache (myslam_lk_track_cached): new token whenever px changes
+    bool undistorted = false;               // Camera::UndistortImage has run on px (a prefetched next left image is undistorted once, then reused)
     ImageView view() { return ImageView{px.data(), rows, cols, cols}; }
 };
 struct MapPoint; struct KeyFrame;
@@ -239,8 +251,14 @@ class StereoSystem {
     // nextLeft (optional): the left image of the FOLLOWING frame when the caller already has it — it is uploaded and down-sampled on the
     // tracker's stream while this frame's pose is optimised (the reference reads one pair per call, app/run_kitti_stereo.cpp:66-67; a reader
     // that decodes ahead can hand the next image over).  Results do not depend on it.
+    // With Camera.bNeedUndistortion the two images (and nextLeft) are undistorted IN PLACE before anything else (frontend.cpp:47-51); an image
+    // whose `undistorted` flag is set already (the nextLeft of the previous call) is not undistorted again.
     bool GrabStereoImage(std::shared_ptr<Image> left, std::shared_ptr<Image> right, double timestamp, std::shared_ptr<Image> nextLeft = nullptr) {
         const auto tg0 = std::chrono::steady_clock::now();
+        if (K_.needUndistortion) {
+            Undistort(left, 0); Undistort(right, 1);
+            if (nextLeft) Undistort(nextLeft, 0);
+        }
         if (left && !left->token) left->token = ++imageTokens_;
         if (nextLeft && !nextLeft->token) nextLeft->token = ++imageTokens_;
         nextLeft_ = std::move(nextLeft);
@@ -286,6 +304,20 @@ class StereoSystem {
 
    private:
     // ------------------------------------------------------------ cameras (camera.cpp:7-45; left extrinsics = identity, right = (-baseline, 0, 0))
+    // Camera::UndistortImage (camera.cpp:36-48) of camera `which` (0 = left, 1 = right), in place; one handle per camera and image size
+    void Undistort(const std::shared_ptr<Image>& im, int which) {
+        if (!im || im->undistorted) return;
+        auto& u = undist_[which];
+        if (!u || u->rows() != im->rows || u->cols() != im->cols) {
+            float K[4]; K_.Intrinsics(K);
+            u.reset(new Camera(im->rows, im->cols, K, which ? K_.distRight : K_.distLeft));
+        }
+        auto v = im->view();
+        u->UndistortImage(v, v);
+        im->undistorted = true;
+        im->token = 0;                               // new bytes: a token handed out before names the distorted ones
+    }
+
     void World2Pixel(const double pw[3], const Mat4& Tcw, bool right, double uv[2]) const {
         double pc[3];
         for (int i = 0; i < 3; i++) pc[i] = (Tcw.m[i][0] * pw[0] + Tcw.m[i][1] * pw[1] + Tcw.m[i][2] * pw[2]) + Tcw.m[i][3];
@@ -703,6 +735,7 @@ class StereoSystem {
     PyrLKTracker lk_;
     uint64_t imageTokens_ = 0;
     std::shared_ptr<Image> nextLeft_;
+    std::unique_ptr<Camera> undist_[2];              // Camera.bNeedUndistortion: the left / right camera's undistortion (created on first use)
     // The upload of the next frame's left image (myslam_lk_prefetch) copies 466 KB out of pageable memory before it returns: a helper thread
     // makes that call, so the tracking thread goes straight on to the pose optimisation.  One job in flight; Wait() before the next call on
     // the handle (it serves one thread at a time) — by then the job is long done.

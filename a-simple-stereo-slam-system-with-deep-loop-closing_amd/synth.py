@@ -528,6 +528,70 @@ def render_corridor_stereo(scene, c, yaw, t=0, **kw):
     return render_corridor_camera(scene, c, yaw, noise_seed=3000 + 2 * t, **kw), render_corridor_camera(scene, cr, yaw, noise_seed=3001 + 2 * t, **kw)
 
 
+# ---- the same corridor seen through a lens with radial-tangential distortion (Camera.bNeedUndistortion = 1 configs: EuRoC, a user's own rig)
+EUROC_LIKE_D = (-0.28, 0.07, 2e-4, 2e-5)          # k1 k2 p1 p2 of EuRoC's cam0 strength
+_DISTORTED_RAYS = {}
+
+
+def undistort_normalized(xd, yd, D, iters=30):
+    """the pinhole ray (x, y) whose image under D = (k1, k2, p1, p2) is the distorted normalised point (xd, yd): fixed-point iteration
+    x = (xd - tangential(x, y)) / radial(x, y), as cv::undistortPoints does"""
+    k1, k2, p1, p2 = (float(v) for v in D)
+    x, y = np.array(xd, float), np.array(yd, float)
+    for _ in range(iters):
+        r2 = x * x + y * y
+        kr = 1.0 + (k1 + k2 * r2) * r2
+        x, y = (xd - (2 * p1 * x * y + p2 * (r2 + 2 * x * x))) / kr, (yd - (p1 * (r2 + 2 * y * y) + 2 * p2 * x * y)) / kr
+    return x, y
+
+
+def render_corridor_camera_distorted(scene, c, yaw, D=EUROC_LIKE_D, h=IMG_H, w=IMG_W, K=KITTI00, noise_seed=None):
+    """render_corridor_camera through a lens with distortion D: pixel (u, v) shows the ray of the UNdistorted normalised point that D maps
+    onto ((u - cx) / fx, (v - cy) / fy).  cv::undistort with the same K and D gives back (up to resampling) the pinhole image."""
+    a, ch, wh, s = scene["a"], scene["cam_h"], scene["wall_h"], scene["s"]
+    key = (tuple(float(v) for v in D), h, w, K["fx"], K["fy"], K["cx"], K["cy"])
+    if key not in _DISTORTED_RAYS:                 # the same rays for every frame of a camera
+        _DISTORTED_RAYS[key] = undistort_normalized(((np.arange(w) - K["cx"]) / K["fx"])[None, :].repeat(h, 0),
+                                                    ((np.arange(h) - K["cy"]) / K["fy"])[:, None].repeat(w, 1), D)
+    xn, yn = _DISTORTED_RAYS[key]
+    dx = np.cos(yaw) * xn + np.sin(yaw); dz = -np.sin(yaw) * xn + np.cos(yaw)
+    dy = yn
+    big = 1e9
+    with np.errstate(divide="ignore", invalid="ignore"):
+        lam_l = np.where(dx < -1e-9, (-a - c[0]) / dx, big); lam_r = np.where(dx > 1e-9, (a - c[0]) / dx, big)
+        lam_g = np.where(dy > 1e-9, (ch - c[1]) / dy, big)
+    lam_w = np.minimum(lam_l, lam_r)
+    yw = c[1] + lam_w * dy
+    wall_ok = (lam_w < big) & (yw > -wh) & (yw <= ch + 1e-6) & (lam_w * dz > 0.3)
+    use_wall = wall_ok & (lam_w <= lam_g)
+    use_ground = ~use_wall & (lam_g < big) & (np.abs(c[0] + lam_g * dx) <= a + 1e-6) & (lam_g * dz > 0.3)
+    img = np.full((h, w), 150.0) - 25.0 * np.clip(yn + 0.6, 0, 1)
+    px = 1.0 / K["fx"]
+    for side, sel in ((0, use_wall & (lam_l <= lam_r)), (1, use_wall & (lam_r < lam_l))):
+        if sel.any():
+            lam = lam_w[sel]
+            z = c[2] + lam * dz[sel]; y = c[1] + lam * dy[sel]
+            rate = lam * px * s / np.maximum(np.abs(dx[sel]) / np.sqrt(dx[sel] ** 2 + dz[sel] ** 2), 0.05)
+            img[sel] = _sample_mips(scene["walls"][side], (z + 1000.0) * s, (y + wh) * s, rate)
+    if use_ground.any():
+        lam = lam_g[use_ground]
+        z = c[2] + lam * dz[use_ground]; x = c[0] + lam * dx[use_ground]
+        rate = lam * px * s / np.maximum(dy[use_ground] / np.sqrt(dy[use_ground] ** 2 + dz[use_ground] ** 2), 0.05)
+        img[use_ground] = _sample_mips(scene["ground"], (z + 1000.0) * s, (x + a) * s, rate)
+    if noise_seed is not None:
+        img = img + _rng(noise_seed).uniform(-1.5, 1.5, size=img.shape)
+    return np.ascontiguousarray(np.clip(np.rint(img), 0, 255).astype(np.uint8))
+
+
+def render_corridor_stereo_distorted(scene, c, yaw, t=0, D_left=EUROC_LIKE_D, D_right=EUROC_LIKE_D, **kw):
+    """render_corridor_stereo with a distorting lens on each camera"""
+    K = kw.get("K", KITTI00)
+    bl = K["bf"] / K["fx"]
+    cr = np.asarray(c, float) + bl * np.array([np.cos(yaw), 0.0, -np.sin(yaw)])
+    return (render_corridor_camera_distorted(scene, c, yaw, D_left, noise_seed=3000 + 2 * t, **kw),
+            render_corridor_camera_distorted(scene, cr, yaw, D_right, noise_seed=3001 + 2 * t, **kw))
+
+
 def corridor_poses(n=200, speed=0.9):
     """a drive along +z at `speed` metres per frame (eased start), a slow lateral sway of +-1.2 m and +-2.5 degrees of yaw"""
     z = speed * np.concatenate([[0.0], np.cumsum(np.minimum(1.0, (np.arange(n - 1) + 0.5) / 10.0))])

@@ -549,6 +549,30 @@ int myslam_lk_track_batch(myslam_lk* h, const uint8_t* d_prev, const uint8_t* d_
                           const float* d_prev_pts, float* d_next_pts, const int32_t* d_counts, int cap, uint8_t* d_status, float* d_err);
 
 /* ------------------------------------------------------------------------------------------
+ * Lens undistortion — replaces Camera::UndistortImage (src/camera.cpp:36-48), which Frontend::GrabStereoImage runs on the left and the
+ * right image before anything else when Camera.bNeedUndistortion is 1 (src/frontend.cpp:47-51): cv::undistort(src, dst, K, D) with
+ * K = (fx, fy, cx, cy) widened from the camera's float members and D = (k1, k2, p1, p2) (read in src/system.cpp:118-138).
+ * The handle holds the map of one camera at one image size: built at create time on the host in f64 the way OpenCV 3.4 builds it (stripes
+ * of min(max(1, 4096 / cols), rows) rows, initUndistortRectifyMap(..., CV_16SC2)), then bilinear remap in fixed point with border 0.
+ * Results are OpenCV's integers (tests/undistort_ref.py restates them; parity against OpenCV itself is unpinned, tests/test_opencv_pin_undistort.py).
+ * MYSLAM_ERR_UNSUPPORTED: the source band of a single 128-pixel tile row exceeds 64 KiB (a map far from the identity).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct myslam_undistort myslam_undistort;
+/* camera.cpp:36-48: K = fx fy cx cy, D = k1 k2 p1 p2 (float, as the reference holds them) */
+int myslam_undistort_create(myslam_undistort** out, int rows, int cols, const float* K, const float* D);
+int myslam_undistort_destroy(myslam_undistort* h);
+int myslam_undistort_set_stream(myslam_undistort* h, void* hip_stream);
+/* frontend.cpp:47-51, one image: host pointers (uploads, runs, downloads, synchronises); src == dst is allowed (the reference's in-place call) */
+int myslam_undistort_image(myslam_undistort* h, const uint8_t* src, int src_step, uint8_t* dst, int dst_step);
+/* frontend.cpp:47-51 for `batch` images (image b at base + b * stride): device pointers, asynchronous on the handle's stream, allocation-free
+ * (recordable between myslam_graph_begin / _end).  Source and destination may not overlap (MYSLAM_ERR_INVALID): the remap is a gather. */
+int myslam_undistort_batch(myslam_undistort* h, const uint8_t* d_src, int batch, int src_step, size_t src_stride, uint8_t* d_dst, int dst_step,
+                           size_t dst_stride);
+/* camera.cpp:36-48's two maps as OpenCV's initUndistortRectifyMap gives them, host function: xy = rows x cols x 2 int16 (CV_16SC2),
+ * frac = rows x cols uint16 (CV_16UC1: (v & 31) * 32 + (u & 31) in 1/32 px); either may be NULL */
+int myslam_undistort_get_map(const myslam_undistort* h, int16_t* xy, uint16_t* frac);
+
+/* ------------------------------------------------------------------------------------------
  * Loop correction — replaces the g2o part of LoopClosing::PoseGraphOptimization (src/loopclosing.cpp:537-610) and the map-point
  * write-back that follows it (:612-640).   [SURVEY.md §8(f) rank 3]
  * poses: n x 7 (qx qy qz qw tx ty tz) Tcw of every key-frame, in/out (VertexPose, :548-565); fixed[i] != 0 for the key-frames the

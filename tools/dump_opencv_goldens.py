@@ -8,7 +8,7 @@ neither OpenCV nor Caffe, so every OpenCV-derived definition of the oracle is "p
 Every fixture stores its INPUTS next to OpenCV's outputs (and cv2.__version__), so the comparison needs nothing but the file.
 Sections: resize (pyramid steps + the 160x120 CALC input), GaussianBlur (7x7 sigma 2 and sigma 0), FAST (score / NMS on cell-sized
 ROIs, thresholds 20 and 7), fastAtan2, BFMatcher(NORM_HAMMING), calcOpticalFlowPyrLK (the reference's parameters), solvePnPRansac
-(the reference's parameters) and, when `caffe` and calc_model/ are present, the CALC forward pass.
+(the reference's parameters), undistort (+ the maps of one stripe) and, when `caffe` and calc_model/ are present, the CALC forward pass.
 Where a section disagrees, the definitions that were chosen without a reference can be changed in one place on each side:
 Gaussian taps — orc_set_gauss_taps / myslam_orb_set_gauss_taps; everything else — oracle/*.cpp and the kernel named in DESIGN.md."""
 import os
@@ -97,7 +97,22 @@ def main():
     np.savez_compressed(os.path.join(OUT, "opencv_pnp.npz"), version=ver, pts3d=pw.astype(np.float32), pts2d=uv.astype(np.float32), K=np.array(K),
                         ok=np.array(bool(ok)), R=Rm, t=tvec.ravel(), inliers=(inl.ravel() if inl is not None else np.zeros(0, np.int32)))
 
-    # 8. the CALC net itself (deeplcd.cpp:55-91), when Caffe and the model files are at hand
+    # 8. cv::undistort as Camera::UndistortImage calls it (camera.cpp:36-48): float K, 4 float coefficients, for a mild and a strong lens —
+    #    the whole output plus initUndistortRectifyMap's CV_16SC2 / CV_16UC1 maps of ONE stripe as cv::undistort builds them (Ar(1,2) = cy - y0)
+    Kf = np.array([[718.856, 0, 607.1928], [0, 718.856, 185.2157], [0, 0, 1]], np.float32)
+    und = {}
+    for name, D in (("mild", (-0.05, 0.01, 1e-4, -5e-5)), ("strong", (-0.28, 0.07, 2e-4, 2e-5))):
+        Df = np.array(D, np.float32)
+        und[f"{name}_D"] = Df
+        und[f"{name}_out"] = cv2.undistort(L, Kf, Df)
+        y0 = 120 - 120 % max(1, 4096 // L.shape[1])            # a stripe start (stripes of min(max(1, 4096 / cols), rows) rows)
+        rows = min(max(1, 4096 // L.shape[1]), L.shape[0] - y0)
+        Ar = Kf.astype(np.float64); Ar[1, 2] = np.float64(Kf[1, 2]) - y0
+        m1, m2 = cv2.initUndistortRectifyMap(Kf.astype(np.float64), Df.astype(np.float64), np.eye(3), Ar, (L.shape[1], rows), cv2.CV_16SC2)
+        und[f"{name}_stripe_y0"] = np.array(y0); und[f"{name}_map_xy"] = m1; und[f"{name}_map_frac"] = m2
+    np.savez_compressed(os.path.join(OUT, "opencv_undistort.npz"), version=ver, src=L, K=Kf, **und)
+
+    # 9. the CALC net itself (deeplcd.cpp:55-91), when Caffe and the model files are at hand
     proto, model = "calc_model/deploy.prototxt", "calc_model/calc.caffemodel"
     try:
         import caffe
