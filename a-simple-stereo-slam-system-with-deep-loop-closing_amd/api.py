@@ -427,7 +427,35 @@ class DeepLCD:
         return out
 
 
-class LoopDatabase:
+class _LoopQueries:
+    """The query entry points of a loop database's built-in context (myslam_lcddb_*) and of a query context (myslam_lcddb_ctx_*)."""
+    _prefix = "myslam_lcddb_"
+
+    def _call(self, name, *args):
+        fn = self._prefix + name
+        _check(getattr(lib(), fn)(self._h, *args), fn)
+
+    def query_batch(self, d_q, cur_ids, nq, d_best, d_max, d_cnt, thr_low=0.92):
+        cur = np.ascontiguousarray(cur_ids, np.uint64)
+        self._call("query_batch", C.c_void_p(d_q), _p(cur), nq, C.c_float(thr_low), C.c_void_p(d_best), C.c_void_p(d_max), C.c_void_p(d_cnt))
+
+    def update_query_limits(self, cur_ids):
+        """new cur_ids (or appended rows) for a query that was recorded into a HIP graph (StepGraph); MyslamError(CAPACITY) = record again"""
+        cur = np.ascontiguousarray(cur_ids, np.uint64)
+        self._call("update_query_limits", _p(cur), len(cur))
+
+    def query_batch_sharded(self, d_q, cur_ids, nq, d_cand, thr_low=0.92):
+        """per-shard records (myslam_lcd_candidate, 16 bytes each, device memory) for the multi-GPU exchange"""
+        cur = np.ascontiguousarray(cur_ids, np.uint64)
+        self._call("query_batch_sharded", d_q, _p(cur), nq, thr_low, d_cand)
+
+    def query_batch_owned(self, d_q, cur_ids, nq, d_cand, thr_low=0.92):
+        """records of a shard whose ids interleave with the other shards' (myslam_lcd_owned_candidate, 32 bytes each, device memory)"""
+        cur = np.ascontiguousarray(cur_ids, np.uint64)
+        self._call("query_batch_owned", d_q, _p(cur), nq, thr_low, d_cand)
+
+
+class LoopDatabase(_LoopQueries):
     """LoopClosing::_mvDatabase + DetectLoop()/AddToDatabase() — loopclosing.cpp:124-161, 651-659."""
 
     def __init__(self, capacity, stream=None):
@@ -477,27 +505,6 @@ class LoopDatabase:
             return False, None
         return True, best
 
-    def query_batch(self, d_q, cur_ids, nq, d_best, d_max, d_cnt, thr_low=0.92):
-        cur = np.ascontiguousarray(cur_ids, np.uint64)
-        _check(lib().myslam_lcddb_query_batch(self._h, C.c_void_p(d_q), _p(cur), nq, C.c_float(thr_low), C.c_void_p(d_best),
-                                              C.c_void_p(d_max), C.c_void_p(d_cnt)), "myslam_lcddb_query_batch")
-
-
-    def update_query_limits(self, cur_ids):
-        """new cur_ids (or appended rows) for a query that was recorded into a HIP graph (StepGraph); MyslamError(CAPACITY) = record again"""
-        cur = np.ascontiguousarray(cur_ids, np.uint64)
-        _check(lib().myslam_lcddb_update_query_limits(self._h, _p(cur), len(cur)), "myslam_lcddb_update_query_limits")
-
-    def query_batch_sharded(self, d_q, cur_ids, nq, d_cand, thr_low=0.92):
-        """per-shard records (myslam_lcd_candidate, 16 bytes each, device memory) for the multi-GPU exchange"""
-        cur = np.ascontiguousarray(cur_ids, np.uint64)
-        _check(lib().myslam_lcddb_query_batch_sharded(self._h, d_q, _p(cur), nq, thr_low, d_cand), "myslam_lcddb_query_batch_sharded")
-
-    def query_batch_owned(self, d_q, cur_ids, nq, d_cand, thr_low=0.92):
-        """records of a shard whose ids interleave with the other shards' (myslam_lcd_owned_candidate, 32 bytes each, device memory)"""
-        cur = np.ascontiguousarray(cur_ids, np.uint64)
-        _check(lib().myslam_lcddb_query_batch_owned(self._h, d_q, _p(cur), nq, thr_low, d_cand), "myslam_lcddb_query_batch_owned")
-
     def generation(self):
         """number of times the descriptor matrix has moved (growth): recorded steps are valid for the generation they were recorded in"""
         return lib().myslam_lcddb_generation(self._h)
@@ -507,9 +514,10 @@ class LoopDatabase:
         return LoopQueryContext(self, stream)
 
 
-class LoopQueryContext:
+class LoopQueryContext(_LoopQueries):
     """myslam_lcddb_query_ctx: the per-stream half of a loop database (row-limit staging, partial results, recorded-step state).
     LoopClosing::_mvDatabase is one std::map per process (loopclosing.h:120): L streams of one GPU scan it through L contexts."""
+    _prefix = "myslam_lcddb_ctx_"
 
     def __init__(self, db, stream):
         self._db = db                       # keeps the database alive: contexts are destroyed before it
@@ -520,24 +528,6 @@ class LoopQueryContext:
         if getattr(self, "_h", None) and self._h.value and _lib is not None and getattr(self._db, "_h", None) and self._db._h.value:
             _lib.myslam_lcddb_query_ctx_destroy(self._h)
         self._h = C.c_void_p()
-
-    def query_batch(self, d_q, cur_ids, nq, d_best, d_max, d_cnt, thr_low=0.92):
-        cur = np.ascontiguousarray(cur_ids, np.uint64)
-        _check(lib().myslam_lcddb_ctx_query_batch(self._h, C.c_void_p(d_q), _p(cur), nq, C.c_float(thr_low), C.c_void_p(d_best),
-                                                  C.c_void_p(d_max), C.c_void_p(d_cnt)), "myslam_lcddb_ctx_query_batch")
-
-    def update_query_limits(self, cur_ids):
-        cur = np.ascontiguousarray(cur_ids, np.uint64)
-        _check(lib().myslam_lcddb_ctx_update_query_limits(self._h, _p(cur), len(cur)), "myslam_lcddb_ctx_update_query_limits")
-
-    def query_batch_sharded(self, d_q, cur_ids, nq, d_cand, thr_low=0.92):
-        cur = np.ascontiguousarray(cur_ids, np.uint64)
-        _check(lib().myslam_lcddb_ctx_query_batch_sharded(self._h, d_q, _p(cur), nq, thr_low, d_cand), "myslam_lcddb_ctx_query_batch_sharded")
-
-
-    def query_batch_owned(self, d_q, cur_ids, nq, d_cand, thr_low=0.92):
-        cur = np.ascontiguousarray(cur_ids, np.uint64)
-        _check(lib().myslam_lcddb_ctx_query_batch_owned(self._h, d_q, _p(cur), nq, thr_low, d_cand), "myslam_lcddb_ctx_query_batch_owned")
 
 
 class StepGraph:

@@ -60,7 +60,7 @@ void drop_events() {
     for (hipEvent_t e : t_events) (void)hipEventDestroy(e);
     t_events.clear();
 }
-// the capture that recorded these scans is over (ended, failed or abandoned): their contexts may synchronise their streams again
+// the capture that recorded these scans is over (ended or failed): their contexts may synchronise their streams again
 void close_deps(std::vector<StepDbDep>& deps) {
     for (StepDbDep& d : deps) d.link->captures_open.fetch_sub(1);
 }
@@ -79,13 +79,14 @@ int graph_note_db_link(const std::shared_ptr<DbGraphLink>& link, uint64_t genera
 
 extern "C" {
 
+// A recording ends only in myslam_graph_end, also when the step's calls failed in between: until then t_capturing refuses another begin on this
+// thread, and the contexts whose scans it recorded refuse to synchronise their streams (DbGraphLink::captures_open).
 int myslam_graph_begin(void* origin_stream, void* const* side_streams, int n_side) {
     if (!origin_stream || n_side < 0 || (n_side && !side_streams) || t_capturing) return MYSLAM_ERR_INVALID;
     if (prof_is_on()) return MYSLAM_ERR_UNSUPPORTED;                 // the profiling events are host-side bookkeeping: not replayable
     hipStream_t o = (hipStream_t)origin_stream;
     MYSLAM_HIP_CHECK(hipStreamBeginCapture(o, hipStreamCaptureModeThreadLocal));
     t_capturing = true;
-    close_deps(t_deps); t_deps.clear();                                // (a capture abandoned without myslam_graph_end on this thread)
     auto fork = [&]() -> int {
         hipEvent_t e;
         int rc = make_event(&e);

@@ -353,7 +353,7 @@ struct myslam_lcddb_query_ctx {
     bool builtin = false;
     Partial* d_partials = nullptr; size_t partialsCap = 0;
     int32_t* d_nvalid = nullptr; int nvalidCap = 0;                 // nq row limits + 1: the row count they were computed against
-    int32_t* h_nvalid = nullptr; hipEvent_t nvEvent = nullptr;      // pinned staging of the per-query row limits + "copy done" event
+    int32_t* h_nvalid = nullptr;                                    // pinned staging of the per-query row limits
     // round 6: eager uploads go through a RING of pinned slots behind slot 0 (slot 0 is what recorded scans read at their replays): a call whose limits changed — a
     // database that grows every step — used to wait for the previous call's upload to leave the one pinned buffer, i.e. for the stream to drain up to it; now it waits for
     // the upload three calls back, which has long gone
@@ -413,6 +413,12 @@ struct myslam_lcddb {
         if (cur >= 19) return first_in(cur - 19, cur);
         return std::min(first_in(0, cur), first_in(UINT64_MAX - (18 - cur), UINT64_MAX));
     }
+    // std::map order: new ids ascend strictly, behind every id held so far
+    bool ascending(const uint64_t* nids, int n) const {
+        for (int i = 0; i < n; i++)
+            if (i == 0 ? !ids.empty() && nids[0] <= ids.back() : nids[i] <= nids[i - 1]) return false;
+        return true;
+    }
 };
 
 static void ctx_free(myslam_lcddb_query_ctx* c) {
@@ -420,7 +426,6 @@ static void ctx_free(myslam_lcddb_query_ctx* c) {
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (c->h_nvalid) (void)hipHostFree(c->h_nvalid);
     if (c->h_own) (void)hipHostFree(c->h_own);
-    if (c->nvEvent) (void)hipEventDestroy(c->nvEvent);
     for (hipEvent_t e : c->nvRingEv) if (e) (void)hipEventDestroy(e);
     if (c->ownEvent) (void)hipEventDestroy(c->ownEvent);
     if (c->link) c->link->invalidate();       // recorded steps that captured this context can no longer be launched
@@ -438,15 +443,105 @@ static int ctx_quiesce(myslam_lcddb_query_ctx* c) {
     return MYSLAM_OK;
 }
 
-// The context's own scratch (pinned / device row limits, partial results, shard scratch) is about to be freed.  A recorded step names those buffers by
-// address and its matrix generation is unchanged: give the link a new scratch epoch so that myslam_graph_launch refuses the old step
-// (MYSLAM_ERR_CAPACITY: record it again) instead of replaying reads and writes of freed memory.  Called after ctx_quiesce (no replay in flight).
-static void ctx_scratch_moves(myslam_lcddb_query_ctx* c) {
-    if (c->graphRows > 0) {
+static bool stream_is_capturing(hipStream_t s) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return st == hipStreamCaptureStatusActive;
+}
+
+// partial results of one scan that reaches `rows` rows: one per block of the kernel a call with nq queries launches (launch_scan)
+static int scan_blocks(int nq, int rows) {
+    const int rowsPerBlock = DB_WAVES * DB_ROWS_PER_WAVE;
+    return std::max(1, nq >= 32 ? (rows + GM - 1) / GM : (rows + rowsPerBlock - 1) / rowsPerBlock);
+}
+
+// frees a piece of scratch (device memory, or pinned host memory) and allocates n elements in its place; null when the allocation failed
+template <class T> static int renew(T*& p, size_t n, bool pinned = false) {
+    if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
+    p = nullptr;
+    MYSLAM_HIP_CHECK(pinned ? hipHostMalloc((void**)&p, sizeof(T) * n) : hipMalloc((void**)&p, sizeof(T) * n));
+    return MYSLAM_OK;
+}
+
+enum QueryKind { Q_PLAIN, Q_SHARDED, Q_OWNED };
+
+// Every piece of the context's scratch that a call of `kind` with nq queries needs, the partial results sized for the whole allocation (a later
+// recording of the same call covers cap_rows rows and must find its scratch in place: nothing may be allocated inside a capture).  Whatever is too
+// small is replaced in one go: refused while the stream is capturing (first call of this shape: run it once outside the capture), else after
+// ctx_quiesce.  A recorded step names the row limits, the partial results and the shard scratch by address, with its matrix generation unchanged:
+// replacing any of them gives the link a new scratch epoch, so that myslam_graph_launch refuses the old step (MYSLAM_ERR_CAPACITY: record it again)
+// instead of replaying reads and writes of freed memory.  The owned-shard scratch is never recorded.  Caller holds h->mu (cap_rows = what its
+// launches cover).
+static int ctx_scratch(myslam_lcddb_query_ctx* c, QueryKind kind, int nq, int cap_rows, bool capturing) {
+    const size_t need = (size_t)scan_blocks(nq, cap_rows) * nq;
+    const bool lim = kind != Q_OWNED && nq > c->nvalidCap, part = need > c->partialsCap;
+    const bool shard = kind == Q_SHARDED && nq > c->shardCap, own = kind == Q_OWNED && nq > c->ownCap;
+    if (!lim && !part && !shard && !own) return MYSLAM_OK;
+    if (capturing) return MYSLAM_ERR_UNSUPPORTED;
+    const int rq = ctx_quiesce(c);
+    if (rq) return rq;
+    if ((lim || part || shard) && c->graphRows > 0) {
         c->link->scratch_epoch.fetch_add(1);
         c->graphRows = 0; c->graphQueries = 0;
     }
+    if (lim) {
+        c->nvalidCap = 0; c->nvFresh = false;
+        if (renew(c->d_nvalid, nq + 1) || renew(c->h_nvalid, (size_t)(nq + 1) * (1 + myslam_lcddb_query_ctx::NV_RING), true)) return MYSLAM_ERR_HIP;
+        for (int r = 0; r < myslam_lcddb_query_ctx::NV_RING; r++) {
+            if (!c->nvRingEv[r]) MYSLAM_HIP_CHECK(hipEventCreateWithFlags(&c->nvRingEv[r], hipEventDisableTiming));
+            c->nvRingPending[r] = false;                              // (ctx_quiesce above: nothing of the old buffer is in flight)
+        }
+        c->nvalidCap = nq;
+    }
+    if (part) {
+        c->partialsCap = 0;
+        if (renew(c->d_partials, need)) return MYSLAM_ERR_HIP;
+        c->partialsCap = need;
+    }
+    if (shard) {
+        c->shardCap = 0;
+        if (renew(c->d_bestS, nq) || renew(c->d_maxS, nq) || renew(c->d_cntS, nq)) return MYSLAM_ERR_HIP;
+        c->shardCap = nq;
+    }
+    if (own) {
+        c->ownCap = 0; c->ownPending = false;
+        if (renew(c->h_own, 4 * nq, true) || renew(c->d_own, 4 * nq) || renew(c->d_bestO, 2 * nq) || renew(c->d_maxO, 2 * nq) || renew(c->d_cntO, 2 * nq))
+            return MYSLAM_ERR_HIP;
+        if (!c->ownEvent) MYSLAM_HIP_CHECK(hipEventCreateWithFlags(&c->ownEvent, hipEventDisableTiming));
+        c->ownCap = nq;
+    }
+    return MYSLAM_OK;
 }
+
+// One scan on the context's stream into its partial results, then the per-query reduce: a query looks at rows [nstart, nvalid) (nstart null = 0), the
+// launch at the blocks that reach maxv rows.  Caller holds h->mu (d_db, d_ids, cap_rows) and checks hipGetLastError.
+static void launch_scan(const myslam_lcddb_query_ctx* c, const float* d_db, const uint64_t* d_ids, int cap_rows, const float* d_q, int nq,
+                        const int32_t* nvalid, const int32_t* nstart, int maxv, float thr_low, uint64_t* best, float* mx, int32_t* cnt) {
+    const int nparts = scan_blocks(nq, maxv);
+    if (nq >= 32) {           // batched: GEMM on the matrix cores with the per-query reduction fused into the epilogue
+        hipLaunchKernelGGL(k_db_scan_bf16x6, dim3(nparts, (nq + GN - 1) / GN), dim3(256), 0, c->stream, d_db, cap_rows, d_q, nq, nvalid, nstart, thr_low,
+                           c->d_partials);
+    } else {                  // a few queries: bandwidth-bound GEMV, one wave per database row
+        const size_t lds = sizeof(Partial) * DB_WAVES * nq + 2 * sizeof(int) * nq;
+        hipLaunchKernelGGL(k_db_scan, dim3(nparts), dim3(256), lds, c->stream, d_db, d_q, nq, nvalid, nstart, thr_low, c->d_partials);
+    }
+    hipLaunchKernelGGL(k_db_reduce, dim3((nq + 3) / 4), dim3(256), 0, c->stream, c->d_partials, nparts, nq, d_ids, best, mx, cnt);
+}
+
+// nothing in flight reads the matrix: every context's stream and every replay of a recorded step that scans through one (ctx_quiesce).  While a step
+// that scans through any of them is being recorded, refused before anything is synchronised.
+static int db_quiesce(myslam_lcddb* h) {
+    for (myslam_lcddb_query_ctx* c : h->ctxs)
+        if (c->link && c->link->captures_open.load() > 0) return MYSLAM_ERR_UNSUPPORTED;
+    for (myslam_lcddb_query_ctx* c : h->ctxs) {
+        const int rc = ctx_quiesce(c);
+        if (rc) return rc;
+    }
+    return MYSLAM_OK;
+}
+
+// the handle's own entry points scan through its built-in context
+static myslam_lcddb_query_ctx* builtin_ctx(myslam_lcddb* h) { return h ? h->ctxs[0] : nullptr; }
 
 static myslam_lcddb_query_ctx* ctx_new(myslam_lcddb* db, hipStream_t s, bool builtin) {
     myslam_lcddb_query_ctx* c = new myslam_lcddb_query_ctx();
@@ -502,8 +597,8 @@ int myslam_lcddb_destroy(myslam_lcddb* h) {
 int myslam_lcddb_set_stream(myslam_lcddb* h, void* s) {
     if (!h) return MYSLAM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipStreamSynchronize(h->stream);
-    (void)ctx_quiesce(h->ctxs[0]);
+    const int rc = ctx_quiesce(h->ctxs[0]);                               // the built-in context shares the handle's stream
+    if (rc) return rc;
     h->stream = (hipStream_t)s;
     h->ctxs[0]->stream = (hipStream_t)s;
     return MYSLAM_OK;
@@ -541,15 +636,10 @@ static int db_reserve(myslam_lcddb* h, long long rows) {
     if (rows <= h->capacity) return MYSLAM_OK;
     if (rows > (long long)INT32_MAX - rowsPerBlock) return MYSLAM_ERR_CAPACITY;
     const int cap = (int)((rows + rowsPerBlock - 1) / rowsPerBlock * rowsPerBlock);
-    for (myslam_lcddb_query_ctx* c : h->ctxs)                              // before anything synchronises: a recording in progress is not disturbed (see ctx_quiesce)
-        if (c->link && c->link->captures_open.load() > 0) return MYSLAM_ERR_UNSUPPORTED;
-    MYSLAM_HIP_CHECK(hipStreamSynchronize(h->stream));
+    const int rq = db_quiesce(h);
+    if (rq) return rq;
     bool recorded = false;
-    for (myslam_lcddb_query_ctx* c : h->ctxs) {                           // nothing in flight reads the old matrix: every context's stream and
-        const int rc = ctx_quiesce(c);                                    // every replay of a recorded step that scans through it
-        if (rc) return rc;
-        recorded = recorded || c->graphRows > 0;
-    }
+    for (const myslam_lcddb_query_ctx* c : h->ctxs) recorded = recorded || c->graphRows > 0;
     float* nd = nullptr; uint64_t* ni = nullptr;
     if (hipMalloc((void**)&nd, (size_t)cap * DIM * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return MYSLAM_ERR_CAPACITY; }
     if (hipMalloc((void**)&ni, (size_t)cap * sizeof(uint64_t)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(nd); return MYSLAM_ERR_CAPACITY; }
@@ -578,11 +668,9 @@ static int db_reserve(myslam_lcddb* h, long long rows) {
 static int db_append(myslam_lcddb* h, const uint64_t* ids, const float* src, int n, hipMemcpyKind kind) {
     if (!h || !ids || !src || n < 0) return MYSLAM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
-    for (int i = 0; i < n; i++) {
-        const uint64_t prev = (i == 0) ? (h->ids.empty() ? 0 : h->ids.back()) : ids[i - 1];
-        const bool first = (i == 0 && h->ids.empty());
-        if (!first && ids[i] <= prev) return MYSLAM_ERR_INVALID;          // std::map order: strictly ascending keys
-    }
+    if (!h->ascending(ids, n)) return MYSLAM_ERR_INVALID;
+    // the call waits for its copies on the handle's stream: while that stream is being recorded, the synchronisation would end the recording
+    if (stream_is_capturing(h->stream)) return MYSLAM_ERR_UNSUPPORTED;
     if ((long long)h->n + n > h->capacity) {                              // geometric growth: AddToDatabase never fails for lack of room
         const int rc = db_reserve(h, std::max<long long>((long long)h->n + n, 2LL * h->capacity));
         if (rc) return rc;
@@ -601,10 +689,7 @@ static int db_append(myslam_lcddb* h, const uint64_t* ids, const float* src, int
 static int db_append_async(myslam_lcddb* h, const uint64_t* ids, const float* d_src, int n, hipStream_t s) {
     if (!h || !ids || !d_src || n < 0) return MYSLAM_ERR_INVALID;
     std::lock_guard<std::mutex> lk(h->mu);
-    for (int i = 0; i < n; i++) {
-        const uint64_t prev = (i == 0) ? (h->ids.empty() ? 0 : h->ids.back()) : ids[i - 1];
-        if (!(i == 0 && h->ids.empty()) && ids[i] <= prev) return MYSLAM_ERR_INVALID;
-    }
+    if (!h->ascending(ids, n)) return MYSLAM_ERR_INVALID;
     if ((long long)h->n + n > h->capacity) return MYSLAM_ERR_CAPACITY;
     if (n == 0) return MYSLAM_OK;
     MYSLAM_HIP_CHECK(hipMemcpyAsync(h->d_db + (size_t)h->n * DIM, d_src, (size_t)n * DIM * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -647,72 +732,37 @@ int myslam_lcddb_append_batch(myslam_lcddb* h, const uint64_t* ids, const float*
 
 }  // extern "C"
 
-static bool stream_is_capturing(hipStream_t s) {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return st == hipStreamCaptureStatusActive;
-}
-
+// Plain (d_cand null: results into d_best / d_max / d_cnt) and sharded (d_cand: one record per query, through the context's shard scratch) scans.
+// Recorded into a HIP graph (graph.hip)?  Then nothing here may synchronise or allocate, the recorded kernels read the row limits from the pinned
+// buffer at EVERY replay (myslam_lcddb_ctx_update_query_limits rewrites it), and the launch covers every row of the ALLOCATION (not only the rows
+// today's limits reach), so that later limits and appends stay inside the captured grid.
 static int db_query(myslam_lcddb_query_ctx* c, const float* d_q, const uint64_t* cur_ids_host, int nq, float thr_low, uint64_t* d_best,
-                    float* d_max, int32_t* d_cnt) {
+                    float* d_max, int32_t* d_cnt, myslam_lcd_candidate* d_cand) {
+    if (!c || !d_q || !cur_ids_host || nq < 1 || nq > 65536 || (!d_cand && (!d_best || !d_max || !d_cnt))) return MYSLAM_ERR_INVALID;
     myslam_lcddb* h = c->db;
-    const int rowsPerBlock = DB_WAVES * DB_ROWS_PER_WAVE;
-    // Recorded into a HIP graph (graph.hip)?  Then nothing here may synchronise or allocate, the copy node of the row limits reads the
-    // pinned buffer at EVERY replay (myslam_lcddb_ctx_update_query_limits rewrites it), and the launch covers every row of the
-    // ALLOCATION (not only the rows today's limits reach), so that later limits and appends stay inside the captured grid.
     const bool cap = stream_is_capturing(c->stream);
-    if (nq > c->nvalidCap) {
-        if (cap) return MYSLAM_ERR_UNSUPPORTED;                          // first call with this many queries: run it once outside the capture
-        const int rq = ctx_quiesce(c);
-        if (rq) return rq;
-        ctx_scratch_moves(c);
-        if (c->d_nvalid) (void)hipFree(c->d_nvalid);
-        if (c->h_nvalid) (void)hipHostFree(c->h_nvalid);
-        c->d_nvalid = nullptr; c->h_nvalid = nullptr; c->nvalidCap = 0;
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&c->d_nvalid, sizeof(int32_t) * (nq + 1)));
-        MYSLAM_HIP_CHECK(hipHostMalloc((void**)&c->h_nvalid, sizeof(int32_t) * (nq + 1) * (1 + myslam_lcddb_query_ctx::NV_RING)));
-        if (!c->nvEvent) MYSLAM_HIP_CHECK(hipEventCreateWithFlags(&c->nvEvent, hipEventDisableTiming));
-        for (int r = 0; r < myslam_lcddb_query_ctx::NV_RING; r++) {
-            if (!c->nvRingEv[r]) MYSLAM_HIP_CHECK(hipEventCreateWithFlags(&c->nvRingEv[r], hipEventDisableTiming));
-            c->nvRingPending[r] = false;                              // (ctx_quiesce above: nothing of the old buffer is in flight)
-        }
-        c->nvalidCap = nq; c->nvFresh = false;
-    }
-    // the row limits of this call; when they equal what the device buffer already holds (the same cur_ids against the same rows, the
-    // usual case of a batch of queries per step) nothing is uploaded and the host never waits for the device
-    // h->mu is held from here until the scan and the reduce are ENQUEUED (round 6): the launches name the matrix by address, and an append from another
+    // h->mu is held from here until the launches are ENQUEUED (round 6): the launches name the matrix by address, and an append from another
     // thread may grow the database (db_reserve) — it takes the same mutex, then synchronises this context's stream, which now covers these launches;
     // released earlier, the old matrix could be freed between the pointer read and the launch
-    int maxv = 0, rows_now, cap_now; float* d_db; uint64_t* d_ids; uint64_t gen;
-    bool same;
     std::lock_guard<std::mutex> lk(h->mu);
-    {
-        rows_now = h->n; cap_now = h->capacity; d_db = h->d_db; d_ids = h->d_ids; gen = h->generation;
-        same = c->nvFresh && !cap && (int)c->lastLimits.size() == nq && c->lastRows == rows_now;
-        c->scratchLimits.resize(nq);
-        for (int i = 0; i < nq; i++) {
-            const int v = h->n_valid(cur_ids_host[i]);
-            c->scratchLimits[i] = v; maxv = std::max(maxv, v);
-            if (same && c->lastLimits[i] != v) same = false;
-        }
-    }
-    if (cap) maxv = cap_now;
-    const int nblocks = std::max(1, (maxv + rowsPerBlock - 1) / rowsPerBlock);
-    // partial results: sized for the whole allocation and this call's kernel (a later recording of the same query covers the allocation
-    // and must find its scratch in place: nothing may be allocated inside a capture)
-    const size_t need = (size_t)std::max(1, nq >= 32 ? (cap_now + GM - 1) / GM : (cap_now + rowsPerBlock - 1) / rowsPerBlock) * nq;
-    if (need > c->partialsCap) {
-        if (cap) return MYSLAM_ERR_UNSUPPORTED;
-        const int rq = ctx_quiesce(c);
-        if (rq) return rq;
-        ctx_scratch_moves(c);
-        if (c->d_partials) (void)hipFree(c->d_partials);
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&c->d_partials, need * sizeof(Partial)));
-        c->partialsCap = need;
+    const int rows_now = h->n, cap_now = h->capacity;
+    const int rs = ctx_scratch(c, d_cand ? Q_SHARDED : Q_PLAIN, nq, cap_now, cap);
+    if (rs) return rs;
+    if (d_cand) { d_best = c->d_bestS; d_max = c->d_maxS; d_cnt = c->d_cntS; }
+    // the row limits of this call; when they equal what the device buffer already holds (the same cur_ids against the same rows, the
+    // usual case of a batch of queries per step) nothing is uploaded and the host never waits for the device
+    int maxv = 0;
+    bool same = c->nvFresh && !cap && (int)c->lastLimits.size() == nq && c->lastRows == rows_now;
+    c->scratchLimits.resize(nq);
+    for (int i = 0; i < nq; i++) {
+        const int v = h->n_valid(cur_ids_host[i]);
+        c->scratchLimits[i] = v; maxv = std::max(maxv, v);
+        if (same && c->lastLimits[i] != v) same = false;
     }
     if (cap) {
-        c->graphRows = maxv; c->graphQueries = nq; c->graphGen = gen;
-        const int rn = graph_note_db_link(c->link, gen);                 // the step being recorded learns which matrix it reads (graph.hip)
+        maxv = cap_now;
+        c->graphRows = maxv; c->graphQueries = nq; c->graphGen = h->generation;
+        const int rn = graph_note_db_link(c->link, h->generation);       // the step being recorded learns which matrix it reads (graph.hip)
         if (rn) return rn;
     }
     if (!same) {
@@ -737,23 +787,17 @@ static int db_query(myslam_lcddb_query_ctx* c, const float* d_q, const uint64_t*
     c->limits = cap ? c->h_nvalid : c->d_nvalid;
     {
         ScopedProf sp(P_DBSCAN, c->stream);
-        int nparts = nblocks;
-        if (nq >= 32) {           // batched: GEMM on the matrix cores with the per-query reduction fused into the epilogue
-            nparts = std::max(1, (maxv + GM - 1) / GM);
-            hipLaunchKernelGGL(k_db_scan_bf16x6, dim3(nparts, (nq + GN - 1) / GN), dim3(256), 0, c->stream, d_db, cap_now, d_q, nq,
-                               c->limits, (const int32_t*)nullptr, thr_low, c->d_partials);
-        } else {                  // a few queries: bandwidth-bound GEMV, one wave per database row
-            const size_t lds = sizeof(Partial) * DB_WAVES * nq + 2 * sizeof(int) * nq;
-            hipLaunchKernelGGL(k_db_scan, dim3(nblocks), dim3(256), lds, c->stream, d_db, d_q, nq, c->limits, (const int32_t*)nullptr, thr_low, c->d_partials);
-        }
-        hipLaunchKernelGGL(k_db_reduce, dim3((nq + 3) / 4), dim3(256), 0, c->stream, c->d_partials, nparts, nq, d_ids, d_best,
-                           d_max, d_cnt);
+        launch_scan(c, h->d_db, h->d_ids, cap_now, d_q, nq, c->limits, nullptr, maxv, thr_low, d_best, d_max, d_cnt);
     }
+    if (d_cand)               // the row count sits behind the nq limits of THIS call (a recorded step's count is refreshed with its limits)
+        hipLaunchKernelGGL(k_db_pack_candidates, dim3((nq + 255) / 256), dim3(256), 0, c->stream, c->d_bestS, c->d_maxS, c->d_cntS, c->limits,
+                           c->limits + nq, nq, d_cand);
     MYSLAM_HIP_CHECK(hipGetLastError());
     return MYSLAM_OK;
 }
 
 static int db_update_limits(myslam_lcddb_query_ctx* c, const uint64_t* cur_ids, int nq) {
+    if (!c || !cur_ids || nq < 1) return MYSLAM_ERR_INVALID;
     myslam_lcddb* h = c->db;
     if (!c->graphRows || nq > c->graphQueries || nq > c->nvalidCap) return MYSLAM_ERR_INVALID;      // no recorded query to feed
     std::lock_guard<std::mutex> lk(h->mu);
@@ -767,53 +811,17 @@ static int db_update_limits(myslam_lcddb_query_ctx* c, const uint64_t* cur_ids, 
     return MYSLAM_OK;
 }
 
-static int db_query_sharded(myslam_lcddb_query_ctx* c, const float* d_q, const uint64_t* cur_ids, int nq, float thr_low, myslam_lcd_candidate* d_cand) {
-    if (nq > c->shardCap) {
-        if (stream_is_capturing(c->stream)) return MYSLAM_ERR_UNSUPPORTED;
-        const int rq = ctx_quiesce(c);
-        if (rq) return rq;
-        ctx_scratch_moves(c);
-        void* old[] = {c->d_bestS, c->d_maxS, c->d_cntS};
-        for (void* p : old) if (p) (void)hipFree(p);
-        c->d_bestS = nullptr; c->d_maxS = nullptr; c->d_cntS = nullptr; c->shardCap = 0;
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&c->d_bestS, sizeof(uint64_t) * nq));
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&c->d_maxS, sizeof(float) * nq));
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&c->d_cntS, sizeof(int32_t) * nq));
-        c->shardCap = nq;
-    }
-    int rc = db_query(c, d_q, cur_ids, nq, thr_low, c->d_bestS, c->d_maxS, c->d_cntS);
-    if (rc) return rc;
-    // the row count sits behind the nq limits of THIS call in d_nvalid (a recorded step's count is refreshed with its limits)
-    hipLaunchKernelGGL(k_db_pack_candidates, dim3((nq + 255) / 256), dim3(256), 0, c->stream, c->d_bestS, c->d_maxS, c->d_cntS, c->limits,
-                       c->limits + nq, nq, d_cand);
-    MYSLAM_HIP_CHECK(hipGetLastError());
-    return MYSLAM_OK;
-}
-
 // One shard of a database whose ids interleave across shards: both parts of the reference's scan + the break flag, 32 bytes per query.
 // Two scans of the same kernels (rows below the window; rows above cur — launched only when some query has such rows), not recordable into a step graph.
 static int db_query_owned(myslam_lcddb_query_ctx* c, const float* d_q, const uint64_t* cur_ids, int nq, float thr_low, myslam_lcd_owned_candidate* d_cand) {
-    myslam_lcddb* h = c->db;
+    if (!c || !d_q || !cur_ids || nq < 1 || nq > 65536 || !d_cand) return MYSLAM_ERR_INVALID;
     if (stream_is_capturing(c->stream)) return MYSLAM_ERR_UNSUPPORTED;
-    const int rowsPerBlock = DB_WAVES * DB_ROWS_PER_WAVE;
-    if (nq > c->ownCap) {
-        const int rq = ctx_quiesce(c);
-        if (rq) return rq;
-        void* old[] = {c->d_own, c->d_bestO, c->d_maxO, c->d_cntO};
-        for (void* p : old) if (p) (void)hipFree(p);
-        if (c->h_own) (void)hipHostFree(c->h_own);
-        c->d_own = nullptr; c->h_own = nullptr; c->d_bestO = nullptr; c->d_maxO = nullptr; c->d_cntO = nullptr; c->ownCap = 0; c->ownPending = false;
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&c->d_own, sizeof(int32_t) * 4 * nq));
-        MYSLAM_HIP_CHECK(hipHostMalloc((void**)&c->h_own, sizeof(int32_t) * 4 * nq));
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&c->d_bestO, sizeof(uint64_t) * 2 * nq));
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&c->d_maxO, sizeof(float) * 2 * nq));
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&c->d_cntO, sizeof(int32_t) * 2 * nq));
-        if (!c->ownEvent) MYSLAM_HIP_CHECK(hipEventCreateWithFlags(&c->ownEvent, hipEventDisableTiming));
-        c->ownCap = nq;
-    }
-    if (c->ownPending) MYSLAM_HIP_CHECK(hipEventSynchronize(c->ownEvent));          // the previous call's upload has left the pinned block
+    myslam_lcddb* h = c->db;
     std::lock_guard<std::mutex> lk(h->mu);                                          // held until everything is enqueued (see db_query)
     const int cap_now = h->capacity;
+    const int rs = ctx_scratch(c, Q_OWNED, nq, cap_now, false);
+    if (rs) return rs;
+    if (c->ownPending) MYSLAM_HIP_CHECK(hipEventSynchronize(c->ownEvent));          // the previous call's upload has left the pinned block
     int32_t* pLim = c->h_own; int32_t* sBeg = pLim + nq; int32_t* sLim = sBeg + nq; int32_t* brk = sLim + nq;
     int maxP = 0, maxS = 0; bool any_suffix = false;
     for (int i = 0; i < nq; i++) {
@@ -825,33 +833,12 @@ static int db_query_owned(myslam_lcddb_query_ctx* c, const float* d_q, const uin
     }
     MYSLAM_HIP_CHECK(hipMemcpyAsync(c->d_own, c->h_own, sizeof(int32_t) * 4 * nq, hipMemcpyHostToDevice, c->stream));
     MYSLAM_HIP_CHECK(hipEventRecord(c->ownEvent, c->stream)); c->ownPending = true;
-    const size_t need = (size_t)std::max(1, nq >= 32 ? (cap_now + GM - 1) / GM : (cap_now + rowsPerBlock - 1) / rowsPerBlock) * nq;
-    if (need > c->partialsCap) {
-        const int rq = ctx_quiesce(c);
-        if (rq) return rq;
-        ctx_scratch_moves(c);
-        if (c->d_partials) (void)hipFree(c->d_partials);
-        c->d_partials = nullptr; c->partialsCap = 0;
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&c->d_partials, need * sizeof(Partial)));
-        c->partialsCap = need;
-    }
     const int32_t* dP = c->d_own; const int32_t* dSb = dP + nq; const int32_t* dSl = dSb + nq; const int32_t* dBr = dSl + nq;
-    auto scan = [&](const int32_t* lim, const int32_t* beg, int maxv, uint64_t* best, float* mx, int32_t* cnt) {
-        int nparts;
-        if (nq >= 32) {
-            nparts = std::max(1, (maxv + GM - 1) / GM);
-            hipLaunchKernelGGL(k_db_scan_bf16x6, dim3(nparts, (nq + GN - 1) / GN), dim3(256), 0, c->stream, h->d_db, cap_now, d_q, nq, lim, beg, thr_low, c->d_partials);
-        } else {
-            nparts = std::max(1, (maxv + rowsPerBlock - 1) / rowsPerBlock);
-            const size_t lds = sizeof(Partial) * DB_WAVES * nq + 2 * sizeof(int) * nq;
-            hipLaunchKernelGGL(k_db_scan, dim3(nparts), dim3(256), lds, c->stream, h->d_db, d_q, nq, lim, beg, thr_low, c->d_partials);
-        }
-        hipLaunchKernelGGL(k_db_reduce, dim3((nq + 3) / 4), dim3(256), 0, c->stream, c->d_partials, nparts, nq, h->d_ids, best, mx, cnt);
-    };
     {
         ScopedProf sp(P_DBSCAN, c->stream);
-        scan(dP, nullptr, maxP, c->d_bestO, c->d_maxO, c->d_cntO);
-        if (any_suffix) scan(dSl, dSb, maxS, c->d_bestO + nq, c->d_maxO + nq, c->d_cntO + nq);       // (the partials are reused: same stream, in order)
+        launch_scan(c, h->d_db, h->d_ids, cap_now, d_q, nq, dP, nullptr, maxP, thr_low, c->d_bestO, c->d_maxO, c->d_cntO);
+        if (any_suffix)       // (the partials are reused: same stream, in order)
+            launch_scan(c, h->d_db, h->d_ids, cap_now, d_q, nq, dSl, dSb, maxS, thr_low, c->d_bestO + nq, c->d_maxO + nq, c->d_cntO + nq);
     }
     hipLaunchKernelGGL(k_db_pack_owned, dim3((nq + 255) / 256), dim3(256), 0, c->stream, c->d_bestO, c->d_maxO, c->d_cntO, c->d_bestO + nq, c->d_maxO + nq,
                        c->d_cntO + nq, dBr, any_suffix ? 1 : 0, nq, d_cand);
@@ -862,13 +849,11 @@ static int db_query_owned(myslam_lcddb_query_ctx* c, const float* d_q, const uin
 extern "C" {
 
 int myslam_lcddb_query_batch_owned(myslam_lcddb* h, const float* d_q, const uint64_t* cur_ids, int nq, float thr_low, myslam_lcd_owned_candidate* d_cand) {
-    if (!h || !d_q || !cur_ids || nq < 1 || nq > 65536 || !d_cand) return MYSLAM_ERR_INVALID;
-    return db_query_owned(h->ctxs[0], d_q, cur_ids, nq, thr_low, d_cand);
+    return db_query_owned(builtin_ctx(h), d_q, cur_ids, nq, thr_low, d_cand);
 }
 
 int myslam_lcddb_ctx_query_batch_owned(myslam_lcddb_query_ctx* c, const float* d_q, const uint64_t* cur_ids, int nq, float thr_low,
                                        myslam_lcd_owned_candidate* d_cand) {
-    if (!c || !d_q || !cur_ids || nq < 1 || nq > 65536 || !d_cand) return MYSLAM_ERR_INVALID;
     return db_query_owned(c, d_q, cur_ids, nq, thr_low, d_cand);
 }
 
@@ -888,36 +873,26 @@ int myslam_lcd_merge_owned_candidates_device(const myslam_lcd_owned_candidate* d
 
 int myslam_lcddb_query_batch(myslam_lcddb* h, const float* d_q, const uint64_t* cur_ids, int nq, float thr_low,
                              uint64_t* d_best_id, float* d_max_score, int32_t* d_cnt) {
-    if (!h || !d_q || !cur_ids || nq < 1 || nq > 65536 || !d_best_id || !d_max_score || !d_cnt) return MYSLAM_ERR_INVALID;
-    return db_query(h->ctxs[0], d_q, cur_ids, nq, thr_low, d_best_id, d_max_score, d_cnt);
+    return db_query(builtin_ctx(h), d_q, cur_ids, nq, thr_low, d_best_id, d_max_score, d_cnt, nullptr);
 }
 
 int myslam_lcddb_ctx_query_batch(myslam_lcddb_query_ctx* c, const float* d_q, const uint64_t* cur_ids, int nq, float thr_low,
                                  uint64_t* d_best_id, float* d_max_score, int32_t* d_cnt) {
-    if (!c || !d_q || !cur_ids || nq < 1 || nq > 65536 || !d_best_id || !d_max_score || !d_cnt) return MYSLAM_ERR_INVALID;
-    return db_query(c, d_q, cur_ids, nq, thr_low, d_best_id, d_max_score, d_cnt);
+    return db_query(c, d_q, cur_ids, nq, thr_low, d_best_id, d_max_score, d_cnt, nullptr);
 }
 
-int myslam_lcddb_update_query_limits(myslam_lcddb* h, const uint64_t* cur_ids, int nq) {
-    if (!h || !cur_ids || nq < 1) return MYSLAM_ERR_INVALID;
-    return db_update_limits(h->ctxs[0], cur_ids, nq);
-}
+int myslam_lcddb_update_query_limits(myslam_lcddb* h, const uint64_t* cur_ids, int nq) { return db_update_limits(builtin_ctx(h), cur_ids, nq); }
 
-int myslam_lcddb_ctx_update_query_limits(myslam_lcddb_query_ctx* c, const uint64_t* cur_ids, int nq) {
-    if (!c || !cur_ids || nq < 1) return MYSLAM_ERR_INVALID;
-    return db_update_limits(c, cur_ids, nq);
-}
+int myslam_lcddb_ctx_update_query_limits(myslam_lcddb_query_ctx* c, const uint64_t* cur_ids, int nq) { return db_update_limits(c, cur_ids, nq); }
 
 int myslam_lcddb_query_batch_sharded(myslam_lcddb* h, const float* d_q, const uint64_t* cur_ids, int nq, float thr_low,
                                      myslam_lcd_candidate* d_cand) {
-    if (!h || !d_q || !cur_ids || nq < 1 || nq > 65536 || !d_cand) return MYSLAM_ERR_INVALID;
-    return db_query_sharded(h->ctxs[0], d_q, cur_ids, nq, thr_low, d_cand);
+    return db_query(builtin_ctx(h), d_q, cur_ids, nq, thr_low, nullptr, nullptr, nullptr, d_cand);
 }
 
 int myslam_lcddb_ctx_query_batch_sharded(myslam_lcddb_query_ctx* c, const float* d_q, const uint64_t* cur_ids, int nq, float thr_low,
                                          myslam_lcd_candidate* d_cand) {
-    if (!c || !d_q || !cur_ids || nq < 1 || nq > 65536 || !d_cand) return MYSLAM_ERR_INVALID;
-    return db_query_sharded(c, d_q, cur_ids, nq, thr_low, d_cand);
+    return db_query(c, d_q, cur_ids, nq, thr_low, nullptr, nullptr, nullptr, d_cand);
 }
 
 int myslam_lcd_merge_candidates(const myslam_lcd_candidate* gathered, int nshards, int nq, uint64_t* best_id, float* max_score, int32_t* cnt) {
@@ -939,7 +914,7 @@ int myslam_lcddb_query(myslam_lcddb* h, const float* descr, uint64_t cur_id, flo
                        int* cnt) {
     if (!h || !descr || !best_id || !max_score || !cnt) return MYSLAM_ERR_INVALID;
     MYSLAM_HIP_CHECK(hipMemcpyAsync(h->d_q1, descr, DIM * sizeof(float), hipMemcpyHostToDevice, h->stream));
-    int rc = db_query(h->ctxs[0], h->d_q1, &cur_id, 1, thr_low, h->d_best1, h->d_max1, h->d_cnt1);
+    int rc = db_query(h->ctxs[0], h->d_q1, &cur_id, 1, thr_low, h->d_best1, h->d_max1, h->d_cnt1, nullptr);
     if (rc) return rc;
     int32_t c = 0;
     MYSLAM_HIP_CHECK(hipMemcpyAsync(best_id, h->d_best1, 8, hipMemcpyDeviceToHost, h->stream));

@@ -339,7 +339,8 @@ int myslam_lcddb_update_query_limits(myslam_lcddb* h, const uint64_t* cur_ids /*
  *     (MYSLAM_ERR_CAPACITY: record it again) — round 6;
  *   - while a step that scans through a context is being RECORDED (myslam_graph_begin .. _end, on any thread), nothing may synchronise that
  *     context's stream: an append / reserve that would have to move the matrix, and myslam_lcddb_set_stream, return MYSLAM_ERR_UNSUPPORTED until
- *     the recording has ended (appends inside the allocation are unaffected) — round 6;
+ *     the recording has ended.  Appends inside the allocation are unaffected, except that myslam_lcddb_append / _append_batch wait for their
+ *     copies on the handle's stream: while THAT stream is being captured they return MYSLAM_ERR_UNSUPPORTED before they enqueue anything — round 6;
  *   - a query holds the database's host lock until its launches are enqueued, so a growing append from another thread waits for them (its stream
  *     synchronisation then covers the scan) instead of freeing the matrix under a launch that is about to be issued — round 6;
  *   - contexts are destroyed before their database (myslam_lcddb_destroy frees any that are left: their pointers die with it).
@@ -647,7 +648,7 @@ int myslam_io_save_loop_edges(const char* path, const uint64_t* cur_ids, const d
  * Every *_batch entry point is asynchronous and allocation-free after its first call with a given shape, so a caller records one step
  * between begin and end — the calls it would make anyway, on the streams it would use — and replays it with one launch per step.
  *   begin: starts a thread-local capture on origin_stream and forks the side streams into it (they must be distinct from the origin);
- *   end:   joins the side streams back, ends the capture and instantiates the graph.
+ *   end:   joins the side streams back, ends the capture and instantiates the graph; a recording whose calls failed must still be ended with it.
  * Rules: run the step once eagerly first (lazy allocations); profiling must be off (MYSLAM_ERR_UNSUPPORTED); events passed to
  * myslam_orb_set_fast_gate must be recorded INSIDE the capture (the first handle of a ring takes no gate); buffers, handles, options and
  * streams the step uses must stay as they were; host code is not replayed — record TWO consecutive steps and replay them alternately so

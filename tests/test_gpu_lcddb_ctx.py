@@ -259,6 +259,94 @@ def test_growth_is_refused_while_a_step_is_being_recorded(api, synth):
         g.launch(st.cuda_stream)
 
 
+def _bufs(nq):
+    import torch
+    return (torch.zeros(nq, dtype=torch.int64, device="cuda"), torch.zeros(nq, device="cuda"), torch.zeros(nq, dtype=torch.int32, device="cuda"))
+
+
+def test_set_stream_is_refused_while_a_step_is_being_recorded(api, oracle, synth):
+    """myslam_lcddb_set_stream waits for the handle's stream before it swaps it.  While a step that scans through the built-in context is being recorded
+    on that stream, it returns MYSLAM_ERR_UNSUPPORTED and touches nothing: the recording ends normally, its replay equals the eager scan, and the
+    database's scans still go to its own stream (the one issued behind the refused call is part of the recording)."""
+    import torch
+    n0, nq = 300, 2
+    db = synth.lcd_database(n0, seed=43); ids = np.arange(n0, dtype=np.uint64)
+    t_db = torch.from_numpy(db).cuda()
+    st, other = torch.cuda.Stream(), torch.cuda.Stream()
+    D = api.LoopDatabase(n0 + 32, stream=st.cuda_stream)
+    D.append_batch(ids, t_db.data_ptr(), n0)
+    qs = db[[7, 250]].copy(); d_q = torch.from_numpy(qs).cuda()
+    cur = np.full(nq, n0 + 20, np.uint64)
+    o1, o2 = _bufs(nq), _bufs(nq)
+    seen = {}
+
+    def body():
+        D.query_batch(d_q.data_ptr(), cur, nq, *[t.data_ptr() for t in o1])
+        seen["rc"] = api.lib().myslam_lcddb_set_stream(D._h, other.cuda_stream)
+        D.query_batch(d_q.data_ptr(), cur, nq, *[t.data_ptr() for t in o2])
+    torch.cuda.synchronize()
+    D.query_batch(d_q.data_ptr(), cur, nq, *[t.data_ptr() for t in o1]); torch.cuda.synchronize()
+    eager = [t.cpu().numpy() for t in o1]
+    _check(oracle, db, ids, n0, qs, cur, *eager, tag="eager")
+    g = api.StepGraph.record(st.cuda_stream, [], body)
+    assert seen["rc"] == -4, seen                                  # MYSLAM_ERR_UNSUPPORTED
+    for t in o1 + o2:
+        t.zero_()
+    torch.cuda.synchronize()
+    g.launch(st.cuda_stream); torch.cuda.synchronize()
+    for o in (o1, o2):
+        assert all(np.array_equal(a, t.cpu().numpy()) for a, t in zip(eager, o)), "replay differs from the eager scan"
+    for t in o2:
+        t.zero_()
+    torch.cuda.synchronize()
+    D.query_batch(d_q.data_ptr(), cur, nq, *[t.data_ptr() for t in o2]); st.synchronize()
+    assert all(np.array_equal(a, t.cpu().numpy()) for a, t in zip(eager, o2)), "eager scan after the refused set_stream"
+
+
+def test_synchronous_append_is_refused_while_its_stream_is_being_recorded(api, oracle, synth):
+    """myslam_lcddb_append_batch waits for its copies on the handle's stream.  When that stream is the one being recorded, an append that fits the
+    allocation returns MYSLAM_ERR_UNSUPPORTED before it enqueues anything: the step still records and replays, and after the recording the same
+    append goes through and the replay (with new limits) sees its rows."""
+    import torch
+    n0, k, nq = 300, 8, 2
+    db = synth.lcd_database(n0 + k, seed=47); ids = np.arange(n0 + k, dtype=np.uint64)
+    t_db = torch.from_numpy(db).cuda()
+    st = torch.cuda.Stream()
+    D = api.LoopDatabase(n0 + 32, stream=st.cuda_stream)
+    D.append_batch(ids[:n0], t_db.data_ptr(), n0)
+    qs = db[[7, n0 + 3]].copy(); d_q = torch.from_numpy(qs).cuda()    # the second query is a row of the refused append
+    cur = np.full(nq, n0 + k + 20, np.uint64)
+    o = _bufs(nq)
+    seen = {}
+
+    def body():
+        D.query_batch(d_q.data_ptr(), cur, nq, *[t.data_ptr() for t in o])
+        try:
+            D.append_batch(ids[n0:], t_db.data_ptr() + n0 * 1064 * 4, k)
+            seen["code"] = 0
+        except api.MyslamError as e:
+            seen["code"] = e.code
+    torch.cuda.synchronize()
+    D.query_batch(d_q.data_ptr(), cur, nq, *[t.data_ptr() for t in o]); torch.cuda.synchronize()
+    eager = [t.cpu().numpy() for t in o]
+    _check(oracle, db, ids, n0, qs, cur, *eager, tag="eager")
+    g = api.StepGraph.record(st.cuda_stream, [], body)
+    assert seen["code"] == -4, seen                                # MYSLAM_ERR_UNSUPPORTED
+    assert len(D) == n0 and D.generation() == 0
+    for t in o:
+        t.zero_()
+    torch.cuda.synchronize()
+    g.launch(st.cuda_stream); torch.cuda.synchronize()
+    assert all(np.array_equal(a, t.cpu().numpy()) for a, t in zip(eager, o)), "replay differs from the eager scan"
+    D.append_batch(ids[n0:], t_db.data_ptr() + n0 * 1064 * 4, k)  # recording closed: the same append goes through
+    assert len(D) == n0 + k and D.generation() == 0
+    D.update_query_limits(cur)
+    g.launch(st.cuda_stream); torch.cuda.synchronize()
+    got = [t.cpu().numpy() for t in o]
+    _check(oracle, db, ids, n0 + k, qs, cur, *got, tag="replay after the append")
+    assert int(got[0][1]) == n0 + 3
+
+
 def test_asynchronous_appends_inside_a_stream_of_scans(api, oracle, synth):
     """myslam_lcddb_append_batch_async (round 6): AddToDatabase inside a pipelined step — the rows are copied on the caller's stream, the call does not wait, and scans issued
     afterwards ON THAT STREAM see them (their row limits are computed from the ids, which are updated at once).  60 rounds of scan + append with no host synchronisation in between,
