@@ -747,6 +747,87 @@ class LKTracker:
                                            C.c_void_p(d_status), C.c_void_p(d_err or None)), "myslam_lk_track_batch")
 
 
+# ---------------------------------------------------------------------------------- multi-stream tracker
+TRACKER_RESULT_DTYPE = np.dtype([("pose7", "<f8", (7,)), ("n_inliers", "<i4"), ("n_features", "<i4"), ("status", "<i4"), ("frame_id", "<i4"),
+                                 ("needs_host", "<i4"), ("reserved", "<i4")])      # myslam_tracker_result
+assert TRACKER_RESULT_DTYPE.itemsize == 80
+
+
+class Tracker:
+    """Frontend::Track() (src/frontend.cpp:86-122) for `streams` independent cameras of one image size and calibration, one frame per
+    step_batch() with all tracker state on the device (myslam_tracker_*).  K = (fx, fy, cx, cy).  A stream's state travels as a dict:
+    xy (n, 2) f32, lm (n,) i32 slots of the landmark table or -1, lm_pos (L, 3) f64, lm_outlier (L,) u8, ref_pose (7,), ref_frame_id,
+    last_rel / rel_motion (4, 4), next_frame_id, status, kf_every; get_frame() adds frozen and outlier_list (landmark slots)."""
+
+    def __init__(self, streams, rows, cols, cap, landmark_cap, K, tracking_good=50, tracking_bad=10, win=11, max_level=3, max_iters=30, eps=0.01,
+                 min_eig=1e-4, stream=None):
+        self.streams, self.rows, self.cols, self.cap, self.landmark_cap = int(streams), int(rows), int(cols), int(cap), int(landmark_cap)
+        self._h = C.c_void_p()
+        _check(lib().myslam_tracker_create(C.byref(self._h), self.streams, self.rows, self.cols, self.cap, self.landmark_cap, C.c_double(K[0]),
+                                           C.c_double(K[1]), C.c_double(K[2]), C.c_double(K[3]), int(tracking_good), int(tracking_bad), int(win),
+                                           int(max_level), int(max_iters), C.c_float(eps), C.c_float(min_eig)), "myslam_tracker_create")
+        if stream is not None:
+            self.set_stream(stream)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and self._h.value and _lib is not None:
+            lib().myslam_tracker_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def set_stream(self, stream):
+        _check(lib().myslam_tracker_set_stream(self._h, C.c_void_p(stream)), "myslam_tracker_set_stream")
+
+    def launches_per_step(self):
+        return lib().myslam_tracker_launches_per_step(self._h)
+
+    def set_frame(self, s, state, image=None):
+        """key-frame hand-off (host arrays, synchronous): uploads the state, unfreezes the stream; image replaces the stored previous image"""
+        xy = np.ascontiguousarray(state["xy"], np.float32).reshape(-1, 2); lm = np.ascontiguousarray(state["lm"], np.int32).reshape(-1)
+        pos = np.ascontiguousarray(state["lm_pos"], np.float64).reshape(-1, 3); out = np.ascontiguousarray(state["lm_outlier"], np.uint8).reshape(-1)
+        if len(xy) != len(lm) or len(pos) != len(out):
+            raise ValueError("feature / landmark arrays of different lengths")
+        ref = np.ascontiguousarray(state["ref_pose"], np.float64).reshape(7)
+        rel = np.ascontiguousarray(state["last_rel"], np.float64).reshape(16); mot = np.ascontiguousarray(state["rel_motion"], np.float64).reshape(16)
+        img, step = None, 0
+        if image is not None:
+            img = np.ascontiguousarray(image, np.uint8)
+            if img.shape != (self.rows, self.cols):
+                raise ValueError(f"expected a {self.rows} x {self.cols} image")
+            step = img.strides[0]
+        _check(lib().myslam_tracker_set_frame(self._h, int(s), _p(xy), _p(lm), len(xy), _p(pos), _p(out), len(pos), _p(ref), int(state["ref_frame_id"]),
+                                              _p(rel), _p(mot), int(state["next_frame_id"]), int(state["status"]), int(state.get("kf_every", 0)),
+                                              _p(img), step), "myslam_tracker_set_frame")
+
+    def get_frame(self, s, image=False):
+        xy = np.zeros((self.cap, 2), np.float32); lm = np.zeros(self.cap, np.int32)
+        pos = np.zeros((self.landmark_cap, 3), np.float64); out = np.zeros(self.landmark_cap, np.uint8)
+        ref = np.zeros(7); rel = np.zeros((4, 4)); mot = np.zeros((4, 4)); lst = np.zeros(2 * self.cap, np.int32)
+        iv = [C.c_int() for _ in range(8)]          # n_feat n_landmarks ref_frame_id next_frame_id status kf_every frozen n_outlier
+        img = np.zeros((self.rows, self.cols), np.uint8) if image else None
+        _check(lib().myslam_tracker_get_frame(self._h, int(s), _p(xy), _p(lm), C.byref(iv[0]), _p(pos), _p(out), C.byref(iv[1]), _p(ref), C.byref(iv[2]),
+                                              _p(rel), _p(mot), C.byref(iv[3]), C.byref(iv[4]), C.byref(iv[5]), C.byref(iv[6]), _p(lst), C.byref(iv[7]),
+                                              _p(img), self.cols if image else 0), "myslam_tracker_get_frame")
+        n, L = iv[0].value, iv[1].value
+        st = {"xy": xy[:n].copy(), "lm": lm[:n].copy(), "lm_pos": pos[:L].copy(), "lm_outlier": out[:L].copy(), "ref_pose": ref,
+              "ref_frame_id": iv[2].value, "last_rel": rel, "rel_motion": mot, "next_frame_id": iv[3].value, "status": iv[4].value,
+              "kf_every": iv[5].value, "frozen": iv[6].value, "outlier_list": lst[:iv[7].value].copy()}
+        if image:
+            st["image"] = img
+        return st
+
+    def step_batch(self, d_left, step, stride, d_results):
+        """device pointers, asynchronous on the handle's stream: image s at d_left + s * stride; d_results: `streams` TRACKER_RESULT_DTYPE records"""
+        _check(lib().myslam_tracker_step_batch(self._h, C.c_void_p(d_left), int(step), C.c_size_t(stride), C.c_void_p(d_results)),
+               "myslam_tracker_step_batch")
+
+    def debug_last_step(self, s):
+        """(p0, p1, tracked, LK status) of stream s in the last step; empty when it was frozen"""
+        p0 = np.zeros((self.cap, 2), np.float32); p1 = np.zeros((self.cap, 2), np.float32); nx = np.zeros((self.cap, 2), np.float32)
+        st = np.zeros(self.cap, np.uint8); n = C.c_int()
+        _check(lib().myslam_tracker_debug_last_step(self._h, int(s), _p(p0), _p(p1), _p(nx), _p(st), C.byref(n)), "myslam_tracker_debug_last_step")
+        return p0[:n.value], p1[:n.value], nx[:n.value], st[:n.value].astype(bool)
+
+
 # ---------------------------------------------------------------------------------- lens undistortion
 class Undistorter:
     """Camera::UndistortImage (src/camera.cpp:36-48) = cv::undistort(src, dst, K, D) for one camera at one image size, as

@@ -37,6 +37,7 @@ UNITS = {
     "prof.hip": [],
     "io.hip": [],
     "graph.hip": [],
+    "tracker.hip": EXACT,                  # the LK start points are the hosts' f64 arithmetic, operation by operation
     "undistort.hip": EXACT,                # the host-built map restates OpenCV's f64 arithmetic product by product
 }
 

@@ -763,3 +763,129 @@ class Chain:
         self.api.save_loop_edges(os.path.join(out_dir, "loopEdges.txt"), np.array([k.id for k in lp], np.uint64), np.array([k.ts for k in lp]),
                                  np.stack([k.pose for k in lp]) if lp else z7, np.array([k.loop_kf.id for k in lp], np.uint64),
                                  np.array([k.loop_kf.ts for k in lp]), np.stack([k.loop_kf.pose for k in lp]) if lp else z7)
+
+
+# ---- S cameras, one tracker step per frame for all of them --------------------------------------------------------------------------
+class StreamBank:
+    """S independent Chain objects advanced one frame per advance(t): the per-frame work (Chain.track() up to the key-frame branch,
+    frontend.cpp:86-122) runs for ALL streams in one asynchronous api.Tracker.step_batch with the tracker state on the device, ONE download
+    brings the S result records back, and only a stream whose record says needs_host (key-frame by the reference's rule or kf_every, or
+    LOST) takes the existing Chain methods (detect_features ... insert_keyframe, back end, loop closer) between get_frame and set_frame.
+    Stereo initialisation stays on Chain.grab().  Device buffers are torch tensors (plumbing only).  Chain itself is the one-camera form."""
+
+    def __init__(self, chains, api, cap=1024, landmark_cap=4096, tracker=None):
+        import torch
+        self.torch, self.api, self.chains = torch, api, list(chains)
+        c0 = self.chains[0]
+        if any(c.K.get("undistort") for c in self.chains):
+            raise ValueError("StreamBank takes undistorted images (Camera.bNeedUndistortion = 0)")
+        if any((c.Kt, c.n_good, c.n_bad) != (c0.Kt, c0.n_good, c0.n_bad) for c in self.chains):
+            raise ValueError("the streams of one bank share the camera and numFeatures.trackingGood / trackingBad")
+        L, _ = c0.frame_images(0)
+        self.rows, self.cols = L.shape
+        self.trk = tracker if tracker is not None else api.Tracker(len(self.chains), self.rows, self.cols, cap, landmark_cap, c0.Kt, c0.n_good, c0.n_bad)
+        self.slots = [[] for _ in self.chains]                        # per stream: MapPoint by landmark slot (as handed over last)
+        self.d_img = torch.zeros((len(self.chains), self.rows, self.cols), dtype=torch.uint8, device="cuda")
+        self.d_res = torch.zeros(len(self.chains) * api.TRACKER_RESULT_DTYPE.itemsize, dtype=torch.uint8, device="cuda")
+        self.on_device = [False] * len(self.chains)
+        self.steps = 0
+
+    # -- the pieces of advance(), separately callable (tests drive them in lock-step with a checker) --
+    def upload(self, t):
+        self.images = [c.frame_images(t) for c in self.chains]
+        self.d_img.copy_(self.torch.from_numpy(np.stack([np.ascontiguousarray(L, np.uint8) for L, _ in self.images])))
+
+    def step(self):
+        self.trk.step_batch(self.d_img.data_ptr(), self.cols, self.rows * self.cols, self.d_res.data_ptr())
+        self.steps += 1
+
+    def results(self):
+        """the ONE download of a step (synchronises)"""
+        return self.d_res.cpu().numpy().view(self.api.TRACKER_RESULT_DTYPE).copy()
+
+    def hand_off(self, s):
+        """the chain's current frame becomes the device's `last` frame of stream s"""
+        c = self.chains[s]
+        feats, mps, slot = c.cur.feats, [], {}
+        lm = np.full(len(feats), -1, np.int32)
+        for i, f in enumerate(feats):
+            mp = f.live()
+            if mp is not None:
+                if mp.id not in slot:
+                    slot[mp.id] = len(mps); mps.append(mp)
+                lm[i] = slot[mp.id]
+        st = {"xy": np.array([[f.x, f.y] for f in feats], np.float32).reshape(-1, 2), "lm": lm,
+              "lm_pos": np.array([m.pos for m in mps], float).reshape(-1, 3), "lm_outlier": np.array([1 if m.outlier else 0 for m in mps], np.uint8),
+              "ref_pose": c.ref_kf.pose, "ref_frame_id": c.ref_kf.frame_id, "last_rel": c.cur.rel, "rel_motion": c.rel_motion,
+              "next_frame_id": c.next_frame_id, "status": c.status, "kf_every": c.kf_every}
+        self.trk.set_frame(s, st, image=c.cur.L)       # the key-frame's image as the loop closer left it (blurred in place, deeplcd.cpp:46)
+        self.slots[s] = mps
+        self.on_device[s] = True
+
+    def host_turn(self, s, rec, t, ts=None):
+        """a frozen stream: the device's frame becomes the chain's current frame, the chain does its key-frame work, the result goes back"""
+        c = self.chains[s]
+        st = self.trk.get_frame(s)
+        L, R = self.images[s]
+        c.cur = Frame(int(rec["frame_id"]), float(ts if ts is not None else (c.ts[t] if c.ts is not None else t)), L, R)
+        c.next_frame_id = int(rec["frame_id"]) + 1
+        mps = self.slots[s]
+        for l in st["outlier_list"]:                    # Map::AddOutlierMapPoint, in the device's (= the features') order
+            mps[l].outlier = True
+            c.outlier_mps.append(mps[l].id)
+        for (x, y), l in zip(st["xy"], st["lm"]):
+            f = Feature(x, y)
+            f.mp = mps[l] if l >= 0 else None
+            c.cur.feats.append(f)
+        c.cur.rel, c.rel_motion, c.status = st["last_rel"], st["rel_motion"], int(rec["status"])
+        if c.status < 0:
+            raise RuntimeError(f"stream {s}: tracker tables too small ({int(rec['status'])})")
+        if c.status != LOST:                            # needs_host && !LOST = the key-frame rule (frontend.cpp:112-120)
+            c.detect_features()
+            c.find_features_in_right()
+            c.triangulate_new_points()
+            c.insert_keyframe()
+        c.poses.append(p7_of(mm(c.cur.rel, T_of(c.ref_kf.pose))))
+        c.last = c.cur
+        self.on_device[s] = False
+        if c.status != LOST:
+            self.hand_off(s)
+
+    def _log_step(self, s, pre, rec):
+        """the chain's "lk_track" / "pose_only" log entries of this frame, rebuilt from the device's buffers (pre = the state before the step)"""
+        c = self.chains[s]
+        _, p1, nxt, st = self.trk.debug_last_step(s)
+        c.rec("lk_track", nxt, st, p1)
+        post = self.trk.get_frame(s)
+        kept = [l for l, ok in zip(pre["lm"], st) if ok and l >= 0]
+        outl = np.array([post["lm"][j] < 0 for j, l in enumerate(kept) if not pre["lm_outlier"][l]], bool)
+        c.rec("pose_only", rec["pose7"], outl, np.array([int(rec["n_inliers"])]))
+
+    def advance(self, t):
+        """one frame of every stream; returns the streams that are still tracking"""
+        self.upload(t)
+        stepped = [s for s, c in enumerate(self.chains) if self.on_device[s]]
+        logged = {s: self.trk.get_frame(s) for s in stepped if self.chains[s].keep_log}       # (a logging chain pays two more downloads per frame)
+        if stepped:
+            self.step()
+            res = self.results()
+        for s, c in enumerate(self.chains):
+            if s in stepped:
+                if s in logged:
+                    self._log_step(s, logged[s], res[s])
+                if res[s]["needs_host"]:
+                    self.host_turn(s, res[s], t)
+                else:
+                    c.status = int(res[s]["status"]); c.next_frame_id = int(res[s]["frame_id"]) + 1
+                    c.poses.append(res[s]["pose7"].copy())
+            elif c.status == INITING:                   # Frontend::StereoInit on the one-camera path
+                c.grab(t)
+                if c.status != INITING:
+                    self.hand_off(s)
+        return [s for s, c in enumerate(self.chains) if c.status in (INITING, TRACKING_GOOD, TRACKING_BAD)]
+
+    def run(self, n):
+        for t in range(n):
+            if not self.advance(t):
+                break
+        return self

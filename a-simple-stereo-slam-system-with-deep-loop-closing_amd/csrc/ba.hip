@@ -1494,6 +1494,21 @@ static void pose_only_launch(const PoseOnlyArgs& a, int batch, int max_edges, hi
     else hipLaunchKernelGGL(k_pose_only<512>, dim3(batch), dim3(512), 0, s, a);
 }
 
+extern "C++" {
+namespace myslam_hip {
+// the multi-stream tracker's pose-only launch (tracker.hip, declared in frontend_launch.h): the batch entry point below without its argument checks
+int pose_only_bank_launch(double* d_poses, const double* d_pts3d, const double* d_obs, const int32_t* d_counts, int batch, int cap, double fx, double fy,
+                          double cx, double cy, double chi2_th, int rounds, int iters, uint8_t* d_outlier, int32_t* d_n_inliers, int32_t* d_status,
+                          hipStream_t s) {
+    PoseOnlyArgs a{d_poses, d_pts3d, d_obs, d_counts, 0, cap, fx, fy, cx, cy, chi2_th, rounds, iters, 0, d_outlier, d_n_inliers, d_status};
+    ScopedProf sp(P_BA, s);
+    pose_only_launch(a, batch, cap, s);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    return MYSLAM_OK;
+}
+}  // namespace myslam_hip
+}  // extern "C++"
+
 int myslam_pose_only_optimize_batch(double* d_poses, const double* d_pts3d, const double* d_obs, const int32_t* d_counts, int batch, int cap,
                                     double fx, double fy, double cx, double cy, double chi2_th, int rounds, int iters, int pre_optimize,
                                     uint8_t* d_outlier, int32_t* d_n_inliers, int32_t* d_status, void* hip_stream) {

@@ -38,11 +38,19 @@ __device__ __forceinline__ int lk_reflect101(int p, int len) {
 }
 
 // cv::pyrDown 8UC1: one thread per destination pixel
+// `sel` (the multi-stream tracker, tracker.hip; NULL everywhere else): image b lives in the sel[b]-th of two equally laid out buffers that are
+// srcSel / dstSel bytes apart; sel[b] < 0 = image b is skipped
 __global__ __launch_bounds__(256) void k_pyr_down(const uint8_t* __restrict__ src, int sw, int sh, int sstep, size_t sstride,
-                                                  uint8_t* __restrict__ dst, int dw, int dh, size_t dstride) {
+                                                  uint8_t* __restrict__ dst, int dw, int dh, size_t dstride, const int32_t* __restrict__ sel,
+                                                  size_t srcSel, size_t dstSel) {
     const int b = blockIdx.z;
     const int x = blockIdx.x * 64 + (threadIdx.x & 63), y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= dw || y >= dh) return;
+    if (sel) {
+        const int k = sel[b];
+        if (k < 0) return;
+        src += (size_t)k * srcSel; dst += (size_t)k * dstSel;
+    }
     const uint8_t* S = src + (size_t)b * sstride;
     int xs[5];
 #pragma unroll
@@ -77,6 +85,9 @@ struct LkArgs {
     const float* prev_pts; float* next_pts; const int32_t* counts; int n_fixed, cap;
     int win, max_iters; float eps2, min_eig;
     uint8_t* status; float* err;
+    // the multi-stream tracker (tracker.hip; NULL everywhere else): pair b tracks from buffer 1 - sel[b] into buffer sel[b] of two equally laid
+    // out (image, pyramid) buffers imgSel / pyrSel bytes apart; prev == next and pyrP == pyrN name buffer 0 then
+    const int32_t* sel; size_t imgSel, pyrSel;
 };
 
 __global__ __launch_bounds__(256) void k_lk_track(LkArgs a) {
@@ -88,6 +99,13 @@ __global__ __launch_bounds__(256) void k_lk_track(LkArgs a) {
     const int pi = blockIdx.x * 4 + wave;
     const int n = a.counts ? a.counts[b] : a.n_fixed;
     if (pi >= n) return;                                            // wave-uniform
+    const uint8_t *prev0 = a.prev, *next0 = a.next, *pyrP = a.pyrP, *pyrN = a.pyrN;
+    if (a.sel) {                                                    // block-uniform
+        const int k = a.sel[b];
+        if (k < 0) return;
+        prev0 += (size_t)(1 - k) * a.imgSel; next0 += (size_t)k * a.imgSel;
+        pyrP += (size_t)(1 - k) * a.pyrSel; pyrN += (size_t)k * a.pyrSel;
+    }
     const int win = a.win, ww = win * win, pI = win + 3, pJ = win + 1;
     const float halfWin = (float)(win - 1) * 0.5f;
     const float* pp = a.prev_pts + ((size_t)b * a.cap + pi) * 2;
@@ -102,8 +120,8 @@ __global__ __launch_bounds__(256) void k_lk_track(LkArgs a) {
     for (int level = a.g.levels; level >= 0; level--) {
         const int lw = a.g.w[level], lh = a.g.h[level];
         const uint8_t* I; const uint8_t* J; int istep, jstep;
-        if (level == 0) { I = a.prev + (size_t)b * a.pstride; J = a.next + (size_t)b * a.nstride; istep = a.pstep; jstep = a.nstep; }
-        else { I = a.pyrP + (size_t)b * a.g.bytes + a.g.off[level]; J = a.pyrN + (size_t)b * a.g.bytes + a.g.off[level]; istep = jstep = lw; }
+        if (level == 0) { I = prev0 + (size_t)b * a.pstride; J = next0 + (size_t)b * a.nstride; istep = a.pstep; jstep = a.nstep; }
+        else { I = pyrP + (size_t)b * a.g.bytes + a.g.off[level]; J = pyrN + (size_t)b * a.g.bytes + a.g.off[level]; istep = jstep = lw; }
         const float sc = (float)(1. / (1 << level));
         float prx = __fmul_rn(p0x, sc), pry = __fmul_rn(p0y, sc);
         float nx, ny;
@@ -306,22 +324,24 @@ static int lk_ensure(myslam_lk* h, int batch, int rows, int cols) {
 }
 
 // levels 1 .. of `batch` images (level 0 at src0, row pitch step0, image stride stride0) into pyr
-static void lk_pyramid(myslam_lk* h, const uint8_t* src0, int step0, size_t stride0, uint8_t* pyr, int batch) {
+// sel / selBytes: see k_pyr_down (the level-0 images are never selected: they are the caller's)
+static void lk_pyramid(myslam_lk* h, const uint8_t* src0, int step0, size_t stride0, uint8_t* pyr, int batch, const int32_t* sel = nullptr,
+                       size_t selBytes = 0) {
     const LkGeom& g = h->g;
     for (int l = 1; l <= g.levels; l++) {
         const uint8_t* src = (l == 1) ? src0 : pyr + g.off[l - 1];
         const int sstep = (l == 1) ? step0 : g.w[l - 1];
         const size_t sstride = (l == 1) ? stride0 : g.bytes;
         hipLaunchKernelGGL(k_pyr_down, dim3((g.w[l] + 63) / 64, (g.h[l] + 3) / 4, batch), dim3(256), 0, h->stream, src, g.w[l - 1], g.h[l - 1], sstep, sstride,
-                           pyr + g.off[l], g.w[l], g.h[l], g.bytes);
+                           pyr + g.off[l], g.w[l], g.h[l], g.bytes, sel, (l == 1) ? (size_t)0 : selBytes, selBytes);
     }
 }
 
 static int lk_track_launch(myslam_lk* h, const uint8_t* d_prev, const uint8_t* d_next, const uint8_t* pyrP, const uint8_t* pyrN, int batch, int rows, int cols,
                            int pstep, int nstep, size_t pstride, size_t nstride, const float* d_prev_pts, float* d_next_pts, const int32_t* d_counts,
-                           int n_fixed, int cap, uint8_t* d_status, float* d_err) {
+                           int n_fixed, int cap, uint8_t* d_status, float* d_err, const int32_t* d_sel = nullptr, size_t imgSel = 0, size_t pyrSel = 0) {
     LkArgs a{d_prev, d_next, rows, cols, pstep, nstep, pstride, nstride, pyrP, pyrN, h->g, d_prev_pts, d_next_pts, d_counts, n_fixed, cap,
-             h->win, h->max_iters, h->eps * h->eps, h->min_eig, d_status, d_err};
+             h->win, h->max_iters, h->eps * h->eps, h->min_eig, d_status, d_err, d_sel, imgSel, pyrSel};
     hipLaunchKernelGGL(k_lk_track, dim3((cap + 3) / 4, batch), dim3(256), 0, h->stream, a);
     MYSLAM_HIP_CHECK(hipGetLastError());
     return MYSLAM_OK;
@@ -372,6 +392,29 @@ static int lk_find_slot(const myslam_lk* h, uint64_t tok, int rows, int cols, in
     for (int i = 0; i < 2; i++) if (h->slot[i].tok == tok && h->slot[i].rows == rows && h->slot[i].cols == cols && h->slot[i].step == step) return i;
     return -1;
 }
+
+// ---- launch helpers of the multi-stream tracker (tracker.hip, declared in frontend_launch.h): the kernels above, unchanged arithmetic ----
+namespace myslam_hip {
+
+int lk_bank_plan(myslam_lk* h, int rows, int cols, size_t* pyr_bytes, int* levels) {
+    lk_plan(h, rows, cols);
+    *pyr_bytes = std::max<size_t>(256, h->g.bytes); *levels = h->g.levels;
+    return MYSLAM_OK;
+}
+
+int lk_bank_pyramid(myslam_lk* h, const uint8_t* d_img, int step, size_t stride, uint8_t* d_pyr, int batch, const int32_t* d_sel, size_t pyr_sel) {
+    lk_pyramid(h, d_img, step, stride, d_pyr, batch, d_sel, pyr_sel);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    return MYSLAM_OK;
+}
+
+int lk_bank_track(myslam_lk* h, const uint8_t* d_img, int step, size_t stride, const uint8_t* d_pyr, int batch, const int32_t* d_sel, size_t img_sel,
+                  size_t pyr_sel, const float* d_prev_pts, float* d_next_pts, const int32_t* d_counts, int cap, uint8_t* d_status) {
+    return lk_track_launch(h, d_img, d_img, d_pyr, d_pyr, batch, h->rows, h->cols, step, step, stride, stride, d_prev_pts, d_next_pts, d_counts, 0, cap,
+                           d_status, nullptr, d_sel, img_sel, pyr_sel);
+}
+
+}  // namespace myslam_hip
 
 extern "C" {
 

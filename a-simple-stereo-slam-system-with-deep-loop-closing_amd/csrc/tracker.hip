@@ -1,0 +1,493 @@
+// tracker.hip — Frontend::Track() (src/frontend.cpp:86-122) for S independent camera streams per call, all tracker state in device memory:
+// constant-velocity prediction and the LK start points (:90-93, :136-147), TrackLastFrame's feature hand-over (:156-170), the inputs of
+// EstimateCurrentPose (:183-205), its outlier bookkeeping (:261-270), the GOOD / BAD / LOST decision (:97-110), the relative motion (:122) and
+// the key-frame rule (:112).  LK and the pose-only optimisation are the kernels of lk.hip / ba.hip (frontend_launch.h); everything between them
+// is here, so that a step never returns to the host.  See include/myslam_hip.h for the rules.
+//
+// One step = head (image copy into the stream's free buffer + rule 1) -> pyramid levels -> LK -> compaction -> pose-only -> tail.
+// The SE3 arithmetic restates chain.py / host/myslam_system.hpp operation by operation with explicitly rounded f64 products and sums:
+// the LK start points are rounded to float, and one ulp there moves a converged track by up to 5e-3 px.
+#include <algorithm>
+#include <vector>
+
+#include "frontend_launch.h"
+
+namespace myslam_hip {
+
+constexpr int TRK_NT = 256;                 // threads of the per-stream blocks
+constexpr int TRK_COPY_ROWS = 4;            // image rows one copy block of the head kernel moves
+enum { TRK_INITING = 0, TRK_GOOD = 1, TRK_BAD = 2, TRK_LOST = 3 };
+
+struct TrkState {
+    double ref_pose[7];
+    double last_rel[16], rel_motion[16];
+    int32_t ref_frame_id, next_frame_id, status, frozen, kf_every;
+    int32_t n_feat, n_lm, n_outl;
+    int32_t slot;                           // which of the two (image, pyramid) buffers holds the stream's previous image
+    int32_t overflow;                       // set_frame did not fit: the next step reports it
+    int32_t pad[2];
+};
+
+struct TrkArgs {
+    TrkState* st; int S, cap, lmCap, rows, cols;
+    double fx, fy, cx, cy; int good, bad;
+    // state tables
+    float* xy; int32_t* lm;                 // S x cap (x 2)
+    double* lmPos; uint8_t* lmOutl;         // S x lmCap (x 3)
+    int32_t* outlList;                      // S x 2 cap
+    // images
+    const uint8_t* left; int step; size_t stride; uint8_t* img; size_t imgBytes, imgSel;
+    // step scratch
+    int32_t* sel; int32_t* counts;          // S
+    float* p0; float* p1; float* nxt; uint8_t* lkSt;          // S x cap
+    float* curXy; int32_t* curLm; int32_t* curPo; int32_t* curN;
+    double* poPose; double* poPts; double* poObs; int32_t* poCounts; uint8_t* poOutl; int32_t* poInl; int32_t* poStatus;
+    myslam_tracker_result* res;
+};
+
+// ---- SE3 on 4 x 4 row-major doubles, the operations of chain.py in its order ----
+__device__ __forceinline__ double dmul(double a, double b) { return __dmul_rn(a, b); }
+__device__ __forceinline__ double dadd(double a, double b) { return __dadd_rn(a, b); }
+__device__ __forceinline__ double dsub(double a, double b) { return __dsub_rn(a, b); }
+__device__ __forceinline__ double ddiv(double a, double b) { return __ddiv_rn(a, b); }
+
+__device__ void se3_mm(const double* A, const double* B, double* C) {          // chain.mm: sum over k in ascending order
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) {
+            double c = dmul(A[4 * i], B[j]);
+            for (int k = 1; k < 4; k++) c = dadd(c, dmul(A[4 * i + k], B[4 * k + j]));
+            C[4 * i + j] = c;
+        }
+}
+
+__device__ void se3_T_of(const double* p, double* T) {                         // chain.T_of / q_to_R
+    const double n = __dsqrt_rn(dadd(dadd(dadd(dmul(p[0], p[0]), dmul(p[1], p[1])), dmul(p[2], p[2])), dmul(p[3], p[3])));
+    const double x = ddiv(p[0], n), y = ddiv(p[1], n), z = ddiv(p[2], n), w = ddiv(p[3], n);
+    T[0] = dsub(1.0, dmul(2.0, dadd(dmul(y, y), dmul(z, z)))); T[1] = dmul(2.0, dsub(dmul(x, y), dmul(z, w))); T[2] = dmul(2.0, dadd(dmul(x, z), dmul(y, w)));
+    T[4] = dmul(2.0, dadd(dmul(x, y), dmul(z, w))); T[5] = dsub(1.0, dmul(2.0, dadd(dmul(x, x), dmul(z, z)))); T[6] = dmul(2.0, dsub(dmul(y, z), dmul(x, w)));
+    T[8] = dmul(2.0, dsub(dmul(x, z), dmul(y, w))); T[9] = dmul(2.0, dadd(dmul(y, z), dmul(x, w))); T[10] = dsub(1.0, dmul(2.0, dadd(dmul(x, x), dmul(y, y))));
+    T[3] = p[4]; T[7] = p[5]; T[11] = p[6];
+    T[12] = 0.0; T[13] = 0.0; T[14] = 0.0; T[15] = 1.0;
+}
+
+__device__ void se3_inv(const double* T, double* Ti) {                         // chain.T_inv: R^T, mv(-R^T, t)
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) Ti[4 * i + j] = T[4 * j + i];
+        double r = dmul(-T[i], T[3]);
+        r = dadd(r, dmul(-T[4 + i], T[7]));
+        r = dadd(r, dmul(-T[8 + i], T[11]));
+        Ti[4 * i + 3] = r;
+    }
+    Ti[12] = 0.0; Ti[13] = 0.0; Ti[14] = 0.0; Ti[15] = 1.0;
+}
+
+__device__ void se3_p7_of(const double* T, double* p) {                        // chain.p7_of / R_to_q
+    const double R00 = T[0], R01 = T[1], R02 = T[2], R10 = T[4], R11 = T[5], R12 = T[6], R20 = T[8], R21 = T[9], R22 = T[10];
+    const double t = dadd(dadd(R00, R11), R22);
+    double q[4];
+    if (t > 0) {
+        const double s = dmul(__dsqrt_rn(dadd(t, 1.0)), 2.0);
+        q[0] = ddiv(dsub(R21, R12), s); q[1] = ddiv(dsub(R02, R20), s); q[2] = ddiv(dsub(R10, R01), s); q[3] = dmul(0.25, s);
+    } else if (R00 > R11 && R00 > R22) {
+        const double s = dmul(__dsqrt_rn(dsub(dsub(dadd(1.0, R00), R11), R22)), 2.0);
+        q[0] = dmul(0.25, s); q[1] = ddiv(dadd(R01, R10), s); q[2] = ddiv(dadd(R02, R20), s); q[3] = ddiv(dsub(R21, R12), s);
+    } else if (R11 > R22) {
+        const double s = dmul(__dsqrt_rn(dsub(dsub(dadd(1.0, R11), R00), R22)), 2.0);
+        q[0] = ddiv(dadd(R01, R10), s); q[1] = dmul(0.25, s); q[2] = ddiv(dadd(R12, R21), s); q[3] = ddiv(dsub(R02, R20), s);
+    } else {
+        const double s = dmul(__dsqrt_rn(dsub(dsub(dadd(1.0, R22), R00), R11)), 2.0);
+        q[0] = ddiv(dadd(R02, R20), s); q[1] = ddiv(dadd(R12, R21), s); q[2] = dmul(0.25, s); q[3] = ddiv(dsub(R10, R01), s);
+    }
+    const bool neg = !(q[3] >= 0);
+    for (int k = 0; k < 4; k++) p[k] = neg ? -q[k] : q[k];
+    p[4] = T[3]; p[5] = T[7]; p[6] = T[11];
+}
+
+// exclusive rank of `flag` among the block's threads (thread order) and the block's total; s_w: one int per wave.  Two barriers.
+__device__ __forceinline__ int block_rank(bool flag, int* s_w, int& total) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned long long m = __ballot(flag);
+    const int inWave = __popcll(m & ((1ull << lane) - 1ull));
+    __syncthreads();                                                           // s_w of the previous use has been read
+    if (lane == 0) s_w[wv] = __popcll(m);
+    __syncthreads();
+    int before = 0; total = 0;
+#pragma unroll
+    for (int k = 0; k < TRK_NT / 64; k++) { const int c = s_w[k]; if (k < wv) before += c; total += c; }
+    return before + inWave;
+}
+
+// ---- head: blockIdx.x == 0 predicts (rule 1) for stream blockIdx.y; the other blocks copy the stream's new image into its free buffer ----
+__global__ __launch_bounds__(TRK_NT) void k_trk_head(TrkArgs a) {
+    const int s = blockIdx.y, t = threadIdx.x;
+    const TrkState& st = a.st[s];
+    const bool idle = st.frozen != 0;
+    if (blockIdx.x > 0) {
+        if (idle || st.overflow) return;
+        const int r0 = (blockIdx.x - 1) * TRK_COPY_ROWS, r1 = min(r0 + TRK_COPY_ROWS, a.rows);
+        const uint8_t* src = a.left + (size_t)s * a.stride;
+        uint8_t* dst = a.img + (size_t)(1 - st.slot) * a.imgSel + (size_t)s * a.imgBytes;
+        if (((a.cols | a.step) & 3) == 0 && (((size_t)src) & 3) == 0) {
+            const int w4 = a.cols >> 2;
+            for (int r = r0; r < r1; r++) {
+                const uint32_t* sp = reinterpret_cast<const uint32_t*>(src + (size_t)r * a.step);
+                uint32_t* dp = reinterpret_cast<uint32_t*>(dst + (size_t)r * a.cols);
+                for (int x = t; x < w4; x += TRK_NT) dp[x] = sp[x];
+            }
+        } else {
+            for (int r = r0; r < r1; r++)
+                for (int x = t; x < a.cols; x += TRK_NT) dst[(size_t)r * a.cols + x] = src[(size_t)r * a.step + x];
+        }
+        return;
+    }
+    if (idle) {
+        if (t == 0) { a.sel[s] = -1; a.counts[s] = 0; a.poCounts[s] = 0; }
+        return;
+    }
+    if (st.overflow) {                       // set_frame did not fit: say so once, freeze
+        if (t == 0) {
+            myslam_tracker_result r;
+            for (int k = 0; k < 7; k++) r.pose7[k] = st.ref_pose[k];
+            r.n_inliers = 0; r.n_features = 0; r.status = MYSLAM_ERR_CAPACITY; r.frame_id = st.next_frame_id; r.needs_host = 1; r.reserved = 0;
+            a.res[s] = r;
+            a.sel[s] = -1; a.counts[s] = 0; a.poCounts[s] = 0;
+            a.st[s].frozen = 1;
+        }
+        return;
+    }
+    __shared__ double sT[16];
+    if (t == 0) {
+        double Tref[16], rel[16], p7[7];
+        se3_T_of(st.ref_pose, Tref);
+        se3_mm(st.rel_motion, st.last_rel, rel);         // cur.rel = rel_motion * last.rel
+        se3_mm(rel, Tref, sT);                           // Tcw
+        se3_p7_of(sT, p7);
+        for (int k = 0; k < 7; k++) a.poPose[(size_t)s * 7 + k] = p7[k];
+        a.sel[s] = 1 - st.slot; a.counts[s] = st.n_feat;
+    }
+    __syncthreads();
+    const int n = st.n_feat;
+    const size_t fb = (size_t)s * a.cap;
+    const double* pos = a.lmPos + (size_t)s * a.lmCap * 3;
+    const uint8_t* outl = a.lmOutl + (size_t)s * a.lmCap;
+    for (int i = t; i < n; i += TRK_NT) {
+        const float x = a.xy[(fb + i) * 2], y = a.xy[(fb + i) * 2 + 1];
+        float u = x, v = y;
+        const int l = a.lm[fb + i];
+        if (l >= 0 && !outl[l]) {                         // world2pixel: pc = mv(R, pw) + t; (fx pc.x / pc.z + cx, fy pc.y / pc.z + cy)
+            const double px = pos[3 * l], py = pos[3 * l + 1], pz = pos[3 * l + 2];
+            double pc[3];
+            for (int r = 0; r < 3; r++)
+                pc[r] = dadd(dadd(dadd(dmul(sT[4 * r], px), dmul(sT[4 * r + 1], py)), dmul(sT[4 * r + 2], pz)), sT[4 * r + 3]);
+            u = __double2float_rn(dadd(ddiv(dmul(a.fx, pc[0]), pc[2]), a.cx));
+            v = __double2float_rn(dadd(ddiv(dmul(a.fy, pc[1]), pc[2]), a.cy));
+        }
+        a.p0[(fb + i) * 2] = x; a.p0[(fb + i) * 2 + 1] = y;
+        a.p1[(fb + i) * 2] = u; a.p1[(fb + i) * 2 + 1] = v;
+        a.nxt[(fb + i) * 2] = u; a.nxt[(fb + i) * 2 + 1] = v;
+    }
+}
+
+// ---- rule 3: one block per stream, ballot + prefix per 256 features, order kept ----
+__global__ __launch_bounds__(TRK_NT) void k_trk_compact(TrkArgs a) {
+    __shared__ int s_w[TRK_NT / 64];
+    const int s = blockIdx.x, t = threadIdx.x;
+    if (a.sel[s] < 0) return;
+    const int n = a.counts[s];
+    const size_t fb = (size_t)s * a.cap;
+    const double* pos = a.lmPos + (size_t)s * a.lmCap * 3;
+    const uint8_t* outl = a.lmOutl + (size_t)s * a.lmCap;
+    int nKeep = 0, nPo = 0;
+    for (int base = 0; base < n; base += TRK_NT) {
+        const int i = base + t;
+        int l = -1; bool keep = false, po = false;
+        if (i < n) {
+            l = a.lm[fb + i];
+            keep = a.lkSt[fb + i] != 0 && l >= 0;
+            po = keep && !outl[l];
+        }
+        int tk, tp;
+        const int rk = block_rank(keep, s_w, tk), rp = block_rank(po, s_w, tp);
+        if (keep) {
+            const int j = nKeep + rk;
+            const float x = a.nxt[(fb + i) * 2], y = a.nxt[(fb + i) * 2 + 1];
+            a.curXy[(fb + j) * 2] = x; a.curXy[(fb + j) * 2 + 1] = y;
+            a.curLm[fb + j] = l;
+            a.curPo[fb + j] = po ? nPo + rp : -1;
+            if (po) {
+                const int k = nPo + rp;
+                a.poPts[(fb + k) * 3] = pos[3 * l]; a.poPts[(fb + k) * 3 + 1] = pos[3 * l + 1]; a.poPts[(fb + k) * 3 + 2] = pos[3 * l + 2];
+                a.poObs[(fb + k) * 2] = (double)x; a.poObs[(fb + k) * 2 + 1] = (double)y;
+            }
+        }
+        nKeep += tk; nPo += tp;
+    }
+    if (t == 0) { a.curN[s] = nKeep; a.poCounts[s] = nPo; }
+}
+
+// ---- rules 5 + 6: one block per stream ----
+__global__ __launch_bounds__(TRK_NT) void k_trk_tail(TrkArgs a) {
+    __shared__ int s_w[TRK_NT / 64];
+    const int s = blockIdx.x, t = threadIdx.x;
+    if (a.sel[s] < 0) return;
+    TrkState& st = a.st[s];
+    const int m = a.curN[s], id = st.next_frame_id;
+    const bool fresh = id - st.ref_frame_id <= 2;        // a map point that fails right after its creation leaves the map (:264-268)
+    const size_t fb = (size_t)s * a.cap;
+    uint8_t* lmOutl = a.lmOutl + (size_t)s * a.lmCap;
+    int32_t* list = a.outlList + (size_t)s * 2 * a.cap;
+    const int listCap = 2 * a.cap;
+    int nList = st.n_outl;
+    bool listFull = false;
+    for (int base = 0; base < m; base += TRK_NT) {
+        const int j = base + t;
+        int l = -1; bool o = false;
+        if (j < m) {
+            l = a.curLm[fb + j];
+            const int k = a.curPo[fb + j];
+            o = k >= 0 && a.poOutl[fb + k] != 0;
+        }
+        int tot;
+        const int r = block_rank(o && fresh, s_w, tot);
+        if (o && fresh) {
+            lmOutl[l] = 1;
+            if (nList + r < listCap) list[nList + r] = l;
+        }
+        if (nList + tot > listCap) listFull = true;
+        nList = min(nList + tot, listCap);
+        if (j < m) {
+            a.xy[(fb + j) * 2] = a.curXy[(fb + j) * 2]; a.xy[(fb + j) * 2 + 1] = a.curXy[(fb + j) * 2 + 1];
+            a.lm[fb + j] = o ? -1 : l;
+        }
+    }
+    if (t != 0) return;
+    double Tp[16], Tref[16], Tri[16], rel[16], Li[16], Tcw[16];
+    myslam_tracker_result r;
+    se3_T_of(a.poPose + (size_t)s * 7, Tp);
+    se3_T_of(st.ref_pose, Tref);
+    se3_inv(Tref, Tri);
+    se3_mm(Tp, Tri, rel);                                // cur.rel = T(pose) * T(ref)^-1
+    se3_inv(st.last_rel, Li);
+    se3_mm(rel, Li, st.rel_motion);                      // rel_motion = cur.rel * last.rel^-1
+    for (int k = 0; k < 16; k++) st.last_rel[k] = rel[k];
+    se3_mm(rel, Tref, Tcw);
+    se3_p7_of(Tcw, r.pose7);
+    const int ninl = a.poInl[s];
+    int status = ninl > a.good ? TRK_GOOD : (ninl > a.bad ? TRK_BAD : TRK_LOST);
+    const bool insert = st.kf_every <= 0 ? status == TRK_BAD : (status != TRK_LOST && id % st.kf_every == 0);
+    int needs = (insert || status == TRK_LOST) ? 1 : 0;
+    st.status = status;
+    if (a.poStatus[s] != MYSLAM_OK || listFull) { status = MYSLAM_ERR_CAPACITY; needs = 1; }
+    r.n_inliers = ninl; r.n_features = m; r.status = status; r.frame_id = id; r.needs_host = needs; r.reserved = 0;
+    a.res[s] = r;
+    st.n_feat = m; st.n_outl = nList; st.next_frame_id = id + 1; st.slot = 1 - st.slot; st.frozen = needs;
+}
+
+}  // namespace myslam_hip
+
+using namespace myslam_hip;
+
+struct myslam_tracker {
+    hipStream_t stream = nullptr;
+    myslam_lk* lk = nullptr;
+    int S = 0, rows = 0, cols = 0, cap = 0, lmCap = 0, levels = 0;
+    size_t pyrBytes = 0;
+    TrkArgs a{};
+    uint8_t* d_pyr = nullptr;
+    std::vector<void*> bufs;
+    std::vector<char> hasImage;
+};
+
+template <class T>
+static int trk_alloc(myslam_tracker* h, T** p, size_t n) {
+    MYSLAM_HIP_CHECK(hipMalloc((void**)p, std::max<size_t>(256, n * sizeof(T))));
+    h->bufs.push_back(*p);
+    return MYSLAM_OK;
+}
+
+static int trk_alloc_all(myslam_tracker* h) {
+    TrkArgs& a = h->a;
+    const size_t S = h->S, F = S * h->cap, L = S * h->lmCap;
+    int rc = 0;
+#define TRK_A(ptr, n) if ((rc = trk_alloc(h, &(ptr), (n)))) return rc
+    TRK_A(a.st, S); TRK_A(a.xy, F * 2); TRK_A(a.lm, F); TRK_A(a.lmPos, L * 3); TRK_A(a.lmOutl, L); TRK_A(a.outlList, F * 2);
+    TRK_A(a.img, 2 * a.imgSel); TRK_A(h->d_pyr, 2 * S * h->pyrBytes);
+    TRK_A(a.sel, S); TRK_A(a.counts, S); TRK_A(a.p0, F * 2); TRK_A(a.p1, F * 2); TRK_A(a.nxt, F * 2); TRK_A(a.lkSt, F);
+    TRK_A(a.curXy, F * 2); TRK_A(a.curLm, F); TRK_A(a.curPo, F); TRK_A(a.curN, S);
+    TRK_A(a.poPose, S * 7); TRK_A(a.poPts, F * 3); TRK_A(a.poObs, F * 2); TRK_A(a.poCounts, S); TRK_A(a.poOutl, F); TRK_A(a.poInl, S); TRK_A(a.poStatus, S);
+#undef TRK_A
+    std::vector<TrkState> init(S);
+    memset(init.data(), 0, S * sizeof(TrkState));
+    for (TrkState& st : init) { st.frozen = 1; st.status = TRK_INITING; }
+    // (every other buffer is written before it is read: tables by set_frame, scratch by the step's own kernels)
+    const std::vector<int32_t> zeros(S, 0);
+    if ((rc = upload_table(a.st, init.data(), S * sizeof(TrkState))) || (rc = upload_table(a.counts, zeros.data(), S * sizeof(int32_t)))) return rc;
+    return MYSLAM_OK;
+}
+
+extern "C" {
+
+int myslam_tracker_create(myslam_tracker** out, int streams, int rows, int cols, int cap, int landmark_cap, double fx, double fy, double cx, double cy,
+                          int tracking_good, int tracking_bad, int win, int max_level, int max_iters, float eps, float min_eig_threshold) {
+    if (!out || streams < 1 || rows < 1 || cols < 1 || cap < 1 || cap > 4096 || landmark_cap < 1) return MYSLAM_ERR_INVALID;
+    myslam_lk* lk = nullptr;
+    int rc = myslam_lk_create(&lk, win, max_level, max_iters, eps, min_eig_threshold);
+    if (rc) return rc;
+    myslam_tracker* h = new myslam_tracker();
+    h->lk = lk; h->S = streams; h->rows = rows; h->cols = cols; h->cap = cap; h->lmCap = landmark_cap;
+    h->hasImage.assign(streams, 0);
+    lk_bank_plan(lk, rows, cols, &h->pyrBytes, &h->levels);
+    TrkArgs& a = h->a;
+    a.S = streams; a.cap = cap; a.lmCap = landmark_cap; a.rows = rows; a.cols = cols;
+    a.fx = fx; a.fy = fy; a.cx = cx; a.cy = cy; a.good = tracking_good; a.bad = tracking_bad;
+    a.imgBytes = ((size_t)rows * cols + 255) & ~(size_t)255; a.imgSel = (size_t)streams * a.imgBytes;
+    if ((rc = trk_alloc_all(h))) { myslam_tracker_destroy(h); return rc; }
+    *out = h;
+    return MYSLAM_OK;
+}
+
+int myslam_tracker_destroy(myslam_tracker* h) {
+    if (!h) return MYSLAM_ERR_INVALID;
+    (void)hipStreamSynchronize(h->stream);
+    for (void* p : h->bufs) (void)hipFree(p);
+    if (h->lk) (void)myslam_lk_destroy(h->lk);
+    delete h;
+    return MYSLAM_OK;
+}
+
+int myslam_tracker_set_stream(myslam_tracker* h, void* s) {
+    if (!h) return MYSLAM_ERR_INVALID;
+    MYSLAM_HIP_CHECK(hipStreamSynchronize(h->stream));
+    h->stream = (hipStream_t)s;
+    return myslam_lk_set_stream(h->lk, s);
+}
+
+int myslam_tracker_launches_per_step(const myslam_tracker* h) {
+    return h ? 5 + h->levels : MYSLAM_ERR_INVALID;
+}
+
+int myslam_tracker_set_frame(myslam_tracker* h, int s, const float* feat_xy, const int32_t* feat_landmark, int n_feat, const double* landmark_pos,
+                             const uint8_t* landmark_outlier, int n_landmarks, const double* ref_pose7, int ref_frame_id, const double* last_rel16,
+                             const double* rel_motion16, int next_frame_id, int status, int kf_every, const uint8_t* prev_image, int image_step) {
+    if (!h || s < 0 || s >= h->S || n_feat < 0 || n_landmarks < 0 || (n_feat > 0 && (!feat_xy || !feat_landmark)) ||
+        (n_landmarks > 0 && (!landmark_pos || !landmark_outlier)) || !ref_pose7 || !last_rel16 || !rel_motion16 || (prev_image && image_step < h->cols))
+        return MYSLAM_ERR_INVALID;
+    if (!prev_image && !h->hasImage[s]) return MYSLAM_ERR_INVALID;
+    const bool fits = n_feat <= h->cap && n_landmarks <= h->lmCap;
+    if (fits)
+        for (int i = 0; i < n_feat; i++) if (feat_landmark[i] < -1 || feat_landmark[i] >= n_landmarks) return MYSLAM_ERR_INVALID;
+    hipStream_t st = h->stream;
+    TrkArgs& a = h->a;
+    TrkState hs;
+    int rc = copy_sync(&hs, a.st + s, sizeof(TrkState), hipMemcpyDeviceToHost, st);
+    if (rc) return rc;
+    memcpy(hs.ref_pose, ref_pose7, sizeof(double) * 7); memcpy(hs.last_rel, last_rel16, sizeof(double) * 16); memcpy(hs.rel_motion, rel_motion16, sizeof(double) * 16);
+    hs.ref_frame_id = ref_frame_id; hs.next_frame_id = next_frame_id; hs.status = status; hs.kf_every = kf_every;
+    hs.frozen = 0; hs.n_outl = 0; hs.overflow = fits ? 0 : 1;
+    hs.n_feat = fits ? n_feat : 0; hs.n_lm = fits ? n_landmarks : 0;
+    if (fits) {
+        const size_t fb = (size_t)s * h->cap, lb = (size_t)s * h->lmCap;
+        if (n_feat) {
+            MYSLAM_HIP_CHECK(hipMemcpyAsync(a.xy + fb * 2, feat_xy, sizeof(float) * 2 * n_feat, hipMemcpyHostToDevice, st));
+            MYSLAM_HIP_CHECK(hipMemcpyAsync(a.lm + fb, feat_landmark, sizeof(int32_t) * n_feat, hipMemcpyHostToDevice, st));
+        }
+        if (n_landmarks) {
+            MYSLAM_HIP_CHECK(hipMemcpyAsync(a.lmPos + lb * 3, landmark_pos, sizeof(double) * 3 * n_landmarks, hipMemcpyHostToDevice, st));
+            MYSLAM_HIP_CHECK(hipMemcpyAsync(a.lmOutl + lb, landmark_outlier, (size_t)n_landmarks, hipMemcpyHostToDevice, st));
+        }
+    }
+    std::vector<uint8_t> packed;
+    if (prev_image) {                        // one contiguous copy, then the levels above 0 of this one image
+        packed.resize((size_t)h->rows * h->cols);
+        for (int r = 0; r < h->rows; r++) memcpy(packed.data() + (size_t)r * h->cols, prev_image + (size_t)r * image_step, h->cols);
+        uint8_t* d_img = a.img + (size_t)hs.slot * a.imgSel + (size_t)s * a.imgBytes;
+        MYSLAM_HIP_CHECK(hipMemcpyAsync(d_img, packed.data(), packed.size(), hipMemcpyHostToDevice, st));
+        if ((rc = lk_bank_pyramid(h->lk, d_img, h->cols, a.imgBytes, h->d_pyr + ((size_t)hs.slot * h->S + s) * h->pyrBytes, 1, nullptr, 0))) return rc;
+        h->hasImage[s] = 1;
+    }
+    MYSLAM_HIP_CHECK(hipMemcpyAsync(a.st + s, &hs, sizeof(TrkState), hipMemcpyHostToDevice, st));
+    MYSLAM_HIP_CHECK(hipStreamSynchronize(st));
+    return fits ? MYSLAM_OK : MYSLAM_ERR_CAPACITY;
+}
+
+int myslam_tracker_get_frame(myslam_tracker* h, int s, float* feat_xy, int32_t* feat_landmark, int* n_feat, double* landmark_pos,
+                             uint8_t* landmark_outlier, int* n_landmarks, double* ref_pose7, int* ref_frame_id, double* last_rel16, double* rel_motion16,
+                             int* next_frame_id, int* status, int* kf_every, int* frozen, int32_t* outlier_landmarks, int* n_outlier_landmarks,
+                             uint8_t* prev_image, int image_step) {
+    if (!h || s < 0 || s >= h->S || (prev_image && image_step < h->cols)) return MYSLAM_ERR_INVALID;
+    hipStream_t st = h->stream;
+    TrkArgs& a = h->a;
+    TrkState hs;
+    int rc = copy_sync(&hs, a.st + s, sizeof(TrkState), hipMemcpyDeviceToHost, st);
+    if (rc) return rc;
+    const size_t fb = (size_t)s * h->cap, lb = (size_t)s * h->lmCap;
+    if (feat_xy && hs.n_feat) MYSLAM_HIP_CHECK(hipMemcpyAsync(feat_xy, a.xy + fb * 2, sizeof(float) * 2 * hs.n_feat, hipMemcpyDeviceToHost, st));
+    if (feat_landmark && hs.n_feat) MYSLAM_HIP_CHECK(hipMemcpyAsync(feat_landmark, a.lm + fb, sizeof(int32_t) * hs.n_feat, hipMemcpyDeviceToHost, st));
+    if (landmark_pos && hs.n_lm) MYSLAM_HIP_CHECK(hipMemcpyAsync(landmark_pos, a.lmPos + lb * 3, sizeof(double) * 3 * hs.n_lm, hipMemcpyDeviceToHost, st));
+    if (landmark_outlier && hs.n_lm) MYSLAM_HIP_CHECK(hipMemcpyAsync(landmark_outlier, a.lmOutl + lb, (size_t)hs.n_lm, hipMemcpyDeviceToHost, st));
+    if (outlier_landmarks && hs.n_outl)
+        MYSLAM_HIP_CHECK(hipMemcpyAsync(outlier_landmarks, a.outlList + fb * 2, sizeof(int32_t) * hs.n_outl, hipMemcpyDeviceToHost, st));
+    std::vector<uint8_t> packed;
+    if (prev_image) {
+        if (!h->hasImage[s]) return MYSLAM_ERR_INVALID;
+        packed.resize((size_t)h->rows * h->cols);
+        MYSLAM_HIP_CHECK(hipMemcpyAsync(packed.data(), a.img + (size_t)hs.slot * a.imgSel + (size_t)s * a.imgBytes, packed.size(), hipMemcpyDeviceToHost, st));
+    }
+    MYSLAM_HIP_CHECK(hipStreamSynchronize(st));
+    if (prev_image)
+        for (int r = 0; r < h->rows; r++) memcpy(prev_image + (size_t)r * image_step, packed.data() + (size_t)r * h->cols, h->cols);
+    if (n_feat) *n_feat = hs.n_feat;
+    if (n_landmarks) *n_landmarks = hs.n_lm;
+    if (ref_pose7) memcpy(ref_pose7, hs.ref_pose, sizeof(double) * 7);
+    if (ref_frame_id) *ref_frame_id = hs.ref_frame_id;
+    if (last_rel16) memcpy(last_rel16, hs.last_rel, sizeof(double) * 16);
+    if (rel_motion16) memcpy(rel_motion16, hs.rel_motion, sizeof(double) * 16);
+    if (next_frame_id) *next_frame_id = hs.next_frame_id;
+    if (status) *status = hs.status;
+    if (kf_every) *kf_every = hs.kf_every;
+    if (frozen) *frozen = hs.frozen;
+    if (n_outlier_landmarks) *n_outlier_landmarks = hs.n_outl;
+    return MYSLAM_OK;
+}
+
+int myslam_tracker_step_batch(myslam_tracker* h, const uint8_t* d_left, int step, size_t stride, myslam_tracker_result* d_results) {
+    if (!h || !d_left || step < h->cols || stride < (size_t)(h->rows - 1) * step + h->cols || !d_results) return MYSLAM_ERR_INVALID;
+    TrkArgs a = h->a;
+    a.left = d_left; a.step = step; a.stride = stride; a.res = d_results;
+    hipStream_t st = h->stream;
+    const int S = h->S;
+    const size_t pyrSel = (size_t)S * h->pyrBytes;
+    hipLaunchKernelGGL(k_trk_head, dim3(1 + (h->rows + TRK_COPY_ROWS - 1) / TRK_COPY_ROWS, S), dim3(TRK_NT), 0, st, a);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    int rc;
+    if ((rc = lk_bank_pyramid(h->lk, d_left, step, stride, h->d_pyr, S, a.sel, pyrSel))) return rc;
+    if ((rc = lk_bank_track(h->lk, a.img, h->cols, a.imgBytes, h->d_pyr, S, a.sel, a.imgSel, pyrSel, a.p0, a.nxt, a.counts, h->cap, a.lkSt))) return rc;
+    hipLaunchKernelGGL(k_trk_compact, dim3(S), dim3(TRK_NT), 0, st, a);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    if ((rc = pose_only_bank_launch(a.poPose, a.poPts, a.poObs, a.poCounts, S, h->cap, a.fx, a.fy, a.cx, a.cy, 5.991, 4, 10, a.poOutl, a.poInl, a.poStatus, st)))
+        return rc;
+    hipLaunchKernelGGL(k_trk_tail, dim3(S), dim3(TRK_NT), 0, st, a);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    return MYSLAM_OK;
+}
+
+int myslam_tracker_debug_last_step(myslam_tracker* h, int s, float* p0, float* p1, float* tracked, uint8_t* lk_status, int* n) {
+    if (!h || s < 0 || s >= h->S || !n) return MYSLAM_ERR_INVALID;
+    hipStream_t st = h->stream;
+    const TrkArgs& a = h->a;
+    int32_t cnt = 0;
+    int rc = copy_sync(&cnt, a.counts + s, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (rc) return rc;
+    const size_t fb = (size_t)s * h->cap;
+    if (cnt > 0) {
+        if (p0) MYSLAM_HIP_CHECK(hipMemcpyAsync(p0, a.p0 + fb * 2, sizeof(float) * 2 * cnt, hipMemcpyDeviceToHost, st));
+        if (p1) MYSLAM_HIP_CHECK(hipMemcpyAsync(p1, a.p1 + fb * 2, sizeof(float) * 2 * cnt, hipMemcpyDeviceToHost, st));
+        if (tracked) MYSLAM_HIP_CHECK(hipMemcpyAsync(tracked, a.nxt + fb * 2, sizeof(float) * 2 * cnt, hipMemcpyDeviceToHost, st));
+        if (lk_status) MYSLAM_HIP_CHECK(hipMemcpyAsync(lk_status, a.lkSt + fb, (size_t)cnt, hipMemcpyDeviceToHost, st));
+        MYSLAM_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    *n = cnt;
+    return MYSLAM_OK;
+}
+
+}  // extern "C"

@@ -363,6 +363,54 @@ public:
     void Prefetch(const ImageView& img, uint64_t token) { check(myslam_lk_prefetch(h_, img.data, token, img.rows, img.cols, img.step), "myslam_lk_prefetch"); }
 };
 
+// Frontend::Track() (src/frontend.cpp:86-122) for `streams` cameras of one image size and calibration at once, the tracker state of every
+// stream on the device (myslam_tracker_*): Step() advances every stream that is not frozen by one frame and never waits for the device;
+// a stream whose result says needs_host takes its key-frame work on the host between GetFrame() and SetFrame().
+class TrackerBank {
+    myslam_tracker* h_ = nullptr;
+    int streams_, rows_, cols_, cap_, lmCap_;
+public:
+    struct StreamState {            // what SetFrame uploads and GetFrame downloads
+        std::vector<Point2f> features; std::vector<int32_t> landmarkOf;          // last frame's features, slot of the landmark table or -1
+        std::vector<double> landmarkPos; std::vector<uint8_t> landmarkIsOutlier;   // n x 3, n
+        double refPose[7] = {0, 0, 0, 1, 0, 0, 0}; int refFrameId = 0;
+        double lastRel[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1}, relMotion[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+        int nextFrameId = 0, status = 0, kfEvery = 0, frozen = 0;
+        std::vector<int32_t> outlierLandmarks;                                     // GetFrame only: Map::AddOutlierMapPoint order
+    };
+    TrackerBank(int streams, int rows, int cols, int cap, int landmarkCap, double fx, double fy, double cx, double cy, int trackingGood = 50,
+                int trackingBad = 10, int win = 11, int maxLevel = 3, int maxCount = 30, float epsilon = 0.01f, float minEigThreshold = 1e-4f)
+        : streams_(streams), rows_(rows), cols_(cols), cap_(cap), lmCap_(landmarkCap) {
+        check(myslam_tracker_create(&h_, streams, rows, cols, cap, landmarkCap, fx, fy, cx, cy, trackingGood, trackingBad, win, maxLevel, maxCount, epsilon,
+                                    minEigThreshold), "myslam_tracker_create");
+    }
+    ~TrackerBank() { if (h_) myslam_tracker_destroy(h_); }
+    TrackerBank(const TrackerBank&) = delete; TrackerBank& operator=(const TrackerBank&) = delete;
+    int streams() const { return streams_; }
+    int launchesPerStep() const { return myslam_tracker_launches_per_step(h_); }
+    void SetStream(void* hipStream) { check(myslam_tracker_set_stream(h_, hipStream), "myslam_tracker_set_stream"); }
+    // prevImage: the image the next step tracks FROM (a key-frame's image after DeepLCD blurred it in place); nullptr keeps the last step's
+    void SetFrame(int stream, const StreamState& s, const ImageView* prevImage = nullptr) {
+        check(myslam_tracker_set_frame(h_, stream, reinterpret_cast<const float*>(s.features.data()), s.landmarkOf.data(), (int)s.features.size(),
+                                       s.landmarkPos.data(), s.landmarkIsOutlier.data(), (int)s.landmarkIsOutlier.size(), s.refPose, s.refFrameId, s.lastRel,
+                                       s.relMotion, s.nextFrameId, s.status, s.kfEvery, prevImage ? prevImage->data : nullptr, prevImage ? prevImage->step : 0),
+              "myslam_tracker_set_frame");
+    }
+    void GetFrame(int stream, StreamState& s) {
+        s.features.resize(cap_); s.landmarkOf.resize(cap_); s.landmarkPos.resize((size_t)lmCap_ * 3); s.landmarkIsOutlier.resize(lmCap_);
+        s.outlierLandmarks.resize((size_t)2 * cap_);
+        int nf = 0, nl = 0, no = 0;
+        check(myslam_tracker_get_frame(h_, stream, reinterpret_cast<float*>(s.features.data()), s.landmarkOf.data(), &nf, s.landmarkPos.data(),
+                                       s.landmarkIsOutlier.data(), &nl, s.refPose, &s.refFrameId, s.lastRel, s.relMotion, &s.nextFrameId, &s.status, &s.kfEvery,
+                                       &s.frozen, s.outlierLandmarks.data(), &no, nullptr, 0), "myslam_tracker_get_frame");
+        s.features.resize(nf); s.landmarkOf.resize(nf); s.landmarkPos.resize((size_t)nl * 3); s.landmarkIsOutlier.resize(nl); s.outlierLandmarks.resize(no);
+    }
+    // device pointers: image s at d_left + s * stride; d_results: streams() records; asynchronous on the handle's stream
+    void Step(const uint8_t* d_left, int step, size_t stride, myslam_tracker_result* d_results) {
+        check(myslam_tracker_step_batch(h_, d_left, step, stride, d_results), "myslam_tracker_step_batch");
+    }
+};
+
 // Camera::UndistortImage (include/myslam/camera.h, src/camera.cpp:36-48): cv::undistort(src, dst, K, distCoef) for one camera at one image
 // size, as Frontend::GrabStereoImage calls it on both images when Camera.bNeedUndistortion is 1 (src/frontend.cpp:47-51).  K = fx fy cx cy,
 // D = k1 k2 p1 p2.  src and dst may be the same image (the reference's in-place call).

@@ -550,6 +550,73 @@ int myslam_lk_track_batch(myslam_lk* h, const uint8_t* d_prev, const uint8_t* d_
                           const float* d_prev_pts, float* d_next_pts, const int32_t* d_counts, int cap, uint8_t* d_status, float* d_err);
 
 /* ------------------------------------------------------------------------------------------
+ * Multi-stream tracker — the work the reference does on EVERY frame, Frontend::Track() (src/frontend.cpp:86-122: constant-velocity
+ * prediction, TrackLastFrame :127-171, EstimateCurrentPose :176-276, the GOOD / BAD / LOST decision), for `streams` independent cameras
+ * of one image size and one calibration, advanced one frame per call with all tracker state in device memory and no host synchronisation.
+ * Per stream the handle holds: the last frame's feature table (<= cap features, cap <= 4096: pixel f32 x, y and a slot of the stream's landmark
+ * table or -1 = no live map point), the landmark table (<= landmark_cap: MapPoint::Pos() 3 x f64, mbIsOutlier), the reference key-frame's
+ * pose7 and frame id, last.rel = RelativePose() of the last frame and _mseRelativeMotion (4 x 4 f64, row-major), the next frame id, the
+ * status (0 INITING 1 TRACKING_GOOD 2 TRACKING_BAD 3 LOST, FrontendStatus), a frozen flag, and the previous left image with its LK pyramid
+ * (two buffers per stream that swap roles at every step: only the new image is down-sampled).
+ *
+ * myslam_tracker_step_batch (device pointers: image s at d_left + s * stride, row pitch `step`; asynchronous on the handle's stream, never
+ * synchronises, allocation-free, recordable between myslam_graph_begin / _end) does for every stream that is not frozen:
+ *   1. cur.rel = rel_motion * last.rel, Tcw = cur.rel * T(ref pose) (:90-93); LK start point of a feature = (float)world2pixel(pos, Tcw) when
+ *      its landmark is not an outlier, else its own pixel (:136-147).  f64, every product and sum rounded on its own in the order the hosts write
+ *      them (chain.py mm / mv / q_to_R / world2pixel = host/myslam_system.hpp): the start points are the hosts' bits;
+ *   2. LK last -> current, the arithmetic of myslam_lk_track (:150-153);
+ *   3. ordered compaction: features with status && landmark form the current frame's table in their old order (:156-170); those whose landmark is
+ *      not an outlier form the pose-only problem in that order, observations widened to f64 (:183-205);
+ *   4. the pose-only optimisation of myslam_pose_only_optimize (chi2 5.991, 4 rounds x 10 iterations, pre_optimize 0) from
+ *      pose7(cur.rel * T(ref)) (:176-260);
+ *   5. outlier features lose their landmark; the landmark is marked outlier and appended to the stream's outlier list (Map::AddOutlierMapPoint,
+ *      feature order) when frame id - ref frame id <= 2 (:261-270); cur.rel = T(pose) * T(ref)^-1; status from the inlier count (> tracking_good:
+ *      GOOD, > tracking_bad: BAD, else LOST, :97-110); rel_motion = cur.rel * last.rel^-1 (:122); last <- cur;
+ *   6. one myslam_tracker_result at d_results[s]: pose7(cur.rel * T(ref)), counts, status, frame id, and needs_host = the key-frame rule
+ *      (status == TRACKING_BAD, :112; or with kf_every > 0: status != LOST && frame id % kf_every == 0) or LOST.
+ * A stream with needs_host set is FROZEN: later steps leave its state, its stored image and d_results[s] untouched until myslam_tracker_set_frame.
+ * A stream that was never set is frozen.  status = MYSLAM_ERR_CAPACITY (needs_host 1, frozen) reports a stream whose tables did not fit
+ * (set_frame beyond cap / landmark_cap, an outlier list beyond 2 x cap); nothing is ever truncated.
+ * A step is 5 + (pyramid levels above 0) dependent launches (8 with the reference's max_level 3): head (image copy + rule 1), one per pyramid
+ * level, LK, compaction, pose-only, tail (rules 5 + 6).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct myslam_tracker myslam_tracker;
+typedef struct myslam_tracker_result {
+    double pose7[7];            /* Tcw of the frame, (qx qy qz qw tx ty tz) */
+    int32_t n_inliers;          /* features.size() - cntOutliers (:275) */
+    int32_t n_features;         /* current frame's feature table */
+    int32_t status;             /* FrontendStatus after the frame, or MYSLAM_ERR_CAPACITY */
+    int32_t frame_id;
+    int32_t needs_host;         /* 1: key-frame work or LOST; the stream is frozen */
+    int32_t reserved;
+} myslam_tracker_result;
+/* win .. min_eig_threshold as myslam_lk_create; tracking_good / tracking_bad = numFeatures.trackingGood / trackingBad */
+int myslam_tracker_create(myslam_tracker** out, int streams, int rows, int cols, int cap, int landmark_cap, double fx, double fy, double cx, double cy,
+                          int tracking_good, int tracking_bad, int win, int max_level, int max_iters, float eps, float min_eig_threshold);
+int myslam_tracker_destroy(myslam_tracker* h);
+int myslam_tracker_set_stream(myslam_tracker* h, void* hip_stream);
+/* Key-frame hand-off, host pointers, synchronous: uploads one stream's state (after StereoInit / InsertKeyFrame: the frame that becomes `last`)
+ * and unfreezes it; the outlier list is emptied.  feat_landmark[i] in [-1, n_landmarks).  prev_image (rows x cols, row pitch image_step) replaces
+ * the stored previous image and its pyramid — the reference's DeepLCD blurs a key-frame's image in place and the tracker then tracks FROM the
+ * blurred pixels (src/deeplcd.cpp:46); NULL keeps the image of the last step (MYSLAM_ERR_INVALID when the stream never saw one).
+ * n_feat > cap or n_landmarks > landmark_cap: MYSLAM_ERR_CAPACITY, and the stream's next result record says so (see above). */
+int myslam_tracker_set_frame(myslam_tracker* h, int stream, const float* feat_xy, const int32_t* feat_landmark, int n_feat, const double* landmark_pos,
+                             const uint8_t* landmark_outlier, int n_landmarks, const double* ref_pose7, int ref_frame_id, const double* last_rel16,
+                             const double* rel_motion16, int next_frame_id, int status, int kf_every, const uint8_t* prev_image, int image_step);
+/* downloads the same (arrays sized cap / landmark_cap by the caller; any pointer may be NULL) plus the frozen flag and the landmark slots the
+ * steps since set_frame marked outlier, in Map::AddOutlierMapPoint order (outlier_landmarks: 2 x cap entries) */
+int myslam_tracker_get_frame(myslam_tracker* h, int stream, float* feat_xy, int32_t* feat_landmark, int* n_feat, double* landmark_pos,
+                             uint8_t* landmark_outlier, int* n_landmarks, double* ref_pose7, int* ref_frame_id, double* last_rel16, double* rel_motion16,
+                             int* next_frame_id, int* status, int* kf_every, int* frozen, int32_t* outlier_landmarks, int* n_outlier_landmarks,
+                             uint8_t* prev_image, int image_step);
+int myslam_tracker_step_batch(myslam_tracker* h, const uint8_t* d_left, int step, size_t stride, myslam_tracker_result* d_results);
+/* kernel launches one myslam_tracker_step_batch enqueues */
+int myslam_tracker_launches_per_step(const myslam_tracker* h);
+/* the last step's LK problem of one stream (host pointers, cap entries each, synchronises): p0 = last frame's pixels, p1 = start points (rule 1),
+ * tracked / lk_status = LK's output; *n = 0 when the stream was frozen during that step */
+int myslam_tracker_debug_last_step(myslam_tracker* h, int stream, float* p0, float* p1, float* tracked, uint8_t* lk_status, int* n);
+
+/* ------------------------------------------------------------------------------------------
  * Lens undistortion — replaces Camera::UndistortImage (src/camera.cpp:36-48), which Frontend::GrabStereoImage runs on the left and the
  * right image before anything else when Camera.bNeedUndistortion is 1 (src/frontend.cpp:47-51): cv::undistort(src, dst, K, D) with
  * K = (fx, fy, cx, cy) widened from the camera's float members and D = (k1, k2, p1, p2) (read in src/system.cpp:118-138).
