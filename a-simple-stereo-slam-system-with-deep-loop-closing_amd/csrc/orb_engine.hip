@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "orb_plan.h"
+#include "resize_tab.h"
 
 namespace myslam_hip {
 
@@ -123,6 +124,8 @@ struct myslam_orb {
     uint16_t* d_order = nullptr;       // processing order of the descriptor kernel (tile order of the selected keys, orb_kernels.hip k_sel_order)
     uint32_t* d_octTab = nullptr;      // per-level oct-tree path-code / cell-index tables (see make_plan)
     uint32_t* d_stripTab = nullptr;    // per-strip head of the grid-FAST kernel (see make_plan, orb_plan.h)
+    uint32_t* d_resizeTab = nullptr;   // column and row records of the strip resize (resize_tab.h), per level that takes the strip form
+    size_t resizeColOff[MAXL] = {0}, resizeRowOff[MAXL] = {0}; bool resizeLvOk[MAXL] = {false};      // dword offsets into d_resizeTab of level l (written from level l - 1)
     // FAST path selection (orb_kernels.hip FastCtl): two [MAXL][4] counter blocks, the launch accumulates into one and reads the other
     uint32_t* d_fastStat = nullptr; int fastFlip = 0;
     // options (myslam_orb_set_option)
@@ -311,7 +314,26 @@ int myslam_orb::make_plan(int r, int c) {
         if ((rc = upload_table(d_stripTab, st.data(), st.size() * sizeof(uint32_t)))) return rc;
         P.stripTab = d_stripTab;
     }
-    full = P;
+    full = P;                          // (level_resize_args reads it)
+    {   // coordinate tables of the strip resize (resize_tab.h): what k_resize_strip derived per wave from the level sizes, for every level that takes the strip form
+        std::vector<uint32_t> rt;
+        std::vector<ResizeColRec> cr; std::vector<ResizeRowRec> rr;
+        for (int l = 1; l < nlevels; l++) {
+            const ResizeArgs a = level_resize_args(nullptr, l);
+            resizeLvOk[l] = resize_uses_strips(a);
+            if (!resizeLvOk[l]) continue;
+            resize_col_records(a.sw, a.dw, a.scale_x, (a.dw + 255) / 256 * 64, cr);
+            resize_row_records(a.sh, a.dh, a.scale_y, rr);
+            resizeColOff[l] = rt.size();                       // records are 32 / 16 bytes: every offset stays 32-byte aligned
+            rt.insert(rt.end(), reinterpret_cast<const uint32_t*>(cr.data()), reinterpret_cast<const uint32_t*>(cr.data() + cr.size()));
+            resizeRowOff[l] = rt.size();
+            rt.insert(rt.end(), reinterpret_cast<const uint32_t*>(rr.data()), reinterpret_cast<const uint32_t*>(rr.data() + rr.size()));
+            rt.resize((rt.size() + 7) & ~(size_t)7, 0u);
+        }
+        int rc = dev_alloc(d_resizeTab, rt.size());
+        if (rc) return rc;
+        if (!rt.empty() && (rc = upload_table(d_resizeTab, rt.data(), rt.size() * sizeof(uint32_t)))) return rc;
+    }
     // Detect(): level 0 only, budget = nfeatures (ORBextractor.cpp:1064-1065)
     det = P;
     det.nlevels = 1;
@@ -424,6 +446,7 @@ ResizeArgs myslam_orb::level_resize_args(uint8_t* base, int l) const {
     a.src0 = nullptr; a.spitch0 = 0; a.n0 = 0; a.sstride0 = 0;
     a.dst = base + P.lv[l].imgOff; a.dw = P.lv[l].w; a.dh = P.lv[l].h; a.dpitch = P.lv[l].pitch; a.dstride = P.pyrBytes;
     a.scale_x = 1. / ((double)a.dw / a.sw); a.scale_y = 1. / ((double)a.dh / a.sh);
+    if (d_resizeTab && resizeLvOk[l]) { a.colTab = d_resizeTab + resizeColOff[l]; a.rowTab = d_resizeTab + resizeRowOff[l]; }
     return a;
 }
 // operand tables of the matrix-core Gaussian: per level of the current plan and tap table (rebuilt when either changes)
@@ -608,7 +631,7 @@ int myslam_orb::ensure_stage(size_t imgBytes, size_t maskBytes, int cap) {
 }
 
 void myslam_orb::free_all() {
-    void* ptrs[] = {d_blurTab, d_fastStat, d_octTab, d_stripTab, d_pyr, d_blur, d_mask, d_cand, d_sort, d_candCount, d_selCount, d_status, d_sel, d_order, d_stageImg, d_stageMask,
+    void* ptrs[] = {d_blurTab, d_fastStat, d_octTab, d_stripTab, d_resizeTab, d_pyr, d_blur, d_mask, d_cand, d_sort, d_candCount, d_selCount, d_status, d_sel, d_order, d_stageImg, d_stageMask,
                     d_stageOut, d_stageKps2, d_stageKeep};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (aux) { (void)hipStreamSynchronize(aux); (void)hipStreamDestroy(aux); (void)hipEventDestroy(evFork); (void)hipEventDestroy(evJoin); aux = nullptr; }

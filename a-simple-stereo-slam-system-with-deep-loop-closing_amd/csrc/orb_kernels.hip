@@ -200,126 +200,132 @@ __device__ __forceinline__ void rc_block(const ResizeChain& c, int blk, int b) {
 
 __global__ __launch_bounds__(256) void k_resize_chain(ResizeChain c) { rc_block(c, blockIdx.x, blockIdx.y); }
 
-// K1b: the same arithmetic, register-only column strips.  Lane l owns destination columns 4l..4l+3 of a 256-column strip
-// and walks RS_R destination rows: x coordinates / weights are computed once, every needed source row is sampled once
-// (one unaligned 2-byte load per pixel = the two horizontal taps, v_perm + v_dot2_u32_u16 = the 11-bit interpolation) and
-// reused by the destination rows that share it (the OpenCV row cache), all row decisions are wave-uniform.
-constexpr int RS_R = 8;                      // destination rows per band (power of two)
-constexpr int RS_NB = 2;                     // bands a wave walks with one set of column coordinates (RS_NB * RS_R <= 64)
-constexpr int RS_MAXR = 12;                  // source rows a band may span: RS_R * scale_y + 2 (scale factors up to 1.25)
+// K1b: the same arithmetic, register-only column strips that roll down the image.  Lane l owns destination columns 4l..4l+3 of a
+// 256-column strip and walks a band of `band` destination rows.  Nothing that the plan's geometry fixes is computed here: the lane reads
+// its column record (source offset of its first column, byte-pair selectors, packed 11-bit weights: resize_tab.h, 32 bytes, two aligned
+// 16-byte loads) and the walk reads one 16-byte record per destination row with scalar loads through the constant address space (upper
+// source row, both-taps-on-it flag, b0 << 12, b1 << 12), the next row's record always in flight behind the current one.
+// The source rows of the band are consecutive (scale factors below 2 use every row), so the walk loads row after row, RS_PF rows ahead
+// of their use, each ONCE, and interpolates it horizontally ONCE (one unaligned 8-byte window per row = the byte pairs of all four columns,
+// v_perm + v_dot2_u32_u16 per pixel); it keeps only the interpolated rows r and r + 1 (the OpenCV row cache, two rows deep) and emits the
+// destination rows whose upper tap is r — a wave-uniform scalar decision, so a source row is followed by zero, one (or, for scale < 1,
+// several) stores.  Loads are unconditional from rows clamped to the band's last one: no branch sits between a load and its use, the
+// compiler's counted s_waitcnt keeps RS_PF - 1 rows in flight (as blur7_strip_wave does).
+// (before: bands of 8 rows that fetched 12 row slots and interpolated 10-11 of them — 1.5 loads and 1.31 horizontal passes per
+// destination row where the scale factor needs 1.2 —, ~84 registers of row cache, and the coordinates of 4 columns and 16 rows
+// recomputed through f64 by every wave of every launch.)
+#ifndef MYSLAM_RS_BAND                 // A/B builds (tools/build_variants.sh): destination rows a wave walks (>= the level's height = the whole strip)
+#define MYSLAM_RS_BAND 64
+#endif
+#ifndef MYSLAM_RS_PF
+#define MYSLAM_RS_PF 4
+#endif
+constexpr int RS_BAND = MYSLAM_RS_BAND;
+constexpr int RS_PF = MYSLAM_RS_PF;          // raw source rows in flight ahead of the horizontal pass
 
-__global__ __launch_bounds__(256) void k_resize_strip(ResizeArgs a, int nstrips, int nbands) {
+typedef uint32_t rs_u32x3 __attribute__((ext_vector_type(3)));
+typedef uint32_t rs_u32x2 __attribute__((ext_vector_type(2)));
+
+template <bool EXT>
+__device__ __forceinline__ void resize_strip_walk(const ResizeArgs& a, const uint8_t* src, int spitch, uint8_t* dst, int lane, int strip, int dy0, int dy1) {
+    typedef const uint32_t __attribute__((address_space(4))) * ConstU32;
+    typedef const uint8_t __attribute__((address_space(1))) * GlobalU8;
+    // a caller's rows (EXT) may start at any byte: the unaligned 8-byte window at sx[0].  Pyramid planes: 12 bytes from the dword-aligned
+    // address below sx[0], shifted into place with two v_alignbyte — an 8-byte load at BYTE alignment costs the texture addresser 32 cycles
+    // per wave instruction, the aligned 12-byte one 17.7 (tools/ta_probe.hip)
+    typedef std::conditional_t<EXT, rs_u32x2, rs_u32x3> Raw;
+    typedef Raw __attribute__((aligned(EXT ? 1 : 4))) RawMem;
+    const int dx4 = strip * 256 + 4 * lane;
+    // the lane's column record (groups past the image's last one repeat it; their lanes have left: k_resize_strip)
+    const uint4* crec = reinterpret_cast<const uint4*>(a.colTab) + 2 * (size_t)(strip * 64 + lane);
+    const uint4 c0 = crec[0], c1 = crec[1];
+    const uint32_t sel[4] = {0x0c010c00u, c0.y, c0.z, c0.w}, aw[4] = {c1.x, c1.y, c1.z, c1.w};
+    const uint32_t xoff = EXT ? c0.x : (c0.x & ~3u), bsh = c0.x & 3u;
+    const ConstU32 rt = (ConstU32)((uintptr_t)a.rowTab);
+    const int r0 = (int)rt[4 * dy0];                                 // the band's first source row
+    const int rlast = min((int)rt[4 * (dy1 - 1)] + 1, a.sh - 1);     // ... and its last: the loads past it re-read it
+    auto load_row = [&](int r) -> Raw {
+        // the row's address stays a scalar (SALU) and the lane's offset a 32-bit register: the load takes both as they are, no vector address arithmetic
+        uintptr_t rp = (uintptr_t)src + (size_t)min(r, rlast) * (size_t)spitch;
+        uint32_t xo = xoff;
+        asm("" : "+s"(rp));
+        asm volatile("" : "+v"(xo));                                    // (keeps the 32-bit offset's widening next to the load: hoisted out of the loop it becomes a 64-bit vector add per row)
+        // at the right border sx = sw-1 and the weight of sx+1 is 0 (OpenCV clamps fx there): the bytes past the row are never weighted
+        return *reinterpret_cast<const RawMem __attribute__((address_space(1)))*>((GlobalU8)rp + xo);
+    };
+    // horizontal pass: h[k] <- 16 x the row-cache value (<= 32640) of one source row at this lane's 4 columns (the low four bits are
+    // cleared instead of shifted out: the vertical step multiplies 24-bit operands and keeps bits 32..)
+    auto hrow = [&](const Raw& w, uint32_t* h) {
+        uint32_t x, y;
+        if constexpr (EXT) { x = w.x; y = w.y; }
+        else { x = __builtin_amdgcn_alignbyte(w.y, w.x, bsh); y = __builtin_amdgcn_alignbyte(w.z, w.y, bsh); }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const uint32_t pp = __builtin_amdgcn_perm(y, x, sel[k]);                              // (p0, p1) as two u16
+            h[k] = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, pp), __builtin_bit_cast(u16x2, aw[k]), 0u, false) & ~15u;
+        }
+    };
+    // vertical pass of one destination row.  (b * t) >> 16 with b <= 2048 and t <= 32640 is the high word of (b << 12) * (16 t): both
+    // factors fit 24 bits, so it is ONE full-rate v_mul_hi_u32_u24 (a 32-bit v_mul_lo_u32 runs at quarter rate).
+    auto emit = [&](int dy, uint32_t b0, uint32_t b1, const uint32_t* tA, const uint32_t* tB) {
+        uint32_t packed = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            uint32_t hA, hB;        // both factors < 2^24 by construction: the instruction itself, without the masks C++ needs to say so
+            asm("v_mul_hi_u32_u24 %0, %1, %2" : "=v"(hA) : "s"(b0), "v"(tA[k]));
+            asm("v_mul_hi_u32_u24 %0, %1, %2" : "=v"(hB) : "s"(b1), "v"(tB[k]));
+            const uint32_t v = (hA + hB + 2u) >> 2;                         // in [0, 255]: the weights of each axis sum to 2048
+            packed |= v << (8 * k);
+        }
+        uintptr_t dp = (uintptr_t)dst + (size_t)dy * (size_t)a.dpitch;
+        uint32_t xd = (uint32_t)dx4;
+        asm("" : "+s"(dp));
+        asm volatile("" : "+v"(xd));
+        *reinterpret_cast<uint32_t __attribute__((address_space(1)))*>((uint8_t __attribute__((address_space(1)))*)dp + xd) = packed;
+    };
+    Raw ring[RS_PF];
+#pragma unroll
+    for (int u = 0; u < RS_PF; u++) ring[u] = load_row(r0 + u);
+    // row records: cs / cb0 / cb1 = destination row dy, ns / nb0 / nb1 = row dy + 1 (the table ends with two spare records).  The records'
+    // both-taps-on-one-row flag needs no decision here: it is set only where the lower tap is clamped to the image's last row (the launcher
+    // admits scale factors >= 1 only: no destination row lies above source row 0), and there the clamped load has fetched that row again
+    int dy = dy0;
+    uint32_t cs = rt[4 * dy], cb0 = rt[4 * dy + 2], cb1 = rt[4 * dy + 3];
+    uint32_t ns = rt[4 * dy + 4], nb0 = rt[4 * dy + 6], nb1 = rt[4 * dy + 7];
+    uint32_t hA[4] = {0u, 0u, 0u, 0u}, hB[4];
+    // step j: hB <- source row r0 + j (its ring slot is refilled with row r0 + j + RS_PF), then the destination row whose upper tap is
+    // row r0 + j - 1 = hA, if there is one (none at j = 0; never two: scale factors >= 1 advance at least one source row per destination row)
+    // (the band's last destination row is written at step rlast - r0 + 1 at the latest: the bound only keeps a table that broke its promise from turning into an endless walk)
+    for (int base = 0; r0 + base <= rlast + 1; base += RS_PF) {
+#pragma unroll
+        for (int u = 0; u < RS_PF; u++) {
+            hrow(ring[u], hB);
+            ring[u] = load_row(r0 + base + u + RS_PF);
+            if ((int)cs == r0 + base + u - 1) {                              // uniform
+                emit(dy, cb0, cb1, hA, hB);
+                if (++dy >= dy1) return;
+                cs = ns; cb0 = nb0; cb1 = nb1;
+                ns = rt[4 * dy + 4]; nb0 = rt[4 * dy + 6]; nb1 = rt[4 * dy + 7];
+            }
+#pragma unroll
+            for (int k = 0; k < 4; k++) hA[k] = hB[k];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_resize_strip(ResizeArgs a, int nstrips, int nbands, int band) {
     MYSLAM_SIDE_PRIO();
     MYSLAM_BT(1);
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));   // scalar: row addressing goes to the SALU
-    const int ngroups = (nbands + RS_NB - 1) / RS_NB;                                              // a wave walks RS_NB consecutive bands of its strip
-    if (wid >= nstrips * ngroups) return;
-    const int strip = wid % nstrips, group = wid / nstrips;
+    if (wid >= nstrips * nbands) return;
+    const int strip = wid % nstrips, bi = wid / nstrips;
     const int b = blockIdx.z;
-    const int dx4 = strip * 256 + 4 * lane;
-    const bool has = dx4 < a.dw;
-    const bool ext = b < a.n0;                                   // block-uniform: level 0 read in place
-    const uint8_t* src = ext ? a.src0 + (size_t)b * a.sstride0 : a.src + (size_t)b * a.sstride;
-    const int spitch = ext ? a.spitch0 : a.spitch;
+    const int dy0 = bi * band, dy1 = min(dy0 + band, a.dh);
+    if (strip * 256 + 4 * lane >= a.dw) return;                  // lanes past the last column leave: no lane looks at another's registers
     uint8_t* dst = a.dst + (size_t)b * a.dstride;
-    int sx[4]; uint32_t aw[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        int c0, c1;
-        resize_coord(min(dx4 + k, a.dw - 1), a.scale_x, a.sw, true, sx[k], c0, c1);
-        aw[k] = (uint32_t)c0 | ((uint32_t)c1 << 16);
-    }
-    // One unaligned 8-byte load per source row covers the byte pairs of all four destination columns (their source columns span at
-    // most 3 scale_x + 2 <= 7 bytes; the launcher checks scale_x): the kernel is bound by the ISSUE of its gather loads, so four
-    // 2-byte loads per row cost four times as much.  The pairs are picked with byte permutes whose selectors are lane constants.
-    uint32_t selk[4];
-#pragma unroll
-    for (int k = 0; k < 4; k++) { const uint32_t o = (uint32_t)(sx[k] - sx[0]); selk[k] = 0x0c000c00u | ((o + 1u) << 16) | o; }
-    // the row coordinates of all RS_NB bands: lane k computes row dy0 + k once (RS_NB * RS_R <= 64), the loops read them back as scalars
-    const int gy0 = group * RS_NB * RS_R;
-    int ysy, yb0, yb1;
-    resize_coord(min(gy0 + (lane & (RS_NB * RS_R - 1)), a.dh - 1), a.scale_y, a.sh, false, ysy, yb0, yb1);
-    for (int bi = 0; bi < RS_NB; bi++) {
-        const int dy0 = gy0 + bi * RS_R, dy1 = min(dy0 + RS_R, a.dh), l0 = bi * RS_R;
-        if (dy0 >= a.dh) break;                                      // uniform
-        // every source row the band needs, fetched in ONE batch of loads (the kernel is latency-bound otherwise) and interpolated
-        // horizontally once (the OpenCV row cache, kept in registers)
-        const int rfirst = min(max(__builtin_amdgcn_readlane(ysy, l0), 0), a.sh - 1);
-        const int rlast = min(max(__builtin_amdgcn_readlane(ysy, l0 + dy1 - 1 - dy0) + 1, 0), a.sh - 1);
-        const int nrows = rlast - rfirst + 1;                        // <= RS_MAXR (checked by the launcher)
-        uint2 raw8[RS_MAXR];
-        if (ext) {                                                   // block-uniform: a caller's rows may start at any byte
-#pragma unroll
-            for (int rr = 0; rr < RS_MAXR; rr++) {
-                const uint8_t* row = src + (size_t)(rfirst + min(rr, nrows - 1)) * spitch;
-                raw8[rr] = make_uint2(0u, 0u);
-                // at the right border sx = sw-1 and the weight of sx+1 is 0 (OpenCV clamps fx there): the bytes past the row are never weighted
-                if (has && rr < nrows) __builtin_memcpy(&raw8[rr], row + sx[0], 8);
-            }
-        } else {
-            // pyramid planes: 12 bytes from the dword-aligned address below sx[0], shifted into place with two v_alignbyte — an 8-byte load
-            // at BYTE alignment costs the texture addresser 32 cycles per wave instruction, the aligned 12-byte one 17.7 (tools/ta_probe.hip)
-            uint32_t raw12[RS_MAXR][3];
-            const uint32_t xal = (uint32_t)sx[0] & ~3u, sh = (uint32_t)sx[0] & 3u;
-#pragma unroll
-            for (int rr = 0; rr < RS_MAXR; rr++) {
-                const uint8_t* row = src + (size_t)(rfirst + min(rr, nrows - 1)) * spitch;
-                raw12[rr][0] = raw12[rr][1] = raw12[rr][2] = 0u;
-                if (has && rr < nrows) __builtin_memcpy(raw12[rr], __builtin_assume_aligned(row + xal, 4), 12);
-            }
-#pragma unroll
-            for (int rr = 0; rr < RS_MAXR; rr++)
-                raw8[rr] = make_uint2(__builtin_amdgcn_alignbyte(raw12[rr][1], raw12[rr][0], sh), __builtin_amdgcn_alignbyte(raw12[rr][2], raw12[rr][1], sh));
-        }
-        // horizontal pass: raw[rr][k] <- 16 x the row-cache value (<= 32640) of source row rfirst + rr at this lane's 4 columns
-        // (the low four bits are cleared instead of shifted out: the vertical step multiplies 24-bit operands and keeps bits 32..)
-        // (a band of 8 destination rows at scale 1.2 spans 10 or 11 source rows, RS_MAXR = 12 is the bound for 1.25: the rows a band does not
-        // have are skipped by a scalar branch — the vertical pass below never reads them — instead of being interpolated from zeros)
-        uint32_t raw[RS_MAXR][4];
-#pragma unroll
-        for (int rr = 0; rr < RS_MAXR; rr++) {
-            if (rr >= RS_R + 1 && rr >= nrows) {                          // wave-uniform; rows 0 .. RS_R always exist for scale >= 1
-#pragma unroll
-                for (int k = 0; k < 4; k++) raw[rr][k] = 0u;
-                continue;
-            }
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const uint32_t pp = __builtin_amdgcn_perm(raw8[rr].y, raw8[rr].x, selk[k]);       // (p0, p1) as two u16
-                raw[rr][k] = __builtin_amdgcn_udot2(__builtin_bit_cast(u16x2, pp), __builtin_bit_cast(u16x2, aw[k]), 0u, false) & ~15u;
-            }
-        }
-        // vertical pass: walk the source rows statically (the row cache stays in registers, no run-time register indexing) and emit the
-        // destination rows whose upper source row is the current one — at most one per source row for scale >= 1; the row coordinates
-        // are wave-uniform scalars.  (b * t) >> 16 with b <= 2048 and t <= 32640 is the high word of (b << 12) * (16 t): both factors
-        // fit 24 bits, so it is ONE full-rate v_mul_hi_u32_u24 (a 32-bit v_mul_lo_u32 runs at quarter rate).
-        int dy = dy0;
-        int sy = __builtin_amdgcn_readlane(ysy, l0);
-        uint32_t b0 = (uint32_t)__builtin_amdgcn_readlane(yb0, l0) << 12, b1 = (uint32_t)__builtin_amdgcn_readlane(yb1, l0) << 12;
-#pragma unroll
-        for (int rr = 0; rr < RS_MAXR; rr++) {
-            while (dy < dy1 && min(max(sy, 0), a.sh - 1) - rfirst == rr) {          // uniform
-                const bool same = min(max(sy + 1, 0), a.sh - 1) - rfirst == rr;     // clamped at an image border: both taps on this row
-                uint32_t packed = 0;
-#pragma unroll
-                for (int k = 0; k < 4; k++) {
-                    const uint32_t tA = raw[rr][k], tB = same ? raw[rr][k] : raw[rr + 1 < RS_MAXR ? rr + 1 : rr][k];
-                    uint32_t hA, hB;        // both factors < 2^24 by construction: the instruction itself, without the masks C++ needs to say so
-                    asm("v_mul_hi_u32_u24 %0, %1, %2" : "=v"(hA) : "s"(b0), "v"(tA));
-                    asm("v_mul_hi_u32_u24 %0, %1, %2" : "=v"(hB) : "s"(b1), "v"(tB));
-                    const uint32_t v = (hA + hB + 2u) >> 2;                         // in [0, 255]: the weights of each axis sum to 2048
-                    packed |= v << (8 * k);
-                }
-                if (has) *reinterpret_cast<uint32_t*>(dst + (size_t)dy * a.dpitch + dx4) = packed;
-                dy++;
-                if (dy < dy1) {
-                    sy = __builtin_amdgcn_readlane(ysy, l0 + dy - dy0);
-                    b0 = (uint32_t)__builtin_amdgcn_readlane(yb0, l0 + dy - dy0) << 12; b1 = (uint32_t)__builtin_amdgcn_readlane(yb1, l0 + dy - dy0) << 12;
-                }
-            }
-        }
-    }
+    if (b < a.n0) resize_strip_walk<true>(a, a.src0 + (size_t)b * a.sstride0, a.spitch0, dst, lane, strip, dy0, dy1);      // block-uniform: level 0 read in place
+    else resize_strip_walk<false>(a, a.src + (size_t)b * a.sstride, a.spitch, dst, lane, strip, dy0, dy1);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2951,7 +2957,7 @@ void launch_ingest_clear(const uint8_t* src, int rows, int cols, int step, size_
 // ------------------------------------------------------------------------------------------------
 // launch helpers (called from orb_engine.hip)
 // ------------------------------------------------------------------------------------------------
-bool resize_uses_strips(const ResizeArgs& a) { return (double)RS_R * a.scale_y + 2.0 <= (double)RS_MAXR && a.scale_x <= 1.6; }
+bool resize_uses_strips(const ResizeArgs& a) { return a.scale_y >= 1.0 && a.scale_y <= 1.25 && a.scale_x <= 1.6; }
 
 bool resize_is_little(const ResizeArgs& a, int batch) { return a.n0 == 0 && (size_t)batch * a.dw * a.dh < (size_t)1500000; }
 
@@ -3000,9 +3006,9 @@ void launch_resize(const ResizeArgs& a, int batch, hipStream_t s) {
     // (tests/test_gpu_fallbacks.py); images read in place (n0 > 0: batched calls only) need the strip form.
     const bool little = resize_is_little(a, batch);
     if (resize_uses_strips(a) && !little) {
-        const int nstrips = (a.dw + 255) / 256, nbands = (a.dh + RS_R - 1) / RS_R;
-        const int ngroups = (nbands + RS_NB - 1) / RS_NB;
-        hipLaunchKernelGGL(k_resize_strip, dim3((nstrips * ngroups + 3) / 4, 1, batch), dim3(256), 0, s, a, nstrips, nbands);
+        if (!a.colTab || !a.rowTab) { fprintf(stderr, "myslam_hip: launch_resize: the plan holds no resize tables for this level\n"); abort(); }      // a missing table is a bug of make_plan, never a reason for the slower kernel
+        const int nstrips = (a.dw + 255) / 256, band = RS_BAND, nbands = (a.dh + band - 1) / band;
+        hipLaunchKernelGGL(k_resize_strip, dim3((nstrips * nbands + 3) / 4, 1, batch), dim3(256), 0, s, a, nstrips, nbands, band);
         return;
     }
     dim3 grid((a.dw + 255) / 256, (a.dh + 3) / 4, batch);

@@ -65,6 +65,10 @@ struct ResizeArgs {
     const uint8_t* src0 = nullptr; int spitch0 = 0, n0 = 0; size_t sstride0 = 0;      // images b < n0 read their source plane here (level 0 in place)
     uint8_t* dst; int dw, dh, dpitch; size_t dstride;
     double scale_x, scale_y;                     // 1 / ((double)dsize / ssize), as cv::resize computes it
+    // coordinate tables of the strip form (k_resize_strip; resize_tab.h), built with the plan and owned by the handle: 32 bytes per group of four
+    // destination columns (whole strips of 64 groups), 16 bytes per destination row.  They depend on the level's source and destination SIZE only:
+    // base and pitch of the source stay arguments (level 0 is read in place).  Null = the level does not take the strip form
+    const uint32_t* colTab = nullptr; const uint32_t* rowTab = nullptr;
 };
 
 struct BlurArgs {
