@@ -22,13 +22,11 @@
 #include <vector>
 
 #include "common.h"
+#include "orb_launch.h"
 #include "orb_plan.h"
 #include "../host/myslam_caffe.hpp"
 
 namespace myslam_hip {
-
-void launch_blur(const BlurArgs& a, int batch, hipStream_t s);
-void gauss_q8(int kind, int q[7]);
 
 constexpr int IN_H = 120, IN_W = 160;
 // the network input lives in a zero-padded plane (conv1 pad 4 + what the clipped pool windows still touch): no bounds tests
@@ -1091,7 +1089,7 @@ int myslam_lcd::describe(uint8_t* d_imgs, int batch, int r, int c, int step, siz
             BlurArgs a{};                                 // GaussianBlur(img, img, Size(7,7), 0)  deeplcd.cpp:46  (src0 / n0 = 0: no in-place images)
             a.src = d_imgs; a.dst = d_blur; a.w = c; a.h = r; a.spitch = step; a.dpitch = blurPitch; a.sstride = stride; a.dstride = blurBytes;
             gauss_q8(1, a.q);
-            launch_blur(a, batch, stream);
+            launch_blur_levels(&a, 1, batch, stream);
             for (int b = 0; b < batch; b++)               // the reference mutates the caller's pixels
                 MYSLAM_HIP_CHECK(hipMemcpy2DAsync(d_imgs + (size_t)b * stride, step, d_blur + (size_t)b * blurBytes, blurPitch, c, r,
                                                   hipMemcpyDeviceToDevice, stream));

@@ -14,41 +14,11 @@
 #include <vector>
 
 #include "common.h"
+#include "orb_launch.h"
 #include "orb_plan.h"
 #include "resize_tab.h"
 
 namespace myslam_hip {
-
-void launch_resize(const ResizeArgs& a, int batch, hipStream_t s);
-void launch_resize_chain(const ResizeArgs* lv, int n, int batch, hipStream_t s);
-bool resize_is_little(const ResizeArgs& a, int batch);
-int resize_chain_max();
-int pyr_head_levels();
-void launch_pyr_head(const ResizeArgs* lv, int n, int rows, int cols, uint8_t* dst0, int dpitch0, size_t dstride0, int b0, int batch,
-                     uint32_t* p0, int n0, uint32_t* p1, int n1, uint32_t* p2, int n2, uint32_t* p3, int n3, hipStream_t s);
-void launch_blur(const BlurArgs& a, int batch, hipStream_t s);
-bool blur_uses_strips(const BlurArgs& a);
-bool resize_uses_strips(const ResizeArgs& a);
-void launch_fast(const OrbPlan& P, const uint8_t* pyr, size_t pyrStride, const uint8_t* maskPyr, uint32_t* cand,
-                 int32_t* candCount, const uint32_t* statPrev, uint32_t* statCur, int forceMode, int batch, hipStream_t s);
-bool launch_octree(const OrbPlan& P, const uint32_t* cand, const int32_t* candCount, uint32_t* sortbuf, const uint32_t* octTab, uint32_t* selOut,
-                   int32_t* selCount, int32_t* status, int batch, uint16_t* order, hipStream_t s, const BlurArgs* blurLv, int nBlur);
-bool describe_uses_tile_order(bool have_order, int detectOnly, int batch);
-void launch_describe(const OrbPlan& P, const uint8_t* pyr, const uint8_t* blur, size_t pyrStride, const uint32_t* selOut,
-                     const int32_t* selCount, myslam_keypoint* kps, uint8_t* desc, int32_t* counts, int32_t* status,
-                     int cap, int detectOnly, int batch, uint16_t* order, bool order_ready, int blocks_per_cu, hipStream_t s);
-void launch_screen(const OrbPlan& P, const uint8_t* pyr, myslam_keypoint* kin, int n, myslam_keypoint* kout, uint8_t* keep,
-                   hipStream_t s);
-void launch_calc_desc(const OrbPlan& P, const uint8_t* blur, const myslam_keypoint* kps, int n, uint8_t* desc, hipStream_t s);
-void launch_unpack_cands(const uint32_t* cand, int n, int32_t* xs, int32_t* ys, int32_t* sc, hipStream_t s);
-void launch_blur_levels(const BlurArgs* lv, int n, int batch, hipStream_t s);
-bool blur_mfma_tables(int w, int h, const int q[7], std::vector<uint4>& tab, size_t& offH, size_t& offV);
-void blur_mfma_ident(std::vector<uint4>& tab, size_t& offI);
-void launch_zero_u32(uint32_t* p0, int n0, uint32_t* p1, int n1, uint32_t* p2, int n2, uint32_t* p3, int n3, hipStream_t s);
-void launch_ingest_clear(const uint8_t* src, int rows, int cols, int step, size_t sstride, uint8_t* dst, int dpitch, size_t dstride, int batch,
-                         uint32_t* p0, int n0, uint32_t* p1, int n1, uint32_t* p2, int n2, uint32_t* p3, int n3, hipStream_t s);
-void launch_ingest(const uint8_t* src, int rows, int cols, int step, size_t sstride, uint8_t* dst, int dpitch,
-                   size_t dstride, int batch, hipStream_t s);
 
 static inline int cv_round(float v) { return (int)lrintf(v); }
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
@@ -62,25 +32,6 @@ void gauss_q8(int kind, int q[7]) {
     double g[7], sum = 0;
     for (int i = 0; i < 7; i++) { double x = i - 3; g[i] = exp(-(x * x) / 8.0); sum += g[i]; }
     for (int i = 0; i < 7; i++) q[i] = (int)lrint(g[i] / sum * 256.0);
-}
-
-// cv::resize INTER_LINEAR coefficient tables (OpenCV 3.4 resize.cpp: fx = (dx+0.5)*scale-0.5, 11-bit weights)
-[[maybe_unused]] static void resize_tables(int ssize, int dsize, bool is_x, std::vector<int32_t>& ofs, std::vector<int16_t>& coef) {
-    const double inv_scale = (double)dsize / ssize;
-    const double scale = 1. / inv_scale;
-    ofs.resize(dsize); coef.resize(2 * dsize);
-    for (int d = 0; d < dsize; d++) {
-        float f = (float)((d + 0.5) * scale - 0.5);
-        int s = (int)floorf(f);
-        f -= s;
-        if (is_x) {
-            if (s < 0) { f = 0; s = 0; }
-            if (s >= ssize - 1) { f = 0; s = ssize - 1; }
-        }
-        ofs[d] = s;
-        coef[2 * d] = (int16_t)cv_round((1.f - f) * 2048.f);
-        coef[2 * d + 1] = (int16_t)cv_round(f * 2048.f);
-    }
 }
 
 template <typename T>
@@ -144,10 +95,24 @@ struct myslam_orb {
     // `gen` changes whenever something a captured graph depends on does (buffers, plan, options, taps, streams): stale graphs are dropped.
     // (the captured hipGraph_t is kept alive beside its executable: on ROCm 7.2 an executable whose source graph has been destroyed reads
     // freed kernel-argument memory as soon as the heap reuses it — found as pixel bytes landing in the candidate counters)
-    struct HostGraph { hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr; uint64_t gen = 0; int rows = 0, cols = 0, step = 0, dcap = 0, calls = 0; bool mask = false; };
+    struct HostGraph {
+        static constexpr int kStayEager = -1000000;      // `calls` of a key that could not be captured or replayed: it runs eagerly from then on
+        hipGraphExec_t exec = nullptr; hipGraph_t graph = nullptr; uint64_t gen = 0; int rows = 0, cols = 0, step = 0, dcap = 0, calls = 0; bool mask = false;
+        void reset(bool stayEager = false) {
+            if (exec) (void)hipGraphExecDestroy(exec);
+            if (graph) (void)hipGraphDestroy(graph);
+            if (stayEager) { exec = nullptr; graph = nullptr; calls = kStayEager; }      // the key stays
+            else *this = HostGraph();
+        }
+        bool matches(uint64_t g, int r, int c, int st, int dc, bool m) const { return gen == g && rows == r && cols == c && step == st && dcap == dc && mask == m; }
+        void rekey(uint64_t g, int r, int c, int st, int dc, bool m) { reset(); gen = g; rows = r; cols = c; step = st; dcap = dc; mask = m; }
+    };
     HostGraph hostGraph[2][2];           // [detectOnly][fastFlip]
     uint64_t gen = 1;
-    struct Clear { uint32_t* p[4]; int n[4]; } clr{{nullptr, nullptr, nullptr, nullptr}, {0, 0, 0, 0}};      // counters the next level-0 ingest clears (run_batch -> build_pyramids)
+    // counters the call's first launch clears (run_batch -> build_pyramids).  Taken exactly once: the list holds the caller's d_stat pointer, which
+    // must not outlive the call, and every later launch gets the empty list
+    ZeroArgs clr{};
+    ZeroArgs take_clear() { const ZeroArgs z = clr; clr = ZeroArgs{}; return z; }
     hipStream_t hostStream = nullptr;    // the host-pointer calls' stream when the handle has none (the legacy NULL stream cannot be captured)
     uint8_t* h_pin = nullptr; size_t pinBytes = 0;      // pinned staging: image, mask, counts, key-points, descriptors
     int ensure_pin(size_t bytes);
@@ -159,9 +124,18 @@ struct myslam_orb {
     uint8_t* d_stageOut = nullptr; size_t stageOutBytes = 0, stageDescOff = 0;      // the block d_stageCounts / d_stageKps / d_stageDesc point into
 
     int make_tables();
+    void level_size(int l, int r, int c, int& w, int& h) const {          // ORBextractor.cpp:1237-1238
+        w = cv_round((float)c * invScale[l]); h = cv_round((float)r * invScale[l]);
+    }
     int make_plan(int r, int c);
     int ensure(int batch, int r, int c, bool needMask);
     int ensure_stage(size_t imgBytes, size_t maskBytes, int cap);
+    int ensure_fast_stat();
+    // level 0 read in place (orb_plan.h ext0): both plans, set by every entry point before it builds a pyramid
+    void set_in_place(const uint8_t* p, size_t stride, int pitch, int n0) {
+        full.ext0 = det.ext0 = p; full.ext0Stride = det.ext0Stride = stride; full.ext0Pitch = det.ext0Pitch = pitch; full.ext0N = det.ext0N = n0;
+    }
+    int stage_pyramid(const uint8_t* img, int r, int c, int step, const uint8_t* mask, int ncap);
     int build_pyramids(const uint8_t* d_imgs, int batch, int step, size_t stride, const uint8_t* d_masks, int nlev);
     ResizeArgs level_resize_args(uint8_t* base, int l) const;
     BlurArgs level_blur_args(int l) const;
@@ -195,14 +169,24 @@ int myslam_orb::make_tables() {
 
 static int ceil_log2(int v) { int b = 0; while ((1 << b) < v) b++; return b; }
 
+// root nodes of a level's oct-tree, the rounded aspect ratio of its FAST area (ORBextractor.cpp:590); 0 = the level is too small to have one
+static int level_nini(int w, int h) {
+    const int bx = w - EDGE_THRESHOLD + 3 - MIN_BORDER, by = h - EDGE_THRESHOLD + 3 - MIN_BORDER;
+    return bx > 0 && by > 0 ? (int)roundf((float)bx / (float)by) : 0;
+}
+// node-list capacity of a level with budget N; the list lives in LDS, which bounds it
+static int node_cap(int N, int nIni, int& cap) {
+    cap = (std::max(N + 4, 4 * nIni + 4) + 3) & ~3;
+    return cap > 4092 ? MYSLAM_ERR_UNSUPPORTED : MYSLAM_OK;
+}
+
 int myslam_orb::make_plan(int r, int c) {
     OrbPlan P{};
     P.nlevels = nlevels; P.rows = r; P.cols = c; P.iniTh = iniTh; P.minTh = minTh;
     size_t imgOff = 0, keyOff = 0; int cellBase = 0, outBase = 0, stripBase = 0;
     for (int l = 0; l < nlevels; l++) {
         LevelGeom& g = P.lv[l];
-        g.w = cv_round((float)c * invScale[l]);                 // ORBextractor.cpp:1237-1238
-        g.h = cv_round((float)r * invScale[l]);
+        level_size(l, r, c, g.w, g.h);
         if (g.w < 1 || g.h < 1) return MYSLAM_ERR_UNSUPPORTED;
         g.pitch = (int)align_up(g.w, 64);
         g.maxBX = g.w - EDGE_THRESHOLD + 3; g.maxBY = g.h - EDGE_THRESHOLD + 3;
@@ -216,7 +200,7 @@ int myslam_orb::make_plan(int r, int c) {
         g.cellBase = cellBase; cellBase += g.nCols * g.nRows;
         g.stripBase = stripBase; stripBase += g.nRows * ((g.nCols + 3) / 4);
         g.N = nPerLevel[l];
-        g.nIni = (int)roundf((float)(g.maxBX - MIN_BORDER) / (g.maxBY - MIN_BORDER));   // :590
+        g.nIni = level_nini(g.w, g.h);
         if (g.nIni < 1 || g.nIni > 64) return MYSLAM_ERR_UNSUPPORTED;
         g.hX = (float)(g.maxBX - MIN_BORDER) / g.nIni;                                  // :592
         const int rootW = (int)ceilf(g.hX) + 2, H = g.maxBY - MIN_BORDER;
@@ -225,8 +209,7 @@ int myslam_orb::make_plan(int r, int c) {
         while (g.sortDepth + 1 <= g.ndepth && (g.nIni << (2 * (g.sortDepth + 1))) <= 1024) g.sortDepth++;
         // a cell interior of a x b pixels holds at most ceil(a/2)*ceil(b/2) strict 8-neighbour maxima: no overflow possible
         g.keyCap = (int)std::min<size_t>(262143, std::max<size_t>(256, (size_t)((g.w + 1) / 2) * ((g.h + 1) / 2)));
-        g.nodeCap = (std::max(g.N + 4, 4 * g.nIni + 4) + 3) & ~3;
-        if (g.nodeCap > 4092) return MYSLAM_ERR_UNSUPPORTED;          // oct-tree node list lives in LDS
+        if (node_cap(g.N, g.nIni, g.nodeCap)) return MYSLAM_ERR_UNSUPPORTED;
         g.outBase = outBase; outBase += g.nodeCap;
         g.scale = scale[l];
         g.scaledPatch = (float)(int)(PATCH_SIZE * scale[l]);                            // :891
@@ -340,8 +323,7 @@ int myslam_orb::make_plan(int r, int c) {
     det.ncells = P.lv[0].nCols * P.lv[0].nRows;
     det.nstrips = P.lv[0].nRows * ((P.lv[0].nCols + 3) / 4);
     det.lv[0].N = nfeatures;
-    det.lv[0].nodeCap = (std::max(nfeatures + 4, 4 * P.lv[0].nIni + 4) + 3) & ~3;
-    if (det.lv[0].nodeCap > 4092) return MYSLAM_ERR_UNSUPPORTED;
+    if (node_cap(nfeatures, P.lv[0].nIni, det.lv[0].nodeCap)) return MYSLAM_ERR_UNSUPPORTED;
     det.lv[0].outBase = 0;
     det.totalOut = det.lv[0].nodeCap;
     rows = r; cols = c;
@@ -391,26 +373,17 @@ int myslam_orb::build_pyramids(const uint8_t* d_imgs, int batch, int step, size_
         int l = 1;
         // a launch with little work (a live stream's frame): ingest, counters and the first levels of all images in ONE launch (k_pyr_head)
         const int nhead = std::min(pyr_head_levels(), nlev - 1);
-        if (nhead >= 1 && batch > n0 && (size_t)batch * P.lv[1].w * P.lv[1].h < (size_t)1500000) {
+        if (nhead >= 1 && batch > n0 && resize_is_little(level_resize_args(base, 1), batch)) {
             ScopedProf sp(P_RESIZE, stream);
             ResizeArgs grp[3];
             for (int j = 0; j < nhead; j++) grp[j] = level_resize_args(base, 1 + j);
             grp[0].src = src; grp[0].spitch = step; grp[0].sstride = stride;      // level 1 (and the levels above, through it) from the caller's buffers
-            const bool c0 = pass == 0 && clr.n[0] > 0;
-            launch_pyr_head(grp, nhead, P.rows, P.cols, base + P.lv[0].imgOff, P.lv[0].pitch, P.pyrBytes, n0, batch,
-                            c0 ? clr.p[0] : nullptr, c0 ? clr.n[0] : 0, c0 ? clr.p[1] : nullptr, c0 ? clr.n[1] : 0, c0 ? clr.p[2] : nullptr,
-                            c0 ? clr.n[2] : 0, c0 ? clr.p[3] : nullptr, c0 ? clr.n[3] : 0, stream);
-            if (c0) clr.n[0] = 0;
+            // (the call's first launch also clears the per-call counters, run_batch: take_clear() is empty after that)
+            launch_pyr_head(grp, nhead, P.rows, P.cols, base + P.lv[0].imgOff, P.lv[0].pitch, P.pyrBytes, n0, batch, take_clear(), stream);
             l = 1 + nhead;
         } else if (batch > n0) {
-            uint8_t* dst0 = base + (size_t)n0 * P.pyrBytes + P.lv[0].imgOff;
-            if (pass == 0 && clr.n[0] > 0) {       // the call's first launch also clears the per-call counters (run_batch)
-                launch_ingest_clear(src + (size_t)n0 * stride, P.rows, P.cols, step, stride, dst0, P.lv[0].pitch, P.pyrBytes, batch - n0,
-                                    clr.p[0], clr.n[0], clr.p[1], clr.n[1], clr.p[2], clr.n[2], clr.p[3], clr.n[3], stream);
-                clr.n[0] = 0;
-            } else {
-                launch_ingest(src + (size_t)n0 * stride, P.rows, P.cols, step, stride, dst0, P.lv[0].pitch, P.pyrBytes, batch - n0, stream);
-            }
+            launch_ingest(src + (size_t)n0 * stride, P.rows, P.cols, step, stride, base + (size_t)n0 * P.pyrBytes + P.lv[0].imgOff, P.lv[0].pitch,
+                          P.pyrBytes, batch - n0, take_clear(), stream);
         }
         for (; l < nlev;) {                                    // ComputePyramid, ORBextractor.cpp:1235-1246
             ScopedProf sp(P_RESIZE, stream);
@@ -503,10 +476,7 @@ int myslam_orb::run_batch(const uint8_t* d_imgs, int batch, int r, int c, int st
     if (optBlurMfma && !detectOnly && (rc = ensure_blur_tables())) return rc;
     const OrbPlan& P = detectOnly ? det : full;
     int32_t* stat = d_stat ? d_stat : d_status;
-    if (!d_fastStat) {
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&d_fastStat, sizeof(uint32_t) * 2 * MAXL * 4));
-        MYSLAM_HIP_CHECK(hipMemsetAsync(d_fastStat, 0, sizeof(uint32_t) * 2 * MAXL * 4, stream));
-    }
+    if ((rc = ensure_fast_stat())) return rc;
     // candidate / selection counters, status words and the FAST statistics block this call accumulates into (run_fast) are cleared by the
     // call's first launch, the level-0 ingest (build_pyramids)
     clr = {{reinterpret_cast<uint32_t*>(d_candCount), reinterpret_cast<uint32_t*>(d_selCount), reinterpret_cast<uint32_t*>(stat), d_fastStat + (size_t)fastFlip * MAXL * 4},
@@ -525,12 +495,10 @@ int myslam_orb::run_batch(const uint8_t* d_imgs, int batch, int r, int c, int st
             if (full.nlevels > 1) ok = ok && resize_uses_strips(level_resize_args(d_pyr, 1));
             if (ok) n0 = batch - 1;
         }
-        full.ext0 = det.ext0 = d_imgs; full.ext0Stride = det.ext0Stride = stride; full.ext0Pitch = det.ext0Pitch = step; full.ext0N = det.ext0N = n0;
+        set_in_place(d_imgs, stride, step, n0);
     }
     if (stop == 1) {
-        launch_ingest_clear(d_imgs, full.rows, full.cols, step, stride, d_pyr + full.lv[0].imgOff, full.lv[0].pitch, full.pyrBytes, batch,
-                            clr.p[0], clr.n[0], clr.p[1], clr.n[1], clr.p[2], clr.n[2], clr.p[3], clr.n[3], stream);
-        clr.n[0] = 0;                      // the list holds the caller's d_stat pointer: it must not outlive the call (build_pyramids resets it too)
+        launch_ingest(d_imgs, full.rows, full.cols, step, stride, d_pyr + full.lv[0].imgOff, full.lv[0].pitch, full.pyrBytes, batch, take_clear(), stream);
         return MYSLAM_OK;
     }
     if ((rc = build_pyramids(d_imgs, batch, step, stride, d_masks, P.nlevels))) return rc;
@@ -606,7 +574,26 @@ int myslam_orb::ensure_pin(size_t bytes) {
 
 void myslam_orb::drop_host_graphs() {
     for (auto& row : hostGraph)
-        for (auto& g : row) { if (g.exec) (void)hipGraphExecDestroy(g.exec); if (g.graph) (void)hipGraphDestroy(g.graph); g = HostGraph(); }
+        for (auto& g : row) g.reset();
+}
+
+int myslam_orb::ensure_fast_stat() {
+    if (d_fastStat) return MYSLAM_OK;
+    MYSLAM_HIP_CHECK(hipMalloc((void**)&d_fastStat, sizeof(uint32_t) * 2 * MAXL * 4));
+    MYSLAM_HIP_CHECK(hipMemsetAsync(d_fastStat, 0, sizeof(uint32_t) * 2 * MAXL * 4, stream));
+    return MYSLAM_OK;
+}
+
+// single-image entry points (Screen / CalcDescriptors, the debug taps): stage the caller's image (and mask) and build its pyramid — nothing is read in place
+int myslam_orb::stage_pyramid(const uint8_t* img, int r, int c, int step, const uint8_t* mask, int ncap) {
+    const size_t bytes = (size_t)r * step;
+    int rc = ensure(1, r, c, mask != nullptr);
+    if (rc) return rc;
+    if ((rc = ensure_stage(bytes, mask ? bytes : 0, ncap))) return rc;
+    MYSLAM_HIP_CHECK(hipMemcpyAsync(d_stageImg, img, bytes, hipMemcpyHostToDevice, stream));
+    if (mask) MYSLAM_HIP_CHECK(hipMemcpyAsync(d_stageMask, mask, bytes, hipMemcpyHostToDevice, stream));
+    set_in_place(nullptr, 0, 0, 0);
+    return build_pyramids(d_stageImg, 1, step, bytes, mask ? d_stageMask : nullptr, nlevels);
 }
 
 int myslam_orb::ensure_stage(size_t imgBytes, size_t maskBytes, int cap) {
@@ -736,9 +723,9 @@ int myslam_orb_max_keypoints_for(const myslam_orb* h, int rows, int cols) {
     // exact bound for this image size: level l returns at most max(N_l + 3, 4 nIni_l) nodes, nIni_l = round of the level's aspect ratio
     int s = 0, first = 0;
     for (int l = 0; l < h->nlevels; l++) {
-        const int w = cv_round((float)cols * h->invScale[l]), hh = cv_round((float)rows * h->invScale[l]);
-        const int bx = w - EDGE_THRESHOLD + 3 - MIN_BORDER, by = hh - EDGE_THRESHOLD + 3 - MIN_BORDER;
-        const int nIni = (bx > 0 && by > 0) ? std::max(1, (int)roundf((float)bx / (float)by)) : 1;
+        int w, hh;
+        h->level_size(l, rows, cols, w, hh);
+        const int nIni = std::max(1, level_nini(w, hh));
         s += std::max(h->nPerLevel[l] + 3, 4 * nIni);
         if (l == 0) first = std::max(h->nfeatures + 3, 4 * nIni);
     }
@@ -763,7 +750,6 @@ static int host_extract(myslam_orb* h, const uint8_t* img, int rows, int cols, i
     if (!h || !n) return MYSLAM_ERR_INVALID;
     *n = 0;
     if (!img || rows <= 0 || cols <= 0) return MYSLAM_OK;            // reference: silent return on empty input (:924, :990)
-    if (detectOnly && !mask) { /* Detect() returns on empty mask (:990); NULL here means "all 255" */ }
     if (step < cols || cap <= 0 || !kps || (!detectOnly && !desc)) return MYSLAM_ERR_INVALID;
     if (mask && mask_step < cols) return MYSLAM_ERR_INVALID;
     int rc = h->ensure(1, rows, cols, mask != nullptr);          // plan first: the exact slot count depends on the image shape
@@ -804,30 +790,25 @@ static int host_extract(myslam_orb* h, const uint8_t* img, int rows, int cols, i
     // a graph is replayable when nothing outside the capture takes part: no profiling events, no caller events, a complete call
     const bool graphable = !prof_is_on() && !h->evUserGate && !h->evUserFast && h->optStopAfter == 0;
     myslam_orb::HostGraph& G = h->hostGraph[detectOnly ? 1 : 0][h->fastFlip & 1];
-    const bool same = G.gen == h->gen && G.rows == rows && G.cols == cols && G.step == step && G.dcap == dcap && G.mask == (mask != nullptr);
-    if (!same) { if (G.exec) (void)hipGraphExecDestroy(G.exec); if (G.graph) (void)hipGraphDestroy(G.graph); G = myslam_orb::HostGraph(); G.gen = h->gen; G.rows = rows; G.cols = cols; G.step = step; G.dcap = dcap; G.mask = mask != nullptr; }
+    if (!G.matches(h->gen, rows, cols, step, dcap, mask != nullptr)) G.rekey(h->gen, rows, cols, step, dcap, mask != nullptr);
     bool done = false;
     if (graphable && G.exec) {
         if (hipGraphLaunch(G.exec, hs) == hipSuccess) { h->fastFlip ^= 1; done = true; }        // the replay stands for run_fast's ping-pong step too
-        else { (void)hipGetLastError(); (void)hipGraphExecDestroy(G.exec); G.exec = nullptr; if (G.graph) { (void)hipGraphDestroy(G.graph); G.graph = nullptr; } G.calls = -1000000; }
+        else { (void)hipGetLastError(); G.reset(true); }
     } else if (graphable && G.calls >= 1) {
         // second call with this key (the first ran eagerly: lazy allocations, stream / event creation): capture, instantiate, launch
         const int flip0 = h->fastFlip;
         if (hipStreamBeginCapture(hs, hipStreamCaptureModeThreadLocal) == hipSuccess) {
             const int r2 = enqueue();
-            hipGraph_t graph = nullptr;
-            const hipError_t e = hipStreamEndCapture(hs, &graph);
-            if (r2 == MYSLAM_OK && e == hipSuccess && graph && hipGraphInstantiate(&G.exec, graph, nullptr, nullptr, 0) == hipSuccess &&
+            const hipError_t e = hipStreamEndCapture(hs, &G.graph);
+            if (r2 == MYSLAM_OK && e == hipSuccess && G.graph && hipGraphInstantiate(&G.exec, G.graph, nullptr, nullptr, 0) == hipSuccess &&
                 hipGraphLaunch(G.exec, hs) == hipSuccess) {
-                done = true; G.graph = graph;
+                done = true;
             } else {                       // not capturable here: stay eager for this key
-                (void)hipGetLastError();
-                if (G.exec) { (void)hipGraphExecDestroy(G.exec); G.exec = nullptr; }
-                if (graph) (void)hipGraphDestroy(graph);
-                G.calls = -1000000; h->fastFlip = flip0;
+                (void)hipGetLastError(); G.reset(true); h->fastFlip = flip0;
             }
         } else {
-            (void)hipGetLastError(); G.calls = -1000000;
+            (void)hipGetLastError(); G.reset(true);
         }
     }
     if (!done && (rc = enqueue())) return rc;
@@ -853,16 +834,6 @@ int myslam_orb_detect(myslam_orb* h, const uint8_t* img, int rows, int cols, int
     return host_extract(h, img, rows, cols, step, mask, mask_step, kps, nullptr, cap, n, true);
 }
 
-// shared front half of Screen / CalcDescriptors: upload, ComputePyramid (ORBextractor.cpp:1096, :1192)
-static int host_pyramid(myslam_orb* h, const uint8_t* img, int rows, int cols, int step, int ncap) {
-    int rc = h->ensure(1, rows, cols, false);
-    if (rc) return rc;
-    if ((rc = h->ensure_stage((size_t)rows * step, 0, ncap))) return rc;
-    MYSLAM_HIP_CHECK(hipMemcpyAsync(h->d_stageImg, img, (size_t)rows * step, hipMemcpyHostToDevice, h->stream));
-    h->full.ext0N = h->det.ext0N = 0;                          // single staged image: nothing is read in place
-    return h->build_pyramids(h->d_stageImg, 1, step, (size_t)rows * step, nullptr, h->nlevels);
-}
-
 int myslam_orb_screen_and_compute_params(myslam_orb* h, const uint8_t* img, int rows, int cols, int step,
                                          myslam_keypoint* kps_in, int n_in, myslam_keypoint* kps_out, int cap, int* n_out) {
     if (!h || !n_out) return MYSLAM_ERR_INVALID;
@@ -870,7 +841,7 @@ int myslam_orb_screen_and_compute_params(myslam_orb* h, const uint8_t* img, int 
     if (!img || rows <= 0 || cols <= 0 || n_in <= 0) return MYSLAM_OK;       // :1085-1088 (logs + returns)
     if (!kps_in || !kps_out || step < cols) return MYSLAM_ERR_INVALID;
     for (int i = 0; i < n_in; i++) if (kps_in[i].octave < 0 || kps_in[i].octave >= h->nlevels) return MYSLAM_ERR_INVALID;
-    int rc = host_pyramid(h, img, rows, cols, step, n_in);
+    int rc = h->stage_pyramid(img, rows, cols, step, nullptr, n_in);        // upload, ComputePyramid (ORBextractor.cpp:1096)
     if (rc) return rc;
     MYSLAM_HIP_CHECK(hipMemcpyAsync(h->d_stageKps, kps_in, sizeof(myslam_keypoint) * n_in, hipMemcpyHostToDevice, h->stream));
     {
@@ -896,7 +867,7 @@ int myslam_orb_calc_descriptors(myslam_orb* h, const uint8_t* img, int rows, int
     if (!img || rows <= 0 || cols <= 0 || n <= 0) return MYSLAM_OK;          // :1183-1186
     if (!kps || !desc || step < cols) return MYSLAM_ERR_INVALID;
     for (int i = 0; i < n; i++) if (kps[i].octave < 0 || kps[i].octave >= h->nlevels) return MYSLAM_ERR_INVALID;
-    int rc = host_pyramid(h, img, rows, cols, step, n);
+    int rc = h->stage_pyramid(img, rows, cols, step, nullptr, n);           // :1192
     if (rc) return rc;
     if ((rc = h->blur_levels(1, h->nlevels, h->stream))) return rc;
     MYSLAM_HIP_CHECK(hipMemcpyAsync(h->d_stageKps, kps, sizeof(myslam_keypoint) * n, hipMemcpyHostToDevice, h->stream));
@@ -922,7 +893,7 @@ static int download_tiled_plane(const uint8_t* d_plane, const LevelGeom& g, uint
 int myslam_orb_debug_pyramid(myslam_orb* h, const uint8_t* img, int rows, int cols, int step, int level, int blurred,
                              uint8_t* out, int out_step, int* w, int* hgt) {
     if (!h || !img || level < 0 || level >= h->nlevels) return MYSLAM_ERR_INVALID;
-    int rc = host_pyramid(h, img, rows, cols, step, 16);
+    int rc = h->stage_pyramid(img, rows, cols, step, nullptr, 16);
     if (rc) return rc;
     if (blurred && (rc = h->blur_levels(1, h->nlevels, h->stream))) return rc;
     const LevelGeom& g = h->full.lv[level];
@@ -941,18 +912,10 @@ int myslam_orb_debug_candidates(myslam_orb* h, const uint8_t* img, int rows, int
                                 int mask_step, int level, int32_t* xs, int32_t* ys, int32_t* scores, int cap, int* n) {
     if (!h || !img || !n || level < 0 || level >= h->nlevels) return MYSLAM_ERR_INVALID;
     if (mask && mask_step != step) return MYSLAM_ERR_INVALID;
-    int rc = h->ensure(1, rows, cols, mask != nullptr);
+    int rc = h->stage_pyramid(img, rows, cols, step, mask, 16);
     if (rc) return rc;
-    if ((rc = h->ensure_stage((size_t)rows * step, mask ? (size_t)rows * step : 0, 16))) return rc;
-    MYSLAM_HIP_CHECK(hipMemcpyAsync(h->d_stageImg, img, (size_t)rows * step, hipMemcpyHostToDevice, h->stream));
-    if (mask) MYSLAM_HIP_CHECK(hipMemcpyAsync(h->d_stageMask, mask, (size_t)rows * step, hipMemcpyHostToDevice, h->stream));
-    if (!h->d_fastStat) {
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&h->d_fastStat, sizeof(uint32_t) * 2 * MAXL * 4));
-        MYSLAM_HIP_CHECK(hipMemsetAsync(h->d_fastStat, 0, sizeof(uint32_t) * 2 * MAXL * 4, h->stream));
-    }
-    launch_zero_u32(reinterpret_cast<uint32_t*>(h->d_candCount), MAXL, h->d_fastStat + (size_t)h->fastFlip * MAXL * 4, MAXL * 4, nullptr, 0, nullptr, 0, h->stream);
-    h->full.ext0N = h->det.ext0N = 0;                          // single staged image: nothing is read in place
-    if ((rc = h->build_pyramids(h->d_stageImg, 1, step, (size_t)rows * step, mask ? h->d_stageMask : nullptr, h->nlevels))) return rc;
+    if ((rc = h->ensure_fast_stat())) return rc;
+    launch_zero_u32(ZeroArgs{{reinterpret_cast<uint32_t*>(h->d_candCount), h->d_fastStat + (size_t)h->fastFlip * MAXL * 4}, {MAXL, MAXL * 4}}, h->stream);
     if ((rc = h->run_fast(h->full, mask ? h->d_mask : nullptr, 1))) return rc;
     int32_t counts[MAXL];
     MYSLAM_HIP_CHECK(hipMemcpyAsync(counts, h->d_candCount, sizeof(counts), hipMemcpyDeviceToHost, h->stream));

@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "orb_launch.h"
 #include "orb_plan.h"
 
 namespace myslam_hip {
@@ -2880,7 +2881,7 @@ __global__ void k_unpack_cands(const uint32_t* __restrict__ cand, int n, int32_t
 // The per-call counters (candidate / selection counts, status words, FAST statistics) are cleared by the FIRST kernel of a call — this
 // one — instead of by hipMemsetAsync: no launch of their own (a one-frame call is a chain of short dependent launches), and kernel nodes
 // are the part of a captured HIP graph that replays reliably (memset nodes of a replayed graph left garbage in the counters on ROCm 7.2).
-struct ZeroArgs { uint32_t* p[4]; int n[4]; };
+// (ZeroArgs: orb_launch.h)
 __device__ __forceinline__ void zero_part(const ZeroArgs& z, int tid, int T) {
 #pragma unroll
     for (int k = 0; k < 4; k++)
@@ -2931,27 +2932,18 @@ __global__ __launch_bounds__(256) void k_zero_u32(ZeroArgs a) {             // t
     for (int k = 0; k < 4; k++)
         if (a.p[k] && i < a.n[k]) a.p[k][i] = 0u;
 }
-void launch_zero_u32(uint32_t* p0, int n0, uint32_t* p1, int n1, uint32_t* p2, int n2, uint32_t* p3, int n3, hipStream_t s) {
-    ZeroArgs a{{p0, p1, p2, p3}, {n0, n1, n2, n3}};
-    const int n = max(max(n0, n1), max(n2, n3));
-    if (n > 0) hipLaunchKernelGGL(k_zero_u32, dim3((n + 255) / 256), dim3(256), 0, s, a);
+void launch_zero_u32(const ZeroArgs& z, hipStream_t s) {
+    const int n = max(max(z.n[0], z.n[1]), max(z.n[2], z.n[3]));
+    if (n > 0) hipLaunchKernelGGL(k_zero_u32, dim3((n + 255) / 256), dim3(256), 0, s, z);
 }
 
-static void ingest_launch(const uint8_t* src, int rows, int cols, int step, size_t sstride, uint8_t* dst, int dpitch,
-                          size_t dstride, int batch, const ZeroArgs& z, hipStream_t s) {
+// level-0 ingest; the call's first launch brings the per-call counters in z
+void launch_ingest(const uint8_t* src, int rows, int cols, int step, size_t sstride, uint8_t* dst, int dpitch, size_t dstride, int batch,
+                   const ZeroArgs& z, hipStream_t s) {
     const int t = (cols + 15) / 16;
     const int tpr = t < 256 ? t : 256, rpb = t < 256 ? 256 / t : 1;
     dim3 grid((t + 255) / 256, (rows + rpb - 1) / rpb, batch);
     hipLaunchKernelGGL(k_ingest, grid, dim3(256), 0, s, src, rows, cols, step, sstride, dst, dpitch, dstride, tpr, rpb, z);
-}
-void launch_ingest(const uint8_t* src, int rows, int cols, int step, size_t sstride, uint8_t* dst, int dpitch,
-                   size_t dstride, int batch, hipStream_t s) {
-    ingest_launch(src, rows, cols, step, sstride, dst, dpitch, dstride, batch, ZeroArgs{{nullptr, nullptr, nullptr, nullptr}, {0, 0, 0, 0}}, s);
-}
-// the call's first launch: level-0 ingest + the per-call counters
-void launch_ingest_clear(const uint8_t* src, int rows, int cols, int step, size_t sstride, uint8_t* dst, int dpitch, size_t dstride, int batch,
-                         uint32_t* p0, int n0, uint32_t* p1, int n1, uint32_t* p2, int n2, uint32_t* p3, int n3, hipStream_t s) {
-    ingest_launch(src, rows, cols, step, sstride, dst, dpitch, dstride, batch, ZeroArgs{{p0, p1, p2, p3}, {n0, n1, n2, n3}}, s);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2984,12 +2976,12 @@ void launch_resize_chain(const ResizeArgs* lv, int n, int batch, hipStream_t s) 
 }
 // levels 1 .. n from the caller's images (lv[0].src / spitch / sstride = the caller's buffer) + ingest of images b >= b0 + the per-call counters
 void launch_pyr_head(const ResizeArgs* lv, int n, int rows, int cols, uint8_t* dst0, int dpitch0, size_t dstride0, int b0, int batch,
-                     uint32_t* p0, int n0, uint32_t* p1, int n1, uint32_t* p2, int n2, uint32_t* p3, int n3, hipStream_t s) {
+                     const ZeroArgs& z, hipStream_t s) {
     const ResizeChain c = make_chain(lv, n);
     const int t = (cols + 15) / 16;
     IngestPart g{lv[0].src, rows, cols, lv[0].spitch, lv[0].sstride, dst0, dpitch0, dstride0, t < 256 ? t : 256, t < 256 ? 256 / t : 1, (t + 255) / 256, b0};
     const int iblocks = g.gx * ((rows + g.rpb - 1) / g.rpb);
-    hipLaunchKernelGGL(k_pyr_head, dim3(c.blk0[RC_MAX] + iblocks, batch), dim3(256), 0, s, c, g, ZeroArgs{{p0, p1, p2, p3}, {n0, n1, n2, n3}});
+    hipLaunchKernelGGL(k_pyr_head, dim3(c.blk0[RC_MAX] + iblocks, batch), dim3(256), 0, s, c, g, z);
 }
 // (measured at 1 pair x 16 lanes, tools/ab_stream_mode.sh, us per step / graph nodes: no head launch, chains of 3: 89.3 / 18; head of 2 levels + chains of 3:
 // 85.2 / 17; head of 3 + chains of 2: 86.9 / 17; head of 3 + one chain of 4: 86.5 / 16 — a node costs ~4.6 us, and the 21 / 85 interpolations per
@@ -3019,44 +3011,52 @@ bool blur_uses_strips(const BlurArgs& a) {
     return a.w >= 8 && a.h >= 8 && (a.spitch & 3) == 0 && ((reinterpret_cast<uintptr_t>(a.src) | a.sstride) & 3) == 0;
 }
 
-// n levels (n <= MAXL): the ones the register-strip kernel can take share one launch, the others (unaligned rows, images narrower
-// than 8 pixels) go through the LDS-tiled kernel one by one
+// the form a level takes: the int8 matrix cores (operand tables given, 16-byte aligned tiled destination), register strips, or — unaligned
+// rows, images narrower than 8 pixels — the LDS-tiled kernel
+enum class BlurForm { Mfma, Strip, Tile };
+static BlurForm blur_form(const BlurArgs& a) {
+    if (a.tabH && a.tabV && a.ident && a.dtiled && (a.dpitch & 15) == 0 && ((reinterpret_cast<uintptr_t>(a.dst) | a.dstride) & 15) == 0) return BlurForm::Mfma;
+    return blur_uses_strips(a) ? BlurForm::Strip : BlurForm::Tile;
+}
+static void blur_multi_add(BlurMulti& M, const BlurArgs& a) {               // one wave per 256-column strip and band of B3_R rows
+    const int nstrips = (a.w + 255) / 256, nbands = (a.h + B3_R - 1) / B3_R;
+    M.a[M.n] = a; M.nstrips[M.n] = nstrips; M.wave0[M.n + 1] = M.wave0[M.n] + nstrips * nbands; M.n++;
+}
+
+// n levels (n <= MAXL): the strip levels share one launch, the matrix-core levels another, LDS-tiled levels go one by one
 void launch_blur_levels(const BlurArgs* lv, int n, int batch, hipStream_t s) {
     BlurMulti M; M.n = 0; M.wave0[0] = 0;
     BlurMfmaMulti X; X.n = 0; X.wave0[0] = 0;
     for (int i = 0; i < n; i++) {
         const BlurArgs& a = lv[i];
-        if (a.tabH && a.tabV && a.ident && a.dtiled && (a.dpitch & 15) == 0 && ((reinterpret_cast<uintptr_t>(a.dst) | a.dstride) & 15) == 0) {
-            // matrix-core form: one wave per 32-column strip of the level, all such levels in one launch.  (tabH / tabV already point at
-            // the level's blocks: the per-level offsets of the multi-launch stay 0)
-            X.a[X.n] = a; X.tabHOff[X.n] = 0; X.tabVOff[X.n] = 0; X.wave0[X.n + 1] = X.wave0[X.n] + (a.w + 31) / 32; X.n++;
-        } else if (blur_uses_strips(a)) {
-            const int nstrips = (a.w + 255) / 256, nbands = (a.h + B3_R - 1) / B3_R;
-            M.a[M.n] = a; M.nstrips[M.n] = nstrips; M.wave0[M.n + 1] = M.wave0[M.n] + nstrips * nbands; M.n++;
-        } else {
-            dim3 grid((a.w + B2_W - 1) / B2_W, (a.h + B2_H - 1) / B2_H, batch);
-            hipLaunchKernelGGL(k_blur7_dot, grid, dim3(256), 0, s, a);
+        switch (blur_form(a)) {
+            case BlurForm::Mfma:
+                // one wave per 32-column strip of the level.  (tabH / tabV already point at the level's blocks: the per-level offsets of
+                // the multi-launch stay 0)
+                X.a[X.n] = a; X.tabHOff[X.n] = 0; X.tabVOff[X.n] = 0; X.wave0[X.n + 1] = X.wave0[X.n] + (a.w + 31) / 32; X.n++;
+                break;
+            case BlurForm::Strip: blur_multi_add(M, a); break;
+            case BlurForm::Tile:
+                hipLaunchKernelGGL(k_blur7_dot, dim3((a.w + B2_W - 1) / B2_W, (a.h + B2_H - 1) / B2_H, batch), dim3(256), 0, s, a);
+                break;
         }
     }
     if (M.n) hipLaunchKernelGGL(k_blur7_strip, dim3((M.wave0[M.n] + 3) / 4, 1, batch), dim3(256), 0, s, M);
     if (X.n) hipLaunchKernelGGL(k_blur7_mfma, dim3((X.wave0[X.n] + 3) / 4, 1, batch), dim3(256), 0, s, X);
 }
-void launch_blur(const BlurArgs& a, int batch, hipStream_t s) { launch_blur_levels(&a, 1, batch, s); }
 
 #ifndef MYSLAM_BLUR_WITH_OCTREE        // A/B builds (tools/build_variants.sh): 0 = the Gaussian keeps its own launch
 #define MYSLAM_BLUR_WITH_OCTREE 1
 #endif
 // small batches: all levels as register strips in the oct-tree's launch — possible when every level takes the strip form (no matrix-core option, aligned planes)
-bool blur_multi_for_octree(const BlurArgs* lv, int n, int batch, BlurMulti& M) {
+static bool blur_multi_for_octree(const BlurArgs* lv, int n, int batch, BlurMulti& M) {
     // (up to 4 pairs per call: +5 % frames/s at 1 - 2 pairs, even at 4; at 8 and 16 pairs the bands, which then wait for 512-thread blocks with the
     // oct-tree's LDS, cost 1 - 3 %: profiles/r05_ab_pairs_8_16.log)
     if (!MYSLAM_BLUR_WITH_OCTREE || batch >= OCT_WIDE_BELOW || batch >= 16) return false;
     M.n = 0; M.wave0[0] = 0;
     for (int i = 0; i < n; i++) {
-        const BlurArgs& a = lv[i];
-        if ((a.tabH && a.tabV) || !blur_uses_strips(a)) return false;
-        const int nstrips = (a.w + 255) / 256, nbands = (a.h + B3_R - 1) / B3_R;
-        M.a[M.n] = a; M.nstrips[M.n] = nstrips; M.wave0[M.n + 1] = M.wave0[M.n] + nstrips * nbands; M.n++;
+        if (blur_form(lv[i]) != BlurForm::Strip) return false;
+        blur_multi_add(M, lv[i]);
     }
     return M.n > 0;
 }
@@ -3084,7 +3084,6 @@ void launch_fast(const OrbPlan& P, const uint8_t* pyr, size_t pyrStride, const u
 
 size_t octree_lds_bytes(int nodeCap) { return 192 + 4 * (size_t)OT_MAXB + 4 * (size_t)(OT_MAXB + 2) + (size_t)nodeCap * 54 + 16; }
 
-bool blur_multi_for_octree(const BlurArgs* lv, int n, int batch, BlurMulti& M);
 // returns true when the Gaussian of the levels blurLv[0 .. nBlur) rode in the launch (small batches; the caller then skips its blur launch)
 bool launch_octree(const OrbPlan& P, const uint32_t* cand, const int32_t* candCount, uint32_t* sortbuf, const uint32_t* octTab, uint32_t* selOut,
                    int32_t* selCount, int32_t* status, int batch, uint16_t* order, hipStream_t s, const BlurArgs* blurLv, int nBlur) {

@@ -467,6 +467,19 @@ def test_level0_read_in_place(api, oracle, synth, copy_input, cols, step, gap):
     gk, gd = ext.DetectAndCompute(other)
     rk, rd = oracle.detect_and_compute(oracle.params(600), other)
     assert gk.tobytes() == rk.tobytes() and np.array_equal(gd, rd)
+    # ... and the loop-closing pair (test_screen_and_calc_descriptors_bitexact), after another batch has been read in place
+    ext.detect_and_compute_batch(d.data_ptr(), B, rows, cols, step, stride, kps.data_ptr(), desc.data_ptr(), cnt.data_ptr(), st.data_ptr(), cap)
+    p = oracle.params(600)
+    feats = oracle.detect(p, other)
+    pyr_kps = np.repeat(feats, 8)
+    pyr_kps["octave"] = np.tile(np.arange(8), len(feats)); pyr_kps["response"] = -1
+    pyr_kps["class_id"] = np.repeat(np.arange(len(feats)), 8)
+    out, _ = ext.ScreenAndComputeKPsParams(other, pyr_kps)
+    rout = oracle.screen(p, other, pyr_kps)
+    assert _kp_equal(out, rout), _explain(out, rout)
+    assert len(out) >= len(feats)
+    sd = ext.CalcDescriptors(other, out)
+    assert np.array_equal(sd, oracle.calc_descriptors(p, other, rout)), (copy_input, "CalcDescriptors")
     det = api.ORBextractor(300)
     det.set_option(det.OPT_COPY_INPUT, copy_input)
     dcap = det.max_keypoints(rows, cols)
