@@ -415,7 +415,8 @@ __global__ __launch_bounds__(256) void k_conv2_bf16x6(const float* __restrict__ 
 // (a - h is exact in f32, the power-of-two scaling keeps the residual out of f16's subnormal range).  Then
 //     2^11 a b  ~  h_a (2^11 h_b)  +  h_a m'_b  +  m'_a h_b            (dropped: m_a m_b and the two rounding terms, <= 2^-21 |a b| together)
 // so that ONE accumulator takes all three products: the weight side carries a third plane Hs = 2^11 h_b (exact in f16 while |w| < 2^5: checked
-// when the model is loaded, as is the bound 65504 on the activations — models outside keep the bf16 x 6 kernel).  Half the matrix
+// when the model is loaded, as are the bound 65504 on the activations and a lower bound 2^-6 on max |w| of conv1 and conv2, which keeps the bulk of the h and m' planes
+// out of f16's subnormal range — models outside keep the bf16 x 6 kernel).  Half the matrix
 // instructions of the bf16 form (12 per wave and K step) and 5 instead of 6 operand planes through LDS; measured against an f64 reference
 // the error is of the same order (tools/conv2_error.py).  Same tiling, staging roles and LDS layout as k_conv2_bf16x6.
 typedef _Float16 cv_f16x8 __attribute__((ext_vector_type(8)));
@@ -1162,6 +1163,13 @@ static int lcd_create(myslam_lcd** out, const myslam_calc_layer* layers, int nla
     if (h->fused.ok) {
         // f16 planes for k_conv2_f16x3 — only when nothing can leave f16's range: |w2| < 2^5 (2^11 h must stay below 65504) and conv2's input,
         // the LRN'd / pooled conv1 map, bounded by sum |w1| + |b1| (inputs are pixels / 255) < 65504 with an LRN that cannot amplify (k >= 1)
+        // ... and nothing may sink below it either: f16 has its 10 mantissa bits only above 2^-14.  With weights (or, behind small conv1 weights,
+        // activations) uniformly below ~2e-5 h goes subnormal and the split loses the bar of 5e-6 (emulated over both scales in
+        // tests/test_calc_f64.py).  With subnormal operands kept by the matrix unit 2^-9 would do (16 x the largest weight of the smallest scale
+        // that still holds the bar); whether they are kept is not measured, so the bound is the one that also holds if they are flushed: twice
+        // the smallest power of two at which the flushed emulation stays under the bar.  tests/test_gpu_lcd_ranges.py runs a model exactly on it.
+        // The bf16 pieces have f32's exponent range: models below keep the bf16 x 6 kernels.
+        constexpr double F16_WMIN = 1.0 / 64;
         const float* w1 = weights; const int n1 = layers[0].num_output, k1 = layers[0].kernel * layers[0].kernel;     // conv1: 1 input channel
         double bound1 = 0, wmax2 = 0;
         for (int oc = 0; oc < n1; oc++) {
@@ -1171,7 +1179,7 @@ static int lcd_create(myslam_lcd** out, const myslam_calc_layer* layers, int nla
         }
         for (float v : w2t) wmax2 = std::max(wmax2, (double)std::fabs(v));
         const bool finite = std::isfinite(bound1) && std::isfinite(wmax2);
-        if (finite && bound1 < 60000.0 && wmax2 < 31.0 && h->fused.lrn[0].k >= 1.0f && h->fused.lrn[0].beta >= 0.0f &&
+        if (finite && bound1 < 60000.0 && wmax2 < 31.0 && wmax2 >= F16_WMIN && h->fused.lrn[0].k >= 1.0f && h->fused.lrn[0].beta >= 0.0f &&
             h->fused.lrn[0].aon >= 0.0f && std::isfinite(h->fused.lrn[0].aon) && std::isfinite(h->fused.lrn[0].beta)) {      // alpha < 0 would make (k + alpha/n ss)^-beta exceed 1 (walk_layers rejects it already)
             auto to_f16 = [](float x) -> uint16_t { const _Float16 v = (_Float16)x; uint16_t u; memcpy(&u, &v, 2); return u; };   // round to nearest even
             auto from_f16 = [](uint16_t b) -> float { _Float16 v; memcpy(&v, &b, 2); return (float)v; };
@@ -1190,7 +1198,7 @@ static int lcd_create(myslam_lcd** out, const myslam_calc_layer* layers, int nla
                 return fail(MYSLAM_ERR_HIP);
             double wmax1 = 0;
             for (int i = 0; i < n1 * k1; i++) wmax1 = std::max(wmax1, (double)std::fabs(w1[i]));
-            if (wmax1 < 31.0 && k1 == 25 && n1 == 64) {
+            if (wmax1 < 31.0 && wmax1 >= F16_WMIN && k1 == 25 && n1 == 64) {
                 // conv1 weights in the B-operand layout of v_mfma_f32_32x32x16_f16: lane (n = lane & 31, k half = lane >> 5) holds k = 16 ks + 8 kh + j
                 std::vector<uint16_t> w1h((size_t)2 * 2 * 3 * 64 * 8);
                 for (int nt = 0; nt < 2; nt++)

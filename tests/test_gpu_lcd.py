@@ -33,36 +33,25 @@ def test_preproc_and_descriptor(api, oracle, synth):
 
 
 def test_layer_taps_against_torch(api, synth):
-    import torch
-    import torch.nn.functional as F
-    w = synth.calc_weights(); lcd = api.DeepLCD(w)
+    """Stage taps 0 .. 3 and the descriptor against the f64 net (tests/calc_f64.py: CPU torch, double precision), both kernel families."""
+    import calc_f64
+    w = synth.calc_weights()
     x = synth._rng(21).uniform(0, 1, (120, 160)).astype(np.float32)
-    o = [0]
-    def take(shape):
-        n = int(np.prod(shape)); t = torch.from_numpy(w[o[0]:o[0] + n].reshape(shape).copy()).double(); o[0] += n
-        return t
-    w1, b1, w2, b2, w3, b3 = take((64, 1, 5, 5)), take((64,)), take((128, 64, 4, 4)), take((128,)), take((4, 128, 3, 3)), take((4,))
-    t = torch.from_numpy(x)[None, None].double()
-    a1 = F.relu(F.conv2d(t, w1, b1, stride=2, padding=4))
-    p1 = F.local_response_norm(F.max_pool2d(a1, 3, 2, ceil_mode=True), 5, alpha=1e-4, beta=0.75, k=1.0)
-    a2 = F.relu(F.conv2d(p1, w2, b2, stride=1, padding=2))
-    p2 = F.local_response_norm(F.max_pool2d(a2, 3, 2, ceil_mode=True), 5, alpha=1e-4, beta=0.75, k=1.0)
-    refs = [(a1, 62, 82, 64), (p1, 31, 41, 64), (a2, 32, 42, 128), (p2, 16, 21, 128)]
-    for stage, (r, h, ww, c) in enumerate(refs):
-        got = _nhwc_to_nchw(lcd.debug_forward(x, stage), h, ww, c)
-        ref = r[0].numpy()
-        err = np.abs(got - ref).max() / max(1e-6, np.abs(ref).max())
-        # f32-level accuracy is what the f16 x 3 / bf16 x 6 split products on the 16-bit matrix cores claim (measured 1.1e-6 against this
-        # f64 net, tools/conv2_error.py): the bar is 5e-6 max-normalised, not the 2e-5 ABSOLUTE bar against the f32 oracle (an asymmetric
-        # weight bank: a transposed tile would fail here by orders of magnitude)
-        assert err < 5e-6, (stage, err)
-    # the bf16 x 6 fallback kernels hold the same bar
-    lcd2 = api.DeepLCD(w); lcd2.set_option(lcd2.OPT_CONV2_BF16X6, 1)
-    for stage, (r, h, ww, c) in enumerate(refs):
-        got = _nhwc_to_nchw(lcd2.debug_forward(x, stage), h, ww, c)
-        ref = r[0].numpy()
-        err = np.abs(got - ref).max() / max(1e-6, np.abs(ref).max())
-        assert err < 5e-6, ("bf16x6", stage, err)
+    refs = calc_f64.forward_f64(calc_f64.default_layers(), w, x)
+    assert [r.shape for r in refs] == [(64, 62, 82), (64, 31, 41), (128, 32, 42), (128, 16, 21), (1064,)]
+    lcd = api.DeepLCD(w)
+    lcd2 = api.DeepLCD(w); lcd2.set_option(lcd2.OPT_CONV2_BF16X6, 1)            # the bf16 x 6 fallback kernels hold the same bar
+    assert lcd.conv2_products() == 3 and lcd2.conv2_products() == 6
+    for family, h in (("f16x3", lcd), ("bf16x6", lcd2)):
+        for stage in range(4):
+            ref = refs[stage]
+            got = calc_f64.nhwc_to_nchw(h.debug_forward(x, stage), ref.shape)
+            err = np.abs(got - ref).max() / max(1e-6, np.abs(ref).max())
+            # f32-level accuracy is what the f16 x 3 / bf16 x 6 split products on the 16-bit matrix cores claim (measured 1.1e-6 against this
+            # f64 net, tools/conv2_error.py): the bar is 5e-6 max-normalised, not the 2e-5 ABSOLUTE bar against the f32 oracle (an asymmetric
+            # weight bank: a transposed tile would fail here by orders of magnitude)
+            assert err < 5e-6, (family, stage, err)
+        assert np.abs(h.debug_forward(x, 4) - refs[4]).max() < DESC_ATOL, family
 
 
 def test_describe_batch(api, oracle, synth):
