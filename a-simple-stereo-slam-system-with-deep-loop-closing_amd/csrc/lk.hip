@@ -11,6 +11,7 @@
 // One wave per point, all pyramid levels inside the wave (coarse to fine), no global scratch: the (win+3)^2 patch of I, its
 // Scharr derivatives and the (win+1)^2 window of J live in LDS; the template patch (I, Ix, Iy at the window pixels) stays in
 // registers (2 window pixels per lane).  Sums over the window are DPP wave reductions of 32-bit halves (exact).
+#include <limits.h>
 #include <math.h>
 #include <stdlib.h>
 
@@ -35,6 +36,13 @@ __device__ __forceinline__ int lk_reflect101(int p, int len) {
     if (len == 1) return 0;
     while (p < 0 || p >= len) p = (p < 0) ? -p : 2 * len - 2 - p;
     return p;
+}
+
+// cvFloor with the rule for what does not fit an int stated: NaN, +-inf and every value outside [-2^31, 2^31) give INT_MIN, which fails
+// each bounds test of the tracker (the point is reported lost); the bare conversion of such a value is undefined in C++
+__device__ __forceinline__ int lk_floor(float v) {
+    if (!(v >= -2147483648.f && v < 2147483648.f)) return INT_MIN;
+    return (int)floorf(v);
 }
 
 // cv::pyrDown 8UC1: one thread per destination pixel
@@ -97,7 +105,7 @@ __global__ __launch_bounds__(256) void k_lk_track(LkArgs a) {
     __shared__ uint8_t s_J[4][PJ_MAX * PJ_MAX];
     const int b = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int pi = blockIdx.x * 4 + wave;
-    const int n = a.counts ? a.counts[b] : a.n_fixed;
+    const int n = a.counts ? min(a.counts[b], a.cap) : a.n_fixed;          // counts above cap are read as cap
     if (pi >= n) return;                                            // wave-uniform
     const uint8_t *prev0 = a.prev, *next0 = a.next, *pyrP = a.pyrP, *pyrN = a.pyrN;
     if (a.sel) {                                                    // block-uniform
@@ -129,7 +137,7 @@ __global__ __launch_bounds__(256) void k_lk_track(LkArgs a) {
         else { nx = __fmul_rn(outx, 2.f); ny = __fmul_rn(outy, 2.f); }
         outx = nx; outy = ny;
         prx = __fsub_rn(prx, halfWin); pry = __fsub_rn(pry, halfWin);
-        const int ipx = (int)floorf(prx), ipy = (int)floorf(pry);
+        const int ipx = lk_floor(prx), ipy = lk_floor(pry);
         if (ipx < -win || ipx >= lw || ipy < -win || ipy >= lh) {
             if (level == 0) { status = 0; errv = 0.f; }
             continue;
@@ -195,7 +203,7 @@ __global__ __launch_bounds__(256) void k_lk_track(LkArgs a) {
         nx = __fsub_rn(nx, halfWin); ny = __fsub_rn(ny, halfWin);
         float pdx = 0.f, pdy = 0.f;
         for (int j = 0; j < a.max_iters; j++) {
-            const int inx = (int)floorf(nx), iny = (int)floorf(ny);
+            const int inx = lk_floor(nx), iny = lk_floor(ny);
             if (inx < -win || inx >= lw || iny < -win || iny >= lh) {
                 if (level == 0) status = 0;
                 break;
@@ -236,7 +244,7 @@ __global__ __launch_bounds__(256) void k_lk_track(LkArgs a) {
         }
         if (status && level == 0) {          // patch error at the final position; also the last bounds test (err is always requested)
             const float fx = __fsub_rn(outx, halfWin), fy = __fsub_rn(outy, halfWin);
-            const int inx = (int)floorf(fx), iny = (int)floorf(fy);
+            const int inx = lk_floor(fx), iny = lk_floor(fy);
             if (inx < -win || inx >= lw || iny < -win || iny >= lh) { status = 0; continue; }
             __builtin_amdgcn_wave_barrier();
             for (int i = lane; i < pJ * pJ; i += 64) {

@@ -530,7 +530,9 @@ typedef struct myslam_lk myslam_lk;
 int myslam_lk_create(myslam_lk** out, int win, int max_level, int max_iters, float eps, float min_eig_threshold);
 int myslam_lk_destroy(myslam_lk* h);
 int myslam_lk_set_stream(myslam_lk* h, void* hip_stream);
-/* host pointers (uploads, runs, downloads, synchronises); pts = n x (x, y) float */
+/* host pointers (uploads, runs, downloads, synchronises); pts = n x (x, y) float.  A point with a non-finite coordinate (NaN, +-inf, in
+ * prev_pts or in the initial flow) is reported lost: status 0, err 0, its position unspecified; so is one whose window origin does not fit
+ * an int.  Rows may be padded (prev_step, next_step >= cols, each image with its own); the last row need only reach its last pixel. */
 int myslam_lk_track(myslam_lk* h, const uint8_t* prev, const uint8_t* next, int rows, int cols, int prev_step, int next_step,
                     const float* prev_pts, float* next_pts, int n, uint8_t* status, float* err);
 /* The same call for a TRACKER that sees one new image per frame (Frontend::TrackLastFrame, src/frontend.cpp:129-172: the `next` image of frame
@@ -545,7 +547,8 @@ int myslam_lk_track_cached(myslam_lk* h, const uint8_t* prev, uint64_t prev_toke
                            int prev_step, int next_step, const float* prev_pts, float* next_pts, int n, uint8_t* status, float* err);
 int myslam_lk_prefetch(myslam_lk* h, const uint8_t* img, uint64_t token, int rows, int cols, int step);
 /* device pointers, asynchronous on the handle's stream: `batch` image pairs (image b at base + b*stride), points of pair b at
- * pts + b*cap*2, d_counts[b] of them valid; d_status batch x cap, d_err batch x cap or NULL */
+ * pts + b*cap*2, d_counts[b] of them valid (counts above cap are read as cap; slots past the count are neither read nor written);
+ * d_status batch x cap, d_err batch x cap or NULL */
 int myslam_lk_track_batch(myslam_lk* h, const uint8_t* d_prev, const uint8_t* d_next, int batch, int rows, int cols, int step, size_t stride,
                           const float* d_prev_pts, float* d_next_pts, const int32_t* d_counts, int cap, uint8_t* d_status, float* d_err);
 

@@ -7,6 +7,7 @@
 // PARITY UNPINNED against OpenCV (no golden vectors exist; its SSE/NEON/scalar builds already differ from each other in the
 // float accumulation order).  This restatement DEFINES the window sums (A11, A12, A22, b1, b2, err) as exact integer sums
 // converted to float once; every other float expression is evaluated left to right without contraction.
+#include <limits.h>
 #include <math.h>
 #include <stdint.h>
 #include <string.h>
@@ -23,7 +24,12 @@ inline int reflect101(int p, int len) {
     while (p < 0 || p >= len) p = (p < 0) ? -p : 2 * len - 2 - p;
     return p;
 }
-inline int cv_floor(float v) { int i = (int)v; return i - (i > v); }
+// cvFloor; NaN, +-inf and values outside [-2^31, 2^31) give INT_MIN (what the x86 conversion behind OpenCV's cvFloor yields, stated here
+// instead of left to the build: the bare conversion is undefined in C++), so such a point fails every bounds test and is reported lost
+inline int cv_floor(float v) {
+    if (!(v >= -2147483648.f && v < 2147483648.f)) return INT_MIN;
+    int i = (int)v; return i - (i > v);
+}
 inline int cv_round(float v) { return (int)lrintf(v); }
 inline int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
 

@@ -511,6 +511,43 @@ def test_lk_recovers_subpixel_translation(oracle, synth):
     assert not st2.any()
 
 
+def test_lk_non_finite_and_out_of_range_points_are_lost(oracle, synth):
+    """cv_floor's stated rule: a coordinate that is NaN, +-inf or outside the int range, in prev_pts or in the initial guess, fails the bounds
+    test: status 0, err 0, and the position is what came in"""
+    import lk_cases as LC
+    a = synth.random_image(77, 120, 160); b = np.roll(a, 1, axis=1).copy()
+    good = np.array([70.25, 61.5], np.float32)
+    pts, init = [good.copy()], [good.copy()]
+    for v in LC.NON_FINITE + LC.OUT_OF_RANGE:
+        for slot in range(4):                                    # prev x, prev y, init x, init y
+            p, q = good.copy(), good.copy()
+            (p if slot < 2 else q)[slot & 1] = v
+            pts.append(p); init.append(q)
+    pts = np.array(pts, np.float32); init = np.array(init, np.float32)
+    for win, lv in ((11, 3), (15, 0), (3, 6)):
+        out, st, err = oracle.lk_track(a, b, pts, init, win=win, max_level=lv)
+        assert st[0] and np.isfinite(out[0]).all()               # the ordinary point among them is tracked
+        assert not st[1:].any() and not np.any(err[1:])
+        assert np.array_equal(out[1:], init[1:], equal_nan=True)
+
+
+def test_lk_window_sums_beyond_32_bits(oracle):
+    """the saturated stripe pattern of tests/lk_cases.py: for a 15 x 15 window sum Ix^2 and the first iteration's sum diff * Ix exceed 2^31 (numpy,
+    int64), and the oracle, which sums in int64, finds the one-pixel move"""
+    import lk_cases as LC
+    a = LC.saturated_pattern(120, 160); b = np.roll(a, 1, axis=1).copy()
+    pts = np.array([[63, 53], [60, 50], [61, 50], [62, 51], [90, 64]], np.float32)
+    assert LC.window_sums(a, b, 63, 53, 15) == (2657280000, -2844262400)
+    assert LC.window_sums(a, b, 63, 53, 11)[0] == 1481497600 and LC.window_sums(a, b, 63, 53, 13)[0] == 1991142400          # smaller windows stay below
+    for x, y in pts.astype(int):
+        s11, sb1 = LC.window_sums(a, b, x, y, 15)
+        assert s11 > 2 ** 31 and abs(sb1) > 2 ** 31
+    out, st, err = oracle.lk_track(a, b, pts, pts, win=15, max_level=0)
+    assert st.all()
+    assert np.abs(out - pts - [1.0, 0.0]).max() < 0.01
+    assert err.max() < 0.5                                       # the patches agree at the found position
+
+
 def test_pose_only_converges_and_flags_gross_outliers(oracle, synth):
     rng = np.random.default_rng(11)
     K = synth.KITTI00; Kt = (K["fx"], K["fy"], K["cx"], K["cy"])
