@@ -579,7 +579,9 @@ int myslam_lk_track_batch(myslam_lk* h, const uint8_t* d_prev, const uint8_t* d_
  *      (status == TRACKING_BAD, :112; or with kf_every > 0: status != LOST && frame id % kf_every == 0) or LOST.
  * A stream with needs_host set is FROZEN: later steps leave its state, its stored image and d_results[s] untouched until myslam_tracker_set_frame.
  * A stream that was never set is frozen.  status = MYSLAM_ERR_CAPACITY (needs_host 1, frozen) reports a stream whose tables did not fit
- * (set_frame beyond cap / landmark_cap, an outlier list beyond 2 x cap); nothing is ever truncated.
+ * (set_frame beyond cap / landmark_cap, an outlier list beyond 2 x cap); nothing is ever truncated.  (As the rules stand the list cannot
+ * overflow: every entry is a feature of the table set_frame uploaded that loses its landmark in the same step and is therefore never kept again,
+ * steps add no features and set_frame empties the list, so it never holds more than n_feat <= cap entries; the clause guards the buffer.)
  * A step is 5 + (pyramid levels above 0) dependent launches (8 with the reference's max_level 3): head (image copy + rule 1), one per pyramid
  * level, LK, compaction, pose-only, tail (rules 5 + 6).
  * ------------------------------------------------------------------------------------------ */
