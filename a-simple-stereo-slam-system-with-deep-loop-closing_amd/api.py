@@ -936,6 +936,49 @@ def solve_pnp_ransac(pts3d, pts2d, K, iterations=100, reproj_error=5.991, confid
     return pose, inl[:n].astype(bool), ni.value
 
 
+VERIFY_CONFIRMED, VERIFY_NO_MODEL, VERIFY_FEW_MATCHES, VERIFY_FEW_INLIERS = 0, 1, 2, 3      # MYSLAM_VERIFY_*
+
+
+class PnPSolver:
+    """Loop verification for a batch of candidates on the device (myslam_pnp_*): the handle owns the workspace of `max_batch` items of `cap`
+    match slots and `max_iterations` hypotheses, the calls take device pointers as ints, enqueue on the handle's stream and return.
+    K = (fx, fy, cx, cy)."""
+
+    def __init__(self, max_batch, cap, max_iterations=100, stream=None):
+        self.max_batch, self.cap, self.max_iterations = int(max_batch), int(cap), int(max_iterations)
+        self._h = C.c_void_p()
+        _check(lib().myslam_pnp_create(C.byref(self._h), self.max_batch, self.cap, self.max_iterations), "myslam_pnp_create")
+        if stream is not None:
+            self.set_stream(stream)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and self._h.value and _lib is not None:
+            lib().myslam_pnp_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def set_stream(self, stream):
+        _check(lib().myslam_pnp_set_stream(self._h, C.c_void_p(stream)), "myslam_pnp_set_stream")
+
+    def solve_batch(self, d_pts3d, d_pts2d, d_counts, batch, K, d_pose7, d_inlier, d_n_inliers, d_status, iterations=100, reproj_error=5.991,
+                    confidence=0.99):
+        """cv::solvePnPRansac (src/loopclosing.cpp:262-272) per item: d_pts3d batch x cap x 3 f32, d_pts2d batch x cap x 2 f32, d_counts batch i32;
+        d_pose7 batch x 7 f64, d_inlier batch x cap u8, d_n_inliers / d_status batch i32 (status 0 = model, 1 = none: pose left alone)"""
+        _check(lib().myslam_solve_pnp_ransac_batch(self._h, C.c_void_p(d_pts3d), C.c_void_p(d_pts2d), C.c_void_p(d_counts), int(batch), C.c_double(K[0]),
+                                                   C.c_double(K[1]), C.c_double(K[2]), C.c_double(K[3]), int(iterations), C.c_double(reproj_error),
+                                                   C.c_double(confidence), C.c_void_p(d_pose7), C.c_void_p(d_inlier), C.c_void_p(d_n_inliers),
+                                                   C.c_void_p(d_status)), "myslam_solve_pnp_ransac_batch")
+
+    def verify_batch(self, d_pts3d, d_pts2d, d_counts, batch, K, d_pose7, d_outlier, d_n_inliers, d_status, d_pnp_pose7=0, d_pnp_inlier=0, iterations=100,
+                     reproj_error=5.991, confidence=0.99, min_matches=10, chi2_th=5.991, rounds=4, iters=10):
+        """LoopClosing::ComputeCorrectPose's arithmetic (src/loopclosing.cpp:208-335) per item: PnP-RANSAC, then the pose-only optimisation with
+        pre_optimize 1 over all the item's matches; d_status batch i32 = VERIFY_*; d_pnp_pose7 / d_pnp_inlier (optional): PnP's own pose and mask"""
+        _check(lib().myslam_loop_verify_batch(self._h, C.c_void_p(d_pts3d), C.c_void_p(d_pts2d), C.c_void_p(d_counts), int(batch), C.c_double(K[0]),
+                                              C.c_double(K[1]), C.c_double(K[2]), C.c_double(K[3]), int(iterations), C.c_double(reproj_error),
+                                              C.c_double(confidence), int(min_matches), C.c_double(chi2_th), int(rounds), int(iters), C.c_void_p(d_pose7),
+                                              C.c_void_p(d_outlier), C.c_void_p(d_n_inliers), C.c_void_p(d_status), C.c_void_p(d_pnp_pose7 or None),
+                                              C.c_void_p(d_pnp_inlier or None)), "myslam_loop_verify_batch")
+
+
 # ---------------------------------------------------------------------------------- host-side formats (no device needed)
 def read_png_gray(path):
     """cv::imread(path, IMREAD_GRAYSCALE) for the KITTI grey PNGs (app/run_kitti_stereo.cpp:66-67) -> uint8 [rows, cols]"""

@@ -1506,6 +1506,16 @@ int pose_only_bank_launch(double* d_poses, const double* d_pts3d, const double* 
     MYSLAM_HIP_CHECK(hipGetLastError());
     return MYSLAM_OK;
 }
+// the loop closer's chain (pnp.hip, myslam_loop_verify_batch): with pre_optimize
+int pose_only_loop_launch(double* d_poses, const double* d_pts3d, const double* d_obs, const int32_t* d_counts, int batch, int cap, double fx, double fy,
+                          double cx, double cy, double chi2_th, int rounds, int iters, int pre_optimize, uint8_t* d_outlier, int32_t* d_n_inliers,
+                          int32_t* d_status, hipStream_t s) {
+    PoseOnlyArgs a{d_poses, d_pts3d, d_obs, d_counts, 0, cap, fx, fy, cx, cy, chi2_th, rounds, iters, pre_optimize, d_outlier, d_n_inliers, d_status};
+    ScopedProf sp(P_BA, s);
+    pose_only_launch(a, batch, cap, s);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    return MYSLAM_OK;
+}
 }  // namespace myslam_hip
 }  // extern "C++"
 

@@ -22,5 +22,9 @@ int lk_bank_track(myslam_lk* h, const uint8_t* d_img, int step, size_t stride, c
 int pose_only_bank_launch(double* d_poses, const double* d_pts3d, const double* d_obs, const int32_t* d_counts, int batch, int cap, double fx, double fy,
                           double cx, double cy, double chi2_th, int rounds, int iters, uint8_t* d_outlier, int32_t* d_n_inliers, int32_t* d_status,
                           hipStream_t s);
+// the same kernel with pre_optimize plain optimize() calls before the rounds, for the loop closer's chain (pnp.hip): LoopClosing::OptimizeCurrentPose
+int pose_only_loop_launch(double* d_poses, const double* d_pts3d, const double* d_obs, const int32_t* d_counts, int batch, int cap, double fx, double fy,
+                          double cx, double cy, double chi2_th, int rounds, int iters, int pre_optimize, uint8_t* d_outlier, int32_t* d_n_inliers,
+                          int32_t* d_status, hipStream_t s);
 
 }  // namespace myslam_hip

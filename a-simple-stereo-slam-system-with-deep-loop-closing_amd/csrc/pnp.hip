@@ -22,6 +22,21 @@
 #include <vector>
 
 #include "common.h"
+#include "frontend_launch.h"
+
+// Everything a batch call touches besides the caller's buffers, allocated once (myslam_pnp_create): the calls themselves only enqueue.
+struct myslam_pnp {
+    int max_batch = 0, cap = 0, max_iterations = 0;
+    hipStream_t stream = nullptr;
+    int32_t* d_samples = nullptr;     // max_batch x max_iterations x 5
+    double* d_models = nullptr;       // max_batch x max_iterations x 12
+    int32_t* d_hyp = nullptr;         // max_batch x max_iterations: inliers per hypothesis
+    int32_t* d_ints = nullptr;        // max_batch x 6: winner record (2), PnP inliers, pose-only count, pose-only inliers, pose-only status
+    uint8_t* d_mask = nullptr;        // max_batch x cap: PnP's mask when the caller of the chain does not ask for it
+    double* d_pose = nullptr;         // max_batch x 7: the chain's working pose
+    double* d_p3 = nullptr;           // max_batch x cap x 3, f64 copies for the pose-only kernel
+    double* d_z2 = nullptr;           // max_batch x cap x 2
+};
 
 namespace myslam_hip {
 
@@ -322,11 +337,11 @@ __device__ __forceinline__ bool pnp_is_inlier(const PnpCam& K, const double* R, 
     return e <= thr;
 }
 
-// one wave per hypothesis: models[h] = {R (9), t (3)}, counts[h] = inliers (or -1 when EPnP found no model)
-__global__ void __launch_bounds__(64) k_pnp_hypotheses(const float* __restrict__ p3, const float* __restrict__ p2, int n, const int32_t* __restrict__ samples,
-                                                       PnpCam K, float thr, double* __restrict__ models, int32_t* __restrict__ counts) {
-    __shared__ PnpLds S;
-    const int lane = threadIdx.x, h = blockIdx.x;
+// one wave, hypothesis h of one problem: models[h] = {R (9), t (3)}, counts[h] = inliers (or -1 when EPnP found no model).
+// Shared by the one-problem kernel and the batch kernel (which hands in the item's rows of every array): one body, the same bits.
+__device__ __forceinline__ void pnp_hypothesis(PnpLds& S, const float* __restrict__ p3, const float* __restrict__ p2, int n, const int32_t* __restrict__ samples,
+                                               int h, const PnpCam& K, float thr, double* __restrict__ models, int32_t* __restrict__ counts) {
+    const int lane = threadIdx.x;
     if (lane == 0) {
         for (int i = 0; i < PNP_MP; i++) {
             const int id = samples[h * PNP_MP + i];
@@ -354,6 +369,64 @@ __global__ void __launch_bounds__(64) k_pnp_hypotheses(const float* __restrict__
         for (int i = 0; i < 9; i++) models[12 * h + i] = R[i];
         for (int i = 0; i < 3; i++) models[12 * h + 9 + i] = t[i];
     }
+}
+
+// one wave per hypothesis
+__global__ void __launch_bounds__(64) k_pnp_hypotheses(const float* __restrict__ p3, const float* __restrict__ p2, int n, const int32_t* __restrict__ samples,
+                                                       PnpCam K, float thr, double* __restrict__ models, int32_t* __restrict__ counts) {
+    __shared__ PnpLds S;
+    pnp_hypothesis(S, p3, p2, n, samples, blockIdx.x, K, thr, models, counts);
+}
+
+// d_counts[b] as every batch kernel reads it: below 0 is 0, above cap is cap (the LK tracker's rule)
+__device__ __forceinline__ int pnp_item_count(const int32_t* __restrict__ counts, int b, int cap) { return min(max(counts[b], 0), cap); }
+
+// RANSACPointSetRegistrator::getSubset on the device: cv::RNG((uint64)-1) and the rejection draw of myslam_solve_pnp_ransac, one lane per item (an
+// item's draws are sequential: the generator state after hypothesis k depends on how many draws k rejected).  samples: item b's `iterations` 5-subsets
+// at (b * iterations + k) * 5.  An item with fewer than min_points (>= 5) points is skipped BEFORE the draw: with n < 5 no fifth distinct index exists.
+// With n >= 5 a draw repeats one of at most four earlier indices, so the loop ends; it is bounded all the same (a slot that saw 4096 repeats
+// takes the lowest unused index — never reached with this generator, and a wave that cannot spin is worth more than the last word on that).
+__global__ void __launch_bounds__(64) k_pnp_sample_batch(const int32_t* __restrict__ counts, int batch, int cap, int min_points, int iterations,
+                                                         int32_t* __restrict__ samples) {
+    const int b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= batch) return;
+    const int n = pnp_item_count(counts, b, cap);
+    if (n < min_points || n < PNP_MP) return;
+    uint64_t state = (uint64_t)-1;
+    int32_t* out = samples + (size_t)b * iterations * PNP_MP;
+    for (int it = 0; it < iterations; it++) {
+        int idx[PNP_MP];
+#pragma unroll
+        for (int i = 0; i < PNP_MP; i++) {
+            bool found = false;
+            for (int tries = 0; tries < 4096 && !found; tries++) {
+                state = (uint64_t)(unsigned)state * 4164903690u + (unsigned)(state >> 32);       // cv::RNG::next
+                idx[i] = (int)((unsigned)state % (unsigned)n);                                   // uniform(0, n)
+                found = true;
+#pragma unroll
+                for (int j = 0; j < i; j++) found = found && idx[j] != idx[i];
+            }
+            for (int c = 0; !found; c++) {                                                       // c < PNP_MP <= n: ends
+                idx[i] = c; found = true;
+#pragma unroll
+                for (int j = 0; j < i; j++) found = found && idx[j] != c;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < PNP_MP; i++) out[(size_t)it * PNP_MP + i] = idx[i];
+    }
+}
+
+// one wave per (hypothesis, item), grid (iterations, batch); an item below min_points has no hypotheses (and no samples)
+__global__ void __launch_bounds__(64) k_pnp_hypotheses_batch(const float* __restrict__ p3, const float* __restrict__ p2, const int32_t* __restrict__ item_counts, int cap,
+                                                             int min_points, const int32_t* __restrict__ samples, PnpCam K, float thr,
+                                                             double* __restrict__ models, int32_t* __restrict__ counts) {
+    __shared__ PnpLds S;
+    const int b = blockIdx.y;
+    const int n = pnp_item_count(item_counts, b, cap);
+    if (n < min_points || n < PNP_MP) return;
+    const size_t o = (size_t)b * gridDim.x;
+    pnp_hypothesis(S, p3 + (size_t)b * cap * 3, p2 + (size_t)b * cap * 2, n, samples + o * PNP_MP, blockIdx.x, K, thr, models + o * 12, counts + o);
 }
 
 __device__ int pnp_update_iters(double p, double ep, int model_points, int max_iters) {
@@ -389,10 +462,11 @@ __device__ double pnp_cost(const PnpCam& K, const double* R, const double* t, co
     return wave_reduce_sum(s);
 }
 
-// out: pose7 (qx qy qz qw tx ty tz), inlier mask, result[0] = inlier count (0 = no model), result[1] = winning hypothesis
-__global__ void __launch_bounds__(64) k_pnp_select_refine(const float* __restrict__ p3, const float* __restrict__ p2, int n, const double* __restrict__ models,
-                                                          const int32_t* __restrict__ counts, int iterations, PnpCam K, float thr, double confidence,
-                                                          double* __restrict__ pose7, uint8_t* __restrict__ mask, int32_t* __restrict__ result) {
+// one wave, one problem.  out: pose7 (qx qy qz qw tx ty tz), inlier mask, result[0] = inlier count (0 = no model), result[1] = winning hypothesis;
+// returns result[0] (wave-uniform).  Without a model pose7 is left alone.  Shared by the one-problem kernel and the batch kernel.
+__device__ __forceinline__ int pnp_select_refine(const float* __restrict__ p3, const float* __restrict__ p2, int n, const double* __restrict__ models,
+                                                 const int32_t* __restrict__ counts, int iterations, const PnpCam& K, float thr, double confidence,
+                                                 double* __restrict__ pose7, uint8_t* __restrict__ mask, int32_t* __restrict__ result) {
     const int lane = threadIdx.x;
     int best = -1, max_good = 0, niters = iterations;
     for (int it = 0; it < niters; it++) {              // uniform replay of RANSACPointSetRegistrator::run's bookkeeping
@@ -403,7 +477,7 @@ __global__ void __launch_bounds__(64) k_pnp_select_refine(const float* __restric
             niters = pnp_update_iters(confidence, (double)(n - good) / n, PNP_MP, niters);
         }
     }
-    if (best < 0) { if (lane == 0) { result[0] = 0; result[1] = -1; } for (int i = lane; i < n; i += 64) mask[i] = 0; return; }
+    if (best < 0) { if (lane == 0) { result[0] = 0; result[1] = -1; } for (int i = lane; i < n; i += 64) mask[i] = 0; return 0; }
     double R[9], t[3];
     for (int i = 0; i < 9; i++) R[i] = models[12 * best + i];
     for (int i = 0; i < 3; i++) t[i] = models[12 * best + 9 + i];
@@ -498,6 +572,68 @@ __global__ void __launch_bounds__(64) k_pnp_select_refine(const float* __restric
         pose7[0] = x; pose7[1] = y; pose7[2] = z; pose7[3] = w; pose7[4] = t[0]; pose7[5] = t[1]; pose7[6] = t[2];
         result[0] = max_good; result[1] = best;
     }
+    return max_good;
+}
+
+__global__ void __launch_bounds__(64) k_pnp_select_refine(const float* __restrict__ p3, const float* __restrict__ p2, int n, const double* __restrict__ models,
+                                                          const int32_t* __restrict__ counts, int iterations, PnpCam K, float thr, double confidence,
+                                                          double* __restrict__ pose7, uint8_t* __restrict__ mask, int32_t* __restrict__ result) {
+    (void)pnp_select_refine(p3, p2, n, models, counts, iterations, K, thr, confidence, pose7, mask, result);
+}
+
+// one wave per item: pose7 batch x 7 (an item without a model keeps what was there), mask batch x cap (slots from the item's count on, and the whole row
+// of an item without a model: 0), n_inliers / status batch (status 0 = model, 1 = none)
+__global__ void __launch_bounds__(64) k_pnp_select_refine_batch(const float* __restrict__ p3, const float* __restrict__ p2, const int32_t* __restrict__ item_counts, int cap,
+                                                                int min_points, const double* __restrict__ models, const int32_t* __restrict__ counts, int iterations,
+                                                                PnpCam K, float thr, double confidence, double* __restrict__ pose7, uint8_t* __restrict__ mask,
+                                                                int32_t* __restrict__ result, int32_t* __restrict__ n_inliers, int32_t* __restrict__ status) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int n = pnp_item_count(item_counts, b, cap);
+    const bool run = n >= min_points && n >= PNP_MP;
+    uint8_t* m = mask + (size_t)b * cap;
+    int good = 0;
+    if (run) {
+        const size_t o = (size_t)b * iterations;
+        good = pnp_select_refine(p3 + (size_t)b * cap * 3, p2 + (size_t)b * cap * 2, n, models + o * 12, counts + o, iterations, K, thr, confidence,
+                                 pose7 + (size_t)b * 7, m, result + 2 * b);
+    }
+    for (int i = (run ? n : 0) + lane; i < cap; i += 64) m[i] = 0;
+    if (lane == 0) { n_inliers[b] = good; if (status) status[b] = good > 0 ? 0 : 1; }
+}
+
+// ---- the verification chain of LoopClosing::ComputeCorrectPose around the two kernels above (myslam_loop_verify_batch) ----
+// points and pixels of the items that have a model widened to f64, (double)float as toVec3 / toVec2 do; an item without one enters the pose-only
+// kernel with count 0 and the identity in its scratch pose.  pnp_pose_out (optional): PnP's own pose of the items that have one.
+__global__ void __launch_bounds__(256) k_verify_widen(const float* __restrict__ p3, const float* __restrict__ p2, const int32_t* __restrict__ item_counts, int cap,
+                                                      const int32_t* __restrict__ pnp_inliers, double* __restrict__ pose, double* __restrict__ P3, double* __restrict__ Z2,
+                                                      int32_t* __restrict__ vcounts, double* __restrict__ pnp_pose_out) {
+    const int b = blockIdx.x, t = threadIdx.x;
+    const bool model = pnp_inliers[b] > 0;
+    const int n = model ? pnp_item_count(item_counts, b, cap) : 0;
+    const size_t o = (size_t)b * cap;
+    for (int i = t; i < 3 * n; i += 256) P3[o * 3 + i] = (double)p3[o * 3 + i];
+    for (int i = t; i < 2 * n; i += 256) Z2[o * 2 + i] = (double)p2[o * 2 + i];
+    if (t == 0) vcounts[b] = n;
+    if (t < 7) {
+        if (!model) pose[7 * b + t] = t == 3 ? 1.0 : 0.0;
+        else if (pnp_pose_out) pnp_pose_out[7 * b + t] = pose[7 * b + t];
+    }
+}
+
+// the verdict (loopclosing.cpp:252, :262-270, :279) and the outputs of the items that reached the optimisation
+__global__ void __launch_bounds__(64) k_verify_finish(const int32_t* __restrict__ item_counts, int cap, int min_matches, const int32_t* __restrict__ pnp_inliers,
+                                                      const double* __restrict__ pose, const int32_t* __restrict__ po_inliers, double* __restrict__ pose7,
+                                                      uint8_t* __restrict__ outlier, int32_t* __restrict__ n_inliers, int32_t* __restrict__ status) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int n = pnp_item_count(item_counts, b, cap);
+    int st;
+    if (n < min_matches) st = MYSLAM_VERIFY_FEW_MATCHES;
+    else if (pnp_inliers[b] <= 0) st = MYSLAM_VERIFY_NO_MODEL;
+    else st = po_inliers[b] < min_matches ? MYSLAM_VERIFY_FEW_INLIERS : MYSLAM_VERIFY_CONFIRMED;
+    const bool ran = st == MYSLAM_VERIFY_CONFIRMED || st == MYSLAM_VERIFY_FEW_INLIERS;
+    for (int i = (ran ? n : 0) + lane; i < cap; i += 64) outlier[(size_t)b * cap + i] = 0;
+    if (ran && lane < 7) pose7[7 * b + lane] = pose[7 * b + lane];
+    if (lane == 0) { n_inliers[b] = ran ? po_inliers[b] : 0; status[b] = st; }
 }
 
 namespace {
@@ -568,6 +704,90 @@ int myslam_solve_pnp_ransac(const float* pts3d, const float* pts2d, int n, doubl
     { const int rc_ = copy_sync(pose7, d_pose, sizeof(double) * 7, hipMemcpyDeviceToHost, st); if (rc_) return rc_; }
     if (inlier) { const int rc_ = copy_sync(inlier, d_mask, (size_t)n, hipMemcpyDeviceToHost, st); if (rc_) return rc_; }
     if (n_inliers) *n_inliers = res[0];
+    return MYSLAM_OK;
+}
+
+int myslam_pnp_destroy(myslam_pnp* h) {
+    if (!h) return MYSLAM_ERR_INVALID;
+    (void)hipStreamSynchronize(h->stream);
+    void* ptrs[] = {h->d_samples, h->d_models, h->d_hyp, h->d_ints, h->d_mask, h->d_pose, h->d_p3, h->d_z2};
+    for (void* p : ptrs) if (p) (void)hipFree(p);
+    delete h;
+    return MYSLAM_OK;
+}
+
+int myslam_pnp_create(myslam_pnp** out, int max_batch, int cap, int max_iterations) {
+    if (!out || max_batch < 1 || max_batch > 65535 || cap < 1 || max_iterations < 1) return MYSLAM_ERR_INVALID;
+    if (cap > 4096 || max_iterations > 100000) return MYSLAM_ERR_CAPACITY;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MYSLAM_ERR_HIP;
+    myslam_pnp* h = new myslam_pnp();
+    h->max_batch = max_batch; h->cap = cap; h->max_iterations = max_iterations;
+    const size_t B = (size_t)max_batch, hyp = B * (size_t)max_iterations, pts = B * (size_t)cap;
+    hipError_t e = hipSuccess;
+    auto alloc = [&](auto** p, size_t count) { if (e == hipSuccess) e = hipMalloc((void**)p, count * sizeof(**p)); };
+    alloc(&h->d_samples, hyp * PNP_MP); alloc(&h->d_models, hyp * 12); alloc(&h->d_hyp, hyp); alloc(&h->d_ints, B * 6);
+    alloc(&h->d_mask, pts); alloc(&h->d_pose, B * 7); alloc(&h->d_p3, pts * 3); alloc(&h->d_z2, pts * 2);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        (void)myslam_pnp_destroy(h);
+        return e == hipErrorOutOfMemory ? MYSLAM_ERR_CAPACITY : MYSLAM_ERR_HIP;
+    }
+    *out = h;
+    return MYSLAM_OK;
+}
+
+int myslam_pnp_set_stream(myslam_pnp* h, void* hip_stream) {
+    if (!h) return MYSLAM_ERR_INVALID;
+    h->stream = (hipStream_t)hip_stream;
+    return MYSLAM_OK;
+}
+
+// sampling, hypotheses, select + refine of `batch` items on the handle's stream; an item below min_points gets no model
+static void pnp_batch_launch(myslam_pnp* h, const float* d_pts3d, const float* d_pts2d, const int32_t* d_counts, int batch, const PnpCam& K, int iterations,
+                             double reproj_error, double confidence, int min_points, double* d_pose7, uint8_t* d_inlier, int32_t* d_n_inliers,
+                             int32_t* d_status) {
+    const float thr = (float)(reproj_error * reproj_error);
+    const hipStream_t st = h->stream;
+    hipLaunchKernelGGL(k_pnp_sample_batch, dim3((batch + 63) / 64), dim3(64), 0, st, d_counts, batch, h->cap, min_points, iterations, h->d_samples);
+    hipLaunchKernelGGL(k_pnp_hypotheses_batch, dim3(iterations, batch), dim3(64), 0, st, d_pts3d, d_pts2d, d_counts, h->cap, min_points, h->d_samples, K, thr,
+                       h->d_models, h->d_hyp);
+    hipLaunchKernelGGL(k_pnp_select_refine_batch, dim3(batch), dim3(64), 0, st, d_pts3d, d_pts2d, d_counts, h->cap, min_points, h->d_models, h->d_hyp, iterations,
+                       K, thr, confidence, d_pose7, d_inlier, h->d_ints, d_n_inliers, d_status);
+}
+
+int myslam_solve_pnp_ransac_batch(myslam_pnp* h, const float* d_pts3d, const float* d_pts2d, const int32_t* d_counts, int batch, double fx, double fy,
+                                  double cx, double cy, int iterations, double reproj_error, double confidence, double* d_pose7, uint8_t* d_inlier,
+                                  int32_t* d_n_inliers, int32_t* d_status) {
+    if (!h || !d_pts3d || !d_pts2d || !d_counts || batch < 1 || iterations < 1 || !d_pose7 || !d_inlier || !d_n_inliers || !d_status) return MYSLAM_ERR_INVALID;
+    if (batch > h->max_batch || iterations > h->max_iterations) return MYSLAM_ERR_CAPACITY;
+    pnp_batch_launch(h, d_pts3d, d_pts2d, d_counts, batch, PnpCam{fx, fy, cx, cy}, iterations, reproj_error, confidence, PNP_MP, d_pose7, d_inlier, d_n_inliers,
+                     d_status);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    return MYSLAM_OK;
+}
+
+int myslam_loop_verify_batch(myslam_pnp* h, const float* d_pts3d, const float* d_pts2d, const int32_t* d_counts, int batch, double fx, double fy, double cx,
+                             double cy, int iterations, double reproj_error, double confidence, int min_matches, double chi2_th, int rounds, int iters,
+                             double* d_pose7, uint8_t* d_outlier, int32_t* d_n_inliers, int32_t* d_status, double* d_pnp_pose7, uint8_t* d_pnp_inlier) {
+    if (!h || !d_pts3d || !d_pts2d || !d_counts || batch < 1 || iterations < 1 || min_matches < 0 || rounds < 1 || iters < 1 || !d_pose7 || !d_outlier ||
+        !d_n_inliers || !d_status)
+        return MYSLAM_ERR_INVALID;
+    if (batch > h->max_batch || iterations > h->max_iterations) return MYSLAM_ERR_CAPACITY;
+    const hipStream_t st = h->stream;
+    int32_t* pnp_inl = h->d_ints + 2 * (size_t)h->max_batch;
+    int32_t* po_cnt = pnp_inl + h->max_batch;
+    int32_t* po_inl = po_cnt + h->max_batch;
+    int32_t* po_st = po_inl + h->max_batch;
+    pnp_batch_launch(h, d_pts3d, d_pts2d, d_counts, batch, PnpCam{fx, fy, cx, cy}, iterations, reproj_error, confidence, std::max(min_matches, PNP_MP), h->d_pose,
+                     d_pnp_inlier ? d_pnp_inlier : h->d_mask, pnp_inl, nullptr);
+    hipLaunchKernelGGL(k_verify_widen, dim3(batch), dim3(256), 0, st, d_pts3d, d_pts2d, d_counts, h->cap, pnp_inl, h->d_pose, h->d_p3, h->d_z2, po_cnt, d_pnp_pose7);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    const int rc = pose_only_loop_launch(h->d_pose, h->d_p3, h->d_z2, po_cnt, batch, h->cap, fx, fy, cx, cy, chi2_th, rounds, iters, 1, d_outlier, po_inl, po_st, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_verify_finish, dim3(batch), dim3(64), 0, st, d_counts, h->cap, min_matches, pnp_inl, h->d_pose, po_inl, d_pose7, d_outlier, d_n_inliers,
+                       d_status);
+    MYSLAM_HIP_CHECK(hipGetLastError());
     return MYSLAM_OK;
 }
 

@@ -468,4 +468,38 @@ inline bool solvePnPRansac(const std::vector<Point3f>& objectPoints, const std::
     return true;
 }
 
+// The same verification for a batch of loop candidates that already live on the device (myslam_pnp_*): the handle owns the workspace, the calls
+// take device pointers (points batch x cap x 3 / pixels batch x cap x 2 float, counts batch), enqueue on the handle's stream and never wait.
+// SolveBatch = solvePnPRansac per item (src/loopclosing.cpp:262-272); VerifyBatch = the arithmetic of LoopClosing::ComputeCorrectPose (:208-335):
+// PnP, OptimizeCurrentPose over all the item's matches, and the two size gates, status[b] = MYSLAM_VERIFY_*.
+class PnPSolver {
+    myslam_pnp* h_ = nullptr;
+    int maxBatch_, cap_, maxIterations_;
+public:
+    PnPSolver(int maxBatch, int cap, int maxIterations = 100) : maxBatch_(maxBatch), cap_(cap), maxIterations_(maxIterations) {
+        check(myslam_pnp_create(&h_, maxBatch, cap, maxIterations), "myslam_pnp_create");
+    }
+    ~PnPSolver() { if (h_) myslam_pnp_destroy(h_); }
+    PnPSolver(const PnPSolver&) = delete; PnPSolver& operator=(const PnPSolver&) = delete;
+    int maxBatch() const { return maxBatch_; }
+    int cap() const { return cap_; }
+    int maxIterations() const { return maxIterations_; }
+    void SetStream(void* hipStream) { check(myslam_pnp_set_stream(h_, hipStream), "myslam_pnp_set_stream"); }
+    void SolveBatch(const float* d_points3d, const float* d_points2d, const int32_t* d_counts, int batch, double fx, double fy, double cx, double cy,
+                    double* d_pose7, uint8_t* d_inlier, int32_t* d_nInliers, int32_t* d_status, int iterationsCount = 100,
+                    double reprojectionError = 5.991, double confidence = 0.99) {
+        check(myslam_solve_pnp_ransac_batch(h_, d_points3d, d_points2d, d_counts, batch, fx, fy, cx, cy, iterationsCount, reprojectionError, confidence,
+                                            d_pose7, d_inlier, d_nInliers, d_status), "myslam_solve_pnp_ransac_batch");
+    }
+    // d_pnpPose7 / d_pnpInlier (optional): PnP's own pose and consensus mask
+    void VerifyBatch(const float* d_points3d, const float* d_points2d, const int32_t* d_counts, int batch, double fx, double fy, double cx, double cy,
+                     double* d_pose7, uint8_t* d_outlier, int32_t* d_nInliers, int32_t* d_status, double* d_pnpPose7 = nullptr,
+                     uint8_t* d_pnpInlier = nullptr, int iterationsCount = 100, double reprojectionError = 5.991, double confidence = 0.99,
+                     int minMatches = 10, double chi2_th = 5.991, int numIterations = 4, int optimizeIters = 10) {
+        check(myslam_loop_verify_batch(h_, d_points3d, d_points2d, d_counts, batch, fx, fy, cx, cy, iterationsCount, reprojectionError, confidence,
+                                       minMatches, chi2_th, numIterations, optimizeIters, d_pose7, d_outlier, d_nInliers, d_status, d_pnpPose7, d_pnpInlier),
+              "myslam_loop_verify_batch");
+    }
+};
+
 }  // namespace myslam

@@ -695,6 +695,42 @@ int myslam_correct_map_points_device(const double* d_old_poses, const double* d_
 int myslam_solve_pnp_ransac(const float* pts3d, const float* pts2d, int n, double fx, double fy, double cx, double cy, int iterations,
                             double reproj_error, double confidence, double* pose7, uint8_t* inlier, int* n_inliers);
 
+/* The same for a BATCH of loop candidates on the device (several streams of cameras against one loop database verify several candidates per
+ * step): a handle owns every buffer the calls need — samples max_batch x max_iterations x 5 int32, models x 12 doubles, counts, the f64 copies of the
+ * chain below — so the two batch calls allocate nothing, never synchronise, never read device memory from the host and can be recorded between
+ * myslam_graph_begin / _end.  cap = match slots per item, <= 4096 (the pose-only kernel's limit); max_iterations <= 100000; beyond: MYSLAM_ERR_CAPACITY. */
+typedef struct myslam_pnp myslam_pnp;
+int myslam_pnp_create(myslam_pnp** out, int max_batch, int cap, int max_iterations);
+int myslam_pnp_destroy(myslam_pnp* h);
+int myslam_pnp_set_stream(myslam_pnp* h, void* hip_stream);
+/* cv::solvePnPRansac + cv::Rodrigues of src/loopclosing.cpp:262-272 for `batch` items, per item the semantics (and the bits of mask, count and
+ * winner) of myslam_solve_pnp_ransac; RANSACPointSetRegistrator::getSubset runs on the device, one lane per item, because the counts live there.
+ * Device pointers, asynchronous on the handle's stream.  d_pts3d batch x cap x 3, d_pts2d batch x cap x 2 (cap = the handle's), d_counts batch: a count
+ * below 0 is read as 0, one above cap as cap; slots from an item's count on are never read.  d_status[b] = 0: a model was found; 1: none (fewer than
+ * 5 points, or no hypothesis won) — then d_pose7[b] is left as it was (OpenCV leaves rvec / tvec alone), d_n_inliers[b] = 0.  d_inlier batch x cap:
+ * slots from the count on, and the row of an item without a model, are 0.  batch / iterations beyond the handle's: MYSLAM_ERR_CAPACITY, nothing enqueued. */
+int myslam_solve_pnp_ransac_batch(myslam_pnp* h, const float* d_pts3d /* batch x cap x 3 */, const float* d_pts2d /* batch x cap x 2 */,
+                                  const int32_t* d_counts, int batch, double fx, double fy, double cx, double cy,
+                                  int iterations, double reproj_error, double confidence,
+                                  double* d_pose7 /* batch x 7 */, uint8_t* d_inlier /* batch x cap */,
+                                  int32_t* d_n_inliers, int32_t* d_status);
+/* The arithmetic of LoopClosing::ComputeCorrectPose (src/loopclosing.cpp:208-335) for `batch` candidates in one enqueue: fewer than min_matches (10)
+ * matches -> give up (:252); PnP-RANSAC as above (:262-272); OptimizeCurrentPose (:275, :339-433) = myslam_pose_only_optimize_batch with
+ * pre_optimize 1 over ALL the item's matches, points and pixels widened (double)float, started from PnP's pose (chi2_th 5.991, rounds 4, iters 10 at the
+ * call site); fewer than min_matches inliers after it -> give up (:279).  d_status[b] = MYSLAM_VERIFY_*.  CONFIRMED and FEW_INLIERS write the
+ * optimised d_pose7[b], the item's d_outlier flags (vEdgeIsOutlier) and d_n_inliers[b]; NO_MODEL and FEW_MATCHES leave d_pose7[b] alone and report 0 inliers.
+ * d_outlier batch x cap: slots from the count on, and the rows of items that did not reach the optimisation, are 0.  d_pnp_pose7 (batch x 7) /
+ * d_pnp_inlier (batch x cap), either may be NULL: PnP's own pose (items with a model only) and consensus mask. */
+#define MYSLAM_VERIFY_CONFIRMED 0
+#define MYSLAM_VERIFY_NO_MODEL 1
+#define MYSLAM_VERIFY_FEW_MATCHES 2
+#define MYSLAM_VERIFY_FEW_INLIERS 3
+int myslam_loop_verify_batch(myslam_pnp* h, const float* d_pts3d, const float* d_pts2d, const int32_t* d_counts, int batch,
+                             double fx, double fy, double cx, double cy, int iterations, double reproj_error, double confidence,
+                             int min_matches, double chi2_th, int rounds, int iters,
+                             double* d_pose7, uint8_t* d_outlier, int32_t* d_n_inliers, int32_t* d_status,
+                             double* d_pnp_pose7, uint8_t* d_pnp_inlier);
+
 /* ------------------------------------------------------------------------------------------
  * Host-side formats of the reference's runner — plain host code, no device needed; the C++ forms live in
  * host/myslam_io.hpp and host/myslam_png.hpp.
