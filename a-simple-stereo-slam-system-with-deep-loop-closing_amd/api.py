@@ -308,6 +308,22 @@ def match_feature_pairs(train_idx, dist, loop_pyr_kps, cur_pyr_kps):
     return pairs[:n.value].copy()
 
 
+LOOP_MATCH_OK, LOOP_MATCH_FEW_PAIRS, LOOP_MATCH_FEW_POINTS = 0, 1, 2      # MYSLAM_LOOP_MATCH_*
+
+
+def loop_match_batch(d_loop_desc, d_n_loop, d_cur_desc, d_n_cur, d_loop_pyr, d_cur_pyr, batch, cap, d_cur_feat_xy, d_loop_feat_landmark, feat_cap,
+                     d_landmark_pos, landmark_stride, landmark_cap, min_matches, out_cap, d_train_idx, d_dist, d_pairs, d_n_pairs, d_valid_pairs,
+                     d_pts3d, d_pts2d, d_counts, d_status, stream=0):
+    """LoopClosing::MatchFeatures (loopclosing.cpp:167-203) and ComputeCorrectPose's gather (:210-253) for `batch` candidates on the device, in the
+    header's argument order: matcher, distance filter, (current id, loop id) set, landmark filter, cv::Point3f / Point2f arrays and counts as
+    PnPSolver.verify_batch reads them.  d_status batch i32 = LOOP_MATCH_* or a negative error code per item."""
+    ptrs = [C.c_void_p(x) for x in (d_loop_desc, d_n_loop, d_cur_desc, d_n_cur, d_loop_pyr, d_cur_pyr)]
+    outs = [C.c_void_p(x) for x in (d_train_idx, d_dist, d_pairs, d_n_pairs, d_valid_pairs, d_pts3d, d_pts2d, d_counts, d_status)]
+    _check(lib().myslam_loop_match_batch(*ptrs, int(batch), int(cap), C.c_void_p(d_cur_feat_xy), C.c_void_p(d_loop_feat_landmark), int(feat_cap),
+                                         C.c_void_p(d_landmark_pos), int(landmark_stride), int(landmark_cap), int(min_matches), int(out_cap), *outs,
+                                         C.c_void_p(stream or None)), "myslam_loop_match_batch")
+
+
 def triangulate_stereo(xl, yl, xr, yr, fx, fy, cx, cy, baseline):
     xl, yl, xr, yr = [np.ascontiguousarray(a, np.float32) for a in (xl, yl, xr, yr)]
     n = len(xl)

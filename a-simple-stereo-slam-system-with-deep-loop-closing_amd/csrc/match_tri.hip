@@ -281,6 +281,163 @@ __global__ __launch_bounds__(256) void k_triangulate(const float* __restrict__ x
     ok[o] = (ratio < 1e-2 && X[2] > 0) ? 1 : 0;
 }
 
+// ------------------------------------------------------------------------------------------------
+// LoopClosing::MatchFeatures after the matcher (src/loopclosing.cpp:175-198) and the point gather at the top of ComputeCorrectPose (:210-253)
+// for one loop candidate per workgroup: what myslam_match_feature_pairs and its callers' gather loops do on the host, on the matcher's output
+// where it lies.  The reference's std::set<std::pair<int,int>> becomes a sort of the keys (current id << 16 | loop id) in LDS followed by
+// adjacent-unique; every list is written by an ORDERED compaction (wave ballot + mbcnt, wave totals through LDS), so a slot never depends on
+// which wave came first.
+constexpr int LM_MAX_CAP = 16384;                 // keys of one item in LDS: 64 KB
+constexpr int LM_MAX_FEAT = 65536;                // a feature id is half a key
+constexpr int LM_MAX_OUT = 4096;                  // match slots of the verify handle (myslam_pnp_create)
+constexpr uint32_t LM_PAD = 0xffffffffu;          // sorts last; equal to the largest real key at most, and only the first m sorted keys are read
+
+struct LoopPairsArgs {
+    const int32_t* n_loop; const int32_t* n_cur;
+    const myslam_keypoint* loop_pyr; const myslam_keypoint* cur_pyr;
+    int cap;
+    const float* cur_feat_xy; const int32_t* loop_feat_landmark; int feat_cap;
+    const double* landmark_pos; size_t landmark_stride; int landmark_cap;
+    int min_matches, out_cap;
+    const int32_t* train_idx; const int32_t* dist;
+    int32_t* pairs; int32_t* n_pairs; int32_t* valid_pairs;
+    float* pts3d; float* pts2d; int32_t* counts; int32_t* status;
+};
+
+// rank of this thread's element among the block's flagged ones, in thread order; total = their number (block-uniform).  s_w: one int per wave.
+__device__ __forceinline__ int block_rank(bool f, int* s_w, int& total) {
+    const int wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const unsigned long long m = __ballot(f);
+    const int in_wave = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    if ((threadIdx.x & 63) == 0) s_w[wv] = __popcll(m);
+    __syncthreads();
+    int before = 0, tot = 0;
+    for (int w = 0; w < nw; w++) { const int c = s_w[w]; before += (w < wv) ? c : 0; tot += c; }
+    __syncthreads();                                         // s_w is free again
+    total = tot;
+    return before + in_wave;
+}
+
+__global__ __launch_bounds__(1024) void k_loop_pairs(LoopPairsArgs a) {
+    MYSLAM_SIDE_PRIO();
+    extern __shared__ uint32_t s_keys[];                     // next power of two >= cap keys
+    __shared__ int s_w[16], s_red[16];
+    const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, wv = tid >> 6, nw = nt >> 6;
+    const int nl = min(max(a.n_loop[b], 0), a.cap), nc = min(max(a.n_cur[b], 0), a.cap);
+    const size_t row0 = (size_t)b * a.cap, feat0 = (size_t)b * a.feat_cap;
+    auto finish = [&](int status, int count) { if (tid == 0) { a.status[b] = status; a.counts[b] = count; } };
+    if (nl == 0 || nc == 0) {                                // an empty side: no match, an empty set
+        if (tid == 0) a.n_pairs[b] = 0;
+        finish(0 < a.min_matches ? MYSLAM_LOOP_MATCH_FEW_PAIRS : MYSLAM_LOOP_MATCH_OK, 0);
+        return;
+    }
+    // min_dist of :175-177
+    int mn = 0x7fffffff;
+    for (int i = tid; i < nl; i += nt) mn = min(mn, a.dist[row0 + i]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mn = min(mn, __shfl_xor(mn, o, 64));
+    if ((tid & 63) == 0) s_red[wv] = mn;
+    __syncthreads();
+    mn = s_red[0];
+    for (int w = 1; w < nw; w++) mn = min(mn, s_red[w]);
+    const double lim = fmax(2.0 * (double)mn, 30.0);         // :183
+    // kept rows -> keys, in row order (:182-186)
+    int m = 0;
+    bool bad = false;
+    for (int base = 0; base < nl; base += nt) {
+        const int i = base + tid;
+        bool keep = false;
+        uint32_t key = 0;
+        if (i < nl && (double)a.dist[row0 + i] <= lim) {
+            const int t = a.train_idx[row0 + i];
+            if (t < 0 || t >= nc) bad = true;
+            else {
+                const int c = a.cur_pyr[row0 + t].class_id, l = a.loop_pyr[row0 + i].class_id;
+                if ((uint32_t)c >= (uint32_t)a.feat_cap || (uint32_t)l >= (uint32_t)a.feat_cap) bad = true;
+                else { keep = true; key = ((uint32_t)c << 16) | (uint32_t)l; }
+            }
+        }
+        int tot;
+        const int r = block_rank(keep, s_w, tot);
+        if (keep) s_keys[m + r] = key;
+        m += tot;
+    }
+    if (__syncthreads_or(bad)) {
+        if (tid == 0) a.n_pairs[b] = 0;
+        finish(MYSLAM_ERR_INVALID, 0);
+        return;
+    }
+    // the set's order: bitonic sort over the next power of two >= m (m >= 1: the minimum row is always kept), padding last
+    int S = 1;
+    while (S < m) S <<= 1;
+    for (int i = m + tid; i < S; i += nt) s_keys[i] = LM_PAD;
+    __syncthreads();
+    for (int k = 2; k <= S; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (S >> 1); t += nt) {
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
+                const uint32_t x = s_keys[i], y = s_keys[l];
+                if ((x > y) == ((i & k) == 0)) { s_keys[i] = y; s_keys[l] = x; }
+            }
+            __syncthreads();
+        }
+    // one entry per feature pair (:188-192): adjacent-unique, compacted in place — an element moves to a slot at or below its own, and the
+    // last slot of a chunk can only be rewritten with its own value, so the next chunk still finds its left neighbour there
+    int u = 0;
+    for (int base = 0; base < m; base += nt) {
+        const int i = base + tid;
+        bool first = false;
+        uint32_t key = 0;
+        if (i < m) { key = s_keys[i]; first = i == 0 || s_keys[i - 1] != key; }
+        int tot;
+        const int r = block_rank(first, s_w, tot);            // (its barriers stand between the reads above and the writes below)
+        if (first) {
+            s_keys[u + r] = key;
+            a.pairs[2 * (row0 + u + r)] = (int32_t)(key >> 16);
+            a.pairs[2 * (row0 + u + r) + 1] = (int32_t)(key & 0xffffu);
+        }
+        u += tot;
+        __syncthreads();
+    }
+    if (tid == 0) a.n_pairs[b] = u;
+    if (u < a.min_matches) { finish(MYSLAM_LOOP_MATCH_FEW_PAIRS, 0); return; }      // :198
+    // ComputeCorrectPose :218-237: pairs whose loop feature has no map point leave the set.  Counted first: nothing is written unless all fits.
+    int nsurv = 0;
+    bad = false;
+    for (int k = tid; k < u; k += nt) {
+        const int slot = a.loop_feat_landmark[feat0 + (s_keys[k] & 0xffffu)];
+        if (slot < -1 || slot >= a.landmark_cap) bad = true;
+        else nsurv += slot >= 0;
+    }
+    nsurv = wave_reduce_sum(nsurv);
+    if ((tid & 63) == 0) s_red[wv] = nsurv;
+    if (__syncthreads_or(bad)) { finish(MYSLAM_ERR_INVALID, 0); return; }
+    nsurv = 0;
+    for (int w = 0; w < nw; w++) nsurv += s_red[w];
+    if (nsurv > a.out_cap) { finish(MYSLAM_ERR_CAPACITY, 0); return; }
+    const size_t out0 = (size_t)b * a.out_cap;
+    const double* pos = a.landmark_pos + (size_t)b * a.landmark_stride * 3;
+    int n = 0;
+    for (int base = 0; base < u; base += nt) {
+        const int k = base + tid;
+        uint32_t key = 0;
+        int slot = -1;
+        if (k < u) { key = s_keys[k]; slot = a.loop_feat_landmark[feat0 + (key & 0xffffu)]; }
+        int tot;
+        const int r = block_rank(slot >= 0, s_w, tot);
+        if (slot >= 0) {
+            const size_t o = out0 + n + r;
+            const int c = (int)(key >> 16);
+            a.valid_pairs[2 * o] = c; a.valid_pairs[2 * o + 1] = (int32_t)(key & 0xffffu);
+            a.pts2d[2 * o] = a.cur_feat_xy[2 * (feat0 + c)]; a.pts2d[2 * o + 1] = a.cur_feat_xy[2 * (feat0 + c) + 1];      // :223-224
+#pragma unroll
+            for (int d = 0; d < 3; d++) a.pts3d[3 * o + d] = (float)pos[3 * (size_t)slot + d];      // cv::Point3f(pos(0), pos(1), pos(2)), :226
+        }
+        n += tot;
+    }
+    finish(n < a.min_matches ? MYSLAM_LOOP_MATCH_FEW_POINTS : MYSLAM_LOOP_MATCH_OK, n);      // :252
+}
+
 }  // namespace myslam_hip
 
 using namespace myslam_hip;
@@ -372,6 +529,33 @@ int myslam_match_feature_pairs(const int32_t* train_idx, const int32_t* dist, in
     v.erase(std::unique(v.begin(), v.end()), v.end());
     for (size_t k = 0; k < v.size(); k++) { pairs[2 * k] = v[k].first; pairs[2 * k + 1] = v[k].second; }
     *n_pairs = (int)v.size();
+    return MYSLAM_OK;
+}
+
+// LoopClosing::MatchFeatures (src/loopclosing.cpp:167-203) and the gather of ComputeCorrectPose (:210-253) for `batch` candidates: the matcher's
+// launch as myslam_hamming_match_batch makes it, then k_loop_pairs on its output — two dependent launches, nothing allocated, nothing read back.
+int myslam_loop_match_batch(const uint8_t* d_loop_desc, const int32_t* d_n_loop, const uint8_t* d_cur_desc, const int32_t* d_n_cur,
+                            const myslam_keypoint* d_loop_pyr, const myslam_keypoint* d_cur_pyr, int batch, int cap,
+                            const float* d_cur_feat_xy, const int32_t* d_loop_feat_landmark, int feat_cap,
+                            const double* d_landmark_pos, size_t landmark_stride, int landmark_cap, int min_matches, int out_cap,
+                            int32_t* d_train_idx, int32_t* d_dist, int32_t* d_pairs, int32_t* d_n_pairs, int32_t* d_valid_pairs,
+                            float* d_pts3d, float* d_pts2d, int32_t* d_counts, int32_t* d_status, void* hip_stream) {
+    if (!d_loop_desc || !d_n_loop || !d_cur_desc || !d_n_cur || !d_loop_pyr || !d_cur_pyr || !d_cur_feat_xy || !d_loop_feat_landmark || !d_landmark_pos ||
+        !d_train_idx || !d_dist || !d_pairs || !d_n_pairs || !d_valid_pairs || !d_pts3d || !d_pts2d || !d_counts || !d_status)
+        return MYSLAM_ERR_INVALID;
+    if (batch <= 0 || cap <= 0 || out_cap <= 0 || feat_cap <= 0 || landmark_cap < 0) return MYSLAM_ERR_INVALID;
+    if (cap > LM_MAX_CAP || feat_cap > LM_MAX_FEAT || out_cap > LM_MAX_OUT) return MYSLAM_ERR_CAPACITY;
+    hipStream_t s = (hipStream_t)hip_stream;
+    int npad = 64;
+    while (npad < cap) npad <<= 1;
+    // the limit belongs to the function, not to a launch (see ba.hip): always what the largest cap needs
+    MYSLAM_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(k_loop_pairs), hipFuncAttributeMaxDynamicSharedMemorySize, LM_MAX_CAP * 4));
+    const int rc = myslam_hamming_match_batch(d_loop_desc, d_n_loop, d_cur_desc, d_n_cur, batch, cap, d_train_idx, d_dist, hip_stream);
+    if (rc) return rc;
+    const LoopPairsArgs a{d_n_loop, d_n_cur, d_loop_pyr, d_cur_pyr, cap, d_cur_feat_xy, d_loop_feat_landmark, feat_cap, d_landmark_pos, landmark_stride,
+                          landmark_cap, min_matches, out_cap, d_train_idx, d_dist, d_pairs, d_n_pairs, d_valid_pairs, d_pts3d, d_pts2d, d_counts, d_status};
+    hipLaunchKernelGGL(k_loop_pairs, dim3(batch), dim3(npad >= 2048 ? 1024 : 256), (size_t)npad * 4, s, a);
+    MYSLAM_HIP_CHECK(hipGetLastError());
     return MYSLAM_OK;
 }
 

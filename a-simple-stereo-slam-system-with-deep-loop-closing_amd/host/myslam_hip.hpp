@@ -502,4 +502,21 @@ public:
     }
 };
 
+// LoopClosing::MatchFeatures (src/loopclosing.cpp:167-203) and the gather of ComputeCorrectPose (:210-253) for a batch of candidates whose key-frames
+// live on the device: descriptors and mvPyramidKeyPoints of the loop and current key-frames (batch x cap), the current features' pixels and the loop
+// features' landmark slots (batch x featCap, -1 = no map point), the landmark positions (landmarkStride 0 = one table for all items).  Writes the
+// matcher's output, _msetValidFeatureMatches in the std::set's order, and vLoopPoints3d / vCurrentPoints2d / their count exactly where
+// PnPSolver::VerifyBatch reads them (outCap = that solver's cap); status[b] = MYSLAM_LOOP_MATCH_* or a negative error.  Enqueues and returns.
+inline void MatchFeaturesBatch(const uint8_t* d_loopDescriptors, const int32_t* d_nLoop, const uint8_t* d_currentDescriptors, const int32_t* d_nCurrent,
+                               const KeyPoint* d_loopPyramidKeyPoints, const KeyPoint* d_currentPyramidKeyPoints, int batch, int cap,
+                               const float* d_currentFeaturePixels, const int32_t* d_loopFeatureLandmark, int featCap, const double* d_landmarkPos,
+                               size_t landmarkStride, int landmarkCap, int outCap, int32_t* d_trainIdx, int32_t* d_distance, int32_t* d_pairs,
+                               int32_t* d_nPairs, int32_t* d_validPairs, float* d_points3d, float* d_points2d, int32_t* d_counts, int32_t* d_status,
+                               void* hipStream = nullptr, int minMatches = 10) {
+    check(myslam_loop_match_batch(d_loopDescriptors, d_nLoop, d_currentDescriptors, d_nCurrent, d_loopPyramidKeyPoints, d_currentPyramidKeyPoints, batch,
+                                  cap, d_currentFeaturePixels, d_loopFeatureLandmark, featCap, d_landmarkPos, landmarkStride, landmarkCap, minMatches,
+                                  outCap, d_trainIdx, d_distance, d_pairs, d_nPairs, d_validPairs, d_points3d, d_points2d, d_counts, d_status, hipStream),
+          "myslam_loop_match_batch");
+}
+
 }  // namespace myslam

@@ -194,6 +194,47 @@ int myslam_expand_pyramid_keypoints(const myslam_keypoint* feats, int n, int nle
 int myslam_match_feature_pairs(const int32_t* train_idx, const int32_t* dist, int n_query, const myslam_keypoint* loop_pyr_kps,
                                const myslam_keypoint* cur_pyr_kps, int n_train, int32_t* pairs, int* n_pairs);
 
+/* LoopClosing::MatchFeatures (src/loopclosing.cpp:167-203) and the point gather at the top of LoopClosing::ComputeCorrectPose (:210-253) for `batch`
+ * (current key-frame, loop key-frame) candidates on the device: everything between "the database names a loop key-frame" and
+ * myslam_loop_verify_batch, whose d_pts3d / d_pts2d / d_counts it writes (out_cap = that handle's cap).  Two dependent launches on hip_stream —
+ * the matcher exactly as myslam_hamming_match_batch launches it (query = loop, train = current, :172), then one workgroup per item — nothing
+ * allocated, nothing synchronised, no device memory read from the host: recordable between myslam_graph_begin / _end.  Per item b:
+ *   d_train_idx, d_dist   the matcher's output, the bits of myslam_hamming_match_batch;
+ *   kept rows             (double)dist <= max(2.0 * min_dist, 30.0) with min_dist over the item's n_loop rows (:175-183);
+ *   d_pairs, d_n_pairs    every kept row as (cur_pyr[train_idx].class_id, loop_pyr[row].class_id), duplicates collapsed, ascending current id then
+ *                         loop id: _msetValidFeatureMatches as the reference's std::set<std::pair<int,int>> iterates (:184-194), and its size;
+ *   fewer than min_matches (10 at :198) pairs: MatchFeatures returns false — d_status[b] = MYSLAM_LOOP_MATCH_FEW_PAIRS, d_counts[b] = 0;
+ *   d_valid_pairs, d_pts2d, d_pts3d, d_counts   otherwise the set is walked in order and pairs whose loop feature has no map point
+ *                         (d_loop_feat_landmark = -1: mpMapPoint.lock() is null) leave it (:218-237); survivor k keeps its pair, takes the current
+ *                         feature's pixel (:223-224) and (float) of the landmark's f64 position, rounded to nearest even as cv::Point3f(pos(0),
+ *                         pos(1), pos(2)) does (:225-226); d_counts[b] = the number of survivors.  Fewer than min_matches (10 at :252):
+ *                         MYSLAM_LOOP_MATCH_FEW_POINTS, count and arrays still written; else MYSLAM_LOOP_MATCH_OK.
+ * n_loop == 0 or n_cur == 0: the reference dereferences the end of an empty range (:175-177); here that item has zero pairs (FEW_PAIRS).
+ * Counts above cap are read as cap, counts below 0 as 0; slots from an item's count on are never read, and class_id is the only field read of a
+ * pyramid key-point, for kept rows only.  Output slots from the written count on are left as they were.  Per-item errors, each with d_counts[b] = 0
+ * and nothing else of that stage written: MYSLAM_ERR_INVALID — a class_id outside [0, feat_cap) (then d_n_pairs[b] = 0 too) or a landmark slot outside
+ * [-1, landmark_cap); MYSLAM_ERR_CAPACITY — more survivors than out_cap (nothing is truncated).  Other items are unaffected.
+ * Call-level, nothing enqueued: NULL pointers, batch / cap / out_cap / feat_cap <= 0, landmark_cap < 0 -> MYSLAM_ERR_INVALID; cap > 16384 (one item's keys are sorted in
+ * LDS), feat_cap > 65536 (a feature id is half a 32-bit key), out_cap > 4096 (myslam_pnp_create's limit) -> MYSLAM_ERR_CAPACITY. */
+#define MYSLAM_LOOP_MATCH_OK 0
+#define MYSLAM_LOOP_MATCH_FEW_PAIRS 1
+#define MYSLAM_LOOP_MATCH_FEW_POINTS 2
+int myslam_loop_match_batch(
+    const uint8_t* d_loop_desc, const int32_t* d_n_loop,      /* query: loop KF's mORBDescriptors, item b at + b*cap*32 */
+    const uint8_t* d_cur_desc,  const int32_t* d_n_cur,       /* train: current KF's */
+    const myslam_keypoint* d_loop_pyr, const myslam_keypoint* d_cur_pyr,   /* mvPyramidKeyPoints, item b at + b*cap; only class_id is read */
+    int batch, int cap,
+    const float*   d_cur_feat_xy,          /* batch x feat_cap x 2: mvpFeaturesLeft[i]->mkpPosition.pt of the current KF */
+    const int32_t* d_loop_feat_landmark,   /* batch x feat_cap: slot in the item's landmark table, -1 = mpMapPoint.lock() is null */
+    int feat_cap,
+    const double*  d_landmark_pos, size_t landmark_stride, int landmark_cap,   /* item b's table at + b*landmark_stride*3 doubles; stride 0 = one shared table */
+    int min_matches, int out_cap,
+    int32_t* d_train_idx, int32_t* d_dist,         /* batch x cap: the matcher's output, as myslam_hamming_match_batch writes it */
+    int32_t* d_pairs, int32_t* d_n_pairs,          /* batch x cap x 2 (current id, loop id) in std::set order; the set's size after :194 */
+    int32_t* d_valid_pairs,                        /* batch x out_cap x 2: the pairs that survive :218-237, same order */
+    float* d_pts3d, float* d_pts2d, int32_t* d_counts,   /* batch x out_cap x 3 / x 2 / batch: verify_batch's inputs */
+    int32_t* d_status, void* hip_stream);
+
 /* ------------------------------------------------------------------------------------------
  * Triangulation — replaces triangulation() include/myslam/algorithm.h:16-33 with the stereo rig
  * of src/system.cpp:108-116,141-145 and Camera::pixel2camera src/camera.cpp:22-26.
