@@ -178,7 +178,10 @@ int myslam_orb_debug_readback(myslam_orb* h, int what, int b, int level, void* o
  * ------------------------------------------------------------------------------------------ */
 int myslam_hamming_match(const uint8_t* query, int nq, const uint8_t* train, int nt,
                          int32_t* train_idx, int32_t* dist);
-/* batch: pair p uses d_q + p*cap*32 (d_nq[p] rows) vs d_t + p*cap*32 (d_nt[p] rows) */
+/* batch: pair p uses d_q + p*cap*32 (d_nq[p] rows) vs d_t + p*cap*32 (d_nt[p] rows).  A count above cap acts as cap; a negative
+ * d_nq[p] writes nothing for that pair; a negative d_nt[p] acts as 0 (train_idx = -1, dist = -1 for each of the pair's query rows).
+ * Slots past a pair's query count are never written.  A train index takes 20 bits beside the distance: nt >= 2^20 (single call) and
+ * cap >= 2^20 (batch) return MYSLAM_ERR_UNSUPPORTED before anything is launched; 2^20 - 1 rows are accepted. */
 int myslam_hamming_match_batch(const uint8_t* d_q, const int32_t* d_nq, const uint8_t* d_t, const int32_t* d_nt,
                                int batch, int cap, int32_t* d_train_idx, int32_t* d_dist, void* hip_stream);
 /* keep[i] = dist[i] <= max(2*min_dist, 30.0)   (loopclosing.cpp:175-186); host-side bookkeeping */
@@ -243,7 +246,10 @@ int myslam_loop_match_batch(
 int myslam_triangulate_stereo(const float* xl, const float* yl, const float* xr, const float* yr, int n,
                               double fx, double fy, double cx, double cy, double baseline,
                               double* xyz, uint8_t* ok);
-/* batch: left keypoint i of pair p is matched to right keypoint d_match[p*cap+i] (<0 = none) */
+/* batch: left keypoint i of pair p is matched to right keypoint d_match[p*cap+i].  An index below 0 or at or above cap means "no
+ * match": ok = 0, xyz = 0.  An index in [number of right key-points, cap) is NOT an error: that slot of d_kps_r is read as it is, so
+ * the caller keeps every slot readable.  Only x and y of a record are read.  d_nl[p] above cap acts as cap, a negative one writes
+ * nothing; slots past it are never written.  A non-finite coordinate gives ok = 0 (xyz unspecified). */
 int myslam_triangulate_stereo_batch(const myslam_keypoint* d_kps_l, const myslam_keypoint* d_kps_r,
                                     const int32_t* d_match, const int32_t* d_nl, int batch, int cap,
                                     double fx, double fy, double cx, double cy, double baseline,
