@@ -239,6 +239,17 @@ class ORBextractor:
                                              C.c_void_p(d_masks or None), C.c_void_p(d_kps), C.c_void_p(d_counts),
                                              C.c_void_p(d_status or None), cap), "myslam_orb_detect_batch")
 
+    def process_keyframes_batch(self, d_imgs, batch, rows, cols, step, img_stride, d_feat_xy, d_n_feat, feat_cap, d_pyr_kps, d_desc, d_counts,
+                                d_status, cap):
+        """The ORB half of LoopClosing::ProcessNewKF (loopclosing.cpp:93-113) for `batch` key-frames on the device, in the header's argument
+        order: expansion of every feature over the levels, ScreenAndComputeKPsParams, CalcDescriptors.  Writes mvPyramidKeyPoints (batch x cap),
+        mORBDescriptors (batch x cap x 32) and their counts where loop_match_batch reads them; d_status batch i32 = 0 or ERR_CAPACITY per item.
+        Enqueues on the handle's stream and returns."""
+        _check(lib().myslam_orb_process_keyframes_batch(self._h, C.c_void_p(d_imgs), int(batch), int(rows), int(cols), int(step),
+                                                        C.c_size_t(img_stride), C.c_void_p(d_feat_xy), C.c_void_p(d_n_feat), int(feat_cap),
+                                                        C.c_void_p(d_pyr_kps), C.c_void_p(d_desc), C.c_void_p(d_counts), C.c_void_p(d_status),
+                                                        int(cap)), "myslam_orb_process_keyframes_batch")
+
     # stage taps
     def debug_pyramid(self, image, level, blurred=False):
         img = self._img(image)

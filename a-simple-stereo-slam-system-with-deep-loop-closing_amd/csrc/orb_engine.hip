@@ -131,6 +131,12 @@ struct myslam_orb {
     int ensure(int batch, int r, int c, bool needMask);
     int ensure_stage(size_t imgBytes, size_t maskBytes, int cap);
     int ensure_fast_stat();
+    // ProcessNewKF's ORB half for a batch of key-frames (myslam_orb_process_keyframes_batch): the screened key-points and keep flags of
+    // batch x feat_cap x nlevels pyramid rows
+    myslam_keypoint* d_pkfRows = nullptr; uint8_t* d_pkfKeep = nullptr; size_t pkfRowCap = 0;
+    int ensure_pkf(size_t nrows);
+    int process_keyframes(const uint8_t* d_imgs, int batch, int r, int c, int step, size_t stride, const float* d_feat_xy, const int32_t* d_n_feat,
+                          int feat_cap, myslam_keypoint* d_pyr_kps, uint8_t* d_desc, int32_t* d_counts, int32_t* d_stat, int cap);
     // level 0 read in place (orb_plan.h ext0): both plans, set by every entry point before it builds a pyramid
     void set_in_place(const uint8_t* p, size_t stride, int pitch, int n0) {
         full.ext0 = det.ext0 = p; full.ext0Stride = det.ext0Stride = stride; full.ext0Pitch = det.ext0Pitch = pitch; full.ext0N = det.ext0N = n0;
@@ -584,6 +590,52 @@ int myslam_orb::ensure_fast_stat() {
     return MYSLAM_OK;
 }
 
+// scratch of process_keyframes, grown like ensure()'s blocks: the stream is drained before a block moves, and whatever was recorded against the
+// old one is dropped
+int myslam_orb::ensure_pkf(size_t nrows) {
+    if (nrows <= pkfRowCap) return MYSLAM_OK;
+    MYSLAM_HIP_CHECK(hipStreamSynchronize(stream));
+    gen++; drop_host_graphs();
+    pkfRowCap = 0;
+    int rc;
+    if ((rc = dev_alloc(d_pkfRows, nrows))) return rc;
+    if ((rc = dev_alloc(d_pkfKeep, nrows))) return rc;
+    pkfRowCap = nrows;
+    return MYSLAM_OK;
+}
+
+// LoopClosing::ProcessNewKF's ORB half (src/loopclosing.cpp:93-113) for `batch` key-frames: ComputePyramid (ORBextractor.cpp:1096), the Gaussian
+// of every level (:1194-1199), then expansion + screening, ordered compaction and descriptors (launch_process_keyframes).  Shares the pyramid
+// and blurred blocks with run_batch and leaves the rest of the handle alone: no FAST launch, so the statistics ping-pong does not move.
+int myslam_orb::process_keyframes(const uint8_t* d_imgs, int batch, int r, int c, int step, size_t stride, const float* d_feat_xy,
+                                  const int32_t* d_n_feat, int feat_cap, myslam_keypoint* d_pyr_kps, uint8_t* d_desc, int32_t* d_counts,
+                                  int32_t* d_stat, int cap) {
+    if (!d_imgs || !d_feat_xy || !d_n_feat || !d_pyr_kps || !d_desc || !d_counts || !d_stat) return MYSLAM_ERR_INVALID;
+    if (batch <= 0 || r <= 0 || c <= 0 || step < c || feat_cap <= 0 || cap <= 0) return MYSLAM_ERR_INVALID;
+    // grid limits: an item's rows along x (a wave each, four per block), the items along y
+    if (batch > 65535 || (size_t)feat_cap * nlevels > ((size_t)1 << 24) || cap > (1 << 24)) return MYSLAM_ERR_CAPACITY;
+    int rc = ensure(batch, r, c, false);
+    if (rc) return rc;
+    if (optBlurMfma && (rc = ensure_blur_tables())) return rc;
+    const int rowCap = feat_cap * nlevels;
+    if ((rc = ensure_pkf((size_t)batch * rowCap))) return rc;
+    // the call's own count and status words ride in the first launch's clear list (nothing of an earlier call is left in it); every image is
+    // copied into the pyramid block, as stage_pyramid does
+    clr = {{reinterpret_cast<uint32_t*>(d_counts), reinterpret_cast<uint32_t*>(d_stat), nullptr, nullptr}, {batch, batch, 0, 0}};
+    set_in_place(nullptr, 0, 0, 0);
+    rc = build_pyramids(d_imgs, batch, step, stride, nullptr, nlevels);
+    clr = ZeroArgs{};
+    if (rc) return rc;
+    if ((rc = blur_levels(batch, nlevels, stream))) return rc;
+    {
+        ScopedProf sp(P_SCREEN, stream);
+        launch_process_keyframes(full, PkfArgs{d_pyr, d_blur, full.pyrBytes, d_feat_xy, d_n_feat, feat_cap, d_pkfRows, d_pkfKeep, rowCap,
+                                               d_pyr_kps, d_desc, d_counts, d_stat, cap}, batch, stream);
+    }
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    return MYSLAM_OK;
+}
+
 // single-image entry points (Screen / CalcDescriptors, the debug taps): stage the caller's image (and mask) and build its pyramid — nothing is read in place
 int myslam_orb::stage_pyramid(const uint8_t* img, int r, int c, int step, const uint8_t* mask, int ncap) {
     const size_t bytes = (size_t)r * step;
@@ -619,7 +671,7 @@ int myslam_orb::ensure_stage(size_t imgBytes, size_t maskBytes, int cap) {
 
 void myslam_orb::free_all() {
     void* ptrs[] = {d_blurTab, d_fastStat, d_octTab, d_stripTab, d_resizeTab, d_pyr, d_blur, d_mask, d_cand, d_sort, d_candCount, d_selCount, d_status, d_sel, d_order, d_stageImg, d_stageMask,
-                    d_stageOut, d_stageKps2, d_stageKeep};
+                    d_stageOut, d_stageKps2, d_stageKeep, d_pkfRows, d_pkfKeep};
     for (void* p : ptrs) if (p) (void)hipFree(p);
     if (aux) { (void)hipStreamSynchronize(aux); (void)hipStreamDestroy(aux); (void)hipEventDestroy(evFork); (void)hipEventDestroy(evJoin); aux = nullptr; }
     drop_host_graphs();
@@ -743,6 +795,14 @@ int myslam_orb_detect_batch(myslam_orb* h, const uint8_t* d_imgs, int batch, int
                             const uint8_t* d_masks, myslam_keypoint* d_kps, int32_t* d_counts, int32_t* d_status, int cap) {
     if (!h) return MYSLAM_ERR_INVALID;
     return h->run_batch(d_imgs, batch, rows, cols, step, img_stride, d_masks, d_kps, nullptr, d_counts, d_status, cap, true);
+}
+
+int myslam_orb_process_keyframes_batch(myslam_orb* h, const uint8_t* d_imgs, int batch, int rows, int cols, int step, size_t img_stride,
+                                       const float* d_feat_xy, const int32_t* d_n_feat, int feat_cap, myslam_keypoint* d_pyr_kps,
+                                       uint8_t* d_desc, int32_t* d_counts, int32_t* d_status, int cap) {
+    if (!h) return MYSLAM_ERR_INVALID;
+    return h->process_keyframes(d_imgs, batch, rows, cols, step, img_stride, d_feat_xy, d_n_feat, feat_cap, d_pyr_kps, d_desc, d_counts,
+                                d_status, cap);
 }
 
 static int host_extract(myslam_orb* h, const uint8_t* img, int rows, int cols, int step, const uint8_t* mask, int mask_step,

@@ -2867,6 +2867,96 @@ __global__ __launch_bounds__(256) void k_calc_desc(OrbPlan P, const uint8_t* __r
     if ((lane & 7) == 0) reinterpret_cast<uint32_t*>(desc + (size_t)i * 32)[lane >> 3] = w;
 }
 
+// ------------------------------------------------------------------------------------------------
+// K8: the ORB half of LoopClosing::ProcessNewKF (src/loopclosing.cpp:93-113) for a batch of key-frames on the device — expansion and
+// screening, ordered compaction, descriptors: three dependent launches behind the pyramid and the Gaussian (PkfArgs: orb_launch.h)
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int pkf_count(const PkfArgs& a, int b) { return min(max(a.nFeat[b], 0), a.featCap); }
+
+// One wave per (key-frame, feature, level): row r = feature * nlevels + level of the expansion (:94-105: octave = level, response = -1,
+// class_id = feature), screened with k_screen's arithmetic (ORBextractor.cpp:1098-1127).  Writes the keep flag of every row below the
+// item's n_feat * nlevels and the finished key-point of the kept ones; rows from there on are neither read nor written.
+__global__ __launch_bounds__(256) void k_pkf_screen(OrbPlan P, PkfArgs a) {
+    const int b = blockIdx.y, r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    const int n = pkf_count(a, b);
+    if (r >= n * P.nlevels) return;
+    const int i = r / P.nlevels, level = r - i * P.nlevels;
+    const LevelGeom& g = P.lv[level];
+    const float scale = g.scale;
+    const float* xy = a.featXy + ((size_t)b * a.featCap + i) * 2;
+    myslam_keypoint k;
+    k.x = __fdiv_rn(xy[0], scale); k.y = __fdiv_rn(xy[1], scale);                               // :1104
+    // (NaN fails every comparison, +inf the upper and -inf the lower ones: dropped, as the reference's !(...) drops them)
+    bool ok = (__fsub_rn(k.y, (float)EDGE_THRESHOLD) >= 0 && __fadd_rn(k.y, (float)EDGE_THRESHOLD) < (float)g.h &&
+               __fsub_rn(k.x, (float)EDGE_THRESHOLD) >= 0 && __fadd_rn(k.x, (float)EDGE_THRESHOLD) < (float)g.w);
+    const uint8_t* img = a.pyr + (size_t)b * a.pyrStride + g.imgOff;
+    int px = 0, py = 0;
+    if (ok) {
+        px = __float2int_rn(k.x); py = __float2int_rn(k.y);
+        ok = is_fast_corner(img, g.pitch, px, py, P.minTh);                                     // :1112
+    }
+    const size_t row = (size_t)b * a.rowCap + r;
+    if (ok) {                                                                                   // wave-uniform
+        k.angle = wave_ic_angle(img, g.pitch, px, py);                                          // :1118
+        k.size = __fmul_rn((float)PATCH_SIZE, scale);                                           // :1121
+        k.x = __fmul_rn(k.x, scale); k.y = __fmul_rn(k.y, scale);                               // :1123
+        k.response = -1.f; k.octave = level; k.class_id = i;
+        if (lane == 0) a.rows[row] = k;
+    }
+    if (lane == 0) a.keep[row] = ok ? 1 : 0;
+}
+
+// One workgroup per key-frame: out_keypoints.push_back in input order (:1125).  The flags are counted first — an item that keeps more rows than
+// cap writes none of them — and then scanned in chunks of 256 rows: ballot and prefix inside a wave, the waves' totals through LDS, the
+// chunks' totals in a register every thread carries.  A row's slot depends on the flags before it alone.
+__global__ __launch_bounds__(256) void k_pkf_compact(OrbPlan P, PkfArgs a) {
+    __shared__ int s_w[4];
+    const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int total = pkf_count(a, b) * P.nlevels;
+    const uint8_t* keep = a.keep + (size_t)b * a.rowCap;
+    const myslam_keypoint* rows = a.rows + (size_t)b * a.rowCap;
+    int mine = 0;
+    for (int r = t; r < total; r += 256) mine += keep[r];
+    mine = wave_reduce_sum(mine);
+    if (lane == 0) s_w[wv] = mine;
+    __syncthreads();
+    const int kept = s_w[0] + s_w[1] + s_w[2] + s_w[3];
+    if (kept > a.cap) {                                          // nothing is truncated
+        if (t == 0) { a.counts[b] = 0; a.status[b] = MYSLAM_ERR_CAPACITY; }
+        return;
+    }
+    myslam_keypoint* out = a.outKps + (size_t)b * a.cap;
+    int done = 0;
+    for (int base = 0; base < total; base += 256) {
+        const int r = base + t;
+        const bool f = r < total && keep[r] != 0;
+        const unsigned long long m = __ballot(f);
+        __syncthreads();                                         // s_w of the count / of the previous chunk has been read
+        if (lane == 0) s_w[wv] = __popcll(m);
+        __syncthreads();
+        int before = 0, sum = 0;
+#pragma unroll
+        for (int k = 0; k < 4; k++) { const int c = s_w[k]; if (k < wv) before += c; sum += c; }
+        if (f) out[done + before + __popcll(m & ((1ull << lane) - 1ull))] = rows[r];
+        done += sum;
+    }
+    if (t == 0) { a.counts[b] = kept; a.status[b] = MYSLAM_OK; }
+}
+
+// One wave per (key-frame, output slot): CalcDescriptors (ORBextractor.cpp:1210-1223) of the compacted rows on the blurred pyramid
+__global__ __launch_bounds__(256) void k_pkf_describe(OrbPlan P, PkfArgs a) {
+    const int b = blockIdx.y, slot = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (slot >= min(a.counts[b], a.cap)) return;
+    const myslam_keypoint k = a.outKps[(size_t)b * a.cap + slot];
+    const int level = min(max(k.octave, 0), P.nlevels - 1);
+    const LevelGeom& g = P.lv[level];
+    const int px = __float2int_rn(__fdiv_rn(k.x, g.scale)), py = __float2int_rn(__fdiv_rn(k.y, g.scale));
+    const uint32_t w = wave_brief<true>(a.blur + (size_t)b * a.pyrStride + g.imgOff, g.pitch, px, py, k.angle);
+    if ((lane & 7) == 0) reinterpret_cast<uint32_t*>(a.outDesc + ((size_t)b * a.cap + slot) * 32)[lane >> 3] = w;
+}
+
 // unpack a level's candidate list for the debug tap
 __global__ void k_unpack_cands(const uint32_t* __restrict__ cand, int n, int32_t* xs, int32_t* ys, int32_t* sc) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -3137,6 +3227,12 @@ void launch_screen(const OrbPlan& P, const uint8_t* pyr, myslam_keypoint* kin, i
 
 void launch_calc_desc(const OrbPlan& P, const uint8_t* blur, const myslam_keypoint* kps, int n, uint8_t* desc, hipStream_t s) {
     hipLaunchKernelGGL(k_calc_desc, dim3((n + 3) / 4), dim3(256), 0, s, P, blur, kps, n, desc);
+}
+
+void launch_process_keyframes(const OrbPlan& P, const PkfArgs& a, int batch, hipStream_t s) {
+    hipLaunchKernelGGL(k_pkf_screen, dim3((a.rowCap + 3) / 4, batch), dim3(256), 0, s, P, a);
+    hipLaunchKernelGGL(k_pkf_compact, dim3(batch), dim3(256), 0, s, P, a);
+    hipLaunchKernelGGL(k_pkf_describe, dim3((min(a.cap, a.rowCap) + 3) / 4, batch), dim3(256), 0, s, P, a);
 }
 
 void launch_unpack_cands(const uint32_t* cand, int n, int32_t* xs, int32_t* ys, int32_t* sc, hipStream_t s) {

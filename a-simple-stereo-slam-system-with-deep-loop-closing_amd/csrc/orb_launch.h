@@ -50,6 +50,17 @@ void launch_describe(const OrbPlan& P, const uint8_t* pyr, const uint8_t* blur, 
 void launch_screen(const OrbPlan& P, const uint8_t* pyr, myslam_keypoint* kin, int n, myslam_keypoint* kout, uint8_t* keep,
                    hipStream_t s);
 void launch_calc_desc(const OrbPlan& P, const uint8_t* blur, const myslam_keypoint* kps, int n, uint8_t* desc, hipStream_t s);
+
+// ProcessNewKF's ORB half for a batch of key-frames (myslam_orb_process_keyframes_batch): the caller's arrays, the handle's pyramid and blurred
+// blocks, and the handle's scratch — rowCap = feat_cap * nlevels screened key-points and keep flags per item
+struct PkfArgs {
+    const uint8_t* pyr; const uint8_t* blur; size_t pyrStride;
+    const float* featXy; const int32_t* nFeat; int featCap;
+    myslam_keypoint* rows; uint8_t* keep; int rowCap;
+    myslam_keypoint* outKps; uint8_t* outDesc; int32_t* counts; int32_t* status; int cap;
+};
+// screen, compaction, descriptors: three dependent launches
+void launch_process_keyframes(const OrbPlan& P, const PkfArgs& a, int batch, hipStream_t s);
 void launch_unpack_cands(const uint32_t* cand, int n, int32_t* xs, int32_t* ys, int32_t* sc, hipStream_t s);
 
 }  // namespace myslam_hip

@@ -502,6 +502,18 @@ public:
     }
 };
 
+// The ORB half of LoopClosing::ProcessNewKF (src/loopclosing.cpp:93-113) for a batch of key-frames whose images and feature pixels live on the device:
+// every feature expanded over the extractor's levels, ScreenAndComputeKPsParams, CalcDescriptors.  Writes mvPyramidKeyPoints (batch x cap),
+// mORBDescriptors (batch x cap x 32) and their counts exactly where MatchFeaturesBatch reads them; status[b] = MYSLAM_OK or MYSLAM_ERR_CAPACITY.  The
+// key-frame's image is the one DeepLCD::calcDescrOriginalImg blurred in place: enqueue that call first, on the extractor's stream.  Enqueues and returns.
+inline void ProcessNewKFBatch(ORBextractor& extractor, const uint8_t* d_images, int batch, int rows, int cols, int step, size_t imageStride,
+                              const float* d_featurePixels, const int32_t* d_nFeatures, int featCap, KeyPoint* d_pyramidKeyPoints,
+                              uint8_t* d_descriptors, int32_t* d_counts, int32_t* d_status, int cap) {
+    check(myslam_orb_process_keyframes_batch(extractor.handle(), d_images, batch, rows, cols, step, imageStride, d_featurePixels, d_nFeatures, featCap,
+                                             d_pyramidKeyPoints, d_descriptors, d_counts, d_status, cap),
+          "myslam_orb_process_keyframes_batch");
+}
+
 // LoopClosing::MatchFeatures (src/loopclosing.cpp:167-203) and the gather of ComputeCorrectPose (:210-253) for a batch of candidates whose key-frames
 // live on the device: descriptors and mvPyramidKeyPoints of the loop and current key-frames (batch x cap), the current features' pixels and the loop
 // features' landmark slots (batch x featCap, -1 = no map point), the landmark positions (landmarkStride 0 = one table for all items).  Writes the

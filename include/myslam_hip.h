@@ -158,6 +158,42 @@ int myslam_orb_detect_batch(myslam_orb* h, const uint8_t* d_imgs, int batch, int
                             int step, size_t img_stride, const uint8_t* d_masks,
                             myslam_keypoint* d_kps, int32_t* d_counts, int32_t* d_status, int cap);
 
+/* The ORB half of LoopClosing::ProcessNewKF (src/loopclosing.cpp:93-113) for `batch` key-frames of one image size on the device: what
+ * myslam_expand_pyramid_keypoints -> myslam_orb_screen_and_compute_params (ORBextractor.cpp:1083-1129) -> myslam_orb_calc_descriptors
+ * (ORBextractor.cpp:1180-1226) give per key-frame through the host, bit for bit, written where myslam_loop_match_batch reads it: mvPyramidKeyPoints
+ * (its d_loop_pyr / d_cur_pyr), mORBDescriptors (d_loop_desc / d_cur_desc) and their count (d_n_loop / d_n_cur).  Images as in
+ * myslam_orb_detect_and_compute_batch; every image is copied into the handle's pyramid block by the first launch.  Per item b:
+ *   expansion    feature i < n_feat, level l < nlevels, in that order: octave = l, response = -1, class_id = i (:94-105).  Only the feature's pixel
+ *                comes from the caller (d_feat_xy, the layout of myslam_loop_match_batch's d_cur_feat_xy);
+ *   screening    a row is kept when pt / scale[l] passes the float border test (19 pixels) and isFastCorner(minThFAST) (:1098-1127); NaN and
+ *                +-inf coordinates fail the border test, as the reference's !(...) does.  A kept row has pt = (pt / scale) * scale in float,
+ *                size = 31 * scale[l], angle = IC_Angle on the level's image;
+ *   order        kept rows in input order — feature-major, level-minor — as out_keypoints.push_back leaves them (:1125);
+ *   descriptors  of the kept rows on the blurred pyramid (:1194-1223);
+ *   d_counts[b]  the number of kept rows; all 28 bytes of a key-point and the 32 of a descriptor are written below it, slots from it on are
+ *                left as they were;
+ *   d_n_feat[b]  below 0 reads as 0, above feat_cap as feat_cap; slots of d_feat_xy from the count on are never read.  n_feat = 0: count 0,
+ *                status 0 (the reference logs and returns);
+ *   d_status[b]  0, or MYSLAM_ERR_CAPACITY when more rows are kept than `cap`: then d_counts[b] = 0 and none of the item's rows are written
+ *                (nothing is truncated).  Other items are unaffected.
+ * The DeepLCD half is not run here: calcDescrOriginalImg blurs the key-frame's image in place BEFORE the ORB half reads it (:91,
+ * deeplcd.cpp:46), so a caller that reproduces ProcessNewKF enqueues myslam_lcd_describe_batch(..., blur_in_place = 1, ...) on the same stream
+ * first and passes the same d_imgs.
+ * Call level, nothing enqueued: NULL pointers, batch / rows / cols / feat_cap / cap <= 0 or step < cols -> MYSLAM_ERR_INVALID; an image size the
+ * extractor's plan refuses -> MYSLAM_ERR_UNSUPPORTED; batch > 65535, feat_cap * nlevels > 2^24 or cap > 2^24 (launch grid) -> MYSLAM_ERR_CAPACITY.
+ * Runs on the handle's stream; shares the handle's pyramid and blurred blocks with the other *_batch calls and leaves their results as they
+ * were.  Scratch (feat_cap * nlevels screened key-points and flags per item) lives in the handle: after one call at a given (batch, shape,
+ * feat_cap) a repeat allocates nothing, never synchronises and reads no device memory from the host — recordable between
+ * myslam_graph_begin / _end on one stream. */
+int myslam_orb_process_keyframes_batch(myslam_orb* h,
+        const uint8_t* d_imgs, int batch, int rows, int cols, int step, size_t img_stride,   /* as myslam_orb_detect_and_compute_batch */
+        const float* d_feat_xy,        /* batch x feat_cap x 2: mvpFeaturesLeft[i]->mkpPosition.pt (the layout of loop_match_batch's d_cur_feat_xy) */
+        const int32_t* d_n_feat,       /* batch */
+        int feat_cap,
+        myslam_keypoint* d_pyr_kps,    /* batch x cap: mvPyramidKeyPoints, item b at + b*cap */
+        uint8_t* d_desc,               /* batch x cap x 32: mORBDescriptors */
+        int32_t* d_counts, int32_t* d_status /* batch each */, int cap);
+
 /* debug/inspection taps used by the stage-level parity tests (host buffers, one image) */
 int myslam_orb_debug_pyramid(myslam_orb* h, const uint8_t* img, int rows, int cols, int step,
                              int level, int blurred, uint8_t* out, int out_step, int* w, int* hgt);
