@@ -1006,6 +1006,55 @@ class PnPSolver:
                                               C.c_void_p(d_pnp_inlier or None)), "myslam_loop_verify_batch")
 
 
+LOOP_CORRECT_DONE, LOOP_CORRECT_NOT_NEEDED, LOOP_CORRECT_SKIPPED, LOOP_CORRECT_FUSED_ONLY = 0, 1, 2, 3      # MYSLAM_LOOP_CORRECT_*
+LOOP_CORRECT_MAX_SEPARATORS = 32                                                                           # MYSLAM_LOOP_CORRECT_MAX_SEPARATORS
+
+
+class LoopCorrector:
+    """LoopClosing::LoopCorrect's arithmetic (src/loopclosing.cpp:437-463) for a batch of maps on the device (myslam_loop_corrector_*): the handle owns
+    the workspace of `max_batch` maps of up to `kf_cap` key-frames, `edge_cap` edges, `active_cap` active key-frames and `point_cap` map points; the
+    call takes device pointers as ints, enqueues on the handle's stream and returns."""
+
+    def __init__(self, max_batch, kf_cap, edge_cap, active_cap, point_cap, stream=None):
+        self.max_batch, self.kf_cap, self.edge_cap, self.active_cap, self.point_cap = int(max_batch), int(kf_cap), int(edge_cap), int(active_cap), int(point_cap)
+        self._h = C.c_void_p()
+        _check(lib().myslam_loop_corrector_create(C.byref(self._h), self.max_batch, self.kf_cap, self.edge_cap, self.active_cap, self.point_cap),
+               "myslam_loop_corrector_create")
+        if stream is not None:
+            self.set_stream(stream)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and self._h.value and _lib is not None:
+            lib().myslam_loop_corrector_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def set_stream(self, stream):
+        _check(lib().myslam_loop_corrector_set_stream(self._h, C.c_void_p(stream)), "myslam_loop_corrector_set_stream")
+
+    def correct_batch(self, d_poses, d_n_kf, d_active, d_n_active, d_cur, d_loop, d_corrected_pose7, d_verify_status, d_edge_v0, d_edge_v1, d_meas,
+                      d_n_edges, d_points, d_n_points, d_first_active, d_first_kf, batch, correct_threshold, max_iters, d_chi2, d_iters, d_status):
+        """The loop edge (:328-330), the need-correct test (:284-289), LoopLocalFusion (:470-507), PoseGraphOptimization (:537-610) and its write-back
+        (:612-641) per item, arguments in the header's order, tables strided by the handle's caps (include/myslam_hip.h); d_verify_status 0 / None =
+        every item is confirmed; correct_threshold = 1.0 (:285) and max_iters = 20 (:606) at the reference's call site;
+        d_status batch i32 = LOOP_CORRECT_* or a negative error, d_chi2 batch f64, d_iters batch i32"""
+        _check(lib().myslam_loop_correct_batch(self._h, C.c_void_p(d_poses), C.c_void_p(d_n_kf), C.c_void_p(d_active), C.c_void_p(d_n_active),
+                                               C.c_void_p(d_cur), C.c_void_p(d_loop), C.c_void_p(d_corrected_pose7), C.c_void_p(d_verify_status or None),
+                                               C.c_void_p(d_edge_v0), C.c_void_p(d_edge_v1), C.c_void_p(d_meas), C.c_void_p(d_n_edges),
+                                               C.c_void_p(d_points or None), C.c_void_p(d_n_points), C.c_void_p(d_first_active or None),
+                                               C.c_void_p(d_first_kf or None), int(batch), C.c_double(correct_threshold), int(max_iters),
+                                               C.c_void_p(d_chi2), C.c_void_p(d_iters), C.c_void_p(d_status)), "myslam_loop_correct_batch")
+
+
+def loop_correct_structure(n_kf, active, loop, edge_v0, edge_v1):
+    """The separator rule of LoopCorrector.correct_batch for one map, on the host -> (separators, chain length, supported)"""
+    active = np.ascontiguousarray(active, np.int32); e0 = np.ascontiguousarray(edge_v0, np.int32); e1 = np.ascontiguousarray(edge_v1, np.int32)
+    assert len(e0) == len(e1)
+    ns = C.c_int(); nc = C.c_int(); ok = C.c_int()
+    _check(lib().myslam_loop_correct_structure(int(n_kf), _p(active), len(active), int(loop), _p(e0), _p(e1), len(e0), C.byref(ns), C.byref(nc), C.byref(ok)),
+           "myslam_loop_correct_structure")
+    return ns.value, nc.value, bool(ok.value)
+
+
 # ---------------------------------------------------------------------------------- host-side formats (no device needed)
 def read_png_gray(path):
     """cv::imread(path, IMREAD_GRAYSCALE) for the KITTI grey PNGs (app/run_kitti_stereo.cpp:66-67) -> uint8 [rows, cols]"""

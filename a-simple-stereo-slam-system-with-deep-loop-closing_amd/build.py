@@ -34,6 +34,7 @@ UNITS = {
     "lk.hip": EXACT,
     "pgo.hip": [],
     "pnp.hip": EXACT,
+    "loop_correct.hip": [],
     "prof.hip": [],
     "io.hip": [],
     "graph.hip": [],

@@ -502,6 +502,43 @@ public:
     }
 };
 
+// LoopClosing::LoopCorrect's arithmetic (src/loopclosing.cpp:437-463) for a batch of maps on the device: the handle owns the workspace of maxBatch maps
+// of up to kfCap key-frames, edgeCap edges, activeCap active key-frames and pointCap map points.  CorrectBatch takes the strided tables of
+// myslam_loop_correct_batch (include/myslam_hip.h), d_correctedPose7 / d_verifyStatus being PnPSolver::VerifyBatch's d_pose7 / d_status (nullptr = every
+// item is confirmed); status[b] = MYSLAM_LOOP_CORRECT_* or a negative error.  Enqueues on the handle's stream and returns.
+class LoopCorrector {
+    myslam_loop_corrector* h_ = nullptr;
+    int maxBatch_, kfCap_, edgeCap_, activeCap_, pointCap_;
+public:
+    LoopCorrector(int maxBatch, int kfCap, int edgeCap, int activeCap, int pointCap)
+        : maxBatch_(maxBatch), kfCap_(kfCap), edgeCap_(edgeCap), activeCap_(activeCap), pointCap_(pointCap) {
+        check(myslam_loop_corrector_create(&h_, maxBatch, kfCap, edgeCap, activeCap, pointCap), "myslam_loop_corrector_create");
+    }
+    ~LoopCorrector() { if (h_) myslam_loop_corrector_destroy(h_); }
+    LoopCorrector(const LoopCorrector&) = delete; LoopCorrector& operator=(const LoopCorrector&) = delete;
+    int maxBatch() const { return maxBatch_; }
+    int kfCap() const { return kfCap_; }
+    int edgeCap() const { return edgeCap_; }
+    int activeCap() const { return activeCap_; }
+    int pointCap() const { return pointCap_; }
+    void SetStream(void* hipStream) { check(myslam_loop_corrector_set_stream(h_, hipStream), "myslam_loop_corrector_set_stream"); }
+    void CorrectBatch(double* d_poses, const int32_t* d_nKF, const int32_t* d_active, const int32_t* d_nActive, const int32_t* d_cur, const int32_t* d_loop,
+                      const double* d_correctedPose7, const int32_t* d_verifyStatus, int32_t* d_edgeV0, int32_t* d_edgeV1, double* d_meas, int32_t* d_nEdges,
+                      double* d_points, const int32_t* d_nPoints, const int32_t* d_firstActive, const int32_t* d_firstKF, int batch, double correctThreshold /*1.0, :285*/,
+                      int maxIters /*20, :606*/, double* d_chi2, int32_t* d_iters, int32_t* d_status) {
+        check(myslam_loop_correct_batch(h_, d_poses, d_nKF, d_active, d_nActive, d_cur, d_loop, d_correctedPose7, d_verifyStatus, d_edgeV0, d_edgeV1, d_meas,
+                                        d_nEdges, d_points, d_nPoints, d_firstActive, d_firstKF, batch, correctThreshold, maxIters, d_chi2, d_iters, d_status),
+              "myslam_loop_correct_batch");
+    }
+    // the separator rule of CorrectBatch for one map, on the host: false = the map would come back MYSLAM_LOOP_CORRECT_FUSED_ONLY
+    static bool Structure(int nKF, const int32_t* active, int nActive, int loop, const int32_t* edgeV0, const int32_t* edgeV1, int nEdges,
+                          int* nSeparators = nullptr, int* chainLength = nullptr) {
+        int ok = 0;
+        check(myslam_loop_correct_structure(nKF, active, nActive, loop, edgeV0, edgeV1, nEdges, nSeparators, chainLength, &ok), "myslam_loop_correct_structure");
+        return ok != 0;
+    }
+};
+
 // The ORB half of LoopClosing::ProcessNewKF (src/loopclosing.cpp:93-113) for a batch of key-frames whose images and feature pixels live on the device:
 // every feature expanded over the extractor's levels, ScreenAndComputeKPsParams, CalcDescriptors.  Writes mvPyramidKeyPoints (batch x cap),
 // mORBDescriptors (batch x cap x 32) and their counts exactly where MatchFeaturesBatch reads them; status[b] = MYSLAM_OK or MYSLAM_ERR_CAPACITY.  The

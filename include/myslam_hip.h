@@ -815,6 +815,73 @@ int myslam_loop_verify_batch(myslam_pnp* h, const float* d_pts3d, const float* d
                              double* d_pnp_pose7, uint8_t* d_pnp_inlier);
 
 /* ------------------------------------------------------------------------------------------
+ * Loop correction for a BATCH of confirmed loops on the device — the arithmetic of LoopClosing::LoopCorrect (src/loopclosing.cpp:437-463) for
+ * `batch` independent maps in one enqueue, reading myslam_loop_verify_batch's d_pose7 / d_status where that call left them: the loop edge of
+ * :328-330, the need-correct test of :284-289, LoopLocalFusion (:470-507), PoseGraphOptimization (:537-610) and its write-back (:612-641).
+ * The one-map, host-pointer forms stay: myslam_loop_local_fusion, myslam_pose_graph_optimize, myslam_correct_map_points.
+ * A handle owns every scratch buffer (per item: the working poses, Jacobians, the block-tridiagonal chain, the dense separator system), so
+ * myslam_loop_correct_batch allocates nothing, never synchronises, never reads device memory from the host and can be recorded between
+ * myslam_graph_begin / _end.  One workgroup solves one map from start to finish (csrc/loop_correct.hip): Levenberg's control flow runs on the device.
+ * Item b is one map; tables are strided by the handle's caps, slots from an item's count on are never read or written:
+ *   d_poses            batch x kf_cap x 7 f64, in/out   GetAllKeyFrames() as Tcw (qx qy qz qw tx ty tz), ascending id; row 0 is key-frame 0
+ *   d_n_kf             batch i32                        key-frames of the map
+ *   d_active           batch x active_cap i32           rows of d_poses that form the active window, strictly ascending;  d_n_active batch i32
+ *   d_cur, d_loop      batch i32                        rows of the current and the loop key-frame; cur is in the active list, loop != cur
+ *   d_corrected_pose7  batch x 7 f64                    _mseCorrectedCurrentPose: myslam_loop_verify_batch's d_pose7
+ *   d_verify_status    batch i32 or NULL                myslam_loop_verify_batch's d_status; NULL = every item is confirmed
+ *   d_edge_v0 / _v1    batch x edge_cap i32, in/out     the edges of :568-602 as they stand BEFORE this loop (v0 != v1);  d_meas batch x edge_cap x 7 f64,
+ *                                                       in/out: T[v0] * T[v1]^-1 as measured;  d_n_edges batch i32, in/out
+ *   d_points           batch x point_cap x 3 f64, in/out   map points;  d_n_points batch i32
+ *   d_first_active     batch x point_cap i32            slot IN THE ITEM'S ACTIVE LIST of the active key-frame that first observes the point; < 0: not an active map point
+ *   d_first_kf         batch x point_cap i32            row of the key-frame that first observed the point; < 0: the skip of :627-631
+ * correct_threshold = 1.0 (:285), max_iters = 20 (:606) at the call site.  Per item, in this order:
+ *   1. d_verify_status[b] != MYSLAM_VERIFY_CONFIRMED -> MYSLAM_LOOP_CORRECT_SKIPPED, nothing of the item's tables is touched;
+ *   2. the edge (cur, loop) with the measurement Tcc * Tloop^-1 (:328-330; Tloop = the loop key-frame's pose as given) is appended at slot d_n_edges[b]
+ *      and the count incremented; a full table -> MYSLAM_ERR_CAPACITY, the item untouched;
+ *   3. |log(Tcur * Tcc^-1)| <= correct_threshold (:284-289) -> MYSLAM_LOOP_CORRECT_NOT_NEEDED: the edge stays, poses and points keep their bits;
+ *   4. LoopLocalFusion (:470-507): every active key-frame becomes Ta * Tcur^-1 * Tcc (cur itself Tcc), renormalised per product as
+ *      myslam_loop_local_fusion does; every point with first_active >= 0 keeps its camera-frame position in that key-frame;
+ *   5. PoseGraphOptimization (:537-610) over the fixed set {active rows, loop row, row 0}: edge error, numeric Jacobian (delta 1e-9) and Levenberg rules
+ *      (lambda init, rho, accept / reject, ten rejected trials, rho == 0, non-finite lambda, a failed pivot = a rejected trial) of
+ *      myslam_pose_graph_optimize; d_chi2[b] / d_iters[b] have the meaning of its *final_chi2 / *iters;
+ *   6. write-back (:612-641): points with first_active < 0 and first_kf >= 0 move from the pose after step 4 to the optimised pose of that key-frame
+ *      (active points are left out, :616-619), the optimised poses of the free key-frames are stored (fixed rows outside the active window keep their bits);
+ *   7. MYSLAM_LOOP_CORRECT_DONE.
+ * An index out of range (an active row, cur, loop, an edge endpoint >= n_kf, first_active >= n_active, first_kf >= n_kf), a count beyond its cap, an active
+ * list that is not strictly ascending, cur outside the active list or cur == loop -> MYSLAM_ERR_INVALID, the item untouched.  Every status but DONE
+ * reports d_chi2[b] = 0 and d_iters[b] = 0.  One item's fault never changes another item's result, and an item's bytes depend neither on its position in
+ * the batch nor on what else is in it (all sums run in a fixed order).
+ * Solver structure: the free key-frames in row order form a block-tridiagonal chain; every edge whose two free endpoints are not neighbours in that
+ * order makes its LATER endpoint a separator of a dense Schur system (chosen on the device, no greedy pass).  A map that needs more than
+ * MYSLAM_LOOP_CORRECT_MAX_SEPARATORS of them (one per closed loop, 17 over KITTI 00) gets MYSLAM_LOOP_CORRECT_FUSED_ONLY: steps 2 to 4 are done, poses
+ * outside the active window and non-active points are untouched, d_iters[b] = 0 — the caller finishes that map with myslam_pose_graph_optimize +
+ * myslam_correct_map_points.  Re-linking observations (:509-532) stays with the caller, as for myslam_loop_local_fusion.
+ * batch beyond the handle's -> MYSLAM_ERR_CAPACITY, nothing enqueued.
+ * ------------------------------------------------------------------------------------------ */
+#define MYSLAM_LOOP_CORRECT_DONE 0
+#define MYSLAM_LOOP_CORRECT_NOT_NEEDED 1
+#define MYSLAM_LOOP_CORRECT_SKIPPED 2
+#define MYSLAM_LOOP_CORRECT_FUSED_ONLY 3
+#define MYSLAM_LOOP_CORRECT_MAX_SEPARATORS 32
+typedef struct myslam_loop_corrector myslam_loop_corrector;
+/* LoopClosing::LoopCorrect's workspace (src/loopclosing.cpp:437-463) for max_batch maps of up to kf_cap key-frames, edge_cap edges (the appended one
+ * included), active_cap active key-frames and point_cap map points each */
+int myslam_loop_corrector_create(myslam_loop_corrector** out, int max_batch, int kf_cap, int edge_cap, int active_cap, int point_cap);
+int myslam_loop_corrector_destroy(myslam_loop_corrector* h);
+int myslam_loop_corrector_set_stream(myslam_loop_corrector* h, void* hip_stream);
+/* src/loopclosing.cpp:284-289, :328-330, :437-463, :470-507, :537-641 as described above.  Device pointers, asynchronous on the handle's stream. */
+int myslam_loop_correct_batch(myslam_loop_corrector* h, double* d_poses, const int32_t* d_n_kf, const int32_t* d_active, const int32_t* d_n_active,
+                              const int32_t* d_cur, const int32_t* d_loop, const double* d_corrected_pose7, const int32_t* d_verify_status,
+                              int32_t* d_edge_v0, int32_t* d_edge_v1, double* d_meas, int32_t* d_n_edges, double* d_points, const int32_t* d_n_points,
+                              const int32_t* d_first_active, const int32_t* d_first_kf, int batch, double correct_threshold, int max_iters,
+                              double* d_chi2, int32_t* d_iters, int32_t* d_status);
+/* The separator rule of myslam_loop_correct_batch for one map, on the host (host arrays, no device needed): the fixed set of :560-562
+ * {active rows, loop row, row 0}, then the rule above over the edges given (the appended edge joins two fixed rows and changes nothing).
+ * *n_separators, *chain_length (free key-frames left in the chain), *supported = n_separators <= MYSLAM_LOOP_CORRECT_MAX_SEPARATORS. */
+int myslam_loop_correct_structure(int n_kf, const int32_t* active, int n_active, int loop, const int32_t* edge_v0, const int32_t* edge_v1, int n_edges,
+                                  int* n_separators, int* chain_length, int* supported);
+
+/* ------------------------------------------------------------------------------------------
  * Host-side formats of the reference's runner — plain host code, no device needed; the C++ forms live in
  * host/myslam_io.hpp and host/myslam_png.hpp.
  * ------------------------------------------------------------------------------------------ */
