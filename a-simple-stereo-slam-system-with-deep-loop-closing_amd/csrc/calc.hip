@@ -919,45 +919,28 @@ struct myslam_lcd {
     // the two f16 matrix-core kernels go together: conv1 hands conv2 its input as two f16 planes (h, m'); the bf16 / f32 pair keeps an f32 map
     bool f16_family() const { return d_w1h && d_w2h && !forceBf16; }
     int skipMask = 0;                  // myslam_lcd_set_option(SKIP_KERNELS): TIMING ONLY — bit 0 input, 1 conv1, 2 conv2, 3 pool2, 4 conv3 + norm are not launched
-    std::vector<float*> d_wt, d_b;     // per convolution: weights re-laid out as [K*K*IC][OC], bias
-    uint4* d_w2s = nullptr;            // fused path: conv2 weights split into three bf16 pieces, [stage][piece][n][k half] x 8 bf16
-    uint4* d_w1h = nullptr;            // conv1 weights as MFMA operands of k_conv1_f16x3_pool_lrn ([n tile][k step][2^11 h, m', h][lane]), same condition as d_w2h
-    uint4* d_w2h = nullptr;            // the same as three f16 planes (2^11 h, m', h) when the model's ranges allow k_conv2_f16x3, else nullptr
+    std::vector<Buf<float>> d_wt, d_b; // per convolution: weights re-laid out as [K*K*IC][OC], bias
+    Buf<uint4> d_w2s;                  // fused path: conv2 weights split into three bf16 pieces, [stage][piece][n][k half] x 8 bf16
+    Buf<uint4> d_w1h;                  // conv1 weights as MFMA operands of k_conv1_f16x3_pool_lrn ([n tile][k step][2^11 h, m', h][lane]), same condition as d_w2h
+    Buf<uint4> d_w2h;                  // the same as three f16 planes (2^11 h, m', h) when the model's ranges allow k_conv2_f16x3, else empty
     size_t actMax = 0;                 // largest activation (floats per image) of the generic path
     // resize tables for the current source size
     int rows = 0, cols = 0;
-    int32_t *d_xofs = nullptr, *d_yofs = nullptr; int16_t *d_xa = nullptr, *d_yb = nullptr;
+    Buf<int32_t> d_xofs, d_yofs; Buf<int16_t> d_xa, d_yb;
     // batch buffers
     int batchCap = 0; size_t blurBytes = 0; int blurPitch = 0;
-    uint8_t* d_blur = nullptr;
-    float *d_in = nullptr, *d_p1 = nullptr, *d_a2 = nullptr, *d_p2 = nullptr;      // fused path activations
-    float *d_g0 = nullptr, *d_g1 = nullptr; int genericCap = 0;                    // generic path ping-pong (allocated on first use)
+    Buf<uint8_t> d_blur;
+    Buf<float> d_in, d_p1, d_a2, d_p2;                                             // fused path activations
+    Buf<float> d_g0, d_g1; int genericCap = 0;                                     // generic path ping-pong (allocated on first use)
     // host-entry staging
-    uint8_t* d_stageImg = nullptr; size_t stageBytes = 0; float* d_stageOut = nullptr; float* h_stageOut = nullptr;
+    Buf<uint8_t> d_stageImg; Buf<float> d_stageOut; PinBuf<float> h_stageOut;
 
     int ensure_tables(int r, int c);
     int ensure_batch(int batch, int r, int c);
     int ensure_generic(int batch);
     int forward_generic(int batch, float* d_out, int stop_after, float** tap);
     int describe(uint8_t* d_imgs, int batch, int r, int c, int step, size_t stride, int blur_in_place, float* d_out);
-    void free_all();
 };
-
-template <typename T>
-static int lcd_alloc(T*& p, size_t n) {
-    if (p) { (void)hipFree(p); p = nullptr; }
-    if (!n) return MYSLAM_OK;
-    MYSLAM_HIP_CHECK(hipMalloc((void**)&p, n * sizeof(T)));
-    return MYSLAM_OK;
-}
-
-void myslam_lcd::free_all() {
-    void* ptrs[] = {d_w2s, d_w2h, d_w1h, d_xofs, d_yofs, d_xa, d_yb, d_blur, d_in, d_p1, d_a2, d_p2, d_g0, d_g1, d_stageImg, d_stageOut};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    for (float* p : d_wt) if (p) (void)hipFree(p);
-    for (float* p : d_b) if (p) (void)hipFree(p);
-    if (h_stageOut) (void)hipHostFree(h_stageOut);
-}
 
 int myslam_lcd::ensure_tables(int r, int c) {
     if (r == rows && c == cols) return MYSLAM_OK;
@@ -965,15 +948,17 @@ int myslam_lcd::ensure_tables(int r, int c) {
     std::vector<int32_t> xo, yo; std::vector<int16_t> xa, yb;
     lcd_resize_tables(c, IN_W, true, xo, xa);
     lcd_resize_tables(r, IN_H, false, yo, yb);
-    int rc;
-    if ((rc = lcd_alloc(d_xofs, xo.size())) || (rc = lcd_alloc(d_xa, xa.size())) || (rc = lcd_alloc(d_yofs, yo.size())) ||
-        (rc = lcd_alloc(d_yb, yb.size())))
-        return rc;
-    if ((rc = upload_table(d_xofs, xo.data(), xo.size() * 4))) return rc;
-    if ((rc = upload_table(d_xa, xa.data(), xa.size() * 2))) return rc;
-    if ((rc = upload_table(d_yofs, yo.data(), yo.size() * 4))) return rc;
-    if ((rc = upload_table(d_yb, yb.data(), yb.size() * 2))) return rc;
-    rows = r; cols = c; batchCap = 0;
+    cols = 0;
+    int rc = regrow(rows, r, [&]() -> int {                // the tables belong to (rows, cols): both stay 0 unless every table is allocated and filled
+        int rc;
+        if ((rc = d_xofs.renew(xo.size())) || (rc = d_xa.renew(xa.size())) || (rc = d_yofs.renew(yo.size())) || (rc = d_yb.renew(yb.size()))) return rc;
+        if ((rc = upload_table(d_xofs, xo.data(), xo.size() * 4))) return rc;
+        if ((rc = upload_table(d_xa, xa.data(), xa.size() * 2))) return rc;
+        if ((rc = upload_table(d_yofs, yo.data(), yo.size() * 4))) return rc;
+        return upload_table(d_yb, yb.data(), yb.size() * 2);
+    });
+    if (rc) return rc;
+    cols = c; batchCap = 0;
     return MYSLAM_OK;
 }
 
@@ -984,25 +969,31 @@ int myslam_lcd::ensure_batch(int batch, int r, int c) {
     MYSLAM_HIP_CHECK(hipStreamSynchronize(stream));
     blurPitch = (c + 63) / 64 * 64;
     blurBytes = ((size_t)blurPitch * r + 255) / 256 * 256;
-    if ((rc = lcd_alloc(d_blur, blurBytes * batch))) return rc;
-    if ((rc = lcd_alloc(d_in, (size_t)batch * IN_PLANE))) return rc;
-    MYSLAM_HIP_CHECK(hipMemsetAsync(d_in, 0, (size_t)batch * IN_PLANE * sizeof(float), stream));     // the padding stays zero: writers touch the interior only
-    if (fused.ok) {
-        if ((rc = lcd_alloc(d_p1, (size_t)batch * HP1 * WP1 * C1))) return rc;
-        if ((rc = lcd_alloc(d_a2, (size_t)batch * H2 * W2 * C2))) return rc;
-        if ((rc = lcd_alloc(d_p2, (size_t)batch * HP2 * WP2 * C2))) return rc;
-    }
-    batchCap = batch; genericCap = 0;
+    rc = regrow(batchCap, batch, [&]() -> int {
+        int rc;
+        if ((rc = d_blur.renew(blurBytes * batch))) return rc;
+        if ((rc = d_in.renew((size_t)batch * IN_PLANE))) return rc;
+        MYSLAM_HIP_CHECK(hipMemsetAsync(d_in, 0, (size_t)batch * IN_PLANE * sizeof(float), stream));     // the padding stays zero: writers touch the interior only
+        if (fused.ok) {
+            if ((rc = d_p1.renew((size_t)batch * HP1 * WP1 * C1))) return rc;
+            if ((rc = d_a2.renew((size_t)batch * H2 * W2 * C2))) return rc;
+            if ((rc = d_p2.renew((size_t)batch * HP2 * WP2 * C2))) return rc;
+        }
+        return MYSLAM_OK;
+    });
+    if (rc) return rc;
+    genericCap = 0;
     return MYSLAM_OK;
 }
 
 int myslam_lcd::ensure_generic(int batch) {
     if (batch <= genericCap) return MYSLAM_OK;
     MYSLAM_HIP_CHECK(hipStreamSynchronize(stream));
-    int rc;
-    if ((rc = lcd_alloc(d_g0, (size_t)batch * actMax)) || (rc = lcd_alloc(d_g1, (size_t)batch * actMax))) return rc;
-    genericCap = batch;
-    return MYSLAM_OK;
+    return regrow(genericCap, batch, [&]() -> int {
+        int rc;
+        if ((rc = d_g0.renew((size_t)batch * actMax)) || (rc = d_g1.renew((size_t)batch * actMax))) return rc;
+        return MYSLAM_OK;
+    });
 }
 
 // layer by layer on the generic kernels.  stop_after >= 0: stop after that layer index and return its activation in *tap.
@@ -1113,7 +1104,7 @@ static int lcd_create(myslam_lcd** out, const myslam_calc_layer* layers, int nla
     h->layers.assign(layers, layers + nlayers); h->shapes = shapes;
     h->fused = match_fused(layers, nlayers);
     for (auto& s : shapes) h->actMax = std::max(h->actMax, (size_t)s.C * s.H * s.W);
-    auto fail = [&](int code) { h->free_all(); delete h; return code; };
+    auto fail = [&](int code) { delete h; return code; };
     // convolution weights: [OC][IC][K][K] -> [K*K*IC][OC] (k = (ky*K + kx)*IC + ic: channel runs contiguous, one coalesced row per k)
     const float* w = weights; int ic = 1;
     std::vector<float> w2t;
@@ -1124,12 +1115,10 @@ static int lcd_create(myslam_lcd** out, const myslam_calc_layer* layers, int nla
         for (int oc = 0; oc < OC; oc++)
             for (int c = 0; c < ic; c++)
                 for (int t = 0; t < KK; t++) wt[((size_t)t * ic + c) * OC + oc] = w[((size_t)oc * ic + c) * KK + t];
-        float *dw = nullptr, *db = nullptr;
-        if (hipMalloc((void**)&dw, wt.size() * sizeof(float)) != hipSuccess) return fail(MYSLAM_ERR_HIP);
-        h->d_wt.push_back(dw);
-        if (hipMalloc((void**)&db, (size_t)OC * sizeof(float)) != hipSuccess) return fail(MYSLAM_ERR_HIP);
-        h->d_b.push_back(db);
-        if (upload_table(dw, wt.data(), wt.size() * sizeof(float)) != MYSLAM_OK ||
+        h->d_wt.emplace_back(); h->d_b.emplace_back();
+        Buf<float> &dw = h->d_wt.back(), &db = h->d_b.back();
+        if (dw.renew(wt.size()) != MYSLAM_OK || db.renew((size_t)OC) != MYSLAM_OK ||
+            upload_table(dw, wt.data(), wt.size() * sizeof(float)) != MYSLAM_OK ||
             upload_table(db, w + (size_t)OC * ic * KK, (size_t)OC * sizeof(float)) != MYSLAM_OK)
             return fail(MYSLAM_ERR_HIP);
         if (conv == 1) w2t.swap(wt);
@@ -1156,7 +1145,7 @@ static int lcd_create(myslam_lcd** out, const myslam_calc_layer* layers, int nla
                 for (int p = 0; p < 3; p++) w2s[(((size_t)st * 3 + p) * 128 + oc) * 16 + kk] = pcs[p];
             }
         }
-        if (hipMalloc((void**)&h->d_w2s, w2s.size() * 2) != hipSuccess ||
+        if (h->d_w2s.renew(w2s.size() * 2 / sizeof(uint4)) != MYSLAM_OK ||
             upload_table(h->d_w2s, w2s.data(), w2s.size() * 2) != MYSLAM_OK)
             return fail(MYSLAM_ERR_HIP);
     }
@@ -1193,7 +1182,7 @@ static int lcd_create(myslam_lcd** out, const myslam_calc_layer* layers, int nla
                     for (int p = 0; p < 3; p++) w2h[(((size_t)st * 3 + p) * 128 + oc) * 16 + kk] = pcs[p];
                 }
             }
-            if (hipMalloc((void**)&h->d_w2h, w2h.size() * 2) != hipSuccess ||
+            if (h->d_w2h.renew(w2h.size() * 2 / sizeof(uint4)) != MYSLAM_OK ||
                 upload_table(h->d_w2h, w2h.data(), w2h.size() * 2) != MYSLAM_OK)
                 return fail(MYSLAM_ERR_HIP);
             double wmax1 = 0;
@@ -1212,7 +1201,7 @@ static int lcd_create(myslam_lcd** out, const myslam_calc_layer* layers, int nla
                                 const uint16_t pcs[3] = {to_f16(hf * 2048.f), to_f16((a - hf) * 2048.f), hb};
                                 for (int pc = 0; pc < 3; pc++) w1h[((((size_t)(nt * 2 + ks) * 3 + pc) * 64 + ln) * 8) + j] = pcs[pc];
                             }
-                if (hipMalloc((void**)&h->d_w1h, w1h.size() * 2) != hipSuccess ||
+                if (h->d_w1h.renew(w1h.size() * 2 / sizeof(uint4)) != MYSLAM_OK ||
                     upload_table(h->d_w1h, w1h.data(), w1h.size() * 2) != MYSLAM_OK)
                     return fail(MYSLAM_ERR_HIP);
             }
@@ -1293,7 +1282,6 @@ int myslam_lcd_create_from_file(myslam_lcd** out, const char* path) {
 int myslam_lcd_destroy(myslam_lcd* h) {
     if (!h) return MYSLAM_ERR_INVALID;
     (void)hipStreamSynchronize(h->stream);
-    h->free_all();
     delete h;
     return MYSLAM_OK;
 }
@@ -1333,9 +1321,10 @@ int myslam_lcd_describe_batch(myslam_lcd* h, uint8_t* d_imgs, int batch, int row
 }
 
 static int lcd_stage(myslam_lcd* h, size_t bytes) {
-    if (bytes > h->stageBytes) { int rc = lcd_alloc(h->d_stageImg, bytes); if (rc) return rc; h->stageBytes = bytes; }
-    if (!h->d_stageOut) { int rc = lcd_alloc(h->d_stageOut, (size_t)MYSLAM_LCD_DIM); if (rc) return rc; }
-    if (!h->h_stageOut) MYSLAM_HIP_CHECK(hipHostMalloc((void**)&h->h_stageOut, sizeof(float) * MYSLAM_LCD_DIM));
+    int rc;
+    if (bytes > h->d_stageImg.size() && (rc = h->d_stageImg.renew(bytes))) return rc;
+    if (!h->d_stageOut && (rc = h->d_stageOut.renew(MYSLAM_LCD_DIM))) return rc;
+    if (!h->h_stageOut && (rc = h->h_stageOut.renew(MYSLAM_LCD_DIM))) return rc;
     return MYSLAM_OK;
 }
 

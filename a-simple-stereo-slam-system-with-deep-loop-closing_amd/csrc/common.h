@@ -11,6 +11,7 @@
 #include <string.h>
 
 #include "../../include/myslam_hip.h"
+#include "dev_mem.h"
 
 #define MYSLAM_HIP_CHECK(expr)                                                              \
     do {                                                                                    \
@@ -74,11 +75,11 @@ inline int copy_sync(void* dst, const void* src, size_t bytes, hipMemcpyKind kin
 
 // ---- staging of the host-pointer ("drop-in", B = 1) entry points --------------------------------------------------------------
 // One grow-only device block, one pinned host block and one stream per calling THREAD, carved into 256-byte aligned pieces per
-// call: no hipMalloc / hipFree per call, one host->device and one device->host copy per call, and nothing to free on an error
+// call: no allocation per call, one host->device and one device->host copy per call, and nothing to free on an error
 // return (the arena owns the memory).  Pieces are laid out [in][inout][out][tmp]; `upload()` copies in + inout, `download()` copies
 // inout + out back and synchronises.  Usage: register pieces, upload(), launch on stream() with dev<T>(piece), download().
 struct HostArena {
-    uint8_t* d = nullptr; uint8_t* h = nullptr; size_t cap = 0; hipStream_t s = nullptr;
+    Buf<uint8_t> d; PinBuf<uint8_t> h; hipStream_t s = nullptr;
     int dev = -1;               // the device block, stream and pinned block belong to: a thread that switches devices gets a fresh arena
     ~HostArena();
     void release();

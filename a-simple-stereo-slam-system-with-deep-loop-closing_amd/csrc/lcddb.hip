@@ -351,9 +351,9 @@ struct myslam_lcddb_query_ctx {
     myslam_lcddb* db = nullptr;
     hipStream_t stream = nullptr;
     bool builtin = false;
-    Partial* d_partials = nullptr; size_t partialsCap = 0;
-    int32_t* d_nvalid = nullptr; int nvalidCap = 0;                 // nq row limits + 1: the row count they were computed against
-    int32_t* h_nvalid = nullptr;                                    // pinned staging of the per-query row limits
+    Buf<Partial> d_partials;
+    Buf<int32_t> d_nvalid; int nvalidCap = 0;                       // nq row limits + 1: the row count they were computed against
+    PinBuf<int32_t> h_nvalid;                                       // pinned staging of the per-query row limits
     // round 6: eager uploads go through a RING of pinned slots behind slot 0 (slot 0 is what recorded scans read at their replays): a call whose limits changed — a
     // database that grows every step — used to wait for the previous call's upload to leave the one pinned buffer, i.e. for the stream to drain up to it; now it waits for
     // the upload three calls back, which has long gone
@@ -362,9 +362,9 @@ struct myslam_lcddb_query_ctx {
     static constexpr int NV_RING = 16;
     hipEvent_t nvRingEv[NV_RING] = {}; bool nvRingPending[NV_RING] = {}; int nvSlot = 0;
     const int32_t* limits = nullptr;                                // what the launches of the current call read: d_nvalid (eager) or h_nvalid itself (recorded)
-    uint64_t* d_bestS = nullptr; float* d_maxS = nullptr; int32_t* d_cntS = nullptr; int shardCap = 0;     // scratch of the sharded query
+    Buf<uint64_t> d_bestS; Buf<float> d_maxS; Buf<int32_t> d_cntS; int shardCap = 0;     // scratch of the sharded query
     // scratch of the owned-shard query (round 6): row ranges [0, pLim) and [sBeg, sLim) + break flags per query (pinned staging + device copy), results of both parts
-    int32_t* h_own = nullptr; int32_t* d_own = nullptr; uint64_t* d_bestO = nullptr; float* d_maxO = nullptr; int32_t* d_cntO = nullptr; int ownCap = 0;
+    PinBuf<int32_t> h_own; Buf<int32_t> d_own; Buf<uint64_t> d_bestO; Buf<float> d_maxO; Buf<int32_t> d_cntO; int ownCap = 0;
     hipEvent_t ownEvent = nullptr; bool ownPending = false;
     int graphRows = 0, graphQueries = 0;      // > 0: a query of this context was recorded into a HIP graph covering this many rows / queries
     uint64_t graphGen = 0;                    // generation of the matrix that recording reads
@@ -375,17 +375,17 @@ struct myslam_lcddb_query_ctx {
 struct myslam_lcddb {
     hipStream_t stream = nullptr;
     int capacity = 0, n = 0;
-    float* d_db = nullptr;
-    uint64_t* d_ids = nullptr;
+    Buf<float> d_db;
+    Buf<uint64_t> d_ids;
     std::vector<uint64_t> ids;
     uint64_t generation = 0;                  // bumped whenever the matrix moves
-    std::vector<std::pair<float*, uint64_t*>> retired;      // matrices a recorded step of an older generation may still name
+    std::vector<std::pair<Buf<float>, Buf<uint64_t>>> retired;     // matrices a recorded step of an older generation may still name
     std::vector<myslam_lcddb_query_ctx*> ctxs;              // every live context (ctxs[0] = the built-in one)
     std::mutex mu;                            // host state: ids, n, capacity, pointers, context list
-    float* d_q1 = nullptr; uint64_t* d_best1 = nullptr; float* d_max1 = nullptr; int32_t* d_cnt1 = nullptr;
+    Buf<float> d_q1; Buf<uint64_t> d_best1; Buf<float> d_max1; Buf<int32_t> d_cnt1;
     // pinned staging of the ids of asynchronous appends (a copy out of pageable host memory makes the runtime wait for the stream): a ring of slots, each with its event
     static constexpr int ID_RING = 16, ID_SLOT = 1024;
-    uint64_t* h_idring = nullptr; hipEvent_t idEv[ID_RING] = {}; bool idPending[ID_RING] = {}; int idSlot = 0;
+    PinBuf<uint64_t> h_idring; hipEvent_t idEv[ID_RING] = {}; bool idPending[ID_RING] = {}; int idSlot = 0;
 
     // index of the first row the reference's scan does NOT look at: it breaks at the first id with
     // (cur - id) < 20 in unsigned arithmetic (loopclosing.cpp:133), i.e. id in [cur-19, cur] mod 2^64
@@ -422,10 +422,6 @@ struct myslam_lcddb {
 };
 
 static void ctx_free(myslam_lcddb_query_ctx* c) {
-    void* ptrs[] = {c->d_partials, c->d_nvalid, c->d_bestS, c->d_maxS, c->d_cntS, c->d_own, c->d_bestO, c->d_maxO, c->d_cntO};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
-    if (c->h_nvalid) (void)hipHostFree(c->h_nvalid);
-    if (c->h_own) (void)hipHostFree(c->h_own);
     for (hipEvent_t e : c->nvRingEv) if (e) (void)hipEventDestroy(e);
     if (c->ownEvent) (void)hipEventDestroy(c->ownEvent);
     if (c->link) c->link->invalidate();       // recorded steps that captured this context can no longer be launched
@@ -455,14 +451,6 @@ static int scan_blocks(int nq, int rows) {
     return std::max(1, nq >= 32 ? (rows + GM - 1) / GM : (rows + rowsPerBlock - 1) / rowsPerBlock);
 }
 
-// frees a piece of scratch (device memory, or pinned host memory) and allocates n elements in its place; null when the allocation failed
-template <class T> static int renew(T*& p, size_t n, bool pinned = false) {
-    if (p) (void)(pinned ? hipHostFree(p) : hipFree(p));
-    p = nullptr;
-    MYSLAM_HIP_CHECK(pinned ? hipHostMalloc((void**)&p, sizeof(T) * n) : hipMalloc((void**)&p, sizeof(T) * n));
-    return MYSLAM_OK;
-}
-
 enum QueryKind { Q_PLAIN, Q_SHARDED, Q_OWNED };
 
 // Every piece of the context's scratch that a call of `kind` with nq queries needs, the partial results sized for the whole allocation (a later
@@ -474,7 +462,7 @@ enum QueryKind { Q_PLAIN, Q_SHARDED, Q_OWNED };
 // launches cover).
 static int ctx_scratch(myslam_lcddb_query_ctx* c, QueryKind kind, int nq, int cap_rows, bool capturing) {
     const size_t need = (size_t)scan_blocks(nq, cap_rows) * nq;
-    const bool lim = kind != Q_OWNED && nq > c->nvalidCap, part = need > c->partialsCap;
+    const bool lim = kind != Q_OWNED && nq > c->nvalidCap, part = need > c->d_partials.size();
     const bool shard = kind == Q_SHARDED && nq > c->shardCap, own = kind == Q_OWNED && nq > c->ownCap;
     if (!lim && !part && !shard && !own) return MYSLAM_OK;
     if (capturing) return MYSLAM_ERR_UNSUPPORTED;
@@ -484,31 +472,40 @@ static int ctx_scratch(myslam_lcddb_query_ctx* c, QueryKind kind, int nq, int ca
         c->link->scratch_epoch.fetch_add(1);
         c->graphRows = 0; c->graphQueries = 0;
     }
+    int rc;
     if (lim) {
-        c->nvalidCap = 0; c->nvFresh = false;
-        if (renew(c->d_nvalid, nq + 1) || renew(c->h_nvalid, (size_t)(nq + 1) * (1 + myslam_lcddb_query_ctx::NV_RING), true)) return MYSLAM_ERR_HIP;
-        for (int r = 0; r < myslam_lcddb_query_ctx::NV_RING; r++) {
-            if (!c->nvRingEv[r]) MYSLAM_HIP_CHECK(hipEventCreateWithFlags(&c->nvRingEv[r], hipEventDisableTiming));
-            c->nvRingPending[r] = false;                              // (ctx_quiesce above: nothing of the old buffer is in flight)
-        }
-        c->nvalidCap = nq;
+        c->nvFresh = false;
+        rc = regrow(c->nvalidCap, nq, [&]() -> int {
+            int rc;
+            if ((rc = c->d_nvalid.renew(nq + 1)) || (rc = c->h_nvalid.renew((size_t)(nq + 1) * (1 + myslam_lcddb_query_ctx::NV_RING)))) return rc;
+            for (int r = 0; r < myslam_lcddb_query_ctx::NV_RING; r++) {
+                if (!c->nvRingEv[r]) MYSLAM_HIP_CHECK(hipEventCreateWithFlags(&c->nvRingEv[r], hipEventDisableTiming));
+                c->nvRingPending[r] = false;                          // (ctx_quiesce above: nothing of the old buffer is in flight)
+            }
+            return MYSLAM_OK;
+        });
+        if (rc) return rc;
     }
-    if (part) {
-        c->partialsCap = 0;
-        if (renew(c->d_partials, need)) return MYSLAM_ERR_HIP;
-        c->partialsCap = need;
-    }
+    if (part && (rc = c->d_partials.renew(need))) return rc;
     if (shard) {
-        c->shardCap = 0;
-        if (renew(c->d_bestS, nq) || renew(c->d_maxS, nq) || renew(c->d_cntS, nq)) return MYSLAM_ERR_HIP;
-        c->shardCap = nq;
+        rc = regrow(c->shardCap, nq, [&]() -> int {
+            int rc;
+            if ((rc = c->d_bestS.renew(nq)) || (rc = c->d_maxS.renew(nq)) || (rc = c->d_cntS.renew(nq))) return rc;
+            return MYSLAM_OK;
+        });
+        if (rc) return rc;
     }
     if (own) {
-        c->ownCap = 0; c->ownPending = false;
-        if (renew(c->h_own, 4 * nq, true) || renew(c->d_own, 4 * nq) || renew(c->d_bestO, 2 * nq) || renew(c->d_maxO, 2 * nq) || renew(c->d_cntO, 2 * nq))
-            return MYSLAM_ERR_HIP;
-        if (!c->ownEvent) MYSLAM_HIP_CHECK(hipEventCreateWithFlags(&c->ownEvent, hipEventDisableTiming));
-        c->ownCap = nq;
+        c->ownPending = false;
+        rc = regrow(c->ownCap, nq, [&]() -> int {
+            int rc;
+            if ((rc = c->h_own.renew(4 * nq)) || (rc = c->d_own.renew(4 * nq)) || (rc = c->d_bestO.renew(2 * nq)) || (rc = c->d_maxO.renew(2 * nq)) ||
+                (rc = c->d_cntO.renew(2 * nq)))
+                return rc;
+            if (!c->ownEvent) MYSLAM_HIP_CHECK(hipEventCreateWithFlags(&c->ownEvent, hipEventDisableTiming));
+            return MYSLAM_OK;
+        });
+        if (rc) return rc;
     }
     return MYSLAM_OK;
 }
@@ -562,17 +559,17 @@ int myslam_lcddb_create(myslam_lcddb** out, int capacity) {
     const int rowsPerBlock = DB_WAVES * DB_ROWS_PER_WAVE;
     h->capacity = (capacity + rowsPerBlock - 1) / rowsPerBlock * rowsPerBlock;      // scan reads whole blocks of rows
     auto alloc_all = [&]() -> int {
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&h->d_db, (size_t)h->capacity * DIM * sizeof(float)));
+        int rc;
+        if ((rc = h->d_db.renew((size_t)h->capacity * DIM))) return rc;
         {   // (not hipMemset: the legacy stream may not be touched while another thread records a graph on a blocking stream, common.h)
             const hipStream_t us = host_call_stream();
             if (!us) return MYSLAM_ERR_HIP;
             MYSLAM_HIP_CHECK(hipMemsetAsync(h->d_db, 0, (size_t)h->capacity * DIM * sizeof(float), us));
             MYSLAM_HIP_CHECK(hipStreamSynchronize(us));
         }
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&h->d_ids, (size_t)h->capacity * sizeof(uint64_t)));
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&h->d_q1, DIM * sizeof(float)));
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&h->d_best1, 8)); MYSLAM_HIP_CHECK(hipMalloc((void**)&h->d_max1, 4));
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&h->d_cnt1, 4));
+        if ((rc = h->d_ids.renew((size_t)h->capacity)) || (rc = h->d_q1.renew(DIM)) || (rc = h->d_best1.renew(1)) || (rc = h->d_max1.renew(1)) ||
+            (rc = h->d_cnt1.renew(1)))
+            return rc;
         return MYSLAM_OK;
     };
     const int rc = alloc_all();
@@ -585,11 +582,7 @@ int myslam_lcddb_destroy(myslam_lcddb* h) {
     if (!h) return MYSLAM_ERR_INVALID;
     (void)hipStreamSynchronize(h->stream);
     for (myslam_lcddb_query_ctx* c : h->ctxs) { (void)ctx_quiesce(c); ctx_free(c); }      // contexts die with their database
-    void* ptrs[] = {h->d_db, h->d_ids, h->d_q1, h->d_best1, h->d_max1, h->d_cnt1};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
     for (int r = 0; r < myslam_lcddb::ID_RING; r++) { if (h->idPending[r]) (void)hipEventSynchronize(h->idEv[r]); if (h->idEv[r]) (void)hipEventDestroy(h->idEv[r]); }
-    if (h->h_idring) (void)hipHostFree(h->h_idring);
-    for (auto& r : h->retired) { (void)hipFree(r.first); (void)hipFree(r.second); }
     delete h;
     return MYSLAM_OK;
 }
@@ -640,9 +633,9 @@ static int db_reserve(myslam_lcddb* h, long long rows) {
     if (rq) return rq;
     bool recorded = false;
     for (const myslam_lcddb_query_ctx* c : h->ctxs) recorded = recorded || c->graphRows > 0;
-    float* nd = nullptr; uint64_t* ni = nullptr;
-    if (hipMalloc((void**)&nd, (size_t)cap * DIM * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); return MYSLAM_ERR_CAPACITY; }
-    if (hipMalloc((void**)&ni, (size_t)cap * sizeof(uint64_t)) != hipSuccess) { (void)hipGetLastError(); (void)hipFree(nd); return MYSLAM_ERR_CAPACITY; }
+    Buf<float> nd; Buf<uint64_t> ni;                                      // the old matrix stays whole until the new one holds its rows
+    int rc;
+    if ((rc = nd.renew((size_t)cap * DIM, MYSLAM_ERR_CAPACITY)) || (rc = ni.renew((size_t)cap, MYSLAM_ERR_CAPACITY))) return rc;
     auto move_rows = [&]() -> int {
         if (h->n) {
             MYSLAM_HIP_CHECK(hipMemcpyAsync(nd, h->d_db, (size_t)h->n * DIM * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
@@ -652,14 +645,12 @@ static int db_reserve(myslam_lcddb* h, long long rows) {
         MYSLAM_HIP_CHECK(hipStreamSynchronize(h->stream));
         return MYSLAM_OK;
     };
-    const int rc = move_rows();
-    if (rc) { (void)hipFree(nd); (void)hipFree(ni); return rc; }
+    if ((rc = move_rows())) return rc;
     // A recorded step names the old pointers in its kernel nodes.  Its launch is refused from now on (generation check in
     // myslam_graph_launch), but a caller that ignores the status must still not touch freed memory: the old matrix stays allocated
     // until the database is destroyed (geometric growth: all retired matrices together are smaller than the live one).
-    if (recorded) h->retired.emplace_back(h->d_db, h->d_ids);
-    else { (void)hipFree(h->d_db); (void)hipFree(h->d_ids); }
-    h->d_db = nd; h->d_ids = ni; h->capacity = cap;
+    if (recorded) h->retired.emplace_back(std::move(h->d_db), std::move(h->d_ids));
+    h->d_db = std::move(nd); h->d_ids = std::move(ni); h->capacity = cap;      // (frees the old matrix unless it was retired)
     h->generation++;
     for (myslam_lcddb_query_ctx* c : h->ctxs) c->link->generation.store(h->generation);
     return MYSLAM_OK;
@@ -695,7 +686,8 @@ static int db_append_async(myslam_lcddb* h, const uint64_t* ids, const float* d_
     MYSLAM_HIP_CHECK(hipMemcpyAsync(h->d_db + (size_t)h->n * DIM, d_src, (size_t)n * DIM * sizeof(float), hipMemcpyDeviceToDevice, s));
     if (n <= myslam_lcddb::ID_SLOT) {                                  // ids through a pinned ring slot: the call never waits for the stream
         if (!h->h_idring) {
-            MYSLAM_HIP_CHECK(hipHostMalloc((void**)&h->h_idring, sizeof(uint64_t) * myslam_lcddb::ID_RING * myslam_lcddb::ID_SLOT));
+            const int rc = h->h_idring.renew((size_t)myslam_lcddb::ID_RING * myslam_lcddb::ID_SLOT);
+            if (rc) return rc;
             for (auto& e : h->idEv) MYSLAM_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         }
         const int r = h->idSlot; h->idSlot = (h->idSlot + 1) % myslam_lcddb::ID_RING;
@@ -784,7 +776,7 @@ static int db_query(myslam_lcddb_query_ctx* c, const float* d_q, const uint64_t*
         }
         c->lastLimits = c->scratchLimits; c->lastRows = rows_now; c->nvFresh = !cap;             // (a recorded scan reads whatever the pinned buffer holds at its replay)
     }
-    c->limits = cap ? c->h_nvalid : c->d_nvalid;
+    c->limits = cap ? c->h_nvalid.get() : c->d_nvalid.get();
     {
         ScopedProf sp(P_DBSCAN, c->stream);
         launch_scan(c, h->d_db, h->d_ids, cap_now, d_q, nq, c->limits, nullptr, maxv, thr_low, d_best, d_max, d_cnt);

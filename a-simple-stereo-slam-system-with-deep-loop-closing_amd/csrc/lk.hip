@@ -287,16 +287,16 @@ struct myslam_lk {
     int win = 11, max_level = 3, max_iters = 30; float eps = 0.01f, min_eig = 1e-4f;
     int rows = 0, cols = 0, batchCap = 0;
     LkGeom g{};
-    uint8_t *d_pyrP = nullptr, *d_pyrN = nullptr;
-    // host-entry staging
-    uint8_t* d_img = nullptr; size_t imgBytes = 0; float* d_pts = nullptr; uint8_t* d_st = nullptr; int ptsCap = 0;
+    Buf<uint8_t> d_pyrP, d_pyrN;
+    // host-entry staging: [prev | next] images; [prev_pts 2c | next_pts 2c | err c] floats and c status bytes for c points
+    Buf<uint8_t> d_img; Buf<float> d_pts; Buf<uint8_t> d_st;
     // myslam_lk_track_cached / myslam_lk_prefetch: two (image, pyramid) slots that remember WHICH image they hold (a caller's token): the
     // `next` image of one tracked frame is the `prev` image of the following one (Frontend::TrackLastFrame, frontend.cpp:150-153), and the
     // frame after that can be uploaded while the current one is still being optimised
-    struct Slot { uint8_t* img = nullptr; size_t imgBytes = 0; uint8_t* pyr = nullptr; size_t pyrBytes = 0; uint64_t tok = 0; int rows = 0, cols = 0, step = 0; };
+    struct Slot { Buf<uint8_t> img, pyr; uint64_t tok = 0; int rows = 0, cols = 0, step = 0; };
     Slot slot[2]; int lastNext = 0;
     // the cached call's points travel as ONE pinned upload [prev_pts | next_pts] and ONE pinned download [next_pts | err | status]
-    uint8_t* h_pin = nullptr; uint8_t* d_stage = nullptr; int stageCap = 0;
+    PinBuf<uint8_t> h_pin; Buf<uint8_t> d_stage;
 };
 
 static int lk_plan(myslam_lk* h, int rows, int cols) {
@@ -320,13 +320,12 @@ static int lk_ensure(myslam_lk* h, int batch, int rows, int cols) {
     if (rows != h->rows || cols != h->cols) { MYSLAM_HIP_CHECK(hipStreamSynchronize(h->stream)); lk_plan(h, rows, cols); }
     if (batch > h->batchCap) {
         MYSLAM_HIP_CHECK(hipStreamSynchronize(h->stream));
-        if (h->d_pyrP) (void)hipFree(h->d_pyrP);
-        if (h->d_pyrN) (void)hipFree(h->d_pyrN);
-        h->d_pyrP = h->d_pyrN = nullptr;
         const size_t nb = std::max<size_t>(256, (size_t)batch * h->g.bytes);
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&h->d_pyrP, nb));
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&h->d_pyrN, nb));
-        h->batchCap = batch;
+        return regrow(h->batchCap, batch, [&]() -> int {
+            int rc;
+            if ((rc = h->d_pyrP.renew(nb))) return rc;
+            return h->d_pyrN.renew(nb);
+        });
     }
     return MYSLAM_OK;
 }
@@ -379,13 +378,11 @@ static int lk_plan_cached(myslam_lk* h, int rows, int cols) {
 static int lk_fill_slot(myslam_lk* h, int i, const uint8_t* img, uint64_t tok, int rows, int cols, int step) {
     myslam_lk::Slot& S = h->slot[i];
     const size_t ib = (size_t)rows * step, pb = std::max<size_t>(256, h->g.bytes);
-    if (ib > S.imgBytes || pb > S.pyrBytes) {
+    if (ib > S.img.size() || pb > S.pyr.size()) {
         MYSLAM_HIP_CHECK(hipStreamSynchronize(h->stream));
-        if (S.img) (void)hipFree(S.img);
-        if (S.pyr) (void)hipFree(S.pyr);
         S = myslam_lk::Slot();
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&S.img, ib)); S.imgBytes = ib;
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&S.pyr, pb)); S.pyrBytes = pb;
+        int rc;
+        if ((rc = S.img.renew(ib)) || (rc = S.pyr.renew(pb))) return rc;
     }
     S.tok = 0;                                               // not valid until everything below is enqueued
     MYSLAM_HIP_CHECK(hipMemcpyAsync(S.img, img, ib - (size_t)(step - cols), hipMemcpyHostToDevice, h->stream));     // the last row ends at its last pixel
@@ -439,9 +436,6 @@ int myslam_lk_create(myslam_lk** out, int win, int max_level, int max_iters, flo
 int myslam_lk_destroy(myslam_lk* h) {
     if (!h) return MYSLAM_ERR_INVALID;
     (void)hipStreamSynchronize(h->stream);
-    void* ptrs[] = {h->d_pyrP, h->d_pyrN, h->d_img, h->d_pts, h->d_st, h->slot[0].img, h->slot[0].pyr, h->slot[1].img, h->slot[1].pyr, h->d_stage};
-    if (h->h_pin) (void)hipHostFree(h->h_pin);
-    for (void* p : ptrs) if (p) (void)hipFree(p);
     delete h;
     return MYSLAM_OK;
 }
@@ -467,27 +461,24 @@ int myslam_lk_track(myslam_lk* h, const uint8_t* prev, const uint8_t* next, int 
     // both images travel as ONE contiguous copy each with their own row pitch (a 2-D copy from pageable memory goes row by row: 5 ms
     // for a 1241 x 376 pair against 0.1 ms), the kernels read them with that pitch
     const size_t pb = ((size_t)rows * prev_step + 255) & ~(size_t)255, nb = (size_t)rows * next_step;
-    if (pb + nb > h->imgBytes) {
+    int rc;
+    if (pb + nb > h->d_img.size()) {
         MYSLAM_HIP_CHECK(hipStreamSynchronize(h->stream));
-        if (h->d_img) (void)hipFree(h->d_img);
-        h->d_img = nullptr; h->imgBytes = 0;
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&h->d_img, pb + nb)); h->imgBytes = pb + nb;
+        if ((rc = h->d_img.renew(pb + nb))) return rc;
     }
-    if (n > h->ptsCap) {
+    if ((size_t)n > std::min(h->d_pts.size() / 5, h->d_st.size())) {
         MYSLAM_HIP_CHECK(hipStreamSynchronize(h->stream));
-        if (h->d_pts) (void)hipFree(h->d_pts);
-        if (h->d_st) (void)hipFree(h->d_st);
-        h->d_pts = nullptr; h->d_st = nullptr; h->ptsCap = 0;
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&h->d_pts, sizeof(float) * 5 * (size_t)n)); MYSLAM_HIP_CHECK(hipMalloc((void**)&h->d_st, (size_t)n));
-        h->ptsCap = n;
+        h->d_pts.release(); h->d_st.release();
+        if ((rc = h->d_pts.renew(5 * (size_t)n)) || (rc = h->d_st.renew((size_t)n))) return rc;
     }
+    const size_t ptsCap = h->d_pts.size() / 5;
     hipStream_t s = h->stream;
     MYSLAM_HIP_CHECK(hipMemcpyAsync(h->d_img, prev, (size_t)rows * prev_step - (size_t)(prev_step - cols), hipMemcpyHostToDevice, s));      // the last row ends at its last pixel
     MYSLAM_HIP_CHECK(hipMemcpyAsync(h->d_img + pb, next, (size_t)rows * next_step - (size_t)(next_step - cols), hipMemcpyHostToDevice, s));
-    float* d_pp = h->d_pts; float* d_np = d_pp + 2 * (size_t)h->ptsCap; float* d_err = d_np + 2 * (size_t)h->ptsCap;
+    float* d_pp = h->d_pts; float* d_np = d_pp + 2 * ptsCap; float* d_err = d_np + 2 * ptsCap;
     MYSLAM_HIP_CHECK(hipMemcpyAsync(d_pp, prev_pts, sizeof(float) * 2 * n, hipMemcpyHostToDevice, s));
     MYSLAM_HIP_CHECK(hipMemcpyAsync(d_np, next_pts, sizeof(float) * 2 * n, hipMemcpyHostToDevice, s));
-    int rc = lk_run(h, h->d_img, h->d_img + pb, 1, rows, cols, prev_step, next_step, pb, nb, d_pp, d_np, nullptr, n, n, h->d_st, d_err);
+    rc = lk_run(h, h->d_img, h->d_img + pb, 1, rows, cols, prev_step, next_step, pb, nb, d_pp, d_np, nullptr, n, n, h->d_st, d_err);
     if (rc) return rc;
     MYSLAM_HIP_CHECK(hipMemcpyAsync(next_pts, d_np, sizeof(float) * 2 * n, hipMemcpyDeviceToHost, s));
     MYSLAM_HIP_CHECK(hipMemcpyAsync(status, h->d_st, n, hipMemcpyDeviceToHost, s));
@@ -515,23 +506,20 @@ int myslam_lk_track_cached(myslam_lk* h, const uint8_t* prev, uint64_t prev_toke
     if (sp >= 0 && sp == sn) sn = -1;                                                     // one token for both images: the second is uploaded
     if (sp < 0) { sp = sn < 0 ? 0 : 1 - sn; if ((rc = lk_fill_slot(h, sp, prev, prev_token, rows, cols, prev_step))) return rc; }
     if (sn < 0) { sn = 1 - sp; if ((rc = lk_fill_slot(h, sn, next, next_token, rows, cols, next_step))) return rc; }
-    if (n > h->stageCap) {
+    if ((size_t)21 * n + 16 > std::min(h->d_stage.size(), h->h_pin.size())) {
         MYSLAM_HIP_CHECK(hipStreamSynchronize(h->stream));
-        if (h->d_stage) (void)hipFree(h->d_stage);
-        if (h->h_pin) (void)hipHostFree(h->h_pin);
-        h->d_stage = nullptr; h->h_pin = nullptr; h->stageCap = 0;
-        const int cap = std::max(n, 512);
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&h->d_stage, (size_t)21 * cap + 16)); MYSLAM_HIP_CHECK(hipHostMalloc((void**)&h->h_pin, (size_t)21 * cap + 16));
-        h->stageCap = cap;
+        h->d_stage.release(); h->h_pin.release();
+        const size_t bytes = (size_t)21 * std::max(n, 512) + 16;
+        if ((rc = h->d_stage.renew(bytes)) || (rc = h->h_pin.renew(bytes))) return rc;
     }
     hipStream_t s = h->stream;
     // device block: [prev_pts 8n][next_pts 8n][err 4n][status n]; upload = the first 16n bytes, download = the last 13n
-    float* d_pp = reinterpret_cast<float*>(h->d_stage); float* d_np = d_pp + 2 * (size_t)n; float* d_err = d_np + 2 * (size_t)n;
+    float* d_pp = reinterpret_cast<float*>(h->d_stage.get()); float* d_np = d_pp + 2 * (size_t)n; float* d_err = d_np + 2 * (size_t)n;
     uint8_t* d_st = reinterpret_cast<uint8_t*>(d_err + n);
     memcpy(h->h_pin, prev_pts, sizeof(float) * 2 * n); memcpy(h->h_pin + sizeof(float) * 2 * n, next_pts, sizeof(float) * 2 * n);
     MYSLAM_HIP_CHECK(hipMemcpyAsync(h->d_stage, h->h_pin, sizeof(float) * 4 * n, hipMemcpyHostToDevice, s));
     const myslam_lk::Slot &P = h->slot[sp], &N = h->slot[sn];
-    if ((rc = lk_track_launch(h, P.img, N.img, P.pyr, N.pyr, 1, rows, cols, prev_step, next_step, P.imgBytes, N.imgBytes, d_pp, d_np, nullptr, n, n, d_st, d_err)))
+    if ((rc = lk_track_launch(h, P.img, N.img, P.pyr, N.pyr, 1, rows, cols, prev_step, next_step, P.img.size(), N.img.size(), d_pp, d_np, nullptr, n, n, d_st, d_err)))
         return rc;
     h->lastNext = sn;
     uint8_t* hp = h->h_pin + sizeof(float) * 2 * n;

@@ -472,8 +472,8 @@ using namespace myslam_hip;
 struct myslam_loop_corrector {
     int max_batch = 0, kf_cap = 0, edge_cap = 0, active_cap = 0, point_cap = 0;
     hipStream_t stream = nullptr;
-    double* d_scratch = nullptr;
-    int32_t* i_scratch = nullptr;
+    Buf<double> d_scratch;
+    Buf<int32_t> i_scratch;
     LcLayout lay{};
 };
 
@@ -481,8 +481,7 @@ extern "C" {
 
 int myslam_loop_corrector_destroy(myslam_loop_corrector* h) {
     if (!h) return MYSLAM_ERR_INVALID;
-    if (h->d_scratch) (void)hipFree(h->d_scratch);
-    if (h->i_scratch) (void)hipFree(h->i_scratch);
+    (void)hipStreamSynchronize(h->stream);
     delete h;
     return MYSLAM_OK;
 }
@@ -506,12 +505,11 @@ int myslam_loop_corrector_create(myslam_loop_corrector** out, int max_batch, int
     o = 0;
     L.fx = take(n); L.fpos = take(n); L.inS = take(n); L.slot = take(n); L.adjOff = take(n + 1); L.adj = take(2 * E);
     L.istride = o;
-    hipError_t e = hipMalloc((void**)&h->d_scratch, L.dstride * (size_t)max_batch * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->i_scratch, L.istride * (size_t)max_batch * sizeof(int32_t));
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        (void)myslam_loop_corrector_destroy(h);
-        return e == hipErrorOutOfMemory ? MYSLAM_ERR_CAPACITY : MYSLAM_ERR_HIP;
+    int rc;
+    if ((rc = h->d_scratch.renew(L.dstride * (size_t)max_batch, MYSLAM_ERR_CAPACITY)) ||
+        (rc = h->i_scratch.renew(L.istride * (size_t)max_batch, MYSLAM_ERR_CAPACITY))) {
+        delete h;
+        return rc;
     }
     *out = h;
     return MYSLAM_OK;

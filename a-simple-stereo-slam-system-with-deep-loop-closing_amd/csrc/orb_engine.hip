@@ -34,14 +34,6 @@ void gauss_q8(int kind, int q[7]) {
     for (int i = 0; i < 7; i++) q[i] = (int)lrint(g[i] / sum * 256.0);
 }
 
-template <typename T>
-static int dev_alloc(T*& p, size_t n) {
-    if (p) { (void)hipFree(p); p = nullptr; }
-    if (n == 0) return MYSLAM_OK;
-    MYSLAM_HIP_CHECK(hipMalloc((void**)&p, n * sizeof(T)));
-    return MYSLAM_OK;
-}
-
 }  // namespace myslam_hip
 
 using namespace myslam_hip;
@@ -66,19 +58,18 @@ struct myslam_orb {
 
     // batch buffers
     int batchCap = 0;
-    bool maskAlloc = false;
-    uint8_t *d_pyr = nullptr, *d_blur = nullptr, *d_mask = nullptr;
-    uint32_t* d_cand = nullptr;
-    uint32_t* d_sort = nullptr;        // per level the candidates' 32-bit sort entries in bucket order + their path codes
-    int32_t *d_candCount = nullptr, *d_selCount = nullptr, *d_status = nullptr;
-    uint32_t* d_sel = nullptr;
-    uint16_t* d_order = nullptr;       // processing order of the descriptor kernel (tile order of the selected keys, orb_kernels.hip k_sel_order)
-    uint32_t* d_octTab = nullptr;      // per-level oct-tree path-code / cell-index tables (see make_plan)
-    uint32_t* d_stripTab = nullptr;    // per-strip head of the grid-FAST kernel (see make_plan, orb_plan.h)
-    uint32_t* d_resizeTab = nullptr;   // column and row records of the strip resize (resize_tab.h), per level that takes the strip form
+    Buf<uint8_t> d_pyr, d_blur, d_mask;      // d_mask: allocated by the first call that brings masks, dropped when the batch grows
+    Buf<uint32_t> d_cand;
+    Buf<uint32_t> d_sort;              // per level the candidates' 32-bit sort entries in bucket order + their path codes
+    Buf<int32_t> d_candCount, d_selCount, d_status;
+    Buf<uint32_t> d_sel;
+    Buf<uint16_t> d_order;             // processing order of the descriptor kernel (tile order of the selected keys, orb_kernels.hip k_sel_order)
+    Buf<uint32_t> d_octTab;            // per-level oct-tree path-code / cell-index tables (see make_plan)
+    Buf<uint32_t> d_stripTab;          // per-strip head of the grid-FAST kernel (see make_plan, orb_plan.h)
+    Buf<uint32_t> d_resizeTab;         // column and row records of the strip resize (resize_tab.h), per level that takes the strip form
     size_t resizeColOff[MAXL] = {0}, resizeRowOff[MAXL] = {0}; bool resizeLvOk[MAXL] = {false};      // dword offsets into d_resizeTab of level l (written from level l - 1)
     // FAST path selection (orb_kernels.hip FastCtl): two [MAXL][4] counter blocks, the launch accumulates into one and reads the other
-    uint32_t* d_fastStat = nullptr; int fastFlip = 0;
+    Buf<uint32_t> d_fastStat; int fastFlip = 0;
     // options (myslam_orb_set_option)
     int optFastMode = -1;              // -1 = chosen per level from the previous launch's statistics, 0 = two-phase, 1 = dense
     int optInternalStream = 1;         // 0 = everything on the caller's stream, 1 = Gaussian pyramid forked after FAST (default), 2 = after the image pyramid
@@ -87,7 +78,7 @@ struct myslam_orb {
     int tapsSet = 0, taps[7] = {0};    // myslam_orb_set_gauss_taps: replacement of the sigma = 2 Q8 taps
     int optSideBlocksPerCu = 0;        // > 0: the descriptor kernel runs as a limited grid of this many blocks per CU (each walks several work items)
     int optBlurMfma = 0;               // 1 = the Gaussian pyramid on the int8 matrix cores (k_blur7_mfma) for every level that can take it
-    uint4* d_blurTab = nullptr; bool blurTabValid = false; size_t blurOffI = 0, blurOffH[MAXL] = {0}, blurOffV[MAXL] = {0}; bool blurLvOk[MAXL] = {false}; int blurVconst = 0;
+    Buf<uint4> d_blurTab; bool blurTabValid = false; size_t blurOffI = 0, blurOffH[MAXL] = {0}, blurOffV[MAXL] = {0}; bool blurLvOk[MAXL] = {false}; int blurVconst = 0;
     int ensure_blur_tables();
 
     // Host-pointer calls (one frame per call: the drop-ins) replay a HIP graph: the ~35 launches, memsets and the copies of a call are
@@ -114,14 +105,17 @@ struct myslam_orb {
     ZeroArgs clr{};
     ZeroArgs take_clear() { const ZeroArgs z = clr; clr = ZeroArgs{}; return z; }
     hipStream_t hostStream = nullptr;    // the host-pointer calls' stream when the handle has none (the legacy NULL stream cannot be captured)
-    uint8_t* h_pin = nullptr; size_t pinBytes = 0;      // pinned staging: image, mask, counts, key-points, descriptors
+    PinBuf<uint8_t> h_pin;               // pinned staging: image, mask, counts, key-points, descriptors
     int ensure_pin(size_t bytes);
     void drop_host_graphs();
     // staging for the host-buffer entry points
-    uint8_t *d_stageImg = nullptr, *d_stageMask = nullptr; size_t stageImgBytes = 0, stageMaskBytes = 0;
-    myslam_keypoint *d_stageKps = nullptr, *d_stageKps2 = nullptr; uint8_t* d_stageDesc = nullptr; uint8_t* d_stageKeep = nullptr;
-    int32_t* d_stageCounts = nullptr; int stageCap = 0;
-    uint8_t* d_stageOut = nullptr; size_t stageOutBytes = 0, stageDescOff = 0;      // the block d_stageCounts / d_stageKps / d_stageDesc point into
+    Buf<uint8_t> d_stageImg, d_stageMask;
+    int stageCap = 0;
+    Buf<uint8_t> d_stageOut; size_t stageDescOff = 0;      // [256 bytes: counts][stageCap key-points][stageCap descriptors], see ensure_stage
+    int32_t* stage_counts() const { return reinterpret_cast<int32_t*>(d_stageOut.get()); }
+    myslam_keypoint* stage_kps() const { return reinterpret_cast<myslam_keypoint*>(d_stageOut + 256); }
+    uint8_t* stage_desc() const { return d_stageOut + stageDescOff; }
+    Buf<myslam_keypoint> d_stageKps2; Buf<uint8_t> d_stageKeep;
 
     int make_tables();
     void level_size(int l, int r, int c, int& w, int& h) const {          // ORBextractor.cpp:1237-1238
@@ -133,7 +127,7 @@ struct myslam_orb {
     int ensure_fast_stat();
     // ProcessNewKF's ORB half for a batch of key-frames (myslam_orb_process_keyframes_batch): the screened key-points and keep flags of
     // batch x feat_cap x nlevels pyramid rows
-    myslam_keypoint* d_pkfRows = nullptr; uint8_t* d_pkfKeep = nullptr; size_t pkfRowCap = 0;
+    Buf<myslam_keypoint> d_pkfRows; Buf<uint8_t> d_pkfKeep;
     int ensure_pkf(size_t nrows);
     int process_keyframes(const uint8_t* d_imgs, int batch, int r, int c, int step, size_t stride, const float* d_feat_xy, const int32_t* d_n_feat,
                           int feat_cap, myslam_keypoint* d_pyr_kps, uint8_t* d_desc, int32_t* d_counts, int32_t* d_stat, int cap);
@@ -263,7 +257,7 @@ int myslam_orb::make_plan(int r, int c) {
                 ycell[py] = (uint32_t)((std::max(py - 3, 0) / g.hCell) * g.nCols);
             }
         }
-        int rc = dev_alloc(d_octTab, tab.size());
+        int rc = d_octTab.renew(tab.size());
         if (rc) return rc;
         if ((rc = upload_table(d_octTab, tab.data(), tab.size() * sizeof(uint32_t)))) return rc;
     }
@@ -298,7 +292,7 @@ int myslam_orb::make_plan(int r, int c) {
                 e[6] = (uint32_t)(g.imgOff & 0xffffffffu); e[7] = (uint32_t)(g.imgOff >> 32);
             }
         }
-        int rc = dev_alloc(d_stripTab, st.size());
+        int rc = d_stripTab.renew(st.size());
         if (rc) return rc;
         if ((rc = upload_table(d_stripTab, st.data(), st.size() * sizeof(uint32_t)))) return rc;
         P.stripTab = d_stripTab;
@@ -319,7 +313,7 @@ int myslam_orb::make_plan(int r, int c) {
             rt.insert(rt.end(), reinterpret_cast<const uint32_t*>(rr.data()), reinterpret_cast<const uint32_t*>(rr.data() + rr.size()));
             rt.resize((rt.size() + 7) & ~(size_t)7, 0u);
         }
-        int rc = dev_alloc(d_resizeTab, rt.size());
+        int rc = d_resizeTab.renew(rt.size());
         if (rc) return rc;
         if (!rt.empty() && (rc = upload_table(d_resizeTab, rt.data(), rt.size() * sizeof(uint32_t)))) return rc;
     }
@@ -348,25 +342,22 @@ int myslam_orb::ensure(int batch, int r, int c, bool needMask) {
     if (batch > batchCap) {
         MYSLAM_HIP_CHECK(hipStreamSynchronize(stream));
         gen++;
-        int rc;
-        if ((rc = dev_alloc(d_pyr, (size_t)batch * full.pyrBytes + 64))) return rc;      // + 64: the resize kernel's 8-byte row loads may run 7 bytes past a row
-        if ((rc = dev_alloc(d_blur, (size_t)batch * full.pyrBytes + 4096))) return rc;     // + 4096: a descriptor window's fourth tile column may lie past the last plane
-        if ((rc = dev_alloc(d_cand, (size_t)batch * full.totalKeyCap))) return rc;
-        if ((rc = dev_alloc(d_sort, (size_t)batch * full.totalKeyCap * 2))) return rc;
-        if ((rc = dev_alloc(d_candCount, (size_t)batch * MAXL))) return rc;
-        if ((rc = dev_alloc(d_selCount, (size_t)batch * MAXL))) return rc;
-        if ((rc = dev_alloc(d_status, (size_t)batch))) return rc;
-        if ((rc = dev_alloc(d_sel, (size_t)batch * selPer))) return rc;
-        if ((rc = dev_alloc(d_order, (size_t)batch * selPer))) return rc;
-        if ((rc = dev_alloc(d_mask, 0))) return rc;
-        maskAlloc = false;
-        batchCap = batch;
-    }
-    if (needMask && !maskAlloc) {
-        int rc = dev_alloc(d_mask, (size_t)batchCap * full.pyrBytes + 64);
+        d_mask.release();
+        int rc = regrow(batchCap, batch, [&]() -> int {
+            int rc;
+            if ((rc = d_pyr.renew((size_t)batch * full.pyrBytes + 64))) return rc;       // + 64: the resize kernel's 8-byte row loads may run 7 bytes past a row
+            if ((rc = d_blur.renew((size_t)batch * full.pyrBytes + 4096))) return rc;    // + 4096: a descriptor window's fourth tile column may lie past the last plane
+            if ((rc = d_cand.renew((size_t)batch * full.totalKeyCap))) return rc;
+            if ((rc = d_sort.renew((size_t)batch * full.totalKeyCap * 2))) return rc;
+            if ((rc = d_candCount.renew((size_t)batch * MAXL))) return rc;
+            if ((rc = d_selCount.renew((size_t)batch * MAXL))) return rc;
+            if ((rc = d_status.renew((size_t)batch))) return rc;
+            if ((rc = d_sel.renew((size_t)batch * selPer))) return rc;
+            return d_order.renew((size_t)batch * selPer);
+        });
         if (rc) return rc;
-        maskAlloc = true;
     }
+    if (needMask && !d_mask) return d_mask.renew((size_t)batchCap * full.pyrBytes + 64);
     return MYSLAM_OK;
 }
 
@@ -440,7 +431,7 @@ int myslam_orb::ensure_blur_tables() {
     blur_mfma_ident(tab, blurOffI);
     for (int l = 0; l < full.nlevels; l++) blurLvOk[l] = blur_mfma_tables(full.lv[l].w, full.lv[l].h, q, tab, blurOffH[l], blurOffV[l]);
     MYSLAM_HIP_CHECK(hipStreamSynchronize(stream));
-    int rc = dev_alloc(d_blurTab, tab.size());
+    int rc = d_blurTab.renew(tab.size());
     if (rc) return rc;
     if ((rc = upload_table(d_blurTab, tab.data(), tab.size() * sizeof(uint4)))) return rc;
     blurTabValid = true; gen++;
@@ -485,7 +476,7 @@ int myslam_orb::run_batch(const uint8_t* d_imgs, int batch, int r, int c, int st
     if ((rc = ensure_fast_stat())) return rc;
     // candidate / selection counters, status words and the FAST statistics block this call accumulates into (run_fast) are cleared by the
     // call's first launch, the level-0 ingest (build_pyramids)
-    clr = {{reinterpret_cast<uint32_t*>(d_candCount), reinterpret_cast<uint32_t*>(d_selCount), reinterpret_cast<uint32_t*>(stat), d_fastStat + (size_t)fastFlip * MAXL * 4},
+    clr = {{reinterpret_cast<uint32_t*>(d_candCount.get()), reinterpret_cast<uint32_t*>(d_selCount.get()), reinterpret_cast<uint32_t*>(stat), d_fastStat + (size_t)fastFlip * MAXL * 4},
            {batch * MAXL, batch * MAXL, batch, MAXL * 4}};
     const int stop = optStopAfter;
     // Level 0 in place: every image but the last of the batch is read where the caller put it (no copy into the pyramid block: 0.94 MB
@@ -569,13 +560,9 @@ int myslam_orb::run_fast(const OrbPlan& P, const uint8_t* maskPyr, int batch) {
 }
 
 int myslam_orb::ensure_pin(size_t bytes) {
-    if (bytes <= pinBytes) return MYSLAM_OK;
-    if (h_pin) { (void)hipHostFree(h_pin); h_pin = nullptr; pinBytes = 0; }
+    if (bytes <= h_pin.size()) return MYSLAM_OK;
     gen++;
-    const size_t want = (bytes + (bytes >> 2) + 4095) & ~(size_t)4095;
-    MYSLAM_HIP_CHECK(hipHostMalloc((void**)&h_pin, want));
-    pinBytes = want;
-    return MYSLAM_OK;
+    return h_pin.renew((bytes + (bytes >> 2) + 4095) & ~(size_t)4095);
 }
 
 void myslam_orb::drop_host_graphs() {
@@ -585,7 +572,8 @@ void myslam_orb::drop_host_graphs() {
 
 int myslam_orb::ensure_fast_stat() {
     if (d_fastStat) return MYSLAM_OK;
-    MYSLAM_HIP_CHECK(hipMalloc((void**)&d_fastStat, sizeof(uint32_t) * 2 * MAXL * 4));
+    int rc = d_fastStat.renew(2 * MAXL * 4);
+    if (rc) return rc;
     MYSLAM_HIP_CHECK(hipMemsetAsync(d_fastStat, 0, sizeof(uint32_t) * 2 * MAXL * 4, stream));
     return MYSLAM_OK;
 }
@@ -593,15 +581,12 @@ int myslam_orb::ensure_fast_stat() {
 // scratch of process_keyframes, grown like ensure()'s blocks: the stream is drained before a block moves, and whatever was recorded against the
 // old one is dropped
 int myslam_orb::ensure_pkf(size_t nrows) {
-    if (nrows <= pkfRowCap) return MYSLAM_OK;
+    if (nrows <= std::min(d_pkfRows.size(), d_pkfKeep.size())) return MYSLAM_OK;
     MYSLAM_HIP_CHECK(hipStreamSynchronize(stream));
     gen++; drop_host_graphs();
-    pkfRowCap = 0;
     int rc;
-    if ((rc = dev_alloc(d_pkfRows, nrows))) return rc;
-    if ((rc = dev_alloc(d_pkfKeep, nrows))) return rc;
-    pkfRowCap = nrows;
-    return MYSLAM_OK;
+    if ((rc = d_pkfRows.renew(nrows))) return rc;
+    return d_pkfKeep.renew(nrows);
 }
 
 // LoopClosing::ProcessNewKF's ORB half (src/loopclosing.cpp:93-113) for `batch` key-frames: ComputePyramid (ORBextractor.cpp:1096), the Gaussian
@@ -649,34 +634,28 @@ int myslam_orb::stage_pyramid(const uint8_t* img, int r, int c, int step, const 
 }
 
 int myslam_orb::ensure_stage(size_t imgBytes, size_t maskBytes, int cap) {
-    if (imgBytes > stageImgBytes) { gen++; int rc = dev_alloc(d_stageImg, imgBytes); if (rc) return rc; stageImgBytes = imgBytes; }
-    if (maskBytes > stageMaskBytes) { gen++; int rc = dev_alloc(d_stageMask, maskBytes); if (rc) return rc; stageMaskBytes = maskBytes; }
+    int rc;
+    if (imgBytes > d_stageImg.size()) { gen++; if ((rc = d_stageImg.renew(imgBytes))) return rc; }
+    if (maskBytes > d_stageMask.size()) { gen++; if ((rc = d_stageMask.renew(maskBytes))) return rc; }
     if (cap > stageCap) {
         gen++;
-        int rc;
         // counts, key-points and descriptors of a one-frame call share ONE block ([256 bytes][cap key-points][cap descriptors]): the
         // call brings all of it back in one device -> host copy
-        const size_t oK = 256, oD = oK + (((size_t)cap * sizeof(myslam_keypoint) + 255) & ~(size_t)255), total = oD + (size_t)cap * 32;
-        if ((rc = dev_alloc(d_stageOut, total))) return rc;
-        stageOutBytes = total; stageDescOff = oD;
-        d_stageCounts = reinterpret_cast<int32_t*>(d_stageOut);
-        d_stageKps = reinterpret_cast<myslam_keypoint*>(d_stageOut + oK);
-        d_stageDesc = d_stageOut + oD;
-        if ((rc = dev_alloc(d_stageKps2, (size_t)cap))) return rc;
-        if ((rc = dev_alloc(d_stageKeep, (size_t)cap))) return rc;
-        stageCap = cap;
+        stageDescOff = 256 + (((size_t)cap * sizeof(myslam_keypoint) + 255) & ~(size_t)255);
+        return regrow(stageCap, cap, [&]() -> int {
+            int rc;
+            if ((rc = d_stageOut.renew(stageDescOff + (size_t)cap * 32))) return rc;
+            if ((rc = d_stageKps2.renew((size_t)cap))) return rc;
+            return d_stageKeep.renew((size_t)cap);
+        });
     }
     return MYSLAM_OK;
 }
 
 void myslam_orb::free_all() {
-    void* ptrs[] = {d_blurTab, d_fastStat, d_octTab, d_stripTab, d_resizeTab, d_pyr, d_blur, d_mask, d_cand, d_sort, d_candCount, d_selCount, d_status, d_sel, d_order, d_stageImg, d_stageMask,
-                    d_stageOut, d_stageKps2, d_stageKeep, d_pkfRows, d_pkfKeep};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
     if (aux) { (void)hipStreamSynchronize(aux); (void)hipStreamDestroy(aux); (void)hipEventDestroy(evFork); (void)hipEventDestroy(evJoin); aux = nullptr; }
     drop_host_graphs();
     if (hostStream) { (void)hipStreamSynchronize(hostStream); (void)hipStreamDestroy(hostStream); hostStream = nullptr; }
-    if (h_pin) { (void)hipHostFree(h_pin); h_pin = nullptr; pinBytes = 0; }
 }
 
 // =================================================================================================
@@ -825,7 +804,7 @@ static int host_extract(myslam_orb* h, const uint8_t* img, int rows, int cols, i
     const size_t oOut = (imgBytes + maskBytes + 255) & ~(size_t)255, oCnt = oOut, oKps = oOut + 256, oDesc = oOut + h->stageDescOff;
     // what a call copies back: everything up to the last slot it can fill (Detect: no descriptors)
     const size_t outBytes = detectOnly ? 256 + sizeof(myslam_keypoint) * (size_t)dcap : h->stageDescOff + (size_t)32 * dcap;
-    if ((rc = h->ensure_pin(oOut + h->stageOutBytes))) return rc;
+    if ((rc = h->ensure_pin(oOut + h->d_stageOut.size()))) return rc;
     // the caller's stream, or a private one: host-pointer calls complete before they return, so the stream they run on is invisible —
     // work the caller queued on the handle's own stream that uses the handle's buffers (a _batch call) is waited for first
     hipStream_t caller = h->stream;
@@ -842,7 +821,7 @@ static int host_extract(myslam_orb* h, const uint8_t* img, int rows, int cols, i
         MYSLAM_HIP_CHECK(hipMemcpyAsync(h->d_stageImg, h->h_pin, imgBytes, hipMemcpyHostToDevice, hs));
         if (mask) MYSLAM_HIP_CHECK(hipMemcpyAsync(h->d_stageMask, h->h_pin + imgBytes, maskBytes, hipMemcpyHostToDevice, hs));
         int r2 = h->run_batch(h->d_stageImg, 1, rows, cols, step, imgBytes, mask ? h->d_stageMask : nullptr,
-                              h->d_stageKps, h->d_stageDesc, h->d_stageCounts, h->d_stageCounts + 1, dcap, detectOnly);
+                              h->stage_kps(), h->stage_desc(), h->stage_counts(), h->stage_counts() + 1, dcap, detectOnly);
         if (r2) return r2;
         MYSLAM_HIP_CHECK(hipMemcpyAsync(h->h_pin + oOut, h->d_stageOut, outBytes, hipMemcpyDeviceToHost, hs));      // counts + key-points (+ descriptors): one copy
         return MYSLAM_OK;
@@ -903,14 +882,14 @@ int myslam_orb_screen_and_compute_params(myslam_orb* h, const uint8_t* img, int 
     for (int i = 0; i < n_in; i++) if (kps_in[i].octave < 0 || kps_in[i].octave >= h->nlevels) return MYSLAM_ERR_INVALID;
     int rc = h->stage_pyramid(img, rows, cols, step, nullptr, n_in);        // upload, ComputePyramid (ORBextractor.cpp:1096)
     if (rc) return rc;
-    MYSLAM_HIP_CHECK(hipMemcpyAsync(h->d_stageKps, kps_in, sizeof(myslam_keypoint) * n_in, hipMemcpyHostToDevice, h->stream));
+    MYSLAM_HIP_CHECK(hipMemcpyAsync(h->stage_kps(), kps_in, sizeof(myslam_keypoint) * n_in, hipMemcpyHostToDevice, h->stream));
     {
         ScopedProf sp(P_SCREEN, h->stream);
-        launch_screen(h->full, h->d_pyr, h->d_stageKps, n_in, h->d_stageKps2, h->d_stageKeep, h->stream);
+        launch_screen(h->full, h->d_pyr, h->stage_kps(), n_in, h->d_stageKps2, h->d_stageKeep, h->stream);
     }
     std::vector<myslam_keypoint> tmp(n_in);
     std::vector<uint8_t> keep(n_in);
-    MYSLAM_HIP_CHECK(hipMemcpyAsync(kps_in, h->d_stageKps, sizeof(myslam_keypoint) * n_in, hipMemcpyDeviceToHost, h->stream));
+    MYSLAM_HIP_CHECK(hipMemcpyAsync(kps_in, h->stage_kps(), sizeof(myslam_keypoint) * n_in, hipMemcpyDeviceToHost, h->stream));
     MYSLAM_HIP_CHECK(hipMemcpyAsync(tmp.data(), h->d_stageKps2, sizeof(myslam_keypoint) * n_in, hipMemcpyDeviceToHost, h->stream));
     MYSLAM_HIP_CHECK(hipMemcpyAsync(keep.data(), h->d_stageKeep, n_in, hipMemcpyDeviceToHost, h->stream));
     MYSLAM_HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -930,12 +909,12 @@ int myslam_orb_calc_descriptors(myslam_orb* h, const uint8_t* img, int rows, int
     int rc = h->stage_pyramid(img, rows, cols, step, nullptr, n);           // :1192
     if (rc) return rc;
     if ((rc = h->blur_levels(1, h->nlevels, h->stream))) return rc;
-    MYSLAM_HIP_CHECK(hipMemcpyAsync(h->d_stageKps, kps, sizeof(myslam_keypoint) * n, hipMemcpyHostToDevice, h->stream));
+    MYSLAM_HIP_CHECK(hipMemcpyAsync(h->stage_kps(), kps, sizeof(myslam_keypoint) * n, hipMemcpyHostToDevice, h->stream));
     {
         ScopedProf sp(P_DESC, h->stream);
-        launch_calc_desc(h->full, h->d_blur, h->d_stageKps, n, h->d_stageDesc, h->stream);
+        launch_calc_desc(h->full, h->d_blur, h->stage_kps(), n, h->stage_desc(), h->stream);
     }
-    MYSLAM_HIP_CHECK(hipMemcpyAsync(desc, h->d_stageDesc, (size_t)32 * n, hipMemcpyDeviceToHost, h->stream));
+    MYSLAM_HIP_CHECK(hipMemcpyAsync(desc, h->stage_desc(), (size_t)32 * n, hipMemcpyDeviceToHost, h->stream));
     MYSLAM_HIP_CHECK(hipStreamSynchronize(h->stream));
     return MYSLAM_OK;
 }
@@ -975,7 +954,7 @@ int myslam_orb_debug_candidates(myslam_orb* h, const uint8_t* img, int rows, int
     int rc = h->stage_pyramid(img, rows, cols, step, mask, 16);
     if (rc) return rc;
     if ((rc = h->ensure_fast_stat())) return rc;
-    launch_zero_u32(ZeroArgs{{reinterpret_cast<uint32_t*>(h->d_candCount), h->d_fastStat + (size_t)h->fastFlip * MAXL * 4}, {MAXL, MAXL * 4}}, h->stream);
+    launch_zero_u32(ZeroArgs{{reinterpret_cast<uint32_t*>(h->d_candCount.get()), h->d_fastStat + (size_t)h->fastFlip * MAXL * 4}, {MAXL, MAXL * 4}}, h->stream);
     if ((rc = h->run_fast(h->full, mask ? h->d_mask : nullptr, 1))) return rc;
     int32_t counts[MAXL];
     MYSLAM_HIP_CHECK(hipMemcpyAsync(counts, h->d_candCount, sizeof(counts), hipMemcpyDeviceToHost, h->stream));
@@ -983,16 +962,15 @@ int myslam_orb_debug_candidates(myslam_orb* h, const uint8_t* img, int rows, int
     const LevelGeom& g = h->full.lv[level];
     *n = counts[level];
     if (counts[level] > g.keyCap || counts[level] > cap) return MYSLAM_ERR_CAPACITY;
-    int32_t* d_tmp = nullptr;
+    Buf<int32_t> d_tmp;
     const int m = counts[level];
     if (m > 0) {
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&d_tmp, sizeof(int32_t) * 3 * m));
+        if ((rc = d_tmp.renew((size_t)3 * m))) return rc;
         launch_unpack_cands(h->d_cand + g.keyOff, m, d_tmp, d_tmp + m, d_tmp + 2 * m, h->stream);
         MYSLAM_HIP_CHECK(hipMemcpyAsync(xs, d_tmp, 4 * m, hipMemcpyDeviceToHost, h->stream));
         MYSLAM_HIP_CHECK(hipMemcpyAsync(ys, d_tmp + m, 4 * m, hipMemcpyDeviceToHost, h->stream));
         MYSLAM_HIP_CHECK(hipMemcpyAsync(scores, d_tmp + 2 * m, 4 * m, hipMemcpyDeviceToHost, h->stream));
         MYSLAM_HIP_CHECK(hipStreamSynchronize(h->stream));
-        (void)hipFree(d_tmp);
     }
     return MYSLAM_OK;
 }

@@ -381,19 +381,9 @@ __global__ void __launch_bounds__(256) k_correct_map_points(const double* __rest
     pts[3 * i] = pw[0] + Tn.t[0]; pts[3 * i + 1] = pw[1] + Tn.t[1]; pts[3 * i + 2] = pw[2] + Tn.t[2];
 }
 
-namespace {
+// a call's own blocks hold one element at least: an empty part of a problem still gives its kernels and memsets a valid address
+static size_t some(size_t count) { return std::max<size_t>(count, 1); }
 
-struct DevBuf {                       // frees on scope exit
-    std::vector<void*> ptrs;
-    ~DevBuf() { for (void* p : ptrs) (void)hipFree(p); }
-    template <typename T> hipError_t alloc(T** p, size_t count) {
-        hipError_t e = hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(*p);
-        return e;
-    }
-};
-
-}  // namespace
 }  // namespace myslam_hip
 
 using namespace myslam_hip;
@@ -511,29 +501,27 @@ int myslam_pose_graph_optimize(double* poses, int n, const uint8_t* fixed, const
     }
 
     // ---- device state ----
-    DevBuf mem;
-    double *d_pose, *d_save, *d_meas, *d_minv, *d_J, *d_err, *d_D, *d_B, *d_C, *d_Z, *d_Lw, *d_Hss, *d_bS, *d_A, *d_xS, *d_xT, *d_y, *d_P, *d_diag,
-        *d_sc, *d_part, *d_res;
-    int32_t *d_e0, *d_e1, *d_slot, *d_seg; uint8_t* d_fx; PgJob* d_jobs; int2* d_list; int* d_status;
+    Buf<double> d_pose, d_save, d_meas, d_minv, d_J, d_err, d_D, d_B, d_C, d_Z, d_Lw, d_Hss, d_bS, d_A, d_xS, d_xT, d_y, d_P, d_diag, d_sc, d_part, d_res, d_inv;
+    Buf<int32_t> d_e0, d_e1, d_slot, d_seg; Buf<uint8_t> d_fx; Buf<PgJob> d_jobs; Buf<int2> d_list; Buf<int> d_status;
     const int nchi = (E + 255) / 256;
     const hipStream_t st = host_call_stream();             // this thread's own non-blocking stream for every kernel, copy and memset of the call (never the legacy stream: common.h)
     if (!st) return MYSLAM_ERR_HIP;
-    MYSLAM_HIP_CHECK(mem.alloc(&d_pose, (size_t)7 * n)); MYSLAM_HIP_CHECK(mem.alloc(&d_save, (size_t)7 * n));
-    MYSLAM_HIP_CHECK(mem.alloc(&d_meas, (size_t)7 * E)); MYSLAM_HIP_CHECK(mem.alloc(&d_minv, (size_t)7 * E));
-    MYSLAM_HIP_CHECK(mem.alloc(&d_J, (size_t)72 * E)); MYSLAM_HIP_CHECK(mem.alloc(&d_err, (size_t)6 * E));
-    MYSLAM_HIP_CHECK(mem.alloc(&d_D, (size_t)36 * std::max(nT, 1))); MYSLAM_HIP_CHECK(mem.alloc(&d_B, (size_t)36 * std::max(nT, 1)));
-    MYSLAM_HIP_CHECK(mem.alloc(&d_C, (size_t)rowsPad * ldz)); MYSLAM_HIP_CHECK(mem.alloc(&d_Z, (size_t)rowsPad * ldz));
-    MYSLAM_HIP_CHECK(mem.alloc(&d_Lw, (size_t)72 * nT)); MYSLAM_HIP_CHECK(mem.alloc(&d_Hss, (size_t)ldz * ldz));
-    MYSLAM_HIP_CHECK(mem.alloc(&d_bS, (size_t)ldz)); MYSLAM_HIP_CHECK(mem.alloc(&d_A, (size_t)ldz * ldz));
-    MYSLAM_HIP_CHECK(mem.alloc(&d_xS, (size_t)ldz)); MYSLAM_HIP_CHECK(mem.alloc(&d_xT, (size_t)rowsPad)); MYSLAM_HIP_CHECK(mem.alloc(&d_y, (size_t)rowsPad));
-    MYSLAM_HIP_CHECK(mem.alloc(&d_P, (size_t)PG_KS * ntile * 256)); MYSLAM_HIP_CHECK(mem.alloc(&d_diag, (size_t)6 * nF));
-    MYSLAM_HIP_CHECK(mem.alloc(&d_sc, (size_t)n)); MYSLAM_HIP_CHECK(mem.alloc(&d_part, (size_t)nchi)); MYSLAM_HIP_CHECK(mem.alloc(&d_res, 4));
-    MYSLAM_HIP_CHECK(mem.alloc(&d_e0, (size_t)E)); MYSLAM_HIP_CHECK(mem.alloc(&d_e1, (size_t)E)); MYSLAM_HIP_CHECK(mem.alloc(&d_slot, (size_t)n));
-    MYSLAM_HIP_CHECK(mem.alloc(&d_fx, (size_t)n)); MYSLAM_HIP_CHECK(mem.alloc(&d_jobs, jobs.size())); MYSLAM_HIP_CHECK(mem.alloc(&d_list, list.size()));
-    MYSLAM_HIP_CHECK(mem.alloc(&d_status, 1)); MYSLAM_HIP_CHECK(mem.alloc(&d_seg, seg.size()));
-    double* d_inv = nullptr;
     const bool bigS = nS > PG_MAXS;
-    MYSLAM_HIP_CHECK(mem.alloc(&d_inv, (size_t)ldz + 16));
+    {
+        int rc;
+        if ((rc = d_pose.renew(some((size_t)7 * n))) || (rc = d_save.renew(some((size_t)7 * n))) || (rc = d_meas.renew(some((size_t)7 * E))) ||
+            (rc = d_minv.renew(some((size_t)7 * E))) || (rc = d_J.renew(some((size_t)72 * E))) || (rc = d_err.renew(some((size_t)6 * E))) ||
+            (rc = d_D.renew((size_t)36 * std::max(nT, 1))) || (rc = d_B.renew((size_t)36 * std::max(nT, 1))) ||
+            (rc = d_C.renew(some((size_t)rowsPad * ldz))) || (rc = d_Z.renew(some((size_t)rowsPad * ldz))) || (rc = d_Lw.renew(some((size_t)72 * nT))) ||
+            (rc = d_Hss.renew(some((size_t)ldz * ldz))) || (rc = d_bS.renew(some((size_t)ldz))) || (rc = d_A.renew(some((size_t)ldz * ldz))) ||
+            (rc = d_xS.renew(some((size_t)ldz))) || (rc = d_xT.renew(some((size_t)rowsPad))) || (rc = d_y.renew(some((size_t)rowsPad))) ||
+            (rc = d_P.renew(some((size_t)PG_KS * ntile * 256))) || (rc = d_diag.renew(some((size_t)6 * nF))) || (rc = d_sc.renew(some((size_t)n))) ||
+            (rc = d_part.renew(some((size_t)nchi))) || (rc = d_res.renew(4)) || (rc = d_e0.renew(some((size_t)E))) || (rc = d_e1.renew(some((size_t)E))) ||
+            (rc = d_slot.renew(some((size_t)n))) || (rc = d_fx.renew(some((size_t)n))) || (rc = d_jobs.renew(some(jobs.size()))) ||
+            (rc = d_list.renew(some(list.size()))) || (rc = d_status.renew(1)) || (rc = d_seg.renew(some(seg.size()))) ||
+            (rc = d_inv.renew((size_t)ldz + 16)))
+            return rc;
+    }
     { const int rc_ = copy_sync(d_seg, seg.data(), sizeof(int32_t) * seg.size(), hipMemcpyHostToDevice, st); if (rc_) return rc_; }
     { const int rc_ = copy_sync(d_pose, poses, sizeof(double) * 7 * n, hipMemcpyHostToDevice, st); if (rc_) return rc_; }
     { const int rc_ = copy_sync(d_fx, fx.data(), n, hipMemcpyHostToDevice, st); if (rc_) return rc_; }
@@ -710,10 +698,11 @@ int myslam_correct_map_points(const double* old_poses, const double* new_poses, 
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MYSLAM_ERR_HIP;
     const hipStream_t st = host_call_stream();
     if (!st) return MYSLAM_ERR_HIP;
-    DevBuf mem;
-    double *d_o, *d_n, *d_p; int32_t *d_k, *d_s;
-    MYSLAM_HIP_CHECK(mem.alloc(&d_o, (size_t)7 * n_poses)); MYSLAM_HIP_CHECK(mem.alloc(&d_n, (size_t)7 * n_poses));
-    MYSLAM_HIP_CHECK(mem.alloc(&d_p, (size_t)3 * n_points)); MYSLAM_HIP_CHECK(mem.alloc(&d_k, (size_t)n_points)); MYSLAM_HIP_CHECK(mem.alloc(&d_s, 1));
+    Buf<double> d_o, d_n, d_p; Buf<int32_t> d_k, d_s;
+    int rc;
+    if ((rc = d_o.renew(some((size_t)7 * n_poses))) || (rc = d_n.renew(some((size_t)7 * n_poses))) || (rc = d_p.renew((size_t)3 * n_points)) ||
+        (rc = d_k.renew((size_t)n_points)) || (rc = d_s.renew(1)))
+        return rc;
     if (n_poses) {
         { const int rc_ = copy_sync(d_o, old_poses, sizeof(double) * 7 * n_poses, hipMemcpyHostToDevice, st); if (rc_) return rc_; }
         { const int rc_ = copy_sync(d_n, new_poses, sizeof(double) * 7 * n_poses, hipMemcpyHostToDevice, st); if (rc_) return rc_; }
@@ -721,7 +710,7 @@ int myslam_correct_map_points(const double* old_poses, const double* new_poses, 
     { const int rc_ = copy_sync(d_p, points, sizeof(double) * 3 * n_points, hipMemcpyHostToDevice, st); if (rc_) return rc_; }
     { const int rc_ = copy_sync(d_k, first_kf, sizeof(int32_t) * n_points, hipMemcpyHostToDevice, st); if (rc_) return rc_; }
     MYSLAM_HIP_CHECK(hipMemsetAsync(d_s, 0, sizeof(int32_t), st));
-    int rc = myslam_correct_map_points_device(d_o, d_n, n_poses, d_k, d_p, n_points, d_s, st);
+    rc = myslam_correct_map_points_device(d_o, d_n, n_poses, d_k, d_p, n_points, d_s, st);
     if (rc != MYSLAM_OK) return rc;
     int32_t stt = 0;
     { const int rc_ = copy_sync(&stt, d_s, sizeof(int32_t), hipMemcpyDeviceToHost, st); if (rc_) return rc_; }

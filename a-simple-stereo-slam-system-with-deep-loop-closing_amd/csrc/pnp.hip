@@ -28,14 +28,14 @@
 struct myslam_pnp {
     int max_batch = 0, cap = 0, max_iterations = 0;
     hipStream_t stream = nullptr;
-    int32_t* d_samples = nullptr;     // max_batch x max_iterations x 5
-    double* d_models = nullptr;       // max_batch x max_iterations x 12
-    int32_t* d_hyp = nullptr;         // max_batch x max_iterations: inliers per hypothesis
-    int32_t* d_ints = nullptr;        // max_batch x 6: winner record (2), PnP inliers, pose-only count, pose-only inliers, pose-only status
-    uint8_t* d_mask = nullptr;        // max_batch x cap: PnP's mask when the caller of the chain does not ask for it
-    double* d_pose = nullptr;         // max_batch x 7: the chain's working pose
-    double* d_p3 = nullptr;           // max_batch x cap x 3, f64 copies for the pose-only kernel
-    double* d_z2 = nullptr;           // max_batch x cap x 2
+    myslam_hip::Buf<int32_t> d_samples;     // max_batch x max_iterations x 5
+    myslam_hip::Buf<double> d_models;       // max_batch x max_iterations x 12
+    myslam_hip::Buf<int32_t> d_hyp;         // max_batch x max_iterations: inliers per hypothesis
+    myslam_hip::Buf<int32_t> d_ints;        // max_batch x 6: winner record (2), PnP inliers, pose-only count, pose-only inliers, pose-only status
+    myslam_hip::Buf<uint8_t> d_mask;        // max_batch x cap: PnP's mask when the caller of the chain does not ask for it
+    myslam_hip::Buf<double> d_pose;         // max_batch x 7: the chain's working pose
+    myslam_hip::Buf<double> d_p3;           // max_batch x cap x 3, f64 copies for the pose-only kernel
+    myslam_hip::Buf<double> d_z2;           // max_batch x cap x 2
 };
 
 namespace myslam_hip {
@@ -643,15 +643,6 @@ struct CvRng {                                             // cv::RNG (multiply-
     unsigned next() { state = (uint64_t)(unsigned)state * 4164903690u + (unsigned)(state >> 32); return (unsigned)state; }
     int uniform(int a, int b) { return a == b ? a : (int)(next() % (unsigned)(b - a) + a); }
 };
-struct PnpBuf {
-    std::vector<void*> ptrs;
-    ~PnpBuf() { for (void* p : ptrs) (void)hipFree(p); }
-    template <typename T> hipError_t alloc(T** p, size_t count) {
-        hipError_t e = hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T));
-        if (e == hipSuccess) ptrs.push_back(*p);
-        return e;
-    }
-};
 }  // namespace
 }  // namespace myslam_hip
 
@@ -683,12 +674,12 @@ int myslam_solve_pnp_ransac(const float* pts3d, const float* pts2d, int n, doubl
     }
     const hipStream_t st = host_call_stream();             // everything below runs on this thread's own non-blocking stream (never the legacy stream: common.h)
     if (!st) return MYSLAM_ERR_HIP;
-    PnpBuf mem;
-    float *d_p3, *d_p2; int32_t *d_samples, *d_counts, *d_result; double *d_models, *d_pose; uint8_t* d_mask;
-    MYSLAM_HIP_CHECK(mem.alloc(&d_p3, (size_t)3 * n)); MYSLAM_HIP_CHECK(mem.alloc(&d_p2, (size_t)2 * n));
-    MYSLAM_HIP_CHECK(mem.alloc(&d_samples, samples.size())); MYSLAM_HIP_CHECK(mem.alloc(&d_counts, (size_t)iterations));
-    MYSLAM_HIP_CHECK(mem.alloc(&d_result, 2)); MYSLAM_HIP_CHECK(mem.alloc(&d_models, (size_t)12 * iterations));
-    MYSLAM_HIP_CHECK(mem.alloc(&d_pose, 7)); MYSLAM_HIP_CHECK(mem.alloc(&d_mask, (size_t)n));
+    Buf<float> d_p3, d_p2; Buf<int32_t> d_samples, d_counts, d_result; Buf<double> d_models, d_pose; Buf<uint8_t> d_mask;      // of this call (n, iterations >= 1)
+    int rc;
+    if ((rc = d_p3.renew((size_t)3 * n)) || (rc = d_p2.renew((size_t)2 * n)) || (rc = d_samples.renew(samples.size())) ||
+        (rc = d_counts.renew((size_t)iterations)) || (rc = d_result.renew(2)) || (rc = d_models.renew((size_t)12 * iterations)) ||
+        (rc = d_pose.renew(7)) || (rc = d_mask.renew((size_t)n)))
+        return rc;
     { const int rc_ = copy_sync(d_p3, pts3d, sizeof(float) * 3 * n, hipMemcpyHostToDevice, st); if (rc_) return rc_; }
     { const int rc_ = copy_sync(d_p2, pts2d, sizeof(float) * 2 * n, hipMemcpyHostToDevice, st); if (rc_) return rc_; }
     { const int rc_ = copy_sync(d_samples, samples.data(), sizeof(int32_t) * samples.size(), hipMemcpyHostToDevice, st); if (rc_) return rc_; }
@@ -710,8 +701,6 @@ int myslam_solve_pnp_ransac(const float* pts3d, const float* pts2d, int n, doubl
 int myslam_pnp_destroy(myslam_pnp* h) {
     if (!h) return MYSLAM_ERR_INVALID;
     (void)hipStreamSynchronize(h->stream);
-    void* ptrs[] = {h->d_samples, h->d_models, h->d_hyp, h->d_ints, h->d_mask, h->d_pose, h->d_p3, h->d_z2};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
     delete h;
     return MYSLAM_OK;
 }
@@ -724,14 +713,13 @@ int myslam_pnp_create(myslam_pnp** out, int max_batch, int cap, int max_iteratio
     myslam_pnp* h = new myslam_pnp();
     h->max_batch = max_batch; h->cap = cap; h->max_iterations = max_iterations;
     const size_t B = (size_t)max_batch, hyp = B * (size_t)max_iterations, pts = B * (size_t)cap;
-    hipError_t e = hipSuccess;
-    auto alloc = [&](auto** p, size_t count) { if (e == hipSuccess) e = hipMalloc((void**)p, count * sizeof(**p)); };
-    alloc(&h->d_samples, hyp * PNP_MP); alloc(&h->d_models, hyp * 12); alloc(&h->d_hyp, hyp); alloc(&h->d_ints, B * 6);
-    alloc(&h->d_mask, pts); alloc(&h->d_pose, B * 7); alloc(&h->d_p3, pts * 3); alloc(&h->d_z2, pts * 2);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        (void)myslam_pnp_destroy(h);
-        return e == hipErrorOutOfMemory ? MYSLAM_ERR_CAPACITY : MYSLAM_ERR_HIP;
+    const int oom = MYSLAM_ERR_CAPACITY;
+    int rc;
+    if ((rc = h->d_samples.renew(hyp * PNP_MP, oom)) || (rc = h->d_models.renew(hyp * 12, oom)) || (rc = h->d_hyp.renew(hyp, oom)) ||
+        (rc = h->d_ints.renew(B * 6, oom)) || (rc = h->d_mask.renew(pts, oom)) || (rc = h->d_pose.renew(B * 7, oom)) ||
+        (rc = h->d_p3.renew(pts * 3, oom)) || (rc = h->d_z2.renew(pts * 2, oom))) {
+        delete h;
+        return rc;
     }
     *out = h;
     return MYSLAM_OK;

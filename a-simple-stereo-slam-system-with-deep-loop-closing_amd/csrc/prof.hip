@@ -1,4 +1,5 @@
 // prof.hip — per-kernel HIP-event timing + library-wide entry points.
+#include <algorithm>
 #include <atomic>
 #include <mutex>
 #include <vector>
@@ -44,13 +45,26 @@ void prof_end(int id, hipStream_t s) {
     t_start[id] = nullptr;
 }
 
+// ---- the library's only allocation calls (dev_mem.h) ----
+int raw_alloc(void** p, size_t bytes, bool pinned) {
+    const hipError_t e = pinned ? hipHostMalloc(p, bytes) : hipMalloc(p, bytes);
+    if (e == hipSuccess) return MYSLAM_OK;
+    (void)hipGetLastError();                  // the failure is reported here: no later launch check may find it
+    fprintf(stderr, "[myslam_hip] %s:%d %s(%zu bytes) -> %s\n", __FILE__, __LINE__, pinned ? "hipHostMalloc" : "hipMalloc", bytes, hipGetErrorString(e));
+    *p = nullptr;
+    return e == hipErrorOutOfMemory ? MYSLAM_ERR_CAPACITY : MYSLAM_ERR_HIP;
+}
+
+void raw_free(void* p, bool pinned) {
+    if (pinned) (void)hipHostFree(p); else (void)hipFree(p);
+}
+
 // ---- thread-local staging of the host-pointer entry points (common.h) ----
 void HostArena::release() {
     if (s) (void)hipStreamSynchronize(s);
-    if (d) (void)hipFree(d);
-    if (h) (void)hipHostFree(h);
+    d.release(); h.release();
     if (s) (void)hipStreamDestroy(s);
-    d = nullptr; h = nullptr; s = nullptr; cap = 0;
+    s = nullptr;
 }
 
 HostArena::~HostArena() { release(); }
@@ -60,15 +74,12 @@ int HostArena::ensure(size_t bytes) {
     MYSLAM_HIP_CHECK(hipGetDevice(&cur));
     if (cur != dev) { release(); dev = cur; }          // the calling thread selected another device since its last call
     if (!s) MYSLAM_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    if (bytes <= cap) return MYSLAM_OK;
+    if (bytes <= std::min(d.size(), h.size())) return MYSLAM_OK;
     MYSLAM_HIP_CHECK(hipStreamSynchronize(s));
-    if (d) { (void)hipFree(d); d = nullptr; }
-    if (h) { (void)hipHostFree(h); h = nullptr; }
-    cap = 0;
+    d.release(); h.release();                          // both go before either comes back, as before
     const size_t want = (bytes + (bytes >> 2) + 65535) & ~(size_t)65535;
-    MYSLAM_HIP_CHECK(hipMalloc((void**)&d, want));
-    MYSLAM_HIP_CHECK(hipHostMalloc((void**)&h, want));
-    cap = want;
+    int rc;
+    if ((rc = d.renew(want)) || (rc = h.renew(want))) return rc;
     return MYSLAM_OK;
 }
 
@@ -142,9 +153,10 @@ const char* myslam_hip_version(void) { return "myslam_hip 0.6 (gfx950) build " M
 
 int myslam_prof_shader_clock_mhz(void* hip_stream, float spin_us, float* mhz) {
     if (!mhz || !(spin_us > 0.f) || spin_us > 1e6f) return MYSLAM_ERR_INVALID;
-    static thread_local unsigned long long* d_t = nullptr;            // two counters, allocated once per calling thread
-    if (!d_t) MYSLAM_HIP_CHECK(hipMalloc((void**)&d_t, 16));
-    hipLaunchKernelGGL(k_clock_probe, dim3(1), dim3(64), 0, (hipStream_t)hip_stream, (unsigned long long)(spin_us * 100.f), d_t);
+    static thread_local Buf<unsigned long long> d_t;                  // two counters, allocated once per calling thread
+    int rc;
+    if (!d_t && (rc = d_t.renew(2))) return rc;
+    hipLaunchKernelGGL(k_clock_probe, dim3(1), dim3(64), 0, (hipStream_t)hip_stream, (unsigned long long)(spin_us * 100.f), d_t.get());
     MYSLAM_HIP_CHECK(hipGetLastError());
     unsigned long long h[2] = {0, 0};
     MYSLAM_HIP_CHECK(hipMemcpyAsync(h, d_t, 16, hipMemcpyDeviceToHost, (hipStream_t)hip_stream));

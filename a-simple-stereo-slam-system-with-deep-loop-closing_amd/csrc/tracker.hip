@@ -294,28 +294,27 @@ struct myslam_tracker {
     size_t pyrBytes = 0;
     TrkArgs a{};
     uint8_t* d_pyr = nullptr;
-    std::vector<void*> bufs;
+    std::vector<Buf<uint8_t>> bufs;        // owns every block that `a` and d_pyr name
     std::vector<char> hasImage;
 };
-
-template <class T>
-static int trk_alloc(myslam_tracker* h, T** p, size_t n) {
-    MYSLAM_HIP_CHECK(hipMalloc((void**)p, std::max<size_t>(256, n * sizeof(T))));
-    h->bufs.push_back(*p);
-    return MYSLAM_OK;
-}
 
 static int trk_alloc_all(myslam_tracker* h) {
     TrkArgs& a = h->a;
     const size_t S = h->S, F = S * h->cap, L = S * h->lmCap;
     int rc = 0;
-#define TRK_A(ptr, n) if ((rc = trk_alloc(h, &(ptr), (n)))) return rc
-    TRK_A(a.st, S); TRK_A(a.xy, F * 2); TRK_A(a.lm, F); TRK_A(a.lmPos, L * 3); TRK_A(a.lmOutl, L); TRK_A(a.outlList, F * 2);
-    TRK_A(a.img, 2 * a.imgSel); TRK_A(h->d_pyr, 2 * S * h->pyrBytes);
-    TRK_A(a.sel, S); TRK_A(a.counts, S); TRK_A(a.p0, F * 2); TRK_A(a.p1, F * 2); TRK_A(a.nxt, F * 2); TRK_A(a.lkSt, F);
-    TRK_A(a.curXy, F * 2); TRK_A(a.curLm, F); TRK_A(a.curPo, F); TRK_A(a.curN, S);
-    TRK_A(a.poPose, S * 7); TRK_A(a.poPts, F * 3); TRK_A(a.poObs, F * 2); TRK_A(a.poCounts, S); TRK_A(a.poOutl, F); TRK_A(a.poInl, S); TRK_A(a.poStatus, S);
-#undef TRK_A
+    auto own = [&](auto*& p, size_t n) -> int {               // p = a block of n elements (256 bytes at least) that the handle owns
+        h->bufs.emplace_back();
+        const int rc = h->bufs.back().renew(std::max<size_t>(256, n * sizeof(*p)));
+        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(h->bufs.back().get());
+        return rc;
+    };
+    if ((rc = own(a.st, S)) || (rc = own(a.xy, F * 2)) || (rc = own(a.lm, F)) || (rc = own(a.lmPos, L * 3)) || (rc = own(a.lmOutl, L)) ||
+        (rc = own(a.outlList, F * 2)) || (rc = own(a.img, 2 * a.imgSel)) || (rc = own(h->d_pyr, 2 * S * h->pyrBytes)) ||
+        (rc = own(a.sel, S)) || (rc = own(a.counts, S)) || (rc = own(a.p0, F * 2)) || (rc = own(a.p1, F * 2)) || (rc = own(a.nxt, F * 2)) ||
+        (rc = own(a.lkSt, F)) || (rc = own(a.curXy, F * 2)) || (rc = own(a.curLm, F)) || (rc = own(a.curPo, F)) || (rc = own(a.curN, S)) ||
+        (rc = own(a.poPose, S * 7)) || (rc = own(a.poPts, F * 3)) || (rc = own(a.poObs, F * 2)) || (rc = own(a.poCounts, S)) ||
+        (rc = own(a.poOutl, F)) || (rc = own(a.poInl, S)) || (rc = own(a.poStatus, S)))
+        return rc;
     std::vector<TrkState> init(S);
     memset(init.data(), 0, S * sizeof(TrkState));
     for (TrkState& st : init) { st.frozen = 1; st.status = TRK_INITING; }
@@ -349,7 +348,6 @@ int myslam_tracker_create(myslam_tracker** out, int streams, int rows, int cols,
 int myslam_tracker_destroy(myslam_tracker* h) {
     if (!h) return MYSLAM_ERR_INVALID;
     (void)hipStreamSynchronize(h->stream);
-    for (void* p : h->bufs) (void)hipFree(p);
     if (h->lk) (void)myslam_lk_destroy(h->lk);
     delete h;
     return MYSLAM_OK;

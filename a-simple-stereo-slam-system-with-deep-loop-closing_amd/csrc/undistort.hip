@@ -104,8 +104,8 @@ struct myslam_undistort {
     int rows = 0, cols = 0, th = 0, tiles_x = 0, tiles_y = 0;
     size_t band_bytes = 0;
     std::vector<int16_t> xy; std::vector<uint16_t> frac;           // OpenCV's CV_16SC2 / CV_16UC1 maps (myslam_undistort_get_map)
-    uint32_t* d_map = nullptr; UdTile* d_tiles = nullptr;
-    uint8_t* d_img = nullptr; size_t imgBytes = 0;                   // staging of myslam_undistort_image
+    Buf<uint32_t> d_map; Buf<UdTile> d_tiles;
+    Buf<uint8_t> d_img;                                  // staging of myslam_undistort_image
     std::vector<uint8_t> hostOut;
 };
 
@@ -138,11 +138,8 @@ int myslam_undistort_create(myslam_undistort** out, int rows, int cols, const fl
     if (th < 1) { delete h; return MYSLAM_ERR_UNSUPPORTED; }       // a single tile row's source band exceeds the LDS budget
     h->th = th; h->tiles_x = (cols + UD_TW - 1) / UD_TW; h->tiles_y = (rows + th - 1) / th;
     h->band_bytes = (h->band_bytes + 15) & ~(size_t)15;
-    if (hipMalloc((void**)&h->d_map, map.size() * 4) != hipSuccess || hipMalloc((void**)&h->d_tiles, tiles.size() * sizeof(UdTile)) != hipSuccess ||
+    if (h->d_map.renew(map.size()) != MYSLAM_OK || h->d_tiles.renew(tiles.size()) != MYSLAM_OK ||
         upload_table(h->d_map, map.data(), map.size() * 4) != MYSLAM_OK || upload_table(h->d_tiles, tiles.data(), tiles.size() * sizeof(UdTile)) != MYSLAM_OK) {
-        (void)hipGetLastError();
-        if (h->d_map) (void)hipFree(h->d_map);
-        if (h->d_tiles) (void)hipFree(h->d_tiles);
         delete h;
         return MYSLAM_ERR_HIP;
     }
@@ -153,8 +150,6 @@ int myslam_undistort_create(myslam_undistort** out, int rows, int cols, const fl
 int myslam_undistort_destroy(myslam_undistort* h) {
     if (!h) return MYSLAM_ERR_INVALID;
     (void)hipStreamSynchronize(h->stream);
-    void* ptrs[] = {h->d_map, h->d_tiles, h->d_img};
-    for (void* p : ptrs) if (p) (void)hipFree(p);
     delete h;
     return MYSLAM_OK;
 }
@@ -176,11 +171,10 @@ int myslam_undistort_image(myslam_undistort* h, const uint8_t* src, int src_step
     if (!h || !src || !dst || src_step < h->cols || dst_step < h->cols) return MYSLAM_ERR_INVALID;
     const int rows = h->rows, cols = h->cols;
     const size_t inBytes = (size_t)(rows - 1) * src_step + cols, inPad = (inBytes + 255) & ~(size_t)255, outBytes = (size_t)rows * cols;
-    if (inPad + outBytes > h->imgBytes) {
+    if (inPad + outBytes > h->d_img.size()) {
         MYSLAM_HIP_CHECK(hipStreamSynchronize(h->stream));
-        if (h->d_img) (void)hipFree(h->d_img);
-        h->d_img = nullptr; h->imgBytes = 0;
-        MYSLAM_HIP_CHECK(hipMalloc((void**)&h->d_img, inPad + outBytes)); h->imgBytes = inPad + outBytes;
+        const int rc = h->d_img.renew(inPad + outBytes);
+        if (rc) return rc;
     }
     hipStream_t s = h->stream;
     MYSLAM_HIP_CHECK(hipMemcpyAsync(h->d_img, src, inBytes, hipMemcpyHostToDevice, s));       // one contiguous copy with the caller's pitch

@@ -1,0 +1,169 @@
+// csrc/dev_mem.h on the host: Buf and regrow over a malloc-backed raw_alloc / raw_free that counts live blocks and can fail the k-th call.
+// Built with AddressSanitizer + UBSan by tests/test_dev_mem.py; exit status 0 and "DEV MEM OK" = every check held and nothing leaked.
+#include <stdio.h>
+#include <stdlib.h>
+
+#include <utility>
+#include <vector>
+
+#include "dev_mem.h"
+
+using namespace myslam_hip;
+
+static int g_live = 0, g_peak = 0, g_calls = 0;
+static int g_fail_at = 0;                   // > 0: the call with this number (counted from 1 since arm()) fails ...
+static int g_fail_code = MYSLAM_ERR_CAPACITY;      // ... with this code
+static int g_pinned_live = 0;
+
+static void arm(int k, int code = MYSLAM_ERR_CAPACITY) { g_calls = 0; g_fail_at = k; g_fail_code = code; }
+
+namespace myslam_hip {
+int raw_alloc(void** p, size_t bytes, bool pinned) {
+    *p = nullptr;
+    if (++g_calls == g_fail_at) return g_fail_code;
+    *p = malloc(bytes);
+    if (!*p) return MYSLAM_ERR_CAPACITY;
+    g_live++; g_pinned_live += pinned;
+    if (g_live > g_peak) g_peak = g_live;
+    return MYSLAM_OK;
+}
+void raw_free(void* p, bool pinned) {
+    free(p);
+    g_live--; g_pinned_live -= pinned;
+}
+}  // namespace myslam_hip
+
+#define CHECK(cond)                                                             \
+    do {                                                                        \
+        if (!(cond)) { printf("FAILED %s:%d %s\n", __FILE__, __LINE__, #cond); exit(1); } \
+    } while (0)
+
+template <class B> static bool empty(const B& b) { return b.size() == 0 && b.get() == nullptr; }
+template <class B> static bool sound(const B& b) { return b.get() != nullptr || b.size() == 0; }      // never a size over a null pointer
+
+static void single_buffer() {
+    Buf<int> b;
+    CHECK(empty(b) && g_live == 0);
+    arm(0);
+    CHECK(b.renew(10) == MYSLAM_OK && b.size() == 10 && b.get() && g_live == 1);
+    for (int i = 0; i < 10; i++) b[i] = i;                     // ten whole elements (ASan checks the bytes)
+    int* viaConv = b;
+    CHECK(viaConv == b.get() && viaConv[9] == 9);
+    // renew frees the old block before it asks for the new one: never two live blocks for one buffer
+    g_peak = g_live;
+    CHECK(b.renew(1000) == MYSLAM_OK && b.size() == 1000 && g_live == 1 && g_peak == 1);
+    CHECK(b.renew(3) == MYSLAM_OK && b.size() == 3 && g_live == 1 && g_peak == 1);      // exactly n, also when smaller
+    // renew(0) stays empty and asks for nothing
+    arm(0);
+    CHECK(b.renew(0) == MYSLAM_OK && empty(b) && g_live == 0 && g_calls == 0);
+    // release
+    CHECK(b.renew(7) == MYSLAM_OK && g_live == 1);
+    b.release();
+    CHECK(empty(b) && g_live == 0);
+    b.release();                                               // twice is harmless
+    CHECK(empty(b) && g_live == 0);
+    // a failed renew: the old block is gone, and so is the size
+    CHECK(b.renew(7) == MYSLAM_OK);
+    arm(1);
+    CHECK(b.renew(9) == MYSLAM_ERR_HIP && empty(b) && g_live == 0);      // out of memory reports the default oom_code
+    arm(0);
+    CHECK(b.renew(9) == MYSLAM_OK && b.size() == 9);                     // and the buffer is usable again
+    // the oom_code mapping; an error that is not out of memory passes through unchanged
+    arm(1);
+    CHECK(b.renew(5, MYSLAM_ERR_CAPACITY) == MYSLAM_ERR_CAPACITY && empty(b));
+    arm(1, MYSLAM_ERR_HIP);
+    CHECK(b.renew(5, MYSLAM_ERR_CAPACITY) == MYSLAM_ERR_HIP && empty(b));
+    arm(1, MYSLAM_ERR_INVALID);
+    CHECK(b.renew(5) == MYSLAM_ERR_INVALID && empty(b));
+    arm(1, MYSLAM_ERR_INVALID);
+    CHECK(b.renew(5, MYSLAM_ERR_CAPACITY) == MYSLAM_ERR_INVALID && empty(b));
+    arm(0);
+    CHECK(g_live == 0);
+    // pinned buffers go through the same two functions with the flag set
+    {
+        PinBuf<double> h;
+        CHECK(h.renew(4) == MYSLAM_OK && h.size() == 4 && g_pinned_live == 1 && g_live == 1);
+        h[3] = 1.0;
+    }
+    CHECK(g_live == 0 && g_pinned_live == 0);                  // the destructor frees
+}
+
+static void moves() {
+    arm(0);
+    Buf<char> a;
+    CHECK(a.renew(16) == MYSLAM_OK);
+    char* const pa = a.get();
+    Buf<char> b(std::move(a));
+    CHECK(empty(a) && b.get() == pa && b.size() == 16 && g_live == 1);
+    Buf<char> c;
+    CHECK(c.renew(8) == MYSLAM_OK && g_live == 2);
+    c = std::move(b);                                          // frees what c held
+    CHECK(empty(b) && c.get() == pa && c.size() == 16 && g_live == 1);
+    Buf<char>& self = c;
+    c = std::move(self);
+    CHECK(c.get() == pa && c.size() == 16 && g_live == 1);
+    // into a vector, through its reallocations
+    std::vector<Buf<char>> v;
+    v.push_back(std::move(c));
+    CHECK(empty(c));
+    for (int i = 0; i < 20; i++) {
+        v.emplace_back();
+        CHECK(v.back().renew(i + 1) == MYSLAM_OK);
+    }
+    CHECK(g_live == 21 && v[0].get() == pa && v[0].size() == 16);
+    for (int i = 0; i < 20; i++) CHECK(v[i + 1].size() == (size_t)i + 1 && v[i + 1].get());
+    v[5] = std::move(v[20]);
+    CHECK(g_live == 20 && empty(v[20]) && v[5].size() == 20);
+    v.erase(v.begin());
+    CHECK(g_live == 19);
+}                                                              // the vector's elements free the rest
+
+struct Group {
+    int cap = 0;
+    Buf<int> a; Buf<float> b; PinBuf<char> c;
+    int grow(int want) {
+        return regrow(cap, want, [&]() -> int {
+            int rc;
+            if ((rc = a.renew(want)) || (rc = b.renew(2 * (size_t)want)) || (rc = c.renew(want + 3, MYSLAM_ERR_CAPACITY))) return rc;
+            return MYSLAM_OK;
+        });
+    }
+    bool whole(int want) const { return cap == want && a.size() == (size_t)want && b.size() == 2 * (size_t)want && c.size() == (size_t)want + 3 && a.get() && b.get() && c.get(); }
+};
+
+static void groups() {
+    for (int k = 1; k <= 3; k++) {
+        Group g;
+        arm(0);
+        CHECK(g.grow(4) == MYSLAM_OK && g.whole(4) && g_live == 3);
+        arm(k);                                                // the k-th of the three allocations fails
+        const int rc = g.grow(8);
+        CHECK(rc == (k == 3 ? MYSLAM_ERR_CAPACITY : MYSLAM_ERR_HIP));
+        CHECK(g.cap == 0);                                     // the guard refuses every size, the old one included
+        CHECK(sound(g.a) && sound(g.b) && sound(g.c));
+        CHECK(g_live == 2);                                    // the one that failed is gone; those before it are new, those behind it still the old ones
+        CHECK(k < 2 || g.a.size() == 8);
+        CHECK(k < 3 || g.b.size() == 16);
+        CHECK((k == 1 ? empty(g.a) : k == 2 ? empty(g.b) : empty(g.c)));
+        arm(0);
+        CHECK(g.grow(2) == MYSLAM_OK && g.whole(2) && g_live == 3);      // a following growth — a smaller one too — leaves all three whole
+        CHECK(g.grow(8) == MYSLAM_OK && g.whole(8) && g_live == 3);
+    }
+    CHECK(g_live == 0);
+    // a step of the group that is no allocation fails (a table upload): the size stays zero as well
+    int cap = 5;
+    Buf<int> t;
+    CHECK(regrow(cap, 9, [&]() -> int { const int rc = t.renew(9); return rc ? rc : MYSLAM_ERR_HIP; }) == MYSLAM_ERR_HIP && cap == 0 && t.size() == 9);
+    CHECK(regrow(cap, 9, [&]() -> int { return t.renew(9); }) == MYSLAM_OK && cap == 9);
+}
+
+int main() {
+    single_buffer();
+    CHECK(g_live == 0);
+    moves();
+    CHECK(g_live == 0);
+    groups();
+    CHECK(g_live == 0 && g_pinned_live == 0);
+    printf("DEV MEM OK\n");
+    return 0;
+}
