@@ -1045,6 +1045,62 @@ class LoopCorrector:
                                                C.c_void_p(d_chi2), C.c_void_p(d_iters), C.c_void_p(d_status)), "myslam_loop_correct_batch")
 
 
+LOOP_DETECT_CANDIDATE, LOOP_DETECT_NO_LOOP = 0, 1      # MYSLAM_LOOP_DETECT_*
+
+
+class LoopKeyFrameStore:
+    """What ProcessNewKF leaves in a KeyFrame, resident on the device (myslam_loop_store_*): `kf_capacity` slots of `cap` pyramid key-points and
+    descriptors and `feat_cap` feature -> landmark entries, and LoopClosing::DetectLoop's decision (src/loopclosing.cpp:147, :151) over
+    LoopDatabase.query_batch's outputs, written where loop_match_batch reads its loop side.  Device pointers as ints; every call enqueues on the
+    handle's stream and returns."""
+
+    def __init__(self, kf_capacity, cap, feat_cap, stream=None):
+        self.cap, self.feat_cap = int(cap), int(feat_cap)
+        self._h = C.c_void_p()
+        _check(lib().myslam_loop_store_create(C.byref(self._h), int(kf_capacity), self.cap, self.feat_cap), "myslam_loop_store_create")
+        if stream is not None:
+            self.set_stream(stream)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and self._h.value and _lib is not None:
+            lib().myslam_loop_store_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def set_stream(self, stream):
+        _check(lib().myslam_loop_store_set_stream(self._h, C.c_void_p(stream)), "myslam_loop_store_set_stream")
+
+    def __len__(self):
+        return lib().myslam_loop_store_size(self._h)
+
+    def capacity(self):
+        return lib().myslam_loop_store_capacity(self._h)
+
+    def put_batch(self, ids, d_pyr_kps, d_desc, d_counts, d_kf_status, d_feat_landmark, d_n_feat):
+        """len(ids) key-frames as ORBextractor.process_keyframes_batch left them (d_kf_status 0 / None: every one is good) + their feature -> landmark
+        tables (batch x feat_cap i32, -1 = no map point) and counts; ids strictly ascending and above every id held (MyslamError(INVALID)),
+        MyslamError(CAPACITY) when they do not fit, MyslamError(UNSUPPORTED) on a capturing stream: nothing stored or enqueued then"""
+        ids = np.ascontiguousarray(ids, np.uint64)
+        _check(lib().myslam_loop_store_put_batch(self._h, _p(ids), len(ids), C.c_void_p(d_pyr_kps), C.c_void_p(d_desc), C.c_void_p(d_counts),
+                                                 C.c_void_p(d_kf_status or None), C.c_void_p(d_feat_landmark), C.c_void_p(d_n_feat)),
+               "myslam_loop_store_put_batch")
+
+    def set_landmarks_batch(self, ids, d_feat_landmark, d_n_feat):
+        """replaces the feature -> landmark table and count of key-frames already held (len(ids) x feat_cap i32); an unknown or repeated id: INVALID"""
+        ids = np.ascontiguousarray(ids, np.uint64)
+        _check(lib().myslam_loop_store_set_landmarks_batch(self._h, _p(ids), len(ids), C.c_void_p(d_feat_landmark), C.c_void_p(d_n_feat)),
+               "myslam_loop_store_set_landmarks_batch")
+
+    def detect_batch(self, d_best_id, d_max_score, d_cnt, nq, d_loop_desc, d_n_loop, d_loop_pyr, d_loop_feat_landmark, d_loop_slot, d_status,
+                     thr_high=0.94, max_suspected=3):
+        """`max_score < thr_high or cnt > max_suspected` -> LOOP_DETECT_NO_LOOP, an id not held -> ERR_INVALID (both with n_loop 0, slot -1, nothing
+        else written), else LOOP_DETECT_CANDIDATE with the key-frame's rows in loop_match_batch's d_loop_desc / d_n_loop / d_loop_pyr /
+        d_loop_feat_landmark layout.  One launch, recordable (StepGraph)."""
+        _check(lib().myslam_loop_detect_batch(self._h, C.c_void_p(d_best_id), C.c_void_p(d_max_score), C.c_void_p(d_cnt), int(nq), C.c_float(thr_high),
+                                              int(max_suspected), C.c_void_p(d_loop_desc), C.c_void_p(d_n_loop), C.c_void_p(d_loop_pyr),
+                                              C.c_void_p(d_loop_feat_landmark), C.c_void_p(d_loop_slot), C.c_void_p(d_status)),
+               "myslam_loop_detect_batch")
+
+
 def loop_correct_structure(n_kf, active, loop, edge_v0, edge_v1):
     """The separator rule of LoopCorrector.correct_batch for one map, on the host -> (separators, chain length, supported)"""
     active = np.ascontiguousarray(active, np.int32); e0 = np.ascontiguousarray(edge_v0, np.int32); e1 = np.ascontiguousarray(edge_v1, np.int32)

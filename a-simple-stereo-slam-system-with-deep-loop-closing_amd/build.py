@@ -35,6 +35,7 @@ UNITS = {
     "pgo.hip": [],
     "pnp.hip": EXACT,
     "loop_correct.hip": [],
+    "loop_store.hip": [],                  # copies and two compares: nothing a contraction could change
     "prof.hip": [],
     "io.hip": [],
     "graph.hip": [],

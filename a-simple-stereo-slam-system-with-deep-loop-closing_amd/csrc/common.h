@@ -73,6 +73,13 @@ inline int copy_sync(void* dst, const void* src, size_t bytes, hipMemcpyKind kin
     return MYSLAM_OK;
 }
 
+// is `s` being recorded into a graph right now?  (Calls that synchronise, or that keep host bookkeeping a replay would not repeat, refuse such a stream.)
+inline bool stream_is_capturing(hipStream_t s) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return st == hipStreamCaptureStatusActive;
+}
+
 // ---- staging of the host-pointer ("drop-in", B = 1) entry points --------------------------------------------------------------
 // One grow-only device block, one pinned host block and one stream per calling THREAD, carved into 256-byte aligned pieces per
 // call: no allocation per call, one host->device and one device->host copy per call, and nothing to free on an error

@@ -439,12 +439,6 @@ static int ctx_quiesce(myslam_lcddb_query_ctx* c) {
     return MYSLAM_OK;
 }
 
-static bool stream_is_capturing(hipStream_t s) {
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &st) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return st == hipStreamCaptureStatusActive;
-}
-
 // partial results of one scan that reaches `rows` rows: one per block of the kernel a call with nq queries launches (launch_scan)
 static int scan_blocks(int nq, int rows) {
     const int rowsPerBlock = DB_WAVES * DB_ROWS_PER_WAVE;

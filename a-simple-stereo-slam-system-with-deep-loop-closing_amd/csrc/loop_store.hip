@@ -1,0 +1,275 @@
+// loop_store.hip — the step between LoopClosing::DetectLoop's scan and MatchFeatures (src/loopclosing.cpp:147, :151) on gfx950: a device-resident store of
+// what ProcessNewKF leaves in a KeyFrame (keyframe.h: mvPyramidKeyPoints, mORBDescriptors, and per feature of mvpFeaturesLeft whether mpMapPoint.lock()
+// still names a landmark), and one launch that applies `maxScore < thr_high || cnt > 3` to myslam_lcddb_query_batch's outputs and writes the chosen
+// key-frames' arrays where myslam_loop_match_batch reads them.
+//
+// The store is kf_capacity slots of fixed size; slot s holds the s-th key-frame put, ids ascend with the slot.  Nothing ever moves, so a recorded
+// launch stays valid; ids, row counts, feature counts and the number of key-frames held are read ON THE DEVICE, so a replay sees what was put after
+// the recording.  Slot strides are rounded up to 4 key-points / 4 landmark entries: every slot starts on a 16-byte boundary.
+//
+// Both kernels are copies and nothing else: a 2-D grid (chunk x item), every workgroup repeats its item's decision (two compares and a binary search
+// over the ids, all wave-uniform) and then moves its share of the item's three arrays, 16 bytes per lane where source and destination of the item are
+// 16-byte aligned (a key-point is 28 bytes: item b of a caller's table starts aligned only when b * cap is a multiple of 4), a dword per lane
+// otherwise, bytes for a pointer that is not even 4-byte aligned.  Chunk 0 writes the item's status, slot and counts.
+#include "common.h"
+
+#include <algorithm>
+
+namespace myslam_hip {
+
+constexpr int LS_THREADS = 256;
+constexpr int LS_MAX_CAP = 16384, LS_MAX_FEAT = 65536;        // myslam_loop_match_batch's limits
+constexpr int LS_MAX_GRID_Y = 65535;
+constexpr size_t LS_MIN_CHUNK_BYTES = (size_t)LS_THREADS * 16;  // a chunk is at least one 16-byte access of every lane
+constexpr int LS_TARGET_BLOCKS = 2048;                          // 256 CUs x 8 workgroups: what a bandwidth kernel needs in flight
+constexpr int LS_KP_BYTES = 28;
+static_assert(sizeof(myslam_keypoint) == LS_KP_BYTES, "cv::KeyPoint layout");
+
+// this workgroup's share of `count` elements of T: element i belongs to chunk (i / LS_THREADS) % nchunks.  A lane with more than three elements
+// (few chunks per item: calls of many items) keeps four loads in flight; with the chunking of ls_chunks a lane of a small call has one element
+// per array, and what is in flight then is the number of workgroups.
+template <class T>
+__device__ __forceinline__ void ls_copy_as(T* __restrict__ dst, const T* __restrict__ src, size_t count, int chunk, int nchunks) {
+    const size_t step = (size_t)nchunks * LS_THREADS;
+    size_t i = (size_t)chunk * LS_THREADS + threadIdx.x;
+    for (; i + 3 * step < count; i += 4 * step) {
+        const T a = src[i], b = src[i + step], c = src[i + 2 * step], d = src[i + 3 * step];
+        dst[i] = a; dst[i + step] = b; dst[i + 2 * step] = c; dst[i + 3 * step] = d;
+    }
+    for (; i < count; i += step) dst[i] = src[i];
+}
+
+// bytes [0, bytes) of one item's array, split over the nchunks workgroups of the item
+__device__ __forceinline__ void ls_copy(void* dst, const void* src, size_t bytes, int chunk, int nchunks) {
+    const uintptr_t both = (uintptr_t)dst | (uintptr_t)src;
+    uint8_t* const d8 = static_cast<uint8_t*>(dst);
+    const uint8_t* const s8 = static_cast<const uint8_t*>(src);
+    size_t done;
+    if ((both & 15) == 0) {
+        ls_copy_as(static_cast<uint4*>(dst), static_cast<const uint4*>(src), bytes >> 4, chunk, nchunks);
+        done = bytes & ~(size_t)15;
+    } else if ((both & 3) == 0) {
+        ls_copy_as(static_cast<uint32_t*>(dst), static_cast<const uint32_t*>(src), bytes >> 2, chunk, nchunks);
+        done = bytes & ~(size_t)3;
+    } else {
+        ls_copy_as(d8, s8, bytes, chunk, nchunks);
+        done = bytes;
+    }
+    if (chunk == 0 && done + threadIdx.x < bytes) d8[done + threadIdx.x] = s8[done + threadIdx.x];      // at most 15 bytes
+}
+
+__device__ __forceinline__ int ls_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+struct LsStore {
+    myslam_keypoint* kps; uint8_t* desc; int32_t* lm;         // slot s at + s * cap_st (x 32) / + s * feat_st
+    int32_t* rows; int32_t* nfeat; uint64_t* ids; int32_t* size;
+    int cap, feat_cap; size_t cap_st, feat_st;
+};
+
+// put: item b of process_keyframes_batch's outputs -> slot first_slot + b.  The ids were copied ahead on the same stream.
+__global__ void __launch_bounds__(LS_THREADS) k_loop_store_put(const LsStore st, int first_slot, int new_size, const myslam_keypoint* __restrict__ kps,
+                                                               const uint8_t* __restrict__ desc, const int32_t* __restrict__ counts,
+                                                               const int32_t* __restrict__ kf_status, const int32_t* __restrict__ lm,
+                                                               const int32_t* __restrict__ n_feat) {
+    const int b = blockIdx.y, chunk = blockIdx.x, nchunks = gridDim.x;
+    const size_t slot = (size_t)first_slot + b;
+    const int n = (kf_status && kf_status[b] != 0) ? 0 : ls_clamp(counts[b], st.cap);      // a key-frame the extractor refused is kept, with no rows
+    const int nf = ls_clamp(n_feat[b], st.feat_cap);
+    if (chunk == 0 && threadIdx.x == 0) {
+        st.rows[slot] = n;
+        st.nfeat[slot] = nf;
+        if (b == 0 && new_size >= 0) *st.size = new_size;
+    }
+    ls_copy(st.kps + slot * st.cap_st, kps + (size_t)b * st.cap, (size_t)n * LS_KP_BYTES, chunk, nchunks);
+    ls_copy(st.desc + slot * st.cap_st * 32, desc + (size_t)b * st.cap * 32, (size_t)n * 32, chunk, nchunks);
+    ls_copy(st.lm + slot * st.feat_st, lm + (size_t)b * st.feat_cap, (size_t)nf * 4, chunk, nchunks);
+}
+
+// set_landmarks: item b's table and count -> slot slots[b]
+__global__ void __launch_bounds__(LS_THREADS) k_loop_store_set_landmarks(const LsStore st, const int32_t* __restrict__ slots, const int32_t* __restrict__ lm,
+                                                                         const int32_t* __restrict__ n_feat) {
+    const int b = blockIdx.y, chunk = blockIdx.x, nchunks = gridDim.x;
+    const size_t slot = (size_t)slots[b];
+    const int nf = ls_clamp(n_feat[b], st.feat_cap);
+    if (chunk == 0 && threadIdx.x == 0) st.nfeat[slot] = nf;
+    ls_copy(st.lm + slot * st.feat_st, lm + (size_t)b * st.feat_cap, (size_t)nf * 4, chunk, nchunks);
+}
+
+// detect: the decision of loopclosing.cpp:147 and `_mpLoopKF = _mvDatabase.at(bestId)` (:151) per item, then the gather
+__global__ void __launch_bounds__(LS_THREADS) k_loop_detect(const LsStore st, const uint64_t* __restrict__ best_id, const float* __restrict__ max_score,
+                                                            const int32_t* __restrict__ cnt, float thr_high, int max_suspected,
+                                                            uint8_t* __restrict__ loop_desc, int32_t* __restrict__ n_loop, myslam_keypoint* __restrict__ loop_pyr,
+                                                            int32_t* __restrict__ loop_lm, int32_t* __restrict__ loop_slot, int32_t* __restrict__ status) {
+    const int b = blockIdx.y, chunk = blockIdx.x, nchunks = gridDim.x;
+    const bool lead = chunk == 0 && threadIdx.x == 0;
+    // the reference's expression as written: a NaN score is not "less" and goes on to the lookup
+    if (max_score[b] < thr_high || cnt[b] > max_suspected) {
+        if (lead) { status[b] = MYSLAM_LOOP_DETECT_NO_LOOP; n_loop[b] = 0; loop_slot[b] = -1; }
+        return;
+    }
+    const uint64_t id = best_id[b];
+    const int held = *st.size;
+    int lo = 0, hi = held;                                      // -> the first slot whose id is not below `id`
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (st.ids[mid] < id) lo = mid + 1; else hi = mid;
+    }
+    if (lo >= held || st.ids[lo] != id) {
+        if (lead) { status[b] = MYSLAM_ERR_INVALID; n_loop[b] = 0; loop_slot[b] = -1; }
+        return;
+    }
+    const size_t slot = (size_t)lo;
+    const int n = st.rows[slot], nf = st.nfeat[slot];           // clamped when they were stored
+    if (lead) { status[b] = MYSLAM_LOOP_DETECT_CANDIDATE; n_loop[b] = n; loop_slot[b] = lo; }
+    ls_copy(loop_pyr + (size_t)b * st.cap, st.kps + slot * st.cap_st, (size_t)n * LS_KP_BYTES, chunk, nchunks);
+    ls_copy(loop_desc + (size_t)b * st.cap * 32, st.desc + slot * st.cap_st * 32, (size_t)n * 32, chunk, nchunks);
+    ls_copy(loop_lm + (size_t)b * st.feat_cap, st.lm + slot * st.feat_st, (size_t)nf * 4, chunk, nchunks);
+}
+
+// workgroups per item: enough of them over the whole call to fill the chip, none with less than one full-width access per lane
+static int ls_chunks(int items, size_t item_bytes) {
+    const size_t most = std::max<size_t>(1, (item_bytes + LS_MIN_CHUNK_BYTES - 1) / LS_MIN_CHUNK_BYTES);
+    const size_t want = (size_t)(LS_TARGET_BLOCKS + items - 1) / items;
+    return (int)std::max<size_t>(1, std::min(most, want));
+}
+
+}  // namespace myslam_hip
+
+using namespace myslam_hip;
+
+struct myslam_loop_store {
+    int kf_capacity = 0, cap = 0, feat_cap = 0, n = 0;
+    hipStream_t stream = nullptr;
+    Buf<myslam_keypoint> d_kps; Buf<uint8_t> d_desc; Buf<int32_t> d_lm, d_rows, d_nfeat, d_size, d_slots;
+    Buf<uint64_t> d_ids;
+    // the ids as the device copies them: slot s is written once, when key-frame s is put, and never again — no copy ever reads a slot that changes
+    PinBuf<uint64_t> h_ids;
+    // slot lists of set_landmarks_batch on their way to the device: a ring, each part with the event behind its copy
+    static constexpr int RING = 4;
+    PinBuf<int32_t> h_slots; hipEvent_t slotEv[RING] = {}; bool slotPending[RING] = {}; int ring = 0;
+    mutable std::mutex mu;                    // host state: n, stream, the ring
+    LsStore view{};
+
+    ~myslam_loop_store() { for (hipEvent_t e : slotEv) if (e) (void)hipEventDestroy(e); }
+    size_t item_bytes() const { return (size_t)cap * (LS_KP_BYTES + 32) + (size_t)feat_cap * 4; }
+    int find(uint64_t id) const {
+        const uint64_t* const b = h_ids.get(), * const e = b + n;
+        const uint64_t* it = std::lower_bound(b, e, id);
+        return (it != e && *it == id) ? (int)(it - b) : -1;
+    }
+};
+
+extern "C" {
+
+int myslam_loop_store_create(myslam_loop_store** out, int kf_capacity, int cap, int feat_cap) {
+    if (!out || kf_capacity <= 0 || cap <= 0 || feat_cap <= 0) return MYSLAM_ERR_INVALID;
+    if (cap > LS_MAX_CAP || feat_cap > LS_MAX_FEAT) return MYSLAM_ERR_CAPACITY;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { (void)hipGetLastError(); return MYSLAM_ERR_HIP; }
+    std::unique_ptr<myslam_loop_store> h(new myslam_loop_store());
+    h->kf_capacity = kf_capacity; h->cap = cap; h->feat_cap = feat_cap;
+    const size_t K = (size_t)kf_capacity, cap_st = ((size_t)cap + 3) & ~(size_t)3, feat_st = ((size_t)feat_cap + 3) & ~(size_t)3;
+    const int oom = MYSLAM_ERR_CAPACITY;
+    int rc;
+    if ((rc = h->d_kps.renew(K * cap_st, oom)) || (rc = h->d_desc.renew(K * cap_st * 32, oom)) || (rc = h->d_lm.renew(K * feat_st, oom)) ||
+        (rc = h->d_rows.renew(K, oom)) || (rc = h->d_nfeat.renew(K, oom)) || (rc = h->d_ids.renew(K, oom)) || (rc = h->d_slots.renew(K, oom)) ||
+        (rc = h->d_size.renew(1, oom)) || (rc = h->h_ids.renew(K, oom)) || (rc = h->h_slots.renew(K * myslam_loop_store::RING, oom)))
+        return rc;
+    for (auto& e : h->slotEv) MYSLAM_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    const int32_t zero = 0;
+    if ((rc = upload_table(h->d_size, &zero, sizeof(zero)))) return rc;      // complete on return: the first launch may come on any stream
+    h->view = LsStore{h->d_kps, h->d_desc, h->d_lm, h->d_rows, h->d_nfeat, h->d_ids, h->d_size, cap, feat_cap, cap_st, feat_st};
+    *out = h.release();
+    return MYSLAM_OK;
+}
+
+int myslam_loop_store_destroy(myslam_loop_store* h) {
+    if (!h) return MYSLAM_ERR_INVALID;
+    (void)hipStreamSynchronize(h->stream);
+    delete h;
+    return MYSLAM_OK;
+}
+
+int myslam_loop_store_set_stream(myslam_loop_store* h, void* hip_stream) {
+    if (!h) return MYSLAM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    h->stream = (hipStream_t)hip_stream;
+    return MYSLAM_OK;
+}
+
+int myslam_loop_store_size(const myslam_loop_store* h) {
+    if (!h) return MYSLAM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    return h->n;
+}
+
+int myslam_loop_store_capacity(const myslam_loop_store* h) { return h ? h->kf_capacity : MYSLAM_ERR_INVALID; }
+
+int myslam_loop_store_put_batch(myslam_loop_store* h, const uint64_t* ids, int batch, const myslam_keypoint* d_pyr_kps, const uint8_t* d_desc,
+                                const int32_t* d_counts, const int32_t* d_kf_status, const int32_t* d_feat_landmark, const int32_t* d_n_feat) {
+    if (!h || !ids || batch <= 0 || !d_pyr_kps || !d_desc || !d_counts || !d_feat_landmark || !d_n_feat) return MYSLAM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    for (int i = 0; i < batch; i++)            // std::map order: strictly ascending, behind every id held
+        if (i == 0 ? h->n > 0 && ids[0] <= h->h_ids[h->n - 1] : ids[i] <= ids[i - 1]) return MYSLAM_ERR_INVALID;
+    if ((long long)h->n + batch > h->kf_capacity) return MYSLAM_ERR_CAPACITY;
+    if (stream_is_capturing(h->stream)) return MYSLAM_ERR_UNSUPPORTED;              // a put is host bookkeeping too: it cannot be replayed
+    memcpy(h->h_ids + h->n, ids, sizeof(uint64_t) * (size_t)batch);
+    MYSLAM_HIP_CHECK(hipMemcpyAsync(h->d_ids + h->n, h->h_ids + h->n, sizeof(uint64_t) * (size_t)batch, hipMemcpyHostToDevice, h->stream));
+    const int chunks = ls_chunks(batch, h->item_bytes());
+    for (int b0 = 0; b0 < batch; b0 += LS_MAX_GRID_Y) {
+        const int nb = std::min(batch - b0, LS_MAX_GRID_Y);
+        // the number of key-frames held changes with the LAST launch: a detect that follows on the stream sees the rows before it sees the count
+        const int new_size = b0 + nb == batch ? h->n + batch : -1;
+        hipLaunchKernelGGL(k_loop_store_put, dim3(chunks, nb), dim3(LS_THREADS), 0, h->stream, h->view, h->n + b0, new_size,
+                           d_pyr_kps + (size_t)b0 * h->cap, d_desc + (size_t)b0 * h->cap * 32, d_counts + b0, d_kf_status ? d_kf_status + b0 : nullptr,
+                           d_feat_landmark + (size_t)b0 * h->feat_cap, d_n_feat + b0);
+        MYSLAM_HIP_CHECK(hipGetLastError());
+    }
+    h->n += batch;
+    return MYSLAM_OK;
+}
+
+int myslam_loop_store_set_landmarks_batch(myslam_loop_store* h, const uint64_t* ids, int n, const int32_t* d_feat_landmark, const int32_t* d_n_feat) {
+    if (!h || !ids || n <= 0 || !d_feat_landmark || !d_n_feat) return MYSLAM_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(h->mu);
+    if (n > h->n) return MYSLAM_ERR_INVALID;                                  // more items than key-frames held: one of them is unknown or repeated
+    std::vector<int32_t> slots((size_t)n);
+    for (int i = 0; i < n; i++)
+        if ((slots[i] = h->find(ids[i])) < 0) return MYSLAM_ERR_INVALID;
+    {   // two items for one key-frame would race
+        std::vector<int32_t> s(slots);
+        std::sort(s.begin(), s.end());
+        if (std::adjacent_find(s.begin(), s.end()) != s.end()) return MYSLAM_ERR_INVALID;
+    }
+    if (stream_is_capturing(h->stream)) return MYSLAM_ERR_UNSUPPORTED;
+    const int r = h->ring; h->ring = (h->ring + 1) % myslam_loop_store::RING;
+    if (h->slotPending[r]) MYSLAM_HIP_CHECK(hipEventSynchronize(h->slotEv[r]));  // the copy of four calls ago: long done
+    int32_t* const stage = h->h_slots + (size_t)r * h->kf_capacity;
+    memcpy(stage, slots.data(), sizeof(int32_t) * (size_t)n);
+    MYSLAM_HIP_CHECK(hipMemcpyAsync(h->d_slots, stage, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, h->stream));
+    MYSLAM_HIP_CHECK(hipEventRecord(h->slotEv[r], h->stream)); h->slotPending[r] = true;
+    const int chunks = ls_chunks(n, (size_t)h->feat_cap * 4);
+    for (int b0 = 0; b0 < n; b0 += LS_MAX_GRID_Y) {
+        const int nb = std::min(n - b0, LS_MAX_GRID_Y);
+        hipLaunchKernelGGL(k_loop_store_set_landmarks, dim3(chunks, nb), dim3(LS_THREADS), 0, h->stream, h->view, h->d_slots + b0,
+                           d_feat_landmark + (size_t)b0 * h->feat_cap, d_n_feat + b0);
+        MYSLAM_HIP_CHECK(hipGetLastError());
+    }
+    return MYSLAM_OK;
+}
+
+int myslam_loop_detect_batch(myslam_loop_store* h, const uint64_t* d_best_id, const float* d_max_score, const int32_t* d_cnt, int nq, float thr_high,
+                             int max_suspected, uint8_t* d_loop_desc, int32_t* d_n_loop, myslam_keypoint* d_loop_pyr, int32_t* d_loop_feat_landmark,
+                             int32_t* d_loop_slot, int32_t* d_status) {
+    if (!h || !d_best_id || !d_max_score || !d_cnt || nq <= 0 || !d_loop_desc || !d_n_loop || !d_loop_pyr || !d_loop_feat_landmark || !d_loop_slot ||
+        !d_status)
+        return MYSLAM_ERR_INVALID;
+    if (nq > LS_MAX_GRID_Y) return MYSLAM_ERR_CAPACITY;
+    std::lock_guard<std::mutex> lk(h->mu);
+    hipLaunchKernelGGL(k_loop_detect, dim3(ls_chunks(nq, h->item_bytes()), nq), dim3(LS_THREADS), 0, h->stream, h->view, d_best_id, d_max_score, d_cnt,
+                       thr_high, max_suspected, d_loop_desc, d_n_loop, d_loop_pyr, d_loop_feat_landmark, d_loop_slot, d_status);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    return MYSLAM_OK;
+}
+
+}  // extern "C"

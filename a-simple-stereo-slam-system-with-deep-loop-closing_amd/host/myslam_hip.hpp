@@ -539,6 +539,42 @@ public:
     }
 };
 
+// What ProcessNewKF leaves in a KeyFrame (mvPyramidKeyPoints, mORBDescriptors, which features still name a map point), resident on the device for up to
+// kfCapacity key-frames of cap rows and featCap features, and LoopClosing::DetectLoop's decision (src/loopclosing.cpp:147, :151) over
+// LoopDatabase's batched scan: DetectBatch writes the chosen key-frames' arrays exactly where MatchFeaturesBatch reads its loop side, status[b] =
+// MYSLAM_LOOP_DETECT_* or MYSLAM_ERR_INVALID (an id that is not held); a rejected item has nLoop 0 and falls through the later stages.  PutBatch takes
+// ProcessNewKFBatch's outputs (ids ascending, on the host); SetLandmarksBatch replaces the landmark tables of key-frames already held.  Every call
+// enqueues on the handle's stream and returns; DetectBatch is one launch and can be recorded.
+class LoopKeyFrameStore {
+    myslam_loop_store* h_ = nullptr;
+    int cap_, featCap_;
+public:
+    LoopKeyFrameStore(int kfCapacity, int cap, int featCap) : cap_(cap), featCap_(featCap) {
+        check(myslam_loop_store_create(&h_, kfCapacity, cap, featCap), "myslam_loop_store_create");
+    }
+    ~LoopKeyFrameStore() { if (h_) myslam_loop_store_destroy(h_); }
+    LoopKeyFrameStore(const LoopKeyFrameStore&) = delete; LoopKeyFrameStore& operator=(const LoopKeyFrameStore&) = delete;
+    int cap() const { return cap_; }
+    int featCap() const { return featCap_; }
+    int size() const { return myslam_loop_store_size(h_); }
+    int capacity() const { return myslam_loop_store_capacity(h_); }
+    void SetStream(void* hipStream) { check(myslam_loop_store_set_stream(h_, hipStream), "myslam_loop_store_set_stream"); }
+    void PutBatch(const std::vector<uint64_t>& ids, const KeyPoint* d_pyramidKeyPoints, const uint8_t* d_descriptors, const int32_t* d_counts,
+                  const int32_t* d_kfStatus /*may be nullptr*/, const int32_t* d_featureLandmark, const int32_t* d_nFeatures) {
+        check(myslam_loop_store_put_batch(h_, ids.data(), (int)ids.size(), d_pyramidKeyPoints, d_descriptors, d_counts, d_kfStatus, d_featureLandmark,
+                                          d_nFeatures), "myslam_loop_store_put_batch");
+    }
+    void SetLandmarksBatch(const std::vector<uint64_t>& ids, const int32_t* d_featureLandmark, const int32_t* d_nFeatures) {
+        check(myslam_loop_store_set_landmarks_batch(h_, ids.data(), (int)ids.size(), d_featureLandmark, d_nFeatures), "myslam_loop_store_set_landmarks_batch");
+    }
+    void DetectBatch(const uint64_t* d_bestId, const float* d_maxScore, const int32_t* d_cntSuspected, int nq, uint8_t* d_loopDescriptors, int32_t* d_nLoop,
+                     KeyPoint* d_loopPyramidKeyPoints, int32_t* d_loopFeatureLandmark, int32_t* d_loopSlot, int32_t* d_status, float thrHigh = 0.94f /*:147*/,
+                     int maxSuspected = 3 /*:147*/) {
+        check(myslam_loop_detect_batch(h_, d_bestId, d_maxScore, d_cntSuspected, nq, thrHigh, maxSuspected, d_loopDescriptors, d_nLoop,
+                                       d_loopPyramidKeyPoints, d_loopFeatureLandmark, d_loopSlot, d_status), "myslam_loop_detect_batch");
+    }
+};
+
 // The ORB half of LoopClosing::ProcessNewKF (src/loopclosing.cpp:93-113) for a batch of key-frames whose images and feature pixels live on the device:
 // every feature expanded over the extractor's levels, ScreenAndComputeKPsParams, CalcDescriptors.  Writes mvPyramidKeyPoints (batch x cap),
 // mORBDescriptors (batch x cap x 32) and their counts exactly where MatchFeaturesBatch reads them; status[b] = MYSLAM_OK or MYSLAM_ERR_CAPACITY.  The

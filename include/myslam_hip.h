@@ -275,6 +275,71 @@ int myslam_loop_match_batch(
     int32_t* d_status, void* hip_stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Loop key-frame store and the decision of LoopClosing::DetectLoop on the device — what lies between myslam_lcddb_query_batch's three outputs and
+ * myslam_loop_match_batch's loop-side inputs: `if (maxScore < 0.94 || cntSuspected > 3) return false` (src/loopclosing.cpp:147, the whole function
+ * :124-161) and `_mpLoopKF = _mvDatabase.at(bestId)` (:151) with what that key-frame holds (include/myslam/keyframe.h: mvPyramidKeyPoints,
+ * mORBDescriptors, and for every feature of mvpFeaturesLeft whether mpMapPoint.lock() still names a landmark).
+ *
+ * The store has kf_capacity slots of `cap` key-points (all 28 bytes), cap x 32 descriptor bytes, a row count, feat_cap landmark slots and a feature
+ * count; slot s is the s-th key-frame put.  Nothing ever moves and nothing grows, so a recorded step that names the store stays valid.  Ids ascend, as
+ * the loop database's do, and are kept on the host and in a device array.
+ *
+ * put_batch: `batch` key-frames as myslam_orb_process_keyframes_batch left them (d_pyr_kps, d_desc, d_counts, item b at + b*cap; d_kf_status = its
+ * d_status or NULL) plus the feature -> landmark table in myslam_loop_match_batch's d_loop_feat_landmark layout (batch x feat_cap, -1 = no map point)
+ * and its count.  ids (host): strictly ascending and above every id held, else MYSLAM_ERR_INVALID; size + batch > kf_capacity: MYSLAM_ERR_CAPACITY; in
+ * both cases nothing is stored or enqueued and the store answers later calls as before.  Counts are read on the device: d_counts[b] below 0 reads as 0,
+ * above cap as cap; d_kf_status[b] != 0 stores the key-frame with 0 rows (the reference keeps such a key-frame, and it matches nothing); d_n_feat[b] is
+ * clamped to [0, feat_cap]; only rows and entries below the counts are read.  Enqueues on the handle's stream and does not wait; the caller's arrays
+ * may be reused once that work is done.  Like myslam_lcddb_append_batch_async it is host bookkeeping as well and cannot be replayed:
+ * MYSLAM_ERR_UNSUPPORTED, before anything is enqueued, while the handle's stream is being captured (the capture stays usable).
+ *
+ * set_landmarks_batch: replaces the feature -> landmark table and feature count of n key-frames already held (mpMapPoint.lock() goes null when the map
+ * removes or fuses a point; that bookkeeping stays with the caller).  An id that is not held, or named twice: MYSLAM_ERR_INVALID, nothing enqueued.
+ * Same stream, capture and clamping rules as put_batch.
+ *
+ * detect_batch: ONE launch on the handle's stream; allocates nothing, never synchronises, reads no device memory from the host: recordable between
+ * myslam_graph_begin / _end.  Ids, counts and the number of key-frames held are read on the device, so a replay sees key-frames put after the
+ * recording.  d_best_id / d_max_score / d_cnt are myslam_lcddb_query_batch's outputs (nq each).  Per item b:
+ *   1. d_max_score[b] < thr_high || d_cnt[b] > max_suspected, f32 and i32 compares, the reference's expression literally (0.94f and 3 at :147):
+ *      d_status[b] = MYSLAM_LOOP_DETECT_NO_LOOP, d_n_loop[b] = 0, d_loop_slot[b] = -1, no other byte of the item is written.  A NaN score is not
+ *      "less", exactly as in the reference, so it goes on to step 2; thr_high = +inf rejects every item with a finite score, which is how a recorded
+ *      step is switched off while the database is below the reference's size gate;
+ *   2. d_best_id[b] is looked up among the ids held; not held: d_status[b] = MYSLAM_ERR_INVALID, d_n_loop[b] = 0, d_loop_slot[b] = -1, no other byte
+ *      of the item is written;
+ *   3. d_status[b] = MYSLAM_LOOP_DETECT_CANDIDATE, d_loop_slot[b] = the slot, d_n_loop[b] = the stored row count; that many key-points (item b at
+ *      d_loop_pyr + b*cap) and descriptors (d_loop_desc + b*cap*32) and the stored number of landmark entries (d_loop_feat_landmark + b*feat_cap) are
+ *      copied.  Output slots from the counts on are left as they were.
+ * A rejected item carries n_loop = 0: myslam_loop_match_batch answers MYSLAM_LOOP_MATCH_FEW_PAIRS for it, myslam_loop_verify_batch
+ * MYSLAM_VERIFY_FEW_MATCHES and myslam_loop_correct_batch MYSLAM_LOOP_CORRECT_SKIPPED, so the chain needs no compaction between its stages.
+ * The gate `_mvDatabase.size() > _mnDatabaseMinSize` (:62) stays with the caller (see thr_high = +inf above), as does AddToDatabase for the items
+ * that end unconfirmed.
+ *
+ * Call level, nothing enqueued: NULL pointers (d_kf_status excepted), nq / batch / n / kf_capacity / cap / feat_cap <= 0 -> MYSLAM_ERR_INVALID;
+ * cap > 16384, feat_cap > 65536 (myslam_loop_match_batch's limits) or nq > 65535 -> MYSLAM_ERR_CAPACITY; create out of device memory ->
+ * MYSLAM_ERR_CAPACITY, any other allocation failure -> MYSLAM_ERR_HIP.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct myslam_loop_store myslam_loop_store;
+int myslam_loop_store_create(myslam_loop_store** out, int kf_capacity, int cap, int feat_cap);
+int myslam_loop_store_destroy(myslam_loop_store* h);
+int myslam_loop_store_set_stream(myslam_loop_store* h, void* hip_stream);
+int myslam_loop_store_size(const myslam_loop_store* h);        /* key-frames held */
+int myslam_loop_store_capacity(const myslam_loop_store* h);
+int myslam_loop_store_put_batch(myslam_loop_store* h, const uint64_t* ids /*host*/, int batch,
+        const myslam_keypoint* d_pyr_kps, const uint8_t* d_desc, const int32_t* d_counts,   /* process_keyframes_batch's outputs, item b at + b*cap */
+        const int32_t* d_kf_status,            /* its d_status, may be NULL */
+        const int32_t* d_feat_landmark,        /* batch x feat_cap, the layout of loop_match_batch's d_loop_feat_landmark */
+        const int32_t* d_n_feat);              /* batch */
+int myslam_loop_store_set_landmarks_batch(myslam_loop_store* h, const uint64_t* ids /*host*/, int n,
+        const int32_t* d_feat_landmark, const int32_t* d_n_feat);
+#define MYSLAM_LOOP_DETECT_CANDIDATE 0
+#define MYSLAM_LOOP_DETECT_NO_LOOP   1
+int myslam_loop_detect_batch(myslam_loop_store* h,
+        const uint64_t* d_best_id, const float* d_max_score, const int32_t* d_cnt, int nq,   /* myslam_lcddb_query_batch's outputs */
+        float thr_high, int max_suspected,                                                   /* 0.94f and 3 at loopclosing.cpp:147 */
+        uint8_t* d_loop_desc, int32_t* d_n_loop, myslam_keypoint* d_loop_pyr, int32_t* d_loop_feat_landmark,   /* loop_match_batch's inputs, item b at + b*cap (+ b*feat_cap) */
+        int32_t* d_loop_slot, int32_t* d_status);                                            /* nq each */
+
+/* ------------------------------------------------------------------------------------------
  * Triangulation — replaces triangulation() include/myslam/algorithm.h:16-33 with the stereo rig
  * of src/system.cpp:108-116,141-145 and Camera::pixel2camera src/camera.cpp:22-26.
  * ok[i] = (sigma3/sigma2 < 1e-2) && z > 0   (frontend.cpp:400, 471).
