@@ -1045,6 +1045,67 @@ class LoopCorrector:
                                                C.c_void_p(d_chi2), C.c_void_p(d_iters), C.c_void_p(d_status)), "myslam_loop_correct_batch")
 
 
+BACKEND_DONE, BACKEND_EMPTY = 0, 1                     # MYSLAM_BACKEND_*
+BACKEND_OBS_ACTIVE, BACKEND_OBS_OUTLIER = 1, 2         # bits of d_obs_flags
+BA_MAX_WINDOW_POSES = 10                               # MYSLAM_BA_MAX_WINDOW_POSES
+
+
+class Backend:
+    """Backend::OptimizeActiveMap (src/backend.cpp:126-266) for a batch of active maps held in device tables (myslam_backend_*): the handle owns the
+    flat windows and the solve's workspace for `max_batch` maps of up to `kf_cap` key-frames, `mp_cap` map points and `obs_cap` observation rows; the
+    call takes device pointers as ints, enqueues three launches on the handle's stream and returns."""
+
+    def __init__(self, max_batch, kf_cap, mp_cap, obs_cap, stream=None):
+        self.max_batch, self.kf_cap, self.mp_cap, self.obs_cap = int(max_batch), int(kf_cap), int(mp_cap), int(obs_cap)
+        self._h = C.c_void_p()
+        _check(lib().myslam_backend_create(C.byref(self._h), self.max_batch, self.kf_cap, self.mp_cap, self.obs_cap), "myslam_backend_create")
+        if stream is not None:
+            self.set_stream(stream)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and self._h.value and _lib is not None:
+            lib().myslam_backend_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def set_stream(self, stream):
+        _check(lib().myslam_backend_set_stream(self._h, C.c_void_p(stream)), "myslam_backend_set_stream")
+
+    def launches_per_call(self):
+        return lib().myslam_backend_launches_per_call(self._h)
+
+    def optimize_batch(self, d_kf_id, d_kf_pose, d_n_kf, d_mp_id, d_mp_pos, d_mp_outlier, d_n_mp, d_obs_mp, d_obs_kf, d_obs_flags, d_obs_uv, d_obs_tag,
+                       d_n_obs, batch, K, d_obs_report, d_mp_report, d_new_outlier_mp, d_n_new_outlier_mp, d_obs_chi2, d_rounds, d_n_outlier_edges,
+                       d_status, delta=5.991, chi2_th=5.991, rounds=5, iters=10):
+        """Graph build (:139-206), solve (:208-243) and write-back (:234-266, map.cpp:126-175) per item, arguments in the header's order, tables strided
+        by the handle's caps and updated in place (include/myslam_hip.h); K = (fx, fy, cx, cy); d_status batch i32 = BACKEND_DONE / BACKEND_EMPTY or
+        a negative error"""
+        ptrs = [C.c_void_p(p) for p in (d_kf_id, d_kf_pose, d_n_kf, d_mp_id, d_mp_pos, d_mp_outlier, d_n_mp, d_obs_mp, d_obs_kf, d_obs_flags, d_obs_uv,
+                                        d_obs_tag, d_n_obs)]
+        outs = [C.c_void_p(p) for p in (d_obs_report, d_mp_report, d_new_outlier_mp, d_n_new_outlier_mp, d_obs_chi2, d_rounds, d_n_outlier_edges, d_status)]
+        _check(lib().myslam_backend_optimize_batch(self._h, *ptrs, int(batch), C.c_double(K[0]), C.c_double(K[1]), C.c_double(K[2]), C.c_double(K[3]),
+                                                   C.c_double(delta), C.c_double(chi2_th), int(rounds), int(iters), *outs),
+               "myslam_backend_optimize_batch")
+
+    def debug_flat(self, item):
+        """The flat window of one item as the last call built it, in ba_flatten_window's form (synchronises)"""
+        ps = np.zeros(self.kf_cap, np.int32); pt = np.zeros(self.mp_cap, np.int32); fixed = np.zeros(self.mp_cap, np.uint8)
+        ep = np.zeros(self.obs_cap, np.int32); el = np.zeros(self.obs_cap, np.int32); eo = np.zeros((self.obs_cap, 2)); es = np.zeros(self.obs_cap, np.int32)
+        sz = np.zeros(3, np.int32)
+        _check(lib().myslam_backend_debug_flat(self._h, int(item), _p(ps), _p(pt), _p(ep), _p(el), _p(eo), _p(es), _p(fixed), _p(sz)),
+               "myslam_backend_debug_flat")
+        P, L, E = (int(v) for v in sz)
+        return dict(pose_src=ps[:P], pt_src=pt[:L], fixed=fixed[:L], edge_pose=ep[:E], edge_pt=el[:E], edge_obs=eo[:E], edge_src=es[:E])
+
+    def debug_solved(self, item):
+        """(poses, points, edge chi2, edge outlier flags, rounds, outlier count) the solve left for that flat window (synchronises)"""
+        po = np.zeros((self.kf_cap, 7)); px = np.zeros((self.mp_cap, 3)); chi = np.zeros(self.obs_cap); out = np.zeros(self.obs_cap, np.uint8)
+        sz = np.zeros(3, np.int32); ro = np.zeros(2, np.int32)
+        _check(lib().myslam_backend_debug_flat(self._h, int(item), None, None, None, None, None, None, None, _p(sz)), "myslam_backend_debug_flat")
+        _check(lib().myslam_backend_debug_solved(self._h, int(item), _p(po), _p(px), _p(chi), _p(out), _p(ro)), "myslam_backend_debug_solved")
+        P, L, E = (int(v) for v in sz)
+        return po[:P], px[:L], chi[:E], out[:E], int(ro[0]), int(ro[1])
+
+
 LOOP_DETECT_CANDIDATE, LOOP_DETECT_NO_LOOP = 0, 1      # MYSLAM_LOOP_DETECT_*
 
 

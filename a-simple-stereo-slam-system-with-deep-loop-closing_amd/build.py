@@ -35,6 +35,7 @@ UNITS = {
     "pgo.hip": [],
     "pnp.hip": EXACT,
     "loop_correct.hip": [],
+    "backend.hip": [],                     # integer scans and copies; the solve stays in ba.hip
     "loop_store.hip": [],                  # copies and two compares: nothing a contraction could change
     "prof.hip": [],
     "io.hip": [],

@@ -43,6 +43,7 @@ struct BaOptArgs {
     int rounds; double chi2_th; double* edge_chi2; uint8_t* outlier; int32_t* rounds_out; int32_t* nout_out;
     size_t wstride = 0;   // scratch doubles per window; 0 = maxE x 18 (the batch entry points' contract).  The host-pointer entry points size it
                           // themselves: a window with many short-lived landmarks (22 doubles each in the HBM form) may need more than its edges give
+    const int32_t* skip = nullptr;      // nwin or NULL: a window whose entry is not 0 is left alone, nothing of it read or written (backend.hip's refused items)
 };
 
 __device__ __forceinline__ void ba_edge(const double* R, const double* pw, const double* z, double fx, double fy, double cx, double cy,
@@ -480,6 +481,7 @@ __global__ __launch_bounds__(BA_NT) void k_ba_optimize(BaOptArgs a) {
     __shared__ int s_poff[16];
     __shared__ int s_bad, s_dup;
     const int w = blockIdx.x, t = threadIdx.x, wv = t >> 6, lane = t & 63;
+    if (a.skip && a.skip[w]) return;
     const int P = a.sizes ? a.sizes[3 * w] : a.nposes;
     const int L = a.sizes ? a.sizes[3 * w + 1] : a.npts;
     const int E = a.sizes ? a.sizes[3 * w + 2] : a.nedges;
@@ -1515,6 +1517,18 @@ int pose_only_loop_launch(double* d_poses, const double* d_pts3d, const double* 
     pose_only_launch(a, batch, cap, s);
     MYSLAM_HIP_CHECK(hipGetLastError());
     return MYSLAM_OK;
+}
+// Backend::OptimizeActiveMap's solve stage for the batched back end (backend.hip, declared in backend_launch.h): myslam_ba_optimize_active_map_batch
+// without its argument checks, with the scratch stride the host-pointer calls use and a per-window skip flag
+size_t ba_active_map_scratch_doubles(int max_pts, int max_edges) { return std::max((size_t)max_edges * 18, ba_opt_scratch_need(max_pts, max_edges, true)); }
+int ba_active_map_launch(double* d_poses, double* d_points, const int32_t* d_edge_pose, const int32_t* d_edge_pt, const double* d_obs, const uint8_t* d_fixed,
+                         const int32_t* d_sizes, const int32_t* d_skip, int nwin, int max_poses, int max_pts, int max_edges, double fx, double fy, double cx,
+                         double cy, double huber_delta, double chi2_th, int max_rounds, int iters_per_round, double* d_scratch, size_t scratch_stride,
+                         double* d_edge_chi2, uint8_t* d_outlier, int32_t* d_rounds, int32_t* d_n_outliers, int32_t* d_status, hipStream_t s) {
+    BaOptArgs a{d_poses, d_points, d_edge_pose, d_edge_pt, d_obs, d_fixed, d_sizes, 0, 0, 0, max_poses, max_pts, max_edges,
+                fx, fy, cx, cy, huber_delta, iters_per_round, d_scratch, nullptr, nullptr, d_status,
+                max_rounds, chi2_th, d_edge_chi2, d_outlier, d_rounds, d_n_outliers, scratch_stride, d_skip};
+    return ba_opt_launch(a, nwin, s);
 }
 }  // namespace myslam_hip
 }  // extern "C++"

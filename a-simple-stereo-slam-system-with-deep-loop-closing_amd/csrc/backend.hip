@@ -1,0 +1,399 @@
+// backend.hip — Backend::OptimizeActiveMap (reference src/backend.cpp:126-266) for a batch of active maps that live in device tables.
+// Three dependent launches on the handle's stream, one workgroup per map in each:
+//   k_backend_flatten     the graph-build rules of :139-206 in the orders of myslam_ba_flatten_window (pose slot = key-frame row, landmark slots in
+//                         map-point row order, edges grouped by landmark in row order), and the validation of the tables;
+//   k_ba_optimize         the solve of :208-243 (ba.hip, through backend_launch.h) on the handle's flat windows;
+//   k_backend_write_back  :234-266 with Map::RemoveAllOutlierMapPoints / RemoveOldActiveMapPoints (src/map.cpp:126-175): outlier edges leave the
+//                         observation table, emptied map points become outliers, poses and positions are stored, the map-point and observation
+//                         tables are compacted in place.
+// Every order is fixed by the tables, so positions come from block-wide exclusive scans (ballot + mbcnt inside a wave, the wave totals in LDS):
+// no global atomics, and an item's bytes depend neither on its slot nor on its neighbours.  See include/myslam_hip.h for the contract.
+#include "backend_launch.h"
+
+namespace myslam_hip {
+
+constexpr int BE_NT = 512, BE_NW = BE_NT / WAVE;
+constexpr int BE_ACTIVE = MYSLAM_BACKEND_OBS_ACTIVE, BE_OUTLIER = MYSLAM_BACKEND_OBS_OUTLIER;
+
+struct BeTables {                       // the caller's tables, strided by the caps
+    const int64_t* kf_id; double* kf_pose; const int32_t* n_kf;
+    int64_t* mp_id; double* mp_pos; uint8_t* mp_outlier; int32_t* n_mp;
+    int32_t* obs_mp; int32_t* obs_kf; uint8_t* obs_flags; float* obs_uv; int32_t* obs_tag; int32_t* n_obs;
+    int kf_cap, mp_cap, obs_cap;
+};
+
+struct BeWork {                         // the handle's buffers, strided by the same caps
+    double* poses; double* pts; int32_t* ep; int32_t* el; double* obs; uint8_t* fixed; int32_t* sizes;       // the flat windows (k_ba_optimize's arguments)
+    int32_t* pt_src; int32_t* edge_src;
+    int32_t* eidx;                      // obs_cap + 1 per item: edges before row r; row r is an edge iff eidx[r + 1] > eidx[r]
+    int32_t* mp_slot;                   // landmark slot of a map-point row, -1 = none
+    int32_t* mp_new;                    // row of a map point after the compaction, -1 = it left the table
+    int32_t* st;                        // the flatten's verdict: 0 = solve this item, else the item's final status (doubles as the solve's skip flag)
+    double* chi2; uint8_t* out; int32_t* rounds; int32_t* nout; int32_t* solve_st;
+};
+
+struct BeOut {
+    uint8_t* obs_report; uint8_t* mp_report; int32_t* new_outlier_mp; int32_t* n_new_outlier_mp; double* obs_chi2;
+    int32_t* rounds; int32_t* n_outlier_edges; int32_t* status;
+};
+
+// lanes below this one whose bit is set in a ballot mask
+__device__ __forceinline__ int be_lane_prefix(unsigned long long m) {
+    return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
+
+// Exclusive position of this thread's flag among the block's flags in thread order, and their number.  Every thread of the block calls it; the two
+// barriers inside also separate what a chunk read before the call from what it writes after it.
+__device__ __forceinline__ int be_block_rank(bool f, int* s_w, int& total) {
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const unsigned long long m = __ballot(f);
+    if (lane == 0) s_w[wv] = __popcll(m);
+    __syncthreads();
+    int off = 0, tot = 0;
+#pragma unroll
+    for (int i = 0; i < BE_NW; i++) { const int c = s_w[i]; off += i < wv ? c : 0; tot += c; }
+    __syncthreads();
+    total = tot;
+    return off + be_lane_prefix(m);
+}
+
+// first index in a[0, n) whose value is not below v (a non-decreasing; on any other input the result still lies in [0, n])
+__device__ __forceinline__ int be_lower(const int32_t* a, int n, int v) {
+    int lo = 0, hi = n;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] < v) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+
+__global__ __launch_bounds__(BE_NT) void k_backend_flatten(BeTables T, BeWork W) {
+    __shared__ int s_w[BE_NW];
+    __shared__ int s_bad;
+    const int b = blockIdx.x, t = threadIdx.x;
+    const int nk = T.n_kf[b], nm = T.n_mp[b], no = T.n_obs[b];
+    int32_t* sizes = W.sizes + 3 * (size_t)b;
+    if (nk < 0 || nk > T.kf_cap || nm < 0 || nm > T.mp_cap || no < 0 || no > T.obs_cap) {        // uniform
+        if (t == 0) { W.st[b] = MYSLAM_ERR_INVALID; sizes[0] = 0; sizes[1] = 0; sizes[2] = 0; }
+        return;
+    }
+    const int64_t* kf_id = T.kf_id + (size_t)b * T.kf_cap;
+    const double* kf_pose = T.kf_pose + (size_t)b * T.kf_cap * 7;
+    const int64_t* mp_id = T.mp_id + (size_t)b * T.mp_cap;
+    const double* mp_pos = T.mp_pos + (size_t)b * T.mp_cap * 3;
+    const uint8_t* mp_outlier = T.mp_outlier + (size_t)b * T.mp_cap;
+    const int32_t* obs_mp = T.obs_mp + (size_t)b * T.obs_cap;
+    const int32_t* obs_kf = T.obs_kf + (size_t)b * T.obs_cap;
+    const uint8_t* obs_flags = T.obs_flags + (size_t)b * T.obs_cap;
+    const float* obs_uv = T.obs_uv + (size_t)b * T.obs_cap * 2;
+    double* f_poses = W.poses + (size_t)b * T.kf_cap * 7;
+    double* f_pts = W.pts + (size_t)b * T.mp_cap * 3;
+    int32_t* f_ep = W.ep + (size_t)b * T.obs_cap;
+    int32_t* f_el = W.el + (size_t)b * T.obs_cap;
+    double* f_obs = W.obs + (size_t)b * T.obs_cap * 2;
+    uint8_t* f_fixed = W.fixed + (size_t)b * T.mp_cap;
+    int32_t* pt_src = W.pt_src + (size_t)b * T.mp_cap;
+    int32_t* edge_src = W.edge_src + (size_t)b * T.obs_cap;
+    int32_t* eidx = W.eidx + (size_t)b * (T.obs_cap + 1);
+    int32_t* mp_slot = W.mp_slot + (size_t)b * T.mp_cap;
+
+    // ---- validation ----
+    if (t == 0) s_bad = 0;
+    __syncthreads();
+    bool bad = false;
+    for (int i = t + 1; i < nk; i += BE_NT) bad |= kf_id[i - 1] >= kf_id[i];
+    for (int r = t; r < no; r += BE_NT) {
+        const int m = obs_mp[r], k = obs_kf[r];
+        bad |= m < 0 || m >= nm || (r > 0 && obs_mp[r - 1] > m) || k < -1 || k >= nk;
+        bad |= (obs_flags[r] & BE_ACTIVE) && k < 0;                         // the assert of :187
+    }
+    for (int m = t; m < nm; m += BE_NT) {
+        bad |= m > 0 && mp_id[m - 1] >= mp_id[m];
+        if (!mp_outlier[m]) {                                               // an active map point without observations (:175 would dereference front())
+            const int s = be_lower(obs_mp, no, m);
+            bad |= s >= no || obs_mp[s] != m;
+        }
+    }
+    if (bad) s_bad = 1;
+    __syncthreads();
+    if (s_bad) {
+        if (t == 0) { W.st[b] = MYSLAM_ERR_INVALID; sizes[0] = 0; sizes[1] = 0; sizes[2] = 0; }
+        return;
+    }
+
+    // ---- edges: ACTIVE && !OUTLIER rows of map points that are no outliers (:163, :183-189), in row order ----
+    int E = 0;
+    for (int base = 0; base < no; base += BE_NT) {
+        const int r = base + t;
+        bool e = false;
+        if (r < no) e = (obs_flags[r] & (BE_ACTIVE | BE_OUTLIER)) == BE_ACTIVE && !mp_outlier[obs_mp[r]];
+        int tot;
+        const int k = E + be_block_rank(e, s_w, tot);
+        if (r < no) eidx[r] = k;
+        if (e) {
+            f_ep[k] = obs_kf[r]; edge_src[k] = r;
+            f_obs[2 * k] = (double)obs_uv[2 * r]; f_obs[2 * k + 1] = (double)obs_uv[2 * r + 1];      // toVec2, :196
+        }
+        E += tot;
+    }
+    if (E == 0) {                                                           // nothing to optimise: the caller's early return
+        if (t == 0) { W.st[b] = MYSLAM_BACKEND_EMPTY; sizes[0] = 0; sizes[1] = 0; sizes[2] = 0; }
+        return;
+    }
+    if (t == 0) eidx[no] = E;
+    __syncthreads();
+
+    // ---- landmark slots: map points with at least one edge, in row order; fixed = the first observer has left the window (:175-177) ----
+    int L = 0;
+    for (int base = 0; base < nm; base += BE_NT) {
+        const int m = base + t;
+        bool has = false;
+        int s = 0;
+        if (m < nm && !mp_outlier[m]) {
+            s = be_lower(obs_mp, no, m);
+            has = eidx[be_lower(obs_mp, no, m + 1)] > eidx[s];
+        }
+        int tot;
+        const int slot = L + be_block_rank(has, s_w, tot);
+        if (m < nm) mp_slot[m] = has ? slot : -1;
+        if (has) {
+            pt_src[slot] = m;
+            f_fixed[slot] = obs_kf[s] < 0 ? 1 : 0;
+            f_pts[3 * slot] = mp_pos[3 * m]; f_pts[3 * slot + 1] = mp_pos[3 * m + 1]; f_pts[3 * slot + 2] = mp_pos[3 * m + 2];
+        }
+        L += tot;
+    }
+    __syncthreads();
+    for (int k = t; k < E; k += BE_NT) f_el[k] = mp_slot[obs_mp[edge_src[k]]];
+    for (int i = t; i < 7 * nk; i += BE_NT) f_poses[i] = kf_pose[i];
+    if (t == 0) { sizes[0] = nk; sizes[1] = L; sizes[2] = E; W.st[b] = 0; }
+}
+
+__global__ __launch_bounds__(BE_NT) void k_backend_write_back(BeTables T, BeWork W, BeOut O) {
+    __shared__ int s_w[BE_NW];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const int nk = T.n_kf[b], nm = T.n_mp[b], no = T.n_obs[b];
+    uint8_t* obs_report = O.obs_report + (size_t)b * T.obs_cap;
+    uint8_t* mp_report = O.mp_report + (size_t)b * T.mp_cap;
+    double* obs_chi2 = O.obs_chi2 + (size_t)b * T.obs_cap;
+    int st = W.st[b];
+    if (st == 0) st = W.solve_st[b];
+    if (st != 0) {                                                          // refused or empty: the tables keep every byte, the reports are zero
+        const int cm = min(max(nm, 0), T.mp_cap), co = min(max(no, 0), T.obs_cap);
+        for (int r = t; r < co; r += BE_NT) { obs_report[r] = 0; obs_chi2[r] = 0.0; }
+        for (int m = t; m < cm; m += BE_NT) mp_report[m] = 0;
+        if (t == 0) { O.rounds[b] = 0; O.n_outlier_edges[b] = 0; O.n_new_outlier_mp[b] = 0; O.status[b] = st; }
+        return;
+    }
+    double* kf_pose = T.kf_pose + (size_t)b * T.kf_cap * 7;
+    int64_t* mp_id = T.mp_id + (size_t)b * T.mp_cap;
+    double* mp_pos = T.mp_pos + (size_t)b * T.mp_cap * 3;
+    uint8_t* mp_outlier = T.mp_outlier + (size_t)b * T.mp_cap;
+    int32_t* obs_mp = T.obs_mp + (size_t)b * T.obs_cap;
+    int32_t* obs_kf = T.obs_kf + (size_t)b * T.obs_cap;
+    uint8_t* obs_flags = T.obs_flags + (size_t)b * T.obs_cap;
+    float* obs_uv = T.obs_uv + (size_t)b * T.obs_cap * 2;
+    int32_t* obs_tag = T.obs_tag + (size_t)b * T.obs_cap;
+    int32_t* new_outlier = O.new_outlier_mp + (size_t)b * T.mp_cap;
+    const double* f_poses = W.poses + (size_t)b * T.kf_cap * 7;
+    const double* f_pts = W.pts + (size_t)b * T.mp_cap * 3;
+    const int32_t* eidx = W.eidx + (size_t)b * (T.obs_cap + 1);
+    const int32_t* mp_slot = W.mp_slot + (size_t)b * T.mp_cap;
+    int32_t* mp_new = W.mp_new + (size_t)b * T.mp_cap;
+    const double* chi2 = W.chi2 + (size_t)b * T.obs_cap;
+    const uint8_t* out = W.out + (size_t)b * T.obs_cap;
+
+    for (int i = t; i < 7 * nk; i += BE_NT) kf_pose[i] = f_poses[i];        // :256-258
+
+    // ---- map points, in ascending chunks: a chunk is read, the block meets in be_block_rank, then the chunk is written at or below where it stood ----
+    int n_keep = 0, n_new = 0;
+    for (int base = 0; base < nm; base += BE_NT) {
+        const int m = base + t;
+        bool keep = false, newout = false;
+        int64_t id = 0;
+        double p0 = 0, p1 = 0, p2 = 0;
+        if (m < nm) {
+            const int s = be_lower(obs_mp, no, m), e = be_lower(obs_mp, no, m + 1);
+            int nrem = 0, nact = 0;
+            for (int k = eidx[s]; k < eidx[e]; k++) nrem += out[k] ? 1 : 0;                       // :237-241: the edge's row leaves both lists
+            for (int r = s; r < e; r++) nact += obs_flags[r] & BE_ACTIVE;
+            const bool old = mp_outlier[m] != 0;
+            newout = !old && nrem == e - s;                                                       // :243-246: no observation left
+            const bool leaves = nact - nrem == 0;                                                 // map.cpp:132
+            const int rep = (old || newout) ? 2 : (leaves ? 1 : 0);
+            mp_report[m] = (uint8_t)rep;
+            keep = rep == 0;
+            id = mp_id[m];
+            const int slot = mp_slot[m];
+            const double* src = slot >= 0 ? f_pts + 3 * slot : mp_pos + 3 * m;                    // :259-261
+            p0 = src[0]; p1 = src[1]; p2 = src[2];
+        }
+        int tot, ntot;
+        const int dst = n_keep + be_block_rank(keep, s_w, tot);
+        const int nd = n_new + be_block_rank(newout, s_w, ntot);
+        if (m < nm) mp_new[m] = keep ? dst : -1;
+        if (keep) { mp_id[dst] = id; mp_pos[3 * dst] = p0; mp_pos[3 * dst + 1] = p1; mp_pos[3 * dst + 2] = p2; mp_outlier[dst] = 0; }
+        if (newout) new_outlier[nd] = m;
+        n_keep += tot; n_new += ntot;
+    }
+    __syncthreads();
+
+    // ---- observation rows, the same way ----
+    int n_rows = 0;
+    for (int base = 0; base < no; base += BE_NT) {
+        const int r = base + t;
+        bool keep = false;
+        int m2 = 0, kf = 0, tag = 0;
+        uint8_t fl = 0;
+        float u = 0, v = 0;
+        if (r < no) {
+            const int k = eidx[r];
+            const bool edge = eidx[r + 1] > k, rem = edge && out[k];
+            m2 = mp_new[obs_mp[r]];
+            keep = m2 >= 0 && !rem;
+            obs_report[r] = rem ? 1 : (m2 < 0 ? 2 : 0);
+            obs_chi2[r] = edge ? chi2[k] : -1.0;
+            kf = obs_kf[r]; tag = obs_tag[r]; u = obs_uv[2 * r]; v = obs_uv[2 * r + 1];
+            fl = obs_flags[r];
+            if (edge) fl &= (uint8_t)~BE_OUTLIER;                                                 // :249
+        }
+        int tot;
+        const int dst = n_rows + be_block_rank(keep, s_w, tot);
+        if (keep) { obs_mp[dst] = m2; obs_kf[dst] = kf; obs_flags[dst] = fl; obs_uv[2 * dst] = u; obs_uv[2 * dst + 1] = v; obs_tag[dst] = tag; }
+        n_rows += tot;
+    }
+    if (t == 0) {
+        T.n_mp[b] = n_keep; T.n_obs[b] = n_rows;
+        O.n_new_outlier_mp[b] = n_new; O.rounds[b] = W.rounds[b]; O.n_outlier_edges[b] = W.nout[b]; O.status[b] = MYSLAM_BACKEND_DONE;
+    }
+}
+
+}  // namespace myslam_hip
+
+using namespace myslam_hip;
+
+struct myslam_backend {
+    int max_batch = 0, kf_cap = 0, mp_cap = 0, obs_cap = 0;
+    hipStream_t stream = nullptr;
+    size_t wstride = 0;
+    Buf<double> poses, pts, obs, scratch, chi2;
+    Buf<int32_t> ep, el, sizes, pt_src, edge_src, eidx, mp_slot, mp_new, st, rounds, nout, solve_st;
+    Buf<uint8_t> fixed, out;
+    BeWork work() const {
+        return BeWork{poses, pts, ep, el, obs, fixed, sizes, pt_src, edge_src, eidx, mp_slot, mp_new, st, chi2, out, rounds, nout, solve_st};
+    }
+};
+
+extern "C" {
+
+int myslam_backend_destroy(myslam_backend* h) {
+    if (!h) return MYSLAM_ERR_INVALID;
+    (void)hipStreamSynchronize(h->stream);
+    delete h;
+    return MYSLAM_OK;
+}
+
+int myslam_backend_create(myslam_backend** out, int max_batch, int kf_cap, int mp_cap, int obs_cap) {
+    if (!out || max_batch < 1 || max_batch > 65535 || kf_cap < 1 || mp_cap < 1 || obs_cap < 1) return MYSLAM_ERR_INVALID;
+    if (kf_cap > MYSLAM_BA_MAX_WINDOW_POSES) return MYSLAM_ERR_UNSUPPORTED;
+    if (mp_cap > (1 << 24) || obs_cap > (1 << 24)) return MYSLAM_ERR_CAPACITY;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MYSLAM_ERR_HIP;
+    myslam_backend* h = new myslam_backend();
+    h->max_batch = max_batch; h->kf_cap = kf_cap; h->mp_cap = mp_cap; h->obs_cap = obs_cap;
+    h->wstride = ba_active_map_scratch_doubles(mp_cap, obs_cap);
+    const size_t B = (size_t)max_batch, K = (size_t)kf_cap, M = (size_t)mp_cap, N = (size_t)obs_cap;
+    const int oom = MYSLAM_ERR_CAPACITY;
+    int rc;
+    if ((rc = h->poses.renew(B * K * 7, oom)) || (rc = h->pts.renew(B * M * 3, oom)) || (rc = h->obs.renew(B * N * 2, oom)) ||
+        (rc = h->scratch.renew(B * h->wstride, oom)) || (rc = h->chi2.renew(B * N, oom)) || (rc = h->ep.renew(B * N, oom)) ||
+        (rc = h->el.renew(B * N, oom)) || (rc = h->sizes.renew(B * 3, oom)) || (rc = h->pt_src.renew(B * M, oom)) ||
+        (rc = h->edge_src.renew(B * N, oom)) || (rc = h->eidx.renew(B * (N + 1), oom)) || (rc = h->mp_slot.renew(B * M, oom)) ||
+        (rc = h->mp_new.renew(B * M, oom)) || (rc = h->st.renew(B, oom)) || (rc = h->rounds.renew(B, oom)) || (rc = h->nout.renew(B, oom)) ||
+        (rc = h->solve_st.renew(B, oom)) || (rc = h->fixed.renew(B * M, oom)) || (rc = h->out.renew(B * N, oom))) {
+        delete h;
+        return rc;
+    }
+    // debug_flat before the first call reports empty windows
+    const std::vector<int32_t> zeros(B * 3, 0);
+    if ((rc = upload_table(h->sizes, zeros.data(), zeros.size() * sizeof(int32_t)))) { delete h; return rc; }
+    *out = h;
+    return MYSLAM_OK;
+}
+
+int myslam_backend_set_stream(myslam_backend* h, void* hip_stream) {
+    if (!h) return MYSLAM_ERR_INVALID;
+    h->stream = (hipStream_t)hip_stream;
+    return MYSLAM_OK;
+}
+
+int myslam_backend_launches_per_call(const myslam_backend* h) { return h ? 3 : MYSLAM_ERR_INVALID; }
+
+int myslam_backend_optimize_batch(myslam_backend* h, const int64_t* d_kf_id, double* d_kf_pose, const int32_t* d_n_kf, int64_t* d_mp_id, double* d_mp_pos,
+                                  uint8_t* d_mp_outlier, int32_t* d_n_mp, int32_t* d_obs_mp, int32_t* d_obs_kf, uint8_t* d_obs_flags, float* d_obs_uv,
+                                  int32_t* d_obs_tag, int32_t* d_n_obs, int batch, double fx, double fy, double cx, double cy, double huber_delta,
+                                  double chi2_th, int max_rounds, int iters_per_round, uint8_t* d_obs_report, uint8_t* d_mp_report,
+                                  int32_t* d_new_outlier_mp, int32_t* d_n_new_outlier_mp, double* d_obs_chi2, int32_t* d_rounds,
+                                  int32_t* d_n_outlier_edges, int32_t* d_status) {
+    if (!h || batch < 0 || max_rounds < 1 || iters_per_round < 1) return MYSLAM_ERR_INVALID;
+    if (batch > h->max_batch) return MYSLAM_ERR_CAPACITY;
+    if (batch == 0) return MYSLAM_OK;
+    if (!d_kf_id || !d_kf_pose || !d_n_kf || !d_mp_id || !d_mp_pos || !d_mp_outlier || !d_n_mp || !d_obs_mp || !d_obs_kf || !d_obs_flags || !d_obs_uv ||
+        !d_obs_tag || !d_n_obs || !d_obs_report || !d_mp_report || !d_new_outlier_mp || !d_n_new_outlier_mp || !d_obs_chi2 || !d_rounds ||
+        !d_n_outlier_edges || !d_status)
+        return MYSLAM_ERR_INVALID;
+    const BeTables T{d_kf_id, d_kf_pose, d_n_kf, d_mp_id, d_mp_pos, d_mp_outlier, d_n_mp, d_obs_mp, d_obs_kf, d_obs_flags, d_obs_uv, d_obs_tag, d_n_obs,
+                     h->kf_cap, h->mp_cap, h->obs_cap};
+    const BeWork W = h->work();
+    const BeOut O{d_obs_report, d_mp_report, d_new_outlier_mp, d_n_new_outlier_mp, d_obs_chi2, d_rounds, d_n_outlier_edges, d_status};
+    hipLaunchKernelGGL(k_backend_flatten, dim3(batch), dim3(BE_NT), 0, h->stream, T, W);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    const int rc = ba_active_map_launch(W.poses, W.pts, W.ep, W.el, W.obs, W.fixed, W.sizes, W.st, batch, h->kf_cap, h->mp_cap, h->obs_cap, fx, fy, cx, cy,
+                                        huber_delta, chi2_th, max_rounds, iters_per_round, h->scratch, h->wstride, W.chi2, W.out, W.rounds, W.nout,
+                                        W.solve_st, h->stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_backend_write_back, dim3(batch), dim3(BE_NT), 0, h->stream, T, W, O);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    return MYSLAM_OK;
+}
+
+static int be_fetch(myslam_backend* h, void* dst, const void* src, size_t bytes) {
+    if (!dst || bytes == 0) return MYSLAM_OK;
+    MYSLAM_HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    return MYSLAM_OK;
+}
+
+int myslam_backend_debug_flat(myslam_backend* h, int item, int32_t* pose_src, int32_t* pt_src, int32_t* edge_pose, int32_t* edge_pt, double* edge_obs,
+                              int32_t* edge_src, uint8_t* fixed, int32_t* sizes3) {
+    if (!h || item < 0 || item >= h->max_batch || !sizes3) return MYSLAM_ERR_INVALID;
+    MYSLAM_HIP_CHECK(hipStreamSynchronize(h->stream));
+    const size_t b = (size_t)item, M = (size_t)h->mp_cap, N = (size_t)h->obs_cap;
+    int rc;
+    if ((rc = be_fetch(h, sizes3, h->sizes + 3 * b, 3 * sizeof(int32_t)))) return rc;
+    const size_t P = (size_t)sizes3[0], L = (size_t)sizes3[1], E = (size_t)sizes3[2];
+    if (pose_src) for (size_t i = 0; i < P; i++) pose_src[i] = (int32_t)i;       // pose slot = key-frame row
+    if ((rc = be_fetch(h, pt_src, h->pt_src + b * M, L * sizeof(int32_t))) || (rc = be_fetch(h, fixed, h->fixed + b * M, L)) ||
+        (rc = be_fetch(h, edge_pose, h->ep + b * N, E * sizeof(int32_t))) || (rc = be_fetch(h, edge_pt, h->el + b * N, E * sizeof(int32_t))) ||
+        (rc = be_fetch(h, edge_obs, h->obs + b * N * 2, E * 2 * sizeof(double))) || (rc = be_fetch(h, edge_src, h->edge_src + b * N, E * sizeof(int32_t))))
+        return rc;
+    return MYSLAM_OK;
+}
+
+int myslam_backend_debug_solved(myslam_backend* h, int item, double* poses, double* points, double* edge_chi2, uint8_t* edge_outlier,
+                                int32_t* rounds_outliers2) {
+    if (!h || item < 0 || item >= h->max_batch) return MYSLAM_ERR_INVALID;
+    MYSLAM_HIP_CHECK(hipStreamSynchronize(h->stream));
+    const size_t b = (size_t)item, K = (size_t)h->kf_cap, M = (size_t)h->mp_cap, N = (size_t)h->obs_cap;
+    int32_t sz[3];
+    int rc;
+    if ((rc = be_fetch(h, sz, h->sizes + 3 * b, sizeof(sz)))) return rc;
+    const size_t P = (size_t)sz[0], L = (size_t)sz[1], E = (size_t)sz[2];
+    if ((rc = be_fetch(h, poses, h->poses + b * K * 7, P * 7 * sizeof(double))) || (rc = be_fetch(h, points, h->pts + b * M * 3, L * 3 * sizeof(double))) ||
+        (rc = be_fetch(h, edge_chi2, h->chi2 + b * N, E * sizeof(double))) || (rc = be_fetch(h, edge_outlier, h->out + b * N, E)))
+        return rc;
+    if (rounds_outliers2) {
+        rounds_outliers2[0] = 0; rounds_outliers2[1] = 0;
+        if (E && ((rc = be_fetch(h, rounds_outliers2, h->rounds + b, sizeof(int32_t))) || (rc = be_fetch(h, rounds_outliers2 + 1, h->nout + b, sizeof(int32_t)))))
+            return rc;
+    }
+    return MYSLAM_OK;
+}
+
+}  // extern "C"

@@ -539,6 +539,46 @@ public:
     }
 };
 
+// Backend::OptimizeActiveMap (src/backend.cpp:126-266) for a batch of active maps held in device tables: the handle owns the flat windows and the
+// solve's workspace of maxBatch maps of up to kfCap active key-frames, mpCap active map points and obsCap observation rows.  OptimizeBatch takes the
+// strided tables of myslam_backend_optimize_batch (include/myslam_hip.h) and updates them in place; status[b] = MYSLAM_BACKEND_DONE / _EMPTY or a
+// negative error.  Enqueues three launches on the handle's stream and returns; DebugFlat synchronises.
+class Backend {
+    myslam_backend* h_ = nullptr;
+    int maxBatch_, kfCap_, mpCap_, obsCap_;
+public:
+    Backend(int maxBatch, int kfCap, int mpCap, int obsCap) : maxBatch_(maxBatch), kfCap_(kfCap), mpCap_(mpCap), obsCap_(obsCap) {
+        check(myslam_backend_create(&h_, maxBatch, kfCap, mpCap, obsCap), "myslam_backend_create");
+    }
+    ~Backend() { if (h_) myslam_backend_destroy(h_); }
+    Backend(const Backend&) = delete; Backend& operator=(const Backend&) = delete;
+    int maxBatch() const { return maxBatch_; }
+    int kfCap() const { return kfCap_; }
+    int mpCap() const { return mpCap_; }
+    int obsCap() const { return obsCap_; }
+    void SetStream(void* hipStream) { check(myslam_backend_set_stream(h_, hipStream), "myslam_backend_set_stream"); }
+    int LaunchesPerCall() const { return myslam_backend_launches_per_call(h_); }
+    void OptimizeBatch(const int64_t* d_kfId, double* d_kfPose, const int32_t* d_nKF, int64_t* d_mpId, double* d_mpPos, uint8_t* d_mpOutlier, int32_t* d_nMP,
+                       int32_t* d_obsMP, int32_t* d_obsKF, uint8_t* d_obsFlags, float* d_obsUV, int32_t* d_obsTag, int32_t* d_nObs, int batch, double fx,
+                       double fy, double cx, double cy, uint8_t* d_obsReport, uint8_t* d_mpReport, int32_t* d_newOutlierMP, int32_t* d_nNewOutlierMP,
+                       double* d_obsChi2, int32_t* d_rounds, int32_t* d_nOutlierEdges, int32_t* d_status, double huberDelta = 5.991 /* :199 */,
+                       double chi2Th = 5.991 /* :155 */, int maxRounds = 5 /* :212 */, int itersPerRound = 10 /* :214 */) {
+        check(myslam_backend_optimize_batch(h_, d_kfId, d_kfPose, d_nKF, d_mpId, d_mpPos, d_mpOutlier, d_nMP, d_obsMP, d_obsKF, d_obsFlags, d_obsUV, d_obsTag,
+                                            d_nObs, batch, fx, fy, cx, cy, huberDelta, chi2Th, maxRounds, itersPerRound, d_obsReport, d_mpReport,
+                                            d_newOutlierMP, d_nNewOutlierMP, d_obsChi2, d_rounds, d_nOutlierEdges, d_status),
+              "myslam_backend_optimize_batch");
+    }
+    // the flat window of one item as the last call built it (host arrays of kfCap / mpCap / obsCap elements, any but sizes3 may be nullptr)
+    void DebugFlat(int item, int32_t* poseSrc, int32_t* ptSrc, int32_t* edgePose, int32_t* edgePt, double* edgeObs, int32_t* edgeSrc, uint8_t* fixed,
+                   int32_t* sizes3) {
+        check(myslam_backend_debug_flat(h_, item, poseSrc, ptSrc, edgePose, edgePt, edgeObs, edgeSrc, fixed, sizes3), "myslam_backend_debug_flat");
+    }
+    // what the solve left for that window, in slot / edge order
+    void DebugSolved(int item, double* poses, double* points, double* edgeChi2, uint8_t* edgeOutlier, int32_t* roundsOutliers2) {
+        check(myslam_backend_debug_solved(h_, item, poses, points, edgeChi2, edgeOutlier, roundsOutliers2), "myslam_backend_debug_solved");
+    }
+};
+
 // What ProcessNewKF leaves in a KeyFrame (mvPyramidKeyPoints, mORBDescriptors, which features still name a map point), resident on the device for up to
 // kfCapacity key-frames of cap rows and featCap features, and LoopClosing::DetectLoop's decision (src/loopclosing.cpp:147, :151) over
 // LoopDatabase's batched scan: DetectBatch writes the chosen key-frames' arrays exactly where MatchFeaturesBatch reads its loop side, status[b] =

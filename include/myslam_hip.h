@@ -947,6 +947,91 @@ int myslam_loop_correct_structure(int n_kf, const int32_t* active, int n_active,
                                   int* n_separators, int* chain_length, int* supported);
 
 /* ------------------------------------------------------------------------------------------
+ * Backend::OptimizeActiveMap (src/backend.cpp:126-266) for a BATCH of active maps that live in device tables — one enqueue takes every map
+ * through the graph build (:139-206, the rules of myslam_ba_flatten_window), the solve (:208-243, the kernel of
+ * myslam_ba_optimize_active_map_batch) and the write-back (:234-266 with Map::RemoveAllOutlierMapPoints / RemoveOldActiveMapPoints,
+ * src/map.cpp:126-175), and leaves each map's tables ready to be the next call's input.  The one-map host forms stay:
+ * myslam_ba_flatten_window + myslam_ba_optimize_active_map[_batch] + the caller's own container surgery.
+ * A handle owns every buffer (the flat windows, the solve's scratch sized as the host-pointer calls size it, per-edge chi2 and flags), so
+ * myslam_backend_optimize_batch allocates nothing, never synchronises, never reads device memory from the host and can be recorded between
+ * myslam_graph_begin / _end.  It is three dependent launches on the handle's stream (csrc/backend.hip, one workgroup per map in each).
+ * Item b is one map; tables are strided by the handle's caps, slots from an item's count on are never read or written:
+ *   d_kf_id        batch x kf_cap i64          Map::GetActiveKeyFrames(): mnKFId, strictly ascending (:135)
+ *   d_kf_pose      batch x kf_cap x 7 f64, in/out   Tcw (qx qy qz qw tx ty tz) (:145, :256-258);   d_n_kf  batch i32
+ *   d_mp_id        batch x mp_cap i64, in/out  Map::GetActiveMapPoints(): mnId, strictly ascending (:136)
+ *   d_mp_pos       batch x mp_cap x 3 f64, in/out   (:169, :259-261)
+ *   d_mp_outlier   batch x mp_cap u8, in/out   mbIsOutlier; an input row with the flag set is on the map's outlier list (both places where the
+ *                                              reference sets the flag also list the point: src/frontend.cpp:263-264, src/backend.cpp:244-245)
+ *   d_n_mp         batch i32, in/out
+ *   Observations: EVERY entry of GetObservations() of every active map point is one row (not only the active ones), grouped by map point, in
+ *   list order within a map point:
+ *   d_obs_mp       batch x obs_cap i32, in/out row of the map point in the item's table, non-decreasing
+ *   d_obs_kf       batch x obs_cap i32, in/out row of the observing key-frame in the item's key-frame table, -1 = that key-frame has left the window
+ *   d_obs_flags    batch x obs_cap u8, in/out  MYSLAM_BACKEND_OBS_ACTIVE: the feature is in GetActiveObservations(); MYSLAM_BACKEND_OBS_OUTLIER:
+ *                                              feature->mbIsOutlier
+ *   d_obs_uv       batch x obs_cap x 2 f32, in/out   mkpPosition.pt (:196)
+ *   d_obs_tag      batch x obs_cap i32, in/out the caller's own handle of the feature: carried along, never interpreted
+ *   d_n_obs        batch i32, in/out
+ * The caller's obligation: the reference appends to both observation lists in key-frame order (src/keyframe.cpp:45, src/map.cpp:38), so the ACTIVE
+ * rows of a map point in this order are its GetActiveObservations() order, and the first row of a segment is GetObservations().front() (:175).
+ * LoopLocalFusion appends observations that are not active (src/loopclosing.cpp:521-525): those rows carry ACTIVE = 0 although their key-frame is
+ * in the window.  Nothing has to be refreshed by the host after a removal.
+ * Per item:
+ *   1. flatten (:139-206): pose slot = key-frame row, landmark slots in map-point row order, edges grouped by landmark in row order.  An edge is an
+ *      ACTIVE && !OUTLIER row of a map point that is no outlier (:163, :189); a map point left without an edge gets no slot; a landmark is fixed when
+ *      the first row of its segment has d_obs_kf < 0 (:175-177); observations are widened f32 -> f64 (toVec2), poses and positions gathered bit for bit.
+ *      MYSLAM_ERR_INVALID: a count negative or beyond its cap, ids not strictly ascending, d_obs_mp decreasing or >= n_mp, d_obs_kf >= n_kf or
+ *      < -1, an ACTIVE row with d_obs_kf < 0 (the assert of :187), a map point that is no outlier and has no row.  An item without a single edge:
+ *      MYSLAM_BACKEND_EMPTY.  In both cases the item's tables keep every byte, its rows of d_obs_report / d_mp_report / d_obs_chi2 are zero and
+ *      d_rounds[b] = d_n_outlier_edges[b] = d_n_new_outlier_mp[b] = 0; the solve does not run for it.
+ *   2. solve (:208-243): as myslam_ba_optimize_active_map_batch (huber_delta = chi2_th = 5.991, max_rounds = 5, iters_per_round = 10 at the call site).
+ *      d_rounds[b] == max_rounds is reported as it is, not as an error: see MYSLAM_BA_CONVERGED.
+ *   3. write-back (:234-266): an edge with chi2 > chi2_th removes its row (RemoveActiveObservation and RemoveObservation, :240-241), every other
+ *      edge row gets OUTLIER cleared (:249); a map point whose segment becomes empty is an outlier (:243-246) and its INPUT row is appended to
+ *      d_new_outlier_mp[b] (batch x mp_cap i32) in edge order; optimised poses go to d_kf_pose, optimised positions to d_mp_pos of the map points
+ *      that had a slot (:256-261); every map point with the outlier flag, old or new, leaves the table with all its rows
+ *      (RemoveAllOutlierMapPoints, src/map.cpp:166-175), then every map point without an ACTIVE row (RemoveOldActiveMapPoints, src/map.cpp:126-140);
+ *      the map-point and observation tables are compacted in place in their old order, d_obs_mp is renumbered, d_mp_outlier of a kept row is 0 and
+ *      the counts are stored.  Rows between a new count and the old one keep their bytes.
+ * Reports, indexed by INPUT row:
+ *   d_obs_report  batch x obs_cap u8   0 kept, 1 removed as an outlier edge (the feature loses its map point, :247), 2 gone with its map point
+ *   d_mp_report   batch x mp_cap u8    0 kept, 1 left the active set, 2 erased as an outlier
+ *   d_obs_chi2    batch x obs_cap f64  the edge's chi2 (edge->chi2(), :237), -1 for a row that was not an edge
+ *   d_rounds / d_n_outlier_edges  batch i32   the *rounds / *n_outliers of myslam_ba_optimize_active_map;   d_status  batch i32
+ * An item's bytes depend neither on its slot in the batch nor on its neighbours.  Out of this call's scope: Map::InsertKeyFrame /
+ * RemoveOldActiveKeyframe (the caller sets d_obs_kf = -1 and clears ACTIVE on the rows of a key-frame that leaves).
+ * Call level, nothing enqueued: NULL pointers, batch < 0, max_rounds / iters_per_round < 1 -> MYSLAM_ERR_INVALID; batch beyond the handle's ->
+ * MYSLAM_ERR_CAPACITY.
+ * ------------------------------------------------------------------------------------------ */
+#define MYSLAM_BACKEND_DONE 0
+#define MYSLAM_BACKEND_EMPTY 1
+#define MYSLAM_BACKEND_OBS_ACTIVE 1
+#define MYSLAM_BACKEND_OBS_OUTLIER 2
+typedef struct myslam_backend myslam_backend;
+/* Backend::OptimizeActiveMap's workspace (src/backend.cpp:126-266) for max_batch maps of up to kf_cap active key-frames, mp_cap active map points
+ * and obs_cap observation rows each.  kf_cap > MYSLAM_BA_MAX_WINDOW_POSES -> MYSLAM_ERR_UNSUPPORTED; out of device memory -> MYSLAM_ERR_CAPACITY. */
+int myslam_backend_create(myslam_backend** out, int max_batch, int kf_cap, int mp_cap, int obs_cap);
+int myslam_backend_destroy(myslam_backend* h);
+int myslam_backend_set_stream(myslam_backend* h, void* hip_stream);
+/* src/backend.cpp:126-266 and src/map.cpp:126-175 as described above.  Device pointers, asynchronous on the handle's stream. */
+int myslam_backend_optimize_batch(myslam_backend* h, const int64_t* d_kf_id, double* d_kf_pose, const int32_t* d_n_kf, int64_t* d_mp_id, double* d_mp_pos,
+                                  uint8_t* d_mp_outlier, int32_t* d_n_mp, int32_t* d_obs_mp, int32_t* d_obs_kf, uint8_t* d_obs_flags, float* d_obs_uv,
+                                  int32_t* d_obs_tag, int32_t* d_n_obs, int batch, double fx, double fy, double cx, double cy, double huber_delta,
+                                  double chi2_th, int max_rounds, int iters_per_round, uint8_t* d_obs_report, uint8_t* d_mp_report,
+                                  int32_t* d_new_outlier_mp, int32_t* d_n_new_outlier_mp, double* d_obs_chi2, int32_t* d_rounds,
+                                  int32_t* d_n_outlier_edges, int32_t* d_status);
+/* launches one myslam_backend_optimize_batch enqueues (3: flatten, solve, write-back) */
+int myslam_backend_launches_per_call(const myslam_backend* h);
+/* The flat window (src/backend.cpp:139-206) of one item as the last call built it, in myslam_ba_flatten_window's outputs: host pointers (any but sizes3
+ * may be NULL) of kf_cap / mp_cap / obs_cap elements, sizes3 = (poses, landmarks, edges), all 0 for an item that was refused or empty.  Synchronises. */
+int myslam_backend_debug_flat(myslam_backend* h, int item, int32_t* pose_src, int32_t* pt_src, int32_t* edge_pose, int32_t* edge_pt, double* edge_obs,
+                              int32_t* edge_src, uint8_t* fixed, int32_t* sizes3);
+/* What the solve (src/backend.cpp:208-243) left for that flat window: poses, landmark positions, per-edge chi2 and outlier flags in slot / edge order,
+ * rounds_outliers2 = (*rounds, *n_outliers).  Host pointers, any may be NULL.  Synchronises. */
+int myslam_backend_debug_solved(myslam_backend* h, int item, double* poses, double* points, double* edge_chi2, uint8_t* edge_outlier,
+                                int32_t* rounds_outliers2);
+
+/* ------------------------------------------------------------------------------------------
  * Host-side formats of the reference's runner — plain host code, no device needed; the C++ forms live in
  * host/myslam_io.hpp and host/myslam_png.hpp.
  * ------------------------------------------------------------------------------------------ */
