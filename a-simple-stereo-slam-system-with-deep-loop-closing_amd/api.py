@@ -1086,6 +1086,26 @@ class Backend:
                                                    C.c_double(delta), C.c_double(chi2_th), int(rounds), int(iters), *outs),
                "myslam_backend_optimize_batch")
 
+    def insert_launches_per_call(self):
+        return lib().myslam_backend_insert_launches_per_call(self._h)
+
+    def insert_keyframe_batch(self, d_kf_id, d_kf_pose, d_n_kf, d_mp_id, d_mp_pos, d_mp_outlier, d_n_mp, d_obs_mp, d_obs_kf, d_obs_flags, d_obs_uv,
+                              d_obs_tag, d_n_obs, d_new_kf_id, d_new_kf_pose, d_feat_mp_id, d_feat_mp_pos, d_feat_uv, d_feat_tag, d_feat_flags, d_n_feat,
+                              feat_cap, d_prior_mp_id, d_prior_kf_id, d_prior_uv, d_prior_tag, d_prior_flags, d_n_prior, prior_cap, d_outlier_mp_id,
+                              d_n_outlier_mp, outlier_cap, batch, window, min_dis_th, d_feat_row, d_mp_new_row, d_removed_kf_id, d_removed_kf_row, d_dis,
+                              d_status):
+        """Map::InsertKeyFrame (src/map.cpp:17-48, :78-140) per item on the tables of optimize_batch, all of them in/out, arguments in the header's
+        order (include/myslam_hip.h); the optional prior / outlier inputs are None (or 0) when absent; window = Map.activeMap.size, min_dis_th = 0.2
+        at the call site; one launch on the handle's stream; d_status batch i32 = 0 or a negative error"""
+        vp = lambda p: C.c_void_p(p or None)
+        tabs = [vp(p) for p in (d_kf_id, d_kf_pose, d_n_kf, d_mp_id, d_mp_pos, d_mp_outlier, d_n_mp, d_obs_mp, d_obs_kf, d_obs_flags, d_obs_uv, d_obs_tag,
+                                d_n_obs, d_new_kf_id, d_new_kf_pose, d_feat_mp_id, d_feat_mp_pos, d_feat_uv, d_feat_tag, d_feat_flags, d_n_feat)]
+        prior = [vp(p) for p in (d_prior_mp_id, d_prior_kf_id, d_prior_uv, d_prior_tag, d_prior_flags, d_n_prior)]
+        outs = [vp(p) for p in (d_feat_row, d_mp_new_row, d_removed_kf_id, d_removed_kf_row, d_dis, d_status)]
+        _check(lib().myslam_backend_insert_keyframe_batch(self._h, *tabs, int(feat_cap), *prior, int(prior_cap), vp(d_outlier_mp_id), vp(d_n_outlier_mp),
+                                                          int(outlier_cap), int(batch), int(window), C.c_double(min_dis_th), *outs),
+               "myslam_backend_insert_keyframe_batch")
+
     def debug_flat(self, item):
         """The flat window of one item as the last call built it, in ba_flatten_window's form (synchronises)"""
         ps = np.zeros(self.kf_cap, np.int32); pt = np.zeros(self.mp_cap, np.int32); fixed = np.zeros(self.mp_cap, np.uint8)

@@ -8,7 +8,10 @@
 //                         tables are compacted in place.
 // Every order is fixed by the tables, so positions come from block-wide exclusive scans (ballot + mbcnt inside a wave, the wave totals in LDS):
 // no global atomics, and an item's bytes depend neither on its slot nor on its neighbours.  See include/myslam_hip.h for the contract.
+// k_backend_insert is Map::InsertKeyFrame (src/map.cpp:17-48 with KeyFrame::CreateKF's AddObservation loop, RemoveOldActiveKeyframe and
+// RemoveOldActiveMapPoints) on the same tables: one launch, one workgroup per map, the same scans; the tables are rebuilt from a copy the handle holds.
 #include "backend_launch.h"
+#include "pg_shared.h"
 
 namespace myslam_hip {
 
@@ -265,6 +268,350 @@ __global__ __launch_bounds__(BE_NT) void k_backend_write_back(BeTables T, BeWork
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------------------------
+// Map::InsertKeyFrame for a batch of maps (myslam_backend_insert_keyframe_batch)
+
+struct InsTables {                      // the caller's tables, all in/out
+    int64_t* kf_id; double* kf_pose; int32_t* n_kf;
+    int64_t* mp_id; double* mp_pos; uint8_t* mp_outlier; int32_t* n_mp;
+    int32_t* obs_mp; int32_t* obs_kf; uint8_t* obs_flags; float* obs_uv; int32_t* obs_tag; int32_t* n_obs;
+    int kf_cap, mp_cap, obs_cap;
+};
+
+struct InsIn {                          // the new key-frame of every item; n_prior / n_outlier NULL = none
+    const int64_t* new_kf_id; const double* new_kf_pose;
+    const int64_t* feat_mp_id; const double* feat_mp_pos; const float* feat_uv; const int32_t* feat_tag; const uint8_t* feat_flags;
+    const int32_t* n_feat; int feat_cap;
+    const int64_t* prior_mp_id; const int64_t* prior_kf_id; const float* prior_uv; const int32_t* prior_tag; const uint8_t* prior_flags;
+    const int32_t* n_prior; int prior_cap;
+    const int64_t* outlier_mp_id; const int32_t* n_outlier; int outlier_cap;
+    int window; double min_dis_th;
+};
+
+struct InsWork {                        // the handle's staging, strided by the caps
+    int64_t* mp_id; double* mp_pos; uint8_t* mp_outlier;                                         // the tables as they came in (outlier ids applied)
+    int32_t* obs_mp; int32_t* obs_kf; uint8_t* obs_flags; float* obs_uv; int32_t* obs_tag;
+    int64_t* vid; int32_t* vft;         // obs_cap: ids / indices of the features that name a map point, in feature order
+    int64_t* sid; int32_t* sfeat;       // obs_cap: the same sorted by (id, feature index)
+    int32_t* dcum;                      // obs_cap + 1: distinct ids that are new to the table among sorted features before s
+    int32_t* pcum;                      // obs_cap + 1: prior rows that enter the table before prior row p
+    int32_t* dmp; int32_t* drows;       // mp_cap + 1: map points / their rows that leave, before input row m
+    int32_t* mp_fin; int32_t* mp_shift; // mp_cap: final row of an input map point (-1 = it leaves); what its observation rows move by
+};
+
+struct InsOut {
+    int32_t* feat_row; int32_t* mp_new_row; int64_t* removed_kf_id; int32_t* removed_kf_row; double* dis; int32_t* status;
+};
+
+// exclusive block-wide prefix sum of v in thread order, and the sum; every thread of the block calls it (two barriers, as be_block_rank)
+__device__ __forceinline__ int be_block_exsum(int v, int* s_w, int& total) {
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int inc = v;
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) { const int o = __shfl_up(inc, d); if (lane >= d) inc += o; }
+    if (lane == WAVE - 1) s_w[wv] = inc;
+    __syncthreads();
+    int off = 0, tot = 0;
+#pragma unroll
+    for (int i = 0; i < BE_NW; i++) { const int c = s_w[i]; off += i < wv ? c : 0; tot += c; }
+    __syncthreads();
+    total = tot;
+    return off + inc - v;
+}
+
+// first index in a[0, n) whose value is not below v / is above v (a non-decreasing; on any other input the result still lies in [0, n])
+__device__ __forceinline__ int be_lower64(const int64_t* a, int n, int64_t v) {
+    int lo = 0, hi = n;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] < v) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+__device__ __forceinline__ int be_upper64(const int64_t* a, int n, int64_t v) {
+    int lo = 0, hi = n;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] <= v) lo = mid + 1; else hi = mid; }
+    return lo;
+}
+
+// One workgroup per map.  Everything is decided from the inputs and the staged copy before the first byte of a table is written; every position is a
+// closed form of binary searches and block scans:
+//   merged map-point row  = rows of the table below the id + distinct new ids below it
+//   merged observation row = the segment's old position + feature rows of smaller ids + prior rows that entered before it
+// minus what RemoveOldActiveMapPoints takes out below it.  The rank sort of the features is quadratic in their number (a key-frame has hundreds).
+__global__ __launch_bounds__(BE_NT) void k_backend_insert(InsTables T, InsIn I, InsWork W, InsOut O) {
+    __shared__ int s_w[BE_NW];
+    __shared__ int s_bad, s_victim;
+    __shared__ long long s_kfid[MYSLAM_BA_MAX_WINDOW_POSES + 1];
+    __shared__ double s_dis[MYSLAM_BA_MAX_WINDOW_POSES];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const int nk = T.n_kf[b], nm = T.n_mp[b], no = T.n_obs[b], nf = I.n_feat[b];
+    const int np = I.n_prior ? I.n_prior[b] : 0, nx = I.n_outlier ? I.n_outlier[b] : 0;
+    int32_t* feat_row = O.feat_row + (size_t)b * I.feat_cap;
+    int32_t* mp_new_row = O.mp_new_row + (size_t)b * T.mp_cap;
+    double* dis_out = O.dis + (size_t)b * T.kf_cap;
+    auto refuse = [&](int st) {                                             // the tables keep every byte; the reports say "nothing"
+        const int cf = min(max(nf, 0), I.feat_cap), cm = min(max(nm, 0), T.mp_cap);
+        for (int f = t; f < cf; f += BE_NT) feat_row[f] = -1;
+        for (int m = t; m < cm; m += BE_NT) mp_new_row[m] = -1;
+        if (t < T.kf_cap) dis_out[t] = -1.0;
+        if (t == 0) { O.removed_kf_id[b] = -1; O.removed_kf_row[b] = -1; O.status[b] = st; }
+    };
+    if (nk < 0 || nk > T.kf_cap || nm < 0 || nm > T.mp_cap || no < 0 || no > T.obs_cap || nf < 0 || nf > I.feat_cap || np < 0 || np > I.prior_cap ||
+        nx < 0 || nx > I.outlier_cap || I.window < 1) {                     // uniform
+        refuse(MYSLAM_ERR_INVALID);
+        return;
+    }
+    int64_t* kf_id = T.kf_id + (size_t)b * T.kf_cap;
+    double* kf_pose = T.kf_pose + (size_t)b * T.kf_cap * 7;
+    int64_t* mp_id = T.mp_id + (size_t)b * T.mp_cap;
+    double* mp_pos = T.mp_pos + (size_t)b * T.mp_cap * 3;
+    uint8_t* mp_outlier = T.mp_outlier + (size_t)b * T.mp_cap;
+    int32_t* obs_mp = T.obs_mp + (size_t)b * T.obs_cap;
+    int32_t* obs_kf = T.obs_kf + (size_t)b * T.obs_cap;
+    uint8_t* obs_flags = T.obs_flags + (size_t)b * T.obs_cap;
+    float* obs_uv = T.obs_uv + (size_t)b * T.obs_cap * 2;
+    int32_t* obs_tag = T.obs_tag + (size_t)b * T.obs_cap;
+    const int64_t new_id = I.new_kf_id[b];
+    const double* new_pose = I.new_kf_pose + (size_t)b * 7;
+    const int64_t* fid = I.feat_mp_id + (size_t)b * I.feat_cap;
+    const double* fpos = I.feat_mp_pos + (size_t)b * I.feat_cap * 3;
+    const float* fuv = I.feat_uv + (size_t)b * I.feat_cap * 2;
+    const int32_t* ftag = I.feat_tag + (size_t)b * I.feat_cap;
+    const uint8_t* fflags = I.feat_flags + (size_t)b * I.feat_cap;
+    const int64_t* pid = np ? I.prior_mp_id + (size_t)b * I.prior_cap : nullptr;
+    const int64_t* pkf = np ? I.prior_kf_id + (size_t)b * I.prior_cap : nullptr;
+    const float* puv = np ? I.prior_uv + (size_t)b * I.prior_cap * 2 : nullptr;
+    const int32_t* ptag = np ? I.prior_tag + (size_t)b * I.prior_cap : nullptr;
+    const uint8_t* pflags = np ? I.prior_flags + (size_t)b * I.prior_cap : nullptr;
+    const int64_t* xid = nx ? I.outlier_mp_id + (size_t)b * I.outlier_cap : nullptr;
+    int64_t* c_mp_id = W.mp_id + (size_t)b * T.mp_cap;
+    double* c_mp_pos = W.mp_pos + (size_t)b * T.mp_cap * 3;
+    uint8_t* c_mp_outlier = W.mp_outlier + (size_t)b * T.mp_cap;
+    int32_t* c_obs_mp = W.obs_mp + (size_t)b * T.obs_cap;
+    int32_t* c_obs_kf = W.obs_kf + (size_t)b * T.obs_cap;
+    uint8_t* c_obs_flags = W.obs_flags + (size_t)b * T.obs_cap;
+    float* c_obs_uv = W.obs_uv + (size_t)b * T.obs_cap * 2;
+    int32_t* c_obs_tag = W.obs_tag + (size_t)b * T.obs_cap;
+    int64_t* vid = W.vid + (size_t)b * T.obs_cap;
+    int32_t* vft = W.vft + (size_t)b * T.obs_cap;
+    int64_t* sid = W.sid + (size_t)b * T.obs_cap;
+    int32_t* sfeat = W.sfeat + (size_t)b * T.obs_cap;
+    int32_t* dcum = W.dcum + (size_t)b * (T.obs_cap + 1);
+    int32_t* pcum = W.pcum + (size_t)b * (T.obs_cap + 1);
+    int32_t* dmp = W.dmp + (size_t)b * (T.mp_cap + 1);
+    int32_t* drows = W.drows + (size_t)b * (T.mp_cap + 1);
+    int32_t* mp_fin = W.mp_fin + (size_t)b * T.mp_cap;
+    int32_t* mp_shift = W.mp_shift + (size_t)b * T.mp_cap;
+
+    // ---- validation, and the copy the tables are rebuilt from ----
+    if (t == 0) { s_bad = 0; s_victim = -1; }
+    if (t <= nk) s_kfid[t] = t < nk ? kf_id[t] : new_id;
+    __syncthreads();
+    bool bad = false;
+    for (int i = t + 1; i < nk; i += BE_NT) bad |= kf_id[i - 1] >= kf_id[i];
+    if (t == 0 && nk > 0) bad |= new_id <= kf_id[nk - 1];                   // mnKFId comes from a counter (keyframe.cpp:24)
+    for (int r = t; r < no; r += BE_NT) {
+        const int m = obs_mp[r], k = obs_kf[r];
+        const uint8_t fl = obs_flags[r];
+        bad |= m < 0 || m >= nm || (r > 0 && obs_mp[r - 1] > m) || k < -1 || k >= nk;
+        bad |= (fl & BE_ACTIVE) && k < 0;
+        c_obs_mp[r] = m; c_obs_kf[r] = k; c_obs_flags[r] = fl; c_obs_uv[2 * r] = obs_uv[2 * r]; c_obs_uv[2 * r + 1] = obs_uv[2 * r + 1];
+        c_obs_tag[r] = obs_tag[r];
+    }
+    for (int m = t; m < nm; m += BE_NT) {
+        bad |= m > 0 && mp_id[m - 1] >= mp_id[m];
+        c_mp_id[m] = mp_id[m]; c_mp_outlier[m] = mp_outlier[m];
+        c_mp_pos[3 * m] = mp_pos[3 * m]; c_mp_pos[3 * m + 1] = mp_pos[3 * m + 1]; c_mp_pos[3 * m + 2] = mp_pos[3 * m + 2];
+    }
+    for (int f = t; f < nf; f += BE_NT) bad |= fid[f] < -1 || (fflags[f] & ~BE_OUTLIER);
+    for (int p = t; p < np; p += BE_NT) bad |= (p > 0 && pid[p - 1] > pid[p]) || (pflags[p] & ~BE_OUTLIER);          // ACTIVE is one of the other bits
+    if (bad) s_bad = 1;
+    __syncthreads();
+    if (s_bad) { refuse(MYSLAM_ERR_INVALID); return; }
+
+    // ---- Map::AddOutlierMapPoint (map.cpp:159-164) on the copy: ids that are not in the table are ignored ----
+    for (int j = t; j < nx; j += BE_NT) {
+        const int m = be_lower64(c_mp_id, nm, xid[j]);
+        if (m < nm && c_mp_id[m] == xid[j]) c_mp_outlier[m] = 1;
+    }
+
+    // ---- the features that name a map point, sorted by (id, feature index): the rows AddObservation / AddActiveObservation push back ----
+    int nv = 0;
+    for (int base = 0; base < nf; base += BE_NT) {
+        const int f = base + t;
+        const bool v = f < nf && fid[f] >= 0;
+        int tot;
+        const int k = nv + be_block_rank(v, s_w, tot);
+        if (v) { vid[k] = fid[f]; vft[k] = f; }
+        nv += tot;
+    }
+    __syncthreads();
+    for (int k = t; k < nv; k += BE_NT) {
+        const int64_t id = vid[k];
+        int r = 0;
+        for (int j = 0; j < nv; j++) { const int64_t o = vid[j]; r += (o < id || (o == id && j < k)) ? 1 : 0; }
+        sid[r] = id; sfeat[r] = vft[k];
+    }
+    __syncthreads();
+    int nu = 0;                                                             // distinct ids that are not in the table: InsertActiveMapPoint adds a row
+    for (int base = 0; base < nv; base += BE_NT) {
+        const int s = base + t;
+        bool fn = false;
+        if (s < nv && (s == 0 || sid[s - 1] != sid[s])) {
+            const int m = be_lower64(c_mp_id, nm, sid[s]);
+            fn = !(m < nm && c_mp_id[m] == sid[s]);
+        }
+        int tot;
+        const int k = nu + be_block_rank(fn, s_w, tot);
+        if (s < nv) dcum[s] = k;
+        nu += tot;
+    }
+    if (t == 0) dcum[nv] = nu;
+    int npu = 0;                                                            // prior rows of those ids
+    for (int base = 0; base < np; base += BE_NT) {
+        const int p = base + t;
+        bool u = false;
+        if (p < np) {
+            const int64_t id = pid[p];
+            const int m = be_lower64(c_mp_id, nm, id), g = be_lower64(sid, nv, id);
+            u = g < nv && sid[g] == id && !(m < nm && c_mp_id[m] == id);
+        }
+        int tot;
+        const int k = npu + be_block_rank(u, s_w, tot);
+        if (p < np) pcum[p] = k;
+        npu += tot;
+    }
+    if (t == 0) pcum[np] = npu;
+    if (nk + 1 > T.kf_cap || nm + nu > T.mp_cap || no + nv + npu > T.obs_cap) { refuse(MYSLAM_ERR_CAPACITY); return; }          // uniform
+
+    // ---- RemoveOldActiveKeyframe's choice (map.cpp:83-107) ----
+    const bool removal = nk + 1 > I.window;                                 // map.cpp:44
+    if (removal && t < nk) {
+        double d[6];
+        pg_log(pg_mul(pg_load(kf_pose + 7 * t), pg_inv(pg_load(new_pose))), d);
+        double s = 0;
+        for (int k = 0; k < 6; k++) s += d[k] * d[k];
+        s_dis[t] = sqrt(s);
+    }
+    __syncthreads();
+    if (removal && t == 0) {
+        double maxDis = 0, minDis = 9999;
+        long long maxId = 0, minId = 0;
+        for (int i = 0; i < nk; i++) {
+            const double d = s_dis[i];
+            if (d > maxDis) { maxDis = d; maxId = s_kfid[i]; }
+            else if (d < minDis) { minDis = d; minId = s_kfid[i]; }
+        }
+        const long long gone = minDis < I.min_dis_th ? minId : maxId;
+        int v = -1;
+        for (int i = 0; i < nk; i++) v = s_kfid[i] == gone ? i : v;         // .at(): an id that is no key-frame of the table throws
+        s_victim = v;
+    }
+    __syncthreads();
+    const int victim = s_victim;
+    if (removal && victim < 0) { refuse(MYSLAM_ERR_INVALID); return; }
+
+    // ---- RemoveOldActiveMapPoints (map.cpp:126-140): an input map point no feature names and whose ACTIVE rows were all the victim's ----
+    int ndm = 0, ndr = 0;
+    for (int base = 0; base < nm; base += BE_NT) {
+        const int m = base + t;
+        bool dead = false;
+        int len = 0, g = 0;
+        if (m < nm) {
+            const int64_t id = c_mp_id[m];
+            g = be_lower64(sid, nv, id);
+            if (removal && !(g < nv && sid[g] == id)) {
+                const int s0 = be_lower(c_obs_mp, no, m), e0 = be_lower(c_obs_mp, no, m + 1);
+                bool act = false;
+                for (int r = s0; r < e0; r++) act |= (c_obs_flags[r] & BE_ACTIVE) && c_obs_kf[r] != victim;
+                dead = !act; len = e0 - s0;
+            }
+        }
+        int tot, rtot;
+        const int dm = ndm + be_block_rank(dead, s_w, tot);
+        const int dr = ndr + be_block_exsum(dead ? len : 0, s_w, rtot);
+        if (m < nm) {
+            dmp[m] = dm; drows[m] = dr;
+            mp_fin[m] = dead ? -1 : m + dcum[g] - dm;
+            mp_shift[m] = g + pcum[be_lower64(pid, np, c_mp_id[m])] - dr;
+        }
+        ndm += tot; ndr += rtot;
+    }
+    if (t == 0) { dmp[nm] = ndm; drows[nm] = ndr; }
+
+    // ---- the key-frame table: the victim's row leaves, the new row is the last ----
+    long long kid = 0;
+    double kp[7];
+    if (t <= nk) {
+        kid = s_kfid[t];
+        const double* src = t < nk ? kf_pose + 7 * t : new_pose;
+        for (int k = 0; k < 7; k++) kp[k] = src[k];
+    }
+    __syncthreads();                                                        // everything above is decided and stored; from here on the tables are written
+    if (t <= nk && t != victim) {
+        const int dst = t - ((removal && t > victim) ? 1 : 0);
+        kf_id[dst] = kid;
+        for (int k = 0; k < 7; k++) kf_pose[7 * dst + k] = kp[k];
+    }
+    const int new_kf_row = removal ? nk - 1 : nk;
+    auto kf_row_after = [&](int k) { return !removal || k < victim ? k : (k == victim ? -1 : k - 1); };
+
+    // ---- map points: the input rows that stay, then the new ids (position from the first feature naming them) ----
+    for (int m = t; m < nm; m += BE_NT) {
+        const int dst = mp_fin[m];
+        mp_new_row[m] = dst;
+        if (dst >= 0 && dst < T.mp_cap) {
+            mp_id[dst] = c_mp_id[m]; mp_outlier[dst] = c_mp_outlier[m];
+            mp_pos[3 * dst] = c_mp_pos[3 * m]; mp_pos[3 * dst + 1] = c_mp_pos[3 * m + 1]; mp_pos[3 * dst + 2] = c_mp_pos[3 * m + 2];
+        }
+    }
+    for (int f = t; f < nf; f += BE_NT) if (fid[f] < 0) feat_row[f] = -1;
+    for (int s = t; s < nv; s += BE_NT) {
+        const int64_t id = sid[s];
+        const int f = sfeat[s];
+        const int lm = be_lower64(c_mp_id, nm, id), g = be_lower64(sid, nv, id);
+        const bool in_table = lm < nm && c_mp_id[lm] == id;
+        const int um = lm + (in_table ? 1 : 0);
+        const int mrow = lm + dcum[g] - dmp[lm];
+        if (!in_table && g == s && (unsigned)mrow < (unsigned)T.mp_cap) {
+            mp_id[mrow] = id; mp_outlier[mrow] = 0;
+            mp_pos[3 * mrow] = fpos[3 * f]; mp_pos[3 * mrow + 1] = fpos[3 * f + 1]; mp_pos[3 * mrow + 2] = fpos[3 * f + 2];
+        }
+        // the feature's row: behind the segment's old rows (or its prior rows), in feature order
+        const int dst = be_lower(c_obs_mp, no, um) + pcum[be_upper64(pid, np, id)] + s - drows[um];
+        if ((unsigned)dst >= (unsigned)T.obs_cap) continue;            // cannot happen: the merged count passed the capacity check
+        obs_mp[dst] = mrow; obs_kf[dst] = new_kf_row; obs_flags[dst] = (uint8_t)(BE_ACTIVE | (fflags[f] & BE_OUTLIER));
+        obs_uv[2 * dst] = fuv[2 * f]; obs_uv[2 * dst + 1] = fuv[2 * f + 1]; obs_tag[dst] = ftag[f];
+        feat_row[f] = dst;
+    }
+    // ---- the input observation rows: RemoveActiveObservation on the victim's, key-frame rows renumbered ----
+    for (int r = t; r < no; r += BE_NT) {
+        const int m = c_obs_mp[r], mrow = mp_fin[m];
+        if (mrow < 0) continue;
+        const int dst = r + mp_shift[m], k = c_obs_kf[r];
+        if ((unsigned)dst >= (unsigned)T.obs_cap) continue;
+        uint8_t fl = c_obs_flags[r];
+        if (removal && k == victim) fl &= (uint8_t)~BE_ACTIVE;
+        obs_mp[dst] = mrow; obs_kf[dst] = k < 0 ? -1 : kf_row_after(k); obs_flags[dst] = fl;
+        obs_uv[2 * dst] = c_obs_uv[2 * r]; obs_uv[2 * dst + 1] = c_obs_uv[2 * r + 1]; obs_tag[dst] = c_obs_tag[r];
+    }
+    // ---- GetObservations() of a map point that comes back: never ACTIVE, key-frame resolved against the final table ----
+    for (int p = t; p < np; p += BE_NT) {
+        if (pcum[p + 1] == pcum[p]) continue;
+        const int64_t id = pid[p];
+        const int lm = be_lower64(c_mp_id, nm, id), g = be_lower64(sid, nv, id);
+        const int dst = be_lower(c_obs_mp, no, lm) + g + pcum[p] - drows[lm];
+        if ((unsigned)dst >= (unsigned)T.obs_cap) continue;
+        int k = -1;
+        for (int i = 0; i <= nk; i++) k = s_kfid[i] == pkf[p] ? i : k;
+        obs_mp[dst] = lm + dcum[g] - dmp[lm]; obs_kf[dst] = k < 0 ? -1 : (k == nk ? new_kf_row : kf_row_after(k)); obs_flags[dst] = pflags[p];
+        obs_uv[2 * dst] = puv[2 * p]; obs_uv[2 * dst + 1] = puv[2 * p + 1]; obs_tag[dst] = ptag[p];
+    }
+    if (t < T.kf_cap) dis_out[t] = (removal && t < nk) ? s_dis[t] : -1.0;
+    if (t == 0) {
+        T.n_kf[b] = new_kf_row + 1; T.n_mp[b] = nm + nu - ndm; T.n_obs[b] = no + nv + npu - ndr;
+        O.removed_kf_id[b] = removal ? (int64_t)s_kfid[victim] : -1; O.removed_kf_row[b] = victim; O.status[b] = MYSLAM_OK;
+    }
+}
+
 }  // namespace myslam_hip
 
 using namespace myslam_hip;
@@ -276,8 +623,18 @@ struct myslam_backend {
     Buf<double> poses, pts, obs, scratch, chi2;
     Buf<int32_t> ep, el, sizes, pt_src, edge_src, eidx, mp_slot, mp_new, st, rounds, nout, solve_st;
     Buf<uint8_t> fixed, out;
+    // myslam_backend_insert_keyframe_batch: the copy the tables are rebuilt from, and its index arrays
+    Buf<int64_t> in_mp_id, in_vid, in_sid;
+    Buf<double> in_mp_pos;
+    Buf<float> in_obs_uv;
+    Buf<uint8_t> in_mp_outlier, in_obs_flags;
+    Buf<int32_t> in_obs_mp, in_obs_kf, in_obs_tag, in_vft, in_sfeat, in_dcum, in_pcum, in_dmp, in_drows, in_mp_fin, in_mp_shift;
     BeWork work() const {
         return BeWork{poses, pts, ep, el, obs, fixed, sizes, pt_src, edge_src, eidx, mp_slot, mp_new, st, chi2, out, rounds, nout, solve_st};
+    }
+    InsWork insert_work() const {
+        return InsWork{in_mp_id, in_mp_pos, in_mp_outlier, in_obs_mp, in_obs_kf, in_obs_flags, in_obs_uv, in_obs_tag, in_vid, in_vft, in_sid, in_sfeat,
+                       in_dcum, in_pcum, in_dmp, in_drows, in_mp_fin, in_mp_shift};
     }
 };
 
@@ -307,7 +664,13 @@ int myslam_backend_create(myslam_backend** out, int max_batch, int kf_cap, int m
         (rc = h->el.renew(B * N, oom)) || (rc = h->sizes.renew(B * 3, oom)) || (rc = h->pt_src.renew(B * M, oom)) ||
         (rc = h->edge_src.renew(B * N, oom)) || (rc = h->eidx.renew(B * (N + 1), oom)) || (rc = h->mp_slot.renew(B * M, oom)) ||
         (rc = h->mp_new.renew(B * M, oom)) || (rc = h->st.renew(B, oom)) || (rc = h->rounds.renew(B, oom)) || (rc = h->nout.renew(B, oom)) ||
-        (rc = h->solve_st.renew(B, oom)) || (rc = h->fixed.renew(B * M, oom)) || (rc = h->out.renew(B * N, oom))) {
+        (rc = h->solve_st.renew(B, oom)) || (rc = h->fixed.renew(B * M, oom)) || (rc = h->out.renew(B * N, oom)) ||
+        (rc = h->in_mp_id.renew(B * M, oom)) || (rc = h->in_mp_pos.renew(B * M * 3, oom)) || (rc = h->in_mp_outlier.renew(B * M, oom)) ||
+        (rc = h->in_obs_mp.renew(B * N, oom)) || (rc = h->in_obs_kf.renew(B * N, oom)) || (rc = h->in_obs_flags.renew(B * N, oom)) ||
+        (rc = h->in_obs_uv.renew(B * N * 2, oom)) || (rc = h->in_obs_tag.renew(B * N, oom)) || (rc = h->in_vid.renew(B * N, oom)) ||
+        (rc = h->in_vft.renew(B * N, oom)) || (rc = h->in_sid.renew(B * N, oom)) || (rc = h->in_sfeat.renew(B * N, oom)) ||
+        (rc = h->in_dcum.renew(B * (N + 1), oom)) || (rc = h->in_pcum.renew(B * (N + 1), oom)) || (rc = h->in_dmp.renew(B * (M + 1), oom)) ||
+        (rc = h->in_drows.renew(B * (M + 1), oom)) || (rc = h->in_mp_fin.renew(B * M, oom)) || (rc = h->in_mp_shift.renew(B * M, oom))) {
         delete h;
         return rc;
     }
@@ -350,6 +713,38 @@ int myslam_backend_optimize_batch(myslam_backend* h, const int64_t* d_kf_id, dou
                                         W.solve_st, h->stream);
     if (rc) return rc;
     hipLaunchKernelGGL(k_backend_write_back, dim3(batch), dim3(BE_NT), 0, h->stream, T, W, O);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    return MYSLAM_OK;
+}
+
+int myslam_backend_insert_launches_per_call(const myslam_backend* h) { return h ? 1 : MYSLAM_ERR_INVALID; }
+
+int myslam_backend_insert_keyframe_batch(myslam_backend* h, int64_t* d_kf_id, double* d_kf_pose, int32_t* d_n_kf, int64_t* d_mp_id, double* d_mp_pos,
+                                         uint8_t* d_mp_outlier, int32_t* d_n_mp, int32_t* d_obs_mp, int32_t* d_obs_kf, uint8_t* d_obs_flags,
+                                         float* d_obs_uv, int32_t* d_obs_tag, int32_t* d_n_obs, const int64_t* d_new_kf_id, const double* d_new_kf_pose,
+                                         const int64_t* d_feat_mp_id, const double* d_feat_mp_pos, const float* d_feat_uv, const int32_t* d_feat_tag,
+                                         const uint8_t* d_feat_flags, const int32_t* d_n_feat, int feat_cap, const int64_t* d_prior_mp_id,
+                                         const int64_t* d_prior_kf_id, const float* d_prior_uv, const int32_t* d_prior_tag, const uint8_t* d_prior_flags,
+                                         const int32_t* d_n_prior, int prior_cap, const int64_t* d_outlier_mp_id, const int32_t* d_n_outlier_mp,
+                                         int outlier_cap, int batch, int window, double min_dis_th, int32_t* d_feat_row, int32_t* d_mp_new_row,
+                                         int64_t* d_removed_kf_id, int32_t* d_removed_kf_row, double* d_dis, int32_t* d_status) {
+    if (!h || batch < 0 || feat_cap < 0) return MYSLAM_ERR_INVALID;
+    if (!d_kf_id || !d_kf_pose || !d_n_kf || !d_mp_id || !d_mp_pos || !d_mp_outlier || !d_n_mp || !d_obs_mp || !d_obs_kf || !d_obs_flags || !d_obs_uv ||
+        !d_obs_tag || !d_n_obs || !d_new_kf_id || !d_new_kf_pose || !d_feat_mp_id || !d_feat_mp_pos || !d_feat_uv || !d_feat_tag || !d_feat_flags ||
+        !d_n_feat || !d_feat_row || !d_mp_new_row || !d_removed_kf_id || !d_removed_kf_row || !d_dis || !d_status)
+        return MYSLAM_ERR_INVALID;
+    // the optional inputs are given by their counts: with a count array, its tables are required
+    if (d_n_prior && (prior_cap < 0 || !d_prior_mp_id || !d_prior_kf_id || !d_prior_uv || !d_prior_tag || !d_prior_flags)) return MYSLAM_ERR_INVALID;
+    if (d_n_outlier_mp && (outlier_cap < 0 || !d_outlier_mp_id)) return MYSLAM_ERR_INVALID;
+    if (batch > h->max_batch || feat_cap > h->obs_cap || (d_n_prior && prior_cap > h->obs_cap)) return MYSLAM_ERR_CAPACITY;
+    if (batch == 0) return MYSLAM_OK;
+    const InsTables T{d_kf_id, d_kf_pose, d_n_kf, d_mp_id, d_mp_pos, d_mp_outlier, d_n_mp, d_obs_mp, d_obs_kf, d_obs_flags, d_obs_uv, d_obs_tag, d_n_obs,
+                      h->kf_cap, h->mp_cap, h->obs_cap};
+    const InsIn I{d_new_kf_id, d_new_kf_pose, d_feat_mp_id, d_feat_mp_pos, d_feat_uv, d_feat_tag, d_feat_flags, d_n_feat, feat_cap,
+                  d_prior_mp_id, d_prior_kf_id, d_prior_uv, d_prior_tag, d_prior_flags, d_n_prior, d_n_prior ? prior_cap : 0,
+                  d_outlier_mp_id, d_n_outlier_mp, d_n_outlier_mp ? outlier_cap : 0, window, min_dis_th};
+    const InsOut O{d_feat_row, d_mp_new_row, d_removed_kf_id, d_removed_kf_row, d_dis, d_status};
+    hipLaunchKernelGGL(k_backend_insert, dim3(batch), dim3(BE_NT), 0, h->stream, T, I, h->insert_work(), O);
     MYSLAM_HIP_CHECK(hipGetLastError());
     return MYSLAM_OK;
 }

@@ -568,6 +568,26 @@ public:
                                             d_newOutlierMP, d_nNewOutlierMP, d_obsChi2, d_rounds, d_nOutlierEdges, d_status),
               "myslam_backend_optimize_batch");
     }
+    // Map::InsertKeyFrame (src/map.cpp:17-48, :78-140) per item on the same tables, all in/out (myslam_backend_insert_keyframe_batch): the new
+    // key-frame's features as device arrays of featCap rows per item, optionally (nullptr counts = none) the observations a re-entering map point already
+    // has and the ids given to Map::AddOutlierMapPoint.  One launch on the handle's stream; status[b] = 0 or a negative error.
+    int InsertLaunchesPerCall() const { return myslam_backend_insert_launches_per_call(h_); }
+    void InsertKeyFrameBatch(int64_t* d_kfId, double* d_kfPose, int32_t* d_nKF, int64_t* d_mpId, double* d_mpPos, uint8_t* d_mpOutlier, int32_t* d_nMP,
+                             int32_t* d_obsMP, int32_t* d_obsKF, uint8_t* d_obsFlags, float* d_obsUV, int32_t* d_obsTag, int32_t* d_nObs,
+                             const int64_t* d_newKFId, const double* d_newKFPose, const int64_t* d_featMPId, const double* d_featMPPos,
+                             const float* d_featUV, const int32_t* d_featTag, const uint8_t* d_featFlags, const int32_t* d_nFeat, int featCap,
+                             const int64_t* d_priorMPId, const int64_t* d_priorKFId, const float* d_priorUV, const int32_t* d_priorTag,
+                             const uint8_t* d_priorFlags, const int32_t* d_nPrior, int priorCap, const int64_t* d_outlierMPId,
+                             const int32_t* d_nOutlierMP, int outlierCap, int batch, int window /* Map.activeMap.size */, int32_t* d_featRow,
+                             int32_t* d_mpNewRow, int64_t* d_removedKFId, int32_t* d_removedKFRow, double* d_dis, int32_t* d_status,
+                             double minDisTh = 0.2 /* map.cpp:101 */) {
+        check(myslam_backend_insert_keyframe_batch(h_, d_kfId, d_kfPose, d_nKF, d_mpId, d_mpPos, d_mpOutlier, d_nMP, d_obsMP, d_obsKF, d_obsFlags, d_obsUV,
+                                                   d_obsTag, d_nObs, d_newKFId, d_newKFPose, d_featMPId, d_featMPPos, d_featUV, d_featTag, d_featFlags,
+                                                   d_nFeat, featCap, d_priorMPId, d_priorKFId, d_priorUV, d_priorTag, d_priorFlags, d_nPrior, priorCap,
+                                                   d_outlierMPId, d_nOutlierMP, outlierCap, batch, window, minDisTh, d_featRow, d_mpNewRow, d_removedKFId,
+                                                   d_removedKFRow, d_dis, d_status),
+              "myslam_backend_insert_keyframe_batch");
+    }
     // the flat window of one item as the last call built it (host arrays of kfCap / mpCap / obsCap elements, any but sizes3 may be nullptr)
     void DebugFlat(int item, int32_t* poseSrc, int32_t* ptSrc, int32_t* edgePose, int32_t* edgePt, double* edgeObs, int32_t* edgeSrc, uint8_t* fixed,
                    int32_t* sizes3) {

@@ -998,8 +998,8 @@ int myslam_loop_correct_structure(int n_kf, const int32_t* active, int n_active,
  *   d_mp_report   batch x mp_cap u8    0 kept, 1 left the active set, 2 erased as an outlier
  *   d_obs_chi2    batch x obs_cap f64  the edge's chi2 (edge->chi2(), :237), -1 for a row that was not an edge
  *   d_rounds / d_n_outlier_edges  batch i32   the *rounds / *n_outliers of myslam_ba_optimize_active_map;   d_status  batch i32
- * An item's bytes depend neither on its slot in the batch nor on its neighbours.  Out of this call's scope: Map::InsertKeyFrame /
- * RemoveOldActiveKeyframe (the caller sets d_obs_kf = -1 and clears ACTIVE on the rows of a key-frame that leaves).
+ * An item's bytes depend neither on its slot in the batch nor on its neighbours.  Map::InsertKeyFrame / RemoveOldActiveKeyframe on
+ * the same tables is myslam_backend_insert_keyframe_batch, below (it sets d_obs_kf = -1 and clears ACTIVE on the rows of a key-frame that leaves).
  * Call level, nothing enqueued: NULL pointers, batch < 0, max_rounds / iters_per_round < 1 -> MYSLAM_ERR_INVALID; batch beyond the handle's ->
  * MYSLAM_ERR_CAPACITY.
  * ------------------------------------------------------------------------------------------ */
@@ -1030,6 +1030,61 @@ int myslam_backend_debug_flat(myslam_backend* h, int item, int32_t* pose_src, in
  * rounds_outliers2 = (*rounds, *n_outliers).  Host pointers, any may be NULL.  Synchronises. */
 int myslam_backend_debug_solved(myslam_backend* h, int item, double* poses, double* points, double* edge_chi2, uint8_t* edge_outlier,
                                 int32_t* rounds_outliers2);
+/* Map::InsertKeyFrame (src/map.cpp:17-48) with KeyFrame::CreateKF's observation loop (src/keyframe.cpp:34-50), RemoveOldActiveKeyframe (:78-120),
+ * RemoveOldActiveMapPoints (:126-140), Map::AddOutlierMapPoint (:159-164) and MapPoint::AddObservation / AddActiveObservation /
+ * RemoveActiveObservation (src/mappoint.cpp:19-44) for a batch of maps held in the tables of myslam_backend_optimize_batch: the call that adds a
+ * key-frame to them, so that insert -> optimise -> insert ... runs without the host touching a table.  Same handle, caps and stream (ordered with
+ * optimize_batch); the handle holds a copy of the map-point and observation tables and the index arrays, so the call allocates nothing, never
+ * synchronises, never reads device memory from the host and can be recorded between myslam_graph_begin / _end.  One launch, one workgroup per item
+ * (k_backend_insert), block scans and binary searches, no global atomics; an item's bytes depend neither on its slot nor on its neighbours.  The
+ * features are ranked by (id, index) with a count over all pairs: quadratic in the features of one key-frame (hundreds).
+ * All thirteen tables are in/out here, d_kf_id and d_n_kf included.  The new key-frame of item b:
+ *   d_new_kf_id   batch i64;   d_new_kf_pose  batch x 7 f64 (Tcw)
+ *   d_feat_mp_id  batch x feat_cap i64      mvpFeaturesLeft order; -1 = mpMapPoint.lock() == nullptr
+ *   d_feat_mp_pos batch x feat_cap x 3 f64  read for the first feature naming an id that is not in the table
+ *   d_feat_uv / d_feat_tag / d_feat_flags   batch x feat_cap (x 2 f32 / i32 / u8: only MYSLAM_BACKEND_OBS_OUTLIER may be set);   d_n_feat  batch i32
+ *   optional, d_n_prior == NULL = none: GetObservations() of map points that had left the active set (LoopLocalFusion, src/loopclosing.cpp:521-525),
+ *   d_prior_mp_id non-decreasing, d_prior_kf_id the observer's mnKFId, flags without ACTIVE; batch x prior_cap rows
+ *   optional, d_n_outlier_mp == NULL = none: ids passed to Map::AddOutlierMapPoint since the last call (src/frontend.cpp:263-264); batch x outlier_cap
+ * feat_cap, prior_cap, outlier_cap are strides.  Per item, everything is decided before anything is written:
+ *   0. every id of d_outlier_mp_id that is in the map-point table gets d_mp_outlier = 1; other ids are ignored.
+ *   1. d_new_kf_id must be above the table's last id (mnKFId comes from a counter); the row is appended with its pose.
+ *   2. every feature with an id, in feature order: an id in the table gets one row at the END of its segment (both lists push_back), an outlier map
+ *      point included (the reference does not look at mbIsOutlier here); an id that is not in the table enters it at its sorted position with the
+ *      position of the first feature naming it and d_mp_outlier = 0, its segment starts with that id's prior rows in prior order (d_obs_kf resolved
+ *      against the FINAL key-frame table, -1 if absent, ACTIVE never set), the new key-frame's rows follow.  A new row is d_obs_kf = the new
+ *      key-frame's row, flags = ACTIVE | (d_feat_flags & OUTLIER), the feature's uv and tag.  Prior rows of ids that are in the table or that no
+ *      feature names are ignored.  Two features naming one id give two rows.
+ *   3. if the key-frame count does not exceed `window` (Map.activeMap.size, :44) the call is done: nothing leaves, not even a map point without an
+ *      ACTIVE row.
+ *   4. otherwise (:78-120), for each OTHER key-frame in id order dis = |log(T_kf * T_new^-1)| (d_dis, batch x kf_cap f64 by INPUT row, -1 elsewhere)
+ *      goes through the reference's scan as written: maxDis = 0, minDis = 9999, both ids 0; `if (dis > maxDis) .. else if (dis < minDis) ..`, so a
+ *      distance that raises the maximum is never a candidate for the minimum and ties keep the earlier key-frame.  minDis < min_dis_th (0.2, :101)
+ *      ? minKFId : maxKFId leaves; an id that is none of the other key-frames' (every distance NaN and no key-frame 0: .at() throws) is
+ *      MYSLAM_ERR_INVALID.  The row leaves both key-frame arrays; rows with its d_obs_kf get -1 and ACTIVE cleared (RemoveActiveObservation: the row
+ *      stays in GetObservations()), larger d_obs_kf are renumbered.
+ *   5. then every map point without an ACTIVE row leaves with all its rows (:126-140); both tables are compacted in their order, d_obs_mp is
+ *      renumbered, the counts are stored.  Rows between a new count and the old one keep their bytes.
+ * Reports: d_feat_row (batch x feat_cap i32) the FINAL row of each feature's observation, -1 without a map point: the caller's handle of the feature;
+ * d_mp_new_row (batch x mp_cap i32, by INPUT row) the row after the call, -1 if it left; d_removed_kf_id / d_removed_kf_row (batch i64 / i32, INPUT
+ * row) -1 when none; d_status 0 or an error.  A refused item keeps every byte of its tables; its report rows (as far as its counts reach, d_dis whole)
+ * are -1.  MYSLAM_ERR_INVALID: a count negative or beyond its cap, window < 1, the table checks of myslam_backend_optimize_batch (ids strictly
+ * ascending, d_obs_mp / d_obs_kf in range and d_obs_mp non-decreasing, no ACTIVE row with d_obs_kf < 0), the new id not above the last, a feature id
+ * below -1, prior ids decreasing, a feature or prior flag with a bit other than OUTLIER (so a prior row with ACTIVE).  MYSLAM_ERR_CAPACITY: the
+ * key-frame, merged map-point or merged observation count BEFORE the removal exceeds its cap.
+ * Call level, nothing enqueued: NULL required pointers, batch < 0, a negative stride -> MYSLAM_ERR_INVALID; batch beyond the handle's, feat_cap or
+ * prior_cap beyond obs_cap -> MYSLAM_ERR_CAPACITY. */
+int myslam_backend_insert_keyframe_batch(myslam_backend* h, int64_t* d_kf_id, double* d_kf_pose, int32_t* d_n_kf, int64_t* d_mp_id, double* d_mp_pos,
+                                         uint8_t* d_mp_outlier, int32_t* d_n_mp, int32_t* d_obs_mp, int32_t* d_obs_kf, uint8_t* d_obs_flags,
+                                         float* d_obs_uv, int32_t* d_obs_tag, int32_t* d_n_obs, const int64_t* d_new_kf_id, const double* d_new_kf_pose,
+                                         const int64_t* d_feat_mp_id, const double* d_feat_mp_pos, const float* d_feat_uv, const int32_t* d_feat_tag,
+                                         const uint8_t* d_feat_flags, const int32_t* d_n_feat, int feat_cap, const int64_t* d_prior_mp_id,
+                                         const int64_t* d_prior_kf_id, const float* d_prior_uv, const int32_t* d_prior_tag, const uint8_t* d_prior_flags,
+                                         const int32_t* d_n_prior, int prior_cap, const int64_t* d_outlier_mp_id, const int32_t* d_n_outlier_mp,
+                                         int outlier_cap, int batch, int window, double min_dis_th, int32_t* d_feat_row, int32_t* d_mp_new_row,
+                                         int64_t* d_removed_kf_id, int32_t* d_removed_kf_row, double* d_dis, int32_t* d_status);
+/* launches one myslam_backend_insert_keyframe_batch enqueues (1) */
+int myslam_backend_insert_launches_per_call(const myslam_backend* h);
 
 /* ------------------------------------------------------------------------------------------
  * Host-side formats of the reference's runner — plain host code, no device needed; the C++ forms live in
