@@ -10,6 +10,8 @@
 // no global atomics, and an item's bytes depend neither on its slot nor on its neighbours.  See include/myslam_hip.h for the contract.
 // k_backend_insert is Map::InsertKeyFrame (src/map.cpp:17-48 with KeyFrame::CreateKF's AddObservation loop, RemoveOldActiveKeyframe and
 // RemoveOldActiveMapPoints) on the same tables: one launch, one workgroup per map, the same scans; the tables are rebuilt from a copy the handle holds.
+// Every argument struct is a set of batch arrays strided by the caps; its item(b, ...) is the one place that states each stride and returns the
+// pointers of map b (arrays with one element per map are indexed by b where they are used).  be_tables_bad is the one validation of the tables.
 #include "backend_launch.h"
 #include "pg_shared.h"
 
@@ -18,14 +20,25 @@ namespace myslam_hip {
 constexpr int BE_NT = 512, BE_NW = BE_NT / WAVE;
 constexpr int BE_ACTIVE = MYSLAM_BACKEND_OBS_ACTIVE, BE_OUTLIER = MYSLAM_BACKEND_OBS_OUTLIER;
 
-struct BeTables {                       // the caller's tables, strided by the caps
-    const int64_t* kf_id; double* kf_pose; const int32_t* n_kf;
+template <class KfId, class NKf>
+struct BeTablesT {                      // the caller's tables, strided by the caps
+    KfId* kf_id; double* kf_pose; NKf* n_kf;
     int64_t* mp_id; double* mp_pos; uint8_t* mp_outlier; int32_t* n_mp;
     int32_t* obs_mp; int32_t* obs_kf; uint8_t* obs_flags; float* obs_uv; int32_t* obs_tag; int32_t* n_obs;
     int kf_cap, mp_cap, obs_cap;
+    struct Item {
+        KfId* kf_id; double* kf_pose; int64_t* mp_id; double* mp_pos; uint8_t* mp_outlier;
+        int32_t* obs_mp; int32_t* obs_kf; uint8_t* obs_flags; float* obs_uv; int32_t* obs_tag;
+    };
+    __device__ __forceinline__ Item item(int b) const {
+        const size_t k = (size_t)b * kf_cap, m = (size_t)b * mp_cap, o = (size_t)b * obs_cap;
+        return {kf_id + k, kf_pose + k * 7, mp_id + m, mp_pos + m * 3, mp_outlier + m, obs_mp + o, obs_kf + o, obs_flags + o, obs_uv + o * 2, obs_tag + o};
+    }
 };
+using BeTables = BeTablesT<const int64_t, const int32_t>;      // optimise: key-frames neither come nor go
+using InsTables = BeTablesT<int64_t, int32_t>;                 // insert: all in/out
 
-struct BeWork {                         // the handle's buffers, strided by the same caps
+struct BeWork {                         // the handle's buffers of optimise, strided by the same caps
     double* poses; double* pts; int32_t* ep; int32_t* el; double* obs; uint8_t* fixed; int32_t* sizes;       // the flat windows (k_ba_optimize's arguments)
     int32_t* pt_src; int32_t* edge_src;
     int32_t* eidx;                      // obs_cap + 1 per item: edges before row r; row r is an edge iff eidx[r + 1] > eidx[r]
@@ -33,11 +46,73 @@ struct BeWork {                         // the handle's buffers, strided by the 
     int32_t* mp_new;                    // row of a map point after the compaction, -1 = it left the table
     int32_t* st;                        // the flatten's verdict: 0 = solve this item, else the item's final status (doubles as the solve's skip flag)
     double* chi2; uint8_t* out; int32_t* rounds; int32_t* nout; int32_t* solve_st;
+    struct Item {
+        double* poses; double* pts; int32_t* ep; int32_t* el; double* obs; uint8_t* fixed; int32_t* sizes;
+        int32_t* pt_src; int32_t* edge_src; int32_t* eidx; int32_t* mp_slot; int32_t* mp_new; double* chi2; uint8_t* out;
+    };
+    __device__ __forceinline__ Item item(int b, int kf_cap, int mp_cap, int obs_cap) const {
+        const size_t k = (size_t)b * kf_cap, m = (size_t)b * mp_cap, o = (size_t)b * obs_cap;
+        return {poses + k * 7, pts + m * 3, ep + o, el + o, obs + o * 2, fixed + m, sizes + 3 * (size_t)b,
+                pt_src + m, edge_src + o, eidx + (size_t)b * (obs_cap + 1), mp_slot + m, mp_new + m, chi2 + o, out + o};
+    }
 };
 
 struct BeOut {
     uint8_t* obs_report; uint8_t* mp_report; int32_t* new_outlier_mp; int32_t* n_new_outlier_mp; double* obs_chi2;
     int32_t* rounds; int32_t* n_outlier_edges; int32_t* status;
+    struct Item { uint8_t* obs_report; uint8_t* mp_report; int32_t* new_outlier_mp; double* obs_chi2; };
+    __device__ __forceinline__ Item item(int b, int mp_cap, int obs_cap) const {
+        const size_t m = (size_t)b * mp_cap, o = (size_t)b * obs_cap;
+        return {obs_report + o, mp_report + m, new_outlier_mp + m, obs_chi2 + o};
+    }
+};
+
+struct InsIn {                          // the new key-frame of every item; n_prior / n_outlier NULL = none
+    const int64_t* new_kf_id; const double* new_kf_pose;
+    const int64_t* feat_mp_id; const double* feat_mp_pos; const float* feat_uv; const int32_t* feat_tag; const uint8_t* feat_flags;
+    const int32_t* n_feat; int feat_cap;
+    const int64_t* prior_mp_id; const int64_t* prior_kf_id; const float* prior_uv; const int32_t* prior_tag; const uint8_t* prior_flags;
+    const int32_t* n_prior; int prior_cap;
+    const int64_t* outlier_mp_id; const int32_t* n_outlier; int outlier_cap;
+    int window; double min_dis_th;
+    struct Item {
+        const double* new_pose;
+        const int64_t* fid; const double* fpos; const float* fuv; const int32_t* ftag; const uint8_t* fflags;
+        const int64_t* pid; const int64_t* pkf; const float* puv; const int32_t* ptag; const uint8_t* pflags;
+        const int64_t* xid;
+    };
+    // np, nx: the item's prior and outlier counts; a group whose count is 0 (its arrays may be NULL) is nullptr
+    __device__ __forceinline__ Item item(int b, int np, int nx) const {
+        const size_t f = (size_t)b * feat_cap, p = (size_t)b * prior_cap;
+        return {new_kf_pose + (size_t)b * 7, feat_mp_id + f, feat_mp_pos + f * 3, feat_uv + f * 2, feat_tag + f, feat_flags + f,
+                np ? prior_mp_id + p : nullptr, np ? prior_kf_id + p : nullptr, np ? prior_uv + p * 2 : nullptr, np ? prior_tag + p : nullptr,
+                np ? prior_flags + p : nullptr, nx ? outlier_mp_id + (size_t)b * outlier_cap : nullptr};
+    }
+};
+
+struct InsWork {                        // the handle's staging of insert, strided by the caps
+    int64_t* mp_id; double* mp_pos; uint8_t* mp_outlier;                                         // the tables as they came in (outlier ids applied)
+    int32_t* obs_mp; int32_t* obs_kf; uint8_t* obs_flags; float* obs_uv; int32_t* obs_tag;
+    int64_t* vid; int32_t* vft;         // obs_cap: ids / indices of the features that name a map point, in feature order
+    int64_t* sid; int32_t* sfeat;       // obs_cap: the same sorted by (id, feature index)
+    int32_t* dcum;                      // obs_cap + 1: distinct ids that are new to the table among sorted features before s
+    int32_t* pcum;                      // obs_cap + 1: prior rows that enter the table before prior row p
+    int32_t* dmp; int32_t* drows;       // mp_cap + 1: map points / their rows that leave, before input row m
+    int32_t* mp_fin; int32_t* mp_shift; // mp_cap: final row of an input map point (-1 = it leaves); what its observation rows move by
+    using Item = InsWork;               // the same fields, of one map
+    __device__ __forceinline__ Item item(int b, int mp_cap, int obs_cap) const {
+        const size_t m = (size_t)b * mp_cap, o = (size_t)b * obs_cap, m1 = (size_t)b * (mp_cap + 1), o1 = (size_t)b * (obs_cap + 1);
+        return {mp_id + m, mp_pos + m * 3, mp_outlier + m, obs_mp + o, obs_kf + o, obs_flags + o, obs_uv + o * 2, obs_tag + o,
+                vid + o, vft + o, sid + o, sfeat + o, dcum + o1, pcum + o1, dmp + m1, drows + m1, mp_fin + m, mp_shift + m};
+    }
+};
+
+struct InsOut {
+    int32_t* feat_row; int32_t* mp_new_row; int64_t* removed_kf_id; int32_t* removed_kf_row; double* dis; int32_t* status;
+    struct Item { int32_t* feat_row; int32_t* mp_new_row; double* dis; };
+    __device__ __forceinline__ Item item(int b, int feat_cap, int mp_cap, int kf_cap) const {
+        return {feat_row + (size_t)b * feat_cap, mp_new_row + (size_t)b * mp_cap, dis + (size_t)b * kf_cap};
+    }
 };
 
 // lanes below this one whose bit is set in a ballot mask
@@ -45,26 +120,71 @@ __device__ __forceinline__ int be_lane_prefix(unsigned long long m) {
     return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
 }
 
-// Exclusive position of this thread's flag among the block's flags in thread order, and their number.  Every thread of the block calls it; the two
-// barriers inside also separate what a chunk read before the call from what it writes after it.
-__device__ __forceinline__ int be_block_rank(bool f, int* s_w, int& total) {
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const unsigned long long m = __ballot(f);
-    if (lane == 0) s_w[wv] = __popcll(m);
+// The tail of both block scans: the lane with `publish` stores its wave's total, the block meets, every thread sums the BE_NW totals -> the totals
+// of the waves below this one, and `total` of all.  Every thread of the block calls it; the two barriers inside also separate what a chunk read
+// before the call from what it writes after it.
+__device__ __forceinline__ int be_wave_totals(bool publish, int wave_total, int* s_w, int& total) {
+    const int wv = threadIdx.x >> 6;
+    if (publish) s_w[wv] = wave_total;
     __syncthreads();
     int off = 0, tot = 0;
 #pragma unroll
     for (int i = 0; i < BE_NW; i++) { const int c = s_w[i]; off += i < wv ? c : 0; tot += c; }
     __syncthreads();
     total = tot;
-    return off + be_lane_prefix(m);
+    return off;
 }
 
-// first index in a[0, n) whose value is not below v (a non-decreasing; on any other input the result still lies in [0, n])
-__device__ __forceinline__ int be_lower(const int32_t* a, int n, int v) {
+// exclusive position of this thread's flag among the block's flags in thread order, and their number (be_wave_totals' rules)
+__device__ __forceinline__ int be_block_rank(bool f, int* s_w, int& total) {
+    const unsigned long long m = __ballot(f);
+    return be_wave_totals((threadIdx.x & 63) == 0, __popcll(m), s_w, total) + be_lane_prefix(m);
+}
+
+// exclusive block-wide prefix sum of v in thread order, and the sum (be_wave_totals' rules)
+__device__ __forceinline__ int be_block_exsum(int v, int* s_w, int& total) {
+    const int lane = threadIdx.x & 63;
+    int inc = v;
+#pragma unroll
+    for (int d = 1; d < WAVE; d <<= 1) { const int o = __shfl_up(inc, d); if (lane >= d) inc += o; }
+    return be_wave_totals(lane == WAVE - 1, inc, s_w, total) + inc - v;
+}
+
+// first index in a[0, n) whose value is not below v (UPPER: is above v); a non-decreasing, on any other input the result still lies in [0, n]
+template <class T, bool UPPER = false>
+__device__ __forceinline__ int be_bound(const T* a, int n, T v) {
     int lo = 0, hi = n;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] < v) lo = mid + 1; else hi = mid; }
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (UPPER ? a[mid] <= v : a[mid] < v) lo = mid + 1; else hi = mid; }
     return lo;
+}
+
+// The rules every operator's tables obey, over counts that are within the caps: key-frame ids ascending, row fields in range and grouped by map
+// point, ACTIVE implies a key-frame (the assert of backend.cpp:187), map-point ids ascending.  -> this thread's `bad`; the block ORs them.
+// COPY: the same pass stages the map-point and observation tables in `copy` (a compile-time switch: behind a run-time one the item's pointers
+// live in scratch memory); without it `copy` is not looked at.
+template <bool COPY, class TablesItem>
+__device__ __forceinline__ bool be_tables_bad(const TablesItem& tb, int nk, int nm, int no, const InsWork::Item& copy) {
+    const int t = threadIdx.x;
+    bool bad = false;
+    for (int i = t + 1; i < nk; i += BE_NT) bad |= tb.kf_id[i - 1] >= tb.kf_id[i];
+    for (int r = t; r < no; r += BE_NT) {
+        const int m = tb.obs_mp[r], k = tb.obs_kf[r];
+        const uint8_t fl = tb.obs_flags[r];
+        bad |= m < 0 || m >= nm || (r > 0 && tb.obs_mp[r - 1] > m) || k < -1 || k >= nk;
+        bad |= (fl & BE_ACTIVE) && k < 0;
+        if (COPY) {
+            copy.obs_mp[r] = m; copy.obs_kf[r] = k; copy.obs_flags[r] = fl;
+            copy.obs_uv[2 * r] = tb.obs_uv[2 * r]; copy.obs_uv[2 * r + 1] = tb.obs_uv[2 * r + 1]; copy.obs_tag[r] = tb.obs_tag[r];
+        }
+    }
+    for (int m = t; m < nm; m += BE_NT) {
+        bad |= m > 0 && tb.mp_id[m - 1] >= tb.mp_id[m];
+        if (COPY) {
+            copy.mp_id[m] = tb.mp_id[m]; copy.mp_outlier[m] = tb.mp_outlier[m];
+            copy.mp_pos[3 * m] = tb.mp_pos[3 * m]; copy.mp_pos[3 * m + 1] = tb.mp_pos[3 * m + 1]; copy.mp_pos[3 * m + 2] = tb.mp_pos[3 * m + 2];
+        }
+    }
+    return bad;
 }
 
 __global__ __launch_bounds__(BE_NT) void k_backend_flatten(BeTables T, BeWork W) {
@@ -72,75 +192,43 @@ __global__ __launch_bounds__(BE_NT) void k_backend_flatten(BeTables T, BeWork W)
     __shared__ int s_bad;
     const int b = blockIdx.x, t = threadIdx.x;
     const int nk = T.n_kf[b], nm = T.n_mp[b], no = T.n_obs[b];
-    int32_t* sizes = W.sizes + 3 * (size_t)b;
-    if (nk < 0 || nk > T.kf_cap || nm < 0 || nm > T.mp_cap || no < 0 || no > T.obs_cap) {        // uniform
-        if (t == 0) { W.st[b] = MYSLAM_ERR_INVALID; sizes[0] = 0; sizes[1] = 0; sizes[2] = 0; }
-        return;
-    }
-    const int64_t* kf_id = T.kf_id + (size_t)b * T.kf_cap;
-    const double* kf_pose = T.kf_pose + (size_t)b * T.kf_cap * 7;
-    const int64_t* mp_id = T.mp_id + (size_t)b * T.mp_cap;
-    const double* mp_pos = T.mp_pos + (size_t)b * T.mp_cap * 3;
-    const uint8_t* mp_outlier = T.mp_outlier + (size_t)b * T.mp_cap;
-    const int32_t* obs_mp = T.obs_mp + (size_t)b * T.obs_cap;
-    const int32_t* obs_kf = T.obs_kf + (size_t)b * T.obs_cap;
-    const uint8_t* obs_flags = T.obs_flags + (size_t)b * T.obs_cap;
-    const float* obs_uv = T.obs_uv + (size_t)b * T.obs_cap * 2;
-    double* f_poses = W.poses + (size_t)b * T.kf_cap * 7;
-    double* f_pts = W.pts + (size_t)b * T.mp_cap * 3;
-    int32_t* f_ep = W.ep + (size_t)b * T.obs_cap;
-    int32_t* f_el = W.el + (size_t)b * T.obs_cap;
-    double* f_obs = W.obs + (size_t)b * T.obs_cap * 2;
-    uint8_t* f_fixed = W.fixed + (size_t)b * T.mp_cap;
-    int32_t* pt_src = W.pt_src + (size_t)b * T.mp_cap;
-    int32_t* edge_src = W.edge_src + (size_t)b * T.obs_cap;
-    int32_t* eidx = W.eidx + (size_t)b * (T.obs_cap + 1);
-    int32_t* mp_slot = W.mp_slot + (size_t)b * T.mp_cap;
+    const auto w = W.item(b, T.kf_cap, T.mp_cap, T.obs_cap);
+    auto refuse = [&](int st) {                                             // nothing to solve: the item's final status, an empty window
+        if (t == 0) { W.st[b] = st; w.sizes[0] = 0; w.sizes[1] = 0; w.sizes[2] = 0; }
+    };
+    if (nk < 0 || nk > T.kf_cap || nm < 0 || nm > T.mp_cap || no < 0 || no > T.obs_cap) { refuse(MYSLAM_ERR_INVALID); return; }      // uniform
+    const auto tb = T.item(b);
 
     // ---- validation ----
     if (t == 0) s_bad = 0;
     __syncthreads();
-    bool bad = false;
-    for (int i = t + 1; i < nk; i += BE_NT) bad |= kf_id[i - 1] >= kf_id[i];
-    for (int r = t; r < no; r += BE_NT) {
-        const int m = obs_mp[r], k = obs_kf[r];
-        bad |= m < 0 || m >= nm || (r > 0 && obs_mp[r - 1] > m) || k < -1 || k >= nk;
-        bad |= (obs_flags[r] & BE_ACTIVE) && k < 0;                         // the assert of :187
-    }
-    for (int m = t; m < nm; m += BE_NT) {
-        bad |= m > 0 && mp_id[m - 1] >= mp_id[m];
-        if (!mp_outlier[m]) {                                               // an active map point without observations (:175 would dereference front())
-            const int s = be_lower(obs_mp, no, m);
-            bad |= s >= no || obs_mp[s] != m;
+    bool bad = be_tables_bad<false>(tb, nk, nm, no, InsWork::Item{});
+    for (int m = t; m < nm; m += BE_NT)
+        if (!tb.mp_outlier[m]) {                                            // an active map point without observations (:175 would dereference front())
+            const int s = be_bound(tb.obs_mp, no, m);
+            bad |= s >= no || tb.obs_mp[s] != m;
         }
-    }
     if (bad) s_bad = 1;
     __syncthreads();
-    if (s_bad) {
-        if (t == 0) { W.st[b] = MYSLAM_ERR_INVALID; sizes[0] = 0; sizes[1] = 0; sizes[2] = 0; }
-        return;
-    }
+    if (s_bad) { refuse(MYSLAM_ERR_INVALID); return; }
 
     // ---- edges: ACTIVE && !OUTLIER rows of map points that are no outliers (:163, :183-189), in row order ----
     int E = 0;
     for (int base = 0; base < no; base += BE_NT) {
         const int r = base + t;
         bool e = false;
-        if (r < no) e = (obs_flags[r] & (BE_ACTIVE | BE_OUTLIER)) == BE_ACTIVE && !mp_outlier[obs_mp[r]];
+        if (r < no) e = (tb.obs_flags[r] & (BE_ACTIVE | BE_OUTLIER)) == BE_ACTIVE && !tb.mp_outlier[tb.obs_mp[r]];
         int tot;
         const int k = E + be_block_rank(e, s_w, tot);
-        if (r < no) eidx[r] = k;
+        if (r < no) w.eidx[r] = k;
         if (e) {
-            f_ep[k] = obs_kf[r]; edge_src[k] = r;
-            f_obs[2 * k] = (double)obs_uv[2 * r]; f_obs[2 * k + 1] = (double)obs_uv[2 * r + 1];      // toVec2, :196
+            w.ep[k] = tb.obs_kf[r]; w.edge_src[k] = r;
+            w.obs[2 * k] = (double)tb.obs_uv[2 * r]; w.obs[2 * k + 1] = (double)tb.obs_uv[2 * r + 1];      // toVec2, :196
         }
         E += tot;
     }
-    if (E == 0) {                                                           // nothing to optimise: the caller's early return
-        if (t == 0) { W.st[b] = MYSLAM_BACKEND_EMPTY; sizes[0] = 0; sizes[1] = 0; sizes[2] = 0; }
-        return;
-    }
-    if (t == 0) eidx[no] = E;
+    if (E == 0) { refuse(MYSLAM_BACKEND_EMPTY); return; }                   // nothing to optimise: the caller's early return
+    if (t == 0) w.eidx[no] = E;
     __syncthreads();
 
     // ---- landmark slots: map points with at least one edge, in row order; fixed = the first observer has left the window (:175-177) ----
@@ -149,61 +237,44 @@ __global__ __launch_bounds__(BE_NT) void k_backend_flatten(BeTables T, BeWork W)
         const int m = base + t;
         bool has = false;
         int s = 0;
-        if (m < nm && !mp_outlier[m]) {
-            s = be_lower(obs_mp, no, m);
-            has = eidx[be_lower(obs_mp, no, m + 1)] > eidx[s];
+        if (m < nm && !tb.mp_outlier[m]) {
+            s = be_bound(tb.obs_mp, no, m);
+            has = w.eidx[be_bound(tb.obs_mp, no, m + 1)] > w.eidx[s];
         }
         int tot;
         const int slot = L + be_block_rank(has, s_w, tot);
-        if (m < nm) mp_slot[m] = has ? slot : -1;
+        if (m < nm) w.mp_slot[m] = has ? slot : -1;
         if (has) {
-            pt_src[slot] = m;
-            f_fixed[slot] = obs_kf[s] < 0 ? 1 : 0;
-            f_pts[3 * slot] = mp_pos[3 * m]; f_pts[3 * slot + 1] = mp_pos[3 * m + 1]; f_pts[3 * slot + 2] = mp_pos[3 * m + 2];
+            w.pt_src[slot] = m;
+            w.fixed[slot] = tb.obs_kf[s] < 0 ? 1 : 0;
+            w.pts[3 * slot] = tb.mp_pos[3 * m]; w.pts[3 * slot + 1] = tb.mp_pos[3 * m + 1]; w.pts[3 * slot + 2] = tb.mp_pos[3 * m + 2];
         }
         L += tot;
     }
     __syncthreads();
-    for (int k = t; k < E; k += BE_NT) f_el[k] = mp_slot[obs_mp[edge_src[k]]];
-    for (int i = t; i < 7 * nk; i += BE_NT) f_poses[i] = kf_pose[i];
-    if (t == 0) { sizes[0] = nk; sizes[1] = L; sizes[2] = E; W.st[b] = 0; }
+    for (int k = t; k < E; k += BE_NT) w.el[k] = w.mp_slot[tb.obs_mp[w.edge_src[k]]];
+    for (int i = t; i < 7 * nk; i += BE_NT) w.poses[i] = tb.kf_pose[i];
+    if (t == 0) { w.sizes[0] = nk; w.sizes[1] = L; w.sizes[2] = E; W.st[b] = 0; }
 }
 
 __global__ __launch_bounds__(BE_NT) void k_backend_write_back(BeTables T, BeWork W, BeOut O) {
     __shared__ int s_w[BE_NW];
     const int b = blockIdx.x, t = threadIdx.x;
     const int nk = T.n_kf[b], nm = T.n_mp[b], no = T.n_obs[b];
-    uint8_t* obs_report = O.obs_report + (size_t)b * T.obs_cap;
-    uint8_t* mp_report = O.mp_report + (size_t)b * T.mp_cap;
-    double* obs_chi2 = O.obs_chi2 + (size_t)b * T.obs_cap;
+    const auto o = O.item(b, T.mp_cap, T.obs_cap);
     int st = W.st[b];
     if (st == 0) st = W.solve_st[b];
     if (st != 0) {                                                          // refused or empty: the tables keep every byte, the reports are zero
         const int cm = min(max(nm, 0), T.mp_cap), co = min(max(no, 0), T.obs_cap);
-        for (int r = t; r < co; r += BE_NT) { obs_report[r] = 0; obs_chi2[r] = 0.0; }
-        for (int m = t; m < cm; m += BE_NT) mp_report[m] = 0;
+        for (int r = t; r < co; r += BE_NT) { o.obs_report[r] = 0; o.obs_chi2[r] = 0.0; }
+        for (int m = t; m < cm; m += BE_NT) o.mp_report[m] = 0;
         if (t == 0) { O.rounds[b] = 0; O.n_outlier_edges[b] = 0; O.n_new_outlier_mp[b] = 0; O.status[b] = st; }
         return;
     }
-    double* kf_pose = T.kf_pose + (size_t)b * T.kf_cap * 7;
-    int64_t* mp_id = T.mp_id + (size_t)b * T.mp_cap;
-    double* mp_pos = T.mp_pos + (size_t)b * T.mp_cap * 3;
-    uint8_t* mp_outlier = T.mp_outlier + (size_t)b * T.mp_cap;
-    int32_t* obs_mp = T.obs_mp + (size_t)b * T.obs_cap;
-    int32_t* obs_kf = T.obs_kf + (size_t)b * T.obs_cap;
-    uint8_t* obs_flags = T.obs_flags + (size_t)b * T.obs_cap;
-    float* obs_uv = T.obs_uv + (size_t)b * T.obs_cap * 2;
-    int32_t* obs_tag = T.obs_tag + (size_t)b * T.obs_cap;
-    int32_t* new_outlier = O.new_outlier_mp + (size_t)b * T.mp_cap;
-    const double* f_poses = W.poses + (size_t)b * T.kf_cap * 7;
-    const double* f_pts = W.pts + (size_t)b * T.mp_cap * 3;
-    const int32_t* eidx = W.eidx + (size_t)b * (T.obs_cap + 1);
-    const int32_t* mp_slot = W.mp_slot + (size_t)b * T.mp_cap;
-    int32_t* mp_new = W.mp_new + (size_t)b * T.mp_cap;
-    const double* chi2 = W.chi2 + (size_t)b * T.obs_cap;
-    const uint8_t* out = W.out + (size_t)b * T.obs_cap;
+    const auto tb = T.item(b);
+    const auto w = W.item(b, T.kf_cap, T.mp_cap, T.obs_cap);
 
-    for (int i = t; i < 7 * nk; i += BE_NT) kf_pose[i] = f_poses[i];        // :256-258
+    for (int i = t; i < 7 * nk; i += BE_NT) tb.kf_pose[i] = w.poses[i];     // :256-258
 
     // ---- map points, in ascending chunks: a chunk is read, the block meets in be_block_rank, then the chunk is written at or below where it stood ----
     int n_keep = 0, n_new = 0;
@@ -213,27 +284,27 @@ __global__ __launch_bounds__(BE_NT) void k_backend_write_back(BeTables T, BeWork
         int64_t id = 0;
         double p0 = 0, p1 = 0, p2 = 0;
         if (m < nm) {
-            const int s = be_lower(obs_mp, no, m), e = be_lower(obs_mp, no, m + 1);
+            const int s = be_bound(tb.obs_mp, no, m), e = be_bound(tb.obs_mp, no, m + 1);
             int nrem = 0, nact = 0;
-            for (int k = eidx[s]; k < eidx[e]; k++) nrem += out[k] ? 1 : 0;                       // :237-241: the edge's row leaves both lists
-            for (int r = s; r < e; r++) nact += obs_flags[r] & BE_ACTIVE;
-            const bool old = mp_outlier[m] != 0;
+            for (int k = w.eidx[s]; k < w.eidx[e]; k++) nrem += w.out[k] ? 1 : 0;                 // :237-241: the edge's row leaves both lists
+            for (int r = s; r < e; r++) nact += tb.obs_flags[r] & BE_ACTIVE;
+            const bool old = tb.mp_outlier[m] != 0;
             newout = !old && nrem == e - s;                                                       // :243-246: no observation left
             const bool leaves = nact - nrem == 0;                                                 // map.cpp:132
             const int rep = (old || newout) ? 2 : (leaves ? 1 : 0);
-            mp_report[m] = (uint8_t)rep;
+            o.mp_report[m] = (uint8_t)rep;
             keep = rep == 0;
-            id = mp_id[m];
-            const int slot = mp_slot[m];
-            const double* src = slot >= 0 ? f_pts + 3 * slot : mp_pos + 3 * m;                    // :259-261
+            id = tb.mp_id[m];
+            const int slot = w.mp_slot[m];
+            const double* src = slot >= 0 ? w.pts + 3 * slot : tb.mp_pos + 3 * m;                 // :259-261
             p0 = src[0]; p1 = src[1]; p2 = src[2];
         }
         int tot, ntot;
         const int dst = n_keep + be_block_rank(keep, s_w, tot);
         const int nd = n_new + be_block_rank(newout, s_w, ntot);
-        if (m < nm) mp_new[m] = keep ? dst : -1;
-        if (keep) { mp_id[dst] = id; mp_pos[3 * dst] = p0; mp_pos[3 * dst + 1] = p1; mp_pos[3 * dst + 2] = p2; mp_outlier[dst] = 0; }
-        if (newout) new_outlier[nd] = m;
+        if (m < nm) w.mp_new[m] = keep ? dst : -1;
+        if (keep) { tb.mp_id[dst] = id; tb.mp_pos[3 * dst] = p0; tb.mp_pos[3 * dst + 1] = p1; tb.mp_pos[3 * dst + 2] = p2; tb.mp_outlier[dst] = 0; }
+        if (newout) o.new_outlier_mp[nd] = m;
         n_keep += tot; n_new += ntot;
     }
     __syncthreads();
@@ -247,19 +318,21 @@ __global__ __launch_bounds__(BE_NT) void k_backend_write_back(BeTables T, BeWork
         uint8_t fl = 0;
         float u = 0, v = 0;
         if (r < no) {
-            const int k = eidx[r];
-            const bool edge = eidx[r + 1] > k, rem = edge && out[k];
-            m2 = mp_new[obs_mp[r]];
+            const int k = w.eidx[r];
+            const bool edge = w.eidx[r + 1] > k, rem = edge && w.out[k];
+            m2 = w.mp_new[tb.obs_mp[r]];
             keep = m2 >= 0 && !rem;
-            obs_report[r] = rem ? 1 : (m2 < 0 ? 2 : 0);
-            obs_chi2[r] = edge ? chi2[k] : -1.0;
-            kf = obs_kf[r]; tag = obs_tag[r]; u = obs_uv[2 * r]; v = obs_uv[2 * r + 1];
-            fl = obs_flags[r];
+            o.obs_report[r] = rem ? 1 : (m2 < 0 ? 2 : 0);
+            o.obs_chi2[r] = edge ? w.chi2[k] : -1.0;
+            kf = tb.obs_kf[r]; tag = tb.obs_tag[r]; u = tb.obs_uv[2 * r]; v = tb.obs_uv[2 * r + 1];
+            fl = tb.obs_flags[r];
             if (edge) fl &= (uint8_t)~BE_OUTLIER;                                                 // :249
         }
         int tot;
         const int dst = n_rows + be_block_rank(keep, s_w, tot);
-        if (keep) { obs_mp[dst] = m2; obs_kf[dst] = kf; obs_flags[dst] = fl; obs_uv[2 * dst] = u; obs_uv[2 * dst + 1] = v; obs_tag[dst] = tag; }
+        if (keep) {
+            tb.obs_mp[dst] = m2; tb.obs_kf[dst] = kf; tb.obs_flags[dst] = fl; tb.obs_uv[2 * dst] = u; tb.obs_uv[2 * dst + 1] = v; tb.obs_tag[dst] = tag;
+        }
         n_rows += tot;
     }
     if (t == 0) {
@@ -270,67 +343,6 @@ __global__ __launch_bounds__(BE_NT) void k_backend_write_back(BeTables T, BeWork
 
 // ---------------------------------------------------------------------------------------------------------------------------------------------
 // Map::InsertKeyFrame for a batch of maps (myslam_backend_insert_keyframe_batch)
-
-struct InsTables {                      // the caller's tables, all in/out
-    int64_t* kf_id; double* kf_pose; int32_t* n_kf;
-    int64_t* mp_id; double* mp_pos; uint8_t* mp_outlier; int32_t* n_mp;
-    int32_t* obs_mp; int32_t* obs_kf; uint8_t* obs_flags; float* obs_uv; int32_t* obs_tag; int32_t* n_obs;
-    int kf_cap, mp_cap, obs_cap;
-};
-
-struct InsIn {                          // the new key-frame of every item; n_prior / n_outlier NULL = none
-    const int64_t* new_kf_id; const double* new_kf_pose;
-    const int64_t* feat_mp_id; const double* feat_mp_pos; const float* feat_uv; const int32_t* feat_tag; const uint8_t* feat_flags;
-    const int32_t* n_feat; int feat_cap;
-    const int64_t* prior_mp_id; const int64_t* prior_kf_id; const float* prior_uv; const int32_t* prior_tag; const uint8_t* prior_flags;
-    const int32_t* n_prior; int prior_cap;
-    const int64_t* outlier_mp_id; const int32_t* n_outlier; int outlier_cap;
-    int window; double min_dis_th;
-};
-
-struct InsWork {                        // the handle's staging, strided by the caps
-    int64_t* mp_id; double* mp_pos; uint8_t* mp_outlier;                                         // the tables as they came in (outlier ids applied)
-    int32_t* obs_mp; int32_t* obs_kf; uint8_t* obs_flags; float* obs_uv; int32_t* obs_tag;
-    int64_t* vid; int32_t* vft;         // obs_cap: ids / indices of the features that name a map point, in feature order
-    int64_t* sid; int32_t* sfeat;       // obs_cap: the same sorted by (id, feature index)
-    int32_t* dcum;                      // obs_cap + 1: distinct ids that are new to the table among sorted features before s
-    int32_t* pcum;                      // obs_cap + 1: prior rows that enter the table before prior row p
-    int32_t* dmp; int32_t* drows;       // mp_cap + 1: map points / their rows that leave, before input row m
-    int32_t* mp_fin; int32_t* mp_shift; // mp_cap: final row of an input map point (-1 = it leaves); what its observation rows move by
-};
-
-struct InsOut {
-    int32_t* feat_row; int32_t* mp_new_row; int64_t* removed_kf_id; int32_t* removed_kf_row; double* dis; int32_t* status;
-};
-
-// exclusive block-wide prefix sum of v in thread order, and the sum; every thread of the block calls it (two barriers, as be_block_rank)
-__device__ __forceinline__ int be_block_exsum(int v, int* s_w, int& total) {
-    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) { const int o = __shfl_up(inc, d); if (lane >= d) inc += o; }
-    if (lane == WAVE - 1) s_w[wv] = inc;
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < BE_NW; i++) { const int c = s_w[i]; off += i < wv ? c : 0; tot += c; }
-    __syncthreads();
-    total = tot;
-    return off + inc - v;
-}
-
-// first index in a[0, n) whose value is not below v / is above v (a non-decreasing; on any other input the result still lies in [0, n])
-__device__ __forceinline__ int be_lower64(const int64_t* a, int n, int64_t v) {
-    int lo = 0, hi = n;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] < v) lo = mid + 1; else hi = mid; }
-    return lo;
-}
-__device__ __forceinline__ int be_upper64(const int64_t* a, int n, int64_t v) {
-    int lo = 0, hi = n;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (a[mid] <= v) lo = mid + 1; else hi = mid; }
-    return lo;
-}
-
 // One workgroup per map.  Everything is decided from the inputs and the staged copy before the first byte of a table is written; every position is a
 // closed form of binary searches and block scans:
 //   merged map-point row  = rows of the table below the id + distinct new ids below it
@@ -344,14 +356,12 @@ __global__ __launch_bounds__(BE_NT) void k_backend_insert(InsTables T, InsIn I, 
     const int b = blockIdx.x, t = threadIdx.x;
     const int nk = T.n_kf[b], nm = T.n_mp[b], no = T.n_obs[b], nf = I.n_feat[b];
     const int np = I.n_prior ? I.n_prior[b] : 0, nx = I.n_outlier ? I.n_outlier[b] : 0;
-    int32_t* feat_row = O.feat_row + (size_t)b * I.feat_cap;
-    int32_t* mp_new_row = O.mp_new_row + (size_t)b * T.mp_cap;
-    double* dis_out = O.dis + (size_t)b * T.kf_cap;
+    const auto o = O.item(b, I.feat_cap, T.mp_cap, T.kf_cap);
     auto refuse = [&](int st) {                                             // the tables keep every byte; the reports say "nothing"
         const int cf = min(max(nf, 0), I.feat_cap), cm = min(max(nm, 0), T.mp_cap);
-        for (int f = t; f < cf; f += BE_NT) feat_row[f] = -1;
-        for (int m = t; m < cm; m += BE_NT) mp_new_row[m] = -1;
-        if (t < T.kf_cap) dis_out[t] = -1.0;
+        for (int f = t; f < cf; f += BE_NT) o.feat_row[f] = -1;
+        for (int m = t; m < cm; m += BE_NT) o.mp_new_row[m] = -1;
+        if (t < T.kf_cap) o.dis[t] = -1.0;
         if (t == 0) { O.removed_kf_id[b] = -1; O.removed_kf_row[b] = -1; O.status[b] = st; }
     };
     if (nk < 0 || nk > T.kf_cap || nm < 0 || nm > T.mp_cap || no < 0 || no > T.obs_cap || nf < 0 || nf > I.feat_cap || np < 0 || np > I.prior_cap ||
@@ -359,134 +369,83 @@ __global__ __launch_bounds__(BE_NT) void k_backend_insert(InsTables T, InsIn I, 
         refuse(MYSLAM_ERR_INVALID);
         return;
     }
-    int64_t* kf_id = T.kf_id + (size_t)b * T.kf_cap;
-    double* kf_pose = T.kf_pose + (size_t)b * T.kf_cap * 7;
-    int64_t* mp_id = T.mp_id + (size_t)b * T.mp_cap;
-    double* mp_pos = T.mp_pos + (size_t)b * T.mp_cap * 3;
-    uint8_t* mp_outlier = T.mp_outlier + (size_t)b * T.mp_cap;
-    int32_t* obs_mp = T.obs_mp + (size_t)b * T.obs_cap;
-    int32_t* obs_kf = T.obs_kf + (size_t)b * T.obs_cap;
-    uint8_t* obs_flags = T.obs_flags + (size_t)b * T.obs_cap;
-    float* obs_uv = T.obs_uv + (size_t)b * T.obs_cap * 2;
-    int32_t* obs_tag = T.obs_tag + (size_t)b * T.obs_cap;
+    const auto tb = T.item(b);
+    const auto in = I.item(b, np, nx);
+    const auto w = W.item(b, T.mp_cap, T.obs_cap);      // w.mp_id ... w.obs_tag: the copy the tables are rebuilt from
     const int64_t new_id = I.new_kf_id[b];
-    const double* new_pose = I.new_kf_pose + (size_t)b * 7;
-    const int64_t* fid = I.feat_mp_id + (size_t)b * I.feat_cap;
-    const double* fpos = I.feat_mp_pos + (size_t)b * I.feat_cap * 3;
-    const float* fuv = I.feat_uv + (size_t)b * I.feat_cap * 2;
-    const int32_t* ftag = I.feat_tag + (size_t)b * I.feat_cap;
-    const uint8_t* fflags = I.feat_flags + (size_t)b * I.feat_cap;
-    const int64_t* pid = np ? I.prior_mp_id + (size_t)b * I.prior_cap : nullptr;
-    const int64_t* pkf = np ? I.prior_kf_id + (size_t)b * I.prior_cap : nullptr;
-    const float* puv = np ? I.prior_uv + (size_t)b * I.prior_cap * 2 : nullptr;
-    const int32_t* ptag = np ? I.prior_tag + (size_t)b * I.prior_cap : nullptr;
-    const uint8_t* pflags = np ? I.prior_flags + (size_t)b * I.prior_cap : nullptr;
-    const int64_t* xid = nx ? I.outlier_mp_id + (size_t)b * I.outlier_cap : nullptr;
-    int64_t* c_mp_id = W.mp_id + (size_t)b * T.mp_cap;
-    double* c_mp_pos = W.mp_pos + (size_t)b * T.mp_cap * 3;
-    uint8_t* c_mp_outlier = W.mp_outlier + (size_t)b * T.mp_cap;
-    int32_t* c_obs_mp = W.obs_mp + (size_t)b * T.obs_cap;
-    int32_t* c_obs_kf = W.obs_kf + (size_t)b * T.obs_cap;
-    uint8_t* c_obs_flags = W.obs_flags + (size_t)b * T.obs_cap;
-    float* c_obs_uv = W.obs_uv + (size_t)b * T.obs_cap * 2;
-    int32_t* c_obs_tag = W.obs_tag + (size_t)b * T.obs_cap;
-    int64_t* vid = W.vid + (size_t)b * T.obs_cap;
-    int32_t* vft = W.vft + (size_t)b * T.obs_cap;
-    int64_t* sid = W.sid + (size_t)b * T.obs_cap;
-    int32_t* sfeat = W.sfeat + (size_t)b * T.obs_cap;
-    int32_t* dcum = W.dcum + (size_t)b * (T.obs_cap + 1);
-    int32_t* pcum = W.pcum + (size_t)b * (T.obs_cap + 1);
-    int32_t* dmp = W.dmp + (size_t)b * (T.mp_cap + 1);
-    int32_t* drows = W.drows + (size_t)b * (T.mp_cap + 1);
-    int32_t* mp_fin = W.mp_fin + (size_t)b * T.mp_cap;
-    int32_t* mp_shift = W.mp_shift + (size_t)b * T.mp_cap;
 
     // ---- validation, and the copy the tables are rebuilt from ----
     if (t == 0) { s_bad = 0; s_victim = -1; }
-    if (t <= nk) s_kfid[t] = t < nk ? kf_id[t] : new_id;
+    if (t <= nk) s_kfid[t] = t < nk ? tb.kf_id[t] : new_id;
     __syncthreads();
-    bool bad = false;
-    for (int i = t + 1; i < nk; i += BE_NT) bad |= kf_id[i - 1] >= kf_id[i];
-    if (t == 0 && nk > 0) bad |= new_id <= kf_id[nk - 1];                   // mnKFId comes from a counter (keyframe.cpp:24)
-    for (int r = t; r < no; r += BE_NT) {
-        const int m = obs_mp[r], k = obs_kf[r];
-        const uint8_t fl = obs_flags[r];
-        bad |= m < 0 || m >= nm || (r > 0 && obs_mp[r - 1] > m) || k < -1 || k >= nk;
-        bad |= (fl & BE_ACTIVE) && k < 0;
-        c_obs_mp[r] = m; c_obs_kf[r] = k; c_obs_flags[r] = fl; c_obs_uv[2 * r] = obs_uv[2 * r]; c_obs_uv[2 * r + 1] = obs_uv[2 * r + 1];
-        c_obs_tag[r] = obs_tag[r];
-    }
-    for (int m = t; m < nm; m += BE_NT) {
-        bad |= m > 0 && mp_id[m - 1] >= mp_id[m];
-        c_mp_id[m] = mp_id[m]; c_mp_outlier[m] = mp_outlier[m];
-        c_mp_pos[3 * m] = mp_pos[3 * m]; c_mp_pos[3 * m + 1] = mp_pos[3 * m + 1]; c_mp_pos[3 * m + 2] = mp_pos[3 * m + 2];
-    }
-    for (int f = t; f < nf; f += BE_NT) bad |= fid[f] < -1 || (fflags[f] & ~BE_OUTLIER);
-    for (int p = t; p < np; p += BE_NT) bad |= (p > 0 && pid[p - 1] > pid[p]) || (pflags[p] & ~BE_OUTLIER);          // ACTIVE is one of the other bits
+    bool bad = be_tables_bad<true>(tb, nk, nm, no, w);
+    if (t == 0 && nk > 0) bad |= new_id <= tb.kf_id[nk - 1];                // mnKFId comes from a counter (keyframe.cpp:24)
+    for (int f = t; f < nf; f += BE_NT) bad |= in.fid[f] < -1 || (in.fflags[f] & ~BE_OUTLIER);
+    for (int p = t; p < np; p += BE_NT) bad |= (p > 0 && in.pid[p - 1] > in.pid[p]) || (in.pflags[p] & ~BE_OUTLIER);  // ACTIVE is one of the other bits
     if (bad) s_bad = 1;
     __syncthreads();
     if (s_bad) { refuse(MYSLAM_ERR_INVALID); return; }
 
     // ---- Map::AddOutlierMapPoint (map.cpp:159-164) on the copy: ids that are not in the table are ignored ----
     for (int j = t; j < nx; j += BE_NT) {
-        const int m = be_lower64(c_mp_id, nm, xid[j]);
-        if (m < nm && c_mp_id[m] == xid[j]) c_mp_outlier[m] = 1;
+        const int m = be_bound(w.mp_id, nm, in.xid[j]);
+        if (m < nm && w.mp_id[m] == in.xid[j]) w.mp_outlier[m] = 1;
     }
 
     // ---- the features that name a map point, sorted by (id, feature index): the rows AddObservation / AddActiveObservation push back ----
     int nv = 0;
     for (int base = 0; base < nf; base += BE_NT) {
         const int f = base + t;
-        const bool v = f < nf && fid[f] >= 0;
+        const bool v = f < nf && in.fid[f] >= 0;
         int tot;
         const int k = nv + be_block_rank(v, s_w, tot);
-        if (v) { vid[k] = fid[f]; vft[k] = f; }
+        if (v) { w.vid[k] = in.fid[f]; w.vft[k] = f; }
         nv += tot;
     }
     __syncthreads();
     for (int k = t; k < nv; k += BE_NT) {
-        const int64_t id = vid[k];
+        const int64_t id = w.vid[k];
         int r = 0;
-        for (int j = 0; j < nv; j++) { const int64_t o = vid[j]; r += (o < id || (o == id && j < k)) ? 1 : 0; }
-        sid[r] = id; sfeat[r] = vft[k];
+        for (int j = 0; j < nv; j++) { const int64_t oid = w.vid[j]; r += (oid < id || (oid == id && j < k)) ? 1 : 0; }
+        w.sid[r] = id; w.sfeat[r] = w.vft[k];
     }
     __syncthreads();
     int nu = 0;                                                             // distinct ids that are not in the table: InsertActiveMapPoint adds a row
     for (int base = 0; base < nv; base += BE_NT) {
         const int s = base + t;
         bool fn = false;
-        if (s < nv && (s == 0 || sid[s - 1] != sid[s])) {
-            const int m = be_lower64(c_mp_id, nm, sid[s]);
-            fn = !(m < nm && c_mp_id[m] == sid[s]);
+        if (s < nv && (s == 0 || w.sid[s - 1] != w.sid[s])) {
+            const int m = be_bound(w.mp_id, nm, w.sid[s]);
+            fn = !(m < nm && w.mp_id[m] == w.sid[s]);
         }
         int tot;
         const int k = nu + be_block_rank(fn, s_w, tot);
-        if (s < nv) dcum[s] = k;
+        if (s < nv) w.dcum[s] = k;
         nu += tot;
     }
-    if (t == 0) dcum[nv] = nu;
+    if (t == 0) w.dcum[nv] = nu;
     int npu = 0;                                                            // prior rows of those ids
     for (int base = 0; base < np; base += BE_NT) {
         const int p = base + t;
         bool u = false;
         if (p < np) {
-            const int64_t id = pid[p];
-            const int m = be_lower64(c_mp_id, nm, id), g = be_lower64(sid, nv, id);
-            u = g < nv && sid[g] == id && !(m < nm && c_mp_id[m] == id);
+            const int64_t id = in.pid[p];
+            const int m = be_bound(w.mp_id, nm, id), g = be_bound(w.sid, nv, id);
+            u = g < nv && w.sid[g] == id && !(m < nm && w.mp_id[m] == id);
         }
         int tot;
         const int k = npu + be_block_rank(u, s_w, tot);
-        if (p < np) pcum[p] = k;
+        if (p < np) w.pcum[p] = k;
         npu += tot;
     }
-    if (t == 0) pcum[np] = npu;
+    if (t == 0) w.pcum[np] = npu;
     if (nk + 1 > T.kf_cap || nm + nu > T.mp_cap || no + nv + npu > T.obs_cap) { refuse(MYSLAM_ERR_CAPACITY); return; }          // uniform
 
     // ---- RemoveOldActiveKeyframe's choice (map.cpp:83-107) ----
     const bool removal = nk + 1 > I.window;                                 // map.cpp:44
     if (removal && t < nk) {
         double d[6];
-        pg_log(pg_mul(pg_load(kf_pose + 7 * t), pg_inv(pg_load(new_pose))), d);
+        pg_log(pg_mul(pg_load(tb.kf_pose + 7 * t), pg_inv(pg_load(in.new_pose))), d);
         double s = 0;
         for (int k = 0; k < 6; k++) s += d[k] * d[k];
         s_dis[t] = sqrt(s);
@@ -516,12 +475,12 @@ __global__ __launch_bounds__(BE_NT) void k_backend_insert(InsTables T, InsIn I, 
         bool dead = false;
         int len = 0, g = 0;
         if (m < nm) {
-            const int64_t id = c_mp_id[m];
-            g = be_lower64(sid, nv, id);
-            if (removal && !(g < nv && sid[g] == id)) {
-                const int s0 = be_lower(c_obs_mp, no, m), e0 = be_lower(c_obs_mp, no, m + 1);
+            const int64_t id = w.mp_id[m];
+            g = be_bound(w.sid, nv, id);
+            if (removal && !(g < nv && w.sid[g] == id)) {
+                const int s0 = be_bound(w.obs_mp, no, m), e0 = be_bound(w.obs_mp, no, m + 1);
                 bool act = false;
-                for (int r = s0; r < e0; r++) act |= (c_obs_flags[r] & BE_ACTIVE) && c_obs_kf[r] != victim;
+                for (int r = s0; r < e0; r++) act |= (w.obs_flags[r] & BE_ACTIVE) && w.obs_kf[r] != victim;
                 dead = !act; len = e0 - s0;
             }
         }
@@ -529,83 +488,83 @@ __global__ __launch_bounds__(BE_NT) void k_backend_insert(InsTables T, InsIn I, 
         const int dm = ndm + be_block_rank(dead, s_w, tot);
         const int dr = ndr + be_block_exsum(dead ? len : 0, s_w, rtot);
         if (m < nm) {
-            dmp[m] = dm; drows[m] = dr;
-            mp_fin[m] = dead ? -1 : m + dcum[g] - dm;
-            mp_shift[m] = g + pcum[be_lower64(pid, np, c_mp_id[m])] - dr;
+            w.dmp[m] = dm; w.drows[m] = dr;
+            w.mp_fin[m] = dead ? -1 : m + w.dcum[g] - dm;
+            w.mp_shift[m] = g + w.pcum[be_bound(in.pid, np, w.mp_id[m])] - dr;
         }
         ndm += tot; ndr += rtot;
     }
-    if (t == 0) { dmp[nm] = ndm; drows[nm] = ndr; }
+    if (t == 0) { w.dmp[nm] = ndm; w.drows[nm] = ndr; }
 
     // ---- the key-frame table: the victim's row leaves, the new row is the last ----
     long long kid = 0;
     double kp[7];
     if (t <= nk) {
         kid = s_kfid[t];
-        const double* src = t < nk ? kf_pose + 7 * t : new_pose;
+        const double* src = t < nk ? tb.kf_pose + 7 * t : in.new_pose;
         for (int k = 0; k < 7; k++) kp[k] = src[k];
     }
     __syncthreads();                                                        // everything above is decided and stored; from here on the tables are written
     if (t <= nk && t != victim) {
         const int dst = t - ((removal && t > victim) ? 1 : 0);
-        kf_id[dst] = kid;
-        for (int k = 0; k < 7; k++) kf_pose[7 * dst + k] = kp[k];
+        tb.kf_id[dst] = kid;
+        for (int k = 0; k < 7; k++) tb.kf_pose[7 * dst + k] = kp[k];
     }
     const int new_kf_row = removal ? nk - 1 : nk;
     auto kf_row_after = [&](int k) { return !removal || k < victim ? k : (k == victim ? -1 : k - 1); };
 
     // ---- map points: the input rows that stay, then the new ids (position from the first feature naming them) ----
     for (int m = t; m < nm; m += BE_NT) {
-        const int dst = mp_fin[m];
-        mp_new_row[m] = dst;
+        const int dst = w.mp_fin[m];
+        o.mp_new_row[m] = dst;
         if (dst >= 0 && dst < T.mp_cap) {
-            mp_id[dst] = c_mp_id[m]; mp_outlier[dst] = c_mp_outlier[m];
-            mp_pos[3 * dst] = c_mp_pos[3 * m]; mp_pos[3 * dst + 1] = c_mp_pos[3 * m + 1]; mp_pos[3 * dst + 2] = c_mp_pos[3 * m + 2];
+            tb.mp_id[dst] = w.mp_id[m]; tb.mp_outlier[dst] = w.mp_outlier[m];
+            tb.mp_pos[3 * dst] = w.mp_pos[3 * m]; tb.mp_pos[3 * dst + 1] = w.mp_pos[3 * m + 1]; tb.mp_pos[3 * dst + 2] = w.mp_pos[3 * m + 2];
         }
     }
-    for (int f = t; f < nf; f += BE_NT) if (fid[f] < 0) feat_row[f] = -1;
+    for (int f = t; f < nf; f += BE_NT) if (in.fid[f] < 0) o.feat_row[f] = -1;
     for (int s = t; s < nv; s += BE_NT) {
-        const int64_t id = sid[s];
-        const int f = sfeat[s];
-        const int lm = be_lower64(c_mp_id, nm, id), g = be_lower64(sid, nv, id);
-        const bool in_table = lm < nm && c_mp_id[lm] == id;
+        const int64_t id = w.sid[s];
+        const int f = w.sfeat[s];
+        const int lm = be_bound(w.mp_id, nm, id), g = be_bound(w.sid, nv, id);
+        const bool in_table = lm < nm && w.mp_id[lm] == id;
         const int um = lm + (in_table ? 1 : 0);
-        const int mrow = lm + dcum[g] - dmp[lm];
+        const int mrow = lm + w.dcum[g] - w.dmp[lm];
         if (!in_table && g == s && (unsigned)mrow < (unsigned)T.mp_cap) {
-            mp_id[mrow] = id; mp_outlier[mrow] = 0;
-            mp_pos[3 * mrow] = fpos[3 * f]; mp_pos[3 * mrow + 1] = fpos[3 * f + 1]; mp_pos[3 * mrow + 2] = fpos[3 * f + 2];
+            tb.mp_id[mrow] = id; tb.mp_outlier[mrow] = 0;
+            tb.mp_pos[3 * mrow] = in.fpos[3 * f]; tb.mp_pos[3 * mrow + 1] = in.fpos[3 * f + 1]; tb.mp_pos[3 * mrow + 2] = in.fpos[3 * f + 2];
         }
         // the feature's row: behind the segment's old rows (or its prior rows), in feature order
-        const int dst = be_lower(c_obs_mp, no, um) + pcum[be_upper64(pid, np, id)] + s - drows[um];
+        const int dst = be_bound(w.obs_mp, no, um) + w.pcum[be_bound<int64_t, true>(in.pid, np, id)] + s - w.drows[um];
         if ((unsigned)dst >= (unsigned)T.obs_cap) continue;            // cannot happen: the merged count passed the capacity check
-        obs_mp[dst] = mrow; obs_kf[dst] = new_kf_row; obs_flags[dst] = (uint8_t)(BE_ACTIVE | (fflags[f] & BE_OUTLIER));
-        obs_uv[2 * dst] = fuv[2 * f]; obs_uv[2 * dst + 1] = fuv[2 * f + 1]; obs_tag[dst] = ftag[f];
-        feat_row[f] = dst;
+        tb.obs_mp[dst] = mrow; tb.obs_kf[dst] = new_kf_row; tb.obs_flags[dst] = (uint8_t)(BE_ACTIVE | (in.fflags[f] & BE_OUTLIER));
+        tb.obs_uv[2 * dst] = in.fuv[2 * f]; tb.obs_uv[2 * dst + 1] = in.fuv[2 * f + 1]; tb.obs_tag[dst] = in.ftag[f];
+        o.feat_row[f] = dst;
     }
     // ---- the input observation rows: RemoveActiveObservation on the victim's, key-frame rows renumbered ----
     for (int r = t; r < no; r += BE_NT) {
-        const int m = c_obs_mp[r], mrow = mp_fin[m];
+        const int m = w.obs_mp[r], mrow = w.mp_fin[m];
         if (mrow < 0) continue;
-        const int dst = r + mp_shift[m], k = c_obs_kf[r];
+        const int dst = r + w.mp_shift[m], k = w.obs_kf[r];
         if ((unsigned)dst >= (unsigned)T.obs_cap) continue;
-        uint8_t fl = c_obs_flags[r];
+        uint8_t fl = w.obs_flags[r];
         if (removal && k == victim) fl &= (uint8_t)~BE_ACTIVE;
-        obs_mp[dst] = mrow; obs_kf[dst] = k < 0 ? -1 : kf_row_after(k); obs_flags[dst] = fl;
-        obs_uv[2 * dst] = c_obs_uv[2 * r]; obs_uv[2 * dst + 1] = c_obs_uv[2 * r + 1]; obs_tag[dst] = c_obs_tag[r];
+        tb.obs_mp[dst] = mrow; tb.obs_kf[dst] = k < 0 ? -1 : kf_row_after(k); tb.obs_flags[dst] = fl;
+        tb.obs_uv[2 * dst] = w.obs_uv[2 * r]; tb.obs_uv[2 * dst + 1] = w.obs_uv[2 * r + 1]; tb.obs_tag[dst] = w.obs_tag[r];
     }
     // ---- GetObservations() of a map point that comes back: never ACTIVE, key-frame resolved against the final table ----
     for (int p = t; p < np; p += BE_NT) {
-        if (pcum[p + 1] == pcum[p]) continue;
-        const int64_t id = pid[p];
-        const int lm = be_lower64(c_mp_id, nm, id), g = be_lower64(sid, nv, id);
-        const int dst = be_lower(c_obs_mp, no, lm) + g + pcum[p] - drows[lm];
+        if (w.pcum[p + 1] == w.pcum[p]) continue;
+        const int64_t id = in.pid[p];
+        const int lm = be_bound(w.mp_id, nm, id), g = be_bound(w.sid, nv, id);
+        const int dst = be_bound(w.obs_mp, no, lm) + g + w.pcum[p] - w.drows[lm];
         if ((unsigned)dst >= (unsigned)T.obs_cap) continue;
         int k = -1;
-        for (int i = 0; i <= nk; i++) k = s_kfid[i] == pkf[p] ? i : k;
-        obs_mp[dst] = lm + dcum[g] - dmp[lm]; obs_kf[dst] = k < 0 ? -1 : (k == nk ? new_kf_row : kf_row_after(k)); obs_flags[dst] = pflags[p];
-        obs_uv[2 * dst] = puv[2 * p]; obs_uv[2 * dst + 1] = puv[2 * p + 1]; obs_tag[dst] = ptag[p];
+        for (int i = 0; i <= nk; i++) k = s_kfid[i] == in.pkf[p] ? i : k;
+        tb.obs_mp[dst] = lm + w.dcum[g] - w.dmp[lm]; tb.obs_kf[dst] = k < 0 ? -1 : (k == nk ? new_kf_row : kf_row_after(k)); tb.obs_flags[dst] = in.pflags[p];
+        tb.obs_uv[2 * dst] = in.puv[2 * p]; tb.obs_uv[2 * dst + 1] = in.puv[2 * p + 1]; tb.obs_tag[dst] = in.ptag[p];
     }
-    if (t < T.kf_cap) dis_out[t] = (removal && t < nk) ? s_dis[t] : -1.0;
+    if (t < T.kf_cap) o.dis[t] = (removal && t < nk) ? s_dis[t] : -1.0;
     if (t == 0) {
         T.n_kf[b] = new_kf_row + 1; T.n_mp[b] = nm + nu - ndm; T.n_obs[b] = no + nv + npu - ndr;
         O.removed_kf_id[b] = removal ? (int64_t)s_kfid[victim] : -1; O.removed_kf_row[b] = victim; O.status[b] = MYSLAM_OK;
@@ -620,22 +579,10 @@ struct myslam_backend {
     int max_batch = 0, kf_cap = 0, mp_cap = 0, obs_cap = 0;
     hipStream_t stream = nullptr;
     size_t wstride = 0;
-    Buf<double> poses, pts, obs, scratch, chi2;
-    Buf<int32_t> ep, el, sizes, pt_src, edge_src, eidx, mp_slot, mp_new, st, rounds, nout, solve_st;
-    Buf<uint8_t> fixed, out;
-    // myslam_backend_insert_keyframe_batch: the copy the tables are rebuilt from, and its index arrays
-    Buf<int64_t> in_mp_id, in_vid, in_sid;
-    Buf<double> in_mp_pos;
-    Buf<float> in_obs_uv;
-    Buf<uint8_t> in_mp_outlier, in_obs_flags;
-    Buf<int32_t> in_obs_mp, in_obs_kf, in_obs_tag, in_vft, in_sfeat, in_dcum, in_pcum, in_dmp, in_drows, in_mp_fin, in_mp_shift;
-    BeWork work() const {
-        return BeWork{poses, pts, ep, el, obs, fixed, sizes, pt_src, edge_src, eidx, mp_slot, mp_new, st, chi2, out, rounds, nout, solve_st};
-    }
-    InsWork insert_work() const {
-        return InsWork{in_mp_id, in_mp_pos, in_mp_outlier, in_obs_mp, in_obs_kf, in_obs_flags, in_obs_uv, in_obs_tag, in_vid, in_vft, in_sid, in_sfeat,
-                       in_dcum, in_pcum, in_dmp, in_drows, in_mp_fin, in_mp_shift};
-    }
+    Buf<double> scratch;                // the solve's
+    BeWork w{};                         // optimise's buffers, which debug_flat / debug_solved read after any later call ...
+    InsWork iw{};                       // ... so insert's staging shares none of them
+    BufSet mem;                         // owns every block that `w` and `iw` name
 };
 
 extern "C" {
@@ -657,26 +604,27 @@ int myslam_backend_create(myslam_backend** out, int max_batch, int kf_cap, int m
     h->max_batch = max_batch; h->kf_cap = kf_cap; h->mp_cap = mp_cap; h->obs_cap = obs_cap;
     h->wstride = ba_active_map_scratch_doubles(mp_cap, obs_cap);
     const size_t B = (size_t)max_batch, K = (size_t)kf_cap, M = (size_t)mp_cap, N = (size_t)obs_cap;
-    const int oom = MYSLAM_ERR_CAPACITY;
+    BeWork& w = h->w;
+    InsWork& iw = h->iw;
+    auto own = [&](auto*& p, size_t n) { return h->mem.own(p, n, MYSLAM_ERR_CAPACITY); };
     int rc;
-    if ((rc = h->poses.renew(B * K * 7, oom)) || (rc = h->pts.renew(B * M * 3, oom)) || (rc = h->obs.renew(B * N * 2, oom)) ||
-        (rc = h->scratch.renew(B * h->wstride, oom)) || (rc = h->chi2.renew(B * N, oom)) || (rc = h->ep.renew(B * N, oom)) ||
-        (rc = h->el.renew(B * N, oom)) || (rc = h->sizes.renew(B * 3, oom)) || (rc = h->pt_src.renew(B * M, oom)) ||
-        (rc = h->edge_src.renew(B * N, oom)) || (rc = h->eidx.renew(B * (N + 1), oom)) || (rc = h->mp_slot.renew(B * M, oom)) ||
-        (rc = h->mp_new.renew(B * M, oom)) || (rc = h->st.renew(B, oom)) || (rc = h->rounds.renew(B, oom)) || (rc = h->nout.renew(B, oom)) ||
-        (rc = h->solve_st.renew(B, oom)) || (rc = h->fixed.renew(B * M, oom)) || (rc = h->out.renew(B * N, oom)) ||
-        (rc = h->in_mp_id.renew(B * M, oom)) || (rc = h->in_mp_pos.renew(B * M * 3, oom)) || (rc = h->in_mp_outlier.renew(B * M, oom)) ||
-        (rc = h->in_obs_mp.renew(B * N, oom)) || (rc = h->in_obs_kf.renew(B * N, oom)) || (rc = h->in_obs_flags.renew(B * N, oom)) ||
-        (rc = h->in_obs_uv.renew(B * N * 2, oom)) || (rc = h->in_obs_tag.renew(B * N, oom)) || (rc = h->in_vid.renew(B * N, oom)) ||
-        (rc = h->in_vft.renew(B * N, oom)) || (rc = h->in_sid.renew(B * N, oom)) || (rc = h->in_sfeat.renew(B * N, oom)) ||
-        (rc = h->in_dcum.renew(B * (N + 1), oom)) || (rc = h->in_pcum.renew(B * (N + 1), oom)) || (rc = h->in_dmp.renew(B * (M + 1), oom)) ||
-        (rc = h->in_drows.renew(B * (M + 1), oom)) || (rc = h->in_mp_fin.renew(B * M, oom)) || (rc = h->in_mp_shift.renew(B * M, oom))) {
+    if ((rc = h->scratch.renew(B * h->wstride, MYSLAM_ERR_CAPACITY)) ||
+        (rc = own(w.poses, B * K * 7)) || (rc = own(w.pts, B * M * 3)) || (rc = own(w.ep, B * N)) || (rc = own(w.el, B * N)) ||
+        (rc = own(w.obs, B * N * 2)) || (rc = own(w.fixed, B * M)) || (rc = own(w.sizes, B * 3)) || (rc = own(w.pt_src, B * M)) ||
+        (rc = own(w.edge_src, B * N)) || (rc = own(w.eidx, B * (N + 1))) || (rc = own(w.mp_slot, B * M)) || (rc = own(w.mp_new, B * M)) ||
+        (rc = own(w.st, B)) || (rc = own(w.chi2, B * N)) || (rc = own(w.out, B * N)) || (rc = own(w.rounds, B)) || (rc = own(w.nout, B)) ||
+        (rc = own(w.solve_st, B)) ||
+        (rc = own(iw.mp_id, B * M)) || (rc = own(iw.mp_pos, B * M * 3)) || (rc = own(iw.mp_outlier, B * M)) || (rc = own(iw.obs_mp, B * N)) ||
+        (rc = own(iw.obs_kf, B * N)) || (rc = own(iw.obs_flags, B * N)) || (rc = own(iw.obs_uv, B * N * 2)) || (rc = own(iw.obs_tag, B * N)) ||
+        (rc = own(iw.vid, B * N)) || (rc = own(iw.vft, B * N)) || (rc = own(iw.sid, B * N)) || (rc = own(iw.sfeat, B * N)) ||
+        (rc = own(iw.dcum, B * (N + 1))) || (rc = own(iw.pcum, B * (N + 1))) || (rc = own(iw.dmp, B * (M + 1))) ||
+        (rc = own(iw.drows, B * (M + 1))) || (rc = own(iw.mp_fin, B * M)) || (rc = own(iw.mp_shift, B * M))) {
         delete h;
         return rc;
     }
     // debug_flat before the first call reports empty windows
     const std::vector<int32_t> zeros(B * 3, 0);
-    if ((rc = upload_table(h->sizes, zeros.data(), zeros.size() * sizeof(int32_t)))) { delete h; return rc; }
+    if ((rc = upload_table(w.sizes, zeros.data(), zeros.size() * sizeof(int32_t)))) { delete h; return rc; }
     *out = h;
     return MYSLAM_OK;
 }
@@ -704,7 +652,7 @@ int myslam_backend_optimize_batch(myslam_backend* h, const int64_t* d_kf_id, dou
         return MYSLAM_ERR_INVALID;
     const BeTables T{d_kf_id, d_kf_pose, d_n_kf, d_mp_id, d_mp_pos, d_mp_outlier, d_n_mp, d_obs_mp, d_obs_kf, d_obs_flags, d_obs_uv, d_obs_tag, d_n_obs,
                      h->kf_cap, h->mp_cap, h->obs_cap};
-    const BeWork W = h->work();
+    const BeWork& W = h->w;
     const BeOut O{d_obs_report, d_mp_report, d_new_outlier_mp, d_n_new_outlier_mp, d_obs_chi2, d_rounds, d_n_outlier_edges, d_status};
     hipLaunchKernelGGL(k_backend_flatten, dim3(batch), dim3(BE_NT), 0, h->stream, T, W);
     MYSLAM_HIP_CHECK(hipGetLastError());
@@ -744,15 +692,17 @@ int myslam_backend_insert_keyframe_batch(myslam_backend* h, int64_t* d_kf_id, do
                   d_prior_mp_id, d_prior_kf_id, d_prior_uv, d_prior_tag, d_prior_flags, d_n_prior, d_n_prior ? prior_cap : 0,
                   d_outlier_mp_id, d_n_outlier_mp, d_n_outlier_mp ? outlier_cap : 0, window, min_dis_th};
     const InsOut O{d_feat_row, d_mp_new_row, d_removed_kf_id, d_removed_kf_row, d_dis, d_status};
-    hipLaunchKernelGGL(k_backend_insert, dim3(batch), dim3(BE_NT), 0, h->stream, T, I, h->insert_work(), O);
+    hipLaunchKernelGGL(k_backend_insert, dim3(batch), dim3(BE_NT), 0, h->stream, T, I, h->iw, O);
     MYSLAM_HIP_CHECK(hipGetLastError());
     return MYSLAM_OK;
 }
 
-static int be_fetch(myslam_backend* h, void* dst, const void* src, size_t bytes) {
+// device -> host, complete on return; on this thread's non-blocking stream, never the legacy stream (common.h).  The caller has waited for h->stream.
+static int be_fetch(void* dst, const void* src, size_t bytes) {
     if (!dst || bytes == 0) return MYSLAM_OK;
-    MYSLAM_HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
-    return MYSLAM_OK;
+    const hipStream_t st = host_call_stream();
+    if (!st) return MYSLAM_ERR_HIP;
+    return copy_sync(dst, src, bytes, hipMemcpyDeviceToHost, st);
 }
 
 int myslam_backend_debug_flat(myslam_backend* h, int item, int32_t* pose_src, int32_t* pt_src, int32_t* edge_pose, int32_t* edge_pt, double* edge_obs,
@@ -760,13 +710,14 @@ int myslam_backend_debug_flat(myslam_backend* h, int item, int32_t* pose_src, in
     if (!h || item < 0 || item >= h->max_batch || !sizes3) return MYSLAM_ERR_INVALID;
     MYSLAM_HIP_CHECK(hipStreamSynchronize(h->stream));
     const size_t b = (size_t)item, M = (size_t)h->mp_cap, N = (size_t)h->obs_cap;
+    const BeWork& w = h->w;
     int rc;
-    if ((rc = be_fetch(h, sizes3, h->sizes + 3 * b, 3 * sizeof(int32_t)))) return rc;
+    if ((rc = be_fetch(sizes3, w.sizes + 3 * b, 3 * sizeof(int32_t)))) return rc;
     const size_t P = (size_t)sizes3[0], L = (size_t)sizes3[1], E = (size_t)sizes3[2];
     if (pose_src) for (size_t i = 0; i < P; i++) pose_src[i] = (int32_t)i;       // pose slot = key-frame row
-    if ((rc = be_fetch(h, pt_src, h->pt_src + b * M, L * sizeof(int32_t))) || (rc = be_fetch(h, fixed, h->fixed + b * M, L)) ||
-        (rc = be_fetch(h, edge_pose, h->ep + b * N, E * sizeof(int32_t))) || (rc = be_fetch(h, edge_pt, h->el + b * N, E * sizeof(int32_t))) ||
-        (rc = be_fetch(h, edge_obs, h->obs + b * N * 2, E * 2 * sizeof(double))) || (rc = be_fetch(h, edge_src, h->edge_src + b * N, E * sizeof(int32_t))))
+    if ((rc = be_fetch(pt_src, w.pt_src + b * M, L * sizeof(int32_t))) || (rc = be_fetch(fixed, w.fixed + b * M, L)) ||
+        (rc = be_fetch(edge_pose, w.ep + b * N, E * sizeof(int32_t))) || (rc = be_fetch(edge_pt, w.el + b * N, E * sizeof(int32_t))) ||
+        (rc = be_fetch(edge_obs, w.obs + b * N * 2, E * 2 * sizeof(double))) || (rc = be_fetch(edge_src, w.edge_src + b * N, E * sizeof(int32_t))))
         return rc;
     return MYSLAM_OK;
 }
@@ -776,16 +727,17 @@ int myslam_backend_debug_solved(myslam_backend* h, int item, double* poses, doub
     if (!h || item < 0 || item >= h->max_batch) return MYSLAM_ERR_INVALID;
     MYSLAM_HIP_CHECK(hipStreamSynchronize(h->stream));
     const size_t b = (size_t)item, K = (size_t)h->kf_cap, M = (size_t)h->mp_cap, N = (size_t)h->obs_cap;
+    const BeWork& w = h->w;
     int32_t sz[3];
     int rc;
-    if ((rc = be_fetch(h, sz, h->sizes + 3 * b, sizeof(sz)))) return rc;
+    if ((rc = be_fetch(sz, w.sizes + 3 * b, sizeof(sz)))) return rc;
     const size_t P = (size_t)sz[0], L = (size_t)sz[1], E = (size_t)sz[2];
-    if ((rc = be_fetch(h, poses, h->poses + b * K * 7, P * 7 * sizeof(double))) || (rc = be_fetch(h, points, h->pts + b * M * 3, L * 3 * sizeof(double))) ||
-        (rc = be_fetch(h, edge_chi2, h->chi2 + b * N, E * sizeof(double))) || (rc = be_fetch(h, edge_outlier, h->out + b * N, E)))
+    if ((rc = be_fetch(poses, w.poses + b * K * 7, P * 7 * sizeof(double))) || (rc = be_fetch(points, w.pts + b * M * 3, L * 3 * sizeof(double))) ||
+        (rc = be_fetch(edge_chi2, w.chi2 + b * N, E * sizeof(double))) || (rc = be_fetch(edge_outlier, w.out + b * N, E)))
         return rc;
     if (rounds_outliers2) {
         rounds_outliers2[0] = 0; rounds_outliers2[1] = 0;
-        if (E && ((rc = be_fetch(h, rounds_outliers2, h->rounds + b, sizeof(int32_t))) || (rc = be_fetch(h, rounds_outliers2 + 1, h->nout + b, sizeof(int32_t)))))
+        if (E && ((rc = be_fetch(rounds_outliers2, w.rounds + b, sizeof(int32_t))) || (rc = be_fetch(rounds_outliers2 + 1, w.nout + b, sizeof(int32_t)))))
             return rc;
     }
     return MYSLAM_OK;

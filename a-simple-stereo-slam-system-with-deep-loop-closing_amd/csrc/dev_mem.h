@@ -1,6 +1,9 @@
 // dev_mem.h — the one owner of device and pinned host memory.  No HIP header: plain C++ (tests/cpp/dev_mem_test.cpp links its own raw_alloc / raw_free).
 #pragma once
 #include <stddef.h>
+#include <stdint.h>
+
+#include <vector>
 
 #include "../../include/myslam_hip.h"
 
@@ -49,6 +52,23 @@ class Buf {
     size_t n_ = 0;
 };
 template <class T> using PinBuf = Buf<T, true>;
+
+// The blocks of one handle whose pointers live in the argument structs of its kernels: own() fills such a pointer by name at the moment its block is
+// allocated, so no list of buffers has to be matched to a list of fields.  Destroying the set frees every block it gave out.
+class BufSet {
+  public:
+    // p = a new block of n elements (256 bytes at least), nullptr if it could not be had; -> renew's code
+    template <class T>
+    int own(T*& p, size_t n, int oom_code = MYSLAM_ERR_HIP) {
+        bufs_.emplace_back();
+        const int rc = bufs_.back().renew(n * sizeof(T) < 256 ? 256 : n * sizeof(T), oom_code);
+        p = reinterpret_cast<T*>(bufs_.back().get());
+        return rc;
+    }
+
+  private:
+    std::vector<Buf<uint8_t>> bufs_;
+};
 
 // Growth of a group of buffers guarded by the logical size `cap`: `renews` (-> 0 or the first renew's error) runs with cap == 0, and cap becomes `want`
 // only when all of them succeeded — a failed growth leaves a guard that refuses every size.

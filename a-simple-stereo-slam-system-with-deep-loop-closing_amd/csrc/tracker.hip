@@ -294,7 +294,7 @@ struct myslam_tracker {
     size_t pyrBytes = 0;
     TrkArgs a{};
     uint8_t* d_pyr = nullptr;
-    std::vector<Buf<uint8_t>> bufs;        // owns every block that `a` and d_pyr name
+    BufSet mem;                            // owns every block that `a` and d_pyr name
     std::vector<char> hasImage;
 };
 
@@ -302,12 +302,7 @@ static int trk_alloc_all(myslam_tracker* h) {
     TrkArgs& a = h->a;
     const size_t S = h->S, F = S * h->cap, L = S * h->lmCap;
     int rc = 0;
-    auto own = [&](auto*& p, size_t n) -> int {               // p = a block of n elements (256 bytes at least) that the handle owns
-        h->bufs.emplace_back();
-        const int rc = h->bufs.back().renew(std::max<size_t>(256, n * sizeof(*p)));
-        p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(h->bufs.back().get());
-        return rc;
-    };
+    auto own = [&](auto*& p, size_t n) { return h->mem.own(p, n); };
     if ((rc = own(a.st, S)) || (rc = own(a.xy, F * 2)) || (rc = own(a.lm, F)) || (rc = own(a.lmPos, L * 3)) || (rc = own(a.lmOutl, L)) ||
         (rc = own(a.outlList, F * 2)) || (rc = own(a.img, 2 * a.imgSel)) || (rc = own(h->d_pyr, 2 * S * h->pyrBytes)) ||
         (rc = own(a.sel, S)) || (rc = own(a.counts, S)) || (rc = own(a.p0, F * 2)) || (rc = own(a.p1, F * 2)) || (rc = own(a.nxt, F * 2)) ||

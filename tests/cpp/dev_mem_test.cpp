@@ -1,4 +1,4 @@
-// csrc/dev_mem.h on the host: Buf and regrow over a malloc-backed raw_alloc / raw_free that counts live blocks and can fail the k-th call.
+// csrc/dev_mem.h on the host: Buf, BufSet and regrow over a malloc-backed raw_alloc / raw_free that counts live blocks and can fail the k-th call.
 // Built with AddressSanitizer + UBSan by tests/test_dev_mem.py; exit status 0 and "DEV MEM OK" = every check held and nothing leaked.
 #include <stdio.h>
 #include <stdlib.h>
@@ -157,12 +157,53 @@ static void groups() {
     CHECK(regrow(cap, 9, [&]() -> int { return t.renew(9); }) == MYSLAM_OK && cap == 9);
 }
 
+struct Args { double* a = nullptr; int32_t* b = nullptr; uint8_t* c = nullptr; };      // as a kernel's argument struct: filled by member name
+
+static void buf_set() {
+    {
+        BufSet s;
+        Args x;
+        arm(0);
+        CHECK(s.own(x.a, 100, MYSLAM_ERR_CAPACITY) == MYSLAM_OK && s.own(x.b, 7, MYSLAM_ERR_CAPACITY) == MYSLAM_OK && s.own(x.c, 300) == MYSLAM_OK);
+        CHECK(g_live == 3 && x.a && x.b && x.c);
+        CHECK((void*)x.a != (void*)x.b && (void*)x.b != (void*)x.c && (void*)x.a != (void*)x.c);
+        x.a[99] = 1.0; x.c[299] = 1;                           // whole elements of the asked-for size (ASan checks the bytes)
+        for (int i = 0; i < 64; i++) x.b[i] = i;               // 7 x 4 bytes asked for: the block has the floor of 256
+        // no element at all still is a block of 256 bytes
+        uint8_t* z = nullptr;
+        CHECK(s.own(z, 0) == MYSLAM_OK && z && g_live == 4);
+        z[0] = 1; z[255] = 2;
+        // more blocks than a vector's first capacities: the pointers given out earlier stay what they were
+        double* const a0 = x.a;
+        for (int i = 0; i < 40; i++) { float* f = nullptr; CHECK(s.own(f, i) == MYSLAM_OK && f); f[63] = 1.0f; }
+        CHECK(g_live == 44 && x.a == a0 && x.a[99] == 1.0 && x.b[63] == 63);
+    }
+    CHECK(g_live == 0);                                        // destroying the set frees every block it gave out
+    // the second of three allocations fails: out of memory is the caller's oom_code, any other failure passes through; the pointer is null
+    const int codes[2][2] = {{MYSLAM_ERR_CAPACITY, MYSLAM_ERR_UNSUPPORTED}, {MYSLAM_ERR_HIP, MYSLAM_ERR_HIP}};
+    for (const auto& c : codes) {
+        {
+            BufSet s;
+            Args x;
+            x.b = reinterpret_cast<int32_t*>(&x);              // stale: a failed own must not leave it
+            arm(2, c[0]);
+            CHECK(s.own(x.a, 10, MYSLAM_ERR_UNSUPPORTED) == MYSLAM_OK && x.a && g_live == 1);
+            CHECK(s.own(x.b, 10, MYSLAM_ERR_UNSUPPORTED) == c[1] && x.b == nullptr && g_live == 1);
+            CHECK(s.own(x.c, 10, MYSLAM_ERR_UNSUPPORTED) == MYSLAM_OK && x.c && g_live == 2);      // the set stays usable
+        }
+        CHECK(g_live == 0);
+    }
+    arm(0);
+}
+
 int main() {
     single_buffer();
     CHECK(g_live == 0);
     moves();
     CHECK(g_live == 0);
     groups();
+    CHECK(g_live == 0);
+    buf_set();
     CHECK(g_live == 0 && g_pinned_live == 0);
     printf("DEV MEM OK\n");
     return 0;
