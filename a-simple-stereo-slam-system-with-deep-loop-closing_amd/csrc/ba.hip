@@ -1325,6 +1325,18 @@ static size_t ba_lds(int maxP, int maxL, int maxE, int nwaves) {
 constexpr int BA_WIDE_BELOW = MYSLAM_BA_WIDE_BELOW;      // fewer windows than this per call: 1024 threads per window (latency), else 256 (throughput)
 constexpr int BA_LISTS_BELOW = MYSLAM_BA_LISTS_BELOW;    // fewer windows than this per call: the staged pose-list form when it fits LDS
 
+// the six inputs every BA host form stages: poses and points (written back when `solve`), observations, the two edge tables, the fixed flags (optional)
+struct BaHostIn { int p, x, o, ep, el, f; };
+static BaHostIn ba_host_inputs(HostCall& hc, bool solve, const double* poses, int nposes, const double* points, int npts, const double* obs,
+                               const int32_t* edge_pose, const int32_t* edge_pt, int nedges, const uint8_t* fixed_pt) {
+    BaHostIn i;                                            // solve: the caller's arrays are its own (non-const) ones
+    i.p = solve ? hc.inout(const_cast<double*>(poses), (size_t)nposes * 7) : hc.in(poses, (size_t)nposes * 7);
+    i.x = solve ? hc.inout(const_cast<double*>(points), (size_t)npts * 3) : hc.in(points, (size_t)npts * 3);
+    i.o = hc.in(obs, (size_t)nedges * 2); i.ep = hc.in(edge_pose, (size_t)nedges); i.el = hc.in(edge_pt, (size_t)nedges);
+    i.f = hc.in(fixed_pt, fixed_pt ? (size_t)npts : 0);
+    return i;
+}
+
 static int ba_launch(const BaArgs& a, int nwin, hipStream_t s) {
     // a handful of windows (a live stream's key-frame): 1024 threads per window and, when the window fits LDS, the pose-list form.  Batches keep
     // 256 threads and the ds_add_f64 form: with two blocks per CU their time is the latency of a few resident waves either way, and the second
@@ -1376,18 +1388,16 @@ int myslam_ba_build(const double* poses, int nposes, const double* points, int n
     if (nedges > 0 && (!edge_pose || !edge_pt || !obs || !Hpl || !chi2)) return MYSLAM_ERR_INVALID;
     for (int k = 0; k < nedges; k++)
         if (edge_pose[k] < 0 || edge_pose[k] >= nposes || edge_pt[k] < 0 || edge_pt[k] >= npts) return MYSLAM_ERR_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MYSLAM_ERR_HIP;
+    if (need_device()) return MYSLAM_ERR_HIP;
     const int E = nedges > 0 ? nedges : 1;
     HostCall hc;
-    const int i_p = hc.in(poses, (size_t)nposes * 7), i_x = hc.in(points, (size_t)npts * 3), i_o = hc.in(obs, (size_t)nedges * 2);
-    const int i_ep = hc.in(edge_pose, (size_t)nedges), i_el = hc.in(edge_pt, (size_t)nedges), i_f = hc.in(fixed_pt, fixed_pt ? (size_t)npts : 0);
+    const BaHostIn i = ba_host_inputs(hc, false, poses, nposes, points, npts, obs, edge_pose, edge_pt, nedges, fixed_pt);
     const int o_pp = hc.out(Hpp, (size_t)nposes * 36), o_ll = hc.out(Hll, (size_t)npts * 9), o_pl = hc.out(Hpl, (size_t)nedges * 18);
     const int o_bp = hc.out(bp, (size_t)nposes * 6), o_bl = hc.out(bl, (size_t)npts * 3), o_c = hc.out(chi2, (size_t)nedges);
     int rc = hc.upload();
     if (rc) return rc;
-    BaArgs a{hc.dev<double>(i_p), hc.dev<double>(i_x), hc.dev<int32_t>(i_ep), hc.dev<int32_t>(i_el), hc.dev<double>(i_o),
-             fixed_pt ? hc.dev<uint8_t>(i_f) : nullptr, nullptr, nposes, npts, nedges, nposes, npts, E,
+    BaArgs a{hc.dev<double>(i.p), hc.dev<double>(i.x), hc.dev<int32_t>(i.ep), hc.dev<int32_t>(i.el), hc.dev<double>(i.o),
+             fixed_pt ? hc.dev<uint8_t>(i.f) : nullptr, nullptr, nposes, npts, nedges, nposes, npts, E,
              fx, fy, cx, cy, huber_delta, hc.dev<double>(o_pp), hc.dev<double>(o_ll), hc.dev<double>(o_pl), hc.dev<double>(o_bp),
              hc.dev<double>(o_bl), hc.dev<double>(o_c)};
     if ((rc = ba_launch(a, 1, hc.stream()))) return rc;
@@ -1410,19 +1420,17 @@ int myslam_ba_optimize(double* poses, int nposes, double* points, int npts, cons
                        const double* obs, int nedges, const uint8_t* fixed_pt, double fx, double fy, double cx, double cy,
                        double huber_delta, int max_iters, double* final_chi2, int* iters) {
     if (!poses || !points || nposes < 1 || npts < 1 || nedges < 1 || !edge_pose || !edge_pt || !obs || max_iters < 1) return MYSLAM_ERR_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MYSLAM_ERR_HIP;
+    if (need_device()) return MYSLAM_ERR_HIP;
     HostCall hc;
     int32_t st[2] = {0, 0}; double chi = 0;
-    const int i_p = hc.inout(poses, (size_t)nposes * 7), i_x = hc.inout(points, (size_t)npts * 3), i_o = hc.in(obs, (size_t)nedges * 2);
-    const int i_ep = hc.in(edge_pose, (size_t)nedges), i_el = hc.in(edge_pt, (size_t)nedges), i_f = hc.in(fixed_pt, fixed_pt ? (size_t)npts : 0);
+    const BaHostIn i = ba_host_inputs(hc, true, poses, nposes, points, npts, obs, edge_pose, edge_pt, nedges, fixed_pt);
     const size_t wneed = std::max((size_t)nedges * 18, ba_opt_scratch_need(npts, nedges, true));
     const int o_st = hc.out(st, 2), o_chi = hc.out(&chi, 1), t_w = hc.tmp<double>(wneed);
     int rc = hc.upload();
     if (rc) return rc;
     int32_t* d_st = hc.dev<int32_t>(o_st);
-    BaOptArgs a{hc.dev<double>(i_p), hc.dev<double>(i_x), hc.dev<int32_t>(i_ep), hc.dev<int32_t>(i_el), hc.dev<double>(i_o),
-                fixed_pt ? hc.dev<uint8_t>(i_f) : nullptr, nullptr, nposes, npts, nedges, nposes, npts, nedges,
+    BaOptArgs a{hc.dev<double>(i.p), hc.dev<double>(i.x), hc.dev<int32_t>(i.ep), hc.dev<int32_t>(i.el), hc.dev<double>(i.o),
+                fixed_pt ? hc.dev<uint8_t>(i.f) : nullptr, nullptr, nposes, npts, nedges, nposes, npts, nedges,
                 fx, fy, cx, cy, huber_delta, max_iters, hc.dev<double>(t_w), hc.dev<double>(o_chi), d_st + 1, d_st, 1, 0.0, nullptr, nullptr, nullptr, nullptr, wneed};
     if ((rc = ba_opt_launch(a, 1, hc.stream()))) return rc;
     if ((rc = hc.download())) return rc;
@@ -1458,20 +1466,18 @@ int myslam_ba_optimize_active_map(double* poses, int nposes, double* points, int
     if (!poses || !points || nposes < 1 || npts < 1 || nedges < 1 || !edge_pose || !edge_pt || !obs || max_rounds < 1 || iters_per_round < 1 ||
         !edge_chi2 || !outlier)
         return MYSLAM_ERR_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MYSLAM_ERR_HIP;
+    if (need_device()) return MYSLAM_ERR_HIP;
     HostCall hc;
     int32_t st[3] = {0, 0, 0};
-    const int i_p = hc.inout(poses, (size_t)nposes * 7), i_x = hc.inout(points, (size_t)npts * 3), i_o = hc.in(obs, (size_t)nedges * 2);
-    const int i_ep = hc.in(edge_pose, (size_t)nedges), i_el = hc.in(edge_pt, (size_t)nedges), i_f = hc.in(fixed_pt, fixed_pt ? (size_t)npts : 0);
+    const BaHostIn i = ba_host_inputs(hc, true, poses, nposes, points, npts, obs, edge_pose, edge_pt, nedges, fixed_pt);
     const int o_st = hc.out(st, 3), o_chi = hc.out(edge_chi2, (size_t)nedges), o_out = hc.out(outlier, (size_t)nedges);
     const size_t wneed = std::max((size_t)nedges * 18, ba_opt_scratch_need(npts, nedges, true));
     const int t_w = hc.tmp<double>(wneed);
     int rc = hc.upload();
     if (rc) return rc;
     int32_t* d_st = hc.dev<int32_t>(o_st);
-    BaOptArgs a{hc.dev<double>(i_p), hc.dev<double>(i_x), hc.dev<int32_t>(i_ep), hc.dev<int32_t>(i_el), hc.dev<double>(i_o),
-                fixed_pt ? hc.dev<uint8_t>(i_f) : nullptr, nullptr, nposes, npts, nedges, nposes, npts, nedges,
+    BaOptArgs a{hc.dev<double>(i.p), hc.dev<double>(i.x), hc.dev<int32_t>(i.ep), hc.dev<int32_t>(i.el), hc.dev<double>(i.o),
+                fixed_pt ? hc.dev<uint8_t>(i.f) : nullptr, nullptr, nposes, npts, nedges, nposes, npts, nedges,
                 fx, fy, cx, cy, huber_delta, iters_per_round, hc.dev<double>(t_w), nullptr, nullptr, d_st, max_rounds, chi2_th,
                 hc.dev<double>(o_chi), hc.dev<uint8_t>(o_out), d_st + 1, d_st + 2, wneed};
     if ((rc = ba_opt_launch(a, 1, hc.stream()))) return rc;
@@ -1498,17 +1504,7 @@ static void pose_only_launch(const PoseOnlyArgs& a, int batch, int max_edges, hi
 
 extern "C++" {
 namespace myslam_hip {
-// the multi-stream tracker's pose-only launch (tracker.hip, declared in frontend_launch.h): the batch entry point below without its argument checks
-int pose_only_bank_launch(double* d_poses, const double* d_pts3d, const double* d_obs, const int32_t* d_counts, int batch, int cap, double fx, double fy,
-                          double cx, double cy, double chi2_th, int rounds, int iters, uint8_t* d_outlier, int32_t* d_n_inliers, int32_t* d_status,
-                          hipStream_t s) {
-    PoseOnlyArgs a{d_poses, d_pts3d, d_obs, d_counts, 0, cap, fx, fy, cx, cy, chi2_th, rounds, iters, 0, d_outlier, d_n_inliers, d_status};
-    ScopedProf sp(P_BA, s);
-    pose_only_launch(a, batch, cap, s);
-    MYSLAM_HIP_CHECK(hipGetLastError());
-    return MYSLAM_OK;
-}
-// the loop closer's chain (pnp.hip, myslam_loop_verify_batch): with pre_optimize
+// the batch entry point below without its argument checks: the loop closer's chain (pnp.hip, myslam_loop_verify_batch) and the entry point itself
 int pose_only_loop_launch(double* d_poses, const double* d_pts3d, const double* d_obs, const int32_t* d_counts, int batch, int cap, double fx, double fy,
                           double cx, double cy, double chi2_th, int rounds, int iters, int pre_optimize, uint8_t* d_outlier, int32_t* d_n_inliers,
                           int32_t* d_status, hipStream_t s) {
@@ -1517,6 +1513,12 @@ int pose_only_loop_launch(double* d_poses, const double* d_pts3d, const double* 
     pose_only_launch(a, batch, cap, s);
     MYSLAM_HIP_CHECK(hipGetLastError());
     return MYSLAM_OK;
+}
+// the multi-stream tracker's (tracker.hip): no pre-optimisation.  Both are declared in frontend_launch.h.
+int pose_only_bank_launch(double* d_poses, const double* d_pts3d, const double* d_obs, const int32_t* d_counts, int batch, int cap, double fx, double fy,
+                          double cx, double cy, double chi2_th, int rounds, int iters, uint8_t* d_outlier, int32_t* d_n_inliers, int32_t* d_status,
+                          hipStream_t s) {
+    return pose_only_loop_launch(d_poses, d_pts3d, d_obs, d_counts, batch, cap, fx, fy, cx, cy, chi2_th, rounds, iters, 0, d_outlier, d_n_inliers, d_status, s);
 }
 // Backend::OptimizeActiveMap's solve stage for the batched back end (backend.hip, declared in backend_launch.h): myslam_ba_optimize_active_map_batch
 // without its argument checks, with the scratch stride the host-pointer calls use and a per-window skip flag
@@ -1539,18 +1541,14 @@ int myslam_pose_only_optimize_batch(double* d_poses, const double* d_pts3d, cons
     if (!d_poses || !d_pts3d || !d_obs || !d_counts || batch < 1 || cap < 1 || rounds < 1 || iters < 1 || pre_optimize < 0 || !d_outlier ||
         !d_n_inliers || !d_status)
         return MYSLAM_ERR_INVALID;
-    PoseOnlyArgs a{d_poses, d_pts3d, d_obs, d_counts, 0, cap, fx, fy, cx, cy, chi2_th, rounds, iters, pre_optimize, d_outlier, d_n_inliers, d_status};
-    ScopedProf sp(P_BA, (hipStream_t)hip_stream);
-    pose_only_launch(a, batch, cap, (hipStream_t)hip_stream);
-    MYSLAM_HIP_CHECK(hipGetLastError());
-    return MYSLAM_OK;
+    return pose_only_loop_launch(d_poses, d_pts3d, d_obs, d_counts, batch, cap, fx, fy, cx, cy, chi2_th, rounds, iters, pre_optimize, d_outlier, d_n_inliers, d_status,
+                                 (hipStream_t)hip_stream);
 }
 
 int myslam_pose_only_optimize(double* pose7, const double* pts3d, const double* obs, int n, double fx, double fy, double cx, double cy,
                               double chi2_th, int rounds, int iters, int pre_optimize, uint8_t* outlier, int* n_inliers) {
     if (!pose7 || n < 0 || (n > 0 && (!pts3d || !obs || !outlier)) || rounds < 1 || iters < 1 || pre_optimize < 0) return MYSLAM_ERR_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MYSLAM_ERR_HIP;
+    if (need_device()) return MYSLAM_ERR_HIP;
     const int m = n > 0 ? n : 1;
     HostCall hc;
     int32_t st[2] = {0, 0};

@@ -598,8 +598,7 @@ int myslam_backend_create(myslam_backend** out, int max_batch, int kf_cap, int m
     if (!out || max_batch < 1 || max_batch > 65535 || kf_cap < 1 || mp_cap < 1 || obs_cap < 1) return MYSLAM_ERR_INVALID;
     if (kf_cap > MYSLAM_BA_MAX_WINDOW_POSES) return MYSLAM_ERR_UNSUPPORTED;
     if (mp_cap > (1 << 24) || obs_cap > (1 << 24)) return MYSLAM_ERR_CAPACITY;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MYSLAM_ERR_HIP;
+    if (need_device()) return MYSLAM_ERR_HIP;
     myslam_backend* h = new myslam_backend();
     h->max_batch = max_batch; h->kf_cap = kf_cap; h->mp_cap = mp_cap; h->obs_cap = obs_cap;
     h->wstride = ba_active_map_scratch_doubles(mp_cap, obs_cap);

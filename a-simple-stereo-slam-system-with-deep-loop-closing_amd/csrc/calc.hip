@@ -1098,8 +1098,7 @@ static int lcd_create(myslam_lcd** out, const myslam_calc_layer* layers, int nla
     int rc = walk_layers(layers, nlayers, shapes, need);
     if (rc) return rc;
     if (nweights != need) return MYSLAM_ERR_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MYSLAM_ERR_HIP;
+    if (need_device()) return MYSLAM_ERR_HIP;
     myslam_lcd* h = new myslam_lcd();
     h->layers.assign(layers, layers + nlayers); h->shapes = shapes;
     h->fused = match_fused(layers, nlayers);

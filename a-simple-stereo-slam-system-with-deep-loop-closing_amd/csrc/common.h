@@ -61,9 +61,9 @@ struct ScopedProf {
 // stream depend on a capturing blocking stream") and poisons that thread's recording (tests/test_gpu_threads.py: one thread makes a plan while another
 // records its one-frame call).  This one copies on a process-wide NON-BLOCKING stream and waits for that stream only.
 int upload_table(void* dst, const void* src, size_t bytes);
-// The stream of the synchronous host-pointer entry points that bring no stream of their own (PnP-RANSAC, pose graph, map-point correction): one NON-BLOCKING
-// stream per calling thread, created on first use — kernels, copies and memsets of such a call all go through it, and the call synchronises it before it reads
-// a result or returns.  nullptr = the stream could not be created.
+// The one stream of the calling thread for synchronous work that brings no stream of its own: the staging arena's (HostArena below), NON-BLOCKING, on the
+// device the thread has selected NOW, created on first use.  Every HostCall runs on it, and so do the loop database's clear at create, the debug reads of the
+// back end and the tracker and myslam_debug_peek; whoever uses it synchronises it before reading a result.  nullptr = the stream could not be created.
 hipStream_t host_call_stream();
 // copy through `st`, complete on return (pageable host memory on either side)
 inline int copy_sync(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t st) {
@@ -80,44 +80,50 @@ inline bool stream_is_capturing(hipStream_t s) {
     return st == hipStreamCaptureStatusActive;
 }
 
+// is there a device at all?  (Every entry point that allocates or launches asks first: no CPU fallback exists.)  Leaves no sticky HIP error behind.
+inline int need_device() {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { (void)hipGetLastError(); return MYSLAM_ERR_HIP; }
+    return MYSLAM_OK;
+}
+
 // ---- staging of the host-pointer ("drop-in", B = 1) entry points --------------------------------------------------------------
 // One grow-only device block, one pinned host block and one stream per calling THREAD, carved into 256-byte aligned pieces per
-// call: no allocation per call, one host->device and one device->host copy per call, and nothing to free on an error
-// return (the arena owns the memory).  Pieces are laid out [in][inout][out][tmp]; `upload()` copies in + inout, `download()` copies
-// inout + out back and synchronises.  Usage: register pieces, upload(), launch on stream() with dev<T>(piece), download().
+// call (CallLayout, dev_mem.h): no allocation per call (but for a device block that trim() gave back), one host->device and one device->host copy per call, and nothing to free on an
+// error return (the arena owns the memory).  Pieces are laid out [in][inout][out][zero][tmp]; `upload()` copies in + inout and clears zero,
+// `download()` copies inout + out back and synchronises, `fetch()` reads one out piece in the middle of a call.  The pinned block mirrors
+// in, inout and out only.  Usage: register pieces, upload(), launch on stream() with dev<T>(piece), download().
 struct HostArena {
-    Buf<uint8_t> d; PinBuf<uint8_t> h; hipStream_t s = nullptr;
+    ArenaMem m; hipStream_t s = nullptr;
     int dev = -1;               // the device block, stream and pinned block belong to: a thread that switches devices gets a fresh arena
     ~HostArena();
     void release();
-    int ensure(size_t bytes);
+    int open();                 // the stream of the device selected now
+    int ensure(size_t dev_bytes, size_t host_bytes);
+    void trim();                // at the end of every call: a device block above 64 MB goes back (prof.hip), anything smaller stays for the thread's next call
 };
 HostArena& host_arena();
 
 class HostCall {
   public:
-    enum Kind { IN = 0, INOUT = 1, OUT = 2, TMP = 3 };
     HostCall() : A(host_arena()) {}
-    template <class T> int in(const T* p, size_t n) { return add(IN, p, nullptr, n * sizeof(T)); }
-    template <class T> int inout(T* p, size_t n) { return add(INOUT, p, p, n * sizeof(T)); }
-    template <class T> int out(T* p, size_t n) { return add(OUT, nullptr, p, n * sizeof(T)); }
-    template <class T> int tmp(size_t n) { return add(TMP, nullptr, nullptr, n * sizeof(T)); }
+    ~HostCall() { A.trim(); }
+    template <class T> int in(const T* p, size_t n) { return L.add(CallLayout::IN, p, nullptr, n * sizeof(T)); }
+    // copy_back == false: download() brings the piece to its mirror only, and the caller takes it from host<T>() once the call is known to have succeeded
+    template <class T> int inout(T* p, size_t n, bool copy_back = true) { return L.add(CallLayout::INOUT, p, copy_back ? p : nullptr, n * sizeof(T)); }
+    template <class T> int out(T* p, size_t n) { return L.add(CallLayout::OUT, nullptr, p, n * sizeof(T)); }      // p == nullptr: read it through host<T>()
+    template <class T> int zero(size_t n) { return L.add(CallLayout::ZERO, nullptr, nullptr, n * sizeof(T)); }
+    template <class T> int tmp(size_t n) { return L.add(CallLayout::TMP, nullptr, nullptr, n * sizeof(T)); }
     int upload();
     int download();
-    template <class T> T* dev(int piece) const { return reinterpret_cast<T*>(A.d + pc[piece].off); }
+    int fetch(int piece);       // one OUT piece device -> pinned mirror, complete on return
+    template <class T> T* dev(int piece) const { return reinterpret_cast<T*>(A.m.d + L.pc[piece].off); }
+    template <class T> const T* host(int piece) const { return reinterpret_cast<const T*>(A.m.h + L.pc[piece].off); }      // INOUT / OUT, after download() or fetch()
     hipStream_t stream() const { return A.s; }
 
   private:
-    struct Piece { Kind kind; const void* src; void* dst; size_t bytes, off; };
-    int add(Kind k, const void* src, void* dst, size_t bytes) {
-        if (npc >= MAXP) { overflow = true; return 0; }           // upload() refuses the call; piece 0 keeps dev<T>() in bounds until then
-        pc[npc] = {k, src, dst, bytes, 0};
-        return npc++;
-    }
-    static constexpr int MAXP = 24;
     HostArena& A;
-    Piece pc[MAXP]; int npc = 0; bool overflow = false;
-    size_t endIn = 0, begOut = 0, endOut = 0;
+    CallLayout L;
 };
 
 // ---- what a recorded step (graph.hip) and a loop-database query context (lcddb.hip) know about each other ------------------------

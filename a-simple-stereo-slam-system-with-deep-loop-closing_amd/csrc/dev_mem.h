@@ -80,4 +80,59 @@ int regrow(Cap& cap, Cap want, F&& renews) {
     return rc;
 }
 
+// ---- the host-pointer entry points' staging, the part that needs no HIP call (HostCall and HostArena, common.h, put the copies and the stream on top) ----
+// The pieces of one call, each 256-byte aligned, laid out by kind: [in][inout][out][zero][tmp].  [0, endIn) goes up in one copy, [begOut, endOut) comes back
+// in one, [begZero, endZero) is cleared by one memset, TMP is whatever an earlier call left there.  Only [0, endOut) has a pinned mirror.
+class CallLayout {
+  public:
+    enum Kind { IN = 0, INOUT = 1, OUT = 2, ZERO = 3, TMP = 4 };
+    static constexpr int MAXP = 32;
+    struct Piece { Kind kind; const void* src; void* dst; size_t bytes, off; };
+
+    // -> the piece's number; past MAXP pieces place() refuses the call, and piece 0 keeps every offset lookup in bounds until then
+    int add(Kind k, const void* src, void* dst, size_t bytes) {
+        if (npc >= MAXP) { overflow = true; return 0; }
+        pc[npc] = {k, src, dst, bytes, 0};
+        return npc++;
+    }
+    int place() {
+        if (overflow) return MYSLAM_ERR_CAPACITY;
+        size_t off = 0;
+        for (int k = IN; k <= TMP; k++) {
+            if (k == INOUT) begOut = off;
+            if (k == ZERO) begZero = off;
+            for (int i = 0; i < npc; i++)
+                if (pc[i].kind == k) { pc[i].off = off; off += (pc[i].bytes + 255) & ~(size_t)255; }
+            if (k == INOUT) endIn = off;
+            if (k == OUT) endOut = off;
+            if (k == ZERO) endZero = off;
+        }
+        total = off;
+        return MYSLAM_OK;
+    }
+    size_t host_bytes() const { return endOut; }       // the pinned block mirrors what is copied, never ZERO or TMP
+    size_t dev_bytes() const { return total; }
+
+    Piece pc[MAXP];
+    int npc = 0;
+    bool overflow = false;
+    size_t endIn = 0, begOut = 0, endOut = 0, begZero = 0, endZero = 0, total = 0;
+};
+
+// The two blocks of a staging arena.  Grow-only, each by its own need; a failed growth frees both, so neither size outlives its block's partner.
+struct ArenaMem {
+    Buf<uint8_t> d; PinBuf<uint8_t> h;
+    bool fits(size_t dev_bytes, size_t host_bytes) const { return d && h && dev_bytes <= d.size() && host_bytes <= h.size(); }
+    // whoever calls this has waited for the work that uses the blocks
+    int grow(size_t dev_bytes, size_t host_bytes) {
+        int rc = MYSLAM_OK;
+        if (!d || d.size() < dev_bytes) rc = d.renew(padded(dev_bytes));
+        if (!rc && (!h || h.size() < host_bytes)) rc = h.renew(padded(host_bytes));
+        if (rc) release();
+        return rc;
+    }
+    void release() { d.release(); h.release(); }
+    static size_t padded(size_t bytes) { return (bytes + (bytes >> 2) + 65536) & ~(size_t)65535; }      // a quarter of headroom, whole 64 KB, never nothing
+};
+
 }  // namespace myslam_hip

@@ -546,8 +546,7 @@ extern "C" {
 
 int myslam_lcddb_create(myslam_lcddb** out, int capacity) {
     if (!out || capacity < 1) return MYSLAM_ERR_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MYSLAM_ERR_HIP;
+    if (need_device()) return MYSLAM_ERR_HIP;
     myslam_lcddb* h = new myslam_lcddb();
     h->ctxs.push_back(ctx_new(h, nullptr, true));
     const int rowsPerBlock = DB_WAVES * DB_ROWS_PER_WAVE;

@@ -425,8 +425,7 @@ extern "C" {
 
 int myslam_lk_create(myslam_lk** out, int win, int max_level, int max_iters, float eps, float min_eig_threshold) {
     if (!out || win < 3 || win > LK_MAXWIN || (win & 1) == 0 || max_level < 0 || max_level > LK_MAXL || max_iters < 1 || !(eps >= 0)) return MYSLAM_ERR_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MYSLAM_ERR_HIP;
+    if (need_device()) return MYSLAM_ERR_HIP;
     myslam_lk* h = new myslam_lk();
     h->win = win; h->max_level = max_level; h->max_iters = max_iters; h->eps = eps; h->min_eig = min_eig_threshold;
     *out = h;

@@ -490,8 +490,7 @@ int myslam_loop_corrector_create(myslam_loop_corrector** out, int max_batch, int
     if (!out || max_batch < 1 || max_batch > 65535 || kf_cap < 1 || edge_cap < 1 || active_cap < 1 || active_cap > kf_cap || point_cap < 0)
         return MYSLAM_ERR_INVALID;
     if (kf_cap > (1 << 20) || edge_cap > (1 << 20)) return MYSLAM_ERR_CAPACITY;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MYSLAM_ERR_HIP;
+    if (need_device()) return MYSLAM_ERR_HIP;
     myslam_loop_corrector* h = new myslam_loop_corrector();
     h->max_batch = max_batch; h->kf_cap = kf_cap; h->edge_cap = edge_cap; h->active_cap = active_cap; h->point_cap = point_cap;
     const size_t n = (size_t)kf_cap, E = (size_t)edge_cap;

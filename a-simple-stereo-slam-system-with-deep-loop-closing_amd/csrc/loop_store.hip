@@ -164,8 +164,7 @@ extern "C" {
 int myslam_loop_store_create(myslam_loop_store** out, int kf_capacity, int cap, int feat_cap) {
     if (!out || kf_capacity <= 0 || cap <= 0 || feat_cap <= 0) return MYSLAM_ERR_INVALID;
     if (cap > LS_MAX_CAP || feat_cap > LS_MAX_FEAT) return MYSLAM_ERR_CAPACITY;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { (void)hipGetLastError(); return MYSLAM_ERR_HIP; }
+    if (need_device()) return MYSLAM_ERR_HIP;
     std::unique_ptr<myslam_loop_store> h(new myslam_loop_store());
     h->kf_capacity = kf_capacity; h->cap = cap; h->feat_cap = feat_cap;
     const size_t K = (size_t)kf_capacity, cap_st = ((size_t)cap + 3) & ~(size_t)3, feat_st = ((size_t)feat_cap + 3) & ~(size_t)3;

@@ -464,8 +464,7 @@ int myslam_hamming_match(const uint8_t* query, int nq, const uint8_t* train, int
     if (nq == 0) return MYSLAM_OK;
     if (!query || !train_idx || !dist || (nt > 0 && !train)) return MYSLAM_ERR_INVALID;
     if (nt >= (1 << 20)) return MYSLAM_ERR_UNSUPPORTED;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MYSLAM_ERR_HIP;
+    if (need_device()) return MYSLAM_ERR_HIP;
     const int cap = std::max(nq, std::max(nt, 1));
     HostCall hc;                                               // thread-local staging: no allocation, one copy each way
     const int pq = hc.in(query, (size_t)nq * 32), pt = hc.in(train, (size_t)nt * 32);
@@ -598,8 +597,7 @@ int myslam_triangulate_stereo(const float* xl, const float* yl, const float* xr,
     if (n < 0) return MYSLAM_ERR_INVALID;
     if (n == 0) return MYSLAM_OK;
     if (!xl || !yl || !xr || !yr || !xyz || !ok) return MYSLAM_ERR_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MYSLAM_ERR_HIP;
+    if (need_device()) return MYSLAM_ERR_HIP;
     HostCall hc;
     const int p0 = hc.in(xl, (size_t)n), p1 = hc.in(yl, (size_t)n), p2 = hc.in(xr, (size_t)n), p3 = hc.in(yr, (size_t)n);
     const int px = hc.out(xyz, (size_t)n * 3), po = hc.out(ok, (size_t)n);

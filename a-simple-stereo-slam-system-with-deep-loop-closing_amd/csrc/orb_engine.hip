@@ -665,8 +665,7 @@ int myslam_orb_create(myslam_orb** out, int nfeatures, float scale_factor, int n
     if (!out || nfeatures < 1 || nlevels < 1 || nlevels > MAXL || !(scale_factor > 1.0f) || ini_th_fast < 0 ||
         min_th_fast < 1 || min_th_fast > ini_th_fast || ini_th_fast > 255 || scale_factor > 2.5f)
         return MYSLAM_ERR_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MYSLAM_ERR_HIP;   // no CPU fallback
+    if (need_device()) return MYSLAM_ERR_HIP;   // no CPU fallback
     myslam_orb* h = new myslam_orb();
     h->nfeatures = nfeatures; h->scaleFactor = scale_factor; h->nlevels = nlevels; h->iniTh = ini_th_fast; h->minTh = min_th_fast;
     int rc = h->make_tables();

@@ -381,9 +381,6 @@ __global__ void __launch_bounds__(256) k_correct_map_points(const double* __rest
     pts[3 * i] = pw[0] + Tn.t[0]; pts[3 * i + 1] = pw[1] + Tn.t[1]; pts[3 * i + 2] = pw[2] + Tn.t[2];
 }
 
-// a call's own blocks hold one element at least: an empty part of a problem still gives its kernels and memsets a valid address
-static size_t some(size_t count) { return std::max<size_t>(count, 1); }
-
 }  // namespace myslam_hip
 
 using namespace myslam_hip;
@@ -396,8 +393,7 @@ int myslam_pose_graph_optimize(double* poses, int n, const uint8_t* fixed, const
     const int E = n_edges;
     for (int k = 0; k < E; k++)
         if (edge_v0[k] < 0 || edge_v0[k] >= n || edge_v1[k] < 0 || edge_v1[k] >= n || edge_v0[k] == edge_v1[k]) return MYSLAM_ERR_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MYSLAM_ERR_HIP;
+    if (need_device()) return MYSLAM_ERR_HIP;
     if (final_chi2) *final_chi2 = 0;
     if (iters) *iters = 0;
     if (n == 0) return MYSLAM_OK;
@@ -500,48 +496,38 @@ int myslam_pose_graph_optimize(double* poses, int n, const uint8_t* fixed, const
         jobs.push_back(j);
     }
 
-    // ---- device state ----
-    Buf<double> d_pose, d_save, d_meas, d_minv, d_J, d_err, d_D, d_B, d_C, d_Z, d_Lw, d_Hss, d_bS, d_A, d_xS, d_xT, d_y, d_P, d_diag, d_sc, d_part, d_res, d_inv;
-    Buf<int32_t> d_e0, d_e1, d_slot, d_seg; Buf<uint8_t> d_fx; Buf<PgJob> d_jobs; Buf<int2> d_list; Buf<int> d_status;
+    // ---- device state: one staged call (HostCall, common.h) ----
     const int nchi = (E + 255) / 256;
-    const hipStream_t st = host_call_stream();             // this thread's own non-blocking stream for every kernel, copy and memset of the call (never the legacy stream: common.h)
-    if (!st) return MYSLAM_ERR_HIP;
     const bool bigS = nS > PG_MAXS;
-    {
-        int rc;
-        if ((rc = d_pose.renew(some((size_t)7 * n))) || (rc = d_save.renew(some((size_t)7 * n))) || (rc = d_meas.renew(some((size_t)7 * E))) ||
-            (rc = d_minv.renew(some((size_t)7 * E))) || (rc = d_J.renew(some((size_t)72 * E))) || (rc = d_err.renew(some((size_t)6 * E))) ||
-            (rc = d_D.renew((size_t)36 * std::max(nT, 1))) || (rc = d_B.renew((size_t)36 * std::max(nT, 1))) ||
-            (rc = d_C.renew(some((size_t)rowsPad * ldz))) || (rc = d_Z.renew(some((size_t)rowsPad * ldz))) || (rc = d_Lw.renew(some((size_t)72 * nT))) ||
-            (rc = d_Hss.renew(some((size_t)ldz * ldz))) || (rc = d_bS.renew(some((size_t)ldz))) || (rc = d_A.renew(some((size_t)ldz * ldz))) ||
-            (rc = d_xS.renew(some((size_t)ldz))) || (rc = d_xT.renew(some((size_t)rowsPad))) || (rc = d_y.renew(some((size_t)rowsPad))) ||
-            (rc = d_P.renew(some((size_t)PG_KS * ntile * 256))) || (rc = d_diag.renew(some((size_t)6 * nF))) || (rc = d_sc.renew(some((size_t)n))) ||
-            (rc = d_part.renew(some((size_t)nchi))) || (rc = d_res.renew(4)) || (rc = d_e0.renew(some((size_t)E))) || (rc = d_e1.renew(some((size_t)E))) ||
-            (rc = d_slot.renew(some((size_t)n))) || (rc = d_fx.renew(some((size_t)n))) || (rc = d_jobs.renew(some(jobs.size()))) ||
-            (rc = d_list.renew(some(list.size()))) || (rc = d_status.renew(1)) || (rc = d_seg.renew(some(seg.size()))) ||
-            (rc = d_inv.renew((size_t)ldz + 16)))
-            return rc;
-    }
-    { const int rc_ = copy_sync(d_seg, seg.data(), sizeof(int32_t) * seg.size(), hipMemcpyHostToDevice, st); if (rc_) return rc_; }
-    { const int rc_ = copy_sync(d_pose, poses, sizeof(double) * 7 * n, hipMemcpyHostToDevice, st); if (rc_) return rc_; }
-    { const int rc_ = copy_sync(d_fx, fx.data(), n, hipMemcpyHostToDevice, st); if (rc_) return rc_; }
-    { const int rc_ = copy_sync(d_slot, slot.data(), sizeof(int32_t) * n, hipMemcpyHostToDevice, st); if (rc_) return rc_; }
-    if (E) {
-        { const int rc_ = copy_sync(d_meas, meas, sizeof(double) * 7 * E, hipMemcpyHostToDevice, st); if (rc_) return rc_; }
-        { const int rc_ = copy_sync(d_e0, edge_v0, sizeof(int32_t) * E, hipMemcpyHostToDevice, st); if (rc_) return rc_; }
-        { const int rc_ = copy_sync(d_e1, edge_v1, sizeof(int32_t) * E, hipMemcpyHostToDevice, st); if (rc_) return rc_; }
-    }
-    if (!jobs.empty()) {
-        { const int rc_ = copy_sync(d_jobs, jobs.data(), sizeof(PgJob) * jobs.size(), hipMemcpyHostToDevice, st); if (rc_) return rc_; }
-        { const int rc_ = copy_sync(d_list, list.data(), sizeof(int2) * list.size(), hipMemcpyHostToDevice, st); if (rc_) return rc_; }
-    }
+    const size_t nCZ = (size_t)rowsPad * ldz;
+    HostCall hc;
+    const int i_seg = hc.in(seg.data(), seg.size()), i_fx = hc.in(fx.data(), (size_t)n), i_slot = hc.in(slot.data(), (size_t)n);
+    const int i_meas = hc.in(meas, (size_t)7 * E), i_e0 = hc.in(edge_v0, (size_t)E), i_e1 = hc.in(edge_v1, (size_t)E);
+    const int i_jobs = hc.in(jobs.data(), jobs.size()), i_list = hc.in(list.data(), list.size());
+    const int io_pose = hc.inout(poses, (size_t)7 * n);
+    const int o_res = hc.out<double>(nullptr, 5);          // chi2, x . (lambda x + b), two spare, and the factorisations' status word behind them: one read per trial
     // blocks no job writes stay zero for the whole run (the sparsity pattern is fixed)
-    MYSLAM_HIP_CHECK(hipMemsetAsync(d_D, 0, sizeof(double) * 36 * std::max(nT, 1), st)); MYSLAM_HIP_CHECK(hipMemsetAsync(d_B, 0, sizeof(double) * 36 * std::max(nT, 1), st));
-    MYSLAM_HIP_CHECK(hipMemsetAsync(d_C, 0, sizeof(double) * std::max<size_t>((size_t)rowsPad * ldz, 1), st));
-    MYSLAM_HIP_CHECK(hipMemsetAsync(d_Z, 0, sizeof(double) * std::max<size_t>((size_t)rowsPad * ldz, 1), st));
-    MYSLAM_HIP_CHECK(hipMemsetAsync(d_Hss, 0, sizeof(double) * ldz * ldz, st)); MYSLAM_HIP_CHECK(hipMemsetAsync(d_bS, 0, sizeof(double) * ldz, st));
-    MYSLAM_HIP_CHECK(hipMemsetAsync(d_diag, 0, sizeof(double) * std::max(6 * nF, 1), st));
-    MYSLAM_HIP_CHECK(hipMemsetAsync(d_xS, 0, sizeof(double) * ldz, st)); MYSLAM_HIP_CHECK(hipMemsetAsync(d_xT, 0, sizeof(double) * std::max(rowsPad, 1), st));
+    const int z_D = hc.zero<double>((size_t)36 * nT), z_B = hc.zero<double>((size_t)36 * nT), z_C = hc.zero<double>(nCZ), z_Z = hc.zero<double>(nCZ);
+    const int z_Hss = hc.zero<double>((size_t)ldz * ldz), z_bS = hc.zero<double>((size_t)ldz), z_diag = hc.zero<double>((size_t)6 * nF);
+    const int z_xS = hc.zero<double>((size_t)ldz), z_xT = hc.zero<double>((size_t)rowsPad);
+    const int t_save = hc.tmp<double>((size_t)7 * n), t_minv = hc.tmp<double>((size_t)7 * E), t_J = hc.tmp<double>((size_t)72 * E), t_err = hc.tmp<double>((size_t)6 * E);
+    const int t_Lw = hc.tmp<double>((size_t)72 * nT), t_A = hc.tmp<double>((size_t)ldz * ldz), t_y = hc.tmp<double>((size_t)rowsPad);
+    const int t_P = hc.tmp<double>((size_t)PG_KS * ntile * 256), t_sc = hc.tmp<double>((size_t)n), t_part = hc.tmp<double>((size_t)nchi);
+    const int t_inv = hc.tmp<double>((size_t)ldz + 16);
+    int it = 0, rc;
+    if ((rc = hc.upload())) return rc;
+    const hipStream_t st = hc.stream();                    // this thread's own non-blocking stream for every kernel, copy and memset of the call (never the legacy stream: common.h)
+    const auto D = [&](int piece) { return hc.dev<double>(piece); };
+    double *const d_pose = D(io_pose), *const d_save = D(t_save), *const d_meas = D(i_meas), *const d_minv = D(t_minv), *const d_J = D(t_J), *const d_err = D(t_err);
+    double *const d_D = D(z_D), *const d_B = D(z_B), *const d_C = D(z_C), *const d_Z = D(z_Z), *const d_Lw = D(t_Lw), *const d_Hss = D(z_Hss), *const d_bS = D(z_bS);
+    double *const d_A = D(t_A), *const d_xS = D(z_xS), *const d_xT = D(z_xT), *const d_y = D(t_y), *const d_P = D(t_P), *const d_diag = D(z_diag), *const d_sc = D(t_sc);
+    double *const d_part = D(t_part), *const d_res = D(o_res), *const d_inv = D(t_inv);
+    int32_t *const d_e0 = hc.dev<int32_t>(i_e0), *const d_e1 = hc.dev<int32_t>(i_e1), *const d_slot = hc.dev<int32_t>(i_slot), *const d_seg = hc.dev<int32_t>(i_seg);
+    uint8_t* const d_fx = hc.dev<uint8_t>(i_fx);
+    PgJob* const d_jobs = hc.dev<PgJob>(i_jobs);
+    int2* const d_list = hc.dev<int2>(i_list);
+    int* const d_status = reinterpret_cast<int*>(d_res + 4);
+    const double* const res = hc.host<double>(o_res);      // valid after a fetch
 
     const int npe = std::max(n, E);
     hipLaunchKernelGGL(k_pg_prepare, dim3((npe + 255) / 256), dim3(256), 0, st, d_pose, n, d_meas, d_minv, E);
@@ -549,10 +535,10 @@ int myslam_pose_graph_optimize(double* poses, int n, const uint8_t* fixed, const
         if (E == 0) { *out = 0; return MYSLAM_OK; }
         hipLaunchKernelGGL(k_pg_chi2, dim3(nchi), dim3(256), 0, st, d_pose, d_minv, d_e0, d_e1, E, d_part);
         hipLaunchKernelGGL(k_pg_reduce, dim3(1), dim3(256), 0, st, d_part, nchi, d_res, 0);
-        { const int rc_ = copy_sync(out, d_res, sizeof(double), hipMemcpyDeviceToHost, st); if (rc_) return rc_; }
-        return MYSLAM_OK;
+        const int rc_ = hc.fetch(o_res);
+        *out = res[0];
+        return rc_;
     };
-    int it = 0, rc;
     double currentChi = 0;
     if ((rc = chi2(&currentChi)) != MYSLAM_OK) return rc;
     if (nF > 0 && E > 0) {
@@ -563,10 +549,9 @@ int myslam_pose_graph_optimize(double* poses, int n, const uint8_t* fixed, const
             hipLaunchKernelGGL(k_pg_assemble, dim3((unsigned)jobs.size()), dim3(64), 0, st, d_jobs, d_list, d_J, d_err, d_D, d_B, d_C, d_Hss, d_bS, d_diag,
                                ldz, mS, nT);
             if (it == 0) {                              // computeLambdaInit: tau * max diagonal
-                double mx = 0;
                 hipLaunchKernelGGL(k_pg_reduce, dim3(1), dim3(256), 0, st, d_diag, 6 * nF, d_res, 1);
-                { const int rc_ = copy_sync(&mx, d_res, sizeof(double), hipMemcpyDeviceToHost, st); if (rc_) return rc_; }
-                lambda = 1e-5 * mx; ni = 2;
+                if ((rc = hc.fetch(o_res))) return rc;
+                lambda = 1e-5 * res[0]; ni = 2;
             }
             double rho = 0;
             int qmax = 0;
@@ -590,10 +575,8 @@ int myslam_pose_graph_optimize(double* poses, int n, const uint8_t* fixed, const
                 hipLaunchKernelGGL(k_pg_chi2, dim3(nchi), dim3(256), 0, st, d_pose, d_minv, d_e0, d_e1, E, d_part);
                 hipLaunchKernelGGL(k_pg_reduce, dim3(1), dim3(256), 0, st, d_part, nchi, d_res, 0);
                 MYSLAM_HIP_CHECK(hipGetLastError());
-                double res[2]; int bad = 0;
-                { const int rc_ = copy_sync(res, d_res, sizeof(res), hipMemcpyDeviceToHost, st); if (rc_) return rc_; }
-                { const int rc_ = copy_sync(&bad, d_status, sizeof(int), hipMemcpyDeviceToHost, st); if (rc_) return rc_; }
-                const bool ok = !bad;
+                if ((rc = hc.fetch(o_res))) return rc;
+                const bool ok = !*reinterpret_cast<const int*>(res + 4);
                 tempChi = ok ? res[0] : 1e300;
                 rho = currentChi - tempChi;
                 double scale = 1e-3;
@@ -613,7 +596,7 @@ int myslam_pose_graph_optimize(double* poses, int n, const uint8_t* fixed, const
             if (qmax == 10 || rho == 0 || !std::isfinite(lambda)) { it++; break; }
         }
     }
-    { const int rc_ = copy_sync(poses, d_pose, sizeof(double) * 7 * n, hipMemcpyDeviceToHost, st); if (rc_) return rc_; }
+    if ((rc = hc.download())) return rc;
     if (final_chi2) *final_chi2 = currentChi;
     if (iters) *iters = it;
     return MYSLAM_OK;
@@ -694,28 +677,19 @@ int myslam_correct_map_points_device(const double* d_old_poses, const double* d_
 int myslam_correct_map_points(const double* old_poses, const double* new_poses, int n_poses, const int32_t* first_kf, double* points, int n_points) {
     if (n_points < 0 || n_poses < 0 || (n_points > 0 && (!old_poses || !new_poses || !first_kf || !points))) return MYSLAM_ERR_INVALID;
     if (n_points == 0) return MYSLAM_OK;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MYSLAM_ERR_HIP;
-    const hipStream_t st = host_call_stream();
-    if (!st) return MYSLAM_ERR_HIP;
-    Buf<double> d_o, d_n, d_p; Buf<int32_t> d_k, d_s;
+    if (need_device()) return MYSLAM_ERR_HIP;
+    HostCall hc;
+    int32_t stt = 0;                                       // goes up as 0 and comes back as the kernel's verdict
+    const int i_o = hc.in(old_poses, (size_t)7 * n_poses), i_n = hc.in(new_poses, (size_t)7 * n_poses), i_k = hc.in(first_kf, (size_t)n_points);
+    const int io_p = hc.inout(points, (size_t)3 * n_points, false), io_s = hc.inout(&stt, 1);
     int rc;
-    if ((rc = d_o.renew(some((size_t)7 * n_poses))) || (rc = d_n.renew(some((size_t)7 * n_poses))) || (rc = d_p.renew((size_t)3 * n_points)) ||
-        (rc = d_k.renew((size_t)n_points)) || (rc = d_s.renew(1)))
+    if ((rc = hc.upload()) ||
+        (rc = myslam_correct_map_points_device(hc.dev<double>(i_o), hc.dev<double>(i_n), n_poses, hc.dev<int32_t>(i_k), hc.dev<double>(io_p), n_points,
+                                               hc.dev<int32_t>(io_s), hc.stream())) ||
+        (rc = hc.download()))
         return rc;
-    if (n_poses) {
-        { const int rc_ = copy_sync(d_o, old_poses, sizeof(double) * 7 * n_poses, hipMemcpyHostToDevice, st); if (rc_) return rc_; }
-        { const int rc_ = copy_sync(d_n, new_poses, sizeof(double) * 7 * n_poses, hipMemcpyHostToDevice, st); if (rc_) return rc_; }
-    }
-    { const int rc_ = copy_sync(d_p, points, sizeof(double) * 3 * n_points, hipMemcpyHostToDevice, st); if (rc_) return rc_; }
-    { const int rc_ = copy_sync(d_k, first_kf, sizeof(int32_t) * n_points, hipMemcpyHostToDevice, st); if (rc_) return rc_; }
-    MYSLAM_HIP_CHECK(hipMemsetAsync(d_s, 0, sizeof(int32_t), st));
-    rc = myslam_correct_map_points_device(d_o, d_n, n_poses, d_k, d_p, n_points, d_s, st);
-    if (rc != MYSLAM_OK) return rc;
-    int32_t stt = 0;
-    { const int rc_ = copy_sync(&stt, d_s, sizeof(int32_t), hipMemcpyDeviceToHost, st); if (rc_) return rc_; }
-    if (stt != 0) return stt;
-    { const int rc_ = copy_sync(points, d_p, sizeof(double) * 3 * n_points, hipMemcpyDeviceToHost, st); if (rc_) return rc_; }
+    if (stt != 0) return stt;                              // the caller's points stay as they were
+    memcpy(points, hc.host<double>(io_p), sizeof(double) * 3 * n_points);
     return MYSLAM_OK;
 }
 

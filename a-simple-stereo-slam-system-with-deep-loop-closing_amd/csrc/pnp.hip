@@ -656,8 +656,7 @@ int myslam_solve_pnp_ransac(const float* pts3d, const float* pts2d, int n, doubl
     if (n_inliers) *n_inliers = 0;
     if (inlier && n) memset(inlier, 0, (size_t)n);
     if (n < PNP_MP) return MYSLAM_ERR_UNSUPPORTED;          // OpenCV: fewer points than the model needs -> false
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MYSLAM_ERR_HIP;
+    if (need_device()) return MYSLAM_ERR_HIP;
     // RANSACPointSetRegistrator::getSubset: 5 distinct uniform indices per iteration, one generator for the whole run
     std::vector<int32_t> samples((size_t)iterations * PNP_MP);
     CvRng rng((uint64_t)-1);
@@ -672,28 +671,27 @@ int myslam_solve_pnp_ransac(const float* pts3d, const float* pts2d, int n, doubl
             }
         }
     }
-    const hipStream_t st = host_call_stream();             // everything below runs on this thread's own non-blocking stream (never the legacy stream: common.h)
-    if (!st) return MYSLAM_ERR_HIP;
-    Buf<float> d_p3, d_p2; Buf<int32_t> d_samples, d_counts, d_result; Buf<double> d_models, d_pose; Buf<uint8_t> d_mask;      // of this call (n, iterations >= 1)
+    HostCall hc;                                           // results come back to the staging mirror only: the caller's pose and mask change when there is a model
+    const int i_p3 = hc.in(pts3d, (size_t)3 * n), i_p2 = hc.in(pts2d, (size_t)2 * n), i_s = hc.in(samples.data(), samples.size());
+    const int o_res = hc.out<int32_t>(nullptr, 2), o_pose = hc.out<double>(nullptr, 7), o_mask = hc.out<uint8_t>(nullptr, (size_t)n);
+    const int t_models = hc.tmp<double>((size_t)12 * iterations), t_counts = hc.tmp<int32_t>((size_t)iterations);
     int rc;
-    if ((rc = d_p3.renew((size_t)3 * n)) || (rc = d_p2.renew((size_t)2 * n)) || (rc = d_samples.renew(samples.size())) ||
-        (rc = d_counts.renew((size_t)iterations)) || (rc = d_result.renew(2)) || (rc = d_models.renew((size_t)12 * iterations)) ||
-        (rc = d_pose.renew(7)) || (rc = d_mask.renew((size_t)n)))
-        return rc;
-    { const int rc_ = copy_sync(d_p3, pts3d, sizeof(float) * 3 * n, hipMemcpyHostToDevice, st); if (rc_) return rc_; }
-    { const int rc_ = copy_sync(d_p2, pts2d, sizeof(float) * 2 * n, hipMemcpyHostToDevice, st); if (rc_) return rc_; }
-    { const int rc_ = copy_sync(d_samples, samples.data(), sizeof(int32_t) * samples.size(), hipMemcpyHostToDevice, st); if (rc_) return rc_; }
+    if ((rc = hc.upload())) return rc;
+    const hipStream_t st = hc.stream();                    // this thread's own non-blocking stream (never the legacy stream: common.h)
+    const float *const d_p3 = hc.dev<float>(i_p3), *const d_p2 = hc.dev<float>(i_p2);
+    double* const d_models = hc.dev<double>(t_models);
+    int32_t* const d_counts = hc.dev<int32_t>(t_counts);
     const PnpCam K{fx, fy, cx, cy};
     const float thr = (float)(reproj_error * reproj_error);
-    hipLaunchKernelGGL(k_pnp_hypotheses, dim3(iterations), dim3(64), 0, st, d_p3, d_p2, n, d_samples, K, thr, d_models, d_counts);
-    hipLaunchKernelGGL(k_pnp_select_refine, dim3(1), dim3(64), 0, st, d_p3, d_p2, n, d_models, d_counts, iterations, K, thr, confidence, d_pose,
-                       d_mask, d_result);
+    hipLaunchKernelGGL(k_pnp_hypotheses, dim3(iterations), dim3(64), 0, st, d_p3, d_p2, n, hc.dev<int32_t>(i_s), K, thr, d_models, d_counts);
+    hipLaunchKernelGGL(k_pnp_select_refine, dim3(1), dim3(64), 0, st, d_p3, d_p2, n, d_models, d_counts, iterations, K, thr, confidence, hc.dev<double>(o_pose),
+                       hc.dev<uint8_t>(o_mask), hc.dev<int32_t>(o_res));
     MYSLAM_HIP_CHECK(hipGetLastError());
-    int32_t res[2];
-    { const int rc_ = copy_sync(res, d_result, sizeof(res), hipMemcpyDeviceToHost, st); if (rc_) return rc_; }
+    if ((rc = hc.download())) return rc;
+    const int32_t* res = hc.host<int32_t>(o_res);
     if (res[0] <= 0) return MYSLAM_ERR_UNSUPPORTED;         // no model: OpenCV returns false and leaves rvec / tvec alone
-    { const int rc_ = copy_sync(pose7, d_pose, sizeof(double) * 7, hipMemcpyDeviceToHost, st); if (rc_) return rc_; }
-    if (inlier) { const int rc_ = copy_sync(inlier, d_mask, (size_t)n, hipMemcpyDeviceToHost, st); if (rc_) return rc_; }
+    memcpy(pose7, hc.host<double>(o_pose), sizeof(double) * 7);
+    if (inlier) memcpy(inlier, hc.host<uint8_t>(o_mask), (size_t)n);
     if (n_inliers) *n_inliers = res[0];
     return MYSLAM_OK;
 }
@@ -708,8 +706,7 @@ int myslam_pnp_destroy(myslam_pnp* h) {
 int myslam_pnp_create(myslam_pnp** out, int max_batch, int cap, int max_iterations) {
     if (!out || max_batch < 1 || max_batch > 65535 || cap < 1 || max_iterations < 1) return MYSLAM_ERR_INVALID;
     if (cap > 4096 || max_iterations > 100000) return MYSLAM_ERR_CAPACITY;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MYSLAM_ERR_HIP;
+    if (need_device()) return MYSLAM_ERR_HIP;
     myslam_pnp* h = new myslam_pnp();
     h->max_batch = max_batch; h->cap = cap; h->max_iterations = max_iterations;
     const size_t B = (size_t)max_batch, hyp = B * (size_t)max_iterations, pts = B * (size_t)cap;

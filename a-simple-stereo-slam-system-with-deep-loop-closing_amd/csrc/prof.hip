@@ -62,25 +62,34 @@ void raw_free(void* p, bool pinned) {
 // ---- thread-local staging of the host-pointer entry points (common.h) ----
 void HostArena::release() {
     if (s) (void)hipStreamSynchronize(s);
-    d.release(); h.release();
+    m.release();
     if (s) (void)hipStreamDestroy(s);
     s = nullptr;
 }
 
 HostArena::~HostArena() { release(); }
 
-int HostArena::ensure(size_t bytes) {
+int HostArena::open() {
     int cur = 0;
     MYSLAM_HIP_CHECK(hipGetDevice(&cur));
     if (cur != dev) { release(); dev = cur; }          // the calling thread selected another device since its last call
     if (!s) MYSLAM_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    if (bytes <= std::min(d.size(), h.size())) return MYSLAM_OK;
-    MYSLAM_HIP_CHECK(hipStreamSynchronize(s));
-    d.release(); h.release();                          // both go before either comes back, as before
-    const size_t want = (bytes + (bytes >> 2) + 65535) & ~(size_t)65535;
-    int rc;
-    if ((rc = d.renew(want)) || (rc = h.renew(want))) return rc;
     return MYSLAM_OK;
+}
+
+int HostArena::ensure(size_t dev_bytes, size_t host_bytes) {
+    const int rc = open();
+    if (rc || m.fits(dev_bytes, host_bytes)) return rc;
+    MYSLAM_HIP_CHECK(hipStreamSynchronize(s));
+    return m.grow(dev_bytes, host_bytes);
+}
+
+// A device block above 64 MB goes back when its call ends, as it did when every call allocated its own: the general Schur path of the pose graph takes
+// gigabytes that nothing else on the thread would use again, and tests/test_gpu_pgo.py holds a thread to 64 MB of device memory across such a call.
+void HostArena::trim() {
+    if (m.d.size() <= ((size_t)64 << 20)) return;
+    if (s) (void)hipStreamSynchronize(s);
+    m.d.release();
 }
 
 HostArena& host_arena() {
@@ -88,29 +97,33 @@ HostArena& host_arena() {
     return a;
 }
 
+hipStream_t host_call_stream() {
+    HostArena& a = host_arena();
+    if (a.open() == MYSLAM_OK) return a.s;
+    (void)hipGetLastError();                           // the caller reports the missing stream: no later launch check may find this
+    return nullptr;
+}
+
 int HostCall::upload() {
-    if (overflow) return MYSLAM_ERR_CAPACITY;          // more pieces than a call may register
-    size_t off = 0;
-    for (int k = IN; k <= TMP; k++) {
-        if (k == INOUT) begOut = off;
-        for (int i = 0; i < npc; i++)
-            if (pc[i].kind == k) { pc[i].off = off; off += (pc[i].bytes + 255) & ~(size_t)255; }
-        if (k == INOUT) endIn = off;
-        if (k == OUT) endOut = off;
-    }
-    int rc = A.ensure(off ? off : 256);
-    if (rc) return rc;
-    for (int i = 0; i < npc; i++)
-        if (pc[i].kind <= INOUT && pc[i].bytes) memcpy(A.h + pc[i].off, pc[i].src, pc[i].bytes);
-    if (endIn) MYSLAM_HIP_CHECK(hipMemcpyAsync(A.d, A.h, endIn, hipMemcpyHostToDevice, A.s));
+    int rc;
+    if ((rc = L.place()) || (rc = A.ensure(L.dev_bytes(), L.host_bytes()))) return rc;
+    for (int i = 0; i < L.npc; i++)
+        if (L.pc[i].kind <= CallLayout::INOUT && L.pc[i].bytes) memcpy(A.m.h + L.pc[i].off, L.pc[i].src, L.pc[i].bytes);
+    if (L.endIn) MYSLAM_HIP_CHECK(hipMemcpyAsync(A.m.d, A.m.h, L.endIn, hipMemcpyHostToDevice, A.s));
+    if (L.endZero > L.begZero) MYSLAM_HIP_CHECK(hipMemsetAsync(A.m.d + L.begZero, 0, L.endZero - L.begZero, A.s));
     return MYSLAM_OK;
 }
 
+int HostCall::fetch(int piece) {
+    const CallLayout::Piece& p = L.pc[piece];
+    return copy_sync(A.m.h + p.off, A.m.d + p.off, p.bytes, hipMemcpyDeviceToHost, A.s);
+}
+
 int HostCall::download() {
-    if (endOut > begOut) MYSLAM_HIP_CHECK(hipMemcpyAsync(A.h + begOut, A.d + begOut, endOut - begOut, hipMemcpyDeviceToHost, A.s));
+    if (L.endOut > L.begOut) MYSLAM_HIP_CHECK(hipMemcpyAsync(A.m.h + L.begOut, A.m.d + L.begOut, L.endOut - L.begOut, hipMemcpyDeviceToHost, A.s));
     MYSLAM_HIP_CHECK(hipStreamSynchronize(A.s));
-    for (int i = 0; i < npc; i++)
-        if ((pc[i].kind == INOUT || pc[i].kind == OUT) && pc[i].bytes && pc[i].dst) memcpy(pc[i].dst, A.h + pc[i].off, pc[i].bytes);
+    for (int i = 0; i < L.npc; i++)
+        if (L.pc[i].kind >= CallLayout::INOUT && L.pc[i].kind <= CallLayout::OUT && L.pc[i].bytes && L.pc[i].dst) memcpy(L.pc[i].dst, A.m.h + L.pc[i].off, L.pc[i].bytes);
     return MYSLAM_OK;
 }
 
@@ -183,8 +196,8 @@ int myslam_prof_count(void) { return P_COUNT; }
 
 // debug: copy n bytes from a device pointer with this library's HIP runtime (diagnoses runtime/VA mismatches)
 int myslam_debug_peek(const void* d_ptr, void* out, size_t n) {
-    MYSLAM_HIP_CHECK(hipMemcpy(out, d_ptr, n, hipMemcpyDeviceToHost));
-    return MYSLAM_OK;
+    const hipStream_t st = host_call_stream();          // never the legacy stream (common.h, upload_table)
+    return st ? copy_sync(out, d_ptr, n, hipMemcpyDeviceToHost, st) : MYSLAM_ERR_HIP;
 }
 
 int myslam_prof_get(int i, const char** name, double* total_ms, long* launches) {

@@ -127,8 +127,7 @@ extern "C" {
 int myslam_undistort_create(myslam_undistort** out, int rows, int cols, const float* K, const float* D) {
     if (!out || !K || !D || rows < 1 || cols < 1 || cols > 30000 || rows > 30000) return MYSLAM_ERR_INVALID;
     for (int i = 0; i < 4; i++) if (!std::isfinite(K[i]) || !std::isfinite(D[i])) return MYSLAM_ERR_INVALID;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return MYSLAM_ERR_HIP;
+    if (need_device()) return MYSLAM_ERR_HIP;
     myslam_undistort* h = new myslam_undistort();
     h->rows = rows; h->cols = cols;
     ud_build_cv_maps(rows, cols, K, D, h->xy, h->frac);

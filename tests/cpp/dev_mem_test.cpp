@@ -1,4 +1,5 @@
-// csrc/dev_mem.h on the host: Buf, BufSet and regrow over a malloc-backed raw_alloc / raw_free that counts live blocks and can fail the k-th call.
+// csrc/dev_mem.h on the host: Buf, BufSet, regrow and the host-pointer calls' staging (CallLayout, ArenaMem) over a malloc-backed raw_alloc / raw_free that
+// counts live blocks and can fail the k-th call.
 // Built with AddressSanitizer + UBSan by tests/test_dev_mem.py; exit status 0 and "DEV MEM OK" = every check held and nothing leaked.
 #include <stdio.h>
 #include <stdlib.h>
@@ -196,7 +197,80 @@ static void buf_set() {
     arm(0);
 }
 
+// the staging of the host-pointer calls: where the pieces of a call lie, and what the arena asks the allocator for
+static void call_layout() {
+    using L = CallLayout;
+    // pieces of every kind, registered out of order, some with no byte at all: offsets in the order in, inout, out, zero, tmp, each 256-byte aligned
+    L c;
+    const int t0 = c.add(L::TMP, nullptr, nullptr, 1000), z0 = c.add(L::ZERO, nullptr, nullptr, 1), o0 = c.add(L::OUT, nullptr, nullptr, 257);
+    const int i0 = c.add(L::IN, nullptr, nullptr, 7), io0 = c.add(L::INOUT, nullptr, nullptr, 256), i1 = c.add(L::IN, nullptr, nullptr, 0);
+    const int z1 = c.add(L::ZERO, nullptr, nullptr, 0), o1 = c.add(L::OUT, nullptr, nullptr, 0), t1 = c.add(L::TMP, nullptr, nullptr, 0), i2 = c.add(L::IN, nullptr, nullptr, 300);
+    const int io1 = c.add(L::INOUT, nullptr, nullptr, 0);
+    CHECK(c.place() == MYSLAM_OK && c.npc == 11);
+    const int order[11] = {i0, i1, i2, io0, io1, o0, o1, z0, z1, t0, t1};
+    size_t off = 0;
+    for (int k = 0; k < 11; k++) {
+        const L::Piece& p = c.pc[order[k]];
+        CHECK(p.off == off && p.off % 256 == 0);
+        CHECK(k == 0 || p.kind >= c.pc[order[k - 1]].kind);
+        off += (p.bytes + 255) / 256 * 256;
+    }
+    CHECK(c.pc[i1].off == c.pc[i2].off);                       // a piece of no bytes takes no room
+    CHECK(c.begOut == c.pc[io0].off && c.endIn == c.pc[o0].off && c.endOut == c.pc[z0].off && c.begZero == c.endOut);
+    CHECK(c.endZero == c.pc[t0].off && c.total == off && c.total == c.pc[t1].off);
+    CHECK(c.host_bytes() == c.endOut && c.dev_bytes() == c.total && c.host_bytes() == 256 + 0 + 512 + 256 + 0 + 512 + 0);
+    // an empty call and a call of empty pieces
+    L e;
+    CHECK(e.place() == MYSLAM_OK && e.total == 0 && e.host_bytes() == 0);
+    e.add(L::ZERO, nullptr, nullptr, 0); e.add(L::IN, nullptr, nullptr, 0);
+    CHECK(e.place() == MYSLAM_OK && e.total == 0 && e.endZero == 0);
+    // 1 GB each of zero and tmp beside 1 KB in and out: the pinned block does not know about them
+    L g;
+    g.add(L::IN, nullptr, nullptr, 512); g.add(L::OUT, nullptr, nullptr, 512); g.add(L::ZERO, nullptr, nullptr, (size_t)1 << 30); g.add(L::TMP, nullptr, nullptr, (size_t)1 << 30);
+    CHECK(g.place() == MYSLAM_OK && g.host_bytes() == 1024 && g.host_bytes() < (64u << 10) && g.dev_bytes() == ((size_t)2 << 30) + 1024);
+    CHECK(ArenaMem::padded(g.host_bytes()) <= (64u << 10));   // what the arena asks the allocator for: one 64 KB granule
+    // MAXP pieces are placed, one more refuses the call (and names piece 0, so that a lookup before place() stays in bounds)
+    L f;
+    for (int k = 0; k < L::MAXP; k++) CHECK(f.add(L::Kind(k % 5), nullptr, nullptr, k) == k);
+    CHECK(L::MAXP == 32 && f.place() == MYSLAM_OK);
+    CHECK(f.add(L::TMP, nullptr, nullptr, 8) == 0 && f.npc == L::MAXP && f.place() == MYSLAM_ERR_CAPACITY);
+}
+
+static void arena_mem() {
+    arm(0);
+    {
+        ArenaMem m;
+        CHECK(!m.fits(0, 0));                                  // no block yet: not even an empty call fits
+        CHECK(m.grow(0, 0) == MYSLAM_OK && m.fits(0, 0) && m.d.size() >= 256 && m.h.size() >= 256 && g_live == 2 && g_pinned_live == 1);
+        m.d[m.d.size() - 1] = 1; m.h[m.h.size() - 1] = 1;      // whole blocks (ASan checks the bytes)
+        // the device side grows alone: the pinned block stays the one it was
+        uint8_t* const h0 = m.h.get();
+        const size_t hs = m.h.size();
+        CHECK(!m.fits(1 << 20, 100) && m.grow(1 << 20, 100) == MYSLAM_OK && m.fits(1 << 20, 100) && m.h.get() == h0 && m.h.size() == hs && g_live == 2);
+        CHECK(m.d.size() >= (1 << 20) + (1 << 18));            // a quarter of headroom
+        uint8_t* const d0 = m.d.get();
+        CHECK(m.grow(1000, hs + 1) == MYSLAM_OK && m.d.get() == d0 && m.h.size() > hs);      // and the pinned side alone; nothing shrinks
+        // a failed growth, of either block, leaves both sizes 0 and nothing live
+        for (int k = 1; k <= 2; k++) {
+            CHECK(m.grow(1, 1) == MYSLAM_OK && g_live == 2);
+            arm(k);
+            CHECK(m.grow(m.d.size() + 1, m.h.size() + 1) == MYSLAM_ERR_HIP);
+            CHECK(empty(m.d) && empty(m.h) && !m.fits(0, 0) && g_live == 0);
+            arm(0);
+        }
+        CHECK(m.grow(1, 1) == MYSLAM_OK && g_live == 2);
+        arm(1);                                                // only the pinned block is short, and its growth fails: the device block goes too
+        CHECK(m.grow(1, m.h.size() + 1) == MYSLAM_ERR_HIP && empty(m.d) && empty(m.h) && g_live == 0);
+        arm(0);
+        CHECK(m.grow(1, 1) == MYSLAM_OK && m.fits(1, 1));       // usable again
+    }
+    CHECK(g_live == 0 && g_pinned_live == 0);
+}
+
 int main() {
+    call_layout();
+    arena_mem();
+    CHECK(g_live == 0);
     single_buffer();
     CHECK(g_live == 0);
     moves();

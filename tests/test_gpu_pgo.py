@@ -87,6 +87,12 @@ def test_pose_graph_iteration_zero_and_no_edges(api, oracle, synth):
     got = api.pose_graph_optimize(poses, allfixed, e0, e1, meas); ref = oracle.pose_graph_optimize(poses, allfixed, e0, e1, meas)
     _cmp(got, ref, tol=1e-15)
     assert got[2] == 0
+    # neither an edge nor a free key-frame (every staged piece of the linear system is empty): unit quaternions come back, nothing else moves
+    unit = poses / np.c_[np.tile(np.linalg.norm(poses[:, :4], axis=1)[:, None], 4), np.ones((len(poses), 3))]
+    got = api.pose_graph_optimize(poses, allfixed, e0[:0], e1[:0], meas[:0])
+    assert got[1] == 0 and got[2] == 0 and np.abs(got[0] - unit).max() < 1e-15 and got[0][:, 4:].tobytes() == poses[:, 4:].tobytes()
+    got = api.pose_graph_optimize(poses[:1], allfixed[:1], e0[:0], e1[:0], meas[:0])
+    assert got[1] == 0 and got[2] == 0 and np.abs(got[0] - unit[:1]).max() < 1e-15
 
 
 def test_pose_graph_general_structure(api, oracle, synth):
@@ -372,6 +378,86 @@ def test_correct_map_points(api, oracle, synth):
     with pytest.raises(Exception):
         api.correct_map_points(poses, new, np.full(5000, 80, np.int32), pts)
     assert api.correct_map_points(poses, new, kf[:0], pts[:0]).shape == (0, 3)
+    # no key-frame at all (the pose pieces of the staged call are empty): points that name none stay, a point that names one is refused
+    none = np.full(7, -1, np.int32)
+    assert api.correct_map_points(poses[:0], new[:0], none, pts[:7]).tobytes() == pts[:7].tobytes()
+    with pytest.raises(api.MyslamError) as ei:
+        api.correct_map_points(poses[:0], new[:0], np.r_[none[:6], 0].astype(np.int32), pts[:7])
+    assert ei.value.code == api.ERR_INVALID
+
+
+def _fresh_thread(fn):
+    """fn() as the first call of a new thread: its staging arena starts empty"""
+    import threading
+    box = []
+
+    def run():
+        try:
+            box.append((fn(), None))
+        except Exception as e:      # noqa: BLE001  (raised again on the calling thread)
+            box.append((None, e))
+
+    th = threading.Thread(target=run); th.start(); th.join(300)
+    assert box, "the thread did not finish"
+    if box[0][1] is not None:
+        raise box[0][1]
+    return box[0][0]
+
+
+def _pgo_device_bytes(n, E, st):
+    """what myslam_pose_graph_optimize asks its staging arena for (csrc/pgo.hip: the pieces it registers, each rounded up to 256 bytes)"""
+    nT, nS = st.n_chain, st.separators
+    ldz = (6 * nS + 1 + 15) // 16 * 16; nt16 = ldz // 16; ntile = nt16 * (nt16 + 1) // 2; rows_pad = (6 * nT + 3) // 4 * 4
+    doubles = [7 * E, 7 * n, 5, 36 * nT, 36 * nT, rows_pad * ldz, rows_pad * ldz, ldz * ldz, ldz, 6 * (nT + nS), ldz, rows_pad,      # meas, poses, results, zero
+               7 * n, 7 * E, 72 * E, 6 * E, 72 * nT, ldz * ldz, rows_pad, 32 * ntile * 256, n, (E + 255) // 256, ldz + 16]           # tmp
+    other = [4 * (n + 1), n, 4 * n, 4 * E, 4 * E, 20 * (3 * E + 2 * n), 8 * 4 * E]                                                  # seg, fixed, slot, e0, e1, jobs and list (upper bounds)
+    return sum((8 * d + 255) // 256 * 256 for d in doubles) + sum((x + 255) // 256 * 256 for x in other)
+
+
+ARENA_KEEPS = 64 << 20                                     # csrc/prof.hip HostArena::trim: a larger device block is freed when its call ends
+
+
+def _arena_block(need):
+    return (need + need // 4 + 65536) // 65536 * 65536     # csrc/dev_mem.h ArenaMem::padded
+
+
+def test_reused_staging_leaves_no_trace(api, oracle, synth):
+    """The host-pointer calls carve their device memory out of one block per thread that is kept from call to call (up to 64 MB), so a call's scratch
+    holds what the call before it left there.  One thread runs, in this order, a pose graph of 1500 key-frames (it sizes and dirties the block:
+    ~20 MB, kept), then a large and a small pose graph, a large and a small PnP, a large and a small map-point correction, all inside that block:
+    every result must equal, bit for bit, the same call made as the FIRST call of a thread of its own.  (The kernels reduce in a fixed order: the
+    library built before the arena existed repeats itself bit for bit on these inputs, each call on fresh allocations.)
+    A graph of the general Schur path can never meet recycled memory: the smallest one (97 separators) needs ~52 MB, a block of ~65 MB, which is
+    allocated for the call and freed at its end like every block above 64 MB.  One runs last here: what the thread kept must not disturb it either."""
+    g1500 = synth.pose_graph(1500, 6, seed=11)[:5]
+    g300 = synth.pose_graph(300, 3, seed=12)[:5]
+    p12, _, e0, e1, meas, gt = synth.pose_graph(12, 0, seed=13, n_active=1)
+    g12 = (p12, np.r_[1, np.zeros(11)].astype(np.uint8), np.r_[e0, 11].astype(np.int32), np.r_[e1, 2].astype(np.int32),
+           np.r_[meas, _noisy_relative(oracle, gt, [11], [2], np.random.default_rng(13))])
+    gbig = _dense_graph(oracle)
+    st = {name: pg_structure(len(G[0]), *G[1:4]) for name, G in (("1500", g1500), ("300", g300), ("12", g12), ("big", gbig))}
+    need = {name: _pgo_device_bytes(len(G[0]), len(G[2]), st[name]) for name, G in (("1500", g1500), ("300", g300), ("12", g12), ("big", gbig))}
+    assert st["1500"].path == st["300"].path == st["12"].path == "fast" and st["big"].path == "general"
+    # the first call's block is kept and holds every later call but the last: they run on recycled memory, the test is about something
+    assert _arena_block(need["1500"]) <= ARENA_KEEPS and need["12"] < need["300"] < need["1500"] and _arena_block(need["big"]) > ARENA_KEEPS, need
+    pnp200 = synth.pnp_problem(200, 0.3, 0.5, seed=22)[:3]; pnp8 = synth.pnp_problem(8, 0.0, 0.5, seed=21)[:3]
+    rng = np.random.default_rng(14)
+    new300 = oracle.pose_graph_optimize(*g300)[0]
+    cmp50 = (g300[0], new300, rng.integers(-1, 300, 50).astype(np.int32), rng.normal(0, 30, (50, 3)))
+    cmp3 = (g300[0][250:254], new300[250:254], np.array([3, -1, 0], np.int32), rng.normal(0, 30, (3, 3)))      # key-frames the loop moves by decimetres
+    calls = [("pgo-1500", lambda: api.pose_graph_optimize(*g1500, iters=3)), ("pgo-300", lambda: api.pose_graph_optimize(*g300)),
+             ("pgo-12", lambda: api.pose_graph_optimize(*g12)), ("pnp-200", lambda: api.solve_pnp_ransac(*pnp200)), ("pnp-8", lambda: api.solve_pnp_ransac(*pnp8)),
+             ("points-50", lambda: api.correct_map_points(*cmp50)), ("points-3", lambda: api.correct_map_points(*cmp3)),
+             ("pgo-general-240", lambda: api.pose_graph_optimize(*gbig, iters=2))]
+
+    def flat(r):
+        return b"".join(np.asarray(x).tobytes() for x in (r if isinstance(r, tuple) else (r,)))
+
+    reused = dict(zip([name for name, _ in calls], _fresh_thread(lambda: [fn() for _, fn in calls])))
+    assert reused["pgo-300"][2] >= 1 and reused["pgo-12"][2] >= 1 and reused["pnp-8"][2] >= 5      # real optimisations, a real model
+    assert np.abs(reused["points-3"] - cmp3[3])[[0, 2]].min() > 1e-6 and reused["points-3"][1].tobytes() == cmp3[3][1].tobytes()
+    for name, fn in calls[1:]:
+        assert flat(reused[name]) == flat(_fresh_thread(fn)), name
 
 
 def test_loop_local_fusion(api, oracle, synth):

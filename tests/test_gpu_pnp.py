@@ -47,3 +47,26 @@ def test_pnp_ransac_parameters_and_edge_cases(api, oracle, synth):
     rng = np.random.default_rng(0)
     pwr = rng.normal(0, 10, (80, 3)).astype(np.float32); uvr = rng.uniform(0, 1000, (80, 2)).astype(np.float32)
     _cmp(api, oracle, pwr, uvr, K)
+
+
+def test_pnp_no_model_keeps_the_callers_bytes(api, oracle, synth):
+    """OpenCV returns false and leaves rvec / tvec alone: MYSLAM_ERR_UNSUPPORTED, the caller's pose untouched, the mask all zero, the count 0 — and the
+    same again behind a successful 200-point call on this thread, whose pose and mask lie in the same staging memory."""
+    import ctypes as C
+    rng = np.random.default_rng(0)
+    pw = rng.normal(0, 10, (8, 3)).astype(np.float32); uv = rng.uniform(0, 1000, (8, 2)).astype(np.float32)
+    big = synth.pnp_problem(200, 0.3, 0.5, seed=22)
+    K = big[2]
+    assert oracle.solve_pnp_ransac(pw, uv, K)[0] != 0, "the oracle finds a model in this noise: the test would check nothing"
+
+    def no_model():
+        pose = np.full(7, -7.25); inl = np.full(8, 0xAA, np.uint8); ni = C.c_int(-1)
+        rc = api.lib().myslam_solve_pnp_ransac(pw.ctypes.data_as(C.c_void_p), uv.ctypes.data_as(C.c_void_p), 8, C.c_double(K[0]), C.c_double(K[1]),
+                                               C.c_double(K[2]), C.c_double(K[3]), 100, C.c_double(5.991), C.c_double(0.99),
+                                               pose.ctypes.data_as(C.c_void_p), inl.ctypes.data_as(C.c_void_p), C.byref(ni))
+        assert rc == api.ERR_UNSUPPORTED
+        assert pose.tobytes() == np.full(7, -7.25).tobytes() and not inl.any() and ni.value == 0
+
+    no_model()
+    assert api.solve_pnp_ransac(*big[:3])[2] > 100
+    no_model()
