@@ -43,7 +43,7 @@ assert OWNED_DTYPE.itemsize == 32
 
 _lib = None
 _SCALARS = {"int": C.c_int, "float": C.c_float, "double": C.c_double, "size_t": C.c_size_t, "uint64_t": C.c_uint64, "long": C.c_long,
-            "int32_t": C.c_int32, "uint8_t": C.c_uint8}
+            "int32_t": C.c_int32, "uint8_t": C.c_uint8, "int64_t": C.c_int64}
 
 
 def header_prototypes(path=HEADER_PATH):
@@ -853,6 +853,60 @@ class Tracker:
         st = np.zeros(self.cap, np.uint8); n = C.c_int()
         _check(lib().myslam_tracker_debug_last_step(self._h, int(s), _p(p0), _p(p1), _p(nx), _p(st), C.byref(n)), "myslam_tracker_debug_last_step")
         return p0[:n.value], p1[:n.value], nx[:n.value], st[:n.value].astype(bool)
+
+    # ---- key-frame turns on the device (myslam_tracker_keyframe_*: the header states every rule) ----
+    NO_TURN = 1                                  # MYSLAM_TRACKER_NO_TURN
+    REPORT_FIELDS = ("status", "frame_id", "n_detected", "n_right", "n_new_mp", "n_feat", "n_landmarks", "reserved")
+
+    def set_ids(self, s, landmark_id, ref_kf_id, next_kf_id, next_mp_id):
+        """MapPoint::mnId by landmark slot and the stream's id counters (host arrays, synchronous); makes the stream's ids valid"""
+        ids = np.ascontiguousarray(landmark_id, np.int64).reshape(-1)
+        _check(lib().myslam_tracker_set_ids(self._h, int(s), _p(ids), len(ids), int(ref_kf_id), int(next_kf_id), int(next_mp_id)), "myslam_tracker_set_ids")
+
+    def get_ids(self, s):
+        ids = np.zeros(self.landmark_cap, np.int64); n, valid = C.c_int(), C.c_int()
+        ref, nkf, nmp = C.c_int64(), C.c_int64(), C.c_int64()
+        _check(lib().myslam_tracker_get_ids(self._h, int(s), _p(ids), C.byref(n), C.byref(ref), C.byref(nkf), C.byref(nmp), C.byref(valid)),
+               "myslam_tracker_get_ids")
+        return {"landmark_id": ids[:n.value].copy(), "ref_kf_id": ref.value, "next_kf_id": nkf.value, "next_mp_id": nmp.value, "valid": valid.value}
+
+    def keyframe_masks(self, d_masks, step, stride):
+        """device pointer, asynchronous: every stream's detection mask in myslam_orb_detect_batch's d_masks layout (all 0 for a stream without a turn)"""
+        _check(lib().myslam_tracker_keyframe_masks(self._h, C.c_void_p(d_masks), int(step), C.c_size_t(stride)), "myslam_tracker_keyframe_masks")
+
+    def keyframe_launches(self):
+        return lib().myslam_tracker_keyframe_launches(self._h)
+
+    def keyframe_batch(self, d_right, step, stride, d_new_kps, d_n_new, kp_cap, baseline, out):
+        """device pointers, asynchronous.  out: dict of device pointers new_kf_id, new_kf_pose, feat_mp_id, feat_mp_pos, feat_uv, feat_tag, feat_flags,
+        n_feat, outlier_mp_id, n_outlier_mp, right_xy, right_ok, report (sizes: the header; feature stride = cap, outlier stride = 2 cap)"""
+        o = [C.c_void_p(out[k]) for k in ("new_kf_id", "new_kf_pose", "feat_mp_id", "feat_mp_pos", "feat_uv", "feat_tag", "feat_flags", "n_feat",
+                                          "outlier_mp_id", "n_outlier_mp", "right_xy", "right_ok", "report")]
+        _check(lib().myslam_tracker_keyframe_batch(self._h, C.c_void_p(d_right), int(step), C.c_size_t(stride), C.c_void_p(d_new_kps), C.c_void_p(d_n_new),
+                                                   int(kp_cap), C.c_double(baseline), *o), "myslam_tracker_keyframe_batch")
+
+    def debug_last_turn(self, s):
+        """(left pixels, right points, right status, triangulation in the camera frame, its ok) of stream s in the last turn; empty without one"""
+        xy = np.zeros((self.cap, 2), np.float32); rx = np.zeros((self.cap, 2), np.float32); ro = np.zeros(self.cap, np.uint8)
+        tx = np.zeros((self.cap, 3), np.float64); to = np.zeros(self.cap, np.uint8); n = C.c_int()
+        _check(lib().myslam_tracker_debug_last_turn(self._h, int(s), _p(xy), _p(rx), _p(ro), _p(tx), _p(to), C.byref(n)), "myslam_tracker_debug_last_turn")
+        n = n.value
+        return xy[:n], rx[:n], ro[:n].astype(bool), tx[:n], to[:n].astype(bool)
+
+    def debug_freeze(self, s, why=1):
+        """test seam: freeze stream s as a step would, recording why (1 key-frame rule, 2 LOST, 3 capacity)"""
+        _check(lib().myslam_tracker_debug_freeze(self._h, int(s), int(why)), "myslam_tracker_debug_freeze")
+
+    def update_from_map(self, d_kf_id, d_kf_pose, d_n_kf, kf_cap, d_mp_id, d_mp_pos, d_mp_outlier, d_n_mp, mp_cap):
+        """device pointers, asynchronous: landmarks and the reference pose of every running stream follow their ids in the back end's tables"""
+        _check(lib().myslam_tracker_update_from_map_batch(self._h, C.c_void_p(d_kf_id), C.c_void_p(d_kf_pose), C.c_void_p(d_n_kf), int(kf_cap),
+                                                          C.c_void_p(d_mp_id), C.c_void_p(d_mp_pos), C.c_void_p(d_mp_outlier), C.c_void_p(d_n_mp),
+                                                          int(mp_cap)), "myslam_tracker_update_from_map_batch")
+
+    def set_image_batch(self, d_imgs, step, stride, d_select):
+        """device pointers, asynchronous: the stored previous left image of every selected stream <- d_imgs[s], pyramid rebuilt"""
+        _check(lib().myslam_tracker_set_image_batch(self._h, C.c_void_p(d_imgs), int(step), C.c_size_t(stride), C.c_void_p(d_select)),
+               "myslam_tracker_set_image_batch")
 
 
 # ---------------------------------------------------------------------------------- lens undistortion

@@ -792,6 +792,7 @@ class StreamBank:
 
     # -- the pieces of advance(), separately callable (tests drive them in lock-step with a checker) --
     def upload(self, t):
+        self.t = t
         self.images = [c.frame_images(t) for c in self.chains]
         self.d_img.copy_(self.torch.from_numpy(np.stack([np.ascontiguousarray(L, np.uint8) for L, _ in self.images])))
 
@@ -819,8 +820,92 @@ class StreamBank:
               "ref_pose": c.ref_kf.pose, "ref_frame_id": c.ref_kf.frame_id, "last_rel": c.cur.rel, "rel_motion": c.rel_motion,
               "next_frame_id": c.next_frame_id, "status": c.status, "kf_every": c.kf_every}
         self.trk.set_frame(s, st, image=c.cur.L)       # the key-frame's image as the loop closer left it (blurred in place, deeplcd.cpp:46)
+        self.trk.set_ids(s, [m.id for m in mps], c.ref_kf.id, c.next_kf_id, c.next_mp_id)      # what a device turn needs to name new map points
         self.slots[s] = mps
         self.on_device[s] = True
+
+    def _turn_buffers(self):
+        if getattr(self, "turn_buf", None) is None:
+            torch, S, cap = self.torch, len(self.chains), self.trk.cap
+            self.orb = self.chains[0].be.orb              # System::_mpORBextractor (nNewFeatures): every stream of a bank shares its configuration
+            self.kp_cap = int(self.orb.max_keypoints(self.rows, self.cols))
+            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device="cuda")
+            self.turn_buf = {"new_kf_id": z(S, torch.int64), "new_kf_pose": z((S, 7), torch.float64), "feat_mp_id": z((S, cap), torch.int64),
+                             "feat_mp_pos": z((S, cap, 3), torch.float64), "feat_uv": z((S, cap, 2), torch.float32), "feat_tag": z((S, cap), torch.int32),
+                             "feat_flags": z((S, cap), torch.uint8), "n_feat": z(S, torch.int32), "outlier_mp_id": z((S, 2 * cap), torch.int64),
+                             "n_outlier_mp": z(S, torch.int32), "right_xy": z((S, cap, 2), torch.float32), "right_ok": z((S, cap), torch.uint8),
+                             "report": z((S, 8), torch.int32)}
+            self.d_right = z((S, self.rows, self.cols), torch.uint8); self.d_mask = z((S, self.rows, self.cols), torch.uint8)
+            self.d_kps = z((S, self.kp_cap, self.api.KP_DTYPE.itemsize), torch.uint8); self.d_nkp = z(S, torch.int32); self.d_kst = z(S, torch.int32)
+        return self.turn_buf
+
+    def enqueue_turn(self):
+        """masks -> detect_batch -> turn for every eligible stream of the bank, asynchronous: three calls on the tracker's stream (the extractor
+        runs on the same one), from the left images of the last step (upload()) and their right images"""
+        buf = self._turn_buffers()
+        img = self.rows * self.cols
+        self.d_right.copy_(self.torch.from_numpy(np.stack([np.ascontiguousarray(R, np.uint8) for _, R in self.images])))
+        self.trk.keyframe_masks(self.d_mask.data_ptr(), self.cols, img)
+        self.orb.detect_batch(self.d_img.data_ptr(), len(self.chains), self.rows, self.cols, self.cols, img, self.d_kps.data_ptr(), self.d_nkp.data_ptr(),
+                              self.d_kst.data_ptr(), self.kp_cap, d_masks=self.d_mask.data_ptr())
+        self.trk.keyframe_batch(self.d_right.data_ptr(), self.cols, img, self.d_kps.data_ptr(), self.d_nkp.data_ptr(), self.kp_cap, self.chains[0].K["baseline"],
+                                {k: v.data_ptr() for k, v in buf.items()})
+
+    def device_turn(self, streams, res=None, t=None, ts=None, resync=True):
+        """The key-frame turns of the frozen streams `streams` (res: the step's result records) ON THE DEVICE: DetectFeatures, FindFeaturesInRight,
+        TriangulateNewPoints and InsertKeyFrame's frontend half never leave it (enqueue_turn), ONE download brings the new key-frames back and the
+        chain's existing host map code (back end, loop closer) takes them.  A stream whose report says no turn (LOST, ids not valid) or capacity
+        takes host_turn.  resync: the chain's map moves points, marks outliers and blurs the key-frame's image on the HOST, so the stream is
+        handed over again afterwards; with those switched off the device's state is already the hand-off and resync=False leaves it alone.
+        res / t default to the last step's records and the frame of the last upload()."""
+        res = self.results() if res is None else res
+        t = self.t if t is None else t
+        self.enqueue_turn()
+        out = {k: v.cpu().numpy() for k, v in self.turn_buf.items()}                  # the one download (synchronises)
+        for s in streams:
+            c, rec = self.chains[s], res[s]
+            if out["report"][s, 0] != 0:
+                self.host_turn(s, rec, t, ts)
+                continue
+            L, R = self.images[s]
+            c.cur = Frame(int(rec["frame_id"]), float(ts if ts is not None else (c.ts[t] if c.ts is not None else t)), L, R)
+            c.next_frame_id = int(rec["frame_id"]) + 1
+            c.status = int(rec["status"])
+            for i in out["outlier_mp_id"][s, :out["n_outlier_mp"][s]]:                # Map::AddOutlierMapPoint, in the device's order
+                c.all_mps[int(i)].outlier = True
+                c.outlier_mps.append(int(i))
+            n, mps, seen = int(out["n_feat"][s]), [], set()
+            for i in range(n):
+                f = Feature(out["feat_uv"][s, i, 0], out["feat_uv"][s, i, 1])
+                mid = int(out["feat_mp_id"][s, i])
+                if mid >= 0:
+                    if mid not in c.all_mps:                                          # a map point the turn created (Map::InsertMapPoint)
+                        c.all_mps[mid] = MapPoint(mid, out["feat_mp_pos"][s, i])
+                        c.next_mp_id = max(c.next_mp_id, mid + 1)
+                    f.mp = c.all_mps[mid]
+                    if mid not in seen:
+                        seen.add(mid); mps.append(f.mp)
+                c.cur.feats.append(f)
+            c.cur.right = [(x, y) if ok else None for (x, y), ok in zip(out["right_xy"][s, :n], out["right_ok"][s, :n])]
+            kf = KeyFrame(int(out["new_kf_id"][s]), c.cur)                            # insert_keyframe() with the device's id and pose
+            c.next_kf_id = kf.id + 1
+            for f in kf.feats:
+                f.kf = kf
+                if f.live() is not None:
+                    f.mp.obs.append(f)
+            kf.pose = out["new_kf_pose"][s].copy()
+            kf.last_kf = c.ref_kf
+            kf.rel_to_last = p7_of(mm(T_of(kf.pose), T_inv(T_of(c.ref_kf.pose))))    # cur.rel, rebuilt from the two poses (the host's to rounding)
+            c.ref_kf = kf
+            c.cur.rel = np.eye(4)
+            c.kf_frames.append(c.cur.id)
+            c.backend_new_keyframe(kf)
+            c.poses.append(p7_of(mm(c.cur.rel, T_of(c.ref_kf.pose))))
+            c.last = c.cur
+            self.slots[s] = mps
+            if resync:
+                c.rel_motion = self.trk.get_frame(s)["rel_motion"]
+                self.hand_off(s)
 
     def host_turn(self, s, rec, t, ts=None):
         """a frozen stream: the device's frame becomes the chain's current frame, the chain does its key-frame work, the result goes back"""
@@ -862,17 +947,21 @@ class StreamBank:
         c.rec("pose_only", rec["pose7"], outl, np.array([int(rec["n_inliers"])]))
 
     def advance(self, t):
-        """one frame of every stream; returns the streams that are still tracking"""
+        """one frame of every stream; returns the streams that are still tracking.  self.device_turns (default False): frozen streams take their
+        key-frame turn through device_turn instead of host_turn"""
         self.upload(t)
         stepped = [s for s, c in enumerate(self.chains) if self.on_device[s]]
         logged = {s: self.trk.get_frame(s) for s in stepped if self.chains[s].keep_log}       # (a logging chain pays two more downloads per frame)
         if stepped:
             self.step()
             res = self.results()
+        turns = [s for s in stepped if res[s]["needs_host"]] if getattr(self, "device_turns", False) else []
         for s, c in enumerate(self.chains):
             if s in stepped:
                 if s in logged:
                     self._log_step(s, logged[s], res[s])
+                if s in turns:
+                    continue
                 if res[s]["needs_host"]:
                     self.host_turn(s, res[s], t)
                 else:
@@ -882,6 +971,8 @@ class StreamBank:
                 c.grab(t)
                 if c.status != INITING:
                     self.hand_off(s)
+        if turns:
+            self.device_turn(turns, res, t, resync=getattr(self, "resync_turns", True))
         return [s for s, c in enumerate(self.chains) if c.status in (INITING, TRACKING_GOOD, TRACKING_BAD)]
 
     def run(self, n):

@@ -11,12 +11,16 @@
 #include <vector>
 
 #include "frontend_launch.h"
+#include "tri_solve.h"
 
 namespace myslam_hip {
 
 constexpr int TRK_NT = 256;                 // threads of the per-stream blocks
 constexpr int TRK_COPY_ROWS = 4;            // image rows one copy block of the head kernel moves
 enum { TRK_INITING = 0, TRK_GOOD = 1, TRK_BAD = 2, TRK_LOST = 3 };
+enum { TRK_WHY_NONE = 0, TRK_WHY_KEYFRAME = 1, TRK_WHY_LOST = 2, TRK_WHY_CAPACITY = 3 };      // why the last step froze the stream
+enum { KF_GO = 0, KF_NO_TURN = 1, KF_CAPACITY = 2 };                        // the turn's head tells its tail
+constexpr int MASK_ROWS = 8;                // mask rows one block of k_kf_masks holds in LDS
 
 struct TrkState {
     double ref_pose[7];
@@ -25,8 +29,11 @@ struct TrkState {
     int32_t n_feat, n_lm, n_outl;
     int32_t slot;                           // which of the two (image, pyramid) buffers holds the stream's previous image
     int32_t overflow;                       // set_frame did not fit: the next step reports it
-    int32_t pad[2];
+    int32_t why;                            // TRK_WHY_*: written by the step that froze the stream, cleared by set_frame and by a turn
+    int32_t idsValid;                       // set_ids since the last set_frame (a turn keeps it)
 };
+static_assert(sizeof(TrkState) == 7 * 8 + 2 * 16 * 8 + 12 * 4, "TrkState");
+
 
 struct TrkArgs {
     TrkState* st; int S, cap, lmCap, rows, cols;
@@ -43,6 +50,14 @@ struct TrkArgs {
     float* curXy; int32_t* curLm; int32_t* curPo; int32_t* curN;
     double* poPose; double* poPts; double* poObs; int32_t* poCounts; uint8_t* poOutl; int32_t* poInl; int32_t* poStatus;
     myslam_tracker_result* res;
+    // ids (MapPoint::mnId by landmark slot; ref_kf_id, next_kf_id, next_mp_id per stream)
+    int64_t* lmId; int64_t* ids;            // S x lmCap; S x 3
+    // key-frame turn scratch (its own: myslam_tracker_debug_last_step keeps reading the last STEP's)
+    int32_t* kfSel; int32_t* kfCounts; int32_t* kfCode;       // S
+    float* kfP0; float* kfNxt; uint8_t* kfSt;                 // S x cap: left pixels, right start points -> right points, LK status
+    double* kfXyz; uint8_t* kfTok; int32_t* kfSlot;           // S x cap: triangulation (camera frame), its ok, the slot a feature opens or -1
+    int32_t* kfFirst; int32_t* kfMap;                         // S x lmCap: first referencing feature, old slot -> new slot
+    double* kfPos; uint8_t* kfOutl; int64_t* kfId;            // S x lmCap: the rebuilt landmark table before it is committed
 };
 
 // ---- SE3 on 4 x 4 row-major doubles, the operations of chain.py in its order ----
@@ -151,7 +166,7 @@ __global__ __launch_bounds__(TRK_NT) void k_trk_head(TrkArgs a) {
             r.n_inliers = 0; r.n_features = 0; r.status = MYSLAM_ERR_CAPACITY; r.frame_id = st.next_frame_id; r.needs_host = 1; r.reserved = 0;
             a.res[s] = r;
             a.sel[s] = -1; a.counts[s] = 0; a.poCounts[s] = 0;
-            a.st[s].frozen = 1;
+            a.st[s].frozen = 1; a.st[s].why = TRK_WHY_CAPACITY;
         }
         return;
     }
@@ -281,6 +296,257 @@ __global__ __launch_bounds__(TRK_NT) void k_trk_tail(TrkArgs a) {
     r.n_inliers = ninl; r.n_features = m; r.status = status; r.frame_id = id; r.needs_host = needs; r.reserved = 0;
     a.res[s] = r;
     st.n_feat = m; st.n_outl = nList; st.next_frame_id = id + 1; st.slot = 1 - st.slot; st.frozen = needs;
+    st.why = !needs ? TRK_WHY_NONE : (status == MYSLAM_ERR_CAPACITY ? TRK_WHY_CAPACITY : (status == TRK_LOST ? TRK_WHY_LOST : TRK_WHY_KEYFRAME));
+}
+
+// =====================================================================================================================================
+// The key-frame turn (include/myslam_hip.h, myslam_tracker_keyframe_*): Frontend::DetectFeatures' mask (:305-309), FindFeaturesInRight
+// (:335-379), TriangulateNewPoints (:451-488) and the pose lines of InsertKeyFrame (:422-446) for every ELIGIBLE stream, on the state above.
+struct KfArgs {
+    const uint8_t* right; int step; size_t stride;
+    const myslam_keypoint* newKps; const int32_t* nNew; int kpCap; double baseline;
+    int64_t* newKfId; double* newKfPose; int64_t* featMpId; double* featMpPos; float* featUv; int32_t* featTag; uint8_t* featFlags; int32_t* nFeat;
+    int64_t* outlMpId; int32_t* nOutlMp; float* rightXy; uint8_t* rightOk; int32_t* report;
+};
+
+__device__ __forceinline__ bool kf_eligible(const TrkState& st) { return st.frozen != 0 && st.why == TRK_WHY_KEYFRAME && st.idsValid != 0; }
+
+// cvRound(float) = rint, ties to even; saturates far outside the image, where the clip below gives the same rectangle
+__device__ __forceinline__ int cv_round(float v) { return __float2int_rn(v); }
+
+// ---- masks: block (x, s) holds MASK_ROWS rows of stream s's mask in LDS: 255, then 0 under every rectangle, then one coalesced store ----
+__global__ __launch_bounds__(TRK_NT) void k_kf_masks(TrkArgs a, uint8_t* masks, int step, size_t stride) {
+    extern __shared__ uint8_t s_band[];                  // MASK_ROWS x cols
+    const int s = blockIdx.y, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const TrkState& st = a.st[s];
+    const int r0 = blockIdx.x * MASK_ROWS, r1 = min(r0 + MASK_ROWS, a.rows), nb = (r1 - r0) * a.cols;
+    const bool el = kf_eligible(st);
+    for (int k = t; k < nb; k += TRK_NT) s_band[k] = el ? 255 : 0;
+    __syncthreads();
+    if (el) {
+        const size_t fb = (size_t)s * a.cap;
+        for (int i = wv; i < st.n_feat; i += TRK_NT / 64) {              // one wave per feature
+            const float x = a.xy[(fb + i) * 2], y = a.xy[(fb + i) * 2 + 1];
+            if (!isfinite(x) || !isfinite(y)) continue;                   // no rectangle (the hosts cannot reach this: LK never keeps such a point)
+            const int x0 = max(cv_round(x - 20.f), 0), x1 = min(cv_round(x + 20.f), a.cols - 1);
+            const int y0 = max(max(cv_round(y - 20.f), 0), r0), y1 = min(min(cv_round(y + 20.f), a.rows - 1), r1 - 1);
+            if (x0 > x1 || y0 > y1) continue;
+            const int w = x1 - x0 + 1, cnt = w * (y1 - y0 + 1);           // <= 41 x MASK_ROWS
+            for (int k = lane; k < cnt; k += 64) s_band[(y0 - r0 + k / w) * a.cols + x0 + k % w] = 0;
+        }
+    }
+    __syncthreads();
+    uint8_t* dst = masks + (size_t)s * stride;
+    for (int k = t; k < nb; k += TRK_NT) dst[(size_t)(r0 + k / a.cols) * step + k % a.cols] = s_band[k];
+}
+
+// ---- turn head: blockIdx.x == 0 decides eligibility, appends the detected key-points and writes the right start points (rules a + b);
+//      the other blocks copy the stream's right image into its free buffer (rule c) ----
+__global__ __launch_bounds__(TRK_NT) void k_kf_head(TrkArgs a, KfArgs k) {
+    const int s = blockIdx.y, t = threadIdx.x;
+    const TrkState& st = a.st[s];
+    const bool el = kf_eligible(st);
+    const int n = st.n_feat, nNew = min(max(k.nNew[s], 0), k.kpCap), m = n + nNew;
+    const bool go = el && m <= a.cap;
+    if (blockIdx.x > 0) {
+        if (!go) return;
+        const int r0 = (blockIdx.x - 1) * TRK_COPY_ROWS, r1 = min(r0 + TRK_COPY_ROWS, a.rows);
+        const uint8_t* src = k.right + (size_t)s * k.stride;
+        uint8_t* dst = a.img + (size_t)(1 - st.slot) * a.imgSel + (size_t)s * a.imgBytes;
+        for (int r = r0; r < r1; r++)
+            for (int x = t; x < a.cols; x += TRK_NT) dst[(size_t)r * a.cols + x] = src[(size_t)r * k.step + x];
+        return;
+    }
+    if (!go) {
+        if (t == 0) { a.kfSel[s] = -1; a.kfCounts[s] = 0; a.kfCode[s] = el ? KF_CAPACITY : KF_NO_TURN; }
+        return;
+    }
+    __shared__ double sT[16];
+    if (t == 0) {
+        double Tref[16];
+        se3_T_of(st.ref_pose, Tref);
+        se3_mm(st.last_rel, Tref, sT);                   // Tcw = cur.rel * T(ref pose), :340
+        a.kfSel[s] = 1 - st.slot; a.kfCounts[s] = m; a.kfCode[s] = KF_GO;
+    }
+    __syncthreads();
+    const size_t fb = (size_t)s * a.cap;
+    const double* pos = a.lmPos + (size_t)s * a.lmCap * 3;
+    const uint8_t* outl = a.lmOutl + (size_t)s * a.lmCap;
+    const myslam_keypoint* kps = k.newKps + (size_t)s * k.kpCap;
+    for (int i = t; i < m; i += TRK_NT) {
+        float x, y;
+        int l = -1;
+        if (i < n) { x = a.xy[(fb + i) * 2]; y = a.xy[(fb + i) * 2 + 1]; l = a.lm[fb + i]; }
+        else { x = kps[i - n].x; y = kps[i - n].y; }
+        float u = x, v = y;
+        if (l >= 0 && !outl[l]) {                        // world2pixel of the RIGHT camera: pc = mv(R, pw) + t, then pc + (-baseline, 0, 0) (:342-349)
+            const double px = pos[3 * l], py = pos[3 * l + 1], pz = pos[3 * l + 2];
+            double pc[3];
+            for (int r = 0; r < 3; r++)
+                pc[r] = dadd(dadd(dadd(dmul(sT[4 * r], px), dmul(sT[4 * r + 1], py)), dmul(sT[4 * r + 2], pz)), sT[4 * r + 3]);
+            pc[0] = dadd(pc[0], -k.baseline); pc[1] = dadd(pc[1], 0.0); pc[2] = dadd(pc[2], 0.0);
+            u = __double2float_rn(dadd(ddiv(dmul(a.fx, pc[0]), pc[2]), a.cx));
+            v = __double2float_rn(dadd(ddiv(dmul(a.fy, pc[1]), pc[2]), a.cy));
+        }
+        a.kfP0[(fb + i) * 2] = x; a.kfP0[(fb + i) * 2 + 1] = y;
+        a.kfNxt[(fb + i) * 2] = u; a.kfNxt[(fb + i) * 2 + 1] = v;
+    }
+}
+
+// ---- turn tail: rules d - g, one block per stream.  Everything is built in scratch and in the output arrays; the state is written last ----
+__global__ __launch_bounds__(TRK_NT) void k_kf_tail(TrkArgs a, KfArgs k) {
+    __shared__ int s_w[TRK_NT / 64];
+    __shared__ double sTcw[16], sTwc[16];
+    const int s = blockIdx.x, t = threadIdx.x;
+    TrkState& st = a.st[s];
+    int32_t* rep = k.report + (size_t)s * 8;
+    const int code = a.kfCode[s];
+    const int n = st.n_feat, nNew = min(max(k.nNew[s], 0), k.kpCap), m = n + nNew, nLm = st.n_lm, nOutl = st.n_outl;
+    auto refuse = [&](int status) {                      // (uniform) no turn: the stream keeps every byte
+        if (t == 0) {
+            k.newKfId[s] = -1; k.nFeat[s] = 0; k.nOutlMp[s] = 0;
+            rep[0] = status; rep[1] = st.next_frame_id - 1; rep[2] = nNew; rep[3] = 0; rep[4] = 0; rep[5] = n; rep[6] = nLm; rep[7] = 0;
+        }
+    };
+    if (code != KF_GO) { refuse(code == KF_CAPACITY ? MYSLAM_ERR_CAPACITY : MYSLAM_TRACKER_NO_TURN); return; }
+    const size_t fb = (size_t)s * a.cap, lb = (size_t)s * a.lmCap;
+    int64_t* ids = a.ids + (size_t)s * 3;
+    const int64_t nextMp = ids[2];
+    if (t == 0) {
+        double Tref[16];
+        se3_T_of(st.ref_pose, Tref);
+        se3_mm(st.last_rel, Tref, sTcw);
+        se3_inv(sTcw, sTwc);                             // Twc of TriangulateNewPoints (:453)
+    }
+    for (int l = t; l < nLm; l += TRK_NT) { a.kfFirst[lb + l] = 0x7fffffff; a.kfMap[lb + l] = -1; }
+    // the outlier list's ids (Map::AddOutlierMapPoint order), read from the table as it is BEFORE the rebuild
+    for (int j = t; j < nOutl; j += TRK_NT) k.outlMpId[(size_t)s * 2 * a.cap + j] = a.lmId[lb + a.outlList[(size_t)s * 2 * a.cap + j]];
+    __syncthreads();
+    // first reference of every old slot (a minimum: the same whatever the order of arrival)
+    for (int i = t; i < n; i += TRK_NT) { const int l = a.lm[fb + i]; if (l >= 0) atomicMin(&a.kfFirst[lb + l], i); }
+    __syncthreads();
+    // rule d (triangulation, feature order) and rule e (slots in order of first reference), 256 features at a time
+    int nTri = 0, nSlots = 0, nRight = 0;
+    for (int base = 0; base < m; base += TRK_NT) {
+        const int i = base + t;
+        int l = -1; bool rok = false, tri = false, opens = false;
+        double X[3] = {0, 0, 0};
+        if (i < m) {
+            l = i < n ? a.lm[fb + i] : -1;
+            rok = a.kfSt[fb + i] != 0;
+            if (l < 0 && rok) {                          // expired() && mvpFeaturesRight[i] != nullptr (:458-459)
+                const double ul = a.kfP0[(fb + i) * 2], vl = a.kfP0[(fb + i) * 2 + 1], ur = a.kfNxt[(fb + i) * 2], vr = a.kfNxt[(fb + i) * 2 + 1];
+                const double P[2][12] = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0},
+                                         {1, 0, 0, -k.baseline, 0, 1, 0, 0, 0, 0, 1, 0}};      // as match_tri.hip's k_triangulate
+                const double pt[2][2] = {{(ul - a.cx) / a.fx, (vl - a.cy) / a.fy}, {(ur - a.cx) / a.fx, (vr - a.cy) / a.fy}};
+                double ratio;
+                tri_solve(P, pt, X, ratio);
+                tri = ratio < 1e-2 && X[2] > 0;
+            }
+            a.kfXyz[(fb + i) * 3] = X[0]; a.kfXyz[(fb + i) * 3 + 1] = X[1]; a.kfXyz[(fb + i) * 3 + 2] = X[2];
+            a.kfTok[fb + i] = tri ? 1 : 0;
+            // (the minimum was formed by atomics in L2: read it there, not from a line this CU may still hold)
+            opens = tri || (l >= 0 && __hip_atomic_load(&a.kfFirst[lb + l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == i);
+        }
+        int tt, ts, tr;
+        const int rt = block_rank(tri, s_w, tt), rs = block_rank(opens, s_w, ts);
+        (void)block_rank(rok, s_w, tr);
+        if (i < m) {
+            const int slot = opens ? nSlots + rs : -1;
+            a.kfSlot[fb + i] = slot;
+            int64_t id = -1;
+            double p[3] = {0, 0, 0};
+            if (tri) {                                   // a new map point: id by rank, pos = mv(Twc.R, p) + Twc.t (:474-476)
+                id = nextMp + nTri + rt;
+                for (int r = 0; r < 3; r++)
+                    p[r] = dadd(dadd(dadd(dmul(sTwc[4 * r], X[0]), dmul(sTwc[4 * r + 1], X[1])), dmul(sTwc[4 * r + 2], X[2])), sTwc[4 * r + 3]);
+            } else if (l >= 0) {
+                id = a.lmId[lb + l];
+                for (int r = 0; r < 3; r++) p[r] = a.lmPos[(lb + l) * 3 + r];
+            }
+            if (opens && slot < a.lmCap) {               // (beyond lmCap the turn is refused below)
+                if (l >= 0) a.kfMap[lb + l] = slot;
+                a.kfId[lb + slot] = id; a.kfOutl[lb + slot] = l >= 0 ? a.lmOutl[lb + l] : 0;
+                for (int r = 0; r < 3; r++) a.kfPos[(lb + slot) * 3 + r] = p[r];
+            }
+            k.featMpId[fb + i] = id;
+            for (int r = 0; r < 3; r++) k.featMpPos[(fb + i) * 3 + r] = p[r];
+            k.featUv[(fb + i) * 2] = a.kfP0[(fb + i) * 2]; k.featUv[(fb + i) * 2 + 1] = a.kfP0[(fb + i) * 2 + 1];
+            k.featTag[fb + i] = i; k.featFlags[fb + i] = 0;
+            k.rightXy[(fb + i) * 2] = a.kfNxt[(fb + i) * 2]; k.rightXy[(fb + i) * 2 + 1] = a.kfNxt[(fb + i) * 2 + 1];
+            k.rightOk[fb + i] = rok ? 1 : 0;
+        }
+        nTri += tt; nSlots += ts; nRight += tr;
+    }
+    if (nSlots > a.lmCap) { refuse(MYSLAM_ERR_CAPACITY); return; }       // uniform
+    __syncthreads();                                     // kfMap, kfPos .. are complete; every read of the old tables is done
+    // ---- commit ----
+    for (int i = t; i < m; i += TRK_NT) {
+        const int l = i < n ? a.lm[fb + i] : -1;
+        const int slot = a.kfSlot[fb + i];
+        a.lm[fb + i] = slot >= 0 ? slot : (l >= 0 ? a.kfMap[lb + l] : -1);
+        if (i >= n) { a.xy[(fb + i) * 2] = a.kfP0[(fb + i) * 2]; a.xy[(fb + i) * 2 + 1] = a.kfP0[(fb + i) * 2 + 1]; }
+    }
+    for (int j = t; j < nSlots; j += TRK_NT) {
+        a.lmId[lb + j] = a.kfId[lb + j]; a.lmOutl[lb + j] = a.kfOutl[lb + j];
+        for (int r = 0; r < 3; r++) a.lmPos[(lb + j) * 3 + r] = a.kfPos[(lb + j) * 3 + r];
+    }
+    if (t != 0) return;
+    double pose[7];
+    se3_p7_of(sTcw, pose);                               // kf.pose = p7(cur.rel * T(ref pose)) (:433)
+    const int64_t kfId = ids[1];
+    for (int c = 0; c < 7; c++) { st.ref_pose[c] = pose[c]; k.newKfPose[(size_t)s * 7 + c] = pose[c]; }
+    for (int c = 0; c < 16; c++) st.last_rel[c] = (c % 5 == 0) ? 1.0 : 0.0;          // cur.rel = I (:440)
+    ids[0] = kfId; ids[1] = kfId + 1; ids[2] = nextMp + nTri;
+    st.ref_frame_id = st.next_frame_id - 1;
+    st.n_feat = m; st.n_lm = nSlots; st.n_outl = 0; st.frozen = 0; st.why = TRK_WHY_NONE;
+    k.newKfId[s] = kfId; k.nFeat[s] = m; k.nOutlMp[s] = nOutl;
+    rep[0] = MYSLAM_OK; rep[1] = st.ref_frame_id; rep[2] = nNew; rep[3] = nRight; rep[4] = nTri; rep[5] = m; rep[6] = nSlots; rep[7] = 0;
+}
+
+// ---- the map moved under the tracker (back end, loop closer): landmarks and the reference pose follow their ids ----
+struct MapArgs {
+    const int64_t* kfId; const double* kfPose; const int32_t* nKf; int kfCap;
+    const int64_t* mpId; const double* mpPos; const uint8_t* mpOutl; const int32_t* nMp; int mpCap;
+};
+
+__device__ __forceinline__ int find_id(const int64_t* ids, int n, int64_t id) {      // ids ascend; -1 = absent
+    int lo = 0, hi = n;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (ids[mid] < id) lo = mid + 1; else hi = mid; }
+    return (lo < n && ids[lo] == id) ? lo : -1;
+}
+
+__global__ __launch_bounds__(TRK_NT) void k_kf_update(TrkArgs a, MapArgs g) {
+    const int s = blockIdx.x, t = threadIdx.x;
+    TrkState& st = a.st[s];
+    if (st.frozen != 0 || st.idsValid == 0) return;
+    const size_t lb = (size_t)s * a.lmCap;
+    const int nMp = min(max(g.nMp[s], 0), g.mpCap), nKf = min(max(g.nKf[s], 0), g.kfCap);
+    const int64_t* mpId = g.mpId + (size_t)s * g.mpCap;
+    for (int l = t; l < st.n_lm; l += TRK_NT) {
+        const int r = find_id(mpId, nMp, a.lmId[lb + l]);
+        if (r < 0) continue;
+        for (int c = 0; c < 3; c++) a.lmPos[(lb + l) * 3 + c] = g.mpPos[((size_t)s * g.mpCap + r) * 3 + c];
+        a.lmOutl[lb + l] = g.mpOutl[(size_t)s * g.mpCap + r];
+    }
+    if (t == 0) {
+        const int r = find_id(g.kfId + (size_t)s * g.kfCap, nKf, a.ids[(size_t)s * 3]);
+        if (r >= 0) for (int c = 0; c < 7; c++) st.ref_pose[c] = g.kfPose[((size_t)s * g.kfCap + r) * 7 + c];
+    }
+}
+
+// ---- the stored previous left image of the selected streams <- imgs (the pyramid follows in lk_bank_pyramid) ----
+__global__ __launch_bounds__(TRK_NT) void k_kf_set_image(TrkArgs a, const uint8_t* imgs, int step, size_t stride, const uint8_t* select) {
+    const int s = blockIdx.y, t = threadIdx.x;
+    const bool on = select[s] != 0;
+    const int slot = a.st[s].slot;
+    if (blockIdx.x == 0) { if (t == 0) a.kfSel[s] = on ? slot : -1; return; }
+    if (!on) return;
+    const int r0 = (blockIdx.x - 1) * TRK_COPY_ROWS, r1 = min(r0 + TRK_COPY_ROWS, a.rows);
+    const uint8_t* src = imgs + (size_t)s * stride;
+    uint8_t* dst = a.img + (size_t)slot * a.imgSel + (size_t)s * a.imgBytes;
+    for (int r = r0; r < r1; r++)
+        for (int x = t; x < a.cols; x += TRK_NT) dst[(size_t)r * a.cols + x] = src[(size_t)r * step + x];
 }
 
 }  // namespace myslam_hip
@@ -308,7 +574,11 @@ static int trk_alloc_all(myslam_tracker* h) {
         (rc = own(a.sel, S)) || (rc = own(a.counts, S)) || (rc = own(a.p0, F * 2)) || (rc = own(a.p1, F * 2)) || (rc = own(a.nxt, F * 2)) ||
         (rc = own(a.lkSt, F)) || (rc = own(a.curXy, F * 2)) || (rc = own(a.curLm, F)) || (rc = own(a.curPo, F)) || (rc = own(a.curN, S)) ||
         (rc = own(a.poPose, S * 7)) || (rc = own(a.poPts, F * 3)) || (rc = own(a.poObs, F * 2)) || (rc = own(a.poCounts, S)) ||
-        (rc = own(a.poOutl, F)) || (rc = own(a.poInl, S)) || (rc = own(a.poStatus, S)))
+        (rc = own(a.poOutl, F)) || (rc = own(a.poInl, S)) || (rc = own(a.poStatus, S)) ||
+        (rc = own(a.lmId, L)) || (rc = own(a.ids, S * 3)) || (rc = own(a.kfSel, S)) || (rc = own(a.kfCounts, S)) || (rc = own(a.kfCode, S)) ||
+        (rc = own(a.kfP0, F * 2)) || (rc = own(a.kfNxt, F * 2)) || (rc = own(a.kfSt, F)) || (rc = own(a.kfXyz, F * 3)) || (rc = own(a.kfTok, F)) ||
+        (rc = own(a.kfSlot, F)) || (rc = own(a.kfFirst, L)) || (rc = own(a.kfMap, L)) || (rc = own(a.kfPos, L * 3)) || (rc = own(a.kfOutl, L)) ||
+        (rc = own(a.kfId, L)))
         return rc;
     std::vector<TrkState> init(S);
     memset(init.data(), 0, S * sizeof(TrkState));
@@ -316,6 +586,8 @@ static int trk_alloc_all(myslam_tracker* h) {
     // (every other buffer is written before it is read: tables by set_frame, scratch by the step's own kernels)
     const std::vector<int32_t> zeros(S, 0);
     if ((rc = upload_table(a.st, init.data(), S * sizeof(TrkState))) || (rc = upload_table(a.counts, zeros.data(), S * sizeof(int32_t)))) return rc;
+    const std::vector<int64_t> zeros64(S * 3, 0);
+    if ((rc = upload_table(a.kfCounts, zeros.data(), S * sizeof(int32_t))) || (rc = upload_table(a.ids, zeros64.data(), S * 3 * sizeof(int64_t)))) return rc;
     return MYSLAM_OK;
 }
 
@@ -377,6 +649,7 @@ int myslam_tracker_set_frame(myslam_tracker* h, int s, const float* feat_xy, con
     memcpy(hs.ref_pose, ref_pose7, sizeof(double) * 7); memcpy(hs.last_rel, last_rel16, sizeof(double) * 16); memcpy(hs.rel_motion, rel_motion16, sizeof(double) * 16);
     hs.ref_frame_id = ref_frame_id; hs.next_frame_id = next_frame_id; hs.status = status; hs.kf_every = kf_every;
     hs.frozen = 0; hs.n_outl = 0; hs.overflow = fits ? 0 : 1;
+    hs.why = TRK_WHY_NONE; hs.idsValid = 0;  // the landmark table is new: its ids are the caller's to give again (myslam_tracker_set_ids)
     hs.n_feat = fits ? n_feat : 0; hs.n_lm = fits ? n_landmarks : 0;
     if (fits) {
         const size_t fb = (size_t)s * h->cap, lb = (size_t)s * h->lmCap;
@@ -481,6 +754,132 @@ int myslam_tracker_debug_last_step(myslam_tracker* h, int s, float* p0, float* p
     }
     *n = cnt;
     return MYSLAM_OK;
+}
+
+// ---- key-frame turns ----
+int myslam_tracker_set_ids(myslam_tracker* h, int s, const int64_t* landmark_id, int n_landmarks, int64_t ref_kf_id, int64_t next_kf_id, int64_t next_mp_id) {
+    if (!h || s < 0 || s >= h->S || n_landmarks < 0 || (n_landmarks > 0 && !landmark_id) || ref_kf_id < 0 || next_kf_id < 0 || next_mp_id < 0)
+        return MYSLAM_ERR_INVALID;
+    hipStream_t st = h->stream;
+    TrkArgs& a = h->a;
+    TrkState hs;
+    int rc = copy_sync(&hs, a.st + s, sizeof(TrkState), hipMemcpyDeviceToHost, st);
+    if (rc) return rc;
+    if (n_landmarks != hs.n_lm) return MYSLAM_ERR_INVALID;
+    for (int l = 0; l < n_landmarks; l++) if (landmark_id[l] < 0 || landmark_id[l] >= next_mp_id) return MYSLAM_ERR_INVALID;
+    const int64_t ids[3] = {ref_kf_id, next_kf_id, next_mp_id};
+    const int32_t one = 1;
+    if (n_landmarks) MYSLAM_HIP_CHECK(hipMemcpyAsync(a.lmId + (size_t)s * h->lmCap, landmark_id, sizeof(int64_t) * n_landmarks, hipMemcpyHostToDevice, st));
+    MYSLAM_HIP_CHECK(hipMemcpyAsync(a.ids + (size_t)s * 3, ids, sizeof(ids), hipMemcpyHostToDevice, st));
+    MYSLAM_HIP_CHECK(hipMemcpyAsync(&a.st[s].idsValid, &one, sizeof(one), hipMemcpyHostToDevice, st));
+    MYSLAM_HIP_CHECK(hipStreamSynchronize(st));
+    return MYSLAM_OK;
+}
+
+int myslam_tracker_get_ids(myslam_tracker* h, int s, int64_t* landmark_id, int* n_landmarks, int64_t* ref_kf_id, int64_t* next_kf_id, int64_t* next_mp_id,
+                           int* valid) {
+    if (!h || s < 0 || s >= h->S) return MYSLAM_ERR_INVALID;
+    hipStream_t st = h->stream;
+    TrkArgs& a = h->a;
+    TrkState hs;
+    int rc = copy_sync(&hs, a.st + s, sizeof(TrkState), hipMemcpyDeviceToHost, st);
+    if (rc) return rc;
+    int64_t ids[3];
+    if (landmark_id && hs.n_lm)
+        MYSLAM_HIP_CHECK(hipMemcpyAsync(landmark_id, a.lmId + (size_t)s * h->lmCap, sizeof(int64_t) * hs.n_lm, hipMemcpyDeviceToHost, st));
+    if ((rc = copy_sync(ids, a.ids + (size_t)s * 3, sizeof(ids), hipMemcpyDeviceToHost, st))) return rc;
+    if (n_landmarks) *n_landmarks = hs.n_lm;
+    if (ref_kf_id) *ref_kf_id = ids[0];
+    if (next_kf_id) *next_kf_id = ids[1];
+    if (next_mp_id) *next_mp_id = ids[2];
+    if (valid) *valid = hs.idsValid;
+    return MYSLAM_OK;
+}
+
+int myslam_tracker_keyframe_masks(myslam_tracker* h, uint8_t* d_masks, int step, size_t stride) {
+    if (!h || !d_masks || step < h->cols || stride < (size_t)(h->rows - 1) * step + h->cols) return MYSLAM_ERR_INVALID;
+    if ((size_t)MASK_ROWS * h->cols > 65536) return MYSLAM_ERR_UNSUPPORTED;           // one block's band of the mask lives in LDS
+    hipLaunchKernelGGL(k_kf_masks, dim3((h->rows + MASK_ROWS - 1) / MASK_ROWS, h->S), dim3(TRK_NT), (size_t)MASK_ROWS * h->cols, h->stream, h->a, d_masks, step,
+                       stride);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    return MYSLAM_OK;
+}
+
+int myslam_tracker_keyframe_launches(const myslam_tracker* h) {
+    return h ? 3 + h->levels : MYSLAM_ERR_INVALID;
+}
+
+int myslam_tracker_keyframe_batch(myslam_tracker* h, const uint8_t* d_right, int step, size_t stride, const myslam_keypoint* d_new_kps,
+                                  const int32_t* d_n_new, int kp_cap, double baseline, int64_t* d_new_kf_id, double* d_new_kf_pose, int64_t* d_feat_mp_id,
+                                  double* d_feat_mp_pos, float* d_feat_uv, int32_t* d_feat_tag, uint8_t* d_feat_flags, int32_t* d_n_feat,
+                                  int64_t* d_outlier_mp_id, int32_t* d_n_outlier_mp, float* d_right_xy, uint8_t* d_right_ok, int32_t* d_report) {
+    if (!h || !d_right || !d_new_kps || !d_n_new || !d_new_kf_id || !d_new_kf_pose || !d_feat_mp_id || !d_feat_mp_pos || !d_feat_uv || !d_feat_tag ||
+        !d_feat_flags || !d_n_feat || !d_outlier_mp_id || !d_n_outlier_mp || !d_right_xy || !d_right_ok || !d_report)
+        return MYSLAM_ERR_INVALID;
+    if (step < h->cols || stride < (size_t)(h->rows - 1) * step + h->cols || kp_cap < 1) return MYSLAM_ERR_INVALID;
+    const TrkArgs& a = h->a;
+    const KfArgs k{d_right, step, stride, d_new_kps, d_n_new, kp_cap, baseline, d_new_kf_id, d_new_kf_pose, d_feat_mp_id, d_feat_mp_pos, d_feat_uv, d_feat_tag,
+                   d_feat_flags, d_n_feat, d_outlier_mp_id, d_n_outlier_mp, d_right_xy, d_right_ok, d_report};
+    hipStream_t st = h->stream;
+    const int S = h->S;
+    const size_t pyrSel = (size_t)S * h->pyrBytes;
+    hipLaunchKernelGGL(k_kf_head, dim3(1 + (h->rows + TRK_COPY_ROWS - 1) / TRK_COPY_ROWS, S), dim3(TRK_NT), 0, st, a, k);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    int rc;
+    // the right image's levels into the stream's FREE buffer, then LK from the left image (buffer `slot`) into it (:358-361)
+    if ((rc = lk_bank_pyramid(h->lk, d_right, step, stride, h->d_pyr, S, a.kfSel, pyrSel))) return rc;
+    if ((rc = lk_bank_track(h->lk, a.img, h->cols, a.imgBytes, h->d_pyr, S, a.kfSel, a.imgSel, pyrSel, a.kfP0, a.kfNxt, a.kfCounts, h->cap, a.kfSt))) return rc;
+    hipLaunchKernelGGL(k_kf_tail, dim3(S), dim3(TRK_NT), 0, st, a, k);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    return MYSLAM_OK;
+}
+
+int myslam_tracker_debug_last_turn(myslam_tracker* h, int s, float* left_xy, float* right_xy, uint8_t* right_ok, double* tri_xyz, uint8_t* tri_ok, int* n) {
+    if (!h || s < 0 || s >= h->S || !n) return MYSLAM_ERR_INVALID;
+    hipStream_t st = h->stream;
+    const TrkArgs& a = h->a;
+    int32_t cnt = 0;
+    int rc = copy_sync(&cnt, a.kfCounts + s, sizeof(int32_t), hipMemcpyDeviceToHost, st);
+    if (rc) return rc;
+    const size_t fb = (size_t)s * h->cap;
+    if (cnt > 0) {
+        if (left_xy) MYSLAM_HIP_CHECK(hipMemcpyAsync(left_xy, a.kfP0 + fb * 2, sizeof(float) * 2 * cnt, hipMemcpyDeviceToHost, st));
+        if (right_xy) MYSLAM_HIP_CHECK(hipMemcpyAsync(right_xy, a.kfNxt + fb * 2, sizeof(float) * 2 * cnt, hipMemcpyDeviceToHost, st));
+        if (right_ok) MYSLAM_HIP_CHECK(hipMemcpyAsync(right_ok, a.kfSt + fb, (size_t)cnt, hipMemcpyDeviceToHost, st));
+        if (tri_xyz) MYSLAM_HIP_CHECK(hipMemcpyAsync(tri_xyz, a.kfXyz + fb * 3, sizeof(double) * 3 * cnt, hipMemcpyDeviceToHost, st));
+        if (tri_ok) MYSLAM_HIP_CHECK(hipMemcpyAsync(tri_ok, a.kfTok + fb, (size_t)cnt, hipMemcpyDeviceToHost, st));
+        MYSLAM_HIP_CHECK(hipStreamSynchronize(st));
+    }
+    *n = cnt;
+    return MYSLAM_OK;
+}
+
+int myslam_tracker_debug_freeze(myslam_tracker* h, int s, int why) {
+    if (!h || s < 0 || s >= h->S || why < TRK_WHY_KEYFRAME || why > TRK_WHY_CAPACITY) return MYSLAM_ERR_INVALID;
+    const int32_t w[2] = {1, why};
+    hipStream_t st = h->stream;
+    MYSLAM_HIP_CHECK(hipMemcpyAsync(&h->a.st[s].frozen, &w[0], sizeof(int32_t), hipMemcpyHostToDevice, st));
+    MYSLAM_HIP_CHECK(hipMemcpyAsync(&h->a.st[s].why, &w[1], sizeof(int32_t), hipMemcpyHostToDevice, st));
+    MYSLAM_HIP_CHECK(hipStreamSynchronize(st));
+    return MYSLAM_OK;
+}
+
+int myslam_tracker_update_from_map_batch(myslam_tracker* h, const int64_t* d_kf_id, const double* d_kf_pose, const int32_t* d_n_kf, int kf_cap,
+                                         const int64_t* d_mp_id, const double* d_mp_pos, const uint8_t* d_mp_outlier, const int32_t* d_n_mp, int mp_cap) {
+    if (!h || !d_kf_id || !d_kf_pose || !d_n_kf || kf_cap < 1 || !d_mp_id || !d_mp_pos || !d_mp_outlier || !d_n_mp || mp_cap < 1) return MYSLAM_ERR_INVALID;
+    const MapArgs g{d_kf_id, d_kf_pose, d_n_kf, kf_cap, d_mp_id, d_mp_pos, d_mp_outlier, d_n_mp, mp_cap};
+    hipLaunchKernelGGL(k_kf_update, dim3(h->S), dim3(TRK_NT), 0, h->stream, h->a, g);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    return MYSLAM_OK;
+}
+
+int myslam_tracker_set_image_batch(myslam_tracker* h, const uint8_t* d_imgs, int step, size_t stride, const uint8_t* d_select) {
+    if (!h || !d_imgs || !d_select || step < h->cols || stride < (size_t)(h->rows - 1) * step + h->cols) return MYSLAM_ERR_INVALID;
+    const TrkArgs& a = h->a;
+    hipLaunchKernelGGL(k_kf_set_image, dim3(1 + (h->rows + TRK_COPY_ROWS - 1) / TRK_COPY_ROWS, h->S), dim3(TRK_NT), 0, h->stream, a, d_imgs, step, stride,
+                       d_select);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    return lk_bank_pyramid(h->lk, d_imgs, step, stride, h->d_pyr, h->S, a.kfSel, (size_t)h->S * h->pyrBytes);
 }
 
 }  // extern "C"

@@ -409,6 +409,46 @@ public:
     void Step(const uint8_t* d_left, int step, size_t stride, myslam_tracker_result* d_results) {
         check(myslam_tracker_step_batch(h_, d_left, step, stride, d_results), "myslam_tracker_step_batch");
     }
+    // ---- key-frame turns on the device (include/myslam_hip.h, "Key-frame turns on the device": every rule and error is stated there) ----
+    struct StreamIds {              // MapPoint::mnId by landmark slot, the reference key-frame's mnKFId and the stream's id counters
+        std::vector<int64_t> landmarkId; int64_t refKfId = 0, nextKfId = 0, nextMpId = 0; int valid = 0;
+    };
+    struct TurnOutputs {            // device pointers, the layout myslam_backend_insert_keyframe_batch reads (feature stride cap, outlier stride 2 cap)
+        int64_t* newKfId; double* newKfPose; int64_t* featMpId; double* featMpPos; float* featUv; int32_t* featTag; uint8_t* featFlags; int32_t* nFeat;
+        int64_t* outlierMpId; int32_t* nOutlierMp; float* rightXy; uint8_t* rightOk; int32_t* report;      // report: streams() x 8
+    };
+    int keyframeLaunches() const { return myslam_tracker_keyframe_launches(h_); }
+    void SetIds(int stream, const StreamIds& ids) {
+        check(myslam_tracker_set_ids(h_, stream, ids.landmarkId.data(), (int)ids.landmarkId.size(), ids.refKfId, ids.nextKfId, ids.nextMpId),
+              "myslam_tracker_set_ids");
+    }
+    void GetIds(int stream, StreamIds& ids) {
+        ids.landmarkId.resize(lmCap_);
+        int n = 0;
+        check(myslam_tracker_get_ids(h_, stream, ids.landmarkId.data(), &n, &ids.refKfId, &ids.nextKfId, &ids.nextMpId, &ids.valid), "myslam_tracker_get_ids");
+        ids.landmarkId.resize(n);
+    }
+    // every stream's detection mask in myslam_orb_detect_batch's d_masks layout (all 0 where no turn is due)
+    void KeyframeMasks(uint8_t* d_masks, int step, size_t stride) {
+        check(myslam_tracker_keyframe_masks(h_, d_masks, step, stride), "myslam_tracker_keyframe_masks");
+    }
+    // d_right: the right images of the step that froze the streams; d_newKps / d_nNew: what detect_batch found under the masks
+    void KeyframeBatch(const uint8_t* d_right, int step, size_t stride, const myslam_keypoint* d_newKps, const int32_t* d_nNew, int kpCap, double baseline,
+                       const TurnOutputs& o) {
+        check(myslam_tracker_keyframe_batch(h_, d_right, step, stride, d_newKps, d_nNew, kpCap, baseline, o.newKfId, o.newKfPose, o.featMpId, o.featMpPos,
+                                            o.featUv, o.featTag, o.featFlags, o.nFeat, o.outlierMpId, o.nOutlierMp, o.rightXy, o.rightOk, o.report),
+              "myslam_tracker_keyframe_batch");
+    }
+    // the back end's tables (item s = stream s) after they moved: running streams follow their ids
+    void UpdateFromMap(const int64_t* d_kfId, const double* d_kfPose, const int32_t* d_nKf, int kfCap, const int64_t* d_mpId, const double* d_mpPos,
+                       const uint8_t* d_mpOutlier, const int32_t* d_nMp, int mpCap) {
+        check(myslam_tracker_update_from_map_batch(h_, d_kfId, d_kfPose, d_nKf, kfCap, d_mpId, d_mpPos, d_mpOutlier, d_nMp, mpCap),
+              "myslam_tracker_update_from_map_batch");
+    }
+    // the stored previous left image of the selected streams <- d_imgs[s] (a key-frame's image after DeepLCD blurred it)
+    void SetImageBatch(const uint8_t* d_imgs, int step, size_t stride, const uint8_t* d_select) {
+        check(myslam_tracker_set_image_batch(h_, d_imgs, step, stride, d_select), "myslam_tracker_set_image_batch");
+    }
 };
 
 // Camera::UndistortImage (include/myslam/camera.h, src/camera.cpp:36-48): cv::undistort(src, dst, K, distCoef) for one camera at one image

@@ -770,6 +770,99 @@ int myslam_tracker_launches_per_step(const myslam_tracker* h);
 int myslam_tracker_debug_last_step(myslam_tracker* h, int stream, float* p0, float* p1, float* tracked, uint8_t* lk_status, int* n);
 
 /* ------------------------------------------------------------------------------------------
+ * Key-frame turns on the device — what a frozen stream needed the host for when the key-frame rule fired: Frontend::DetectFeatures' mask
+ * (src/frontend.cpp:302-328), FindFeaturesInRight (:335-379), TriangulateNewPoints (:451-488) and the frontend's half of InsertKeyFrame
+ * (:422-446), for every eligible stream of the bank at once, written where myslam_backend_insert_keyframe_batch reads a new key-frame.
+ * Detection itself stays myslam_orb_detect_batch: masks -> detect_batch (the caller's extractor, same stream) -> turn -> next step.
+ *
+ * Ids.  Per stream the handle also holds MapPoint::mnId by landmark slot (i64), ref_kf_id = the reference key-frame's mnKFId, next_kf_id and
+ * next_mp_id (the id factories, keyframe.cpp:14 / mappoint.cpp:8, per stream) and an "ids valid" flag that myslam_tracker_set_frame CLEARS
+ * (a new landmark table has no ids yet).  set_ids / get_ids: host pointers, synchronous, as set_frame / get_frame.  set_ids returns
+ * MYSLAM_ERR_INVALID when n_landmarks is not the stream's landmark count, when an id (ref_kf_id and the counters included) is negative or when
+ * next_mp_id is not above every landmark id; otherwise it stores the ids and sets the flag.  Each step also records WHY it froze a stream:
+ * the key-frame rule, LOST, or capacity (one word of the state, one store in the step's tail; nothing else of a step changes).
+ * A stream is ELIGIBLE for a turn when it is frozen, the freezing step recorded "key-frame rule" (not LOST, not capacity, not "never set")
+ * and its ids are valid.
+ *
+ * myslam_tracker_keyframe_masks — 1 launch on the handle's stream, asynchronous: writes every stream's whole mask (rows x cols bytes, mask s at
+ * d_masks + s * stride, row pitch `step`: the d_masks layout of myslam_orb_detect_batch).  Eligible stream: 255, then 0 in
+ * [cvRound(x - 20), cvRound(x + 20)] x [cvRound(y - 20), cvRound(y + 20)] around every feature of its table, both ends included, clipped to the
+ * image; x -+ 20 in f32, cvRound = round to nearest, ties to even (cv::rectangle(pt - (20, 20), pt + (20, 20), 0, CV_FILLED), :305-309).
+ * Rectangles overlap freely.  A feature with a non-finite coordinate draws NOTHING (a choice: the hosts cannot reach it, LK never keeps such a
+ * point).  Stream not eligible: all 0 (the extractor then finds nothing).  step < cols, a stride that does not hold the image or NULL:
+ * MYSLAM_ERR_INVALID; cols > 8192 (8 mask rows of one block live in LDS): MYSLAM_ERR_UNSUPPORTED.
+ *
+ * myslam_tracker_keyframe_batch — device pointers, asynchronous on the handle's stream, never synchronises, allocates nothing (its scratch
+ * is the handle's from create on), recordable between myslam_graph_begin / _end; myslam_tracker_keyframe_launches = 3 + (pyramid levels
+ * above 0) dependent launches: head, one per level, LK, tail.  d_right (image s at d_right + s * stride, pitch step) = the right images of the
+ * step that froze the streams; d_new_kps S x kp_cap (only x, y are read), d_n_new S (below 0 reads as 0, above kp_cap as kp_cap).
+ * For an eligible stream, everything is decided before a byte of its state is written:
+ *   a. the detected key-points follow the table's features in order, landmark -1 (:319-323);
+ *   b. right start point of a feature whose landmark is not marked outlier = (float)world2pixel_right(pos, Tcw), Tcw = last.rel * T(ref pose):
+ *      pc = mv(R, pw) + t, then pc + (-baseline, 0, 0) — f64, each product and sum rounded on its own as in rule 1 of the step; every other
+ *      feature starts at its own pixel (:342-353);
+ *   c. the right image goes into the stream's FREE image buffer (where the next step's image goes anyway) with its pyramid levels, and LK tracks
+ *      left -> right with the arithmetic of myslam_lk_track (:358-361): mvpFeaturesRight[i] = (point, status);
+ *   d. every feature with landmark -1 and right status set, in feature order (:456-485), is triangulated with match_tri's solve
+ *      (myslam_triangulate_stereo's bits: one device function, csrc/tri_solve.h); where sigma3 / sigma2 < 1e-2 && z > 0 a map point is created:
+ *      id = next_mp_id + its rank among the successes, pos = mv(Twc.R, p) + Twc.t with Twc = T_inv(Tcw) (:474-476);
+ *   e. the landmark table is rebuilt: slots in order of FIRST reference by the features of the final table, two features on one landmark share
+ *      a slot, landmarks nobody names are dropped; outlier flags and ids move with their landmarks;
+ *   f. InsertKeyFrame (:422-446): kf_id = next_kf_id++, pose = p7(last.rel * T(ref pose)); ref pose = pose, ref_kf_id = kf_id, ref frame id =
+ *      next frame id - 1, last.rel = I; rel_motion and status are kept; the outlier list is emptied, frozen = 0 (ids stay valid);
+ *   g. outputs, feature stride = the tracker's cap (the layout myslam_backend_insert_keyframe_batch reads with feat_cap = cap, outlier_cap = 2 cap):
+ *      d_new_kf_id S i64 (-1: no turn), d_new_kf_pose S x 7, d_feat_mp_id (-1: none) / d_feat_mp_pos (0 without a map point) / d_feat_uv /
+ *      d_feat_tag (= the feature's index) / d_feat_flags (0), d_n_feat (0: no turn); d_outlier_mp_id S x 2 cap = the ids of the stream's outlier
+ *      list in its order, read BEFORE the rebuild, d_n_outlier_mp; d_right_xy / d_right_ok S x cap; d_report S x 8 i32 = (turn status, frame id of
+ *      the stream's last frame, detected features, right matches, new map points, final feature count, final landmark count, 0).  d_feat_uv with
+ *      d_n_feat is also myslam_orb_process_keyframes_batch's d_feat_xy.  Rows from a count on, and the feature rows of a refused turn, are
+ *      unspecified.
+ * Turn status: 0 taken; MYSLAM_TRACKER_NO_TURN the stream was not eligible — its state, stored images and pyramids keep every byte;
+ * MYSLAM_ERR_CAPACITY when n_feat + n_new > cap or the rebuilt table has more than landmark_cap landmarks — the stream stays frozen with every
+ * byte of its state as before (get_frame and a host turn still work; only its free image buffer may hold the right image).
+ * Call level, nothing enqueued: NULL pointers, step < cols, a stride that does not hold the image or kp_cap < 1 -> MYSLAM_ERR_INVALID.
+ * What myslam_backend_insert_keyframe_batch does with a no-turn item (d_new_kf_id = -1, d_n_feat = 0): on a table that holds a key-frame the id
+ * is not above the last one -> that item is refused with MYSLAM_ERR_INVALID and keeps every byte.  On an EMPTY key-frame table there is no last
+ * id to compare with and the row (-1, pose) WOULD BE APPENDED: a stream's table holds its StereoInit key-frame before any turn can happen, and a
+ * caller that batches other tables must take such items out itself.
+ *
+ * myslam_tracker_update_from_map_batch — 1 launch.  In the reference the frontend holds the MapPoint / KeyFrame objects the back end and the loop
+ * closer move.  Item s = stream s: d_kf_id S x kf_cap ascending / d_kf_pose x 7 / d_n_kf, d_mp_id S x mp_cap ascending / d_mp_pos x 3 /
+ * d_mp_outlier / d_n_mp (the tables of myslam_backend_optimize_batch; counts are clamped to [0, cap]).  For every stream that is NOT frozen and whose
+ * ids are valid: each landmark whose id is found (binary search) takes that row's position and outlier flag; ref pose takes the pose of the row whose
+ * id is ref_kf_id.  Absent ids keep their values.  NULL pointers or a cap < 1: MYSLAM_ERR_INVALID.
+ *
+ * myslam_tracker_set_image_batch — 1 + levels launches: for every stream with d_select[s] != 0 the stored previous left image becomes d_imgs[s] and
+ * its pyramid levels are rebuilt: the device form of set_frame's prev_image (DeepLCD blurs the key-frame's image in place and the tracker then
+ * tracks FROM the blurred pixels, src/deeplcd.cpp:46).  Frozen or not.  NULL pointers, step < cols or a short stride: MYSLAM_ERR_INVALID.
+ * (The selection lives on the device, so the host-side "this stream has an image" mark of set_frame / get_frame is not touched: a stream that was
+ * never given an image through set_frame still reports none to them.)
+ * ------------------------------------------------------------------------------------------ */
+#define MYSLAM_TRACKER_NO_TURN 1    /* d_report[s][0]: the stream was not eligible, nothing of it was touched */
+int myslam_tracker_set_ids(myslam_tracker* h, int stream, const int64_t* landmark_id, int n_landmarks, int64_t ref_kf_id, int64_t next_kf_id,
+                           int64_t next_mp_id);
+/* landmark_id sized landmark_cap by the caller; any pointer may be NULL */
+int myslam_tracker_get_ids(myslam_tracker* h, int stream, int64_t* landmark_id, int* n_landmarks, int64_t* ref_kf_id, int64_t* next_kf_id,
+                           int64_t* next_mp_id, int* valid);
+int myslam_tracker_keyframe_masks(myslam_tracker* h, uint8_t* d_masks, int step, size_t stride);
+int myslam_tracker_keyframe_batch(myslam_tracker* h, const uint8_t* d_right, int step, size_t stride, const myslam_keypoint* d_new_kps,
+                                  const int32_t* d_n_new, int kp_cap, double baseline, int64_t* d_new_kf_id, double* d_new_kf_pose, int64_t* d_feat_mp_id,
+                                  double* d_feat_mp_pos, float* d_feat_uv, int32_t* d_feat_tag, uint8_t* d_feat_flags, int32_t* d_n_feat,
+                                  int64_t* d_outlier_mp_id, int32_t* d_n_outlier_mp, float* d_right_xy, uint8_t* d_right_ok, int32_t* d_report);
+/* kernel launches one myslam_tracker_keyframe_batch enqueues */
+int myslam_tracker_keyframe_launches(const myslam_tracker* h);
+/* the last turn's problem of one stream (host pointers, cap entries each, synchronises): left pixels of the final table, LK's right points and
+ * status, the triangulation in the camera frame and its ok (0 where none was attempted); *n = 0 when the stream took no turn in that call */
+int myslam_tracker_debug_last_turn(myslam_tracker* h, int stream, float* left_xy, float* right_xy, uint8_t* right_ok, double* tri_xyz, uint8_t* tri_ok,
+                                   int* n);
+/* test seam (host call, synchronous): freezes a stream as a step would and records `why` = 1 key-frame rule, 2 LOST, 3 capacity — so that a
+ * hand-made table (set_frame, any coordinates and counts) can meet the masks and the turn without a step's LK in between */
+int myslam_tracker_debug_freeze(myslam_tracker* h, int stream, int why);
+int myslam_tracker_update_from_map_batch(myslam_tracker* h, const int64_t* d_kf_id, const double* d_kf_pose, const int32_t* d_n_kf, int kf_cap,
+                                         const int64_t* d_mp_id, const double* d_mp_pos, const uint8_t* d_mp_outlier, const int32_t* d_n_mp, int mp_cap);
+int myslam_tracker_set_image_batch(myslam_tracker* h, const uint8_t* d_imgs, int step, size_t stride, const uint8_t* d_select);
+
+/* ------------------------------------------------------------------------------------------
  * Lens undistortion — replaces Camera::UndistortImage (src/camera.cpp:36-48), which Frontend::GrabStereoImage runs on the left and the
  * right image before anything else when Camera.bNeedUndistortion is 1 (src/frontend.cpp:47-51): cv::undistort(src, dst, K, D) with
  * K = (fx, fy, cx, cy) widened from the camera's float members and D = (k1, k2, p1, p2) (read in src/system.cpp:118-138).
