@@ -1091,7 +1091,7 @@ __global__ __launch_bounds__(NT) void k_pose_only(PoseOnlyArgs a) {
     __shared__ double sT[12], sTb[12], sH[27], sx[6], s_part[NW][27];
     __shared__ double s_sc[4];          // [0] lambda [1] ni [2] ok
     const int f = blockIdx.x, t = threadIdx.x, wv = t >> 6, lane = t & 63;
-    const int n = a.counts ? a.counts[f] : a.n_fixed;
+    const int n = a.counts ? min(max(a.counts[f], 0), a.cap) : a.n_fixed;      // a count below 0 is 0, above cap is cap (as pnp_item_count, the LK tracker)
     const double* P3 = a.pts3d + (size_t)f * a.cap * 3;
     const double* Z2 = a.obs + (size_t)f * a.cap * 2;
     double* pose = a.poses + (size_t)f * 7;

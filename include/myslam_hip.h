@@ -660,7 +660,9 @@ int myslam_ba_set_option(int option, int value);
  * ------------------------------------------------------------------------------------------ */
 int myslam_pose_only_optimize(double* pose7, const double* pts3d, const double* obs, int n, double fx, double fy, double cx, double cy,
                               double chi2_th, int rounds, int iters, int pre_optimize, uint8_t* outlier, int* n_inliers);
-/* `batch` frames: d_poses batch x 7, d_pts3d batch x cap x 3, d_obs batch x cap x 2, d_counts batch, d_outlier batch x cap */
+/* `batch` frames: d_poses batch x 7, d_pts3d batch x cap x 3, d_obs batch x cap x 2, d_counts batch, d_outlier batch x cap.  A count below 0 is
+ * read as 0, one above cap as cap; slots from a frame's count on are neither read nor written; a frame of 0 matches reports 0 inliers and status OK
+ * and keeps its pose (the unit quaternion of the one it had), as myslam_pose_only_optimize does for n = 0. */
 int myslam_pose_only_optimize_batch(double* d_poses, const double* d_pts3d, const double* d_obs, const int32_t* d_counts, int batch, int cap,
                                     double fx, double fy, double cx, double cy, double chi2_th, int rounds, int iters, int pre_optimize,
                                     uint8_t* d_outlier, int32_t* d_n_inliers, int32_t* d_status, void* hip_stream);
