@@ -908,6 +908,28 @@ class Tracker:
         _check(lib().myslam_tracker_set_image_batch(self._h, C.c_void_p(d_imgs), int(step), C.c_size_t(stride), C.c_void_p(d_select)),
                "myslam_tracker_set_image_batch")
 
+    # ---- StereoInit on the device (myslam_tracker_init_*: the header states every rule) ----
+    INIT_RETRY = 2                               # MYSLAM_TRACKER_INIT_RETRY
+
+    def reset_stream(self, s, next_frame_id=0, next_kf_id=0, next_mp_id=0, kf_every=0):
+        """host call, synchronous: stream s back into the created (init-eligible) state, with the given id counters"""
+        _check(lib().myslam_tracker_reset_stream(self._h, int(s), int(next_frame_id), int(next_kf_id), int(next_mp_id), int(kf_every)),
+               "myslam_tracker_reset_stream")
+
+    def init_masks(self, d_masks, step, stride):
+        """device pointer, asynchronous: all 255 for every init-eligible stream, all 0 for the others (keyframe_masks' layout)"""
+        _check(lib().myslam_tracker_init_masks(self._h, C.c_void_p(d_masks), int(step), C.c_size_t(stride)), "myslam_tracker_init_masks")
+
+    def init_launches(self):
+        return lib().myslam_tracker_init_launches(self._h)
+
+    def init_batch(self, d_left, d_right, step, stride, d_new_kps, d_n_new, kp_cap, baseline, init_good, out):
+        """device pointers, asynchronous: StereoInit of every init-eligible stream.  out: keyframe_batch's dict of device pointers"""
+        o = [C.c_void_p(out[k]) for k in ("new_kf_id", "new_kf_pose", "feat_mp_id", "feat_mp_pos", "feat_uv", "feat_tag", "feat_flags", "n_feat",
+                                          "outlier_mp_id", "n_outlier_mp", "right_xy", "right_ok", "report")]
+        _check(lib().myslam_tracker_init_batch(self._h, C.c_void_p(d_left), C.c_void_p(d_right), int(step), C.c_size_t(stride), C.c_void_p(d_new_kps),
+                                               C.c_void_p(d_n_new), int(kp_cap), C.c_double(baseline), int(init_good), *o), "myslam_tracker_init_batch")
+
 
 # ---------------------------------------------------------------------------------- lens undistortion
 class Undistorter:

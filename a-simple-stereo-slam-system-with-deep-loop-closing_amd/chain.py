@@ -771,7 +771,10 @@ class StreamBank:
     frontend.cpp:86-122) runs for ALL streams in one asynchronous api.Tracker.step_batch with the tracker state on the device, ONE download
     brings the S result records back, and only a stream whose record says needs_host (key-frame by the reference's rule or kf_every, or
     LOST) takes the existing Chain methods (detect_features ... insert_keyframe, back end, loop closer) between get_frame and set_frame.
-    Stereo initialisation stays on Chain.grab().  Device buffers are torch tensors (plumbing only).  Chain itself is the one-camera form."""
+    Stereo initialisation stays on Chain.grab() unless self.device_init is set: then every INITING stream starts on the device (device_init_turn).
+    Device buffers are torch tensors (plumbing only).  Chain itself is the one-camera form."""
+
+    device_init = False                                               # advance(): INITING streams take StereoInit through device_init_turn
 
     def __init__(self, chains, api, cap=1024, landmark_cap=4096, tracker=None):
         import torch
@@ -907,6 +910,81 @@ class StreamBank:
                 c.rel_motion = self.trk.get_frame(s)["rel_motion"]
                 self.hand_off(s)
 
+    def enqueue_init(self):
+        """masks -> detect_batch on the INIT extractor -> init for every init-eligible stream of the bank, asynchronous: three calls on the tracker's
+        stream, from the stereo pairs of the last upload()"""
+        buf = self._turn_buffers()
+        if getattr(self, "d_kps_init", None) is None:
+            self.orb_init = self.chains[0].be.det_init    # Frontend::_mpORBextractorInit (nInitFeatures): every stream of a bank shares its configuration
+            self.kp_cap_init = int(self.orb_init.max_keypoints(self.rows, self.cols))
+            self.d_kps_init = self.torch.zeros((len(self.chains), self.kp_cap_init, self.api.KP_DTYPE.itemsize), dtype=self.torch.uint8, device="cuda")
+        img = self.rows * self.cols
+        self.d_right.copy_(self.torch.from_numpy(np.stack([np.ascontiguousarray(R, np.uint8) for _, R in self.images])))
+        self.trk.init_masks(self.d_mask.data_ptr(), self.cols, img)
+        self.orb_init.detect_batch(self.d_img.data_ptr(), len(self.chains), self.rows, self.cols, self.cols, img, self.d_kps_init.data_ptr(),
+                                   self.d_nkp.data_ptr(), self.d_kst.data_ptr(), self.kp_cap_init, d_masks=self.d_mask.data_ptr())
+        self.trk.init_batch(self.d_img.data_ptr(), self.d_right.data_ptr(), self.cols, img, self.d_kps_init.data_ptr(), self.d_nkp.data_ptr(), self.kp_cap_init,
+                            self.chains[0].K["baseline"], self.chains[0].n_init_good, {k: v.data_ptr() for k, v in buf.items()})
+
+    def device_init_turn(self, streams, t=None, ts=None, resync=True):
+        """Frontend::StereoInit of the INITING streams `streams` ON THE DEVICE (enqueue_init): DetectFeatures, FindFeaturesInRight, BuildInitMap and
+        InsertKeyFrame's INITING branch never leave it, ONE download brings the first key-frames back and the chain's existing host map code takes
+        them.  A stream that was not armed yet is put into the created state with its chain's id counters and kf_every first (reset_stream: one
+        small host call per start, none per retry).  A retry item (too few right matches) spends a frame id and appends the identity pose, as
+        Chain.grab() does.  resync: as device_turn."""
+        t = self.t if t is None else t
+        if getattr(self, "armed", None) is None:
+            self.armed = [False] * len(self.chains)
+        if any(c.n_init_good != self.chains[0].n_init_good for c in self.chains):
+            raise ValueError("the streams of one bank share numFeatures.initGood")
+        for s in streams:
+            c = self.chains[s]
+            if not self.armed[s]:
+                self.trk.reset_stream(s, c.next_frame_id, c.next_kf_id, c.next_mp_id, max(int(c.kf_every), 0))
+                self.armed[s] = True
+        self.enqueue_init()
+        out = {k: v.cpu().numpy() for k, v in self.turn_buf.items()}                  # the one download (synchronises)
+        for s in streams:
+            c, rep = self.chains[s], out["report"][s]
+            if rep[0] not in (0, self.trk.INIT_RETRY):
+                raise RuntimeError(f"stream {s}: StereoInit on the device reports {int(rep[0])}")
+            L, R = self.images[s]
+            c.cur = Frame(int(rep[1]), float(ts if ts is not None else (c.ts[t] if c.ts is not None else t)), L, R)
+            c.next_frame_id = int(rep[1]) + 1
+            if rep[0] == self.trk.INIT_RETRY:                                         # StereoInit returned false: the frame is dropped
+                c.poses.append(IDENT.copy())
+                c.last = c.cur
+                continue
+            n, mps = int(out["n_feat"][s]), []
+            for i in range(n):
+                f = Feature(out["feat_uv"][s, i, 0], out["feat_uv"][s, i, 1])
+                mid = int(out["feat_mp_id"][s, i])
+                if mid >= 0:                                                          # a map point BuildInitMap created (Map::InsertMapPoint)
+                    c.all_mps[mid] = f.mp = MapPoint(mid, out["feat_mp_pos"][s, i])
+                    c.next_mp_id = max(c.next_mp_id, mid + 1)
+                    mps.append(f.mp)
+                c.cur.feats.append(f)
+            c.cur.right = [(x, y) if ok else None for (x, y), ok in zip(out["right_xy"][s, :n], out["right_ok"][s, :n])]
+            kf = KeyFrame(int(out["new_kf_id"][s]), c.cur)                            # insert_keyframe(), INITING branch, with the device's id and pose
+            c.next_kf_id = kf.id + 1
+            for f in kf.feats:
+                f.kf = kf
+                if f.live() is not None:
+                    f.mp.obs.append(f)
+            kf.pose = out["new_kf_pose"][s].copy()
+            c.ref_kf = kf
+            c.cur.rel = np.eye(4)
+            c.kf_frames.append(c.cur.id)
+            c.backend_new_keyframe(kf)
+            c.status = TRACKING_GOOD
+            c.poses.append(p7_of(mm(c.cur.rel, T_of(c.ref_kf.pose))))
+            c.last = c.cur
+            self.slots[s] = mps
+            self.on_device[s] = True
+            self.armed[s] = False                                                     # a later restart arms the stream again
+            if resync:
+                self.hand_off(s)
+
     def host_turn(self, s, rec, t, ts=None):
         """a frozen stream: the device's frame becomes the chain's current frame, the chain does its key-frame work, the result goes back"""
         c = self.chains[s]
@@ -948,7 +1026,9 @@ class StreamBank:
 
     def advance(self, t):
         """one frame of every stream; returns the streams that are still tracking.  self.device_turns (default False): frozen streams take their
-        key-frame turn through device_turn instead of host_turn"""
+        key-frame turn through device_turn instead of host_turn.  self.device_init (default False): INITING streams start through
+        device_init_turn (one masks -> detect_batch -> init_batch -> download for all of them) instead of Chain.grab() + hand_off, handed over
+        again afterwards unless self.resync_init is False"""
         self.upload(t)
         stepped = [s for s, c in enumerate(self.chains) if self.on_device[s]]
         logged = {s: self.trk.get_frame(s) for s in stepped if self.chains[s].keep_log}       # (a logging chain pays two more downloads per frame)
@@ -967,10 +1047,13 @@ class StreamBank:
                 else:
                     c.status = int(res[s]["status"]); c.next_frame_id = int(res[s]["frame_id"]) + 1
                     c.poses.append(res[s]["pose7"].copy())
-            elif c.status == INITING:                   # Frontend::StereoInit on the one-camera path
+            elif c.status == INITING and not self.device_init:           # Frontend::StereoInit on the one-camera path
                 c.grab(t)
                 if c.status != INITING:
                     self.hand_off(s)
+        inits = [s for s, c in enumerate(self.chains) if s not in stepped and c.status == INITING] if self.device_init else []
+        if inits:
+            self.device_init_turn(inits, t, resync=getattr(self, "resync_init", True))
         if turns:
             self.device_turn(turns, res, t, resync=getattr(self, "resync_turns", True))
         return [s for s, c in enumerate(self.chains) if c.status in (INITING, TRACKING_GOOD, TRACKING_BAD)]

@@ -549,6 +549,148 @@ __global__ __launch_bounds__(TRK_NT) void k_kf_set_image(TrkArgs a, const uint8_
         for (int x = t; x < a.cols; x += TRK_NT) dst[(size_t)r * a.cols + x] = src[(size_t)r * step + x];
 }
 
+// =====================================================================================================================================
+// StereoInit (include/myslam_hip.h, myslam_tracker_init_*): Frontend::StereoInit (:282-295) with DetectFeatures' mask over an empty table
+// (:305-309), FindFeaturesInRight (:335-379), BuildInitMap (:385-417) and InsertKeyFrame's INITING branch (:427-428, :441-443) for every
+// INIT-ELIGIBLE stream.  Its own head and tail: the turn's kernels above keep their code, resources and outputs.
+__device__ __forceinline__ bool init_eligible(const TrkState& st) {
+    return st.frozen != 0 && st.status == TRK_INITING && st.why == TRK_WHY_NONE && st.overflow == 0;
+}
+
+// ---- masks: 255 everywhere for an init-eligible stream (no feature draws a rectangle), 0 otherwise; no LDS ----
+__global__ __launch_bounds__(TRK_NT) void k_init_masks(TrkArgs a, uint8_t* masks, int step, size_t stride) {
+    const int s = blockIdx.y, t = threadIdx.x;
+    const int r0 = blockIdx.x * MASK_ROWS, r1 = min(r0 + MASK_ROWS, a.rows), nb = (r1 - r0) * a.cols;
+    const uint8_t v = init_eligible(a.st[s]) ? 255 : 0;
+    uint8_t* dst = masks + (size_t)s * stride;
+    for (int k = t; k < nb; k += TRK_NT) dst[(size_t)(r0 + k / a.cols) * step + k % a.cols] = v;
+}
+
+// ---- init head: blockIdx.x == 0 decides eligibility and writes the detected key-points as left pixels and right start points (rules a + b);
+//      the other blocks copy the left image into the stream's buffer `slot` and the right image into buffer 1 - slot ----
+__global__ __launch_bounds__(TRK_NT) void k_init_head(TrkArgs a, KfArgs k, const uint8_t* left, int32_t* selLeft) {
+    const int s = blockIdx.y, t = threadIdx.x;
+    const TrkState& st = a.st[s];
+    const bool el = init_eligible(st);
+    const int m = min(max(k.nNew[s], 0), k.kpCap);
+    const bool go = el && m <= a.cap;
+    if (blockIdx.x > 0) {
+        if (!go) return;
+        const int r0 = (blockIdx.x - 1) * TRK_COPY_ROWS, r1 = min(r0 + TRK_COPY_ROWS, a.rows);
+        const uint8_t* srcL = left + (size_t)s * k.stride;
+        const uint8_t* srcR = k.right + (size_t)s * k.stride;
+        uint8_t* dstL = a.img + (size_t)st.slot * a.imgSel + (size_t)s * a.imgBytes;
+        uint8_t* dstR = a.img + (size_t)(1 - st.slot) * a.imgSel + (size_t)s * a.imgBytes;
+        for (int r = r0; r < r1; r++)
+            for (int x = t; x < a.cols; x += TRK_NT) {
+                dstL[(size_t)r * a.cols + x] = srcL[(size_t)r * k.step + x];
+                dstR[(size_t)r * a.cols + x] = srcR[(size_t)r * k.step + x];
+            }
+        return;
+    }
+    if (t == 0) {
+        selLeft[s] = go ? st.slot : -1; a.kfSel[s] = go ? 1 - st.slot : -1;       // LK tracks from buffer 1 - kfSel into buffer kfSel
+        a.kfCounts[s] = go ? m : 0; a.kfCode[s] = go ? KF_GO : (el ? KF_CAPACITY : KF_NO_TURN);
+    }
+    if (!go) return;
+    const size_t fb = (size_t)s * a.cap;
+    const myslam_keypoint* kps = k.newKps + (size_t)s * k.kpCap;
+    for (int i = t; i < m; i += TRK_NT) {                    // every start point is the feature's own pixel (:350-352)
+        const float x = kps[i].x, y = kps[i].y;
+        a.kfP0[(fb + i) * 2] = x; a.kfP0[(fb + i) * 2 + 1] = y;
+        a.kfNxt[(fb + i) * 2] = x; a.kfNxt[(fb + i) * 2 + 1] = y;
+    }
+}
+
+// ---- init tail: rules c - g, one block per stream.  Everything is built in scratch and in the output arrays; the state is written last ----
+__global__ __launch_bounds__(TRK_NT) void k_init_tail(TrkArgs a, KfArgs k, int initGood) {
+    __shared__ int s_w[TRK_NT / 64];
+    const int s = blockIdx.x, t = threadIdx.x;
+    TrkState& st = a.st[s];
+    int32_t* rep = k.report + (size_t)s * 8;
+    const int code = a.kfCode[s];
+    const int m = min(max(k.nNew[s], 0), k.kpCap);
+    auto refuse = [&](int status, int frameId, int nRight) { // (uniform) no key-frame
+        if (t == 0) {
+            k.newKfId[s] = -1; k.nFeat[s] = 0; k.nOutlMp[s] = 0;
+            rep[0] = status; rep[1] = frameId; rep[2] = m; rep[3] = nRight; rep[4] = 0; rep[5] = st.n_feat; rep[6] = st.n_lm; rep[7] = 0;
+        }
+    };
+    if (code == KF_NO_TURN) { refuse(MYSLAM_TRACKER_NO_TURN, st.next_frame_id - 1, 0); return; }
+    const int frameId = st.next_frame_id;                    // the Frame that GrabStereoImage constructed
+    if (code != KF_GO) { refuse(MYSLAM_ERR_CAPACITY, frameId, 0); return; }
+    const size_t fb = (size_t)s * a.cap, lb = (size_t)s * a.lmCap;
+    int64_t* ids = a.ids + (size_t)s * 3;
+    const int64_t nextMp = ids[2];
+    // rule d (triangulation in feature order, slot = rank among the successes), 256 features at a time
+    int nTri = 0, nRight = 0;
+    for (int base = 0; base < m; base += TRK_NT) {
+        const int i = base + t;
+        bool rok = false, tri = false;
+        double X[3] = {0, 0, 0};
+        if (i < m) {
+            rok = a.kfSt[fb + i] != 0;
+            if (rok) {                                       // mvpFeaturesRight[i] != nullptr (:394)
+                const double ul = a.kfP0[(fb + i) * 2], vl = a.kfP0[(fb + i) * 2 + 1], ur = a.kfNxt[(fb + i) * 2], vr = a.kfNxt[(fb + i) * 2 + 1];
+                const double P[2][12] = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0},
+                                         {1, 0, 0, -k.baseline, 0, 1, 0, 0, 0, 0, 1, 0}};      // as k_kf_tail
+                const double pt[2][2] = {{(ul - a.cx) / a.fx, (vl - a.cy) / a.fy}, {(ur - a.cx) / a.fx, (vr - a.cy) / a.fy}};
+                double ratio;
+                tri_solve(P, pt, X, ratio);
+                tri = ratio < 1e-2 && X[2] > 0;
+            }
+            a.kfXyz[(fb + i) * 3] = X[0]; a.kfXyz[(fb + i) * 3 + 1] = X[1]; a.kfXyz[(fb + i) * 3 + 2] = X[2];
+            a.kfTok[fb + i] = tri ? 1 : 0;
+        }
+        int tt, tr;
+        const int rt = block_rank(tri, s_w, tt);
+        (void)block_rank(rok, s_w, tr);
+        if (i < m) {
+            const int slot = tri ? nTri + rt : -1;
+            a.kfSlot[fb + i] = slot;
+            const int64_t id = tri ? nextMp + slot : -1;
+            if (!tri) { X[0] = 0; X[1] = 0; X[2] = 0; }
+            if (tri && slot < a.lmCap) {                     // (beyond lmCap the init is refused below); the key-frame's pose is I: pos = X itself
+                a.kfId[lb + slot] = id;
+                for (int r = 0; r < 3; r++) a.kfPos[(lb + slot) * 3 + r] = X[r];
+            }
+            k.featMpId[fb + i] = id;
+            for (int r = 0; r < 3; r++) k.featMpPos[(fb + i) * 3 + r] = X[r];
+            k.featUv[(fb + i) * 2] = a.kfP0[(fb + i) * 2]; k.featUv[(fb + i) * 2 + 1] = a.kfP0[(fb + i) * 2 + 1];
+            k.featTag[fb + i] = i; k.featFlags[fb + i] = 0;
+            k.rightXy[(fb + i) * 2] = a.kfNxt[(fb + i) * 2]; k.rightXy[(fb + i) * 2 + 1] = a.kfNxt[(fb + i) * 2 + 1];
+            k.rightOk[fb + i] = rok ? 1 : 0;
+        }
+        nTri += tt; nRight += tr;
+    }
+    if (nRight < initGood) {                                 // uniform.  StereoInit returns false (:285-287): only the Frame's id was spent
+        refuse(MYSLAM_TRACKER_INIT_RETRY, frameId, nRight);
+        if (t == 0) st.next_frame_id = frameId + 1;
+        return;
+    }
+    if (nTri > a.lmCap) { refuse(MYSLAM_ERR_CAPACITY, frameId, nRight); return; }      // uniform
+    __syncthreads();                                         // kfSlot, kfPos, kfId are complete
+    // ---- commit ----
+    for (int i = t; i < m; i += TRK_NT) {
+        a.lm[fb + i] = a.kfSlot[fb + i];
+        a.xy[(fb + i) * 2] = a.kfP0[(fb + i) * 2]; a.xy[(fb + i) * 2 + 1] = a.kfP0[(fb + i) * 2 + 1];
+    }
+    for (int j = t; j < nTri; j += TRK_NT) {
+        a.lmId[lb + j] = a.kfId[lb + j]; a.lmOutl[lb + j] = 0;
+        for (int r = 0; r < 3; r++) a.lmPos[(lb + j) * 3 + r] = a.kfPos[(lb + j) * 3 + r];
+    }
+    if (t != 0) return;
+    const int64_t kfId = ids[1];
+    for (int c = 0; c < 7; c++) { const double p = c == 3 ? 1.0 : 0.0; st.ref_pose[c] = p; k.newKfPose[(size_t)s * 7 + c] = p; }
+    for (int c = 0; c < 16; c++) { const double e = (c % 5 == 0) ? 1.0 : 0.0; st.last_rel[c] = e; st.rel_motion[c] = e; }
+    ids[0] = kfId; ids[1] = kfId + 1; ids[2] = nextMp + nTri;
+    st.ref_frame_id = frameId; st.next_frame_id = frameId + 1;
+    st.n_feat = m; st.n_lm = nTri; st.n_outl = 0;
+    st.status = TRK_GOOD; st.frozen = 0; st.why = TRK_WHY_NONE; st.idsValid = 1;
+    k.newKfId[s] = kfId; k.nFeat[s] = m; k.nOutlMp[s] = 0;
+    rep[0] = MYSLAM_OK; rep[1] = frameId; rep[2] = m; rep[3] = nRight; rep[4] = nTri; rep[5] = m; rep[6] = nTri; rep[7] = 0;
+}
+
 }  // namespace myslam_hip
 
 using namespace myslam_hip;
@@ -560,7 +702,8 @@ struct myslam_tracker {
     size_t pyrBytes = 0;
     TrkArgs a{};
     uint8_t* d_pyr = nullptr;
-    BufSet mem;                            // owns every block that `a` and d_pyr name
+    int32_t* d_selLeft = nullptr;          // StereoInit: the buffer the left image's levels go to (a.kfSel names the right image's)
+    BufSet mem;                            // owns every block that `a`, d_pyr and d_selLeft name
     std::vector<char> hasImage;
 };
 
@@ -578,7 +721,7 @@ static int trk_alloc_all(myslam_tracker* h) {
         (rc = own(a.lmId, L)) || (rc = own(a.ids, S * 3)) || (rc = own(a.kfSel, S)) || (rc = own(a.kfCounts, S)) || (rc = own(a.kfCode, S)) ||
         (rc = own(a.kfP0, F * 2)) || (rc = own(a.kfNxt, F * 2)) || (rc = own(a.kfSt, F)) || (rc = own(a.kfXyz, F * 3)) || (rc = own(a.kfTok, F)) ||
         (rc = own(a.kfSlot, F)) || (rc = own(a.kfFirst, L)) || (rc = own(a.kfMap, L)) || (rc = own(a.kfPos, L * 3)) || (rc = own(a.kfOutl, L)) ||
-        (rc = own(a.kfId, L)))
+        (rc = own(a.kfId, L)) || (rc = own(h->d_selLeft, S)))
         return rc;
     std::vector<TrkState> init(S);
     memset(init.data(), 0, S * sizeof(TrkState));
@@ -830,6 +973,63 @@ int myslam_tracker_keyframe_batch(myslam_tracker* h, const uint8_t* d_right, int
     if ((rc = lk_bank_pyramid(h->lk, d_right, step, stride, h->d_pyr, S, a.kfSel, pyrSel))) return rc;
     if ((rc = lk_bank_track(h->lk, a.img, h->cols, a.imgBytes, h->d_pyr, S, a.kfSel, a.imgSel, pyrSel, a.kfP0, a.kfNxt, a.kfCounts, h->cap, a.kfSt))) return rc;
     hipLaunchKernelGGL(k_kf_tail, dim3(S), dim3(TRK_NT), 0, st, a, k);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    return MYSLAM_OK;
+}
+
+// ---- StereoInit ----
+int myslam_tracker_reset_stream(myslam_tracker* h, int s, int next_frame_id, int64_t next_kf_id, int64_t next_mp_id, int kf_every) {
+    if (!h || s < 0 || s >= h->S || next_frame_id < 0 || next_kf_id < 0 || next_mp_id < 0 || kf_every < 0) return MYSLAM_ERR_INVALID;
+    hipStream_t st = h->stream;
+    TrkArgs& a = h->a;
+    TrkState hs;
+    int rc = copy_sync(&hs, a.st + s, sizeof(TrkState), hipMemcpyDeviceToHost, st);
+    if (rc) return rc;
+    const int slot = hs.slot;                // the two image buffers keep their roles
+    memset(&hs, 0, sizeof(hs));
+    hs.ref_pose[3] = 1.0;
+    for (int c = 0; c < 16; c += 5) hs.last_rel[c] = hs.rel_motion[c] = 1.0;
+    hs.next_frame_id = next_frame_id; hs.status = TRK_INITING; hs.frozen = 1; hs.kf_every = kf_every; hs.slot = slot;
+    const int64_t ids[3] = {0, next_kf_id, next_mp_id};
+    MYSLAM_HIP_CHECK(hipMemcpyAsync(a.ids + (size_t)s * 3, ids, sizeof(ids), hipMemcpyHostToDevice, st));
+    MYSLAM_HIP_CHECK(hipMemcpyAsync(a.st + s, &hs, sizeof(TrkState), hipMemcpyHostToDevice, st));
+    MYSLAM_HIP_CHECK(hipStreamSynchronize(st));
+    return MYSLAM_OK;
+}
+
+int myslam_tracker_init_masks(myslam_tracker* h, uint8_t* d_masks, int step, size_t stride) {
+    if (!h || !d_masks || step < h->cols || stride < (size_t)(h->rows - 1) * step + h->cols) return MYSLAM_ERR_INVALID;
+    hipLaunchKernelGGL(k_init_masks, dim3((h->rows + MASK_ROWS - 1) / MASK_ROWS, h->S), dim3(TRK_NT), 0, h->stream, h->a, d_masks, step, stride);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    return MYSLAM_OK;
+}
+
+int myslam_tracker_init_launches(const myslam_tracker* h) {
+    return h ? 3 + 2 * h->levels : MYSLAM_ERR_INVALID;
+}
+
+int myslam_tracker_init_batch(myslam_tracker* h, const uint8_t* d_left, const uint8_t* d_right, int step, size_t stride, const myslam_keypoint* d_new_kps,
+                              const int32_t* d_n_new, int kp_cap, double baseline, int init_good, int64_t* d_new_kf_id, double* d_new_kf_pose,
+                              int64_t* d_feat_mp_id, double* d_feat_mp_pos, float* d_feat_uv, int32_t* d_feat_tag, uint8_t* d_feat_flags, int32_t* d_n_feat,
+                              int64_t* d_outlier_mp_id, int32_t* d_n_outlier_mp, float* d_right_xy, uint8_t* d_right_ok, int32_t* d_report) {
+    if (!h || !d_left || !d_right || !d_new_kps || !d_n_new || !d_new_kf_id || !d_new_kf_pose || !d_feat_mp_id || !d_feat_mp_pos || !d_feat_uv ||
+        !d_feat_tag || !d_feat_flags || !d_n_feat || !d_outlier_mp_id || !d_n_outlier_mp || !d_right_xy || !d_right_ok || !d_report)
+        return MYSLAM_ERR_INVALID;
+    if (step < h->cols || stride < (size_t)(h->rows - 1) * step + h->cols || kp_cap < 1) return MYSLAM_ERR_INVALID;
+    const TrkArgs& a = h->a;
+    const KfArgs k{d_right, step, stride, d_new_kps, d_n_new, kp_cap, baseline, d_new_kf_id, d_new_kf_pose, d_feat_mp_id, d_feat_mp_pos, d_feat_uv, d_feat_tag,
+                   d_feat_flags, d_n_feat, d_outlier_mp_id, d_n_outlier_mp, d_right_xy, d_right_ok, d_report};
+    hipStream_t st = h->stream;
+    const int S = h->S;
+    const size_t pyrSel = (size_t)S * h->pyrBytes;
+    hipLaunchKernelGGL(k_init_head, dim3(1 + (h->rows + TRK_COPY_ROWS - 1) / TRK_COPY_ROWS, S), dim3(TRK_NT), 0, st, a, k, d_left, h->d_selLeft);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    int rc;
+    // the left image's levels into buffer `slot`, the right image's into buffer 1 - slot, then LK from the one into the other (:358-361)
+    if ((rc = lk_bank_pyramid(h->lk, d_left, step, stride, h->d_pyr, S, h->d_selLeft, pyrSel))) return rc;
+    if ((rc = lk_bank_pyramid(h->lk, d_right, step, stride, h->d_pyr, S, a.kfSel, pyrSel))) return rc;
+    if ((rc = lk_bank_track(h->lk, a.img, h->cols, a.imgBytes, h->d_pyr, S, a.kfSel, a.imgSel, pyrSel, a.kfP0, a.kfNxt, a.kfCounts, h->cap, a.kfSt))) return rc;
+    hipLaunchKernelGGL(k_init_tail, dim3(S), dim3(TRK_NT), 0, st, a, k, init_good);
     MYSLAM_HIP_CHECK(hipGetLastError());
     return MYSLAM_OK;
 }

@@ -449,6 +449,23 @@ public:
     void SetImageBatch(const uint8_t* d_imgs, int step, size_t stride, const uint8_t* d_select) {
         check(myslam_tracker_set_image_batch(h_, d_imgs, step, stride, d_select), "myslam_tracker_set_image_batch");
     }
+    // ---- StereoInit on the device (include/myslam_hip.h, "StereoInit on the device"): masks -> detect_batch on the INIT extractor -> InitBatch ----
+    int initLaunches() const { return myslam_tracker_init_launches(h_); }
+    // back into the created (init-eligible) state with the given id counters: a restart after LOST, or streams that share an id space
+    void ResetStream(int stream, int nextFrameId = 0, int64_t nextKfId = 0, int64_t nextMpId = 0, int kfEvery = 0) {
+        check(myslam_tracker_reset_stream(h_, stream, nextFrameId, nextKfId, nextMpId, kfEvery), "myslam_tracker_reset_stream");
+    }
+    // all 255 for every init-eligible stream, all 0 for the others (KeyframeMasks' layout)
+    void InitMasks(uint8_t* d_masks, int step, size_t stride) {
+        check(myslam_tracker_init_masks(h_, d_masks, step, stride), "myslam_tracker_init_masks");
+    }
+    // d_left / d_right: the streams' first stereo pairs; the report's status is 0, MYSLAM_TRACKER_INIT_RETRY, MYSLAM_TRACKER_NO_TURN or an error
+    void InitBatch(const uint8_t* d_left, const uint8_t* d_right, int step, size_t stride, const myslam_keypoint* d_newKps, const int32_t* d_nNew, int kpCap,
+                   double baseline, int initGood, const TurnOutputs& o) {
+        check(myslam_tracker_init_batch(h_, d_left, d_right, step, stride, d_newKps, d_nNew, kpCap, baseline, initGood, o.newKfId, o.newKfPose, o.featMpId,
+                                        o.featMpPos, o.featUv, o.featTag, o.featFlags, o.nFeat, o.outlierMpId, o.nOutlierMp, o.rightXy, o.rightOk, o.report),
+              "myslam_tracker_init_batch");
+    }
 };
 
 // Camera::UndistortImage (include/myslam/camera.h, src/camera.cpp:36-48): cv::undistort(src, dst, K, distCoef) for one camera at one image

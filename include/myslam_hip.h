@@ -865,6 +865,69 @@ int myslam_tracker_update_from_map_batch(myslam_tracker* h, const int64_t* d_kf_
 int myslam_tracker_set_image_batch(myslam_tracker* h, const uint8_t* d_imgs, int step, size_t stride, const uint8_t* d_select);
 
 /* ------------------------------------------------------------------------------------------
+ * StereoInit on the device — how a stream STARTS: Frontend::StereoInit (src/frontend.cpp:282-295) with DetectFeatures over an empty feature
+ * table (:305-309, :312-313 the init extractor, :319-323), FindFeaturesInRight (:335-379; every start point is the feature's own pixel,
+ * :350-352, :358-361), BuildInitMap (:385-417) and InsertKeyFrame's INITING branch (:427-428, :441-443), for every init-eligible stream of
+ * the bank at once: masks -> detect_batch (the caller's INIT extractor, same stream) -> init -> first step.
+ *
+ * A stream is INIT-ELIGIBLE when it is frozen, its status is INITING (0), no step recorded why it froze and set_frame left no overflow: a
+ * stream as myslam_tracker_create leaves it (every counter 0, kf_every 0: the reference's id factories at program start) or as
+ * myslam_tracker_reset_stream leaves it.  No stream is eligible for an init and for a turn at once.
+ *
+ * myslam_tracker_reset_stream — host call, synchronous as set_frame / set_ids: puts the stream back into the created state (no features, no
+ * landmarks, empty outlier list, last.rel = rel_motion = I, ref pose = (0, 0, 0, 1, 0, 0, 0), ref frame id 0, frozen, nothing recorded, no
+ * overflow, ids not valid, ref_kf_id 0) with the given counters: a restart after LOST, or streams that share an id space.  A negative value:
+ * MYSLAM_ERR_INVALID.  The stream's image buffers keep their roles and the host-side "this stream has an image" mark is left alone.
+ *
+ * myslam_tracker_init_masks — 1 launch on the handle's stream, asynchronous, the layout of myslam_tracker_keyframe_masks: mask s is all 255 for
+ * an init-eligible stream (no feature draws a rectangle) and all 0 otherwise.  NULL, step < cols or a stride that does not hold the image:
+ * MYSLAM_ERR_INVALID.  No LDS, so no limit on cols.
+ *
+ * myslam_tracker_init_batch — device pointers, asynchronous on the handle's stream, never synchronises, allocates nothing (its scratch is the
+ * turn's plus one selector array, the handle's from create on), recordable between myslam_graph_begin / _end; myslam_tracker_init_launches =
+ * 3 + 2 x (pyramid levels above 0) dependent launches: head, the left image's levels, the right image's levels, LK, tail.  d_left / d_right share
+ * step and stride; d_new_kps, d_n_new, kp_cap, baseline and the thirteen outputs are those of myslam_tracker_keyframe_batch, same layout.
+ * For an init-eligible stream, everything is decided before a byte of its state is written:
+ *   a. m = clamp(d_n_new[s], 0, kp_cap) features = the detected key-points in order, landmark -1 (:319-323);
+ *   b. the left image goes into the stream's image buffer `slot` (where a step looks for the previous image) and the right image into the other
+ *      one, each with its pyramid levels; LK tracks left -> right from every feature's own pixel with the arithmetic of myslam_lk_track;
+ *      nRight = the number of set statuses;
+ *   c. nRight < init_good (:285-287): MYSLAM_TRACKER_INIT_RETRY.  next frame id += 1 (the Frame was constructed) and nothing else of the
+ *      state changes: the stream stays init-eligible.  d_new_kf_id = -1, d_n_feat = 0, d_n_outlier_mp = 0;
+ *   d. otherwise BuildInitMap: every feature with right status set, in feature order, is triangulated with match_tri's solve (the P and point
+ *      expressions of the turn's rule d: myslam_triangulate_stereo's bits); where sigma3 / sigma2 < 1e-2 && z > 0 a map point is created:
+ *      id = next_mp_id + its rank among the successes, pos = the solve's X itself (the key-frame's pose is the identity and the hosts do not
+ *      multiply by it);
+ *   e. landmark table: a success's slot = its rank, outlier flags 0; every other feature keeps landmark -1; all m features stay in the table;
+ *   f. InsertKeyFrame, INITING branch: kf_id = next_kf_id++, pose = (0, 0, 0, 1, 0, 0, 0) = ref pose, ref_kf_id = kf_id, ref frame id = next
+ *      frame id, then next frame id += 1; last.rel = rel_motion = I; status = TRACKING_GOOD (:291), frozen = 0, nothing recorded, the outlier
+ *      list empty, next_mp_id += successes, ids valid.  `slot` is unchanged: the left image is the stream's previous image for the next step.
+ *      Zero successes still insert the key-frame (BuildInitMap returns true);
+ *   g. outputs as the turn's rule g with d_n_outlier_mp = 0; d_report[s] = (status, frame id, m, nRight, successes, m, successes, 0).  The
+ *      turn's scratch is filled, so myslam_tracker_debug_last_turn reads an init like a turn.
+ * Report of an item without a key-frame: (status, frame id, m, nRight or 0, 0, the state's feature count, its landmark count, 0), frame id =
+ * the id the constructed Frame took (retry, capacity) or the stream's last frame (not eligible).
+ * Not eligible: MYSLAM_TRACKER_NO_TURN — state, stored images and pyramids keep every byte; a turn-eligible stream of the same bank is not
+ * touched by this call, nor an init-eligible one by myslam_tracker_keyframe_batch.  MYSLAM_ERR_CAPACITY when m > cap or successes >
+ * landmark_cap: the state keeps every byte, frame id included; only the two image buffers may have been written.
+ * Call level, nothing enqueued: NULL pointers, step < cols, a stride that does not hold the image or kp_cap < 1 -> MYSLAM_ERR_INVALID;
+ * init_good may be any int.
+ * The outputs feed myslam_backend_insert_keyframe_batch on an EMPTY table: the first id has nothing to be above, so the row is appended and
+ * every success becomes a map-point row (take retry / no-turn items out first, see above).
+ * As after myslam_tracker_set_image_batch, set_frame(..., prev_image = NULL) still reports "no image" after a device init: the images arrived
+ * on the device and the host-side mark was not touched.
+ * ------------------------------------------------------------------------------------------ */
+#define MYSLAM_TRACKER_INIT_RETRY 2 /* d_report[s][0]: fewer than init_good right matches, only the frame id advanced */
+int myslam_tracker_reset_stream(myslam_tracker* h, int stream, int next_frame_id, int64_t next_kf_id, int64_t next_mp_id, int kf_every);
+int myslam_tracker_init_masks(myslam_tracker* h, uint8_t* d_masks, int step, size_t stride);
+int myslam_tracker_init_batch(myslam_tracker* h, const uint8_t* d_left, const uint8_t* d_right, int step, size_t stride, const myslam_keypoint* d_new_kps,
+                              const int32_t* d_n_new, int kp_cap, double baseline, int init_good, int64_t* d_new_kf_id, double* d_new_kf_pose,
+                              int64_t* d_feat_mp_id, double* d_feat_mp_pos, float* d_feat_uv, int32_t* d_feat_tag, uint8_t* d_feat_flags, int32_t* d_n_feat,
+                              int64_t* d_outlier_mp_id, int32_t* d_n_outlier_mp, float* d_right_xy, uint8_t* d_right_ok, int32_t* d_report);
+/* kernel launches one myslam_tracker_init_batch enqueues */
+int myslam_tracker_init_launches(const myslam_tracker* h);
+
+/* ------------------------------------------------------------------------------------------
  * Lens undistortion — replaces Camera::UndistortImage (src/camera.cpp:36-48), which Frontend::GrabStereoImage runs on the left and the
  * right image before anything else when Camera.bNeedUndistortion is 1 (src/frontend.cpp:47-51): cv::undistort(src, dst, K, D) with
  * K = (fx, fy, cx, cy) widened from the camera's float members and D = (k1, k2, p1, p2) (read in src/system.cpp:118-138).
