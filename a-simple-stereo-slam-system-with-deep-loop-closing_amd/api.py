@@ -1202,6 +1202,111 @@ class Backend:
         return po[:P], px[:L], chi[:E], out[:E], int(ro[0]), int(ro[1])
 
 
+MAP_AFTER_INSERT, MAP_AFTER_OPTIMIZE = 0, 1            # MYSLAM_MAP_AFTER_*
+MAP_UPDATED, MAP_SKIPPED = 0, 1                        # MYSLAM_MAP_*
+
+
+class MapTables(C.Structure):                          # myslam_map_tables
+    _fields_ = [(n, C.c_void_p) for n in ("kf_id", "kf_pose", "n_kf", "edge_v0", "edge_v1", "meas", "n_edges", "mp_id", "mp_pos", "mp_first_kf",
+                                          "mp_state", "n_mp")] + \
+               [(n, C.c_int32) for n in ("max_batch", "kf_cap", "edge_cap", "point_cap", "backend_mp_cap")]
+
+
+class MapArchive:
+    """Map::mmAllKeyFrames / mmAllMapPoints and KeyFrame::mpLastKF / mRelativePoseToLastKF of `max_batch` streams as device tables (myslam_map_*),
+    kept up to date from the back end's active tables after every insert and optimise and laid out as LoopCorrector.correct_batch's tables.  The
+    handle owns every buffer; `view()` gives the device pointers.  Batch calls take device pointers as ints, enqueue one launch on the handle's stream
+    and return; `be` arguments are the back end's tables in the header's order."""
+
+    def __init__(self, max_batch, kf_cap, edge_cap, point_cap, backend_mp_cap, stream=None):
+        self.max_batch, self.kf_cap, self.edge_cap, self.point_cap, self.backend_mp_cap = (int(max_batch), int(kf_cap), int(edge_cap), int(point_cap),
+                                                                                             int(backend_mp_cap))
+        self._h = C.c_void_p()
+        _check(lib().myslam_map_create(C.byref(self._h), self.max_batch, self.kf_cap, self.edge_cap, self.point_cap, self.backend_mp_cap),
+               "myslam_map_create")
+        if stream is not None:
+            self.set_stream(stream)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and self._h.value and _lib is not None:
+            lib().myslam_map_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def set_stream(self, stream):
+        _check(lib().myslam_map_set_stream(self._h, C.c_void_p(stream)), "myslam_map_set_stream")
+
+    def launches_per_update(self):
+        return lib().myslam_map_launches_per_update(self._h)
+
+    def view(self):
+        """MapTables: the device pointers (ints or None) and caps of the per-item tables"""
+        t = MapTables()
+        _check(lib().myslam_map_view(self._h, C.byref(t)), "myslam_map_view")
+        return t
+
+    def load(self, item, kf_id, kf_pose, edge_v0, edge_v1, meas, mp_id, mp_pos, mp_first_kf, mp_state, snapshot=(), mp_gone_kf=None, mp_win_mask=None,
+             win_kf=()):
+        """one item from host arrays (synchronous); MyslamError(INVALID / CAPACITY) on what the header lists, the item then keeps every byte"""
+        kf_id = np.ascontiguousarray(kf_id, np.int64); kf_pose = np.ascontiguousarray(kf_pose, np.float64).reshape(-1, 7)
+        e0 = np.ascontiguousarray(edge_v0, np.int32); e1 = np.ascontiguousarray(edge_v1, np.int32); meas = np.ascontiguousarray(meas, np.float64).reshape(-1, 7)
+        mp_id = np.ascontiguousarray(mp_id, np.int64); mp_pos = np.ascontiguousarray(mp_pos, np.float64).reshape(-1, 3)
+        fk = np.ascontiguousarray(mp_first_kf, np.int32); st = np.ascontiguousarray(mp_state, np.uint8); snap = np.ascontiguousarray(snapshot, np.int32)
+        gone = None if mp_gone_kf is None else np.ascontiguousarray(mp_gone_kf, np.int32)
+        mask = None if mp_win_mask is None else np.ascontiguousarray(mp_win_mask, np.uint16)
+        win = np.ascontiguousarray(win_kf, np.int32)
+        assert len(kf_pose) == len(kf_id) and len(e1) == len(e0) == len(meas) and len(mp_pos) == len(mp_id) == len(fk) == len(st)
+        assert (gone is None or len(gone) == len(mp_id)) and (mask is None or len(mask) == len(mp_id))
+        _check(lib().myslam_map_load(self._h, int(item), _p(kf_id), _p(kf_pose), len(kf_id), _p(e0), _p(e1), _p(meas), len(e0), _p(mp_id), _p(mp_pos),
+                                     _p(fk), _p(st), len(mp_id), _p(snap), len(snap), _p(gone), _p(mask), _p(win), len(win)), "myslam_map_load")
+
+    def get(self, item):
+        """one item's tables as a dict of numpy arrays cut to their counts (synchronises)"""
+        K, E, P, M = self.kf_cap, self.edge_cap, self.point_cap, self.backend_mp_cap
+        a = dict(kf_id=np.zeros(K, np.int64), kf_pose=np.zeros((K, 7)), edge_v0=np.zeros(E, np.int32), edge_v1=np.zeros(E, np.int32), meas=np.zeros((E, 7)),
+                 mp_id=np.zeros(P, np.int64), mp_pos=np.zeros((P, 3)), mp_first_kf=np.zeros(P, np.int32), mp_state=np.zeros(P, np.uint8),
+                 snapshot=np.zeros(M, np.int32), mp_gone_kf=np.zeros(P, np.int32), mp_win_mask=np.zeros(P, np.uint16),
+                 win_kf=np.zeros(BA_MAX_WINDOW_POSES, np.int32))
+        n = [C.c_int() for _ in range(5)]
+        _check(lib().myslam_map_get(self._h, int(item), _p(a["kf_id"]), _p(a["kf_pose"]), C.byref(n[0]), _p(a["edge_v0"]), _p(a["edge_v1"]), _p(a["meas"]),
+                                    C.byref(n[1]), _p(a["mp_id"]), _p(a["mp_pos"]), _p(a["mp_first_kf"]), _p(a["mp_state"]), C.byref(n[2]),
+                                    _p(a["snapshot"]), C.byref(n[3]), _p(a["mp_gone_kf"]), _p(a["mp_win_mask"]), _p(a["win_kf"]), C.byref(n[4])),
+               "myslam_map_get")
+        nk, ne, nm, ns, nw = (v.value for v in n)
+        cut = dict(kf_id=nk, kf_pose=nk, edge_v0=ne, edge_v1=ne, meas=ne, mp_id=nm, mp_pos=nm, mp_first_kf=nm, mp_state=nm, snapshot=ns, mp_gone_kf=nm,
+                   mp_win_mask=nm, win_kf=nw)
+        return {k: v[:cut[k]].copy() for k, v in a.items()}
+
+    def update_batch(self, mode, d_kf_id, d_kf_pose, d_n_kf, be_kf_cap, d_mp_id, d_mp_pos, d_n_mp, be_mp_cap, d_obs_mp, d_obs_kf, d_obs_flags, d_n_obs,
+                     be_obs_cap, d_backend_status, d_outlier_mp_id, d_n_outlier_mp, outlier_cap, d_mp_report, batch, d_status):
+        """after each back-end call: mode MAP_AFTER_INSERT with insert_keyframe_batch's d_status and the turn's outlier ids (None / 0 = none), or
+        MAP_AFTER_OPTIMIZE with optimize_batch's d_status and d_mp_report; d_status batch i32 = MAP_UPDATED / MAP_SKIPPED or a negative error"""
+        vp = lambda p: C.c_void_p(p or None)
+        _check(lib().myslam_map_update_batch(self._h, int(mode), vp(d_kf_id), vp(d_kf_pose), vp(d_n_kf), int(be_kf_cap), vp(d_mp_id), vp(d_mp_pos), vp(d_n_mp),
+                                             int(be_mp_cap), vp(d_obs_mp), vp(d_obs_kf), vp(d_obs_flags), vp(d_n_obs), int(be_obs_cap), vp(d_backend_status),
+                                             vp(d_outlier_mp_id), vp(d_n_outlier_mp), int(outlier_cap), vp(d_mp_report), int(batch), vp(d_status)),
+               "myslam_map_update_batch")
+
+    def loop_inputs_batch(self, d_kf_id, d_n_kf, be_kf_cap, d_mp_id, d_n_mp, be_mp_cap, d_obs_mp, d_obs_kf, d_obs_flags, d_n_obs, be_obs_cap, d_cur_kf_id,
+                          d_loop_kf_id, d_detect_status, active_cap, batch, d_active, d_n_active, d_cur, d_loop, d_first_active, d_first_kf, d_n_points):
+        """LoopCorrector.correct_batch's per-loop index inputs from the archive and the back end's tables"""
+        vp = lambda p: C.c_void_p(p or None)
+        _check(lib().myslam_map_loop_inputs_batch(self._h, vp(d_kf_id), vp(d_n_kf), int(be_kf_cap), vp(d_mp_id), vp(d_n_mp), int(be_mp_cap), vp(d_obs_mp),
+                                                  vp(d_obs_kf), vp(d_obs_flags), vp(d_n_obs), int(be_obs_cap), vp(d_cur_kf_id), vp(d_loop_kf_id),
+                                                  vp(d_detect_status), int(active_cap), int(batch), vp(d_active), vp(d_n_active), vp(d_cur), vp(d_loop),
+                                                  vp(d_first_active), vp(d_first_kf), vp(d_n_points)), "myslam_map_loop_inputs_batch")
+
+    def write_backend_batch(self, d_kf_id, d_kf_pose, d_n_kf, be_kf_cap, d_mp_id, d_mp_pos, d_n_mp, be_mp_cap, d_select, batch):
+        """archive poses / positions into the back end's rows of the items with d_select != 0 (None / 0 = all)"""
+        vp = lambda p: C.c_void_p(p or None)
+        _check(lib().myslam_map_write_backend_batch(self._h, vp(d_kf_id), vp(d_kf_pose), vp(d_n_kf), int(be_kf_cap), vp(d_mp_id), vp(d_mp_pos), vp(d_n_mp),
+                                                    int(be_mp_cap), vp(d_select), int(batch)), "myslam_map_write_backend_batch")
+
+    def feature_slots_batch(self, d_feat_mp_id, d_n_feat, feat_cap, batch, d_feat_landmark):
+        """map-point id -> archive slot per feature, -1 for none / absent / erased: LoopKeyFrameStore.put_batch's d_feat_landmark"""
+        _check(lib().myslam_map_feature_slots_batch(self._h, C.c_void_p(d_feat_mp_id or None), C.c_void_p(d_n_feat or None), int(feat_cap), int(batch),
+                                                    C.c_void_p(d_feat_landmark or None)), "myslam_map_feature_slots_batch")
+
+
 LOOP_DETECT_CANDIDATE, LOOP_DETECT_NO_LOOP = 0, 1      # MYSLAM_LOOP_DETECT_*
 
 

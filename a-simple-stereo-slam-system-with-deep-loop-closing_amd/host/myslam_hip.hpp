@@ -656,6 +656,67 @@ public:
     }
 };
 
+// Map::mmAllKeyFrames / mmAllMapPoints and KeyFrame::mpLastKF / mRelativePoseToLastKF of maxBatch streams as device tables (myslam_map_*,
+// include/myslam_hip.h): UpdateBatch after EVERY Backend call on the same stream keeps them current, and they are laid out as
+// LoopCorrector::CorrectBatch's tables (View() gives the device pointers).  Order of a key-frame: InsertKeyFrameBatch -> UpdateBatch(AFTER_INSERT) ->
+// OptimizeBatch -> UpdateBatch(AFTER_OPTIMIZE) -> ... -> LoopInputsBatch -> CorrectBatch -> WriteBackendBatch -> Tracker::UpdateFromMap.  Left with
+// the caller: LoopLocalFusion's re-linking of observations, and clearing single features' landmarks in the loop store when BA culls an observation.
+class MapArchive {
+    myslam_map* h_ = nullptr;
+public:
+    MapArchive(int maxBatch, int kfCap, int edgeCap, int pointCap, int backendMpCap) {
+        check(myslam_map_create(&h_, maxBatch, kfCap, edgeCap, pointCap, backendMpCap), "myslam_map_create");
+    }
+    ~MapArchive() { if (h_) myslam_map_destroy(h_); }
+    MapArchive(const MapArchive&) = delete; MapArchive& operator=(const MapArchive&) = delete;
+    void SetStream(void* hipStream) { check(myslam_map_set_stream(h_, hipStream), "myslam_map_set_stream"); }
+    int LaunchesPerUpdate() const { return myslam_map_launches_per_update(h_); }
+    myslam_map_tables View() const { myslam_map_tables t; check(myslam_map_view(h_, &t), "myslam_map_view"); return t; }
+    // one item from / to host arrays (synchronous); Get's arrays are sized by the caps, any pointer may be nullptr
+    void Load(int item, const int64_t* kfId, const double* kfPose, int nKF, const int32_t* edgeV0, const int32_t* edgeV1, const double* meas, int nEdges,
+              const int64_t* mpId, const double* mpPos, const int32_t* mpFirstKF, const uint8_t* mpState, int nMP, const int32_t* snapshot = nullptr,
+              int nSnapshot = 0, const int32_t* mpGoneKF = nullptr, const uint16_t* mpWinMask = nullptr, const int32_t* winKF = nullptr, int nWin = 0) {
+        check(myslam_map_load(h_, item, kfId, kfPose, nKF, edgeV0, edgeV1, meas, nEdges, mpId, mpPos, mpFirstKF, mpState, nMP, snapshot, nSnapshot, mpGoneKF,
+                              mpWinMask, winKF, nWin),
+              "myslam_map_load");
+    }
+    void Get(int item, int64_t* kfId, double* kfPose, int* nKF, int32_t* edgeV0, int32_t* edgeV1, double* meas, int* nEdges, int64_t* mpId, double* mpPos,
+             int32_t* mpFirstKF, uint8_t* mpState, int* nMP, int32_t* snapshot = nullptr, int* nSnapshot = nullptr,
+             int32_t* mpGoneKF = nullptr, uint16_t* mpWinMask = nullptr, int32_t* winKF = nullptr, int* nWin = nullptr) {
+        check(myslam_map_get(h_, item, kfId, kfPose, nKF, edgeV0, edgeV1, meas, nEdges, mpId, mpPos, mpFirstKF, mpState, nMP, snapshot, nSnapshot, mpGoneKF,
+                             mpWinMask, winKF, nWin),
+              "myslam_map_get");
+    }
+    // mode = MYSLAM_MAP_AFTER_INSERT (d_backendStatus = InsertKeyFrameBatch's status, the turn's outlier ids, d_mpReport unused) or
+    // MYSLAM_MAP_AFTER_OPTIMIZE (OptimizeBatch's status and d_mpReport); status[b] = MYSLAM_MAP_UPDATED / _SKIPPED or a negative error
+    void UpdateBatch(int mode, const Backend& be, const int64_t* d_kfId, const double* d_kfPose, const int32_t* d_nKF, const int64_t* d_mpId,
+                     const double* d_mpPos, const int32_t* d_nMP, const int32_t* d_obsMP, const int32_t* d_obsKF, const uint8_t* d_obsFlags,
+                     const int32_t* d_nObs, const int32_t* d_backendStatus, const int64_t* d_outlierMPId, const int32_t* d_nOutlierMP, int outlierCap,
+                     const uint8_t* d_mpReport, int batch, int32_t* d_status) {
+        check(myslam_map_update_batch(h_, mode, d_kfId, d_kfPose, d_nKF, be.kfCap(), d_mpId, d_mpPos, d_nMP, be.mpCap(), d_obsMP, d_obsKF, d_obsFlags, d_nObs,
+                                      be.obsCap(), d_backendStatus, d_outlierMPId, d_nOutlierMP, outlierCap, d_mpReport, batch, d_status),
+              "myslam_map_update_batch");
+    }
+    // LoopCorrector::CorrectBatch's per-loop index inputs (activeCap = that corrector's)
+    void LoopInputsBatch(const Backend& be, const int64_t* d_kfId, const int32_t* d_nKF, const int64_t* d_mpId, const int32_t* d_nMP, const int32_t* d_obsMP,
+                         const int32_t* d_obsKF, const uint8_t* d_obsFlags, const int32_t* d_nObs, const int64_t* d_curKFId, const uint64_t* d_loopKFId,
+                         const int32_t* d_detectStatus, int activeCap, int batch, int32_t* d_active, int32_t* d_nActive, int32_t* d_cur, int32_t* d_loop,
+                         int32_t* d_firstActive, int32_t* d_firstKF, int32_t* d_nPoints) {
+        check(myslam_map_loop_inputs_batch(h_, d_kfId, d_nKF, be.kfCap(), d_mpId, d_nMP, be.mpCap(), d_obsMP, d_obsKF, d_obsFlags, d_nObs, be.obsCap(),
+                                           d_curKFId, d_loopKFId, d_detectStatus, activeCap, batch, d_active, d_nActive, d_cur, d_loop, d_firstActive,
+                                           d_firstKF, d_nPoints), "myslam_map_loop_inputs_batch");
+    }
+    void WriteBackendBatch(const Backend& be, const int64_t* d_kfId, double* d_kfPose, const int32_t* d_nKF, const int64_t* d_mpId, double* d_mpPos,
+                           const int32_t* d_nMP, const uint8_t* d_select /*nullptr = all*/, int batch) {
+        check(myslam_map_write_backend_batch(h_, d_kfId, d_kfPose, d_nKF, be.kfCap(), d_mpId, d_mpPos, d_nMP, be.mpCap(), d_select, batch),
+              "myslam_map_write_backend_batch");
+    }
+    // map-point id -> archive slot per feature: LoopKeyFrameStore::PutBatch's d_featureLandmark
+    void FeatureSlotsBatch(const int64_t* d_featMPId, const int32_t* d_nFeat, int featCap, int batch, int32_t* d_featureLandmark) {
+        check(myslam_map_feature_slots_batch(h_, d_featMPId, d_nFeat, featCap, batch, d_featureLandmark), "myslam_map_feature_slots_batch");
+    }
+};
+
 // What ProcessNewKF leaves in a KeyFrame (mvPyramidKeyPoints, mORBDescriptors, which features still name a map point), resident on the device for up to
 // kfCapacity key-frames of cap rows and featCap features, and LoopClosing::DetectLoop's decision (src/loopclosing.cpp:147, :151) over
 // LoopDatabase's batched scan: DetectBatch writes the chosen key-frames' arrays exactly where MatchFeaturesBatch reads its loop side, status[b] =

@@ -1245,6 +1245,127 @@ int myslam_backend_insert_keyframe_batch(myslam_backend* h, int64_t* d_kf_id, do
 int myslam_backend_insert_launches_per_call(const myslam_backend* h);
 
 /* ------------------------------------------------------------------------------------------
+ * The whole map of every stream on the device — Map::mmAllKeyFrames / mmAllMapPoints (src/map.cpp: InsertKeyFrame, InsertMapPoint, RemoveMapPoint,
+ * AddOutlierMapPoint, RemoveAllOutlierMapPoints) and the link fields KeyFrame::mpLastKF / mRelativePoseToLastKF (include/myslam/keyframe.h, set in
+ * src/frontend.cpp:424-447), kept up to date from the back end's ACTIVE tables after every insert and optimise and laid out so that they ARE the
+ * tables of myslam_loop_correct_batch: the fixed set of src/loopclosing.cpp:560-562, the edges of :568-602 and the map points of :612-641.
+ * Order of one key-frame:  insert -> update(AFTER_INSERT) -> optimise -> update(AFTER_OPTIMIZE) -> ... -> detect / match / verify -> loop_inputs ->
+ * myslam_loop_correct_batch on the archive's own tables -> write_backend -> myslam_tracker_update_from_map_batch.
+ * The handle owns every buffer and nothing moves after create, so a recorded step that names the tables stays valid.  Item b is one stream's map;
+ * tables are strided by the caps, slots from a count on are never read or written (myslam_map_view gives the device pointers):
+ *   kf_id        max_batch x kf_cap i64, ascending, append-only      mnKFId of every key-frame; row 0 is the stream's first key-frame
+ *   kf_pose      max_batch x kf_cap x 7 f64                          Tcw: myslam_loop_correct_batch's d_poses;   n_kf  max_batch i32
+ *   edge_v0 / edge_v1 / meas / n_edges   i32, i32, f64 x 7, i32      myslam_loop_correct_batch's d_edge_*, which appends its loop edge here in place
+ *   mp_id        max_batch x point_cap i64, ascending, append-only   mnId of every map point
+ *   mp_pos       max_batch x point_cap x 3 f64                       d_points, and myslam_loop_match_batch's d_landmark_pos with landmark_stride = point_cap
+ *   mp_first_kf  max_batch x point_cap i32                           row in kf_id of GetObservations().front()->mpKF, -1 = never seen with an observer
+ *   mp_state     max_batch x point_cap u8                            0 alive; 1 on the map's outlier list (AddOutlierMapPoint) but not yet erased; 2 erased
+ *   n_mp         max_batch i32
+ * and, internal, the SNAPSHOT: per item the archive slot of every row of the back end's map-point table as of the last update, with its count; and the
+ * WINDOW RECORD that keeps mp_first_kf exact (a back-end row with d_obs_kf = -1 no longer says whose it is): win_kf = the archive row of every row of the
+ * back end's key-frame table at the last update (up to MYSLAM_BA_MAX_WINDOW_POSES), mp_win_mask (u16 per point) = bit k: the point had a row on row k
+ * of that table, mp_gone_kf (i32 per point) = the lowest archive row among the point's observers that have left the window, -1 = none.
+ * CONTRACT: exactly one back-end call on an item lies between two updates of it.  myslam_backend_optimize_batch's d_mp_report is indexed by INPUT row,
+ * and after its compaction only the snapshot says which point that row was.
+ *
+ * myslam_map_load / myslam_map_get — host pointers, synchronous (they wait for the handle's stream; MYSLAM_ERR_UNSUPPORTED while it is recorded): one
+ * item from / to the host, for streams that move over from a host map and for hand-made states.  load validates: ids strictly ascending, counts
+ * within the caps (MYSLAM_ERR_CAPACITY beyond), edge endpoints in [0, n_kf) and distinct, mp_first_kf and mp_gone_kf in [-1, n_kf), states in {0, 1, 2},
+ * snapshot entries in [0, n_mp), win_kf entries in [0, n_kf), no mask bit from n_win on — else MYSLAM_ERR_INVALID and the item keeps every byte.
+ * snapshot / win_kf may be NULL with a count of 0; mp_gone_kf NULL = all -1, mp_win_mask NULL = all 0 (a map whose window is empty).  get: arrays sized
+ * by the caps (snapshot: backend_mp_cap, win_kf: MYSLAM_BA_MAX_WINDOW_POSES), any pointer may be NULL.
+ *
+ * myslam_map_update_batch — device pointers, ONE launch (k_map_update, one workgroup per item), after EACH back-end call on the same stream.  It reads
+ * the back end's tables as they stand after that call (be_kf_cap / be_mp_cap / be_obs_cap = that handle's caps; be_mp_cap must be the archive's
+ * backend_mp_cap), d_backend_status = that call's d_status, and
+ *   mode MYSLAM_MAP_AFTER_INSERT:   d_outlier_mp_id (batch x outlier_cap) / d_n_outlier_mp of the turn or init, NULL count = none;
+ *   mode MYSLAM_MAP_AFTER_OPTIMIZE: d_mp_report of myslam_backend_optimize_batch.
+ * Per item everything is decided before anything is written.  After insert:
+ *   1. d_backend_status[b] != 0: the item is untouched, MYSLAM_MAP_SKIPPED.
+ *   2. every back-end key-frame id above the archive's last is appended with its pose, in order (Map::InsertKeyFrame); every appended row except the
+ *      archive's first gets the edge (new row, previous row, meas), meas = p7_of(mm(T_of(new), T_inv(T_of(prev)))) with prev = the archive's pose of
+ *      the previous row: mRelativePoseToLastKF as T[v0] * T[v1]^-1, in chain.py's arithmetic and operation order, every f64 operation rounded alone.
+ *   3. every back-end map-point id that is not in the archive is appended (Map::InsertMapPoint) with state 0; it must be above the archive's last id,
+ *      otherwise MYSLAM_ERR_INVALID.  An id that is archived (a point that comes back) is just found.
+ *   4. every listed outlier id that is archived with state 0 gets state 1 (Map::AddOutlierMapPoint); other ids are ignored.
+ *   5. refresh: every back-end key-frame row's pose and map-point row's position goes to its archive row.  First observers: a key-frame row of the
+ *      window record that is no longer in the table has left the window; every point of the OLD snapshot whose mask names it lowers its mp_gone_kf to
+ *      that row.  Both observation lists are in key-frame order (src/keyframe.cpp:45, src/map.cpp:38), so GetObservations().front()->mpKF is the
+ *      lowest archive row among the point's rows with d_obs_kf >= 0 (the first of them) and mp_gone_kf: a point of the table takes that minimum, a
+ *      point that left the table takes mp_gone_kf (all its rows are of key-frames that left; such rows are never ACTIVE, the optimiser cannot remove
+ *      them).  "The record stays when the front row has d_obs_kf < 0" alone is NOT exact: when the optimiser removes a front observation whose
+ *      key-frame is in the window and the next row is one of a key-frame that left, the front becomes that key-frame (tests/test_map_archive_ref.py
+ *      holds such a point).  Rows LoopLocalFusion appended out of key-frame order are out of scope, below.
+ *   6. the snapshot, the masks and the window record are rebuilt from the table.  MYSLAM_MAP_UPDATED.
+ * After optimise: MYSLAM_BACKEND_DONE -> every snapshot row whose d_mp_report is 2 gets state 2, then every archive point with state 1 gets state 2
+ * (Map::RemoveAllOutlierMapPoints empties the whole list, points that are not active included), then 5 and 6.  MYSLAM_BACKEND_EMPTY or an error: the
+ * reference returns before the removal — nothing changes, state 1 stays, MYSLAM_MAP_SKIPPED.  A table that holds an id the archive lacks, or more rows
+ * than the snapshot: MYSLAM_ERR_INVALID.
+ * A key-frame, edge or point count that would exceed its cap: MYSLAM_ERR_CAPACITY.  A count out of range, a key-frame id at or below the archive's
+ * last that it does not hold: MYSLAM_ERR_INVALID.  An item with an error keeps every byte.
+ *
+ * myslam_map_loop_inputs_batch — one launch: myslam_loop_correct_batch's per-loop index inputs.  d_active (batch x active_cap, active_cap >= be_kf_cap)
+ * / d_n_active = archive rows of the back end's key-frame ids in table order (ascending by construction; :560); d_cur = row of d_cur_kf_id[b] (i64,
+ * the turn's d_new_kf_id); d_loop = row of d_loop_kf_id[b] (u64, the scan's d_best_id), -1 when absent or d_detect_status[b] !=
+ * MYSLAM_LOOP_DETECT_CANDIDATE; d_first_active (batch x point_cap): for a point in the back end's table the d_obs_kf of its first ACTIVE row
+ * (GetActiveObservations().front(); the active list is the table's order), else -1; d_first_kf: mp_first_kf for states 0 and 1, -1 for state 2 (:625-629);
+ * d_n_points = n_mp.  d_cur_kf_id[b] < 0: d_cur = d_loop = -1 and empty lists; the corrector skips the item on its verify status.
+ *
+ * myslam_map_write_backend_batch — one launch, after myslam_loop_correct_batch ran on the archive's tables: for items with d_select[b] != 0 (NULL = all)
+ * every back-end key-frame row takes its archive pose and every map-point row its archive position, found by id (:612-641 reach the active map through
+ * the shared objects).  For an item the corrector skipped this is a copy of equal bits.
+ *
+ * myslam_map_feature_slots_batch — one launch: d_feat_mp_id (batch x feat_cap) / d_n_feat of the turn -> the archive slot per feature (binary search),
+ * -1 for no id, an absent id or a point with state 2: myslam_loop_store_put_batch's d_feat_landmark.
+ *
+ * All batch calls allocate nothing, never synchronise, read no device memory from the host, are recordable between myslam_graph_begin / _end and use no
+ * global atomics; an item's bytes depend neither on its slot nor on its neighbours.  Call level, nothing enqueued: NULL pointers, an unknown mode, a
+ * back-end cap that does not match (be_kf_cap beyond MYSLAM_BA_MAX_WINDOW_POSES included) -> MYSLAM_ERR_INVALID; batch beyond the handle's -> MYSLAM_ERR_CAPACITY.
+ * OUT OF SCOPE, left with the caller: LoopLocalFusion's re-linking of observations (src/loopclosing.cpp:509-532) with its effect on the back end's
+ * tables and the tracker's landmark ids; clearing single features' landmarks in the loop store when BA culls an observation
+ * (myslam_loop_store_set_landmarks_batch).
+ * ------------------------------------------------------------------------------------------ */
+#define MYSLAM_MAP_AFTER_INSERT 0
+#define MYSLAM_MAP_AFTER_OPTIMIZE 1
+#define MYSLAM_MAP_UPDATED 0
+#define MYSLAM_MAP_SKIPPED 1
+typedef struct myslam_map myslam_map;
+typedef struct myslam_map_tables {
+    int64_t* kf_id; double* kf_pose; int32_t* n_kf;
+    int32_t* edge_v0; int32_t* edge_v1; double* meas; int32_t* n_edges;
+    int64_t* mp_id; double* mp_pos; int32_t* mp_first_kf; uint8_t* mp_state; int32_t* n_mp;
+    int32_t max_batch, kf_cap, edge_cap, point_cap, backend_mp_cap;
+} myslam_map_tables;
+int myslam_map_create(myslam_map** out, int max_batch, int kf_cap, int edge_cap, int point_cap, int backend_mp_cap);
+int myslam_map_destroy(myslam_map* h);
+int myslam_map_set_stream(myslam_map* h, void* hip_stream);
+/* the device pointers and caps of the per-item tables: valid until destroy */
+int myslam_map_view(const myslam_map* h, myslam_map_tables* out);
+int myslam_map_load(myslam_map* h, int item, const int64_t* kf_id, const double* kf_pose, int n_kf, const int32_t* edge_v0, const int32_t* edge_v1,
+                    const double* meas, int n_edges, const int64_t* mp_id, const double* mp_pos, const int32_t* mp_first_kf, const uint8_t* mp_state, int n_mp,
+                    const int32_t* snapshot, int n_snapshot, const int32_t* mp_gone_kf, const uint16_t* mp_win_mask, const int32_t* win_kf, int n_win);
+int myslam_map_get(myslam_map* h, int item, int64_t* kf_id, double* kf_pose, int* n_kf, int32_t* edge_v0, int32_t* edge_v1, double* meas, int* n_edges,
+                   int64_t* mp_id, double* mp_pos, int32_t* mp_first_kf, uint8_t* mp_state, int* n_mp, int32_t* snapshot, int* n_snapshot,
+                   int32_t* mp_gone_kf, uint16_t* mp_win_mask, int32_t* win_kf, int* n_win);
+/* src/map.cpp InsertKeyFrame / InsertMapPoint / AddOutlierMapPoint / RemoveAllOutlierMapPoints and src/frontend.cpp:424-447 as described above */
+int myslam_map_update_batch(myslam_map* h, int mode, const int64_t* d_kf_id, const double* d_kf_pose, const int32_t* d_n_kf, int be_kf_cap,
+                            const int64_t* d_mp_id, const double* d_mp_pos, const int32_t* d_n_mp, int be_mp_cap, const int32_t* d_obs_mp,
+                            const int32_t* d_obs_kf, const uint8_t* d_obs_flags, const int32_t* d_n_obs, int be_obs_cap, const int32_t* d_backend_status,
+                            const int64_t* d_outlier_mp_id, const int32_t* d_n_outlier_mp, int outlier_cap, const uint8_t* d_mp_report, int batch,
+                            int32_t* d_status);
+/* kernel launches one myslam_map_update_batch enqueues (1) */
+int myslam_map_launches_per_update(const myslam_map* h);
+/* src/loopclosing.cpp:560-562 and the index inputs of :470-507 / :612-641 as described above */
+int myslam_map_loop_inputs_batch(myslam_map* h, const int64_t* d_kf_id, const int32_t* d_n_kf, int be_kf_cap, const int64_t* d_mp_id, const int32_t* d_n_mp,
+                                 int be_mp_cap, const int32_t* d_obs_mp, const int32_t* d_obs_kf, const uint8_t* d_obs_flags, const int32_t* d_n_obs,
+                                 int be_obs_cap, const int64_t* d_cur_kf_id, const uint64_t* d_loop_kf_id, const int32_t* d_detect_status, int active_cap,
+                                 int batch, int32_t* d_active, int32_t* d_n_active, int32_t* d_cur, int32_t* d_loop, int32_t* d_first_active,
+                                 int32_t* d_first_kf, int32_t* d_n_points);
+int myslam_map_write_backend_batch(myslam_map* h, const int64_t* d_kf_id, double* d_kf_pose, const int32_t* d_n_kf, int be_kf_cap, const int64_t* d_mp_id,
+                                   double* d_mp_pos, const int32_t* d_n_mp, int be_mp_cap, const uint8_t* d_select, int batch);
+int myslam_map_feature_slots_batch(myslam_map* h, const int64_t* d_feat_mp_id, const int32_t* d_n_feat, int feat_cap, int batch, int32_t* d_feat_landmark);
+
+/* ------------------------------------------------------------------------------------------
  * Host-side formats of the reference's runner — plain host code, no device needed; the C++ forms live in
  * host/myslam_io.hpp and host/myslam_png.hpp.
  * ------------------------------------------------------------------------------------------ */
