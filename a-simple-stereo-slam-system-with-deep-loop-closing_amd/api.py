@@ -877,11 +877,14 @@ class Tracker:
     def keyframe_launches(self):
         return lib().myslam_tracker_keyframe_launches(self._h)
 
+    # the outputs of a turn and of an init, in the order of the C calls' trailing pointers
+    TURN_OUTPUTS = ("new_kf_id", "new_kf_pose", "feat_mp_id", "feat_mp_pos", "feat_uv", "feat_tag", "feat_flags", "n_feat", "outlier_mp_id", "n_outlier_mp",
+                    "right_xy", "right_ok", "report")
+
     def keyframe_batch(self, d_right, step, stride, d_new_kps, d_n_new, kp_cap, baseline, out):
-        """device pointers, asynchronous.  out: dict of device pointers new_kf_id, new_kf_pose, feat_mp_id, feat_mp_pos, feat_uv, feat_tag, feat_flags,
-        n_feat, outlier_mp_id, n_outlier_mp, right_xy, right_ok, report (sizes: the header; feature stride = cap, outlier stride = 2 cap)"""
-        o = [C.c_void_p(out[k]) for k in ("new_kf_id", "new_kf_pose", "feat_mp_id", "feat_mp_pos", "feat_uv", "feat_tag", "feat_flags", "n_feat",
-                                          "outlier_mp_id", "n_outlier_mp", "right_xy", "right_ok", "report")]
+        """device pointers, asynchronous.  out: dict of device pointers, one per name in TURN_OUTPUTS (sizes: the header; feature stride = cap,
+        outlier stride = 2 cap)"""
+        o = [C.c_void_p(out[k]) for k in self.TURN_OUTPUTS]
         _check(lib().myslam_tracker_keyframe_batch(self._h, C.c_void_p(d_right), int(step), C.c_size_t(stride), C.c_void_p(d_new_kps), C.c_void_p(d_n_new),
                                                    int(kp_cap), C.c_double(baseline), *o), "myslam_tracker_keyframe_batch")
 
@@ -925,8 +928,7 @@ class Tracker:
 
     def init_batch(self, d_left, d_right, step, stride, d_new_kps, d_n_new, kp_cap, baseline, init_good, out):
         """device pointers, asynchronous: StereoInit of every init-eligible stream.  out: keyframe_batch's dict of device pointers"""
-        o = [C.c_void_p(out[k]) for k in ("new_kf_id", "new_kf_pose", "feat_mp_id", "feat_mp_pos", "feat_uv", "feat_tag", "feat_flags", "n_feat",
-                                          "outlier_mp_id", "n_outlier_mp", "right_xy", "right_ok", "report")]
+        o = [C.c_void_p(out[k]) for k in self.TURN_OUTPUTS]
         _check(lib().myslam_tracker_init_batch(self._h, C.c_void_p(d_left), C.c_void_p(d_right), int(step), C.c_size_t(stride), C.c_void_p(d_new_kps),
                                                C.c_void_p(d_n_new), int(kp_cap), C.c_double(baseline), int(init_good), *o), "myslam_tracker_init_batch")
 

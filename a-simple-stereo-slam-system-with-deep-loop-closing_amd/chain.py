@@ -842,17 +842,57 @@ class StreamBank:
             self.d_kps = z((S, self.kp_cap, self.api.KP_DTYPE.itemsize), torch.uint8); self.d_nkp = z(S, torch.int32); self.d_kst = z(S, torch.int32)
         return self.turn_buf
 
-    def enqueue_turn(self):
-        """masks -> detect_batch -> turn for every eligible stream of the bank, asynchronous: three calls on the tracker's stream (the extractor
-        runs on the same one), from the left images of the last step (upload()) and their right images"""
-        buf = self._turn_buffers()
+    def _enqueue_detect(self, masks, orb, d_kps, kp_cap):
+        """what enqueue_turn and enqueue_init share: the right images of the last upload() go up, then masks -> detect_batch on the tracker's stream
+        (the extractor runs on the same one).  Returns the arguments their batch call ends with: right images .. key-point capacity"""
         img = self.rows * self.cols
         self.d_right.copy_(self.torch.from_numpy(np.stack([np.ascontiguousarray(R, np.uint8) for _, R in self.images])))
-        self.trk.keyframe_masks(self.d_mask.data_ptr(), self.cols, img)
-        self.orb.detect_batch(self.d_img.data_ptr(), len(self.chains), self.rows, self.cols, self.cols, img, self.d_kps.data_ptr(), self.d_nkp.data_ptr(),
-                              self.d_kst.data_ptr(), self.kp_cap, d_masks=self.d_mask.data_ptr())
-        self.trk.keyframe_batch(self.d_right.data_ptr(), self.cols, img, self.d_kps.data_ptr(), self.d_nkp.data_ptr(), self.kp_cap, self.chains[0].K["baseline"],
-                                {k: v.data_ptr() for k, v in buf.items()})
+        masks(self.d_mask.data_ptr(), self.cols, img)
+        orb.detect_batch(self.d_img.data_ptr(), len(self.chains), self.rows, self.cols, self.cols, img, d_kps.data_ptr(), self.d_nkp.data_ptr(),
+                         self.d_kst.data_ptr(), kp_cap, d_masks=self.d_mask.data_ptr())
+        return self.d_right.data_ptr(), self.cols, img, d_kps.data_ptr(), self.d_nkp.data_ptr(), kp_cap
+
+    def enqueue_turn(self):
+        """masks -> detect_batch -> turn for every eligible stream of the bank, asynchronous: three calls on the tracker's stream, from the left
+        images of the last step (upload()) and their right images"""
+        outs = {k: v.data_ptr() for k, v in self._turn_buffers().items()}
+        self.trk.keyframe_batch(*self._enqueue_detect(self.trk.keyframe_masks, self.orb, self.d_kps, self.kp_cap), self.chains[0].K["baseline"], outs)
+
+    def adopt_keyframe(self, s, out, last_kf=None):
+        """The key-frame the device made of stream s's current frame (out: the downloaded turn buffers) enters the chain: the features with their map
+        points (one the chain does not know yet is created: Map::InsertMapPoint), the right matches, insert_keyframe() with the device's id and
+        pose (last_kf: the reference key-frame a turn leaves behind, None for a map's first), the back end, the pose list and the slots"""
+        c = self.chains[s]
+        n, mps, seen = int(out["n_feat"][s]), [], set()
+        for i in range(n):
+            f = Feature(out["feat_uv"][s, i, 0], out["feat_uv"][s, i, 1])
+            mid = int(out["feat_mp_id"][s, i])
+            if mid >= 0:
+                if mid not in c.all_mps:
+                    c.all_mps[mid] = MapPoint(mid, out["feat_mp_pos"][s, i])
+                    c.next_mp_id = max(c.next_mp_id, mid + 1)
+                f.mp = c.all_mps[mid]
+                if mid not in seen:
+                    seen.add(mid); mps.append(f.mp)
+            c.cur.feats.append(f)
+        c.cur.right = [(x, y) if ok else None for (x, y), ok in zip(out["right_xy"][s, :n], out["right_ok"][s, :n])]
+        kf = KeyFrame(int(out["new_kf_id"][s]), c.cur)
+        c.next_kf_id = kf.id + 1
+        for f in kf.feats:
+            f.kf = kf
+            if f.live() is not None:
+                f.mp.obs.append(f)
+        kf.pose = out["new_kf_pose"][s].copy()
+        if last_kf is not None:
+            kf.last_kf = last_kf
+            kf.rel_to_last = p7_of(mm(T_of(kf.pose), T_inv(T_of(last_kf.pose))))      # cur.rel, rebuilt from the two poses (the host's to rounding)
+        c.ref_kf = kf
+        c.cur.rel = np.eye(4)
+        c.kf_frames.append(c.cur.id)
+        c.backend_new_keyframe(kf)
+        c.poses.append(p7_of(mm(c.cur.rel, T_of(c.ref_kf.pose))))
+        c.last = c.cur
+        self.slots[s] = mps
 
     def device_turn(self, streams, res=None, t=None, ts=None, resync=True):
         """The key-frame turns of the frozen streams `streams` (res: the step's result records) ON THE DEVICE: DetectFeatures, FindFeaturesInRight,
@@ -877,35 +917,7 @@ class StreamBank:
             for i in out["outlier_mp_id"][s, :out["n_outlier_mp"][s]]:                # Map::AddOutlierMapPoint, in the device's order
                 c.all_mps[int(i)].outlier = True
                 c.outlier_mps.append(int(i))
-            n, mps, seen = int(out["n_feat"][s]), [], set()
-            for i in range(n):
-                f = Feature(out["feat_uv"][s, i, 0], out["feat_uv"][s, i, 1])
-                mid = int(out["feat_mp_id"][s, i])
-                if mid >= 0:
-                    if mid not in c.all_mps:                                          # a map point the turn created (Map::InsertMapPoint)
-                        c.all_mps[mid] = MapPoint(mid, out["feat_mp_pos"][s, i])
-                        c.next_mp_id = max(c.next_mp_id, mid + 1)
-                    f.mp = c.all_mps[mid]
-                    if mid not in seen:
-                        seen.add(mid); mps.append(f.mp)
-                c.cur.feats.append(f)
-            c.cur.right = [(x, y) if ok else None for (x, y), ok in zip(out["right_xy"][s, :n], out["right_ok"][s, :n])]
-            kf = KeyFrame(int(out["new_kf_id"][s]), c.cur)                            # insert_keyframe() with the device's id and pose
-            c.next_kf_id = kf.id + 1
-            for f in kf.feats:
-                f.kf = kf
-                if f.live() is not None:
-                    f.mp.obs.append(f)
-            kf.pose = out["new_kf_pose"][s].copy()
-            kf.last_kf = c.ref_kf
-            kf.rel_to_last = p7_of(mm(T_of(kf.pose), T_inv(T_of(c.ref_kf.pose))))    # cur.rel, rebuilt from the two poses (the host's to rounding)
-            c.ref_kf = kf
-            c.cur.rel = np.eye(4)
-            c.kf_frames.append(c.cur.id)
-            c.backend_new_keyframe(kf)
-            c.poses.append(p7_of(mm(c.cur.rel, T_of(c.ref_kf.pose))))
-            c.last = c.cur
-            self.slots[s] = mps
+            self.adopt_keyframe(s, out, last_kf=c.ref_kf)
             if resync:
                 c.rel_motion = self.trk.get_frame(s)["rel_motion"]
                 self.hand_off(s)
@@ -913,18 +925,13 @@ class StreamBank:
     def enqueue_init(self):
         """masks -> detect_batch on the INIT extractor -> init for every init-eligible stream of the bank, asynchronous: three calls on the tracker's
         stream, from the stereo pairs of the last upload()"""
-        buf = self._turn_buffers()
+        outs = {k: v.data_ptr() for k, v in self._turn_buffers().items()}
         if getattr(self, "d_kps_init", None) is None:
             self.orb_init = self.chains[0].be.det_init    # Frontend::_mpORBextractorInit (nInitFeatures): every stream of a bank shares its configuration
             self.kp_cap_init = int(self.orb_init.max_keypoints(self.rows, self.cols))
             self.d_kps_init = self.torch.zeros((len(self.chains), self.kp_cap_init, self.api.KP_DTYPE.itemsize), dtype=self.torch.uint8, device="cuda")
-        img = self.rows * self.cols
-        self.d_right.copy_(self.torch.from_numpy(np.stack([np.ascontiguousarray(R, np.uint8) for _, R in self.images])))
-        self.trk.init_masks(self.d_mask.data_ptr(), self.cols, img)
-        self.orb_init.detect_batch(self.d_img.data_ptr(), len(self.chains), self.rows, self.cols, self.cols, img, self.d_kps_init.data_ptr(),
-                                   self.d_nkp.data_ptr(), self.d_kst.data_ptr(), self.kp_cap_init, d_masks=self.d_mask.data_ptr())
-        self.trk.init_batch(self.d_img.data_ptr(), self.d_right.data_ptr(), self.cols, img, self.d_kps_init.data_ptr(), self.d_nkp.data_ptr(), self.kp_cap_init,
-                            self.chains[0].K["baseline"], self.chains[0].n_init_good, {k: v.data_ptr() for k, v in buf.items()})
+        self.trk.init_batch(self.d_img.data_ptr(), *self._enqueue_detect(self.trk.init_masks, self.orb_init, self.d_kps_init, self.kp_cap_init),
+                            self.chains[0].K["baseline"], self.chains[0].n_init_good, outs)
 
     def device_init_turn(self, streams, t=None, ts=None, resync=True):
         """Frontend::StereoInit of the INITING streams `streams` ON THE DEVICE (enqueue_init): DetectFeatures, FindFeaturesInRight, BuildInitMap and
@@ -955,31 +962,8 @@ class StreamBank:
                 c.poses.append(IDENT.copy())
                 c.last = c.cur
                 continue
-            n, mps = int(out["n_feat"][s]), []
-            for i in range(n):
-                f = Feature(out["feat_uv"][s, i, 0], out["feat_uv"][s, i, 1])
-                mid = int(out["feat_mp_id"][s, i])
-                if mid >= 0:                                                          # a map point BuildInitMap created (Map::InsertMapPoint)
-                    c.all_mps[mid] = f.mp = MapPoint(mid, out["feat_mp_pos"][s, i])
-                    c.next_mp_id = max(c.next_mp_id, mid + 1)
-                    mps.append(f.mp)
-                c.cur.feats.append(f)
-            c.cur.right = [(x, y) if ok else None for (x, y), ok in zip(out["right_xy"][s, :n], out["right_ok"][s, :n])]
-            kf = KeyFrame(int(out["new_kf_id"][s]), c.cur)                            # insert_keyframe(), INITING branch, with the device's id and pose
-            c.next_kf_id = kf.id + 1
-            for f in kf.feats:
-                f.kf = kf
-                if f.live() is not None:
-                    f.mp.obs.append(f)
-            kf.pose = out["new_kf_pose"][s].copy()
-            c.ref_kf = kf
-            c.cur.rel = np.eye(4)
-            c.kf_frames.append(c.cur.id)
-            c.backend_new_keyframe(kf)
+            self.adopt_keyframe(s, out)                                               # insert_keyframe()'s INITING branch: every map point is BuildInitMap's
             c.status = TRACKING_GOOD
-            c.poses.append(p7_of(mm(c.cur.rel, T_of(c.ref_kf.pose))))
-            c.last = c.cur
-            self.slots[s] = mps
             self.on_device[s] = True
             self.armed[s] = False                                                     # a later restart arms the stream again
             if resync:

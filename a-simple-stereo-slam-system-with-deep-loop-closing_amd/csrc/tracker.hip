@@ -75,27 +75,49 @@ __device__ __forceinline__ int block_rank(bool flag, int* s_w, int& total) {
     return before + inWave;
 }
 
+// ---- the pieces the step, the key-frame turn and StereoInit are built from: each rule below has this one definition ----
+// stream s's image buffer `slot` (rows packed at `cols` bytes; every buffer starts on a 256-byte boundary)
+__device__ __forceinline__ uint8_t* trk_image(const TrkArgs& a, int s, int slot) { return a.img + (size_t)slot * a.imgSel + (size_t)s * a.imgBytes; }
+
+// copy block `band` (blockIdx.x - 1 in trk_copy_grid) moves its TRK_COPY_ROWS rows of one stream's image: 4-byte words when the widths and THIS source's base allow it
+__device__ __forceinline__ void copy_image_rows(const TrkArgs& a, int band, const uint8_t* src, int step, uint8_t* dst) {
+    const int t = threadIdx.x, r0 = band * TRK_COPY_ROWS, r1 = min(r0 + TRK_COPY_ROWS, a.rows);
+    if (((a.cols | step) & 3) == 0 && (((size_t)src) & 3) == 0) {
+        const int w4 = a.cols >> 2;
+        for (int r = r0; r < r1; r++) {
+            const uint32_t* sp = reinterpret_cast<const uint32_t*>(src + (size_t)r * step);
+            uint32_t* dp = reinterpret_cast<uint32_t*>(dst + (size_t)r * a.cols);
+            for (int x = t; x < w4; x += TRK_NT) dp[x] = sp[x];
+        }
+    } else {
+        for (int r = r0; r < r1; r++)
+            for (int x = t; x < a.cols; x += TRK_NT) dst[(size_t)r * a.cols + x] = src[(size_t)r * step + x];
+    }
+}
+
+// Tcw = rel * T(ref pose), one thread.  (The step forms this product around its own T(ref pose): its tail needs that again, its head 28 VGPRs more here)
+__device__ __forceinline__ void tcw_of(const double* rel, const double* ref_pose, double* Tcw) {
+    double Tref[16];
+    se3_T_of(ref_pose, Tref); se3_mm(rel, Tref, Tcw);
+}
+
+// q = mv(R, p) + t of the 4 x 4 T: a landmark into the camera frame, a triangulated point into the world
+__device__ __forceinline__ void se3_apply(const double* T, const double* p, double* q) {
+    for (int r = 0; r < 3; r++) q[r] = dadd(dadd(dadd(dmul(T[4 * r], p[0]), dmul(T[4 * r + 1], p[1])), dmul(T[4 * r + 2], p[2])), T[4 * r + 3]);
+}
+// camera2pixel, rounded to the float LK starts from: (fx pc.x / pc.z + cx, fy pc.y / pc.z + cy).  A right camera shifts pc first (k_kf_head)
+__device__ __forceinline__ void pixel_of(const TrkArgs& a, const double* pc, float& u, float& v) {
+    u = __double2float_rn(dadd(ddiv(dmul(a.fx, pc[0]), pc[2]), a.cx));
+    v = __double2float_rn(dadd(ddiv(dmul(a.fy, pc[1]), pc[2]), a.cy));
+}
+
 // ---- head: blockIdx.x == 0 predicts (rule 1) for stream blockIdx.y; the other blocks copy the stream's new image into its free buffer ----
 __global__ __launch_bounds__(TRK_NT) void k_trk_head(TrkArgs a) {
     const int s = blockIdx.y, t = threadIdx.x;
     const TrkState& st = a.st[s];
     const bool idle = st.frozen != 0;
     if (blockIdx.x > 0) {
-        if (idle || st.overflow) return;
-        const int r0 = (blockIdx.x - 1) * TRK_COPY_ROWS, r1 = min(r0 + TRK_COPY_ROWS, a.rows);
-        const uint8_t* src = a.left + (size_t)s * a.stride;
-        uint8_t* dst = a.img + (size_t)(1 - st.slot) * a.imgSel + (size_t)s * a.imgBytes;
-        if (((a.cols | a.step) & 3) == 0 && (((size_t)src) & 3) == 0) {
-            const int w4 = a.cols >> 2;
-            for (int r = r0; r < r1; r++) {
-                const uint32_t* sp = reinterpret_cast<const uint32_t*>(src + (size_t)r * a.step);
-                uint32_t* dp = reinterpret_cast<uint32_t*>(dst + (size_t)r * a.cols);
-                for (int x = t; x < w4; x += TRK_NT) dp[x] = sp[x];
-            }
-        } else {
-            for (int r = r0; r < r1; r++)
-                for (int x = t; x < a.cols; x += TRK_NT) dst[(size_t)r * a.cols + x] = src[(size_t)r * a.step + x];
-        }
+        if (!idle && !st.overflow) copy_image_rows(a, blockIdx.x - 1, a.left + (size_t)s * a.stride, a.step, trk_image(a, s, 1 - st.slot));
         return;
     }
     if (idle) {
@@ -132,13 +154,10 @@ __global__ __launch_bounds__(TRK_NT) void k_trk_head(TrkArgs a) {
         const float x = a.xy[(fb + i) * 2], y = a.xy[(fb + i) * 2 + 1];
         float u = x, v = y;
         const int l = a.lm[fb + i];
-        if (l >= 0 && !outl[l]) {                         // world2pixel: pc = mv(R, pw) + t; (fx pc.x / pc.z + cx, fy pc.y / pc.z + cy)
-            const double px = pos[3 * l], py = pos[3 * l + 1], pz = pos[3 * l + 2];
+        if (l >= 0 && !outl[l]) {                         // world2pixel of the left camera
             double pc[3];
-            for (int r = 0; r < 3; r++)
-                pc[r] = dadd(dadd(dadd(dmul(sT[4 * r], px), dmul(sT[4 * r + 1], py)), dmul(sT[4 * r + 2], pz)), sT[4 * r + 3]);
-            u = __double2float_rn(dadd(ddiv(dmul(a.fx, pc[0]), pc[2]), a.cx));
-            v = __double2float_rn(dadd(ddiv(dmul(a.fy, pc[1]), pc[2]), a.cy));
+            se3_apply(sT, pos + 3 * l, pc);
+            pixel_of(a, pc, u, v);
         }
         a.p0[(fb + i) * 2] = x; a.p0[(fb + i) * 2 + 1] = y;
         a.p1[(fb + i) * 2] = u; a.p1[(fb + i) * 2 + 1] = v;
@@ -257,12 +276,20 @@ __device__ __forceinline__ bool kf_eligible(const TrkState& st) { return st.froz
 // cvRound(float) = rint, ties to even; saturates far outside the image, where the clip below gives the same rectangle
 __device__ __forceinline__ int cv_round(float v) { return __float2int_rn(v); }
 
+// block blockIdx.x of a mask kernel owns rows [r0, r1) of stream blockIdx.y's mask; returns the band's byte count
+__device__ __forceinline__ int mask_band(const TrkArgs& a, int& r0, int& r1) { r0 = blockIdx.x * MASK_ROWS; r1 = min(r0 + MASK_ROWS, a.rows); return (r1 - r0) * a.cols; }
+// the band's nb bytes (row-major, `cols` wide) into the stream's mask: band[k], or `fill` everywhere when there is no band
+__device__ __forceinline__ void store_mask_band(const TrkArgs& a, uint8_t* masks, int step, size_t stride, int r0, int nb, const uint8_t* band, uint8_t fill) {
+    uint8_t* dst = masks + (size_t)blockIdx.y * stride;
+    for (int k = threadIdx.x; k < nb; k += TRK_NT) dst[(size_t)(r0 + k / a.cols) * step + k % a.cols] = band ? band[k] : fill;
+}
+
 // ---- masks: block (x, s) holds MASK_ROWS rows of stream s's mask in LDS: 255, then 0 under every rectangle, then one coalesced store ----
 __global__ __launch_bounds__(TRK_NT) void k_kf_masks(TrkArgs a, uint8_t* masks, int step, size_t stride) {
     extern __shared__ uint8_t s_band[];                  // MASK_ROWS x cols
     const int s = blockIdx.y, t = threadIdx.x, lane = t & 63, wv = t >> 6;
     const TrkState& st = a.st[s];
-    const int r0 = blockIdx.x * MASK_ROWS, r1 = min(r0 + MASK_ROWS, a.rows), nb = (r1 - r0) * a.cols;
+    int r0, r1; const int nb = mask_band(a, r0, r1);
     const bool el = kf_eligible(st);
     for (int k = t; k < nb; k += TRK_NT) s_band[k] = el ? 255 : 0;
     __syncthreads();
@@ -279,8 +306,64 @@ __global__ __launch_bounds__(TRK_NT) void k_kf_masks(TrkArgs a, uint8_t* masks, 
         }
     }
     __syncthreads();
-    uint8_t* dst = masks + (size_t)s * stride;
-    for (int k = t; k < nb; k += TRK_NT) dst[(size_t)(r0 + k / a.cols) * step + k % a.cols] = s_band[k];
+    store_mask_band(a, masks, step, stride, r0, nb, s_band, 0);
+}
+
+// one feature's row of a turn's or an init's outputs: its map point (id -1, position 0 = none), its left pixel, its right match
+__device__ __forceinline__ void write_feature_row(const TrkArgs& a, const KfArgs& k, size_t fb, int i, int64_t id, const double* p, bool rok) {
+    k.featMpId[fb + i] = id; k.featTag[fb + i] = i; k.featFlags[fb + i] = 0; k.rightOk[fb + i] = rok ? 1 : 0;
+    for (int r = 0; r < 3; r++) k.featMpPos[(fb + i) * 3 + r] = p[r];
+    k.featUv[(fb + i) * 2] = a.kfP0[(fb + i) * 2]; k.featUv[(fb + i) * 2 + 1] = a.kfP0[(fb + i) * 2 + 1];
+    k.rightXy[(fb + i) * 2] = a.kfNxt[(fb + i) * 2]; k.rightXy[(fb + i) * 2 + 1] = a.kfNxt[(fb + i) * 2 + 1];
+}
+
+// feature f of the scratch tables: triangulate its left pixel and right match in the left camera's frame when `attempt`, store the point and whether it stands
+__device__ __forceinline__ bool triangulate_feature(const TrkArgs& a, double baseline, size_t f, bool attempt, double* X) {
+    bool tri = false; X[0] = 0; X[1] = 0; X[2] = 0;
+    if (attempt) {
+        const double ul = a.kfP0[f * 2], vl = a.kfP0[f * 2 + 1], ur = a.kfNxt[f * 2], vr = a.kfNxt[f * 2 + 1];
+        const double P[2][12] = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0},
+                                 {1, 0, 0, -baseline, 0, 1, 0, 0, 0, 0, 1, 0}};                  // as match_tri.hip's k_triangulate
+        const double pt[2][2] = {{(ul - a.cx) / a.fx, (vl - a.cy) / a.fy}, {(ur - a.cx) / a.fx, (vr - a.cy) / a.fy}};
+        double ratio; tri_solve(P, pt, X, ratio);
+        tri = ratio < 1e-2 && X[2] > 0;
+    }
+    a.kfXyz[f * 3] = X[0]; a.kfXyz[f * 3 + 1] = X[1]; a.kfXyz[f * 3 + 2] = X[2]; a.kfTok[f] = tri ? 1 : 0;
+    return tri;
+}
+
+// what a turn or an init tells about stream s (thread 0): the new key-frame's id, feature and outlier counts, and the 8-int report
+__device__ __forceinline__ void write_report(const KfArgs& k, int s, int64_t kfId, int nFeatOut, int nOutlMp, int status, int frameId, int nNew, int nRight,
+                                             int nTri, int nFeat, int nLm) {
+    int32_t* rep = k.report + (size_t)s * 8;
+    k.newKfId[s] = kfId; k.nFeat[s] = nFeatOut; k.nOutlMp[s] = nOutlMp;
+    rep[0] = status; rep[1] = frameId; rep[2] = nNew; rep[3] = nRight; rep[4] = nTri; rep[5] = nFeat; rep[6] = nLm; rep[7] = 0;
+}
+
+// (uniform) no key-frame: no id, no features, and the table sizes the stream keeps
+__device__ __forceinline__ void refuse(const KfArgs& k, int s, const TrkState& st, int status, int frameId, int nNew, int nRight) {
+    if (threadIdx.x == 0) write_report(k, s, -1, 0, 0, status, frameId, nNew, nRight, 0, st.n_feat, st.n_lm);
+}
+
+// the rebuilt landmark table kfId / kfOutl / kfPos[0, nLm) becomes the stream's (all threads, after a barrier behind the last read of the old one)
+__device__ __forceinline__ void commit_landmarks(const TrkArgs& a, size_t lb, int nLm) {
+    for (int j = threadIdx.x; j < nLm; j += TRK_NT) {
+        a.lmId[lb + j] = a.kfId[lb + j]; a.lmOutl[lb + j] = a.kfOutl[lb + j];
+        for (int r = 0; r < 3; r++) a.lmPos[(lb + j) * 3 + r] = a.kfPos[(lb + j) * 3 + r];
+    }
+}
+
+// thread 0, last: frame frameId becomes key-frame ids[1] at `pose` and the stream's reference, cur.rel = I (:440), nTri map-point ids are spent,
+// the stream holds m features on nLm landmarks, runs again, and reports
+__device__ __forceinline__ void adopt_keyframe(const TrkArgs& a, const KfArgs& k, int s, const double* pose, int frameId, int nNew, int nRight, int nTri, int m,
+                                               int nLm, int nOutl) {
+    TrkState& st = a.st[s]; int64_t* ids = a.ids + (size_t)s * 3;
+    const int64_t kfId = ids[1];
+    for (int c = 0; c < 7; c++) { st.ref_pose[c] = pose[c]; k.newKfPose[(size_t)s * 7 + c] = pose[c]; }
+    for (int c = 0; c < 16; c++) st.last_rel[c] = (c % 5 == 0) ? 1.0 : 0.0;
+    ids[0] = kfId; ids[1] = kfId + 1; ids[2] += nTri;
+    st.ref_frame_id = frameId; st.n_feat = m; st.n_lm = nLm; st.n_outl = 0; st.frozen = 0; st.why = TRK_WHY_NONE;
+    write_report(k, s, kfId, m, nOutl, MYSLAM_OK, frameId, nNew, nRight, nTri, m, nLm);
 }
 
 // ---- turn head: blockIdx.x == 0 decides eligibility, appends the detected key-points and writes the right start points (rules a + b);
@@ -292,12 +375,7 @@ __global__ __launch_bounds__(TRK_NT) void k_kf_head(TrkArgs a, KfArgs k) {
     const int n = st.n_feat, nNew = min(max(k.nNew[s], 0), k.kpCap), m = n + nNew;
     const bool go = el && m <= a.cap;
     if (blockIdx.x > 0) {
-        if (!go) return;
-        const int r0 = (blockIdx.x - 1) * TRK_COPY_ROWS, r1 = min(r0 + TRK_COPY_ROWS, a.rows);
-        const uint8_t* src = k.right + (size_t)s * k.stride;
-        uint8_t* dst = a.img + (size_t)(1 - st.slot) * a.imgSel + (size_t)s * a.imgBytes;
-        for (int r = r0; r < r1; r++)
-            for (int x = t; x < a.cols; x += TRK_NT) dst[(size_t)r * a.cols + x] = src[(size_t)r * k.step + x];
+        if (go) copy_image_rows(a, blockIdx.x - 1, k.right + (size_t)s * k.stride, k.step, trk_image(a, s, 1 - st.slot));
         return;
     }
     if (!go) {
@@ -306,9 +384,7 @@ __global__ __launch_bounds__(TRK_NT) void k_kf_head(TrkArgs a, KfArgs k) {
     }
     __shared__ double sT[16];
     if (t == 0) {
-        double Tref[16];
-        se3_T_of(st.ref_pose, Tref);
-        se3_mm(st.last_rel, Tref, sT);                   // Tcw = cur.rel * T(ref pose), :340
+        tcw_of(st.last_rel, st.ref_pose, sT);            // :340
         a.kfSel[s] = 1 - st.slot; a.kfCounts[s] = m; a.kfCode[s] = KF_GO;
     }
     __syncthreads();
@@ -323,13 +399,10 @@ __global__ __launch_bounds__(TRK_NT) void k_kf_head(TrkArgs a, KfArgs k) {
         else { x = kps[i - n].x; y = kps[i - n].y; }
         float u = x, v = y;
         if (l >= 0 && !outl[l]) {                        // world2pixel of the RIGHT camera: pc = mv(R, pw) + t, then pc + (-baseline, 0, 0) (:342-349)
-            const double px = pos[3 * l], py = pos[3 * l + 1], pz = pos[3 * l + 2];
             double pc[3];
-            for (int r = 0; r < 3; r++)
-                pc[r] = dadd(dadd(dadd(dmul(sT[4 * r], px), dmul(sT[4 * r + 1], py)), dmul(sT[4 * r + 2], pz)), sT[4 * r + 3]);
-            pc[0] = dadd(pc[0], -k.baseline); pc[1] = dadd(pc[1], 0.0); pc[2] = dadd(pc[2], 0.0);
-            u = __double2float_rn(dadd(ddiv(dmul(a.fx, pc[0]), pc[2]), a.cx));
-            v = __double2float_rn(dadd(ddiv(dmul(a.fy, pc[1]), pc[2]), a.cy));
+            se3_apply(sT, pos + 3 * l, pc);
+            pc[0] = dadd(pc[0], -k.baseline); pc[1] = dadd(pc[1], 0.0); pc[2] = dadd(pc[2], 0.0);      // (the sums with 0.0 turn -0.0 into +0.0, as the hosts')
+            pixel_of(a, pc, u, v);
         }
         a.kfP0[(fb + i) * 2] = x; a.kfP0[(fb + i) * 2 + 1] = y;
         a.kfNxt[(fb + i) * 2] = u; a.kfNxt[(fb + i) * 2 + 1] = v;
@@ -342,23 +415,15 @@ __global__ __launch_bounds__(TRK_NT) void k_kf_tail(TrkArgs a, KfArgs k) {
     __shared__ double sTcw[16], sTwc[16];
     const int s = blockIdx.x, t = threadIdx.x;
     TrkState& st = a.st[s];
-    int32_t* rep = k.report + (size_t)s * 8;
     const int code = a.kfCode[s];
     const int n = st.n_feat, nNew = min(max(k.nNew[s], 0), k.kpCap), m = n + nNew, nLm = st.n_lm, nOutl = st.n_outl;
-    auto refuse = [&](int status) {                      // (uniform) no turn: the stream keeps every byte
-        if (t == 0) {
-            k.newKfId[s] = -1; k.nFeat[s] = 0; k.nOutlMp[s] = 0;
-            rep[0] = status; rep[1] = st.next_frame_id - 1; rep[2] = nNew; rep[3] = 0; rep[4] = 0; rep[5] = n; rep[6] = nLm; rep[7] = 0;
-        }
-    };
-    if (code != KF_GO) { refuse(code == KF_CAPACITY ? MYSLAM_ERR_CAPACITY : MYSLAM_TRACKER_NO_TURN); return; }
+    const int frameId = st.next_frame_id - 1;            // the frame the last step tracked
+    // no turn: the stream keeps every byte
+    if (code != KF_GO) { refuse(k, s, st, code == KF_CAPACITY ? MYSLAM_ERR_CAPACITY : MYSLAM_TRACKER_NO_TURN, frameId, nNew, 0); return; }
     const size_t fb = (size_t)s * a.cap, lb = (size_t)s * a.lmCap;
-    int64_t* ids = a.ids + (size_t)s * 3;
-    const int64_t nextMp = ids[2];
+    const int64_t nextMp = a.ids[(size_t)s * 3 + 2];
     if (t == 0) {
-        double Tref[16];
-        se3_T_of(st.ref_pose, Tref);
-        se3_mm(st.last_rel, Tref, sTcw);
+        tcw_of(st.last_rel, st.ref_pose, sTcw);
         se3_inv(sTcw, sTwc);                             // Twc of TriangulateNewPoints (:453)
     }
     for (int l = t; l < nLm; l += TRK_NT) { a.kfFirst[lb + l] = 0x7fffffff; a.kfMap[lb + l] = -1; }
@@ -377,17 +442,7 @@ __global__ __launch_bounds__(TRK_NT) void k_kf_tail(TrkArgs a, KfArgs k) {
         if (i < m) {
             l = i < n ? a.lm[fb + i] : -1;
             rok = a.kfSt[fb + i] != 0;
-            if (l < 0 && rok) {                          // expired() && mvpFeaturesRight[i] != nullptr (:458-459)
-                const double ul = a.kfP0[(fb + i) * 2], vl = a.kfP0[(fb + i) * 2 + 1], ur = a.kfNxt[(fb + i) * 2], vr = a.kfNxt[(fb + i) * 2 + 1];
-                const double P[2][12] = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0},
-                                         {1, 0, 0, -k.baseline, 0, 1, 0, 0, 0, 0, 1, 0}};      // as match_tri.hip's k_triangulate
-                const double pt[2][2] = {{(ul - a.cx) / a.fx, (vl - a.cy) / a.fy}, {(ur - a.cx) / a.fx, (vr - a.cy) / a.fy}};
-                double ratio;
-                tri_solve(P, pt, X, ratio);
-                tri = ratio < 1e-2 && X[2] > 0;
-            }
-            a.kfXyz[(fb + i) * 3] = X[0]; a.kfXyz[(fb + i) * 3 + 1] = X[1]; a.kfXyz[(fb + i) * 3 + 2] = X[2];
-            a.kfTok[fb + i] = tri ? 1 : 0;
+            tri = triangulate_feature(a, k.baseline, fb + i, l < 0 && rok, X);       // expired() && mvpFeaturesRight[i] != nullptr (:458-459)
             // (the minimum was formed by atomics in L2: read it there, not from a line this CU may still hold)
             opens = tri || (l >= 0 && __hip_atomic_load(&a.kfFirst[lb + l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == i);
         }
@@ -401,8 +456,7 @@ __global__ __launch_bounds__(TRK_NT) void k_kf_tail(TrkArgs a, KfArgs k) {
             double p[3] = {0, 0, 0};
             if (tri) {                                   // a new map point: id by rank, pos = mv(Twc.R, p) + Twc.t (:474-476)
                 id = nextMp + nTri + rt;
-                for (int r = 0; r < 3; r++)
-                    p[r] = dadd(dadd(dadd(dmul(sTwc[4 * r], X[0]), dmul(sTwc[4 * r + 1], X[1])), dmul(sTwc[4 * r + 2], X[2])), sTwc[4 * r + 3]);
+                se3_apply(sTwc, X, p);
             } else if (l >= 0) {
                 id = a.lmId[lb + l];
                 for (int r = 0; r < 3; r++) p[r] = a.lmPos[(lb + l) * 3 + r];
@@ -412,16 +466,11 @@ __global__ __launch_bounds__(TRK_NT) void k_kf_tail(TrkArgs a, KfArgs k) {
                 a.kfId[lb + slot] = id; a.kfOutl[lb + slot] = l >= 0 ? a.lmOutl[lb + l] : 0;
                 for (int r = 0; r < 3; r++) a.kfPos[(lb + slot) * 3 + r] = p[r];
             }
-            k.featMpId[fb + i] = id;
-            for (int r = 0; r < 3; r++) k.featMpPos[(fb + i) * 3 + r] = p[r];
-            k.featUv[(fb + i) * 2] = a.kfP0[(fb + i) * 2]; k.featUv[(fb + i) * 2 + 1] = a.kfP0[(fb + i) * 2 + 1];
-            k.featTag[fb + i] = i; k.featFlags[fb + i] = 0;
-            k.rightXy[(fb + i) * 2] = a.kfNxt[(fb + i) * 2]; k.rightXy[(fb + i) * 2 + 1] = a.kfNxt[(fb + i) * 2 + 1];
-            k.rightOk[fb + i] = rok ? 1 : 0;
+            write_feature_row(a, k, fb, i, id, p, rok);
         }
         nTri += tt; nSlots += ts; nRight += tr;
     }
-    if (nSlots > a.lmCap) { refuse(MYSLAM_ERR_CAPACITY); return; }       // uniform
+    if (nSlots > a.lmCap) { refuse(k, s, st, MYSLAM_ERR_CAPACITY, frameId, nNew, 0); return; }
     __syncthreads();                                     // kfMap, kfPos .. are complete; every read of the old tables is done
     // ---- commit ----
     for (int i = t; i < m; i += TRK_NT) {
@@ -430,21 +479,11 @@ __global__ __launch_bounds__(TRK_NT) void k_kf_tail(TrkArgs a, KfArgs k) {
         a.lm[fb + i] = slot >= 0 ? slot : (l >= 0 ? a.kfMap[lb + l] : -1);
         if (i >= n) { a.xy[(fb + i) * 2] = a.kfP0[(fb + i) * 2]; a.xy[(fb + i) * 2 + 1] = a.kfP0[(fb + i) * 2 + 1]; }
     }
-    for (int j = t; j < nSlots; j += TRK_NT) {
-        a.lmId[lb + j] = a.kfId[lb + j]; a.lmOutl[lb + j] = a.kfOutl[lb + j];
-        for (int r = 0; r < 3; r++) a.lmPos[(lb + j) * 3 + r] = a.kfPos[(lb + j) * 3 + r];
-    }
+    commit_landmarks(a, lb, nSlots);
     if (t != 0) return;
     double pose[7];
     se3_p7_of(sTcw, pose);                               // kf.pose = p7(cur.rel * T(ref pose)) (:433)
-    const int64_t kfId = ids[1];
-    for (int c = 0; c < 7; c++) { st.ref_pose[c] = pose[c]; k.newKfPose[(size_t)s * 7 + c] = pose[c]; }
-    for (int c = 0; c < 16; c++) st.last_rel[c] = (c % 5 == 0) ? 1.0 : 0.0;          // cur.rel = I (:440)
-    ids[0] = kfId; ids[1] = kfId + 1; ids[2] = nextMp + nTri;
-    st.ref_frame_id = st.next_frame_id - 1;
-    st.n_feat = m; st.n_lm = nSlots; st.n_outl = 0; st.frozen = 0; st.why = TRK_WHY_NONE;
-    k.newKfId[s] = kfId; k.nFeat[s] = m; k.nOutlMp[s] = nOutl;
-    rep[0] = MYSLAM_OK; rep[1] = st.ref_frame_id; rep[2] = nNew; rep[3] = nRight; rep[4] = nTri; rep[5] = m; rep[6] = nSlots; rep[7] = 0;
+    adopt_keyframe(a, k, s, pose, frameId, nNew, nRight, nTri, m, nSlots, nOutl);
 }
 
 // ---- the map moved under the tracker (back end, loop closer): landmarks and the reference pose follow their ids ----
@@ -484,29 +523,20 @@ __global__ __launch_bounds__(TRK_NT) void k_kf_set_image(TrkArgs a, const uint8_
     const bool on = select[s] != 0;
     const int slot = a.st[s].slot;
     if (blockIdx.x == 0) { if (t == 0) a.kfSel[s] = on ? slot : -1; return; }
-    if (!on) return;
-    const int r0 = (blockIdx.x - 1) * TRK_COPY_ROWS, r1 = min(r0 + TRK_COPY_ROWS, a.rows);
-    const uint8_t* src = imgs + (size_t)s * stride;
-    uint8_t* dst = a.img + (size_t)slot * a.imgSel + (size_t)s * a.imgBytes;
-    for (int r = r0; r < r1; r++)
-        for (int x = t; x < a.cols; x += TRK_NT) dst[(size_t)r * a.cols + x] = src[(size_t)r * step + x];
+    if (on) copy_image_rows(a, blockIdx.x - 1, imgs + (size_t)s * stride, step, trk_image(a, s, slot));
 }
 
 // =====================================================================================================================================
 // StereoInit (include/myslam_hip.h, myslam_tracker_init_*): Frontend::StereoInit (:282-295) with DetectFeatures' mask over an empty table
 // (:305-309), FindFeaturesInRight (:335-379), BuildInitMap (:385-417) and InsertKeyFrame's INITING branch (:427-428, :441-443) for every
-// INIT-ELIGIBLE stream.  Its own head and tail: the turn's kernels above keep their code, resources and outputs.
-__device__ __forceinline__ bool init_eligible(const TrkState& st) {
-    return st.frozen != 0 && st.status == TRK_INITING && st.why == TRK_WHY_NONE && st.overflow == 0;
-}
+// INIT-ELIGIBLE stream.  Its head and tail are kernels of their own (no landmark to project or to keep, a pose of I, the retry rule) over the
+// pieces the turn's kernels are made of.
+__device__ __forceinline__ bool init_eligible(const TrkState& st) { return st.frozen != 0 && st.status == TRK_INITING && st.why == TRK_WHY_NONE && st.overflow == 0; }
 
 // ---- masks: 255 everywhere for an init-eligible stream (no feature draws a rectangle), 0 otherwise; no LDS ----
 __global__ __launch_bounds__(TRK_NT) void k_init_masks(TrkArgs a, uint8_t* masks, int step, size_t stride) {
-    const int s = blockIdx.y, t = threadIdx.x;
-    const int r0 = blockIdx.x * MASK_ROWS, r1 = min(r0 + MASK_ROWS, a.rows), nb = (r1 - r0) * a.cols;
-    const uint8_t v = init_eligible(a.st[s]) ? 255 : 0;
-    uint8_t* dst = masks + (size_t)s * stride;
-    for (int k = t; k < nb; k += TRK_NT) dst[(size_t)(r0 + k / a.cols) * step + k % a.cols] = v;
+    int r0, r1; const int nb = mask_band(a, r0, r1);
+    store_mask_band(a, masks, step, stride, r0, nb, nullptr, init_eligible(a.st[blockIdx.y]) ? 255 : 0);
 }
 
 // ---- init head: blockIdx.x == 0 decides eligibility and writes the detected key-points as left pixels and right start points (rules a + b);
@@ -519,16 +549,9 @@ __global__ __launch_bounds__(TRK_NT) void k_init_head(TrkArgs a, KfArgs k, const
     const bool go = el && m <= a.cap;
     if (blockIdx.x > 0) {
         if (!go) return;
-        const int r0 = (blockIdx.x - 1) * TRK_COPY_ROWS, r1 = min(r0 + TRK_COPY_ROWS, a.rows);
-        const uint8_t* srcL = left + (size_t)s * k.stride;
-        const uint8_t* srcR = k.right + (size_t)s * k.stride;
-        uint8_t* dstL = a.img + (size_t)st.slot * a.imgSel + (size_t)s * a.imgBytes;
-        uint8_t* dstR = a.img + (size_t)(1 - st.slot) * a.imgSel + (size_t)s * a.imgBytes;
-        for (int r = r0; r < r1; r++)
-            for (int x = t; x < a.cols; x += TRK_NT) {
-                dstL[(size_t)r * a.cols + x] = srcL[(size_t)r * k.step + x];
-                dstR[(size_t)r * a.cols + x] = srcR[(size_t)r * k.step + x];
-            }
+        uint8_t *dstL = trk_image(a, s, st.slot), *dstR = trk_image(a, s, 1 - st.slot);      // (both before the first store: `slot` is read once)
+        copy_image_rows(a, blockIdx.x - 1, left + (size_t)s * k.stride, k.step, dstL);
+        copy_image_rows(a, blockIdx.x - 1, k.right + (size_t)s * k.stride, k.step, dstR);
         return;
     }
     if (t == 0) {
@@ -550,21 +573,13 @@ __global__ __launch_bounds__(TRK_NT) void k_init_tail(TrkArgs a, KfArgs k, int i
     __shared__ int s_w[TRK_NT / 64];
     const int s = blockIdx.x, t = threadIdx.x;
     TrkState& st = a.st[s];
-    int32_t* rep = k.report + (size_t)s * 8;
     const int code = a.kfCode[s];
     const int m = min(max(k.nNew[s], 0), k.kpCap);
-    auto refuse = [&](int status, int frameId, int nRight) { // (uniform) no key-frame
-        if (t == 0) {
-            k.newKfId[s] = -1; k.nFeat[s] = 0; k.nOutlMp[s] = 0;
-            rep[0] = status; rep[1] = frameId; rep[2] = m; rep[3] = nRight; rep[4] = 0; rep[5] = st.n_feat; rep[6] = st.n_lm; rep[7] = 0;
-        }
-    };
-    if (code == KF_NO_TURN) { refuse(MYSLAM_TRACKER_NO_TURN, st.next_frame_id - 1, 0); return; }
+    if (code == KF_NO_TURN) { refuse(k, s, st, MYSLAM_TRACKER_NO_TURN, st.next_frame_id - 1, m, 0); return; }
     const int frameId = st.next_frame_id;                    // the Frame that GrabStereoImage constructed
-    if (code != KF_GO) { refuse(MYSLAM_ERR_CAPACITY, frameId, 0); return; }
+    if (code != KF_GO) { refuse(k, s, st, MYSLAM_ERR_CAPACITY, frameId, m, 0); return; }
     const size_t fb = (size_t)s * a.cap, lb = (size_t)s * a.lmCap;
-    int64_t* ids = a.ids + (size_t)s * 3;
-    const int64_t nextMp = ids[2];
+    const int64_t nextMp = a.ids[(size_t)s * 3 + 2];
     // rule d (triangulation in feature order, slot = rank among the successes), 256 features at a time
     int nTri = 0, nRight = 0;
     for (int base = 0; base < m; base += TRK_NT) {
@@ -573,17 +588,7 @@ __global__ __launch_bounds__(TRK_NT) void k_init_tail(TrkArgs a, KfArgs k, int i
         double X[3] = {0, 0, 0};
         if (i < m) {
             rok = a.kfSt[fb + i] != 0;
-            if (rok) {                                       // mvpFeaturesRight[i] != nullptr (:394)
-                const double ul = a.kfP0[(fb + i) * 2], vl = a.kfP0[(fb + i) * 2 + 1], ur = a.kfNxt[(fb + i) * 2], vr = a.kfNxt[(fb + i) * 2 + 1];
-                const double P[2][12] = {{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0},
-                                         {1, 0, 0, -k.baseline, 0, 1, 0, 0, 0, 0, 1, 0}};      // as k_kf_tail
-                const double pt[2][2] = {{(ul - a.cx) / a.fx, (vl - a.cy) / a.fy}, {(ur - a.cx) / a.fx, (vr - a.cy) / a.fy}};
-                double ratio;
-                tri_solve(P, pt, X, ratio);
-                tri = ratio < 1e-2 && X[2] > 0;
-            }
-            a.kfXyz[(fb + i) * 3] = X[0]; a.kfXyz[(fb + i) * 3 + 1] = X[1]; a.kfXyz[(fb + i) * 3 + 2] = X[2];
-            a.kfTok[fb + i] = tri ? 1 : 0;
+            tri = triangulate_feature(a, k.baseline, fb + i, rok, X);            // mvpFeaturesRight[i] != nullptr (:394)
         }
         int tt, tr;
         const int rt = block_rank(tri, s_w, tt);
@@ -594,44 +599,31 @@ __global__ __launch_bounds__(TRK_NT) void k_init_tail(TrkArgs a, KfArgs k, int i
             const int64_t id = tri ? nextMp + slot : -1;
             if (!tri) { X[0] = 0; X[1] = 0; X[2] = 0; }
             if (tri && slot < a.lmCap) {                     // (beyond lmCap the init is refused below); the key-frame's pose is I: pos = X itself
-                a.kfId[lb + slot] = id;
+                a.kfId[lb + slot] = id; a.kfOutl[lb + slot] = 0;
                 for (int r = 0; r < 3; r++) a.kfPos[(lb + slot) * 3 + r] = X[r];
             }
-            k.featMpId[fb + i] = id;
-            for (int r = 0; r < 3; r++) k.featMpPos[(fb + i) * 3 + r] = X[r];
-            k.featUv[(fb + i) * 2] = a.kfP0[(fb + i) * 2]; k.featUv[(fb + i) * 2 + 1] = a.kfP0[(fb + i) * 2 + 1];
-            k.featTag[fb + i] = i; k.featFlags[fb + i] = 0;
-            k.rightXy[(fb + i) * 2] = a.kfNxt[(fb + i) * 2]; k.rightXy[(fb + i) * 2 + 1] = a.kfNxt[(fb + i) * 2 + 1];
-            k.rightOk[fb + i] = rok ? 1 : 0;
+            write_feature_row(a, k, fb, i, id, X, rok);
         }
         nTri += tt; nRight += tr;
     }
     if (nRight < initGood) {                                 // uniform.  StereoInit returns false (:285-287): only the Frame's id was spent
-        refuse(MYSLAM_TRACKER_INIT_RETRY, frameId, nRight);
+        refuse(k, s, st, MYSLAM_TRACKER_INIT_RETRY, frameId, m, nRight);
         if (t == 0) st.next_frame_id = frameId + 1;
         return;
     }
-    if (nTri > a.lmCap) { refuse(MYSLAM_ERR_CAPACITY, frameId, nRight); return; }      // uniform
+    if (nTri > a.lmCap) { refuse(k, s, st, MYSLAM_ERR_CAPACITY, frameId, m, nRight); return; }
     __syncthreads();                                         // kfSlot, kfPos, kfId are complete
     // ---- commit ----
     for (int i = t; i < m; i += TRK_NT) {
         a.lm[fb + i] = a.kfSlot[fb + i];
         a.xy[(fb + i) * 2] = a.kfP0[(fb + i) * 2]; a.xy[(fb + i) * 2 + 1] = a.kfP0[(fb + i) * 2 + 1];
     }
-    for (int j = t; j < nTri; j += TRK_NT) {
-        a.lmId[lb + j] = a.kfId[lb + j]; a.lmOutl[lb + j] = 0;
-        for (int r = 0; r < 3; r++) a.lmPos[(lb + j) * 3 + r] = a.kfPos[(lb + j) * 3 + r];
-    }
+    commit_landmarks(a, lb, nTri);
     if (t != 0) return;
-    const int64_t kfId = ids[1];
-    for (int c = 0; c < 7; c++) { const double p = c == 3 ? 1.0 : 0.0; st.ref_pose[c] = p; k.newKfPose[(size_t)s * 7 + c] = p; }
-    for (int c = 0; c < 16; c++) { const double e = (c % 5 == 0) ? 1.0 : 0.0; st.last_rel[c] = e; st.rel_motion[c] = e; }
-    ids[0] = kfId; ids[1] = kfId + 1; ids[2] = nextMp + nTri;
-    st.ref_frame_id = frameId; st.next_frame_id = frameId + 1;
-    st.n_feat = m; st.n_lm = nTri; st.n_outl = 0;
-    st.status = TRK_GOOD; st.frozen = 0; st.why = TRK_WHY_NONE; st.idsValid = 1;
-    k.newKfId[s] = kfId; k.nFeat[s] = m; k.nOutlMp[s] = 0;
-    rep[0] = MYSLAM_OK; rep[1] = frameId; rep[2] = m; rep[3] = nRight; rep[4] = nTri; rep[5] = m; rep[6] = nTri; rep[7] = 0;
+    const double ident[7] = {0, 0, 0, 1, 0, 0, 0};
+    adopt_keyframe(a, k, s, ident, frameId, m, nRight, nTri, m, nTri, 0);
+    for (int c = 0; c < 16; c++) st.rel_motion[c] = (c % 5 == 0) ? 1.0 : 0.0;
+    st.next_frame_id = frameId + 1; st.status = TRK_GOOD; st.idsValid = 1;
 }
 
 }  // namespace myslam_hip
@@ -674,6 +666,46 @@ static int trk_alloc_all(myslam_tracker* h) {
     if ((rc = upload_table(a.st, init.data(), S * sizeof(TrkState))) || (rc = upload_table(a.counts, zeros.data(), S * sizeof(int32_t)))) return rc;
     const std::vector<int64_t> zeros64(S * 3, 0);
     if ((rc = upload_table(a.kfCounts, zeros.data(), S * sizeof(int32_t))) || (rc = upload_table(a.ids, zeros64.data(), S * 3 * sizeof(int64_t)))) return rc;
+    return MYSLAM_OK;
+}
+
+// a batch of S images, `step` bytes between rows and `stride` between images, does not hold rows x cols each
+static bool image_args_bad(const myslam_tracker* h, int step, size_t stride) { return step < h->cols || stride < (size_t)(h->rows - 1) * step + h->cols; }
+// stream s's state as the device has it once the handle's stream has drained (synchronous)
+static int trk_fetch_state(myslam_tracker* h, int s, TrkState& hs) { return copy_sync(&hs, h->a.st + s, sizeof(TrkState), hipMemcpyDeviceToHost, h->stream); }
+// grid of the kernels that copy images: per stream, block 0 for the rules and one block per TRK_COPY_ROWS rows (copy_image_rows)
+static dim3 trk_copy_grid(const myslam_tracker* h) { return dim3(1 + (h->rows + TRK_COPY_ROWS - 1) / TRK_COPY_ROWS, h->S); }
+
+// the arguments myslam_tracker_keyframe_batch and myslam_tracker_init_batch share -> k; false when one of them is invalid
+static bool kf_args(const myslam_tracker* h, const uint8_t* d_right, int step, size_t stride, const myslam_keypoint* d_new_kps, const int32_t* d_n_new, int kp_cap,
+                    double baseline, int64_t* d_new_kf_id, double* d_new_kf_pose, int64_t* d_feat_mp_id, double* d_feat_mp_pos, float* d_feat_uv,
+                    int32_t* d_feat_tag, uint8_t* d_feat_flags, int32_t* d_n_feat, int64_t* d_outlier_mp_id, int32_t* d_n_outlier_mp, float* d_right_xy,
+                    uint8_t* d_right_ok, int32_t* d_report, KfArgs& k) {
+    if (!h || !d_right || !d_new_kps || !d_n_new || !d_new_kf_id || !d_new_kf_pose || !d_feat_mp_id || !d_feat_mp_pos || !d_feat_uv || !d_feat_tag ||
+        !d_feat_flags || !d_n_feat || !d_outlier_mp_id || !d_n_outlier_mp || !d_right_xy || !d_right_ok || !d_report || image_args_bad(h, step, stride) || kp_cap < 1)
+        return false;
+    k = KfArgs{d_right, step, stride, d_new_kps, d_n_new, kp_cap, baseline, d_new_kf_id, d_new_kf_pose, d_feat_mp_id, d_feat_mp_pos, d_feat_uv, d_feat_tag,
+               d_feat_flags, d_n_feat, d_outlier_mp_id, d_n_outlier_mp, d_right_xy, d_right_ok, d_report};
+    return true;
+}
+
+// head -> pyramid levels -> LK from the left image's buffer into the right image's -> tail: a key-frame turn (d_left null: the left image and
+// its levels are the last step's, buffer `slot`) or StereoInit (d_left: its levels go to buffer `slot` first) (:358-361)
+static int trk_run_turn(myslam_tracker* h, const KfArgs& k, const uint8_t* d_left, int init_good) {
+    const TrkArgs& a = h->a;
+    hipStream_t st = h->stream;
+    const int S = h->S;
+    const size_t pyrSel = (size_t)S * h->pyrBytes;
+    if (d_left) hipLaunchKernelGGL(k_init_head, trk_copy_grid(h), dim3(TRK_NT), 0, st, a, k, d_left, h->d_selLeft);
+    else hipLaunchKernelGGL(k_kf_head, trk_copy_grid(h), dim3(TRK_NT), 0, st, a, k);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    int rc;
+    if (d_left && (rc = lk_bank_pyramid(h->lk, d_left, k.step, k.stride, h->d_pyr, S, h->d_selLeft, pyrSel))) return rc;
+    if ((rc = lk_bank_pyramid(h->lk, k.right, k.step, k.stride, h->d_pyr, S, a.kfSel, pyrSel))) return rc;
+    if ((rc = lk_bank_track(h->lk, a.img, h->cols, a.imgBytes, h->d_pyr, S, a.kfSel, a.imgSel, pyrSel, a.kfP0, a.kfNxt, a.kfCounts, h->cap, a.kfSt))) return rc;
+    if (d_left) hipLaunchKernelGGL(k_init_tail, dim3(S), dim3(TRK_NT), 0, st, a, k, init_good);
+    else hipLaunchKernelGGL(k_kf_tail, dim3(S), dim3(TRK_NT), 0, st, a, k);
+    MYSLAM_HIP_CHECK(hipGetLastError());
     return MYSLAM_OK;
 }
 
@@ -730,8 +762,7 @@ int myslam_tracker_set_frame(myslam_tracker* h, int s, const float* feat_xy, con
     hipStream_t st = h->stream;
     TrkArgs& a = h->a;
     TrkState hs;
-    int rc = copy_sync(&hs, a.st + s, sizeof(TrkState), hipMemcpyDeviceToHost, st);
-    if (rc) return rc;
+    if (int rc = trk_fetch_state(h, s, hs)) return rc;
     memcpy(hs.ref_pose, ref_pose7, sizeof(double) * 7); memcpy(hs.last_rel, last_rel16, sizeof(double) * 16); memcpy(hs.rel_motion, rel_motion16, sizeof(double) * 16);
     hs.ref_frame_id = ref_frame_id; hs.next_frame_id = next_frame_id; hs.status = status; hs.kf_every = kf_every;
     hs.frozen = 0; hs.n_outl = 0; hs.overflow = fits ? 0 : 1;
@@ -754,7 +785,7 @@ int myslam_tracker_set_frame(myslam_tracker* h, int s, const float* feat_xy, con
         for (int r = 0; r < h->rows; r++) memcpy(packed.data() + (size_t)r * h->cols, prev_image + (size_t)r * image_step, h->cols);
         uint8_t* d_img = a.img + (size_t)hs.slot * a.imgSel + (size_t)s * a.imgBytes;
         MYSLAM_HIP_CHECK(hipMemcpyAsync(d_img, packed.data(), packed.size(), hipMemcpyHostToDevice, st));
-        if ((rc = lk_bank_pyramid(h->lk, d_img, h->cols, a.imgBytes, h->d_pyr + ((size_t)hs.slot * h->S + s) * h->pyrBytes, 1, nullptr, 0))) return rc;
+        if (int rc = lk_bank_pyramid(h->lk, d_img, h->cols, a.imgBytes, h->d_pyr + ((size_t)hs.slot * h->S + s) * h->pyrBytes, 1, nullptr, 0)) return rc;
         h->hasImage[s] = 1;
     }
     MYSLAM_HIP_CHECK(hipMemcpyAsync(a.st + s, &hs, sizeof(TrkState), hipMemcpyHostToDevice, st));
@@ -770,8 +801,7 @@ int myslam_tracker_get_frame(myslam_tracker* h, int s, float* feat_xy, int32_t* 
     hipStream_t st = h->stream;
     TrkArgs& a = h->a;
     TrkState hs;
-    int rc = copy_sync(&hs, a.st + s, sizeof(TrkState), hipMemcpyDeviceToHost, st);
-    if (rc) return rc;
+    if (int rc = trk_fetch_state(h, s, hs)) return rc;
     const size_t fb = (size_t)s * h->cap, lb = (size_t)s * h->lmCap;
     if (feat_xy && hs.n_feat) MYSLAM_HIP_CHECK(hipMemcpyAsync(feat_xy, a.xy + fb * 2, sizeof(float) * 2 * hs.n_feat, hipMemcpyDeviceToHost, st));
     if (feat_landmark && hs.n_feat) MYSLAM_HIP_CHECK(hipMemcpyAsync(feat_landmark, a.lm + fb, sizeof(int32_t) * hs.n_feat, hipMemcpyDeviceToHost, st));
@@ -803,13 +833,13 @@ int myslam_tracker_get_frame(myslam_tracker* h, int s, float* feat_xy, int32_t* 
 }
 
 int myslam_tracker_step_batch(myslam_tracker* h, const uint8_t* d_left, int step, size_t stride, myslam_tracker_result* d_results) {
-    if (!h || !d_left || step < h->cols || stride < (size_t)(h->rows - 1) * step + h->cols || !d_results) return MYSLAM_ERR_INVALID;
+    if (!h || !d_left || image_args_bad(h, step, stride) || !d_results) return MYSLAM_ERR_INVALID;
     TrkArgs a = h->a;
     a.left = d_left; a.step = step; a.stride = stride; a.res = d_results;
     hipStream_t st = h->stream;
     const int S = h->S;
     const size_t pyrSel = (size_t)S * h->pyrBytes;
-    hipLaunchKernelGGL(k_trk_head, dim3(1 + (h->rows + TRK_COPY_ROWS - 1) / TRK_COPY_ROWS, S), dim3(TRK_NT), 0, st, a);
+    hipLaunchKernelGGL(k_trk_head, trk_copy_grid(h), dim3(TRK_NT), 0, st, a);
     MYSLAM_HIP_CHECK(hipGetLastError());
     int rc;
     if ((rc = lk_bank_pyramid(h->lk, d_left, step, stride, h->d_pyr, S, a.sel, pyrSel))) return rc;
@@ -849,8 +879,7 @@ int myslam_tracker_set_ids(myslam_tracker* h, int s, const int64_t* landmark_id,
     hipStream_t st = h->stream;
     TrkArgs& a = h->a;
     TrkState hs;
-    int rc = copy_sync(&hs, a.st + s, sizeof(TrkState), hipMemcpyDeviceToHost, st);
-    if (rc) return rc;
+    if (int rc = trk_fetch_state(h, s, hs)) return rc;
     if (n_landmarks != hs.n_lm) return MYSLAM_ERR_INVALID;
     for (int l = 0; l < n_landmarks; l++) if (landmark_id[l] < 0 || landmark_id[l] >= next_mp_id) return MYSLAM_ERR_INVALID;
     const int64_t ids[3] = {ref_kf_id, next_kf_id, next_mp_id};
@@ -868,12 +897,11 @@ int myslam_tracker_get_ids(myslam_tracker* h, int s, int64_t* landmark_id, int* 
     hipStream_t st = h->stream;
     TrkArgs& a = h->a;
     TrkState hs;
-    int rc = copy_sync(&hs, a.st + s, sizeof(TrkState), hipMemcpyDeviceToHost, st);
-    if (rc) return rc;
+    if (int rc = trk_fetch_state(h, s, hs)) return rc;
     int64_t ids[3];
     if (landmark_id && hs.n_lm)
         MYSLAM_HIP_CHECK(hipMemcpyAsync(landmark_id, a.lmId + (size_t)s * h->lmCap, sizeof(int64_t) * hs.n_lm, hipMemcpyDeviceToHost, st));
-    if ((rc = copy_sync(ids, a.ids + (size_t)s * 3, sizeof(ids), hipMemcpyDeviceToHost, st))) return rc;
+    if (int rc = copy_sync(ids, a.ids + (size_t)s * 3, sizeof(ids), hipMemcpyDeviceToHost, st)) return rc;
     if (n_landmarks) *n_landmarks = hs.n_lm;
     if (ref_kf_id) *ref_kf_id = ids[0];
     if (next_kf_id) *next_kf_id = ids[1];
@@ -883,7 +911,7 @@ int myslam_tracker_get_ids(myslam_tracker* h, int s, int64_t* landmark_id, int* 
 }
 
 int myslam_tracker_keyframe_masks(myslam_tracker* h, uint8_t* d_masks, int step, size_t stride) {
-    if (!h || !d_masks || step < h->cols || stride < (size_t)(h->rows - 1) * step + h->cols) return MYSLAM_ERR_INVALID;
+    if (!h || !d_masks || image_args_bad(h, step, stride)) return MYSLAM_ERR_INVALID;
     if ((size_t)MASK_ROWS * h->cols > 65536) return MYSLAM_ERR_UNSUPPORTED;           // one block's band of the mask lives in LDS
     hipLaunchKernelGGL(k_kf_masks, dim3((h->rows + MASK_ROWS - 1) / MASK_ROWS, h->S), dim3(TRK_NT), (size_t)MASK_ROWS * h->cols, h->stream, h->a, d_masks, step,
                        stride);
@@ -899,25 +927,11 @@ int myslam_tracker_keyframe_batch(myslam_tracker* h, const uint8_t* d_right, int
                                   const int32_t* d_n_new, int kp_cap, double baseline, int64_t* d_new_kf_id, double* d_new_kf_pose, int64_t* d_feat_mp_id,
                                   double* d_feat_mp_pos, float* d_feat_uv, int32_t* d_feat_tag, uint8_t* d_feat_flags, int32_t* d_n_feat,
                                   int64_t* d_outlier_mp_id, int32_t* d_n_outlier_mp, float* d_right_xy, uint8_t* d_right_ok, int32_t* d_report) {
-    if (!h || !d_right || !d_new_kps || !d_n_new || !d_new_kf_id || !d_new_kf_pose || !d_feat_mp_id || !d_feat_mp_pos || !d_feat_uv || !d_feat_tag ||
-        !d_feat_flags || !d_n_feat || !d_outlier_mp_id || !d_n_outlier_mp || !d_right_xy || !d_right_ok || !d_report)
+    KfArgs k;
+    if (!kf_args(h, d_right, step, stride, d_new_kps, d_n_new, kp_cap, baseline, d_new_kf_id, d_new_kf_pose, d_feat_mp_id, d_feat_mp_pos, d_feat_uv, d_feat_tag,
+                 d_feat_flags, d_n_feat, d_outlier_mp_id, d_n_outlier_mp, d_right_xy, d_right_ok, d_report, k))
         return MYSLAM_ERR_INVALID;
-    if (step < h->cols || stride < (size_t)(h->rows - 1) * step + h->cols || kp_cap < 1) return MYSLAM_ERR_INVALID;
-    const TrkArgs& a = h->a;
-    const KfArgs k{d_right, step, stride, d_new_kps, d_n_new, kp_cap, baseline, d_new_kf_id, d_new_kf_pose, d_feat_mp_id, d_feat_mp_pos, d_feat_uv, d_feat_tag,
-                   d_feat_flags, d_n_feat, d_outlier_mp_id, d_n_outlier_mp, d_right_xy, d_right_ok, d_report};
-    hipStream_t st = h->stream;
-    const int S = h->S;
-    const size_t pyrSel = (size_t)S * h->pyrBytes;
-    hipLaunchKernelGGL(k_kf_head, dim3(1 + (h->rows + TRK_COPY_ROWS - 1) / TRK_COPY_ROWS, S), dim3(TRK_NT), 0, st, a, k);
-    MYSLAM_HIP_CHECK(hipGetLastError());
-    int rc;
-    // the right image's levels into the stream's FREE buffer, then LK from the left image (buffer `slot`) into it (:358-361)
-    if ((rc = lk_bank_pyramid(h->lk, d_right, step, stride, h->d_pyr, S, a.kfSel, pyrSel))) return rc;
-    if ((rc = lk_bank_track(h->lk, a.img, h->cols, a.imgBytes, h->d_pyr, S, a.kfSel, a.imgSel, pyrSel, a.kfP0, a.kfNxt, a.kfCounts, h->cap, a.kfSt))) return rc;
-    hipLaunchKernelGGL(k_kf_tail, dim3(S), dim3(TRK_NT), 0, st, a, k);
-    MYSLAM_HIP_CHECK(hipGetLastError());
-    return MYSLAM_OK;
+    return trk_run_turn(h, k, nullptr, 0);
 }
 
 // ---- StereoInit ----
@@ -926,8 +940,7 @@ int myslam_tracker_reset_stream(myslam_tracker* h, int s, int next_frame_id, int
     hipStream_t st = h->stream;
     TrkArgs& a = h->a;
     TrkState hs;
-    int rc = copy_sync(&hs, a.st + s, sizeof(TrkState), hipMemcpyDeviceToHost, st);
-    if (rc) return rc;
+    if (int rc = trk_fetch_state(h, s, hs)) return rc;
     const int slot = hs.slot;                // the two image buffers keep their roles
     memset(&hs, 0, sizeof(hs));
     hs.ref_pose[3] = 1.0;
@@ -941,7 +954,7 @@ int myslam_tracker_reset_stream(myslam_tracker* h, int s, int next_frame_id, int
 }
 
 int myslam_tracker_init_masks(myslam_tracker* h, uint8_t* d_masks, int step, size_t stride) {
-    if (!h || !d_masks || step < h->cols || stride < (size_t)(h->rows - 1) * step + h->cols) return MYSLAM_ERR_INVALID;
+    if (!h || !d_masks || image_args_bad(h, step, stride)) return MYSLAM_ERR_INVALID;
     hipLaunchKernelGGL(k_init_masks, dim3((h->rows + MASK_ROWS - 1) / MASK_ROWS, h->S), dim3(TRK_NT), 0, h->stream, h->a, d_masks, step, stride);
     MYSLAM_HIP_CHECK(hipGetLastError());
     return MYSLAM_OK;
@@ -955,26 +968,11 @@ int myslam_tracker_init_batch(myslam_tracker* h, const uint8_t* d_left, const ui
                               const int32_t* d_n_new, int kp_cap, double baseline, int init_good, int64_t* d_new_kf_id, double* d_new_kf_pose,
                               int64_t* d_feat_mp_id, double* d_feat_mp_pos, float* d_feat_uv, int32_t* d_feat_tag, uint8_t* d_feat_flags, int32_t* d_n_feat,
                               int64_t* d_outlier_mp_id, int32_t* d_n_outlier_mp, float* d_right_xy, uint8_t* d_right_ok, int32_t* d_report) {
-    if (!h || !d_left || !d_right || !d_new_kps || !d_n_new || !d_new_kf_id || !d_new_kf_pose || !d_feat_mp_id || !d_feat_mp_pos || !d_feat_uv ||
-        !d_feat_tag || !d_feat_flags || !d_n_feat || !d_outlier_mp_id || !d_n_outlier_mp || !d_right_xy || !d_right_ok || !d_report)
+    KfArgs k;
+    if (!d_left || !kf_args(h, d_right, step, stride, d_new_kps, d_n_new, kp_cap, baseline, d_new_kf_id, d_new_kf_pose, d_feat_mp_id, d_feat_mp_pos, d_feat_uv,
+                            d_feat_tag, d_feat_flags, d_n_feat, d_outlier_mp_id, d_n_outlier_mp, d_right_xy, d_right_ok, d_report, k))
         return MYSLAM_ERR_INVALID;
-    if (step < h->cols || stride < (size_t)(h->rows - 1) * step + h->cols || kp_cap < 1) return MYSLAM_ERR_INVALID;
-    const TrkArgs& a = h->a;
-    const KfArgs k{d_right, step, stride, d_new_kps, d_n_new, kp_cap, baseline, d_new_kf_id, d_new_kf_pose, d_feat_mp_id, d_feat_mp_pos, d_feat_uv, d_feat_tag,
-                   d_feat_flags, d_n_feat, d_outlier_mp_id, d_n_outlier_mp, d_right_xy, d_right_ok, d_report};
-    hipStream_t st = h->stream;
-    const int S = h->S;
-    const size_t pyrSel = (size_t)S * h->pyrBytes;
-    hipLaunchKernelGGL(k_init_head, dim3(1 + (h->rows + TRK_COPY_ROWS - 1) / TRK_COPY_ROWS, S), dim3(TRK_NT), 0, st, a, k, d_left, h->d_selLeft);
-    MYSLAM_HIP_CHECK(hipGetLastError());
-    int rc;
-    // the left image's levels into buffer `slot`, the right image's into buffer 1 - slot, then LK from the one into the other (:358-361)
-    if ((rc = lk_bank_pyramid(h->lk, d_left, step, stride, h->d_pyr, S, h->d_selLeft, pyrSel))) return rc;
-    if ((rc = lk_bank_pyramid(h->lk, d_right, step, stride, h->d_pyr, S, a.kfSel, pyrSel))) return rc;
-    if ((rc = lk_bank_track(h->lk, a.img, h->cols, a.imgBytes, h->d_pyr, S, a.kfSel, a.imgSel, pyrSel, a.kfP0, a.kfNxt, a.kfCounts, h->cap, a.kfSt))) return rc;
-    hipLaunchKernelGGL(k_init_tail, dim3(S), dim3(TRK_NT), 0, st, a, k, init_good);
-    MYSLAM_HIP_CHECK(hipGetLastError());
-    return MYSLAM_OK;
+    return trk_run_turn(h, k, d_left, init_good);
 }
 
 int myslam_tracker_debug_last_turn(myslam_tracker* h, int s, float* left_xy, float* right_xy, uint8_t* right_ok, double* tri_xyz, uint8_t* tri_ok, int* n) {
@@ -1017,9 +1015,9 @@ int myslam_tracker_update_from_map_batch(myslam_tracker* h, const int64_t* d_kf_
 }
 
 int myslam_tracker_set_image_batch(myslam_tracker* h, const uint8_t* d_imgs, int step, size_t stride, const uint8_t* d_select) {
-    if (!h || !d_imgs || !d_select || step < h->cols || stride < (size_t)(h->rows - 1) * step + h->cols) return MYSLAM_ERR_INVALID;
+    if (!h || !d_imgs || !d_select || image_args_bad(h, step, stride)) return MYSLAM_ERR_INVALID;
     const TrkArgs& a = h->a;
-    hipLaunchKernelGGL(k_kf_set_image, dim3(1 + (h->rows + TRK_COPY_ROWS - 1) / TRK_COPY_ROWS, h->S), dim3(TRK_NT), 0, h->stream, a, d_imgs, step, stride,
+    hipLaunchKernelGGL(k_kf_set_image, trk_copy_grid(h), dim3(TRK_NT), 0, h->stream, a, d_imgs, step, stride,
                        d_select);
     MYSLAM_HIP_CHECK(hipGetLastError());
     return lk_bank_pyramid(h->lk, d_imgs, step, stride, h->d_pyr, h->S, a.kfSel, (size_t)h->S * h->pyrBytes);

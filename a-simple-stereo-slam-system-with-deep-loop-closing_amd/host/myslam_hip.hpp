@@ -435,9 +435,7 @@ public:
     // d_right: the right images of the step that froze the streams; d_newKps / d_nNew: what detect_batch found under the masks
     void KeyframeBatch(const uint8_t* d_right, int step, size_t stride, const myslam_keypoint* d_newKps, const int32_t* d_nNew, int kpCap, double baseline,
                        const TurnOutputs& o) {
-        check(myslam_tracker_keyframe_batch(h_, d_right, step, stride, d_newKps, d_nNew, kpCap, baseline, o.newKfId, o.newKfPose, o.featMpId, o.featMpPos,
-                                            o.featUv, o.featTag, o.featFlags, o.nFeat, o.outlierMpId, o.nOutlierMp, o.rightXy, o.rightOk, o.report),
-              "myslam_tracker_keyframe_batch");
+        check(withOutputs(myslam_tracker_keyframe_batch, o, h_, d_right, step, stride, d_newKps, d_nNew, kpCap, baseline), "myslam_tracker_keyframe_batch");
     }
     // the back end's tables (item s = stream s) after they moved: running streams follow their ids
     void UpdateFromMap(const int64_t* d_kfId, const double* d_kfPose, const int32_t* d_nKf, int kfCap, const int64_t* d_mpId, const double* d_mpPos,
@@ -462,9 +460,14 @@ public:
     // d_left / d_right: the streams' first stereo pairs; the report's status is 0, MYSLAM_TRACKER_INIT_RETRY, MYSLAM_TRACKER_NO_TURN or an error
     void InitBatch(const uint8_t* d_left, const uint8_t* d_right, int step, size_t stride, const myslam_keypoint* d_newKps, const int32_t* d_nNew, int kpCap,
                    double baseline, int initGood, const TurnOutputs& o) {
-        check(myslam_tracker_init_batch(h_, d_left, d_right, step, stride, d_newKps, d_nNew, kpCap, baseline, initGood, o.newKfId, o.newKfPose, o.featMpId,
-                                        o.featMpPos, o.featUv, o.featTag, o.featFlags, o.nFeat, o.outlierMpId, o.nOutlierMp, o.rightXy, o.rightOk, o.report),
-              "myslam_tracker_init_batch");
+        check(withOutputs(myslam_tracker_init_batch, o, h_, d_left, d_right, step, stride, d_newKps, d_nNew, kpCap, baseline, initGood), "myslam_tracker_init_batch");
+    }
+private:
+    // call(lead..., the 13 pointers of o): the order in which myslam_tracker_keyframe_batch and myslam_tracker_init_batch end
+    template <class Call, class... Lead>
+    static int withOutputs(Call call, const TurnOutputs& o, Lead... lead) {
+        return call(lead..., o.newKfId, o.newKfPose, o.featMpId, o.featMpPos, o.featUv, o.featTag, o.featFlags, o.nFeat, o.outlierMpId, o.nOutlierMp, o.rightXy,
+                    o.rightOk, o.report);
     }
 };
 

@@ -30,12 +30,14 @@ def pair(synth, name, m, seed, d=3, rows=120, cols=160, lose=False):
 
 
 class InitRig(Rig):
-    """Rig with the left images on the device as well; cases of streams that take an init are pair()s"""
+    """Rig with the left images on the device as well; cases of streams that take an init are pair()s.  left_offset: the left images start
+    that many bytes into their allocation, so that a left image's address can be aligned where its right image's is not, and the reverse"""
 
-    def __init__(self, api, chain, S, **kw):
+    def __init__(self, api, chain, S, left_offset=0, **kw):
         super().__init__(api, S, **kw)
         self.chain, self.marked = chain, set()
-        self.d_left = self.torch.zeros((S, self.stride), dtype=self.torch.uint8, device="cuda")
+        self.left_store = self.torch.zeros(left_offset + S * self.stride, dtype=self.torch.uint8, device="cuda")
+        self.d_left = self.left_store[left_offset:].view(S, self.stride)
 
     def arm(self, s, case, mark=None):
         """stream s will see `case`; mark = reset_stream's counters: the stream is given a (black) image through set_frame first, so that
@@ -257,6 +259,22 @@ def test_a_streams_bytes_do_not_depend_on_its_slot_or_neighbours(api, pkg, synth
         assert _same(x, y) or (k == "right_xy" and _same(x[ok], y[ok])), k
     assert _state_bytes(a.trk.get_frame(2, image=True), a.trk.get_ids(2)) == _state_bytes(b.trk.get_frame(0, image=True), b.trk.get_ids(0))
     assert all(_same(x, y) for x, y in zip(a.trk.debug_last_turn(2), b.trk.debug_last_turn(0)))
+
+
+def test_init_copies_words_and_bytes_per_source_in_one_launch(api, pkg, synth, lk):
+    """the head's image copy moves 4-byte words when the widths and that SOURCE's own base allow it.  Rows of whole words, an odd stride and the
+    left images 3 bytes into their allocation: stream 0 copies its right image by words and its left image by bytes, stream 1 the reverse.
+    check_init holds the right tracks to myslam_lk_track's bits on the unpadded pair and the stored image to the left input (no 0xDD, no 0xEE)"""
+    from test_gpu_tracker_kf import WORD_PITCH, WORD_STRIDE
+    rig = InitRig(api, pkg.chain, 2, left_offset=(-WORD_STRIDE) % 4, pitch=WORD_PITCH, stride=WORD_STRIDE)
+    aligned = lambda d: [(d.data_ptr() + s * rig.stride) % 4 == 0 for s in range(2)]
+    assert aligned(rig.d_right) == [True, False] and aligned(rig.d_left) == [False, True]
+    for s in range(2):
+        rig.arm(s, pair(synth, f"word{s}", 120, 395 + s, lose=True), mark=(s, 0, 0, 0))
+    out, reps = init_and_check(rig, lk, 50)
+    assert all(r[0] == 0 and r[2] == 120 and r[3] >= 60 and r[4] >= 30 for r in reps), [r.tolist() for r in reps]
+    for s in range(2):
+        assert _same(rig.trk.get_frame(s, image=True)["image"], rig.cases[s]["left"])
 
 
 def test_init_and_turn_touch_disjoint_streams_and_the_first_step_follows(api, pkg, synth, lk):

@@ -33,15 +33,16 @@ def _state_bytes(st, ids):
 
 
 class Rig:
-    """a tracker of S streams with the device buffers of a turn; pitch > cols pads the rows of the right images and the masks"""
+    """a tracker of S streams with the device buffers of a turn; pitch > cols pads the rows of the right images and the masks; stride: bytes from
+    one stream's image to the next (the default keeps every stream's base 4-byte aligned when the pitch is a multiple of 4)"""
 
-    def __init__(self, api, S, rows=120, cols=160, cap=CAP, lm_cap=LM_CAP, kp_cap=KP_CAP, pitch=None, good=KC.GOOD, bad=KC.BAD, stream=None):
+    def __init__(self, api, S, rows=120, cols=160, cap=CAP, lm_cap=LM_CAP, kp_cap=KP_CAP, pitch=None, good=KC.GOOD, bad=KC.BAD, stream=None, stride=None):
         import torch
         self.torch, self.api, self.S, self.rows, self.cols, self.cap, self.lm_cap, self.kp_cap = torch, api, S, rows, cols, cap, lm_cap, kp_cap
         self.K = TC.K_of(rows, cols)
         self.trk = api.Tracker(S, rows, cols, cap, lm_cap, self.K, good, bad, stream=stream)
         self.pitch = pitch or cols
-        self.stride = rows * self.pitch + 32
+        self.stride = stride or rows * self.pitch + 32
         z = lambda shape, dt: torch.zeros(shape, dtype=getattr(torch, dt), device="cuda")
         dims = {"cap": cap, "cap2": 2 * cap}
         self.out = {k: z((S,) + tuple(dims.get(d, d) for d in shp), dt) for k, (shp, dt) in OUT_SPEC.items()}
@@ -262,6 +263,21 @@ def test_turn_odd_sizes(api, pkg, synth, lk, k):
     assert reps[1][0] == 0 and reps[1][4] >= 10 and reps[0][0] == api.Tracker.NO_TURN
 
 
+WORD_PITCH, WORD_STRIDE = 164, 120 * 164 + 33     # rows of whole words; the odd stride puts stream 1's image on an odd address
+
+
+def test_turn_copies_words_and_bytes_in_one_launch(api, pkg, synth, lk):
+    """the image copy moves 4-byte words when the widths and the stream's own source base allow it: stream 0 does, stream 1 (odd base) moves bytes.
+    The right image is only seen through LK: check_stream holds the right tracks to myslam_lk_track's bits on the unpadded images"""
+    rig = Rig(api, 2, pitch=WORD_PITCH, stride=WORD_STRIDE)
+    assert rig.d_right.data_ptr() % 4 == 0 and (rig.d_right.data_ptr() + rig.stride) % 4 != 0
+    rig.load(0, KC.rich_case(pkg.chain, synth)); rig.load(1, KC.make(pkg.chain, synth, "odd_base", n=40, n_new=24, seed=270, no_lm=(6, 7)))
+    out, reps = run_and_check(pkg, rig, lk)
+    assert all(r[0] == 0 and r[3] >= 30 and r[4] >= 10 for r in reps), [r.tolist() for r in reps]
+    for s in range(2):                                   # the stored left image stays, and no pad byte of the right image's rows reached it
+        assert _same(rig.trk.get_frame(s, image=True)["image"], rig.cases[s]["left"])
+
+
 def test_landmark_cap_met_exactly_and_exceeded_by_one(api, pkg, synth, lk):
     if "rich" not in _cache:
         test_turn_rich_disparities_and_neighbours(api, pkg, synth, lk)
@@ -425,4 +441,32 @@ def test_update_from_map_and_set_image(api, pkg, synth, lk):
     assert ra.cpu().numpy().tobytes() == rb.cpu().numpy().tobytes()
     for s in range(3):
         assert _state_bytes(a.trk.get_frame(s, image=True), a.trk.get_ids(s)) == _state_bytes(b.trk.get_frame(s, image=True), b.trk.get_ids(s))
+        assert all(x.tobytes() == y.tobytes() for x, y in zip(a.trk.debug_last_step(s), b.trk.debug_last_step(s)))
+
+
+def test_set_image_copies_words_and_bytes_in_one_launch(api, pkg, synth):
+    """set_image_batch with rows of whole words: stream 0's source base is 4-byte aligned (word copy), stream 1's is odd (byte copy).  Both equal
+    set_frame(prev_image=...) byte for byte, pyramid included (one following step shows it), so no 0xAB pad byte reached a stored image"""
+    import torch
+    chain = pkg.chain
+    a, b = Rig(api, 2, good=20, bad=10), Rig(api, 2, good=20, bad=10)
+    new_img = [TC.images(synth, 260 + s, 120, 160, (1, 0))[1] for s in range(2)]
+    nxt_img = torch.from_numpy(np.stack([TC.images(synth, 260 + s, 120, 160, (2, 0))[1] for s in range(2)])).cuda()
+    for s in range(2):
+        c = KC.make(chain, synth, f"wimg{s}", n=30, n_new=0, seed=260 + s)
+        a.load(s, c, why=0); b.load(s, c, why=0)
+        b.trk.set_frame(s, c["st"], image=new_img[s]); b.trk.set_ids(s, **{k: c["ids"][k] for k in c["ids"]})
+    pad = np.full((2, WORD_STRIDE), 0xAB, np.uint8)
+    for s in range(2):
+        pad[s, :120 * WORD_PITCH].reshape(120, WORD_PITCH)[:, :160] = new_img[s]
+    d_pad = torch.from_numpy(pad).cuda(); sel = torch.from_numpy(np.array([1, 1], np.uint8)).cuda()
+    assert d_pad.data_ptr() % 4 == 0 and (d_pad.data_ptr() + WORD_STRIDE) % 4 != 0
+    a.trk.set_image_batch(d_pad.data_ptr(), WORD_PITCH, WORD_STRIDE, sel.data_ptr())
+    ra, rb = torch.zeros(2 * 80, dtype=torch.uint8, device="cuda"), torch.zeros(2 * 80, dtype=torch.uint8, device="cuda")
+    for s in range(2):
+        assert _same(a.trk.get_frame(s, image=True)["image"], new_img[s]), f"stream {s}: stored image"
+        assert _state_bytes(a.trk.get_frame(s, image=True), a.trk.get_ids(s)) == _state_bytes(b.trk.get_frame(s, image=True), b.trk.get_ids(s))
+    a.trk.step_batch(nxt_img.data_ptr(), 160, 120 * 160, ra.data_ptr()); b.trk.step_batch(nxt_img.data_ptr(), 160, 120 * 160, rb.data_ptr())
+    assert ra.cpu().numpy().tobytes() == rb.cpu().numpy().tobytes()
+    for s in range(2):
         assert all(x.tobytes() == y.tobytes() for x, y in zip(a.trk.debug_last_step(s), b.trk.debug_last_step(s)))
