@@ -1164,6 +1164,12 @@ class Backend:
                                                    C.c_double(delta), C.c_double(chi2_th), int(rounds), int(iters), *outs),
                "myslam_backend_optimize_batch")
 
+    def solve_view(self):
+        """(device pointer of the solve's positions by landmark slot, device pointer of the slot of every input map-point row): MapArchive.attach_solve"""
+        pts, slot = C.c_void_p(), C.c_void_p()
+        _check(lib().myslam_backend_solve_view(self._h, C.byref(pts), C.byref(slot)), "myslam_backend_solve_view")
+        return pts.value, slot.value
+
     def insert_launches_per_call(self):
         return lib().myslam_backend_insert_launches_per_call(self._h)
 
@@ -1239,6 +1245,11 @@ class MapArchive:
 
     def launches_per_update(self):
         return lib().myslam_map_launches_per_update(self._h)
+
+    def attach_solve(self, d_solve_points, d_solve_mp_slot):
+        """Backend.solve_view() of the back end whose tables the updates read: a point that leaves the active set with an optimise then takes the solve's
+        position (None, None detaches)"""
+        _check(lib().myslam_map_attach_solve(self._h, C.c_void_p(d_solve_points or None), C.c_void_p(d_solve_mp_slot or None)), "myslam_map_attach_solve")
 
     def view(self):
         """MapTables: the device pointers (ints or None) and caps of the per-item tables"""

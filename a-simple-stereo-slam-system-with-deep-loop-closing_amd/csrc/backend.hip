@@ -636,6 +636,12 @@ int myslam_backend_set_stream(myslam_backend* h, void* hip_stream) {
 
 int myslam_backend_launches_per_call(const myslam_backend* h) { return h ? 3 : MYSLAM_ERR_INVALID; }
 
+int myslam_backend_solve_view(const myslam_backend* h, const double** d_points, const int32_t** d_mp_slot) {
+    if (!h || !d_points || !d_mp_slot) return MYSLAM_ERR_INVALID;
+    *d_points = h->w.pts; *d_mp_slot = h->w.mp_slot;
+    return MYSLAM_OK;
+}
+
 int myslam_backend_optimize_batch(myslam_backend* h, const int64_t* d_kf_id, double* d_kf_pose, const int32_t* d_n_kf, int64_t* d_mp_id, double* d_mp_pos,
                                   uint8_t* d_mp_outlier, int32_t* d_n_mp, int32_t* d_obs_mp, int32_t* d_obs_kf, uint8_t* d_obs_flags, float* d_obs_uv,
                                   int32_t* d_obs_tag, int32_t* d_n_obs, int batch, double fx, double fy, double cx, double cy, double huber_delta,

@@ -67,7 +67,10 @@ __device__ __forceinline__ int ma_find(const T* a, int n, int64_t v) {
     return i < n && a[i] == v ? i : -1;
 }
 
-struct MaUpdateIn { int mode; const int32_t* be_status; const int64_t* outlier_id; const int32_t* n_outlier; int outlier_cap; const uint8_t* mp_report; };
+struct MaUpdateIn {
+    int mode; const int32_t* be_status; const int64_t* outlier_id; const int32_t* n_outlier; int outlier_cap; const uint8_t* mp_report;
+    const double* solve_pts; const int32_t* solve_slot;     // myslam_map_attach_solve: the solve's positions by landmark slot, the slot of every INPUT row
+};
 
 __global__ __launch_bounds__(MA_NT) void k_map_update(MaTables A, MaBackend B, MaUpdateIn U, int32_t* status) {
     __shared__ int s_bad;
@@ -152,6 +155,17 @@ __global__ __launch_bounds__(MA_NT) void k_map_update(MaTables A, MaBackend B, M
                 const int s = a.snap[m];
                 if (s >= 0 && s < aM) a.mp_state[s] = 2;
             }
+        // SetPos reaches every vertex (backend.cpp:259-261) before RemoveOldActiveMapPoints (map.cpp:126-140): a point that leaves the table alive with
+        // this optimise takes the solve's position, which the compacted table no longer holds
+        if (U.solve_pts)
+            for (int m = t; m < nsnap; m += MA_NT)
+                if (U.mp_report[(size_t)b * B.mp_cap + m] == 1) {
+                    const int s = a.snap[m], slot = U.solve_slot[(size_t)b * B.mp_cap + m];
+                    if (s >= 0 && s < aM && slot >= 0 && slot < B.mp_cap) {
+                        const double* p = U.solve_pts + ((size_t)b * B.mp_cap + slot) * 3;
+                        a.mp_pos[3 * s] = p[0]; a.mp_pos[3 * s + 1] = p[1]; a.mp_pos[3 * s + 2] = p[2];
+                    }
+                }
         __syncthreads();
         for (int s = t; s < aM; s += MA_NT)
             if (a.mp_state[s] == 1) a.mp_state[s] = 2;
@@ -277,6 +291,8 @@ struct myslam_map {
     hipStream_t stream = nullptr;
     MaTables t{};
     BufSet mem;                         // owns every block that `t` names
+    const double* solve_pts = nullptr;  // myslam_map_attach_solve: the back end's, not owned
+    const int32_t* solve_slot = nullptr;
 };
 
 // host <-> one item's rows, complete on return, on the calling thread's non-blocking stream (common.h); the caller has waited for the handle's stream
@@ -340,6 +356,12 @@ int myslam_map_view(const myslam_map* h, myslam_map_tables* out) {
 }
 
 int myslam_map_launches_per_update(const myslam_map* h) { return h ? 1 : MYSLAM_ERR_INVALID; }
+
+int myslam_map_attach_solve(myslam_map* h, const double* d_solve_points, const int32_t* d_solve_mp_slot) {
+    if (!h || (d_solve_points == nullptr) != (d_solve_mp_slot == nullptr)) return MYSLAM_ERR_INVALID;
+    h->solve_pts = d_solve_points; h->solve_slot = d_solve_mp_slot;
+    return MYSLAM_OK;
+}
 
 int myslam_map_load(myslam_map* h, int item, const int64_t* kf_id, const double* kf_pose, int n_kf, const int32_t* edge_v0, const int32_t* edge_v1,
                     const double* meas, int n_edges, const int64_t* mp_id, const double* mp_pos, const int32_t* mp_first_kf, const uint8_t* mp_state, int n_mp,
@@ -430,7 +452,7 @@ int myslam_map_update_batch(myslam_map* h, int mode, const int64_t* d_kf_id, con
     const bool ins = mode == MYSLAM_MAP_AFTER_INSERT;
     const MaBackend B{d_kf_id, d_kf_pose, d_n_kf, d_mp_id, d_mp_pos, d_n_mp, d_obs_mp, d_obs_kf, d_obs_flags, d_n_obs, be_kf_cap, be_mp_cap, be_obs_cap};
     const MaUpdateIn U{mode, d_backend_status, ins ? d_outlier_mp_id : nullptr, ins ? d_n_outlier_mp : nullptr, (ins && d_n_outlier_mp) ? outlier_cap : 0,
-                       d_mp_report};
+                       d_mp_report, ins ? nullptr : h->solve_pts, ins ? nullptr : h->solve_slot};
     hipLaunchKernelGGL(k_map_update, dim3(batch), dim3(MA_NT), 0, h->stream, h->t, B, U, d_status);
     MYSLAM_HIP_CHECK(hipGetLastError());
     return MYSLAM_OK;

@@ -618,6 +618,10 @@ public:
     int obsCap() const { return obsCap_; }
     void SetStream(void* hipStream) { check(myslam_backend_set_stream(h_, hipStream), "myslam_backend_set_stream"); }
     int LaunchesPerCall() const { return myslam_backend_launches_per_call(h_); }
+    // the last optimise's positions by landmark slot and the slot of every input map-point row (device pointers): MapArchive::AttachSolve
+    void SolveView(const double** d_points, const int32_t** d_mpSlot) const {
+        check(myslam_backend_solve_view(h_, d_points, d_mpSlot), "myslam_backend_solve_view");
+    }
     void OptimizeBatch(const int64_t* d_kfId, double* d_kfPose, const int32_t* d_nKF, int64_t* d_mpId, double* d_mpPos, uint8_t* d_mpOutlier, int32_t* d_nMP,
                        int32_t* d_obsMP, int32_t* d_obsKF, uint8_t* d_obsFlags, float* d_obsUV, int32_t* d_obsTag, int32_t* d_nObs, int batch, double fx,
                        double fy, double cx, double cy, uint8_t* d_obsReport, uint8_t* d_mpReport, int32_t* d_newOutlierMP, int32_t* d_nNewOutlierMP,
@@ -674,6 +678,12 @@ public:
     MapArchive(const MapArchive&) = delete; MapArchive& operator=(const MapArchive&) = delete;
     void SetStream(void* hipStream) { check(myslam_map_set_stream(h_, hipStream), "myslam_map_set_stream"); }
     int LaunchesPerUpdate() const { return myslam_map_launches_per_update(h_); }
+    // a map point that leaves the active set with an optimise takes the solve's position (src/backend.cpp:259-261 come before src/map.cpp:126-140)
+    void AttachSolve(const Backend& be) {
+        const double* pts = nullptr; const int32_t* slot = nullptr;
+        be.SolveView(&pts, &slot);
+        check(myslam_map_attach_solve(h_, pts, slot), "myslam_map_attach_solve");
+    }
     myslam_map_tables View() const { myslam_map_tables t; check(myslam_map_view(h_, &t), "myslam_map_view"); return t; }
     // one item from / to host arrays (synchronous); Get's arrays are sized by the caps, any pointer may be nullptr
     void Load(int item, const int64_t* kfId, const double* kfPose, int nKF, const int32_t* edgeV0, const int32_t* edgeV1, const double* meas, int nEdges,

@@ -1180,6 +1180,9 @@ int myslam_backend_optimize_batch(myslam_backend* h, const int64_t* d_kf_id, dou
                                   int32_t* d_n_outlier_edges, int32_t* d_status);
 /* launches one myslam_backend_optimize_batch enqueues (3: flatten, solve, write-back) */
 int myslam_backend_launches_per_call(const myslam_backend* h);
+/* What the last optimise's solve left, as device pointers that stay valid until destroy: *d_points max_batch x mp_cap x 3 f64 by landmark slot,
+ * *d_mp_slot max_batch x mp_cap i32 = the landmark slot of every INPUT map-point row, -1 = it had no vertex.  For myslam_map_attach_solve. */
+int myslam_backend_solve_view(const myslam_backend* h, const double** d_points, const int32_t** d_mp_slot);
 /* The flat window (src/backend.cpp:139-206) of one item as the last call built it, in myslam_ba_flatten_window's outputs: host pointers (any but sizes3
  * may be NULL) of kf_cap / mp_cap / obs_cap elements, sizes3 = (poses, landmarks, edges), all 0 for an item that was refused or empty.  Synchronises. */
 int myslam_backend_debug_flat(myslam_backend* h, int item, int32_t* pose_src, int32_t* pt_src, int32_t* edge_pose, int32_t* edge_pt, double* edge_obs,
@@ -1298,7 +1301,8 @@ int myslam_backend_insert_launches_per_call(const myslam_backend* h);
  *      holds such a point).  Rows LoopLocalFusion appended out of key-frame order are out of scope, below.
  *   6. the snapshot, the masks and the window record are rebuilt from the table.  MYSLAM_MAP_UPDATED.
  * After optimise: MYSLAM_BACKEND_DONE -> every snapshot row whose d_mp_report is 2 gets state 2, then every archive point with state 1 gets state 2
- * (Map::RemoveAllOutlierMapPoints empties the whole list, points that are not active included), then 5 and 6.  MYSLAM_BACKEND_EMPTY or an error: the
+ * (Map::RemoveAllOutlierMapPoints empties the whole list, points that are not active included), then 5 and 6.  A snapshot row whose d_mp_report is 1
+ * (the point left the active set alive) takes the solve's position if the solve is attached: myslam_map_attach_solve, below.  MYSLAM_BACKEND_EMPTY or an error: the
  * reference returns before the removal — nothing changes, state 1 stays, MYSLAM_MAP_SKIPPED.  A table that holds an id the archive lacks, or more rows
  * than the snapshot: MYSLAM_ERR_INVALID.
  * A key-frame, edge or point count that would exceed its cap: MYSLAM_ERR_CAPACITY.  A count out of range, a key-frame id at or below the archive's
@@ -1355,6 +1359,15 @@ int myslam_map_update_batch(myslam_map* h, int mode, const int64_t* d_kf_id, con
                             int32_t* d_status);
 /* kernel launches one myslam_map_update_batch enqueues (1) */
 int myslam_map_launches_per_update(const myslam_map* h);
+/* The optimised position of a map point that LEAVES the active set with the optimise.  Backend::OptimizeActiveMap sets the position of every vertex
+ * (src/backend.cpp:259-261) before Map::RemoveOldActiveMapPoints (src/map.cpp:126-140) takes the points without an active observation out of the active
+ * set, so Map::mmAllMapPoints holds the optimised position of such a point; the back end's compacted table no longer has its row.  With the two
+ * pointers of myslam_backend_solve_view (of the back end whose tables the updates read; its mp_cap is the archive's backend_mp_cap) attached, an
+ * update after optimise gives every snapshot row whose d_mp_report is 1 and that had a vertex the solve's position.  Without them (the state after
+ * create; both NULL detaches) such a point keeps the position it had before the optimise.  One NULL and one not: MYSLAM_ERR_INVALID.  It concerns
+ * a landmark that is not fixed and loses its last active observation to the optimiser while older rows remain; tests/test_whole_map_model.py holds
+ * the shortest such history. */
+int myslam_map_attach_solve(myslam_map* h, const double* d_solve_points, const int32_t* d_solve_mp_slot);
 /* src/loopclosing.cpp:560-562 and the index inputs of :470-507 / :612-641 as described above */
 int myslam_map_loop_inputs_batch(myslam_map* h, const int64_t* d_kf_id, const int32_t* d_n_kf, int be_kf_cap, const int64_t* d_mp_id, const int32_t* d_n_mp,
                                  int be_mp_cap, const int32_t* d_obs_mp, const int32_t* d_obs_kf, const uint8_t* d_obs_flags, const int32_t* d_n_obs,

@@ -94,11 +94,12 @@ def flatten(m):
 
 def walk(m, solve):
     """Backend::OptimizeActiveMap on `m` (changed in place).  solve(poses, pts, edge_pose, edge_pt, edge_obs, fixed) -> (poses, pts, chi2, outlier flags,
-    rounds, outlier count): backend.cpp:208-232 and the test `chi2 > chi2_th` of :237.  Returns the reports of myslam_backend_optimize_batch by INPUT row."""
+    rounds, outlier count): backend.cpp:208-232 and the test `chi2 > chi2_th` of :237.  Returns the reports of myslam_backend_optimize_batch by INPUT row,
+    and left_pos: INPUT row -> the optimised position of every map point that had a vertex and left the active set alive."""
     rows = rows_of(m)
     n_mp, n_obs = len(m.mps), len(rows)
     rep = dict(status=DONE, obs_report=np.zeros(n_obs, np.uint8), mp_report=np.zeros(n_mp, np.uint8), new_outlier=[], obs_chi2=np.zeros(n_obs),
-               rounds=0, n_outlier_edges=0, flat=None)
+               rounds=0, n_outlier_edges=0, flat=None, left_pos={})
     if not validate(m):
         rep["status"] = INVALID
         return rep
@@ -141,6 +142,8 @@ def walk(m, solve):
     for mid in [k for k, mp in m.mps.items() if not mp.active_obs]:        # RemoveOldActiveMapPoints, map.cpp:126-140
         rep["mp_report"][row_of_mp[mid]] = 1
         gone.append(m.mps.pop(mid))
+        if _is_in(slot_mps, gone[-1]):                                      # :259-261 came first: the point leaves with its optimised position, which
+            rep["left_pos"][row_of_mp[mid]] = gone[-1].pos.copy()           # the tables no longer hold (INPUT row -> position: myslam_map_attach_solve)
     for mp in gone:
         for o in mp.obs:
             rep["obs_report"][row_of_obs[id(o)]] = 2

@@ -11,6 +11,10 @@ import backend_ref as br
 AFTER_INSERT, AFTER_OPTIMIZE = 0, 1         # MYSLAM_MAP_AFTER_*
 UPDATED, SKIPPED, INVALID, CAPACITY = 0, 1, -1, -3
 FAULTS = ("no_promotion", "no_first_refresh", "edge_to_row0", "report_by_output_row")
+# two more, rehearsed by tests/test_whole_map_model.py only (the rendered run of tests/test_map_archive_ref.py holds ONE point that tells the first from
+# the rule, and none that tells the second): the shorter first-observer rule the header warns about ("the record stays when the front row has
+# obs_kf = -1"), and the last instead of the lowest departed observer
+MORE_FAULTS = ("front_record_stays", "last_departed_observer")
 FIELDS = ("kf_id", "kf_pose", "edge_v0", "edge_v1", "meas", "mp_id", "mp_pos", "mp_first_kf", "mp_state", "snapshot", "mp_gone_kf", "mp_win_mask", "win_kf")
 
 
@@ -49,9 +53,10 @@ def edge_meas(chain, new_pose, prev_pose):
     return chain.p7_of(chain.mm(chain.T_of(np.asarray(new_pose, float)), chain.T_inv(chain.T_of(np.asarray(prev_pose, float)))))
 
 
-def update(chain, a, mode, t, be_status, outlier_ids=(), mp_report=None, caps=None, faults=()):
+def update(chain, a, mode, t, be_status, outlier_ids=(), mp_report=None, caps=None, faults=(), left_pos=None):
     """myslam_map_update_batch for one item.  t: the back end's tables after the call, unpadded (backend_ref.pack's kf_id, kf_pose, mp_id, mp_pos, obs_mp,
-    obs_kf); caps = (kf_cap, edge_cap, point_cap) or None.  `a` is changed in place unless the status is not UPDATED."""
+    obs_kf); caps = (kf_cap, edge_cap, point_cap) or None; left_pos = backend_ref.walk's (INPUT row -> the optimised position of a point that left the
+    table alive: what myslam_map_attach_solve lets the device read), None = nothing attached.  `a` is changed in place unless the status is not UPDATED."""
     if be_status != 0:
         return SKIPPED
     kf_id = [int(v) for v in t["kf_id"]]; mp_id = [int(v) for v in t["mp_id"]]
@@ -91,6 +96,9 @@ def update(chain, a, mode, t, be_status, outlier_ids=(), mp_report=None, caps=No
             for m, s in enumerate(a.snapshot):
                 if mp_report[m] == 2:
                     a.mp_state[s] = 2
+        for m, s in enumerate(a.snapshot):          # SetPos (backend.cpp:259-261) before RemoveOldActiveMapPoints (map.cpp:126-140)
+            if mp_report[m] == 1 and left_pos is not None and m in left_pos:
+                a.mp_pos[s] = np.array(left_pos[m], float)
         if "no_promotion" not in faults:
             a.mp_state = [2 if s == 1 else s for s in a.mp_state]
     kf_at = {v: i for i, v in enumerate(a.kf_id)}
@@ -101,8 +109,8 @@ def update(chain, a, mode, t, be_status, outlier_ids=(), mp_report=None, caps=No
     for s in a.snapshot:                            # the points of the table before the call: observers that left the window with this insert
         for k, row in enumerate(a.win_kf):
             if row not in win and (a.mp_win_mask[s] >> k) & 1:
-                a.mp_gone_kf[s] = row if a.mp_gone_kf[s] < 0 else min(a.mp_gone_kf[s], row)
-        if a.mp_gone_kf[s] >= 0 and not frozen(s):  # a point that is leaving keeps only such rows: the lowest of them is its front
+                a.mp_gone_kf[s] = row if a.mp_gone_kf[s] < 0 else (max if "last_departed_observer" in faults else min)(a.mp_gone_kf[s], row)
+        if a.mp_gone_kf[s] >= 0 and not frozen(s) and "front_record_stays" not in faults:  # a point that is leaving keeps only such rows: the lowest is its front
             a.mp_first_kf[s] = a.mp_gone_kf[s]
     for m, mid in enumerate(mp_id):
         s = mp_at[mid]
@@ -110,6 +118,9 @@ def update(chain, a, mode, t, be_status, outlier_ids=(), mp_report=None, caps=No
         rows = [int(k) for k in np.asarray(t["obs_kf"])[np.asarray(t["obs_mp"]) == m] if k >= 0]
         a.mp_win_mask[s] = sum(1 << k for k in set(rows))
         cand = [c for c in ([win[rows[0]]] if rows else []) + [a.mp_gone_kf[s]] if c >= 0]
+        if "front_record_stays" in faults:          # the front row alone decides: a key-frame of the window is taken, -1 keeps what was recorded
+            front = [int(k) for k in np.asarray(t["obs_kf"])[np.asarray(t["obs_mp"]) == m]][:1]
+            cand = [win[front[0]]] if front and front[0] >= 0 else []
         if cand and not frozen(s):                  # both observation lists are in key-frame order: the front is the lowest row
             a.mp_first_kf[s] = min(cand)
     a.snapshot = [mp_at[mid] for mid in mp_id]

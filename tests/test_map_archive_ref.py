@@ -7,7 +7,11 @@ meas against Chain's rel_to_last: the host turn stores cur.rel itself, the archi
 on this run (printed by the test, no bar set): at most 1.33e-15 in any component over the 40 edges; DESIGN.md section 3.16c.
 
 The first-observer rule that is pinned here is the header's (window record, mp_gone_kf).  The shorter rule "the record stays when the front row has
-obs_kf = -1" fails this pin at map point 352, key-frame 29: BA removes its front observation and the next one belongs to a key-frame that left."""
+obs_kf = -1" fails this pin at map point 352, key-frame 29: BA removes its front observation and the next one belongs to a key-frame that left.
+That is ONE witness in this run.  The rule is pinned a second time in tests/test_whole_map_model.py: 12 seeded random histories on an object model of
+the reference's Map (tests/whole_map_model.py), where that case occurs 34 times, the front removed with the next observer in the window 35 times, and
+where the shorter rule and "the last instead of the lowest departed observer" are rehearsed as stand-ins of their own (map_archive_ref.MORE_FAULTS);
+test_path_counters there prints the counts.  The rendered run stays the only pin against <pkg>/chain.py's own objects."""
 import numpy as np
 import pytest
 
