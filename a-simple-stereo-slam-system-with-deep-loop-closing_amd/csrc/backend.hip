@@ -6,37 +6,22 @@
 //   k_backend_write_back  :234-266 with Map::RemoveAllOutlierMapPoints / RemoveOldActiveMapPoints (src/map.cpp:126-175): outlier edges leave the
 //                         observation table, emptied map points become outliers, poses and positions are stored, the map-point and observation
 //                         tables are compacted in place.
-// Every order is fixed by the tables, so positions come from block-wide exclusive scans (ballot + mbcnt inside a wave, the wave totals in LDS):
-// no global atomics, and an item's bytes depend neither on its slot nor on its neighbours.  See include/myslam_hip.h for the contract.
+// Every order is fixed by the tables, so positions come from block-wide exclusive scans (block_rank / block_exsum of dev_tables.h, whose two
+// barriers the in-place compactions of the write-back stand on): no global atomics, and an item's bytes depend neither on its slot nor on its
+// neighbours.  See include/myslam_hip.h for the contract.
 // k_backend_insert is Map::InsertKeyFrame (src/map.cpp:17-48 with KeyFrame::CreateKF's AddObservation loop, RemoveOldActiveKeyframe and
 // RemoveOldActiveMapPoints) on the same tables: one launch, one workgroup per map, the same scans; the tables are rebuilt from a copy the handle holds.
 // Every argument struct is a set of batch arrays strided by the caps; its item(b, ...) is the one place that states each stride and returns the
-// pointers of map b (arrays with one element per map are indexed by b where they are used).  be_tables_bad is the one validation of the tables.
+// pointers of map b (arrays with one element per map are indexed by b where they are used).  The caller's tables are dev_tables.h's BeTables /
+// InsTables, rows are found with its lower_row / upper_row.  be_tables_bad is the one validation of the tables.
 #include "backend_launch.h"
+#include "dev_tables.h"
 #include "pg_shared.h"
 
 namespace myslam_hip {
 
 constexpr int BE_NT = 512, BE_NW = BE_NT / WAVE;
 constexpr int BE_ACTIVE = MYSLAM_BACKEND_OBS_ACTIVE, BE_OUTLIER = MYSLAM_BACKEND_OBS_OUTLIER;
-
-template <class KfId, class NKf>
-struct BeTablesT {                      // the caller's tables, strided by the caps
-    KfId* kf_id; double* kf_pose; NKf* n_kf;
-    int64_t* mp_id; double* mp_pos; uint8_t* mp_outlier; int32_t* n_mp;
-    int32_t* obs_mp; int32_t* obs_kf; uint8_t* obs_flags; float* obs_uv; int32_t* obs_tag; int32_t* n_obs;
-    int kf_cap, mp_cap, obs_cap;
-    struct Item {
-        KfId* kf_id; double* kf_pose; int64_t* mp_id; double* mp_pos; uint8_t* mp_outlier;
-        int32_t* obs_mp; int32_t* obs_kf; uint8_t* obs_flags; float* obs_uv; int32_t* obs_tag;
-    };
-    __device__ __forceinline__ Item item(int b) const {
-        const size_t k = (size_t)b * kf_cap, m = (size_t)b * mp_cap, o = (size_t)b * obs_cap;
-        return {kf_id + k, kf_pose + k * 7, mp_id + m, mp_pos + m * 3, mp_outlier + m, obs_mp + o, obs_kf + o, obs_flags + o, obs_uv + o * 2, obs_tag + o};
-    }
-};
-using BeTables = BeTablesT<const int64_t, const int32_t>;      // optimise: key-frames neither come nor go
-using InsTables = BeTablesT<int64_t, int32_t>;                 // insert: all in/out
 
 struct BeWork {                         // the handle's buffers of optimise, strided by the same caps
     double* poses; double* pts; int32_t* ep; int32_t* el; double* obs; uint8_t* fixed; int32_t* sizes;       // the flat windows (k_ba_optimize's arguments)
@@ -115,49 +100,6 @@ struct InsOut {
     }
 };
 
-// lanes below this one whose bit is set in a ballot mask
-__device__ __forceinline__ int be_lane_prefix(unsigned long long m) {
-    return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
-
-// The tail of both block scans: the lane with `publish` stores its wave's total, the block meets, every thread sums the BE_NW totals -> the totals
-// of the waves below this one, and `total` of all.  Every thread of the block calls it; the two barriers inside also separate what a chunk read
-// before the call from what it writes after it.
-__device__ __forceinline__ int be_wave_totals(bool publish, int wave_total, int* s_w, int& total) {
-    const int wv = threadIdx.x >> 6;
-    if (publish) s_w[wv] = wave_total;
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < BE_NW; i++) { const int c = s_w[i]; off += i < wv ? c : 0; tot += c; }
-    __syncthreads();
-    total = tot;
-    return off;
-}
-
-// exclusive position of this thread's flag among the block's flags in thread order, and their number (be_wave_totals' rules)
-__device__ __forceinline__ int be_block_rank(bool f, int* s_w, int& total) {
-    const unsigned long long m = __ballot(f);
-    return be_wave_totals((threadIdx.x & 63) == 0, __popcll(m), s_w, total) + be_lane_prefix(m);
-}
-
-// exclusive block-wide prefix sum of v in thread order, and the sum (be_wave_totals' rules)
-__device__ __forceinline__ int be_block_exsum(int v, int* s_w, int& total) {
-    const int lane = threadIdx.x & 63;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) { const int o = __shfl_up(inc, d); if (lane >= d) inc += o; }
-    return be_wave_totals(lane == WAVE - 1, inc, s_w, total) + inc - v;
-}
-
-// first index in a[0, n) whose value is not below v (UPPER: is above v); a non-decreasing, on any other input the result still lies in [0, n]
-template <class T, bool UPPER = false>
-__device__ __forceinline__ int be_bound(const T* a, int n, T v) {
-    int lo = 0, hi = n;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (UPPER ? a[mid] <= v : a[mid] < v) lo = mid + 1; else hi = mid; }
-    return lo;
-}
-
 // The rules every operator's tables obey, over counts that are within the caps: key-frame ids ascending, row fields in range and grouped by map
 // point, ACTIVE implies a key-frame (the assert of backend.cpp:187), map-point ids ascending.  -> this thread's `bad`; the block ORs them.
 // COPY: the same pass stages the map-point and observation tables in `copy` (a compile-time switch: behind a run-time one the item's pointers
@@ -205,7 +147,7 @@ __global__ __launch_bounds__(BE_NT) void k_backend_flatten(BeTables T, BeWork W)
     bool bad = be_tables_bad<false>(tb, nk, nm, no, InsWork::Item{});
     for (int m = t; m < nm; m += BE_NT)
         if (!tb.mp_outlier[m]) {                                            // an active map point without observations (:175 would dereference front())
-            const int s = be_bound(tb.obs_mp, no, m);
+            const int s = lower_row(tb.obs_mp, no, m);
             bad |= s >= no || tb.obs_mp[s] != m;
         }
     if (bad) s_bad = 1;
@@ -219,7 +161,7 @@ __global__ __launch_bounds__(BE_NT) void k_backend_flatten(BeTables T, BeWork W)
         bool e = false;
         if (r < no) e = (tb.obs_flags[r] & (BE_ACTIVE | BE_OUTLIER)) == BE_ACTIVE && !tb.mp_outlier[tb.obs_mp[r]];
         int tot;
-        const int k = E + be_block_rank(e, s_w, tot);
+        const int k = E + block_rank<BE_NW>(e, s_w, tot);
         if (r < no) w.eidx[r] = k;
         if (e) {
             w.ep[k] = tb.obs_kf[r]; w.edge_src[k] = r;
@@ -238,11 +180,11 @@ __global__ __launch_bounds__(BE_NT) void k_backend_flatten(BeTables T, BeWork W)
         bool has = false;
         int s = 0;
         if (m < nm && !tb.mp_outlier[m]) {
-            s = be_bound(tb.obs_mp, no, m);
-            has = w.eidx[be_bound(tb.obs_mp, no, m + 1)] > w.eidx[s];
+            s = lower_row(tb.obs_mp, no, m);
+            has = w.eidx[lower_row(tb.obs_mp, no, m + 1)] > w.eidx[s];
         }
         int tot;
-        const int slot = L + be_block_rank(has, s_w, tot);
+        const int slot = L + block_rank<BE_NW>(has, s_w, tot);
         if (m < nm) w.mp_slot[m] = has ? slot : -1;
         if (has) {
             w.pt_src[slot] = m;
@@ -265,7 +207,7 @@ __global__ __launch_bounds__(BE_NT) void k_backend_write_back(BeTables T, BeWork
     int st = W.st[b];
     if (st == 0) st = W.solve_st[b];
     if (st != 0) {                                                          // refused or empty: the tables keep every byte, the reports are zero
-        const int cm = min(max(nm, 0), T.mp_cap), co = min(max(no, 0), T.obs_cap);
+        const int cm = clamped_count(nm, T.mp_cap), co = clamped_count(no, T.obs_cap);
         for (int r = t; r < co; r += BE_NT) { o.obs_report[r] = 0; o.obs_chi2[r] = 0.0; }
         for (int m = t; m < cm; m += BE_NT) o.mp_report[m] = 0;
         if (t == 0) { O.rounds[b] = 0; O.n_outlier_edges[b] = 0; O.n_new_outlier_mp[b] = 0; O.status[b] = st; }
@@ -276,7 +218,7 @@ __global__ __launch_bounds__(BE_NT) void k_backend_write_back(BeTables T, BeWork
 
     for (int i = t; i < 7 * nk; i += BE_NT) tb.kf_pose[i] = w.poses[i];     // :256-258
 
-    // ---- map points, in ascending chunks: a chunk is read, the block meets in be_block_rank, then the chunk is written at or below where it stood ----
+    // ---- map points, in ascending chunks: a chunk is read, the block meets in block_rank, then the chunk is written at or below where it stood ----
     int n_keep = 0, n_new = 0;
     for (int base = 0; base < nm; base += BE_NT) {
         const int m = base + t;
@@ -284,7 +226,7 @@ __global__ __launch_bounds__(BE_NT) void k_backend_write_back(BeTables T, BeWork
         int64_t id = 0;
         double p0 = 0, p1 = 0, p2 = 0;
         if (m < nm) {
-            const int s = be_bound(tb.obs_mp, no, m), e = be_bound(tb.obs_mp, no, m + 1);
+            const int s = lower_row(tb.obs_mp, no, m), e = lower_row(tb.obs_mp, no, m + 1);
             int nrem = 0, nact = 0;
             for (int k = w.eidx[s]; k < w.eidx[e]; k++) nrem += w.out[k] ? 1 : 0;                 // :237-241: the edge's row leaves both lists
             for (int r = s; r < e; r++) nact += tb.obs_flags[r] & BE_ACTIVE;
@@ -300,8 +242,8 @@ __global__ __launch_bounds__(BE_NT) void k_backend_write_back(BeTables T, BeWork
             p0 = src[0]; p1 = src[1]; p2 = src[2];
         }
         int tot, ntot;
-        const int dst = n_keep + be_block_rank(keep, s_w, tot);
-        const int nd = n_new + be_block_rank(newout, s_w, ntot);
+        const int dst = n_keep + block_rank<BE_NW>(keep, s_w, tot);
+        const int nd = n_new + block_rank<BE_NW>(newout, s_w, ntot);
         if (m < nm) w.mp_new[m] = keep ? dst : -1;
         if (keep) { tb.mp_id[dst] = id; tb.mp_pos[3 * dst] = p0; tb.mp_pos[3 * dst + 1] = p1; tb.mp_pos[3 * dst + 2] = p2; tb.mp_outlier[dst] = 0; }
         if (newout) o.new_outlier_mp[nd] = m;
@@ -329,7 +271,7 @@ __global__ __launch_bounds__(BE_NT) void k_backend_write_back(BeTables T, BeWork
             if (edge) fl &= (uint8_t)~BE_OUTLIER;                                                 // :249
         }
         int tot;
-        const int dst = n_rows + be_block_rank(keep, s_w, tot);
+        const int dst = n_rows + block_rank<BE_NW>(keep, s_w, tot);
         if (keep) {
             tb.obs_mp[dst] = m2; tb.obs_kf[dst] = kf; tb.obs_flags[dst] = fl; tb.obs_uv[2 * dst] = u; tb.obs_uv[2 * dst + 1] = v; tb.obs_tag[dst] = tag;
         }
@@ -358,7 +300,7 @@ __global__ __launch_bounds__(BE_NT) void k_backend_insert(InsTables T, InsIn I, 
     const int np = I.n_prior ? I.n_prior[b] : 0, nx = I.n_outlier ? I.n_outlier[b] : 0;
     const auto o = O.item(b, I.feat_cap, T.mp_cap, T.kf_cap);
     auto refuse = [&](int st) {                                             // the tables keep every byte; the reports say "nothing"
-        const int cf = min(max(nf, 0), I.feat_cap), cm = min(max(nm, 0), T.mp_cap);
+        const int cf = clamped_count(nf, I.feat_cap), cm = clamped_count(nm, T.mp_cap);
         for (int f = t; f < cf; f += BE_NT) o.feat_row[f] = -1;
         for (int m = t; m < cm; m += BE_NT) o.mp_new_row[m] = -1;
         if (t < T.kf_cap) o.dis[t] = -1.0;
@@ -388,7 +330,7 @@ __global__ __launch_bounds__(BE_NT) void k_backend_insert(InsTables T, InsIn I, 
 
     // ---- Map::AddOutlierMapPoint (map.cpp:159-164) on the copy: ids that are not in the table are ignored ----
     for (int j = t; j < nx; j += BE_NT) {
-        const int m = be_bound(w.mp_id, nm, in.xid[j]);
+        const int m = lower_row(w.mp_id, nm, in.xid[j]);
         if (m < nm && w.mp_id[m] == in.xid[j]) w.mp_outlier[m] = 1;
     }
 
@@ -398,7 +340,7 @@ __global__ __launch_bounds__(BE_NT) void k_backend_insert(InsTables T, InsIn I, 
         const int f = base + t;
         const bool v = f < nf && in.fid[f] >= 0;
         int tot;
-        const int k = nv + be_block_rank(v, s_w, tot);
+        const int k = nv + block_rank<BE_NW>(v, s_w, tot);
         if (v) { w.vid[k] = in.fid[f]; w.vft[k] = f; }
         nv += tot;
     }
@@ -415,11 +357,11 @@ __global__ __launch_bounds__(BE_NT) void k_backend_insert(InsTables T, InsIn I, 
         const int s = base + t;
         bool fn = false;
         if (s < nv && (s == 0 || w.sid[s - 1] != w.sid[s])) {
-            const int m = be_bound(w.mp_id, nm, w.sid[s]);
+            const int m = lower_row(w.mp_id, nm, w.sid[s]);
             fn = !(m < nm && w.mp_id[m] == w.sid[s]);
         }
         int tot;
-        const int k = nu + be_block_rank(fn, s_w, tot);
+        const int k = nu + block_rank<BE_NW>(fn, s_w, tot);
         if (s < nv) w.dcum[s] = k;
         nu += tot;
     }
@@ -430,11 +372,11 @@ __global__ __launch_bounds__(BE_NT) void k_backend_insert(InsTables T, InsIn I, 
         bool u = false;
         if (p < np) {
             const int64_t id = in.pid[p];
-            const int m = be_bound(w.mp_id, nm, id), g = be_bound(w.sid, nv, id);
+            const int m = lower_row(w.mp_id, nm, id), g = lower_row(w.sid, nv, id);
             u = g < nv && w.sid[g] == id && !(m < nm && w.mp_id[m] == id);
         }
         int tot;
-        const int k = npu + be_block_rank(u, s_w, tot);
+        const int k = npu + block_rank<BE_NW>(u, s_w, tot);
         if (p < np) w.pcum[p] = k;
         npu += tot;
     }
@@ -476,21 +418,21 @@ __global__ __launch_bounds__(BE_NT) void k_backend_insert(InsTables T, InsIn I, 
         int len = 0, g = 0;
         if (m < nm) {
             const int64_t id = w.mp_id[m];
-            g = be_bound(w.sid, nv, id);
+            g = lower_row(w.sid, nv, id);
             if (removal && !(g < nv && w.sid[g] == id)) {
-                const int s0 = be_bound(w.obs_mp, no, m), e0 = be_bound(w.obs_mp, no, m + 1);
+                const int s0 = lower_row(w.obs_mp, no, m), e0 = lower_row(w.obs_mp, no, m + 1);
                 bool act = false;
                 for (int r = s0; r < e0; r++) act |= (w.obs_flags[r] & BE_ACTIVE) && w.obs_kf[r] != victim;
                 dead = !act; len = e0 - s0;
             }
         }
         int tot, rtot;
-        const int dm = ndm + be_block_rank(dead, s_w, tot);
-        const int dr = ndr + be_block_exsum(dead ? len : 0, s_w, rtot);
+        const int dm = ndm + block_rank<BE_NW>(dead, s_w, tot);
+        const int dr = ndr + block_exsum<BE_NW>(dead ? len : 0, s_w, rtot);
         if (m < nm) {
             w.dmp[m] = dm; w.drows[m] = dr;
             w.mp_fin[m] = dead ? -1 : m + w.dcum[g] - dm;
-            w.mp_shift[m] = g + w.pcum[be_bound(in.pid, np, w.mp_id[m])] - dr;
+            w.mp_shift[m] = g + w.pcum[lower_row(in.pid, np, w.mp_id[m])] - dr;
         }
         ndm += tot; ndr += rtot;
     }
@@ -526,7 +468,7 @@ __global__ __launch_bounds__(BE_NT) void k_backend_insert(InsTables T, InsIn I, 
     for (int s = t; s < nv; s += BE_NT) {
         const int64_t id = w.sid[s];
         const int f = w.sfeat[s];
-        const int lm = be_bound(w.mp_id, nm, id), g = be_bound(w.sid, nv, id);
+        const int lm = lower_row(w.mp_id, nm, id), g = lower_row(w.sid, nv, id);
         const bool in_table = lm < nm && w.mp_id[lm] == id;
         const int um = lm + (in_table ? 1 : 0);
         const int mrow = lm + w.dcum[g] - w.dmp[lm];
@@ -535,7 +477,7 @@ __global__ __launch_bounds__(BE_NT) void k_backend_insert(InsTables T, InsIn I, 
             tb.mp_pos[3 * mrow] = in.fpos[3 * f]; tb.mp_pos[3 * mrow + 1] = in.fpos[3 * f + 1]; tb.mp_pos[3 * mrow + 2] = in.fpos[3 * f + 2];
         }
         // the feature's row: behind the segment's old rows (or its prior rows), in feature order
-        const int dst = be_bound(w.obs_mp, no, um) + w.pcum[be_bound<int64_t, true>(in.pid, np, id)] + s - w.drows[um];
+        const int dst = lower_row(w.obs_mp, no, um) + w.pcum[upper_row(in.pid, np, id)] + s - w.drows[um];
         if ((unsigned)dst >= (unsigned)T.obs_cap) continue;            // cannot happen: the merged count passed the capacity check
         tb.obs_mp[dst] = mrow; tb.obs_kf[dst] = new_kf_row; tb.obs_flags[dst] = (uint8_t)(BE_ACTIVE | (in.fflags[f] & BE_OUTLIER));
         tb.obs_uv[2 * dst] = in.fuv[2 * f]; tb.obs_uv[2 * dst + 1] = in.fuv[2 * f + 1]; tb.obs_tag[dst] = in.ftag[f];
@@ -556,8 +498,8 @@ __global__ __launch_bounds__(BE_NT) void k_backend_insert(InsTables T, InsIn I, 
     for (int p = t; p < np; p += BE_NT) {
         if (w.pcum[p + 1] == w.pcum[p]) continue;
         const int64_t id = in.pid[p];
-        const int lm = be_bound(w.mp_id, nm, id), g = be_bound(w.sid, nv, id);
-        const int dst = be_bound(w.obs_mp, no, lm) + g + w.pcum[p] - w.drows[lm];
+        const int lm = lower_row(w.mp_id, nm, id), g = lower_row(w.sid, nv, id);
+        const int dst = lower_row(w.obs_mp, no, lm) + g + w.pcum[p] - w.drows[lm];
         if ((unsigned)dst >= (unsigned)T.obs_cap) continue;
         int k = -1;
         for (int i = 0; i <= nk; i++) k = s_kfid[i] == in.pkf[p] ? i : k;

@@ -6,12 +6,10 @@
 //   k_map_loop_inputs    the per-loop index inputs of myslam_loop_correct_batch;
 //   k_map_write_backend  the corrected poses and positions back into the back end's rows;
 //   k_map_feature_slots  map-point id -> archive slot per feature (myslam_loop_store_put_batch's d_feat_landmark).
-// Ids ascend in every table, so a row is found by binary search and a new row's slot is a closed form: no scans, no atomics; an item's bytes depend
+// Ids ascend in every table, so a row is found by binary search (sorted_rows.h) and a new row's slot is a closed form: no scans, no atomics; an item's bytes depend
 // neither on its slot nor on its neighbours.  The edge measurement uses se3_chain.h (chain.py's arithmetic, built with -ffp-contract=off).
 // See include/myslam_hip.h for the contract.
-#include <algorithm>
-
-#include "common.h"
+#include "dev_tables.h"
 #include "se3_chain.h"
 
 namespace myslam_hip {
@@ -41,38 +39,15 @@ struct MaTables {                       // the archive, strided by the caps; sna
     }
 };
 
-struct MaBackend {                      // the back end's tables as myslam_backend_* leaves them, read only here
-    const int64_t* kf_id; const double* kf_pose; const int32_t* n_kf;
-    const int64_t* mp_id; const double* mp_pos; const int32_t* n_mp;
-    const int32_t* obs_mp; const int32_t* obs_kf; const uint8_t* obs_flags; const int32_t* n_obs;
-    int kf_cap, mp_cap, obs_cap;
-    struct Item { const int64_t* kf_id; const double* kf_pose; const int64_t* mp_id; const double* mp_pos; const int32_t* obs_mp; const int32_t* obs_kf; const uint8_t* obs_flags; };
-    __device__ __forceinline__ Item item(int b) const {
-        const size_t k = (size_t)b * kf_cap, m = (size_t)b * mp_cap, o = (size_t)b * obs_cap;
-        return {kf_id + k, kf_pose + k * 7, mp_id + m, mp_pos + m * 3, obs_mp + o, obs_kf + o, obs_flags + o};
-    }
-};
-
-// first index in a[0, n) whose value is not below v; a ascending
-template <class T, class V>
-__device__ __forceinline__ int ma_lower(const T* a, int n, V v) {
-    int lo = 0, hi = n;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if ((V)a[mid] < v) lo = mid + 1; else hi = mid; }
-    return lo;
-}
-// row of id v in a[0, n), -1 if absent
-template <class T>
-__device__ __forceinline__ int ma_find(const T* a, int n, int64_t v) {
-    const int i = ma_lower(a, n, v);
-    return i < n && a[i] == v ? i : -1;
-}
+// The back end's tables as myslam_backend_* leaves them are dev_tables.h's view (BeTablesRead; BeTablesPose where poses and positions go back), with
+// nullptr for every column a call does not take: no kernel here reads mp_outlier, obs_uv or obs_tag.
 
 struct MaUpdateIn {
     int mode; const int32_t* be_status; const int64_t* outlier_id; const int32_t* n_outlier; int outlier_cap; const uint8_t* mp_report;
     const double* solve_pts; const int32_t* solve_slot;     // myslam_map_attach_solve: the solve's positions by landmark slot, the slot of every INPUT row
 };
 
-__global__ __launch_bounds__(MA_NT) void k_map_update(MaTables A, MaBackend B, MaUpdateIn U, int32_t* status) {
+__global__ __launch_bounds__(MA_NT) void k_map_update(MaTables A, BeTablesRead B, MaUpdateIn U, int32_t* status) {
     __shared__ int s_bad;
     __shared__ int s_kfrow[MA_MAX_BE_KF];                                   // archive row of every back-end key-frame row
     __shared__ int s_prev[MA_MAX_BE_KF];                                    // the same at the last update, and which of those rows have left since
@@ -97,19 +72,19 @@ __global__ __launch_bounds__(MA_NT) void k_map_update(MaTables A, MaBackend B, M
 
     // ---- decide: where every back-end row lives in the archive, what is new ----
     const int64_t last_kf = aK ? a.kf_id[aK - 1] : INT64_MIN, last_mp = aM ? a.mp_id[aM - 1] : INT64_MIN;
-    const int k0 = aK ? ma_lower(be.kf_id, nk, last_kf + 1) : 0;            // back-end key-frame rows from k0 on are above the archive's last id
-    const int m0 = aM ? ma_lower(be.mp_id, nm, last_mp + 1) : 0;
+    const int k0 = aK ? lower_row(be.kf_id, nk, last_kf + 1) : 0;            // back-end key-frame rows from k0 on are above the archive's last id
+    const int m0 = aM ? lower_row(be.mp_id, nm, last_mp + 1) : 0;
     const int newK = nk - k0, newM = nm - m0;
     if (t == 0) { s_bad = 0; s_left = 0u; }
     if (t < nwin) s_prev[t] = a.win_kf[t];
     __syncthreads();
     bool bad = false;
     if (t < nk) {
-        const int r = t < k0 ? ma_find(a.kf_id, aK, be.kf_id[t]) : aK + (t - k0);
+        const int r = t < k0 ? find_row(a.kf_id, aK, be.kf_id[t]) : aK + (t - k0);
         s_kfrow[t] = r;
         bad |= r < 0;                                                       // a key-frame id below the archive's last that it never saw
     }
-    for (int m = t; m < m0; m += MA_NT) bad |= ma_find(a.mp_id, aM, be.mp_id[m]) < 0;      // an unarchived id below the archive's last
+    for (int m = t; m < m0; m += MA_NT) bad |= find_row(a.mp_id, aM, be.mp_id[m]) < 0;      // an unarchived id below the archive's last
     if (!ins) bad |= newK > 0 || newM > 0 || nm > nsnap;                    // an optimise adds nothing
     if (bad) s_bad = 1;
     __syncthreads();
@@ -145,7 +120,7 @@ __global__ __launch_bounds__(MA_NT) void k_map_update(MaTables A, MaBackend B, M
         __syncthreads();                                                    // the outlier ids may name a row appended above; t == 0's pose of row aK - 1 is read
         // AddOutlierMapPoint (map.cpp): alive points only
         for (int j = t; j < nx; j += MA_NT) {
-            const int s = ma_find(a.mp_id, aM + newM, U.outlier_id[(size_t)b * U.outlier_cap + j]);
+            const int s = find_row(a.mp_id, aM + newM, U.outlier_id[(size_t)b * U.outlier_cap + j]);
             if (s >= 0 && a.mp_state[s] == 0) a.mp_state[s] = 1;
         }
     } else {
@@ -195,13 +170,13 @@ __global__ __launch_bounds__(MA_NT) void k_map_update(MaTables A, MaBackend B, M
     // ---- refresh: poses, positions, first observers; the snapshot ----
     for (int i = t; i < 7 * nk; i += MA_NT) a.kf_pose[7 * s_kfrow[i / 7] + i % 7] = be.kf_pose[i];
     for (int m = t; m < nm; m += MA_NT) {
-        const int s = m < m0 ? ma_lower(a.mp_id, aM, be.mp_id[m]) : aM + (m - m0);
+        const int s = m < m0 ? lower_row(a.mp_id, aM, be.mp_id[m]) : aM + (m - m0);
         a.mp_pos[3 * s] = be.mp_pos[3 * m]; a.mp_pos[3 * s + 1] = be.mp_pos[3 * m + 1]; a.mp_pos[3 * s + 2] = be.mp_pos[3 * m + 2];
         // GetObservations().front()->mpKF: both observation lists are in key-frame order, so the front is the lowest archive row among the rows whose
         // key-frame is in the window (the first of them) and the observers that left it
         int first = a.gone_kf[s];
         unsigned mask = 0;
-        for (int r = ma_lower(be.obs_mp, no, m); r < no && be.obs_mp[r] == m; r++) {
+        for (int r = lower_row(be.obs_mp, no, m); r < no && be.obs_mp[r] == m; r++) {
             const int k = be.obs_kf[r];
             if (k < 0 || k >= nk) continue;
             if (!mask) first = first < 0 ? s_kfrow[k] : min(first, s_kfrow[k]);
@@ -222,63 +197,62 @@ struct MaLoopIn { const int64_t* cur_kf_id; const uint64_t* loop_kf_id; const in
 struct MaLoopOut { int32_t* active; int32_t* n_active; int32_t* cur; int32_t* loop; int32_t* first_active; int32_t* first_kf; int32_t* n_points; };
 
 // grid (point_cap / MA_NT rounded up, batch): block (c, b) writes the point rows [c MA_NT, (c + 1) MA_NT) of item b, block (0, b) also the key-frame side
-__global__ __launch_bounds__(MA_NT) void k_map_loop_inputs(MaTables A, MaBackend B, MaLoopIn I, MaLoopOut O) {
+__global__ __launch_bounds__(MA_NT) void k_map_loop_inputs(MaTables A, BeTablesRead B, MaLoopIn I, MaLoopOut O) {
     const int b = blockIdx.y, c = blockIdx.x, t = threadIdx.x;
     const int64_t cur_id = I.cur_kf_id[b];
-    const int aK = min(max(A.n_kf[b], 0), A.kf_cap), aM = min(max(A.n_mp[b], 0), A.point_cap);
-    const int nk = min(min(max(B.n_kf[b], 0), B.kf_cap), I.active_cap), nm = min(max(B.n_mp[b], 0), B.mp_cap), no = min(max(B.n_obs[b], 0), B.obs_cap);
+    const int aK = clamped_count(A.n_kf, b, A.kf_cap), aM = clamped_count(A.n_mp, b, A.point_cap);
+    const int nk = min(clamped_count(B.n_kf, b, B.kf_cap), I.active_cap), nm = clamped_count(B.n_mp, b, B.mp_cap), no = clamped_count(B.n_obs, b, B.obs_cap);
     if (cur_id < 0) {                                                       // no key-frame this turn: myslam_loop_correct_batch skips the item on its verify status
         if (c == 0 && t == 0) { O.n_active[b] = 0; O.cur[b] = -1; O.loop[b] = -1; O.n_points[b] = 0; }
         return;
     }
     const auto a = A.item(b);
     const auto be = B.item(b);
-    if (c == 0 && t < nk) O.active[(size_t)b * I.active_cap + t] = ma_find(a.kf_id, aK, be.kf_id[t]);       // GetActiveKeyFrames(), :560
+    if (c == 0 && t < nk) O.active[(size_t)b * I.active_cap + t] = find_row(a.kf_id, aK, be.kf_id[t]);       // GetActiveKeyFrames(), :560
     if (c == 0 && t == 0) {
         O.n_active[b] = nk; O.n_points[b] = aM;
-        O.cur[b] = ma_find(a.kf_id, aK, cur_id);
+        O.cur[b] = find_row(a.kf_id, aK, cur_id);
         const uint64_t lid = I.loop_kf_id[b];
-        O.loop[b] = (I.detect_status[b] == MYSLAM_LOOP_DETECT_CANDIDATE && lid <= (uint64_t)INT64_MAX) ? ma_find(a.kf_id, aK, (int64_t)lid) : -1;
+        O.loop[b] = (I.detect_status[b] == MYSLAM_LOOP_DETECT_CANDIDATE && lid <= (uint64_t)INT64_MAX) ? find_row(a.kf_id, aK, (int64_t)lid) : -1;
     }
     const int s = c * MA_NT + t;
     if (s < aM) {
         int fa = -1;
-        const int m = ma_find(be.mp_id, nm, a.mp_id[s]);
+        const int m = find_row(be.mp_id, nm, a.mp_id[s]);
         if (m >= 0)                                                         // GetActiveObservations().front(): the first ACTIVE row of the segment
-            for (int r = ma_lower(be.obs_mp, no, m); r < no && be.obs_mp[r] == m; r++)
+            for (int r = lower_row(be.obs_mp, no, m); r < no && be.obs_mp[r] == m; r++)
                 if (be.obs_flags[r] & MYSLAM_BACKEND_OBS_ACTIVE) { fa = be.obs_kf[r]; break; }
         O.first_active[(size_t)b * A.point_cap + s] = fa;
         O.first_kf[(size_t)b * A.point_cap + s] = a.mp_state[s] == 2 ? -1 : a.mp_first_kf[s];     // :625-629: an erased point is skipped
     }
 }
 
-__global__ __launch_bounds__(MA_NT) void k_map_write_backend(MaTables A, const int64_t* be_kf_id, double* be_kf_pose, const int32_t* be_n_kf, int be_kf_cap,
-                                                              const int64_t* be_mp_id, double* be_mp_pos, const int32_t* be_n_mp, int be_mp_cap,
-                                                              const uint8_t* select) {
+__global__ __launch_bounds__(MA_NT) void k_map_write_backend(MaTables A, BeTablesPose B, const uint8_t* select) {
     const int b = blockIdx.x, t = threadIdx.x;
     if (select && !select[b]) return;
-    const int aK = min(max(A.n_kf[b], 0), A.kf_cap), aM = min(max(A.n_mp[b], 0), A.point_cap);
-    const int nk = min(max(be_n_kf[b], 0), be_kf_cap), nm = min(max(be_n_mp[b], 0), be_mp_cap);
+    const int aK = clamped_count(A.n_kf, b, A.kf_cap), aM = clamped_count(A.n_mp, b, A.point_cap);
+    const int nk = clamped_count(B.n_kf, b, B.kf_cap), nm = clamped_count(B.n_mp, b, B.mp_cap);
     const auto a = A.item(b);
+    const auto be = B.item(b);
     for (int i = t; i < 7 * nk; i += MA_NT) {
-        const int r = ma_find(a.kf_id, aK, be_kf_id[(size_t)b * be_kf_cap + i / 7]);
-        if (r >= 0) be_kf_pose[(size_t)b * be_kf_cap * 7 + i] = a.kf_pose[7 * r + i % 7];
+        const int r = find_row(a.kf_id, aK, be.kf_id[i / 7]);
+        if (r >= 0) be.kf_pose[i] = a.kf_pose[7 * r + i % 7];
     }
     for (int m = t; m < nm; m += MA_NT) {
-        const int s = ma_find(a.mp_id, aM, be_mp_id[(size_t)b * be_mp_cap + m]);
-        double* dst = be_mp_pos + ((size_t)b * be_mp_cap + m) * 3;
+        const int s = find_row(a.mp_id, aM, be.mp_id[m]);
+        double* dst = be.mp_pos + 3 * m;
         if (s >= 0) { dst[0] = a.mp_pos[3 * s]; dst[1] = a.mp_pos[3 * s + 1]; dst[2] = a.mp_pos[3 * s + 2]; }
     }
 }
 
 __global__ __launch_bounds__(MA_NT) void k_map_feature_slots(MaTables A, const int64_t* feat_mp_id, const int32_t* n_feat, int feat_cap, int32_t* feat_landmark) {
     const int b = blockIdx.y, f = blockIdx.x * MA_NT + threadIdx.x;
-    const int nf = min(max(n_feat[b], 0), feat_cap);
+    const int nf = clamped_count(n_feat, b, feat_cap);
     if (f >= nf) return;
-    const int aM = min(max(A.n_mp[b], 0), A.point_cap);
+    const int aM = clamped_count(A.n_mp, b, A.point_cap);
     const auto a = A.item(b);
     const int64_t id = feat_mp_id[(size_t)b * feat_cap + f];
-    const int s = id < 0 ? -1 : ma_find(a.mp_id, aM, id);
+    const int s = id < 0 ? -1 : find_row(a.mp_id, aM, id);
     feat_landmark[(size_t)b * feat_cap + f] = (s >= 0 && a.mp_state[s] != 2) ? s : -1;
 }
 
@@ -417,9 +391,9 @@ int myslam_map_get(myslam_map* h, int item, int64_t* kf_id, double* kf_pose, int
     if ((rc = down(&c[0], t.n_kf + b, 4)) || (rc = down(&c[1], t.n_edges + b, 4)) || (rc = down(&c[2], t.n_mp + b, 4)) || (rc = down(&c[3], t.n_snap + b, 4)) ||
         (rc = down(&c[4], t.n_win + b, 4)))
         return rc;
-    const size_t nK = (size_t)std::min(std::max(c[0], 0), t.kf_cap), nE = (size_t)std::min(std::max(c[1], 0), t.edge_cap);
-    const size_t nP = (size_t)std::min(std::max(c[2], 0), t.point_cap), nS = (size_t)std::min(std::max(c[3], 0), t.be_mp_cap);
-    const size_t nW = (size_t)std::min(std::max(c[4], 0), MA_MAX_BE_KF);
+    const size_t nK = (size_t)clamped_count(c[0], t.kf_cap), nE = (size_t)clamped_count(c[1], t.edge_cap);
+    const size_t nP = (size_t)clamped_count(c[2], t.point_cap), nS = (size_t)clamped_count(c[3], t.be_mp_cap);
+    const size_t nW = (size_t)clamped_count(c[4], MA_MAX_BE_KF);
     if ((rc = down(kf_id, t.kf_id + b * K, nK * sizeof(int64_t))) || (rc = down(kf_pose, t.kf_pose + b * K * 7, nK * 7 * sizeof(double))) ||
         (rc = down(edge_v0, t.edge_v0 + b * E, nE * sizeof(int32_t))) || (rc = down(edge_v1, t.edge_v1 + b * E, nE * sizeof(int32_t))) ||
         (rc = down(meas, t.meas + b * E * 7, nE * 7 * sizeof(double))) || (rc = down(mp_id, t.mp_id + b * P, nP * sizeof(int64_t))) ||
@@ -450,7 +424,8 @@ int myslam_map_update_batch(myslam_map* h, int mode, const int64_t* d_kf_id, con
     if (batch > h->max_batch) return MYSLAM_ERR_CAPACITY;
     if (batch == 0) return MYSLAM_OK;
     const bool ins = mode == MYSLAM_MAP_AFTER_INSERT;
-    const MaBackend B{d_kf_id, d_kf_pose, d_n_kf, d_mp_id, d_mp_pos, d_n_mp, d_obs_mp, d_obs_kf, d_obs_flags, d_n_obs, be_kf_cap, be_mp_cap, be_obs_cap};
+    const BeTablesRead B{d_kf_id, d_kf_pose, d_n_kf, d_mp_id, d_mp_pos, nullptr, d_n_mp, d_obs_mp, d_obs_kf, d_obs_flags, nullptr, nullptr, d_n_obs,
+                         be_kf_cap, be_mp_cap, be_obs_cap};
     const MaUpdateIn U{mode, d_backend_status, ins ? d_outlier_mp_id : nullptr, ins ? d_n_outlier_mp : nullptr, (ins && d_n_outlier_mp) ? outlier_cap : 0,
                        d_mp_report, ins ? nullptr : h->solve_pts, ins ? nullptr : h->solve_slot};
     hipLaunchKernelGGL(k_map_update, dim3(batch), dim3(MA_NT), 0, h->stream, h->t, B, U, d_status);
@@ -470,7 +445,8 @@ int myslam_map_loop_inputs_batch(myslam_map* h, const int64_t* d_kf_id, const in
         return MYSLAM_ERR_INVALID;
     if (batch > h->max_batch) return MYSLAM_ERR_CAPACITY;
     if (batch == 0) return MYSLAM_OK;
-    const MaBackend B{d_kf_id, nullptr, d_n_kf, d_mp_id, nullptr, d_n_mp, d_obs_mp, d_obs_kf, d_obs_flags, d_n_obs, be_kf_cap, be_mp_cap, be_obs_cap};
+    const BeTablesRead B{d_kf_id, nullptr, d_n_kf, d_mp_id, nullptr, nullptr, d_n_mp, d_obs_mp, d_obs_kf, d_obs_flags, nullptr, nullptr, d_n_obs,
+                         be_kf_cap, be_mp_cap, be_obs_cap};
     const MaLoopIn I{d_cur_kf_id, d_loop_kf_id, d_detect_status, active_cap};
     const MaLoopOut O{d_active, d_n_active, d_cur, d_loop, d_first_active, d_first_kf, d_n_points};
     hipLaunchKernelGGL(k_map_loop_inputs, dim3((h->t.point_cap + MA_NT - 1) / MA_NT, batch), dim3(MA_NT), 0, h->stream, h->t, B, I, O);
@@ -484,8 +460,9 @@ int myslam_map_write_backend_batch(myslam_map* h, const int64_t* d_kf_id, double
         return MYSLAM_ERR_INVALID;
     if (batch > h->max_batch) return MYSLAM_ERR_CAPACITY;
     if (batch == 0) return MYSLAM_OK;
-    hipLaunchKernelGGL(k_map_write_backend, dim3(batch), dim3(MA_NT), 0, h->stream, h->t, d_kf_id, d_kf_pose, d_n_kf, be_kf_cap, d_mp_id, d_mp_pos, d_n_mp,
-                       be_mp_cap, d_select);
+    const BeTablesPose B{d_kf_id, d_kf_pose, d_n_kf, d_mp_id, d_mp_pos, nullptr, d_n_mp, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                         be_kf_cap, be_mp_cap, 0};
+    hipLaunchKernelGGL(k_map_write_backend, dim3(batch), dim3(MA_NT), 0, h->stream, h->t, B, d_select);
     MYSLAM_HIP_CHECK(hipGetLastError());
     return MYSLAM_OK;
 }

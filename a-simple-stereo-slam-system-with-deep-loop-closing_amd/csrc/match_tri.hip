@@ -10,7 +10,7 @@
 #include <utility>
 #include <vector>
 
-#include "common.h"
+#include "dev_tables.h"
 #include "tri_solve.h"
 
 namespace myslam_hip {
@@ -222,8 +222,8 @@ __global__ __launch_bounds__(256) void k_triangulate(const float* __restrict__ x
 // LoopClosing::MatchFeatures after the matcher (src/loopclosing.cpp:175-198) and the point gather at the top of ComputeCorrectPose (:210-253)
 // for one loop candidate per workgroup: what myslam_match_feature_pairs and its callers' gather loops do on the host, on the matcher's output
 // where it lies.  The reference's std::set<std::pair<int,int>> becomes a sort of the keys (current id << 16 | loop id) in LDS followed by
-// adjacent-unique; every list is written by an ORDERED compaction (wave ballot + mbcnt, wave totals through LDS), so a slot never depends on
-// which wave came first.
+// adjacent-unique; every list is written by an ORDERED compaction (dev_tables.h's block_rank in its run-time form: the launch picks the block
+// size), so a slot never depends on which wave came first.
 constexpr int LM_MAX_CAP = 16384;                 // keys of one item in LDS: 64 KB
 constexpr int LM_MAX_FEAT = 65536;                // a feature id is half a key
 constexpr int LM_MAX_OUT = 4096;                  // match slots of the verify handle (myslam_pnp_create)
@@ -241,26 +241,12 @@ struct LoopPairsArgs {
     float* pts3d; float* pts2d; int32_t* counts; int32_t* status;
 };
 
-// rank of this thread's element among the block's flagged ones, in thread order; total = their number (block-uniform).  s_w: one int per wave.
-__device__ __forceinline__ int block_rank(bool f, int* s_w, int& total) {
-    const int wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    const unsigned long long m = __ballot(f);
-    const int in_wave = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-    if ((threadIdx.x & 63) == 0) s_w[wv] = __popcll(m);
-    __syncthreads();
-    int before = 0, tot = 0;
-    for (int w = 0; w < nw; w++) { const int c = s_w[w]; before += (w < wv) ? c : 0; tot += c; }
-    __syncthreads();                                         // s_w is free again
-    total = tot;
-    return before + in_wave;
-}
-
 __global__ __launch_bounds__(1024) void k_loop_pairs(LoopPairsArgs a) {
     MYSLAM_SIDE_PRIO();
     extern __shared__ uint32_t s_keys[];                     // next power of two >= cap keys
     __shared__ int s_w[16], s_red[16];
     const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, wv = tid >> 6, nw = nt >> 6;
-    const int nl = min(max(a.n_loop[b], 0), a.cap), nc = min(max(a.n_cur[b], 0), a.cap);
+    const int nl = clamped_count(a.n_loop, b, a.cap), nc = clamped_count(a.n_cur, b, a.cap);
     const size_t row0 = (size_t)b * a.cap, feat0 = (size_t)b * a.feat_cap;
     auto finish = [&](int status, int count) { if (tid == 0) { a.status[b] = status; a.counts[b] = count; } };
     if (nl == 0 || nc == 0) {                                // an empty side: no match, an empty set

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "dev_tables.h"
 #include "frontend_launch.h"
 #include "se3_chain.h"
 #include "tri_solve.h"
@@ -61,20 +62,8 @@ struct TrkArgs {
     double* kfPos; uint8_t* kfOutl; int64_t* kfId;            // S x lmCap: the rebuilt landmark table before it is committed
 };
 
-// exclusive rank of `flag` among the block's threads (thread order) and the block's total; s_w: one int per wave.  Two barriers.
-__device__ __forceinline__ int block_rank(bool flag, int* s_w, int& total) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const unsigned long long m = __ballot(flag);
-    const int inWave = __popcll(m & ((1ull << lane) - 1ull));
-    __syncthreads();                                                           // s_w of the previous use has been read
-    if (lane == 0) s_w[wv] = __popcll(m);
-    __syncthreads();
-    int before = 0; total = 0;
-#pragma unroll
-    for (int k = 0; k < TRK_NT / 64; k++) { const int c = s_w[k]; if (k < wv) before += c; total += c; }
-    return before + inWave;
-}
-
+// ordered positions among a stream's features, TRK_NT at a time, come from dev_tables.h's block_rank<TRK_NW> (its contract is stated there)
+constexpr int TRK_NW = TRK_NT / WAVE;
 // ---- the pieces the step, the key-frame turn and StereoInit are built from: each rule below has this one definition ----
 // stream s's image buffer `slot` (rows packed at `cols` bytes; every buffer starts on a 256-byte boundary)
 __device__ __forceinline__ uint8_t* trk_image(const TrkArgs& a, int s, int slot) { return a.img + (size_t)slot * a.imgSel + (size_t)s * a.imgBytes; }
@@ -167,7 +156,7 @@ __global__ __launch_bounds__(TRK_NT) void k_trk_head(TrkArgs a) {
 
 // ---- rule 3: one block per stream, ballot + prefix per 256 features, order kept ----
 __global__ __launch_bounds__(TRK_NT) void k_trk_compact(TrkArgs a) {
-    __shared__ int s_w[TRK_NT / 64];
+    __shared__ int s_w[TRK_NW];
     const int s = blockIdx.x, t = threadIdx.x;
     if (a.sel[s] < 0) return;
     const int n = a.counts[s];
@@ -184,7 +173,7 @@ __global__ __launch_bounds__(TRK_NT) void k_trk_compact(TrkArgs a) {
             po = keep && !outl[l];
         }
         int tk, tp;
-        const int rk = block_rank(keep, s_w, tk), rp = block_rank(po, s_w, tp);
+        const int rk = block_rank<TRK_NW>(keep, s_w, tk), rp = block_rank<TRK_NW>(po, s_w, tp);
         if (keep) {
             const int j = nKeep + rk;
             const float x = a.nxt[(fb + i) * 2], y = a.nxt[(fb + i) * 2 + 1];
@@ -204,7 +193,7 @@ __global__ __launch_bounds__(TRK_NT) void k_trk_compact(TrkArgs a) {
 
 // ---- rules 5 + 6: one block per stream ----
 __global__ __launch_bounds__(TRK_NT) void k_trk_tail(TrkArgs a) {
-    __shared__ int s_w[TRK_NT / 64];
+    __shared__ int s_w[TRK_NW];
     const int s = blockIdx.x, t = threadIdx.x;
     if (a.sel[s] < 0) return;
     TrkState& st = a.st[s];
@@ -225,7 +214,7 @@ __global__ __launch_bounds__(TRK_NT) void k_trk_tail(TrkArgs a) {
             o = k >= 0 && a.poOutl[fb + k] != 0;
         }
         int tot;
-        const int r = block_rank(o && fresh, s_w, tot);
+        const int r = block_rank<TRK_NW>(o && fresh, s_w, tot);
         if (o && fresh) {
             lmOutl[l] = 1;
             if (nList + r < listCap) list[nList + r] = l;
@@ -372,7 +361,7 @@ __global__ __launch_bounds__(TRK_NT) void k_kf_head(TrkArgs a, KfArgs k) {
     const int s = blockIdx.y, t = threadIdx.x;
     const TrkState& st = a.st[s];
     const bool el = kf_eligible(st);
-    const int n = st.n_feat, nNew = min(max(k.nNew[s], 0), k.kpCap), m = n + nNew;
+    const int n = st.n_feat, nNew = clamped_count(k.nNew, s, k.kpCap), m = n + nNew;
     const bool go = el && m <= a.cap;
     if (blockIdx.x > 0) {
         if (go) copy_image_rows(a, blockIdx.x - 1, k.right + (size_t)s * k.stride, k.step, trk_image(a, s, 1 - st.slot));
@@ -411,12 +400,12 @@ __global__ __launch_bounds__(TRK_NT) void k_kf_head(TrkArgs a, KfArgs k) {
 
 // ---- turn tail: rules d - g, one block per stream.  Everything is built in scratch and in the output arrays; the state is written last ----
 __global__ __launch_bounds__(TRK_NT) void k_kf_tail(TrkArgs a, KfArgs k) {
-    __shared__ int s_w[TRK_NT / 64];
+    __shared__ int s_w[TRK_NW];
     __shared__ double sTcw[16], sTwc[16];
     const int s = blockIdx.x, t = threadIdx.x;
     TrkState& st = a.st[s];
     const int code = a.kfCode[s];
-    const int n = st.n_feat, nNew = min(max(k.nNew[s], 0), k.kpCap), m = n + nNew, nLm = st.n_lm, nOutl = st.n_outl;
+    const int n = st.n_feat, nNew = clamped_count(k.nNew, s, k.kpCap), m = n + nNew, nLm = st.n_lm, nOutl = st.n_outl;
     const int frameId = st.next_frame_id - 1;            // the frame the last step tracked
     // no turn: the stream keeps every byte
     if (code != KF_GO) { refuse(k, s, st, code == KF_CAPACITY ? MYSLAM_ERR_CAPACITY : MYSLAM_TRACKER_NO_TURN, frameId, nNew, 0); return; }
@@ -447,8 +436,8 @@ __global__ __launch_bounds__(TRK_NT) void k_kf_tail(TrkArgs a, KfArgs k) {
             opens = tri || (l >= 0 && __hip_atomic_load(&a.kfFirst[lb + l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == i);
         }
         int tt, ts, tr;
-        const int rt = block_rank(tri, s_w, tt), rs = block_rank(opens, s_w, ts);
-        (void)block_rank(rok, s_w, tr);
+        const int rt = block_rank<TRK_NW>(tri, s_w, tt), rs = block_rank<TRK_NW>(opens, s_w, ts);
+        (void)block_rank<TRK_NW>(rok, s_w, tr);
         if (i < m) {
             const int slot = opens ? nSlots + rs : -1;
             a.kfSlot[fb + i] = slot;
@@ -487,33 +476,23 @@ __global__ __launch_bounds__(TRK_NT) void k_kf_tail(TrkArgs a, KfArgs k) {
 }
 
 // ---- the map moved under the tracker (back end, loop closer): landmarks and the reference pose follow their ids ----
-struct MapArgs {
-    const int64_t* kfId; const double* kfPose; const int32_t* nKf; int kfCap;
-    const int64_t* mpId; const double* mpPos; const uint8_t* mpOutl; const int32_t* nMp; int mpCap;
-};
-
-__device__ __forceinline__ int find_id(const int64_t* ids, int n, int64_t id) {      // ids ascend; -1 = absent
-    int lo = 0, hi = n;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (ids[mid] < id) lo = mid + 1; else hi = mid; }
-    return (lo < n && ids[lo] == id) ? lo : -1;
-}
-
-__global__ __launch_bounds__(TRK_NT) void k_kf_update(TrkArgs a, MapArgs g) {
+// (g: dev_tables.h's view of the back end's tables; the observation columns are not given)
+__global__ __launch_bounds__(TRK_NT) void k_kf_update(TrkArgs a, BeTablesRead g) {
     const int s = blockIdx.x, t = threadIdx.x;
     TrkState& st = a.st[s];
     if (st.frozen != 0 || st.idsValid == 0) return;
     const size_t lb = (size_t)s * a.lmCap;
-    const int nMp = min(max(g.nMp[s], 0), g.mpCap), nKf = min(max(g.nKf[s], 0), g.kfCap);
-    const int64_t* mpId = g.mpId + (size_t)s * g.mpCap;
+    const int nMp = clamped_count(g.n_mp, s, g.mp_cap), nKf = clamped_count(g.n_kf, s, g.kf_cap);
+    const auto m = g.item(s);
     for (int l = t; l < st.n_lm; l += TRK_NT) {
-        const int r = find_id(mpId, nMp, a.lmId[lb + l]);
+        const int r = find_row(m.mp_id, nMp, a.lmId[lb + l]);
         if (r < 0) continue;
-        for (int c = 0; c < 3; c++) a.lmPos[(lb + l) * 3 + c] = g.mpPos[((size_t)s * g.mpCap + r) * 3 + c];
-        a.lmOutl[lb + l] = g.mpOutl[(size_t)s * g.mpCap + r];
+        for (int c = 0; c < 3; c++) a.lmPos[(lb + l) * 3 + c] = m.mp_pos[3 * r + c];
+        a.lmOutl[lb + l] = m.mp_outlier[r];
     }
     if (t == 0) {
-        const int r = find_id(g.kfId + (size_t)s * g.kfCap, nKf, a.ids[(size_t)s * 3]);
-        if (r >= 0) for (int c = 0; c < 7; c++) st.ref_pose[c] = g.kfPose[((size_t)s * g.kfCap + r) * 7 + c];
+        const int r = find_row(m.kf_id, nKf, a.ids[(size_t)s * 3]);
+        if (r >= 0) for (int c = 0; c < 7; c++) st.ref_pose[c] = m.kf_pose[7 * r + c];
     }
 }
 
@@ -545,7 +524,7 @@ __global__ __launch_bounds__(TRK_NT) void k_init_head(TrkArgs a, KfArgs k, const
     const int s = blockIdx.y, t = threadIdx.x;
     const TrkState& st = a.st[s];
     const bool el = init_eligible(st);
-    const int m = min(max(k.nNew[s], 0), k.kpCap);
+    const int m = clamped_count(k.nNew, s, k.kpCap);
     const bool go = el && m <= a.cap;
     if (blockIdx.x > 0) {
         if (!go) return;
@@ -570,11 +549,11 @@ __global__ __launch_bounds__(TRK_NT) void k_init_head(TrkArgs a, KfArgs k, const
 
 // ---- init tail: rules c - g, one block per stream.  Everything is built in scratch and in the output arrays; the state is written last ----
 __global__ __launch_bounds__(TRK_NT) void k_init_tail(TrkArgs a, KfArgs k, int initGood) {
-    __shared__ int s_w[TRK_NT / 64];
+    __shared__ int s_w[TRK_NW];
     const int s = blockIdx.x, t = threadIdx.x;
     TrkState& st = a.st[s];
     const int code = a.kfCode[s];
-    const int m = min(max(k.nNew[s], 0), k.kpCap);
+    const int m = clamped_count(k.nNew, s, k.kpCap);
     if (code == KF_NO_TURN) { refuse(k, s, st, MYSLAM_TRACKER_NO_TURN, st.next_frame_id - 1, m, 0); return; }
     const int frameId = st.next_frame_id;                    // the Frame that GrabStereoImage constructed
     if (code != KF_GO) { refuse(k, s, st, MYSLAM_ERR_CAPACITY, frameId, m, 0); return; }
@@ -591,8 +570,8 @@ __global__ __launch_bounds__(TRK_NT) void k_init_tail(TrkArgs a, KfArgs k, int i
             tri = triangulate_feature(a, k.baseline, fb + i, rok, X);            // mvpFeaturesRight[i] != nullptr (:394)
         }
         int tt, tr;
-        const int rt = block_rank(tri, s_w, tt);
-        (void)block_rank(rok, s_w, tr);
+        const int rt = block_rank<TRK_NW>(tri, s_w, tt);
+        (void)block_rank<TRK_NW>(rok, s_w, tr);
         if (i < m) {
             const int slot = tri ? nTri + rt : -1;
             a.kfSlot[fb + i] = slot;
@@ -1008,7 +987,7 @@ int myslam_tracker_debug_freeze(myslam_tracker* h, int s, int why) {
 int myslam_tracker_update_from_map_batch(myslam_tracker* h, const int64_t* d_kf_id, const double* d_kf_pose, const int32_t* d_n_kf, int kf_cap,
                                          const int64_t* d_mp_id, const double* d_mp_pos, const uint8_t* d_mp_outlier, const int32_t* d_n_mp, int mp_cap) {
     if (!h || !d_kf_id || !d_kf_pose || !d_n_kf || kf_cap < 1 || !d_mp_id || !d_mp_pos || !d_mp_outlier || !d_n_mp || mp_cap < 1) return MYSLAM_ERR_INVALID;
-    const MapArgs g{d_kf_id, d_kf_pose, d_n_kf, kf_cap, d_mp_id, d_mp_pos, d_mp_outlier, d_n_mp, mp_cap};
+    const BeTablesRead g{d_kf_id, d_kf_pose, d_n_kf, d_mp_id, d_mp_pos, d_mp_outlier, d_n_mp, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, kf_cap, mp_cap, 0};
     hipLaunchKernelGGL(k_kf_update, dim3(h->S), dim3(TRK_NT), 0, h->stream, h->a, g);
     MYSLAM_HIP_CHECK(hipGetLastError());
     return MYSLAM_OK;

@@ -237,8 +237,8 @@ def cases():
     # scan and chunk edges of the 512-thread workgroup
     for n_obs in (0, 1, 511, 512, 513, 1025):
         c["obs_%d" % n_obs] = sized_case(max(1, n_obs // 3), n_obs, 40, 0x100 + n_obs)
-    for n_feat in (0, 1, 64, 65, 513):
+    for n_feat in (0, 1, 64, 65, 511, 512, 513):
         c["feat_%d" % n_feat] = sized_case(100, 300, n_feat, 0x200 + n_feat)
-    for n_mp in (1, 512, 513):
+    for n_mp in (1, 511, 512, 513):
         c["mp_%d" % n_mp] = sized_case(n_mp, 2 * n_mp + 1, 70, 0x300 + n_mp)
     return c

@@ -232,6 +232,33 @@ def test_shapes(api, synth):
     check_against_walk(r, r.host, out, [m])
 
 
+def test_counts_around_the_block_size(api, synth):
+    """n map points with one ACTIVE row each on one key-frame, n = 511, 512, 513: the edge of the 512-thread block's chunk in the edge and landmark
+    scans of the flatten and in both compactions of the write-back.  Every fifth map point is an input outlier, so map points and rows on both sides
+    of the edge move down by a different number of places."""
+    K = br.make_map(synth, 1, n_kf=2, n_mp=3)[1]
+    sizes = (511, 512, 513)
+    maps = []
+    for n in sizes:
+        rng = np.random.default_rng(n)
+        m = br.Map(); m.kfs[4] = np.array([0, 0, 0, 1, 0, 0, 0.0])
+        for j in range(n):
+            pos = np.array([rng.uniform(-3, 3), rng.uniform(-1, 1), rng.uniform(8, 20)])
+            mp = br.MapPoint(100 + 3 * j, pos, outlier=j % 5 == 2)
+            o = br.Obs(4, K[0] * pos[0] / pos[2] + K[2], K[1] * pos[1] / pos[2] + K[3], False, 1000 + j)
+            mp.obs.append(o); mp.active_obs.append(o); m.mps[mp.id] = mp
+            if mp.outlier:
+                m.outlier_list.append(mp.id)
+        maps.append(m)
+    r, out = run(api, maps, K)
+    assert [(int(r.host["n_mp"][b]), int(r.host["n_obs"][b])) for b in range(3)] == [(n, n) for n in sizes]
+    check_against_walk(r, r.host, out, maps)
+    for b, n in enumerate(sizes):
+        left = n - len(range(2, n, 5))
+        assert out["n_mp"][b] == out["n_obs"][b] == left and len(r.h.debug_flat(b)["edge_src"]) == left
+        assert (out["mp_report"][b, :n] == np.where(np.arange(n) % 5 == 2, 2, 0)).all() and (out["obs_report"][b, :n] == out["mp_report"][b, :n]).all()
+
+
 def _bad_cases(good, K, synth):
     """name -> (mutation of the packed tables of item 1, expected status)"""
     def set_(name, idx, val):

@@ -266,6 +266,17 @@ def test_kept_row_counts_around_the_sort_padding(api, oracle):
 
 
 @gpu
+def test_kept_row_counts_around_the_1024_thread_block(api, oracle):
+    """cap 2048 launches the pair stage with 1024 threads (the counts above cross its 256-thread form's chunk edge): 1023, 1024 and 1025 kept rows,
+    as many distinct pairs, and the eighth of them whose loop feature has a map point in the gather"""
+    ks = (1023, 1024, 1025)
+    r, es = run_and_check(api, oracle, [kept_item(k) for k in ks], cap=2048, out_cap=256)
+    for k, e in zip(ks, es):
+        assert (e["dist"] <= 30).sum() == k and (e["dist"] == 50).sum() == 20
+        assert len(e["pairs"]) == k and e["status"] == OK and e["count"] == k // 64 * 8 + min(k % 64, 8)
+
+
+@gpu
 def test_empty_sides_and_clamped_counts(api, oracle):
     full_loop = kept_item(0, n_rows=CAP); full_loop.n_loop = CAP + 5
     full_cur = scene(7, [(g, g, g % 5) for g in range(20)], cur_levels=8); full_cur.n_cur = CAP + 5
