@@ -65,29 +65,12 @@ __device__ __forceinline__ void ba_edge(const double* R, const double* pw, const
 
 typedef double ba_d4 __attribute__((ext_vector_type(4)));
 
-// f64 wave sum on the DPP network (no LDS crossbar): the total lands in lane 63
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_shift_add(double v) {
-    const int lo = __double2loint(v), hi = __double2hiint(v);
-    const int lo2 = __builtin_amdgcn_update_dpp(0, lo, CTRL, ROW_MASK, 0xf, false);
-    const int hi2 = __builtin_amdgcn_update_dpp(0, hi, CTRL, ROW_MASK, 0xf, false);
-    return v + __hiloint2double(hi2, lo2);
-}
-__device__ __forceinline__ double wave_sum_lane63(double v) {
-    v = dpp_shift_add<0xB1, 0xf>(v);      // quad_perm [1,0,3,2]
-    v = dpp_shift_add<0x4E, 0xf>(v);      // quad_perm [2,3,0,1]
-    v = dpp_shift_add<0x141, 0xf>(v);     // row_half_mirror
-    v = dpp_shift_add<0x140, 0xf>(v);     // row_mirror: every lane holds its 16-lane row sum
-    v = dpp_shift_add<0x142, 0xa>(v);     // row_bcast15 into rows 1 and 3
-    v = dpp_shift_add<0x143, 0xc>(v);     // row_bcast31 into rows 2 and 3
-    return v;
-}
 // 32 f64 wave sums at once by halving: each step exchanges HALF of the values a lane still holds with a partner lane and adds the other half,
 // so 32 values cost 16 + 8 + 4 + 2 + 1 + 1 exchange-and-add steps instead of 32 x 6 (v_permlane32/16_swap for the two widest steps: one
 // instruction moves both directions).  On return lane l holds the total of value l >> 1 in h[0] (both lanes of a pair).
 template <int CTRL>
-__device__ __forceinline__ double dpp_fetch(double v) {
-    return __hiloint2double(__builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false), __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false));
+__device__ __forceinline__ double dpp_fetch(double v) {      // dpp_mov (wave_ops.h) of both halves, the high one first as this kernel was scheduled with
+    return __hiloint2double(dpp_mov<CTRL, 0xf>(__double2hiint(v)), dpp_mov<CTRL, 0xf>(__double2loint(v)));
 }
 __device__ __forceinline__ void wave_sum32_halving(double* h, int lane) {
 #pragma unroll

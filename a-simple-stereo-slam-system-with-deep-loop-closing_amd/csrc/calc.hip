@@ -66,11 +66,6 @@ __global__ __launch_bounds__(256) void k_lcd_input(const uint8_t* __restrict__ s
 // responses from an 8 x 8 source window — the blur is exact integer arithmetic ((sum_r q_r sum_c q_c p + 32768) >> 16, no
 // intermediate rounding), so the results equal the two-pass kernel's bit for bit.  REFLECT_101 rows by index; a window that leaves
 // the image sideways takes the byte-wise path.
-__device__ __forceinline__ int lcd_reflect101(int p, int len) {
-    if (len == 1) return 0;
-    while (p < 0 || p >= len) p = (p < 0) ? -p : 2 * len - 2 - p;
-    return p;
-}
 struct LcdTaps { int q[7]; };
 __global__ __launch_bounds__(256) void k_lcd_input_fused(const uint8_t* __restrict__ src, int sw, int sh, int spitch, size_t sstride,
                                                          const int32_t* __restrict__ xofs, const int16_t* __restrict__ xa,
@@ -102,12 +97,12 @@ __global__ __launch_bounds__(256) void k_lcd_input_fused(const uint8_t* __restri
     } else {                                                       // border outputs: byte-wise with REFLECT_101 indices
 #pragma unroll 1
         for (int j = 0; j < 8; j++) {
-            const uint8_t* row = img + (size_t)lcd_reflect101(sy0 - 3 + j, sh) * spitch;
+            const uint8_t* row = img + (size_t)reflect101(sy0 - 3 + j, sh) * spitch;
             uint32_t a = 0, c = 0;
 #pragma unroll 1
             for (int k = 0; k < 7; k++) {
-                a += (uint32_t)tp.q[k] * row[lcd_reflect101(sx - 3 + k, sw)];
-                c += (uint32_t)tp.q[k] * row[lcd_reflect101(sx1 - 3 + k, sw)];
+                a += (uint32_t)tp.q[k] * row[reflect101(sx - 3 + k, sw)];
+                c += (uint32_t)tp.q[k] * row[reflect101(sx1 - 3 + k, sw)];
             }
             // (dynamic index into a register array: kept out of the fast path)
 #pragma unroll
@@ -271,17 +266,6 @@ __global__ __launch_bounds__(256) void k_conv1_pool_lrn2(const float* __restrict
     if (row1 && col1) lrn_store(m11, oy + 1, ox + 1);
 }
 
-// f32 wave sum on the DPP network; the total lands in lane 63
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ float dpp_add_f32(float v) {
-    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
-}
-__device__ __forceinline__ float wave_sum_lane63_f32(float v) {
-    v = dpp_add_f32<0xB1, 0xf>(v); v = dpp_add_f32<0x4E, 0xf>(v); v = dpp_add_f32<0x141, 0xf>(v); v = dpp_add_f32<0x140, 0xf>(v);
-    v = dpp_add_f32<0x142, 0xa>(v); v = dpp_add_f32<0x143, 0xc>(v);
-    return v;
-}
-
 constexpr int CV_BN = 128;
 
 // ---- conv2 + ReLU as an implicit GEMM on the bf16 matrix cores with fp32 accuracy ----
@@ -296,17 +280,6 @@ constexpr int CV_BN = 128;
 // Block tile 128 x 128, 4 waves x (2 x 2) tiles, BK = 16 = one MFMA K: 24 MFMAs of 32 cycles per wave and stage against
 // 32 x 64 cycles for the f32 form.
 typedef __bf16 cv_bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ void cv_split3(float a0, float a1, uint32_t& h, uint32_t& m, uint32_t& l) {    // two elements per dword, a0 low
-    const __bf16 h0 = (__bf16)a0, h1 = (__bf16)a1;
-    const float r0 = a0 - (float)h0, r1 = a1 - (float)h1;
-    const __bf16 m0 = (__bf16)r0, m1 = (__bf16)r1;
-    const float q0 = r0 - (float)m0, q1 = r1 - (float)m1;
-    const __bf16 l0 = (__bf16)q0, l1 = (__bf16)q1;
-    h = (uint32_t)__builtin_bit_cast(unsigned short, h0) | ((uint32_t)__builtin_bit_cast(unsigned short, h1) << 16);
-    m = (uint32_t)__builtin_bit_cast(unsigned short, m0) | ((uint32_t)__builtin_bit_cast(unsigned short, m1) << 16);
-    l = (uint32_t)__builtin_bit_cast(unsigned short, l0) | ((uint32_t)__builtin_bit_cast(unsigned short, l1) << 16);
-}
 
 __global__ __launch_bounds__(256) void k_conv2_bf16x6(const float* __restrict__ in /*[B][31*41][64]*/,
                                                       const uint4* __restrict__ wt3 /*[64 stages][3][128 n][2 k-halves] x 8 bf16*/,
@@ -347,8 +320,8 @@ __global__ __launch_bounds__(256) void k_conv2_bf16x6(const float* __restrict__ 
     auto store_stage = [&](int buf) {
         const float z = rav ? 1.f : 0.f;
         uint4 h, m, l;
-        cv_split3(ra0.x * z, ra0.y * z, h.x, m.x, l.x); cv_split3(ra0.z * z, ra0.w * z, h.y, m.y, l.y);
-        cv_split3(ra1.x * z, ra1.y * z, h.z, m.z, l.z); cv_split3(ra1.z * z, ra1.w * z, h.w, m.w, l.w);
+        bf16_split3(ra0.x * z, ra0.y * z, h.x, m.x, l.x); bf16_split3(ra0.z * z, ra0.w * z, h.y, m.y, l.y);
+        bf16_split3(ra1.x * z, ra1.y * z, h.z, m.z, l.z); bf16_split3(ra1.z * z, ra1.w * z, h.w, m.w, l.w);
         const int si = akh * KH + am;                                     // (row, k half) of this thread's slab piece
         s_a[buf][0][si] = h; s_a[buf][1][si] = m; s_a[buf][2][si] = l;
         s_b[buf][0][si] = rb0; s_b[buf][1][si] = rb1; s_b[buf][2][si] = rb2;
@@ -701,8 +674,8 @@ __global__ __launch_bounds__(CV3_T) void k_conv3_norm(const float* __restrict__ 
         float4 acc = make_float4(0, 0, 0, 0);
 #pragma unroll
         for (int j = 0; j < 18; j++) { acc.x += v[j] * w[j].x; acc.y += v[j] * w[j].y; acc.z += v[j] * w[j].z; acc.w += v[j] * w[j].w; }
-        acc.x = wave_sum_lane63_f32(acc.x); acc.y = wave_sum_lane63_f32(acc.y);
-        acc.z = wave_sum_lane63_f32(acc.z); acc.w = wave_sum_lane63_f32(acc.w);
+        acc.x = wave_sum_lane63(acc.x); acc.y = wave_sum_lane63(acc.y);
+        acc.z = wave_sum_lane63(acc.z); acc.w = wave_sum_lane63(acc.w);
         if (lane == 63) {
             float r[4] = {acc.x + b3[0], acc.y + b3[1], acc.z + b3[2], acc.w + b3[3]};
 #pragma unroll
@@ -727,7 +700,7 @@ __global__ __launch_bounds__(256) void k_l2norm_1064(float* __restrict__ out, in
         vv[u] = i < MYSLAM_LCD_DIM ? O[i] : 0.f;
         ss += vv[u] * vv[u];
     }
-    ss = wave_sum_lane63_f32(ss);
+    ss = wave_sum_lane63(ss);
     const float nrm = sqrtf(__shfl(ss, 63, 64));                              // deeplcd.cpp:88
 #pragma unroll
     for (int u = 0; u < NV; u++) {
@@ -810,7 +783,7 @@ __global__ __launch_bounds__(256) void k_flatten_norm_generic(const float* __res
     const float* I = in + (size_t)b * HW * C;
     float ss = 0.f;
     for (int i = threadIdx.x; i < HW * C; i += 256) ss += I[i] * I[i];
-    ss = wave_sum_lane63_f32(ss);
+    ss = wave_sum_lane63(ss);
     if (lane == 63) s_red[wave] = ss;
     __syncthreads();
     const float nrm = sqrtf(s_red[0] + s_red[1] + s_red[2] + s_red[3]);

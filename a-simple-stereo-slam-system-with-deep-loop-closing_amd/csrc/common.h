@@ -12,6 +12,7 @@
 
 #include "../../include/myslam_hip.h"
 #include "dev_mem.h"
+#include "wave_ops.h"
 
 #define MYSLAM_HIP_CHECK(expr)                                                              \
     do {                                                                                    \
@@ -187,12 +188,5 @@ struct DbGraphLink {
 // called by a context whose scan is being captured: the step being recorded on this thread (myslam_graph_begin) takes note.
 // MYSLAM_ERR_UNSUPPORTED when the capture was not started by myslam_graph_begin on this thread (nobody would check the generation).
 int graph_note_db_link(const std::shared_ptr<DbGraphLink>& link, uint64_t generation);
-
-template <typename T>
-__device__ __forceinline__ T wave_reduce_sum(T v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 }  // namespace myslam_hip

@@ -91,16 +91,6 @@ __device__ __forceinline__ bool better(float s, int row, float bs, int brow) {
 // vector rate and competes with the VALU-bound ORB kernels of the other stream (0.28 against 0.15 ms per 512 queries x 10 k rows).  Database rows and queries are split exactly into
 // three bf16 pieces while they are staged into LDS; hh + hm + mh + hl + lh + mm are accumulated in f32.
 typedef __bf16 db_bf16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ void db_split3(float a0, float a1, uint32_t& h, uint32_t& m, uint32_t& l) {
-    const __bf16 h0 = (__bf16)a0, h1 = (__bf16)a1;
-    const float r0 = a0 - (float)h0, r1 = a1 - (float)h1;
-    const __bf16 m0 = (__bf16)r0, m1 = (__bf16)r1;
-    const float q0 = r0 - (float)m0, q1 = r1 - (float)m1;
-    const __bf16 l0 = (__bf16)q0, l1 = (__bf16)q1;
-    h = (uint32_t)__builtin_bit_cast(unsigned short, h0) | ((uint32_t)__builtin_bit_cast(unsigned short, h1) << 16);
-    m = (uint32_t)__builtin_bit_cast(unsigned short, m0) | ((uint32_t)__builtin_bit_cast(unsigned short, m1) << 16);
-    l = (uint32_t)__builtin_bit_cast(unsigned short, l0) | ((uint32_t)__builtin_bit_cast(unsigned short, l1) << 16);
-}
 
 __global__ __launch_bounds__(256) void k_db_scan_bf16x6(const float* __restrict__ db, int rows_alloc, const float* __restrict__ q,
                                                         int nq, const int32_t* __restrict__ nvalid, const int32_t* __restrict__ nstart, float thr_low,
@@ -138,11 +128,11 @@ __global__ __launch_bounds__(256) void k_db_scan_bf16x6(const float* __restrict_
     auto store_stage = [&](int buf) {
         const float za = (a_ok && kv) ? 1.f : 0.f, zb = (b_ok && kv) ? 1.f : 0.f;
         uint4 h, m, l;
-        db_split3(ra0.x * za, ra0.y * za, h.x, m.x, l.x); db_split3(ra0.z * za, ra0.w * za, h.y, m.y, l.y);
-        db_split3(ra1.x * za, ra1.y * za, h.z, m.z, l.z); db_split3(ra1.z * za, ra1.w * za, h.w, m.w, l.w);
+        bf16_split3(ra0.x * za, ra0.y * za, h.x, m.x, l.x); bf16_split3(ra0.z * za, ra0.w * za, h.y, m.y, l.y);
+        bf16_split3(ra1.x * za, ra1.y * za, h.z, m.z, l.z); bf16_split3(ra1.z * za, ra1.w * za, h.w, m.w, l.w);
         s_a[buf][0][t] = h; s_a[buf][1][t] = m; s_a[buf][2][t] = l;
-        db_split3(rb0.x * zb, rb0.y * zb, h.x, m.x, l.x); db_split3(rb0.z * zb, rb0.w * zb, h.y, m.y, l.y);
-        db_split3(rb1.x * zb, rb1.y * zb, h.z, m.z, l.z); db_split3(rb1.z * zb, rb1.w * zb, h.w, m.w, l.w);
+        bf16_split3(rb0.x * zb, rb0.y * zb, h.x, m.x, l.x); bf16_split3(rb0.z * zb, rb0.w * zb, h.y, m.y, l.y);
+        bf16_split3(rb1.x * zb, rb1.y * zb, h.z, m.z, l.z); bf16_split3(rb1.z * zb, rb1.w * zb, h.w, m.w, l.w);
         s_b[buf][0][t] = h; s_b[buf][1][t] = m; s_b[buf][2][t] = l;
     };
     f32x16 acc[2][2];

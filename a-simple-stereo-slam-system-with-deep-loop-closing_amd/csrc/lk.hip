@@ -32,12 +32,6 @@ struct LkGeom {
     size_t bytes;                   // pyramid block bytes per image (levels >= 1)
 };
 
-__device__ __forceinline__ int lk_reflect101(int p, int len) {
-    if (len == 1) return 0;
-    while (p < 0 || p >= len) p = (p < 0) ? -p : 2 * len - 2 - p;
-    return p;
-}
-
 // cvFloor with the rule for what does not fit an int stated: NaN, +-inf and every value outside [-2^31, 2^31) give INT_MIN, which fails
 // each bounds test of the tracker (the point is reported lost); the bare conversion of such a value is undefined in C++
 __device__ __forceinline__ int lk_floor(float v) {
@@ -62,27 +56,21 @@ __global__ __launch_bounds__(256) void k_pyr_down(const uint8_t* __restrict__ sr
     const uint8_t* S = src + (size_t)b * sstride;
     int xs[5];
 #pragma unroll
-    for (int i = 0; i < 5; i++) xs[i] = lk_reflect101(2 * x + i - 2, sw);
+    for (int i = 0; i < 5; i++) xs[i] = reflect101(2 * x + i - 2, sw);
     int s = 0;
 #pragma unroll
     for (int j = 0; j < 5; j++) {
-        const uint8_t* row = S + (size_t)lk_reflect101(2 * y + j - 2, sh) * sstep;
+        const uint8_t* row = S + (size_t)reflect101(2 * y + j - 2, sh) * sstep;
         const int r = row[xs[0]] + 4 * row[xs[1]] + 6 * row[xs[2]] + 4 * row[xs[3]] + row[xs[4]];
         s += (j == 0 || j == 4) ? r : (j == 2 ? 6 * r : 4 * r);
     }
     dst[(size_t)b * dstride + (size_t)y * dw + x] = (uint8_t)((s + 128) >> 8);
 }
 
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int lk_dpp_add(int v) { return v + __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xf, false); }
-__device__ __forceinline__ int lk_wave_sum(int v) {                 // total in lane 63, broadcast to the wave
-    v = lk_dpp_add<0xB1, 0xf>(v); v = lk_dpp_add<0x4E, 0xf>(v); v = lk_dpp_add<0x141, 0xf>(v); v = lk_dpp_add<0x140, 0xf>(v);
-    v = lk_dpp_add<0x142, 0xa>(v); v = lk_dpp_add<0x143, 0xc>(v);
-    return __builtin_amdgcn_readlane(v, 63);
-}
-// exact wave sum of per-lane int32 partials whose total may exceed 32 bits: sum the high part and the low byte separately
+// exact wave sum of per-lane int32 partials whose total may exceed 32 bits: sum the high part and the low byte separately (wave_sum_lane63,
+// wave_ops.h: the total in lane 63, broadcast to the wave)
 __device__ __forceinline__ long long lk_wave_sum64(int v) {
-    const int hi = lk_wave_sum(v >> 8), lo = lk_wave_sum(v & 0xff);
+    const int hi = __builtin_amdgcn_readlane(wave_sum_lane63(v >> 8), 63), lo = __builtin_amdgcn_readlane(wave_sum_lane63(v & 0xff), 63);
     return (long long)hi * 256 + lo;
 }
 
@@ -146,7 +134,7 @@ __global__ __launch_bounds__(256) void k_lk_track(LkArgs a) {
         __builtin_amdgcn_wave_barrier();
         for (int i = lane; i < pI * pI; i += 64) {
             const int r = i / pI, c = i - r * pI;
-            sI[i] = I[(size_t)lk_reflect101(ipy - 1 + r, lh) * istep + lk_reflect101(ipx - 1 + c, lw)];
+            sI[i] = I[(size_t)reflect101(ipy - 1 + r, lh) * istep + reflect101(ipx - 1 + c, lw)];
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         // ---- Scharr derivatives at the (win+1)^2 positions the bilinear taps touch; zero outside the image ----
@@ -211,7 +199,7 @@ __global__ __launch_bounds__(256) void k_lk_track(LkArgs a) {
             __builtin_amdgcn_wave_barrier();
             for (int i = lane; i < pJ * pJ; i += 64) {
                 const int r = i / pJ, c = i - r * pJ;
-                sJ[i] = J[(size_t)lk_reflect101(iny + r, lh) * jstep + lk_reflect101(inx + c, lw)];
+                sJ[i] = J[(size_t)reflect101(iny + r, lh) * jstep + reflect101(inx + c, lw)];
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             fa = __fsub_rn(nx, (float)inx); fb = __fsub_rn(ny, (float)iny);
@@ -249,7 +237,7 @@ __global__ __launch_bounds__(256) void k_lk_track(LkArgs a) {
             __builtin_amdgcn_wave_barrier();
             for (int i = lane; i < pJ * pJ; i += 64) {
                 const int r = i / pJ, c = i - r * pJ;
-                sJ[i] = J[(size_t)lk_reflect101(iny + r, lh) * jstep + lk_reflect101(inx + c, lw)];
+                sJ[i] = J[(size_t)reflect101(iny + r, lh) * jstep + reflect101(inx + c, lw)];
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             fa = __fsub_rn(fx, (float)inx); fb = __fsub_rn(fy, (float)iny);

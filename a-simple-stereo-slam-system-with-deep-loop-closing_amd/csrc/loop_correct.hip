@@ -16,7 +16,7 @@
 //              What remains of the chain is block tridiagonal: two remaining free key-frames joined by an edge were neighbours
 //              before the separators left, and still are.  More than MYSLAM_LOOP_CORRECT_MAX_SEPARATORS                 -> FUSED_ONLY
 //   adjacency  per key-frame the list of (edge, side) in edge order: the assembly sums in that order
-//   per iteration: linearize (pgo.hip's numeric Jacobian, one thread per (edge, side, coordinate)), assemble (one wave per key-frame:
+//   per iteration: linearize (pg_shared.h's numeric Jacobian, one thread per (edge, side, coordinate)), assemble (one wave per key-frame:
 //              its diagonal block and right-hand side, then every off-diagonal block it owns), and per Levenberg trial:
 //              sweep (pg_sweep: one lane per right-hand-side column, 6 S + 1 <= 193 columns in the 256 threads), Z^T Z with
 //              v_mfma_f64_16x16x4 one wave per 16x16 tile subtracted from Hss + lambda I, dense Cholesky with the right-hand side as the
@@ -59,40 +59,11 @@ struct LcArgs {
 
 __device__ __forceinline__ Se3 lc_load_unit(const double* p) { Se3 T = pg_load(p); pg_qnorm(T.q); return T; }
 
-// p <- Tn^-1 (To p), the arithmetic of k_correct_map_points (src/loopclosing.cpp:486-502, :621-633)
-__device__ __forceinline__ void lc_move_point(Se3 To, Se3 Tn, double* p) {
-    pg_qnorm(To.q); pg_qnorm(Tn.q);
-    Tn = pg_inv(Tn);
-    double pc[3], pw[3];
-    pg_rot(To.q, p, pc);
-    pc[0] += To.t[0]; pc[1] += To.t[1]; pc[2] += To.t[2];
-    pg_rot(Tn.q, pc, pw);
-    p[0] = pw[0] + Tn.t[0]; p[1] = pw[1] + Tn.t[1]; p[2] = pw[2] + Tn.t[2];
-}
-
-// fixed-order sum (mode 0) or maximum (mode 1) of one value per thread; every thread receives it
-__device__ __forceinline__ double lc_block_reduce(double v, double* sm, int mode) {
-    const int tid = threadIdx.x;
-    __syncthreads();
-    sm[tid] = v;
-    __syncthreads();
-    for (int s = LC_THREADS / 2; s > 0; s >>= 1) {
-        if (tid < s) sm[tid] = mode ? fmax(sm[tid], sm[tid + s]) : sm[tid] + sm[tid + s];
-        __syncthreads();
-    }
-    return sm[0];
-}
-
 __device__ __forceinline__ double lc_chi2(const double* P, const double* minv, const int32_t* e0, const int32_t* e1, int E, double* sm) {
     double c = 0;
-    for (int k = threadIdx.x; k < E; k += LC_THREADS) {
-        double e[6];
-        pg_edge_error(pg_load(minv + 7 * k), pg_load(P + 7 * e0[k]), pg_load(P + 7 * e1[k]), e);
-        double s = 0;
-        for (int a = 0; a < 6; a++) s += e[a] * e[a];
-        c += s;
-    }
-    return lc_block_reduce(c, sm, 0);
+    for (int k = threadIdx.x; k < E; k += LC_THREADS)
+        c += pg_edge_chi2(P, minv, e0, e1, k);
+    return pg_block_reduce<LC_THREADS>(c, sm, 0);
 }
 
 typedef double lc_d4 __attribute__((ext_vector_type(4)));
@@ -194,7 +165,7 @@ __global__ void __launch_bounds__(LC_THREADS) k_loop_correct(const LcArgs a) {
     for (int i = tid; i < na; i += LC_THREADS) pg_store(pg_load(poses + 7 * active[i]), P + 7 * active[i]);
     for (int i = tid; i < np; i += LC_THREADS) {
         const int fa = first_active[i];
-        if (fa >= 0) lc_move_point(pg_load(oldA + 7 * fa), pg_load(poses + 7 * active[fa]), points + 3 * i);      // :486-502
+        if (fa >= 0) pg_move_point(pg_load(oldA + 7 * fa), pg_load(poses + 7 * active[fa]), points + 3 * i);      // :486-502
     }
     if (tid == 0) { fx[loop] = 1; fx[0] = 1; }
     __syncthreads();
@@ -257,32 +228,7 @@ __global__ void __launch_bounds__(LC_THREADS) k_loop_correct(const LcArgs a) {
         double lambda = 0, ni = 2;
         for (; it < a.max_iters; it++) {
             // linearize: one thread per (edge, side, tangent coordinate), central differences with delta 1e-9
-            for (int id = tid; id < 12 * E1; id += LC_THREADS) {
-                const int k = id / 12, rem = id - 12 * k, side = rem / 6, d = rem - 6 * side;
-                const int vi[2] = {e0[k], e1[k]};
-                const Se3 Mi = pg_load(minv + 7 * k);
-                const Se3 v0 = pg_load(P + 7 * vi[0]), v1 = pg_load(P + 7 * vi[1]);
-                if (rem == 0) {
-                    double e[6]; pg_edge_error(Mi, v0, v1, e);
-                    for (int q = 0; q < 6; q++) err[6 * k + q] = e[q];
-                }
-                double* Jc = J + ((size_t)k * 2 + side) * 36;
-                if (fx[vi[side]]) {
-                    for (int r = 0; r < 6; r++) Jc[r * 6 + d] = 0.0;
-                    continue;
-                }
-                double add[6], ep[6], em[6];
-#pragma unroll
-                for (int q = 0; q < 6; q++) add[q] = (q == d) ? 1e-9 : 0.0;
-                Se3 vp = pg_mul(pg_exp(add), side ? v1 : v0);
-                pg_edge_error(Mi, side ? v0 : vp, side ? vp : v1, ep);
-#pragma unroll
-                for (int q = 0; q < 6; q++) add[q] = (q == d) ? -1e-9 : 0.0;
-                vp = pg_mul(pg_exp(add), side ? v1 : v0);
-                pg_edge_error(Mi, side ? v0 : vp, side ? vp : v1, em);
-                const double scalar = 1.0 / (2 * 1e-9);
-                for (int r = 0; r < 6; r++) Jc[r * 6 + d] = scalar * (ep[r] - em[r]);
-            }
+            for (int id = tid; id < 12 * E1; id += LC_THREADS) pg_jacobian_column(id, P, minv, e0, e1, fx, J, err);
             __syncthreads();
             // assemble: one wave per free key-frame; lanes 0..35 one entry of a 6x6 block, lanes 36..41 one entry of the right-hand side
             for (int v = wv; v < n; v += NW) {
@@ -295,9 +241,9 @@ __global__ void __launch_bounds__(LC_THREADS) k_loop_correct(const LcArgs a) {
                 for (int p = a0; p < a1; p++) {
                     const int k = adj[p] >> 1, side = adj[p] & 1;
                     const double* Jr = J + ((size_t)k * 2 + side) * 36;
-                    double h = 0;
-                    if (!isb) { for (int m = 0; m < 6; m++) h += Jr[m * 6 + r] * Jr[m * 6 + c]; }
-                    else { for (int m = 0; m < 6; m++) h += Jr[m * 6 + r] * err[(size_t)k * 6 + m]; }
+                    double h;
+                    if (!isb) h = pg_jtj(Jr, Jr, r, c);
+                    else h = pg_jte(Jr, err + (size_t)k * 6, r);
                     sum += h;
                 }
                 if (vT) {
@@ -325,6 +271,8 @@ __global__ void __launch_bounds__(LC_THREADS) k_loop_correct(const LcArgs a) {
                         if ((sq ? e0[kq] : e1[kq]) != u) continue;
                         const double* Jr = J + ((size_t)kq * 2 + sq) * 36;
                         const double* Jc = J + ((size_t)kq * 2 + (1 - sq)) * 36;
+                        // pg_jtj(Jr, Jc, r, c), written out: behind the call, in whatever form, this kernel's register allocation tips over
+                        // (SGPR spills 210 -> 221, +440 instructions) and a batch runs 2.3 % longer (measured)
                         double h = 0;
                         for (int m = 0; m < 6; m++) h += Jr[m * 6 + r] * Jc[m * 6 + c];
                         s2 += h;
@@ -341,7 +289,7 @@ __global__ void __launch_bounds__(LC_THREADS) k_loop_correct(const LcArgs a) {
                     const int f = i / 6, q = i - 6 * f;
                     mx = fmax(mx, fabs(f < nT ? D[(size_t)f * 36 + 7 * q] : Hss[(size_t)(6 * (f - nT) + q) * ldz + 6 * (f - nT) + q]));
                 }
-                lambda = 1e-5 * lc_block_reduce(mx, sRed, 1); ni = 2;
+                lambda = 1e-5 * pg_block_reduce<LC_THREADS>(mx, sRed, 1); ni = 2;
             }
             double rho = 0;
             int qmax = 0;
@@ -356,9 +304,8 @@ __global__ void __launch_bounds__(LC_THREADS) k_loop_correct(const LcArgs a) {
                 if (mS > 0) {
                     const int nt = ldz >> 4, ntile = nt * (nt + 1) / 2, k4 = (rows + 3) >> 2;
                     for (int tile = wv; tile < ntile; tile += NW) {
-                        int ti = 0;
-                        while ((ti + 1) * (ti + 2) / 2 <= tile) ti++;
-                        const int tj = tile - ti * (ti + 1) / 2;
+                        int ti, tj;
+                        pg_tri_decode(tile, ti, tj);
                         lc_d4 acc = {0, 0, 0, 0};
                         const int zr = lane >> 4, zc = lane & 15;
                         for (int g = 0; g < k4; g++) {
@@ -371,7 +318,7 @@ __global__ void __launch_bounds__(LC_THREADS) k_loop_correct(const LcArgs a) {
                         for (int v = 0; v < 4; v++) {
                             const int i = 16 * ti + 4 * v + zr, j = 16 * tj + zc;
                             double val = 0;
-                            if (i <= mS && j <= i && j < mS) val = (i < mS ? Hss[(size_t)i * ldz + j] + (i == j ? lambda : 0.0) : bS[j]) - acc[v];
+                            if (pg_schur_kept(i, j, mS)) val = pg_schur_entry(Hss, bS, i, j, mS, ldz, lambda) - acc[v];
                             A[(size_t)i * ldz + j] = val;
                         }
                     }
@@ -417,17 +364,9 @@ __global__ void __launch_bounds__(LC_THREADS) k_loop_correct(const LcArgs a) {
                 for (int v = tid; v < n; v += LC_THREADS) {
                     const int sl = slot[v];
                     if (sl < 0) continue;
-                    double x[6], s = 0;
-                    for (int q = 0; q < 6; q++) {
-                        double bq;
-                        if (sl < nT) { x[q] = xT[6 * sl + q]; bq = C[(size_t)(6 * sl + q) * ldz + mS]; }
-                        else { x[q] = sX[6 * (sl - nT) + q]; bq = bS[6 * (sl - nT) + q]; }
-                        s += x[q] * (lambda * x[q] + bq);
-                    }
-                    pg_store(pg_mul(pg_exp(x), pg_load(P + 7 * v)), P + 7 * v);
-                    sc += s;
+                    sc += pg_update_pose(P + 7 * v, sl, nT, xT, sX, C, bS, ldz, mS, lambda);
                 }
-                const double den = lc_block_reduce(sc, sRed, 0);
+                const double den = pg_block_reduce<LC_THREADS>(sc, sRed, 0);
                 const double newChi = lc_chi2(P, minv, e0, e1, E1, sRed);
                 const bool ok = !sBad;
                 const double tempChi = ok ? newChi : 1e300;
@@ -436,7 +375,7 @@ __global__ void __launch_bounds__(LC_THREADS) k_loop_correct(const LcArgs a) {
                 if (ok) scale += den;
                 rho /= scale;
                 if (rho > 0 && isfinite(tempChi) && ok) {
-                    const double t = 2 * rho - 1;
+                    const double t = 2 * rho - 1;                     // myslam_pose_graph_optimize (pgo.hip) writes pow(2 * rho - 1, 3): kept apart, the two need not round alike
                     double alpha = 1. - t * t * t;
                     alpha = fmin(alpha, 2. / 3.);
                     lambda *= fmax(1. / 3., alpha); ni = 2; currentChi = tempChi;
@@ -458,7 +397,7 @@ __global__ void __launch_bounds__(LC_THREADS) k_loop_correct(const LcArgs a) {
     for (int i = tid; i < np; i += LC_THREADS) {
         const int k = first_kf[i];
         if (first_active[i] >= 0 || k < 0) continue;                                   // :616-619, :627-631
-        lc_move_point(pg_load(Pf + 7 * k), pg_load(P + 7 * k), points + 3 * i);
+        pg_move_point(pg_load(Pf + 7 * k), pg_load(P + 7 * k), points + 3 * i);
     }
     for (int v = tid; v < n; v += LC_THREADS)
         if (slot[v] >= 0) pg_store(pg_load(P + 7 * v), poses + 7 * v);

@@ -332,12 +332,6 @@ __global__ __launch_bounds__(256) void k_resize_strip(ResizeArgs a, int nstrips,
 // ------------------------------------------------------------------------------------------------
 // K2: 7x7 separable Gaussian, Q8 coefficients (<= 255 each, sum <= 257: the Q8.8 row sums fit 16 bits), REFLECT_101, u8 saturation.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int reflect101(int p, int len) {
-    if (len == 1) return 0;
-    while (p < 0 || p >= len) p = (p < 0) ? -p : 2 * len - 2 - p;
-    return p;
-}
-
 // Four vertical sums (Q16.16 + rounding seed, each < 2^25) -> four u8 in one dword, SATURATED as OpenCV's ufixedpoint32 -> uint8_t
 // conversion does: taps that sum to 257 (OpenCV 3.4.8's independently rounded sigma = 2 table) reach 257 on saturated image regions.
 // v_perm picks the two high halves, v_sat_pk_u8_i16 clamps both to 0..255: 5 instructions per 4 pixels.
@@ -774,15 +768,10 @@ __global__ __launch_bounds__(256) void k_blur7_mfma(BlurMfmaMulti M) {
 }
 
 // ---- host: operand tables of k_blur7_mfma ----
-static int bl_reflect101(int p, int len) {
-    if (len == 1) return 0;
-    while (p < 0 || p >= len) p = (p < 0) ? -p : 2 * len - 2 - p;
-    return p;
-}
 static int bl_coef(const int q[7], int out, int in, int len) {          // weight of input position `in` in output position `out`
     if (out < 0 || out >= len || in < 0 || in >= len) return 0;
     int c = 0;
-    for (int t = 0; t < 7; t++) if (bl_reflect101(out + t - 3, len) == in) c += q[t];
+    for (int t = 0; t < 7; t++) if (reflect101(out + t - 3, len) == in) c += q[t];
     return c;
 }
 static inline int bl_slot_row(int b, int half) { return (b & 3) + 8 * (b >> 2) + 4 * half; }
@@ -814,7 +803,7 @@ bool blur_mfma_tables(int w, int h, const int q[7], std::vector<uint4>& tab, siz
             }
         // every input column an output column of this strip needs must lie inside the 64-column window
         for (int j = 0; j < 32 && x0 + j < w; j++)
-            for (int t = 0; t < 7; t++) { const int in = bl_reflect101(x0 + j + t - 3, w); if (in < ws || in >= ws + 64) { tab.resize(keep); return false; } }
+            for (int t = 0; t < 7; t++) { const int in = reflect101(x0 + j + t - 3, w); if (in < ws || in >= ws + 64) { tab.resize(keep); return false; } }
     }
     offV = tab.size();
     for (int ty = 0; ty < ntile; ty++)
@@ -1006,17 +995,6 @@ __device__ __forceinline__ uint32_t nms_strict4(const RU& U, const NmsRow& M, co
     __builtin_memcpy(&zacc, &zs, 4);
     uint32_t za, zb; __builtin_memcpy(&za, &ka, 4); __builtin_memcpy(&zb, &kb, 4);
     return __builtin_amdgcn_perm(zb, za, 0x06040200u);
-}
-
-// inclusive prefix sum over the 64 lanes on the DPP network (row_shr 1/2/4/8, then the two row broadcasts)
-__device__ __forceinline__ int wave_incl_scan_dpp(int v) {
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);        // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);        // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);        // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);        // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);        // row_bcast15 -> rows 1, 3
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);        // row_bcast31 -> rows 2, 3
-    return v;
 }
 
 // number of set bits of a 64-bit ballot below this lane, added to acc: two v_mbcnt (the mask-and-popcount form costs five)
@@ -1328,7 +1306,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CW <= 40 ? 
     auto push_maxima = [&](int mk, uint32_t zc0, uint32_t zc1, int zshift, int c, int px0, int py0) __attribute__((always_inline)) {
         int incl = __popc(mk);
         const int cnt = incl;
-        incl = wave_incl_scan_dpp(incl);
+        incl = wave_incl_scan(incl);
         const int total = __builtin_amdgcn_readlane(incl, 63);
         if (total == 0) return;                                        // wave-uniform
         int base = 0;
@@ -1394,7 +1372,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CW <= 40 ? 
             }
             int incl = __popc(pm);
             const int cnt = incl;
-            incl = wave_incl_scan_dpp(incl);
+            incl = wave_incl_scan(incl);
             const int total = __builtin_amdgcn_readlane(incl, 63);
             if (total == 0) continue;                                  // wave-uniform
             int base = 0;
@@ -1707,30 +1685,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CW <= 40 ? 
 // them 512 wide (53 us instead of 75)
 constexpr int OT_MAXB = 1024;        // buckets of the counting sort
 
-// inclusive prefix sum of a 64-bit value over the 64 lanes on the DPP network (both halves moved, one 64-bit add per step; lanes
-// without a source add zero): 24 VALU operations instead of 12 dependent trips through the LDS crossbar
-__device__ __forceinline__ uint64_t wave_incl_scan64(uint64_t v) {
-#define MYSLAM_SCAN64_STEP(CTRL, ROWS)                                                                                   \
-    {                                                                                                                    \
-        const uint32_t l2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)v, CTRL, ROWS, 0xf, false);          \
-        const uint32_t h2 = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(v >> 32), CTRL, ROWS, 0xf, false);  \
-        v += ((uint64_t)h2 << 32) | l2;                                                                                  \
-    }
-    MYSLAM_SCAN64_STEP(0x111, 0xf)          // row_shr:1
-    MYSLAM_SCAN64_STEP(0x112, 0xf)          // row_shr:2
-    MYSLAM_SCAN64_STEP(0x114, 0xf)          // row_shr:4
-    MYSLAM_SCAN64_STEP(0x118, 0xf)          // row_shr:8
-    MYSLAM_SCAN64_STEP(0x142, 0xa)          // row_bcast15 -> rows 1, 3
-    MYSLAM_SCAN64_STEP(0x143, 0xc)          // row_bcast31 -> rows 2, 3
-#undef MYSLAM_SCAN64_STEP
-    return v;
-}
-
-// exclusive block scan of a packed 64-bit counter; s_w = OT/64 uint64 of LDS scratch
+// exclusive block scan of a packed 64-bit counter; s_w = OT/64 uint64 of LDS scratch.  The wave step is wave_incl_scan<uint64_t> (wave_ops.h): both
+// halves moved on the DPP network, one 64-bit add per step, 24 VALU operations instead of 12 dependent trips through the LDS crossbar
 template <int OT>
 __device__ __forceinline__ uint64_t block_excl_scan64(uint64_t v, uint64_t* s_w, uint64_t& total) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const uint64_t incl = wave_incl_scan64(v);
+    const uint64_t incl = wave_incl_scan(v);
     __syncthreads();                       // previous users of s_w are done
     if (lane == 63) s_w[wid] = incl;
     __syncthreads();
@@ -2420,14 +2380,6 @@ constexpr int DB_IT = 3;                                                        
 //                           patch as it lies in memory is the A operand (p - 128; the masked weights sum to zero), 16 MFMAs
 //   B  thread per keypoint: fastAtan2, deterministic sin/cos, cv::KeyPoint fields
 //   C  wave per keypoint  : blurred 37x37 window -> LDS, 4 steered BRIEF tests per lane
-
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp_add_i32(int v) { return v + __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xf, false); }
-__device__ __forceinline__ int wave_sum_lane63_i32(int v) {
-    v = dpp_add_i32<0xB1, 0xf>(v); v = dpp_add_i32<0x4E, 0xf>(v); v = dpp_add_i32<0x141, 0xf>(v); v = dpp_add_i32<0x140, 0xf>(v);
-    v = dpp_add_i32<0x142, 0xa>(v); v = dpp_add_i32<0x143, 0xc>(v);
-    return v;
-}
 
 constexpr int KD_KPB = 64;                                       // keypoints per block
 #ifndef MYSLAM_KD_GLDS                                              // windows a wave of the descriptor kernel keeps in flight in phase C (direct-to-LDS loads); 0 = the register-staged form

@@ -1,50 +1,27 @@
-// pg_shared.h — device code shared by the pose-graph units (pgo.hip, loop_correct.hip): Sophus-style SE3 on unit quaternions, the edge error of
-// g2o_types.h:161-167, and the two serial halves of the block-tridiagonal elimination (forward sweep, backward chain).  gfx950 only.
+// pg_shared.h — every rule the two pose-graph solvers have in common, once.  pgo.hip runs them as kernels per phase driven by the host,
+// loop_correct.hip inside one workgroup with barriers; what this header owns is the same lines in both:
+//   SE3 exp / log on unit quaternions (the products and the pose layout: se3_quat.h, shared with the host) and the edge error of g2o_types.h:161-167
+//   pg_jacobian_column    g2o's numeric Jacobian column of one (edge, side, coordinate)
+//   pg_edge_chi2          e^T e of one edge
+//   pg_jtj / pg_jte       the 6-term products of the assembly
+//   pg_sweep / pg_back    the two serial halves of the block-tridiagonal elimination (forward sweep, backward chain)
+//   pg_tri_decode         lower-triangle tile number -> (row tile, column tile)
+//   pg_schur_kept, _entry Hss + lambda I | bS, the dense Schur system before Z^T Z comes off
+//   pg_update_pose        pose <- exp(x) pose and the gain term x . (lambda x + b)
+//   pg_move_point         p <- Tn^-1 (To p), the rigid move of a map point
+//   pg_block_reduce       fixed-order sum / maximum of one value per thread
+// Left apart on purpose: the dense factorisation (blocked MFMA Cholesky in k_pg_schur, unblocked in k_loop_correct), the separator rule (greedy on
+// the host, lc_separator on the device) and Levenberg's accept / reject arithmetic (pow on the host, t*t*t on the device: they need not round alike).
+// gfx950 only.
 #pragma once
 #include <math.h>
 
 #include "common.h"
+#include "se3_quat.h"
 
 namespace myslam_hip {
 
 constexpr double PG_EPS = 1e-10;     // Sophus::Constants<double>::epsilon()
-
-struct Se3 { double q[4]; double t[3]; };      // q = (x, y, z, w)
-
-__device__ __forceinline__ void pg_rot(const double* q, const double* v, double* o) {
-    double uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
-    uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-    o[0] = v[0] + q[3] * uv[0] + (q[1] * uv[2] - q[2] * uv[1]);
-    o[1] = v[1] + q[3] * uv[1] + (q[2] * uv[0] - q[0] * uv[2]);
-    o[2] = v[2] + q[3] * uv[2] + (q[0] * uv[1] - q[1] * uv[0]);
-}
-
-__device__ __forceinline__ void pg_qnorm(double* q) {
-    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    q[0] /= n; q[1] /= n; q[2] /= n; q[3] /= n;
-}
-
-__device__ __forceinline__ Se3 pg_mul(const Se3& a, const Se3& b) {
-    Se3 r;
-    r.q[3] = a.q[3] * b.q[3] - a.q[0] * b.q[0] - a.q[1] * b.q[1] - a.q[2] * b.q[2];
-    r.q[0] = a.q[3] * b.q[0] + a.q[0] * b.q[3] + a.q[1] * b.q[2] - a.q[2] * b.q[1];
-    r.q[1] = a.q[3] * b.q[1] - a.q[0] * b.q[2] + a.q[1] * b.q[3] + a.q[2] * b.q[0];
-    r.q[2] = a.q[3] * b.q[2] + a.q[0] * b.q[1] - a.q[1] * b.q[0] + a.q[2] * b.q[3];
-    pg_qnorm(r.q);
-    double rt[3];
-    pg_rot(a.q, b.t, rt);
-    r.t[0] = a.t[0] + rt[0]; r.t[1] = a.t[1] + rt[1]; r.t[2] = a.t[2] + rt[2];
-    return r;
-}
-
-__device__ __forceinline__ Se3 pg_inv(const Se3& a) {
-    Se3 r;
-    r.q[0] = -a.q[0]; r.q[1] = -a.q[1]; r.q[2] = -a.q[2]; r.q[3] = a.q[3];
-    double rt[3];
-    pg_rot(r.q, a.t, rt);
-    r.t[0] = -rt[0]; r.t[1] = -rt[1]; r.t[2] = -rt[2];
-    return r;
-}
 
 // Sophus SE3::exp, tangent (upsilon, omega)
 __device__ inline Se3 pg_exp(const double* d) {
@@ -94,18 +71,116 @@ __device__ inline void pg_log(const Se3& T, double* d) {
     d[3] = wx; d[4] = wy; d[5] = wz;
 }
 
-__device__ __forceinline__ Se3 pg_load(const double* p) {
-    Se3 T;
-    T.q[0] = p[0]; T.q[1] = p[1]; T.q[2] = p[2]; T.q[3] = p[3]; T.t[0] = p[4]; T.t[1] = p[5]; T.t[2] = p[6];
-    return T;
-}
-__device__ __forceinline__ void pg_store(const Se3& T, double* p) {
-    p[0] = T.q[0]; p[1] = T.q[1]; p[2] = T.q[2]; p[3] = T.q[3]; p[4] = T.t[0]; p[5] = T.t[1]; p[6] = T.t[2];
-}
-
 // g2o_types.h:161-167
 __device__ __forceinline__ void pg_edge_error(const Se3& Minv, const Se3& v0, const Se3& v1, double* e) {
     pg_log(pg_mul(pg_mul(Minv, v0), pg_inv(v1)), e);
+}
+
+// e^T e of edge k
+__device__ __forceinline__ double pg_edge_chi2(const double* poses, const double* minv, const int32_t* e0, const int32_t* e1, int k) {
+    double e[6], c = 0;
+    pg_edge_error(pg_load(minv + 7 * k), pg_load(poses + 7 * e0[k]), pg_load(poses + 7 * e1[k]), e);
+    for (int a = 0; a < 6; a++) c += e[a] * e[a];
+    return c;
+}
+
+// g2o BaseBinaryEdge::linearizeOplus, numeric branch, for id = (12 edge + 6 side + coordinate) < 12 E: column `coordinate` of J[edge][side] (6x6, row
+// major) by central differences with delta 1e-9 on the left-multiplied update, zeros when that side's vertex is fixed (fixedv[vertex] != 0, any
+// integer type); the id with side = coordinate = 0 also writes the edge's error into err[6 edge ..].
+template <typename Fixed>
+__device__ __forceinline__ void pg_jacobian_column(int id, const double* poses, const double* minv, const int32_t* e0, const int32_t* e1,
+                                                   const Fixed* fixedv, double* J /*E x 2 x 36*/, double* err /*E x 6*/) {
+    const int k = id / 12, rem = id - 12 * k, side = rem / 6, d = rem - 6 * side;
+    const int vi[2] = {e0[k], e1[k]};
+    const Se3 Mi = pg_load(minv + 7 * k);
+    const Se3 v0 = pg_load(poses + 7 * vi[0]), v1 = pg_load(poses + 7 * vi[1]);
+    if (rem == 0) {
+        double e[6]; pg_edge_error(Mi, v0, v1, e);
+        for (int a = 0; a < 6; a++) err[6 * k + a] = e[a];
+    }
+    double* Jc = J + ((size_t)k * 2 + side) * 36;
+    if (fixedv[vi[side]]) {
+        for (int r = 0; r < 6; r++) Jc[r * 6 + d] = 0.0;
+        return;
+    }
+    double add[6], ep[6], em[6];
+#pragma unroll
+    for (int a = 0; a < 6; a++) add[a] = (a == d) ? 1e-9 : 0.0;
+    Se3 vp = pg_mul(pg_exp(add), side ? v1 : v0);
+    pg_edge_error(Mi, side ? v0 : vp, side ? vp : v1, ep);
+#pragma unroll
+    for (int a = 0; a < 6; a++) add[a] = (a == d) ? -1e-9 : 0.0;
+    vp = pg_mul(pg_exp(add), side ? v1 : v0);
+    pg_edge_error(Mi, side ? v0 : vp, side ? vp : v1, em);
+    const double scalar = 1.0 / (2 * 1e-9);
+    for (int r = 0; r < 6; r++) Jc[r * 6 + d] = scalar * (ep[r] - em[r]);
+}
+
+// entry (r, c) of Jr^T Jc and entry r of Jr^T e, 6x6 row-major blocks, summed over the six error rows in order
+__device__ __forceinline__ double pg_jtj(const double* Jr, const double* Jc, int r, int c) {
+    double h = 0;
+    for (int m = 0; m < 6; m++) h += Jr[m * 6 + r] * Jc[m * 6 + c];
+    return h;
+}
+__device__ __forceinline__ double pg_jte(const double* Jr, const double* e, int r) {
+    double h = 0;
+    for (int m = 0; m < 6; m++) h += Jr[m * 6 + r] * e[m];
+    return h;
+}
+
+// tile q of a lower triangle numbered row by row: q = ti (ti + 1) / 2 + tj, tj <= ti
+__device__ __forceinline__ void pg_tri_decode(int q, int& ti, int& tj) {
+    ti = 0;
+    while ((ti + 1) * (ti + 2) / 2 <= q) ti++;
+    tj = q - ti * (ti + 1) / 2;
+}
+
+// The dense Schur system before Z^T Z comes off: Hss + lambda I in rows < mS, the right-hand side bS as row mS.  Only the lower triangle of the
+// columns < mS is kept (pg_schur_kept); every other entry of the padded matrix is 0.
+__device__ __forceinline__ bool pg_schur_kept(int i, int j, int mS) { return i <= mS && j <= i && j < mS; }
+__device__ __forceinline__ double pg_schur_entry(const double* Hss, const double* bS, int i, int j, int mS, int ldz, double lambda) {
+    return i < mS ? Hss[(size_t)i * ldz + j] + (i == j ? lambda : 0.0) : bS[j];
+}
+
+// pose <- exp(x) * pose for a free key-frame in slot sl (chain position t < nT: x = xT[6 t ..], b = column mS of C; else separator sl - nT: xS, bS);
+// returns its share x . (lambda x + b) of the gain's denominator
+__device__ __forceinline__ double pg_update_pose(double* pose, int sl, int nT, const double* xT, const double* xS, const double* C, const double* bS,
+                                                 int ldz, int mS, double lambda) {
+    double x[6], s = 0;
+    for (int q = 0; q < 6; q++) {
+        double bq;
+        if (sl < nT) { x[q] = xT[6 * sl + q]; bq = C[(size_t)(6 * sl + q) * ldz + mS]; }
+        else { x[q] = xS[6 * (sl - nT) + q]; bq = bS[6 * (sl - nT) + q]; }
+        s += x[q] * (lambda * x[q] + bq);
+    }
+    pg_store(pg_mul(pg_exp(x), pg_load(pose)), pose);
+    return s;
+}
+
+// p <- Tn^-1 (To p): a map point moves rigidly with its key-frame from pose To to pose Tn (src/loopclosing.cpp:486-502, :621-633)
+__device__ __forceinline__ void pg_move_point(Se3 To, Se3 Tn, double* p) {
+    pg_qnorm(To.q); pg_qnorm(Tn.q);
+    Tn = pg_inv(Tn);
+    double pc[3], pw[3];
+    pg_rot(To.q, p, pc);
+    pc[0] += To.t[0]; pc[1] += To.t[1]; pc[2] += To.t[2];
+    pg_rot(Tn.q, pc, pw);
+    p[0] = pw[0] + Tn.t[0]; p[1] = pw[1] + Tn.t[1]; p[2] = pw[2] + Tn.t[2];
+}
+
+// Fixed-order sum (mode 0) or maximum (mode 1) of one value per thread of an NT-thread workgroup (NT a power of two, sm = NT doubles of LDS); every
+// thread receives it.  Opens with a barrier, so sm may still be in use by the previous reduction when it is called.
+template <int NT>
+__device__ __forceinline__ double pg_block_reduce(double v, double* sm, int mode) {
+    const int tid = threadIdx.x;
+    __syncthreads();
+    sm[tid] = v;
+    __syncthreads();
+    for (int s = NT / 2; s > 0; s >>= 1) {
+        if (tid < s) sm[tid] = mode ? fmax(sm[tid], sm[tid + s]) : sm[tid] + sm[tid + s];
+        __syncthreads();
+    }
+    return sm[0];
 }
 
 // 1 / sqrt(s) to double precision: v_rsq_f64 seed (~2^-23) + two cubic Newton steps — a fraction of the sqrt + divide sequences,

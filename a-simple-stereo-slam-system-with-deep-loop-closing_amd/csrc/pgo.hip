@@ -51,55 +51,14 @@ __global__ void k_pg_linearize(const double* __restrict__ poses, const double* _
                                const int32_t* __restrict__ e1, const uint8_t* __restrict__ fixedv, int E,
                                double* __restrict__ J /*E x 2 x 36*/, double* __restrict__ err /*E x 6*/) {
     const int id = blockIdx.x * blockDim.x + threadIdx.x;
-    if (id >= 12 * E) return;
-    const int k = id / 12, rem = id - 12 * k, side = rem / 6, d = rem - 6 * side;
-    const int vi[2] = {e0[k], e1[k]};
-    const Se3 Mi = pg_load(minv + 7 * k);
-    const Se3 v0 = pg_load(poses + 7 * vi[0]), v1 = pg_load(poses + 7 * vi[1]);
-    if (rem == 0) {
-        double e[6]; pg_edge_error(Mi, v0, v1, e);
-        for (int a = 0; a < 6; a++) err[6 * k + a] = e[a];
-    }
-    double* Jc = J + ((size_t)k * 2 + side) * 36;
-    if (fixedv[vi[side]]) {
-        for (int r = 0; r < 6; r++) Jc[r * 6 + d] = 0.0;
-        return;
-    }
-    double add[6] = {0, 0, 0, 0, 0, 0}, ep[6], em[6];
-#pragma unroll
-    for (int a = 0; a < 6; a++) add[a] = (a == d) ? 1e-9 : 0.0;
-    Se3 vp = pg_mul(pg_exp(add), side ? v1 : v0);
-    pg_edge_error(Mi, side ? v0 : vp, side ? vp : v1, ep);
-#pragma unroll
-    for (int a = 0; a < 6; a++) add[a] = (a == d) ? -1e-9 : 0.0;
-    vp = pg_mul(pg_exp(add), side ? v1 : v0);
-    pg_edge_error(Mi, side ? v0 : vp, side ? vp : v1, em);
-    const double scalar = 1.0 / (2 * 1e-9);
-    for (int r = 0; r < 6; r++) Jc[r * 6 + d] = scalar * (ep[r] - em[r]);
-}
-
-// fixed-order block sum of `v` over 256 threads; valid in thread 0
-__device__ __forceinline__ double pg_block_sum256(double v, double* sm) {
-    sm[threadIdx.x] = v;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sm[threadIdx.x] += sm[threadIdx.x + s];
-        __syncthreads();
-    }
-    return sm[0];
+    if (id < 12 * E) pg_jacobian_column(id, poses, minv, e0, e1, fixedv, J, err);
 }
 
 __global__ void __launch_bounds__(256) k_pg_chi2(const double* __restrict__ poses, const double* __restrict__ minv, const int32_t* __restrict__ e0,
                                                  const int32_t* __restrict__ e1, int E, double* __restrict__ partial) {
     __shared__ double sm[256];
     const int k = blockIdx.x * 256 + threadIdx.x;
-    double c = 0;
-    if (k < E) {
-        double e[6];
-        pg_edge_error(pg_load(minv + 7 * k), pg_load(poses + 7 * e0[k]), pg_load(poses + 7 * e1[k]), e);
-        for (int a = 0; a < 6; a++) c += e[a] * e[a];
-    }
-    const double s = pg_block_sum256(c, sm);
+    const double s = pg_block_reduce<256>(k < E ? pg_edge_chi2(poses, minv, e0, e1, k) : 0.0, sm, 0);
     if (threadIdx.x == 0) partial[blockIdx.x] = s;
 }
 
@@ -108,13 +67,8 @@ __global__ void __launch_bounds__(256) k_pg_reduce(const double* __restrict__ v,
     __shared__ double sm[256];
     double a = 0;
     for (int i = threadIdx.x; i < n; i += 256) a = mode ? fmax(a, fabs(v[i])) : a + v[i];
-    sm[threadIdx.x] = a;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sm[threadIdx.x] = mode ? fmax(sm[threadIdx.x], sm[threadIdx.x + s]) : sm[threadIdx.x] + sm[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *out = sm[0];
+    a = pg_block_reduce<256>(a, sm, mode);
+    if (threadIdx.x == 0) *out = a;
 }
 
 // One wave per destination 6x6 block.  kind 0: D_t (+ bT_t into column mS of C)  1: B_t  2: C block (t, s)
@@ -135,9 +89,9 @@ __global__ void __launch_bounds__(64) k_pg_assemble(const PgJob* __restrict__ jo
         const int2 en = list[i];
         const double* Jr = J + ((size_t)en.x * 2 + (en.y & 1)) * 36;
         const double* Jc = J + ((size_t)en.x * 2 + (en.y >> 1)) * 36;
-        double h = 0;
-        if (!isb) { for (int m = 0; m < 6; m++) h += Jr[m * 6 + r] * Jc[m * 6 + c]; }
-        else { for (int m = 0; m < 6; m++) h += Jr[m * 6 + r] * err[(size_t)en.x * 6 + m]; }
+        double h;
+        if (!isb) h = pg_jtj(Jr, Jc, r, c);
+        else h = pg_jte(Jr, err + (size_t)en.x * 6, r);
         sum += h;
     }
     switch (jb.kind) {
@@ -169,9 +123,8 @@ __global__ void __launch_bounds__(64) k_pg_sweep(const double* __restrict__ D, c
 typedef double pg_d4 __attribute__((ext_vector_type(4)));
 __global__ void __launch_bounds__(64) k_pg_syrk(const double* __restrict__ Z, double* __restrict__ P, int ldz, int k4 /*groups of 4 rows*/, int ntile) {
     const int tile = blockIdx.x, ks = blockIdx.y, lane = threadIdx.x;
-    int ti = 0;
-    while ((ti + 1) * (ti + 2) / 2 <= tile) ti++;
-    const int tj = tile - ti * (ti + 1) / 2;
+    int ti, tj;
+    pg_tri_decode(tile, ti, tj);
     const int per = (k4 + PG_KS - 1) / PG_KS, g0 = ks * per, g1 = min(k4, g0 + per);
     pg_d4 acc = {0, 0, 0, 0};
     const double* pa = Z + (size_t)(lane >> 4) * ldz + 16 * ti + (lane & 15);
@@ -213,9 +166,8 @@ __global__ void __launch_bounds__(1024) k_pg_schur(const double* __restrict__ Hs
     for (int i = ty; i < ldz; i += 32)
         for (int j = tx; j < ldz; j += 32) {
             double v = 0;
-            if (i <= mS && j <= i && j < mS) {
-                if (i < mS) v = Hss[(size_t)i * ldz + j] + ((i == j) ? lambda : 0.0);
-                else v = bS[j];
+            if (pg_schur_kept(i, j, mS)) {
+                v = pg_schur_entry(Hss, bS, i, j, mS, ldz, lambda);
                 if (haveZ) v -= pg_ztz(P, ntile, i, j);
             }
             A[(size_t)i * ldz + j] = v;
@@ -264,9 +216,9 @@ __global__ void __launch_bounds__(1024) k_pg_schur(const double* __restrict__ Hs
         // trailing update: tile (ti, tj), p < tj <= ti < nt; A-operand lane value X[16 ti + (lane & 15)][c0 + 4 g + (lane >> 4)]
         const int nrem = nt - p - 1, ntr = nrem * (nrem + 1) / 2;
         for (int q = wv; q < ntr; q += 16) {
-            int a = 0;
-            while ((a + 1) * (a + 2) / 2 <= q) a++;
-            const int ti = p + 1 + a, tj = p + 1 + (q - a * (a + 1) / 2);
+            int ti, tj;
+            pg_tri_decode(q, ti, tj);
+            ti += p + 1; tj += p + 1;
             const double* pa = A + (size_t)(16 * ti + (lane & 15)) * ldz + c0 + (lane >> 4);
             const double* pb = A + (size_t)(16 * tj + (lane & 15)) * ldz + c0 + (lane >> 4);
             double* pc = A + (size_t)(16 * ti + (lane >> 4)) * ldz + 16 * tj + (lane & 15);
@@ -350,17 +302,7 @@ __global__ void __launch_bounds__(256) k_pg_update(double* __restrict__ poses, c
     const int v = blockIdx.x * 256 + threadIdx.x;
     if (v >= n) return;
     const int sl = slot[v];
-    double s = 0;
-    if (sl >= 0) {
-        double x[6], b[6];
-        for (int a = 0; a < 6; a++) {
-            if (sl < nT) { x[a] = xT[6 * sl + a]; b[a] = C[(size_t)(6 * sl + a) * ldz + mS]; }
-            else { x[a] = xS[6 * (sl - nT) + a]; b[a] = bS[6 * (sl - nT) + a]; }
-            s += x[a] * (lambda * x[a] + b[a]);
-        }
-        pg_store(pg_mul(pg_exp(x), pg_load(poses + 7 * v)), poses + 7 * v);
-    }
-    sc[v] = s;
+    sc[v] = sl >= 0 ? pg_update_pose(poses + 7 * v, sl, nT, xT, xS, C, bS, ldz, mS, lambda) : 0.0;
 }
 
 // src/loopclosing.cpp:621-633: p <- T_new[kf]^-1 * (T_old[kf] * p)
@@ -371,14 +313,7 @@ __global__ void __launch_bounds__(256) k_correct_map_points(const double* __rest
     const int k = kf[i];
     if (k < 0) return;
     if (k >= nposes) { *status = MYSLAM_ERR_INVALID; return; }
-    Se3 To = pg_load(oldp + 7 * k), Tn = pg_load(newp + 7 * k);
-    pg_qnorm(To.q); pg_qnorm(Tn.q);
-    Tn = pg_inv(Tn);
-    double pc[3], pw[3];
-    pg_rot(To.q, pts + 3 * i, pc);
-    pc[0] += To.t[0]; pc[1] += To.t[1]; pc[2] += To.t[2];
-    pg_rot(Tn.q, pc, pw);
-    pts[3 * i] = pw[0] + Tn.t[0]; pts[3 * i + 1] = pw[1] + Tn.t[1]; pts[3 * i + 2] = pw[2] + Tn.t[2];
+    pg_move_point(pg_load(oldp + 7 * k), pg_load(newp + 7 * k), pts + 3 * i);
 }
 
 }  // namespace myslam_hip
@@ -583,7 +518,7 @@ int myslam_pose_graph_optimize(double* poses, int n, const uint8_t* fixed, const
                 if (ok) scale += res[1];
                 rho /= scale;
                 if (rho > 0 && std::isfinite(tempChi) && ok) {
-                    double alpha = 1. - pow(2 * rho - 1, 3);
+                    double alpha = 1. - pow(2 * rho - 1, 3);                 // k_loop_correct (loop_correct.hip) writes t * t * t: kept apart, the two need not round alike
                     alpha = std::min(alpha, 2. / 3.);
                     lambda *= std::max(1. / 3., alpha); ni = 2; currentChi = tempChi;
                 } else {
@@ -604,58 +539,17 @@ int myslam_pose_graph_optimize(double* poses, int n, const uint8_t* fixed, const
 
 // LoopClosing::LoopLocalFusion, src/loopclosing.cpp:466-507 (the arithmetic; the re-linking of observations :509-532 is Map bookkeeping
 // and stays with the integrator).  A handful of SE3 products on the host (unit quaternion + translation, renormalised after every
-// product as Sophus does), the map points on the device.
-namespace {
-struct HostSE3 { double q[4], t[3]; };
-inline void h_rot(const double* q, const double* v, double* out) {
-    double uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
-    uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-    out[0] = v[0] + q[3] * uv[0] + (q[1] * uv[2] - q[2] * uv[1]);
-    out[1] = v[1] + q[3] * uv[1] + (q[2] * uv[0] - q[0] * uv[2]);
-    out[2] = v[2] + q[3] * uv[2] + (q[0] * uv[1] - q[1] * uv[0]);
-}
-inline HostSE3 h_load(const double* p) {
-    HostSE3 r;
-    const double n = sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2] + p[3] * p[3]);
-    for (int k = 0; k < 4; k++) r.q[k] = p[k] / n;
-    for (int k = 0; k < 3; k++) r.t[k] = p[4 + k];
-    return r;
-}
-inline HostSE3 h_mul(const HostSE3& a, const HostSE3& b) {
-    HostSE3 r;
-    r.q[3] = a.q[3] * b.q[3] - a.q[0] * b.q[0] - a.q[1] * b.q[1] - a.q[2] * b.q[2];
-    r.q[0] = a.q[3] * b.q[0] + a.q[0] * b.q[3] + a.q[1] * b.q[2] - a.q[2] * b.q[1];
-    r.q[1] = a.q[3] * b.q[1] - a.q[0] * b.q[2] + a.q[1] * b.q[3] + a.q[2] * b.q[0];
-    r.q[2] = a.q[3] * b.q[2] + a.q[0] * b.q[1] - a.q[1] * b.q[0] + a.q[2] * b.q[3];
-    const double n = sqrt(r.q[0] * r.q[0] + r.q[1] * r.q[1] + r.q[2] * r.q[2] + r.q[3] * r.q[3]);
-    for (int k = 0; k < 4; k++) r.q[k] /= n;
-    double rt[3];
-    h_rot(a.q, b.t, rt);
-    for (int k = 0; k < 3; k++) r.t[k] = a.t[k] + rt[k];
-    return r;
-}
-inline HostSE3 h_inv(const HostSE3& a) {
-    HostSE3 r;
-    r.q[0] = -a.q[0]; r.q[1] = -a.q[1]; r.q[2] = -a.q[2]; r.q[3] = a.q[3];
-    double rt[3];
-    h_rot(r.q, a.t, rt);
-    for (int k = 0; k < 3; k++) r.t[k] = -rt[k];
-    return r;
-}
-}  // namespace
-
+// product as Sophus does: se3_quat.h, the device's own functions), the map points on the device.
 int myslam_loop_local_fusion(double* active_poses, int n_active, int cur, const double* corrected_cur_pose7, const int32_t* first_active_kf,
                              double* points, int n_points) {
     if (!active_poses || n_active < 1 || n_active > 64 || cur < 0 || cur >= n_active || !corrected_cur_pose7 || n_points < 0 ||
         (n_points > 0 && (!first_active_kf || !points)))
         return MYSLAM_ERR_INVALID;
     std::vector<double> oldp(active_poses, active_poses + (size_t)7 * n_active), newp((size_t)7 * n_active);
-    const HostSE3 Tc_inv = h_inv(h_load(active_poses + 7 * cur)), Tcc = h_load(corrected_cur_pose7);
-    for (int a = 0; a < n_active; a++) {
-        const HostSE3 T = (a == cur) ? Tcc : h_mul(h_mul(h_load(active_poses + 7 * a), Tc_inv), Tcc);       // :480-482
-        for (int k = 0; k < 4; k++) newp[7 * a + k] = T.q[k];
-        for (int k = 0; k < 3; k++) newp[7 * a + 4 + k] = T.t[k];
-    }
+    const auto load_unit = [](const double* p) { Se3 T = pg_load(p); pg_qnorm(T.q); return T; };
+    const Se3 Tc_inv = pg_inv(load_unit(active_poses + 7 * cur)), Tcc = load_unit(corrected_cur_pose7);
+    for (int a = 0; a < n_active; a++)
+        pg_store((a == cur) ? Tcc : pg_mul(pg_mul(load_unit(active_poses + 7 * a), Tc_inv), Tcc), newp.data() + 7 * a);       // :480-482
     if (n_points > 0) {
         int rc = myslam_correct_map_points(oldp.data(), newp.data(), n_active, first_active_kf, points, n_points);     // :486-502
         if (rc) return rc;

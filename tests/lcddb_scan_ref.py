@@ -163,7 +163,7 @@ def bf16_rne(x):
 
 
 def bf16_split3(x):
-    """(h, m, l): x split into three bf16 pieces by round-to-nearest-even, each as f32 (db_split3 of lcddb.hip)"""
+    """(h, m, l): x split into three bf16 pieces by round-to-nearest-even, each as f32 (bf16_split3 of csrc/wave_ops.h)"""
     x = np.asarray(x, np.float32)
     h = bf16_rne(x); r = (x - h).astype(np.float32)
     m = bf16_rne(r); q = (r - m).astype(np.float32)
