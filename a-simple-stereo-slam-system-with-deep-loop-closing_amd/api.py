@@ -906,6 +906,13 @@ class Tracker:
                                                           C.c_void_p(d_mp_id), C.c_void_p(d_mp_pos), C.c_void_p(d_mp_outlier), C.c_void_p(d_n_mp),
                                                           int(mp_cap)), "myslam_tracker_update_from_map_batch")
 
+    def clear_links_batch(self, d_kf_id, d_tag, d_n, list_cap, d_n_cleared=None):
+        """device pointers, asynchronous: Backend.culled_view()'s lists (stream s at + s * list_cap).  A stream with valid ids whose last frame is its
+        reference key-frame's frame (no step since the turn or the init) drops the landmark of every listed feature of that key-frame; any other
+        stream keeps every byte.  d_n_cleared `streams` i32 or None."""
+        _check(lib().myslam_tracker_clear_links_batch(self._h, C.c_void_p(d_kf_id or None), C.c_void_p(d_tag or None), C.c_void_p(d_n or None),
+                                                      int(list_cap), C.c_void_p(d_n_cleared or None)), "myslam_tracker_clear_links_batch")
+
     def set_image_batch(self, d_imgs, step, stride, d_select):
         """device pointers, asynchronous: the stored previous left image of every selected stream <- d_imgs[s], pyramid rebuilt"""
         _check(lib().myslam_tracker_set_image_batch(self._h, C.c_void_p(d_imgs), int(step), C.c_size_t(stride), C.c_void_p(d_select)),
@@ -1170,6 +1177,13 @@ class Backend:
         _check(lib().myslam_backend_solve_view(self._h, C.byref(pts), C.byref(slot)), "myslam_backend_solve_view")
         return pts.value, slot.value
 
+    def culled_view(self):
+        """(d_kf_id, d_tag, d_n_culled): device pointers of the list optimize_batch leaves of the features whose edge the solve removed
+        (src/backend.cpp:236-247), per item in input row order, strided by obs_cap: LoopKeyFrameStore.clear_links_batch / Tracker.clear_links_batch"""
+        kf, tag, n = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(lib().myslam_backend_culled_view(self._h, C.byref(kf), C.byref(tag), C.byref(n)), "myslam_backend_culled_view")
+        return kf.value, tag.value, n.value
+
     def insert_launches_per_call(self):
         return lib().myslam_backend_insert_launches_per_call(self._h)
 
@@ -1319,6 +1333,12 @@ class MapArchive:
         _check(lib().myslam_map_feature_slots_batch(self._h, C.c_void_p(d_feat_mp_id or None), C.c_void_p(d_n_feat or None), int(feat_cap), int(batch),
                                                     C.c_void_p(d_feat_landmark or None)), "myslam_map_feature_slots_batch")
 
+    def filter_landmarks_batch(self, d_feat_landmark, feat_cap, batch, d_n_dropped=None):
+        """LoopKeyFrameStore.detect_batch's d_loop_feat_landmark before loop_match_batch: every entry of the whole row that names an erased point
+        (state 2) becomes -1 (src/map.cpp:166-175 as src/loopclosing.cpp:218-237 sees it); d_n_dropped batch i32 or None.  One launch, recordable."""
+        _check(lib().myslam_map_filter_landmarks_batch(self._h, C.c_void_p(d_feat_landmark or None), int(feat_cap), int(batch),
+                                                       C.c_void_p(d_n_dropped or None)), "myslam_map_filter_landmarks_batch")
+
 
 LOOP_DETECT_CANDIDATE, LOOP_DETECT_NO_LOOP = 0, 1      # MYSLAM_LOOP_DETECT_*
 
@@ -1365,6 +1385,14 @@ class LoopKeyFrameStore:
         _check(lib().myslam_loop_store_set_landmarks_batch(self._h, _p(ids), len(ids), C.c_void_p(d_feat_landmark), C.c_void_p(d_n_feat)),
                "myslam_loop_store_set_landmarks_batch")
 
+    def clear_links_batch(self, d_kf_id, d_tag, d_n, list_cap, batch, d_pending_kf_id=None, d_pending_feat_landmark=None, d_n_cleared=None):
+        """Backend.culled_view()'s lists (item b at + b * list_cap): the named feature of a key-frame held, or of the pending key-frame (its id per item
+        and its batch x feat_cap table, in/out, both or neither), loses its landmark; ids not held and tags out of range are ignored.  d_n_cleared
+        batch i32 or None.  One launch, no host bookkeeping: recordable (StepGraph)."""
+        vp = lambda p: C.c_void_p(p or None)
+        _check(lib().myslam_loop_store_clear_links_batch(self._h, vp(d_kf_id), vp(d_tag), vp(d_n), int(list_cap), int(batch), vp(d_pending_kf_id),
+                                                         vp(d_pending_feat_landmark), vp(d_n_cleared)), "myslam_loop_store_clear_links_batch")
+
     def detect_batch(self, d_best_id, d_max_score, d_cnt, nq, d_loop_desc, d_n_loop, d_loop_pyr, d_loop_feat_landmark, d_loop_slot, d_status,
                      thr_high=0.94, max_suspected=3):
         """`max_score < thr_high or cnt > max_suspected` -> LOOP_DETECT_NO_LOOP, an id not held -> ERR_INVALID (both with n_loop 0, slot -1, nothing
@@ -1374,6 +1402,9 @@ class LoopKeyFrameStore:
                                               int(max_suspected), C.c_void_p(d_loop_desc), C.c_void_p(d_n_loop), C.c_void_p(d_loop_pyr),
                                               C.c_void_p(d_loop_feat_landmark), C.c_void_p(d_loop_slot), C.c_void_p(d_status)),
                "myslam_loop_detect_batch")
+
+
+LoopStore = LoopKeyFrameStore                          # the handle's name in the C ABI (myslam_loop_store)
 
 
 def loop_correct_structure(n_kf, active, loop, edge_v0, edge_v1):

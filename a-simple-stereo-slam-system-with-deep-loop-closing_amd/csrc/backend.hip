@@ -5,7 +5,8 @@
 //   k_ba_optimize         the solve of :208-243 (ba.hip, through backend_launch.h) on the handle's flat windows;
 //   k_backend_write_back  :234-266 with Map::RemoveAllOutlierMapPoints / RemoveOldActiveMapPoints (src/map.cpp:126-175): outlier edges leave the
 //                         observation table, emptied map points become outliers, poses and positions are stored, the map-point and observation
-//                         tables are compacted in place.
+//                         tables are compacted in place; the (key-frame id, feature tag) of every removed edge is listed in the handle's buffers
+//                         (myslam_backend_culled_view), for the loop store and the tracker, which hold those features too.
 // Every order is fixed by the tables, so positions come from block-wide exclusive scans (block_rank / block_exsum of dev_tables.h, whose two
 // barriers the in-place compactions of the write-back stand on): no global atomics, and an item's bytes depend neither on its slot nor on its
 // neighbours.  See include/myslam_hip.h for the contract.
@@ -45,10 +46,11 @@ struct BeWork {                         // the handle's buffers of optimise, str
 struct BeOut {
     uint8_t* obs_report; uint8_t* mp_report; int32_t* new_outlier_mp; int32_t* n_new_outlier_mp; double* obs_chi2;
     int32_t* rounds; int32_t* n_outlier_edges; int32_t* status;
-    struct Item { uint8_t* obs_report; uint8_t* mp_report; int32_t* new_outlier_mp; double* obs_chi2; };
+    int64_t* culled_kf_id; int32_t* culled_tag; int32_t* n_culled;         // the handle's: the features whose edge the solve removed (myslam_backend_culled_view)
+    struct Item { uint8_t* obs_report; uint8_t* mp_report; int32_t* new_outlier_mp; double* obs_chi2; int64_t* culled_kf_id; int32_t* culled_tag; };
     __device__ __forceinline__ Item item(int b, int mp_cap, int obs_cap) const {
         const size_t m = (size_t)b * mp_cap, o = (size_t)b * obs_cap;
-        return {obs_report + o, mp_report + m, new_outlier_mp + m, obs_chi2 + o};
+        return {obs_report + o, mp_report + m, new_outlier_mp + m, obs_chi2 + o, culled_kf_id + o, culled_tag + o};
     }
 };
 
@@ -210,7 +212,7 @@ __global__ __launch_bounds__(BE_NT) void k_backend_write_back(BeTables T, BeWork
         const int cm = clamped_count(nm, T.mp_cap), co = clamped_count(no, T.obs_cap);
         for (int r = t; r < co; r += BE_NT) { o.obs_report[r] = 0; o.obs_chi2[r] = 0.0; }
         for (int m = t; m < cm; m += BE_NT) o.mp_report[m] = 0;
-        if (t == 0) { O.rounds[b] = 0; O.n_outlier_edges[b] = 0; O.n_new_outlier_mp[b] = 0; O.status[b] = st; }
+        if (t == 0) { O.rounds[b] = 0; O.n_outlier_edges[b] = 0; O.n_new_outlier_mp[b] = 0; O.n_culled[b] = 0; O.status[b] = st; }
         return;
     }
     const auto tb = T.item(b);
@@ -251,17 +253,18 @@ __global__ __launch_bounds__(BE_NT) void k_backend_write_back(BeTables T, BeWork
     }
     __syncthreads();
 
-    // ---- observation rows, the same way ----
-    int n_rows = 0;
+    // ---- observation rows, the same way; the removed edges' (key-frame id, feature tag) are listed in row order (:236-247 reset that feature) ----
+    int n_rows = 0, n_cull = 0;
     for (int base = 0; base < no; base += BE_NT) {
         const int r = base + t;
-        bool keep = false;
+        bool keep = false, rem = false;
         int m2 = 0, kf = 0, tag = 0;
         uint8_t fl = 0;
         float u = 0, v = 0;
         if (r < no) {
             const int k = w.eidx[r];
-            const bool edge = w.eidx[r + 1] > k, rem = edge && w.out[k];
+            const bool edge = w.eidx[r + 1] > k;
+            rem = edge && w.out[k];
             m2 = w.mp_new[tb.obs_mp[r]];
             keep = m2 >= 0 && !rem;
             o.obs_report[r] = rem ? 1 : (m2 < 0 ? 2 : 0);
@@ -270,16 +273,18 @@ __global__ __launch_bounds__(BE_NT) void k_backend_write_back(BeTables T, BeWork
             fl = tb.obs_flags[r];
             if (edge) fl &= (uint8_t)~BE_OUTLIER;                                                 // :249
         }
-        int tot;
+        int tot, ctot;
         const int dst = n_rows + block_rank<BE_NW>(keep, s_w, tot);
+        const int cd = n_cull + block_rank<BE_NW>(rem, s_w, ctot);
         if (keep) {
             tb.obs_mp[dst] = m2; tb.obs_kf[dst] = kf; tb.obs_flags[dst] = fl; tb.obs_uv[2 * dst] = u; tb.obs_uv[2 * dst + 1] = v; tb.obs_tag[dst] = tag;
         }
-        n_rows += tot;
+        if (rem) { o.culled_kf_id[cd] = kf >= 0 ? tb.kf_id[kf] : -1; o.culled_tag[cd] = tag; }     // an edge row is ACTIVE: kf >= 0 (be_tables_bad)
+        n_rows += tot; n_cull += ctot;
     }
     if (t == 0) {
         T.n_mp[b] = n_keep; T.n_obs[b] = n_rows;
-        O.n_new_outlier_mp[b] = n_new; O.rounds[b] = W.rounds[b]; O.n_outlier_edges[b] = W.nout[b]; O.status[b] = MYSLAM_BACKEND_DONE;
+        O.n_new_outlier_mp[b] = n_new; O.n_culled[b] = n_cull; O.rounds[b] = W.rounds[b]; O.n_outlier_edges[b] = W.nout[b]; O.status[b] = MYSLAM_BACKEND_DONE;
     }
 }
 
@@ -524,7 +529,8 @@ struct myslam_backend {
     Buf<double> scratch;                // the solve's
     BeWork w{};                         // optimise's buffers, which debug_flat / debug_solved read after any later call ...
     InsWork iw{};                       // ... so insert's staging shares none of them
-    BufSet mem;                         // owns every block that `w` and `iw` name
+    int64_t* culled_kf_id = nullptr; int32_t* culled_tag = nullptr; int32_t* n_culled = nullptr;    // the write-back's list of culled features
+    BufSet mem;                         // owns every block that `w` and `iw` name, and the culled list
 };
 
 extern "C" {
@@ -559,13 +565,18 @@ int myslam_backend_create(myslam_backend** out, int max_batch, int kf_cap, int m
         (rc = own(iw.obs_kf, B * N)) || (rc = own(iw.obs_flags, B * N)) || (rc = own(iw.obs_uv, B * N * 2)) || (rc = own(iw.obs_tag, B * N)) ||
         (rc = own(iw.vid, B * N)) || (rc = own(iw.vft, B * N)) || (rc = own(iw.sid, B * N)) || (rc = own(iw.sfeat, B * N)) ||
         (rc = own(iw.dcum, B * (N + 1))) || (rc = own(iw.pcum, B * (N + 1))) || (rc = own(iw.dmp, B * (M + 1))) ||
-        (rc = own(iw.drows, B * (M + 1))) || (rc = own(iw.mp_fin, B * M)) || (rc = own(iw.mp_shift, B * M))) {
+        (rc = own(iw.drows, B * (M + 1))) || (rc = own(iw.mp_fin, B * M)) || (rc = own(iw.mp_shift, B * M)) ||
+        (rc = own(h->culled_kf_id, B * N)) || (rc = own(h->culled_tag, B * N)) || (rc = own(h->n_culled, B))) {
         delete h;
         return rc;
     }
     // debug_flat before the first call reports empty windows
     const std::vector<int32_t> zeros(B * 3, 0);
-    if ((rc = upload_table(w.sizes, zeros.data(), zeros.size() * sizeof(int32_t)))) { delete h; return rc; }
+    if ((rc = upload_table(w.sizes, zeros.data(), zeros.size() * sizeof(int32_t))) ||
+        (rc = upload_table(h->n_culled, zeros.data(), B * sizeof(int32_t)))) {             // culled_view before the first call: empty lists
+        delete h;
+        return rc;
+    }
     *out = h;
     return MYSLAM_OK;
 }
@@ -581,6 +592,12 @@ int myslam_backend_launches_per_call(const myslam_backend* h) { return h ? 3 : M
 int myslam_backend_solve_view(const myslam_backend* h, const double** d_points, const int32_t** d_mp_slot) {
     if (!h || !d_points || !d_mp_slot) return MYSLAM_ERR_INVALID;
     *d_points = h->w.pts; *d_mp_slot = h->w.mp_slot;
+    return MYSLAM_OK;
+}
+
+int myslam_backend_culled_view(const myslam_backend* h, const int64_t** d_kf_id, const int32_t** d_tag, const int32_t** d_n_culled) {
+    if (!h || !d_kf_id || !d_tag || !d_n_culled) return MYSLAM_ERR_INVALID;
+    *d_kf_id = h->culled_kf_id; *d_tag = h->culled_tag; *d_n_culled = h->n_culled;
     return MYSLAM_OK;
 }
 
@@ -600,7 +617,8 @@ int myslam_backend_optimize_batch(myslam_backend* h, const int64_t* d_kf_id, dou
     const BeTables T{d_kf_id, d_kf_pose, d_n_kf, d_mp_id, d_mp_pos, d_mp_outlier, d_n_mp, d_obs_mp, d_obs_kf, d_obs_flags, d_obs_uv, d_obs_tag, d_n_obs,
                      h->kf_cap, h->mp_cap, h->obs_cap};
     const BeWork& W = h->w;
-    const BeOut O{d_obs_report, d_mp_report, d_new_outlier_mp, d_n_new_outlier_mp, d_obs_chi2, d_rounds, d_n_outlier_edges, d_status};
+    const BeOut O{d_obs_report, d_mp_report, d_new_outlier_mp, d_n_new_outlier_mp, d_obs_chi2, d_rounds, d_n_outlier_edges, d_status,
+                  h->culled_kf_id, h->culled_tag, h->n_culled};
     hipLaunchKernelGGL(k_backend_flatten, dim3(batch), dim3(BE_NT), 0, h->stream, T, W);
     MYSLAM_HIP_CHECK(hipGetLastError());
     const int rc = ba_active_map_launch(W.poses, W.pts, W.ep, W.el, W.obs, W.fixed, W.sizes, W.st, batch, h->kf_cap, h->mp_cap, h->obs_cap, fx, fy, cx, cy,

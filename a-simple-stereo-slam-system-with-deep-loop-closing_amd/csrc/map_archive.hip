@@ -5,7 +5,8 @@
 //                        of every point, refreshes poses, positions and first observers, and remembers which archive slot each back-end row had;
 //   k_map_loop_inputs    the per-loop index inputs of myslam_loop_correct_batch;
 //   k_map_write_backend  the corrected poses and positions back into the back end's rows;
-//   k_map_feature_slots  map-point id -> archive slot per feature (myslam_loop_store_put_batch's d_feat_landmark).
+//   k_map_feature_slots  map-point id -> archive slot per feature (myslam_loop_store_put_batch's d_feat_landmark);
+//   k_map_filter_landmarks  the links of a gathered table to points erased since (one workgroup per item, a block scan for its count).
 // Ids ascend in every table, so a row is found by binary search (sorted_rows.h) and a new row's slot is a closed form: no scans, no atomics; an item's bytes depend
 // neither on its slot nor on its neighbours.  The edge measurement uses se3_chain.h (chain.py's arithmetic, built with -ffp-contract=off).
 // See include/myslam_hip.h for the contract.
@@ -256,6 +257,31 @@ __global__ __launch_bounds__(MA_NT) void k_map_feature_slots(MaTables A, const i
     feat_landmark[(size_t)b * feat_cap + f] = (s >= 0 && a.mp_state[s] != 2) ? s : -1;
 }
 
+// One workgroup per item over the whole row of a gathered feature -> landmark table (the matcher indexes it by class_id < feat_cap, without a count):
+// an entry that names an erased point becomes -1, as mpMapPoint.lock() of ComputeCorrectPose (src/loopclosing.cpp:218-237) finds it once
+// Map::RemoveAllOutlierMapPoints (src/map.cpp:166-175) dropped the point.  Every other value keeps its bits.
+__global__ __launch_bounds__(MA_NT) void k_map_filter_landmarks(MaTables A, int32_t* feat_landmark, int feat_cap, int32_t* n_dropped) {
+    __shared__ int s_w[MA_NT / WAVE];
+    const int b = blockIdx.x, t = threadIdx.x;
+    const int aM = clamped_count(A.n_mp, b, A.point_cap);
+    const uint8_t* const state = A.mp_state + (size_t)b * A.point_cap;
+    int32_t* const row = feat_landmark + (size_t)b * feat_cap;
+    int dropped = 0;
+    for (int base = 0; base < feat_cap; base += MA_NT) {                    // uniform
+        const int f = base + t;
+        bool drop = false;
+        if (f < feat_cap) {
+            const int e = row[f];
+            drop = e >= 0 && e < aM && state[e] == 2;
+            if (drop) row[f] = -1;
+        }
+        int tot;
+        (void)block_rank<MA_NT / WAVE>(drop, s_w, tot);
+        dropped += tot;
+    }
+    if (t == 0 && n_dropped) n_dropped[b] = dropped;
+}
+
 }  // namespace myslam_hip
 
 using namespace myslam_hip;
@@ -473,6 +499,15 @@ int myslam_map_feature_slots_batch(myslam_map* h, const int64_t* d_feat_mp_id, c
     if (batch == 0) return MYSLAM_OK;
     hipLaunchKernelGGL(k_map_feature_slots, dim3((feat_cap + MA_NT - 1) / MA_NT, batch), dim3(MA_NT), 0, h->stream, h->t, d_feat_mp_id, d_n_feat, feat_cap,
                        d_feat_landmark);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    return MYSLAM_OK;
+}
+
+int myslam_map_filter_landmarks_batch(myslam_map* h, int32_t* d_feat_landmark, int feat_cap, int batch, int32_t* d_n_dropped) {
+    if (!h || batch < 0 || !d_feat_landmark || feat_cap < 1) return MYSLAM_ERR_INVALID;
+    if (batch > h->max_batch) return MYSLAM_ERR_CAPACITY;
+    if (batch == 0) return MYSLAM_OK;
+    hipLaunchKernelGGL(k_map_filter_landmarks, dim3(batch), dim3(MA_NT), 0, h->stream, h->t, d_feat_landmark, feat_cap, d_n_dropped);
     MYSLAM_HIP_CHECK(hipGetLastError());
     return MYSLAM_OK;
 }

@@ -496,6 +496,32 @@ __global__ __launch_bounds__(TRK_NT) void k_kf_update(TrkArgs a, BeTablesRead g)
     }
 }
 
+// ---- the optimiser reset features of the reference key-frame (src/backend.cpp:236-247).  KeyFrame shares its Feature objects with its Frame
+//      (src/keyframe.cpp:21), so while the last frame IS that key-frame's frame (no step since the turn or the init) TrackLastFrame
+//      (src/frontend.cpp:127-171) sees the reset: feature `tag` of the stream loses its landmark.  Nothing else of the stream changes ----
+__global__ __launch_bounds__(TRK_NT) void k_trk_clear_links(TrkArgs a, const int64_t* kf_id, const int32_t* tag, const int32_t* n, int list_cap, int32_t* n_cleared) {
+    __shared__ int s_w[TRK_NW];
+    const int s = blockIdx.x, t = threadIdx.x;
+    const TrkState& st = a.st[s];
+    const bool on = st.idsValid != 0 && st.ref_frame_id == st.next_frame_id - 1;          // uniform
+    const int cnt = on ? clamped_count(n, s, list_cap) : 0, nFeat = clamped_count(st.n_feat, a.cap);
+    const int64_t ref = a.ids[(size_t)s * 3];
+    int cleared = 0;
+    for (int base = 0; base < cnt; base += TRK_NT) {
+        const int j = base + t;
+        bool hit = false;
+        if (j < cnt) {
+            const int f = tag[(size_t)s * list_cap + j];
+            hit = kf_id[(size_t)s * list_cap + j] == ref && f >= 0 && f < nFeat;
+            if (hit) a.lm[(size_t)s * a.cap + f] = -1;
+        }
+        int tot;
+        (void)block_rank<TRK_NW>(hit, s_w, tot);
+        cleared += tot;
+    }
+    if (t == 0 && n_cleared) n_cleared[s] = cleared;
+}
+
 // ---- the stored previous left image of the selected streams <- imgs (the pyramid follows in lk_bank_pyramid) ----
 __global__ __launch_bounds__(TRK_NT) void k_kf_set_image(TrkArgs a, const uint8_t* imgs, int step, size_t stride, const uint8_t* select) {
     const int s = blockIdx.y, t = threadIdx.x;
@@ -989,6 +1015,13 @@ int myslam_tracker_update_from_map_batch(myslam_tracker* h, const int64_t* d_kf_
     if (!h || !d_kf_id || !d_kf_pose || !d_n_kf || kf_cap < 1 || !d_mp_id || !d_mp_pos || !d_mp_outlier || !d_n_mp || mp_cap < 1) return MYSLAM_ERR_INVALID;
     const BeTablesRead g{d_kf_id, d_kf_pose, d_n_kf, d_mp_id, d_mp_pos, d_mp_outlier, d_n_mp, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, kf_cap, mp_cap, 0};
     hipLaunchKernelGGL(k_kf_update, dim3(h->S), dim3(TRK_NT), 0, h->stream, h->a, g);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    return MYSLAM_OK;
+}
+
+int myslam_tracker_clear_links_batch(myslam_tracker* h, const int64_t* d_kf_id, const int32_t* d_tag, const int32_t* d_n, int list_cap, int32_t* d_n_cleared) {
+    if (!h || !d_kf_id || !d_tag || !d_n || list_cap <= 0) return MYSLAM_ERR_INVALID;
+    hipLaunchKernelGGL(k_trk_clear_links, dim3(h->S), dim3(TRK_NT), 0, h->stream, h->a, d_kf_id, d_tag, d_n, list_cap, d_n_cleared);
     MYSLAM_HIP_CHECK(hipGetLastError());
     return MYSLAM_OK;
 }

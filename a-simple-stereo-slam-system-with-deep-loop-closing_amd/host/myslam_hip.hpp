@@ -443,6 +443,11 @@ public:
         check(myslam_tracker_update_from_map_batch(h_, d_kfId, d_kfPose, d_nKf, kfCap, d_mpId, d_mpPos, d_mpOutlier, d_nMp, mpCap),
               "myslam_tracker_update_from_map_batch");
     }
+    // Backend::CulledView's lists (stream s at + s * listCap): a stream whose last frame is its reference key-frame's frame drops the landmark of every
+    // listed feature of that key-frame (src/keyframe.cpp:21: the Feature objects are shared); any other stream keeps every byte
+    void ClearLinksBatch(const int64_t* d_kfId, const int32_t* d_tag, const int32_t* d_n, int listCap, int32_t* d_nCleared = nullptr) {
+        check(myslam_tracker_clear_links_batch(h_, d_kfId, d_tag, d_n, listCap, d_nCleared), "myslam_tracker_clear_links_batch");
+    }
     // the stored previous left image of the selected streams <- d_imgs[s] (a key-frame's image after DeepLCD blurred it)
     void SetImageBatch(const uint8_t* d_imgs, int step, size_t stride, const uint8_t* d_select) {
         check(myslam_tracker_set_image_batch(h_, d_imgs, step, stride, d_select), "myslam_tracker_set_image_batch");
@@ -622,6 +627,11 @@ public:
     void SolveView(const double** d_points, const int32_t** d_mpSlot) const {
         check(myslam_backend_solve_view(h_, d_points, d_mpSlot), "myslam_backend_solve_view");
     }
+    // the features whose edge the last OptimizeBatch removed (src/backend.cpp:236-247): (key-frame id, feature index) per item in input row order,
+    // stride obsCap, and their counts; valid until destruction.  LoopKeyFrameStore::ClearLinksBatch / TrackerBank::ClearLinksBatch take them
+    void CulledView(const int64_t** d_kfId, const int32_t** d_tag, const int32_t** d_nCulled) const {
+        check(myslam_backend_culled_view(h_, d_kfId, d_tag, d_nCulled), "myslam_backend_culled_view");
+    }
     void OptimizeBatch(const int64_t* d_kfId, double* d_kfPose, const int32_t* d_nKF, int64_t* d_mpId, double* d_mpPos, uint8_t* d_mpOutlier, int32_t* d_nMP,
                        int32_t* d_obsMP, int32_t* d_obsKF, uint8_t* d_obsFlags, float* d_obsUV, int32_t* d_obsTag, int32_t* d_nObs, int batch, double fx,
                        double fy, double cx, double cy, uint8_t* d_obsReport, uint8_t* d_mpReport, int32_t* d_newOutlierMP, int32_t* d_nNewOutlierMP,
@@ -666,8 +676,9 @@ public:
 // Map::mmAllKeyFrames / mmAllMapPoints and KeyFrame::mpLastKF / mRelativePoseToLastKF of maxBatch streams as device tables (myslam_map_*,
 // include/myslam_hip.h): UpdateBatch after EVERY Backend call on the same stream keeps them current, and they are laid out as
 // LoopCorrector::CorrectBatch's tables (View() gives the device pointers).  Order of a key-frame: InsertKeyFrameBatch -> UpdateBatch(AFTER_INSERT) ->
-// OptimizeBatch -> UpdateBatch(AFTER_OPTIMIZE) -> ... -> LoopInputsBatch -> CorrectBatch -> WriteBackendBatch -> Tracker::UpdateFromMap.  Left with
-// the caller: LoopLocalFusion's re-linking of observations, and clearing single features' landmarks in the loop store when BA culls an observation.
+// OptimizeBatch -> UpdateBatch(AFTER_OPTIMIZE) -> Backend::CulledView's lists into LoopKeyFrameStore::ClearLinksBatch and TrackerBank::ClearLinksBatch
+// -> ... -> DetectBatch -> FilterLandmarksBatch -> MatchFeaturesBatch -> ... -> LoopInputsBatch -> CorrectBatch -> WriteBackendBatch ->
+// Tracker::UpdateFromMap.  Left with the caller: LoopLocalFusion's re-linking of observations.
 class MapArchive {
     myslam_map* h_ = nullptr;
 public:
@@ -728,6 +739,10 @@ public:
     void FeatureSlotsBatch(const int64_t* d_featMPId, const int32_t* d_nFeat, int featCap, int batch, int32_t* d_featureLandmark) {
         check(myslam_map_feature_slots_batch(h_, d_featMPId, d_nFeat, featCap, batch, d_featureLandmark), "myslam_map_feature_slots_batch");
     }
+    // DetectBatch's d_loopFeatureLandmark before MatchFeaturesBatch: links to points erased since the key-frame was stored become -1 (src/map.cpp:166-175)
+    void FilterLandmarksBatch(int32_t* d_featureLandmark, int featCap, int batch, int32_t* d_nDropped = nullptr) {
+        check(myslam_map_filter_landmarks_batch(h_, d_featureLandmark, featCap, batch, d_nDropped), "myslam_map_filter_landmarks_batch");
+    }
 };
 
 // What ProcessNewKF leaves in a KeyFrame (mvPyramidKeyPoints, mORBDescriptors, which features still name a map point), resident on the device for up to
@@ -757,6 +772,13 @@ public:
     }
     void SetLandmarksBatch(const std::vector<uint64_t>& ids, const int32_t* d_featureLandmark, const int32_t* d_nFeatures) {
         check(myslam_loop_store_set_landmarks_batch(h_, ids.data(), (int)ids.size(), d_featureLandmark, d_nFeatures), "myslam_loop_store_set_landmarks_batch");
+    }
+    // Backend::CulledView's lists: the named feature of a key-frame held, or of the pending one (its id per item and its table, both or neither), loses its
+    // landmark; ids that are not held are ignored.  One launch, no host bookkeeping: it can be recorded
+    void ClearLinksBatch(const int64_t* d_kfId, const int32_t* d_tag, const int32_t* d_n, int listCap, int batch, const int64_t* d_pendingKfId = nullptr,
+                         int32_t* d_pendingFeatureLandmark = nullptr, int32_t* d_nCleared = nullptr) {
+        check(myslam_loop_store_clear_links_batch(h_, d_kfId, d_tag, d_n, listCap, batch, d_pendingKfId, d_pendingFeatureLandmark, d_nCleared),
+              "myslam_loop_store_clear_links_batch");
     }
     void DetectBatch(const uint64_t* d_bestId, const float* d_maxScore, const int32_t* d_cntSuspected, int nq, uint8_t* d_loopDescriptors, int32_t* d_nLoop,
                      KeyPoint* d_loopPyramidKeyPoints, int32_t* d_loopFeatureLandmark, int32_t* d_loopSlot, int32_t* d_status, float thrHigh = 0.94f /*:147*/,

@@ -1326,8 +1326,8 @@ int myslam_backend_insert_launches_per_call(const myslam_backend* h);
  * global atomics; an item's bytes depend neither on its slot nor on its neighbours.  Call level, nothing enqueued: NULL pointers, an unknown mode, a
  * back-end cap that does not match (be_kf_cap beyond MYSLAM_BA_MAX_WINDOW_POSES included) -> MYSLAM_ERR_INVALID; batch beyond the handle's -> MYSLAM_ERR_CAPACITY.
  * OUT OF SCOPE, left with the caller: LoopLocalFusion's re-linking of observations (src/loopclosing.cpp:509-532) with its effect on the back end's
- * tables and the tracker's landmark ids; clearing single features' landmarks in the loop store when BA culls an observation
- * (myslam_loop_store_set_landmarks_batch).
+ * tables and the tracker's landmark ids.  Culled and erased links: LINK UPKEEP, below; whole tables from a host map:
+ * myslam_loop_store_set_landmarks_batch.
  * ------------------------------------------------------------------------------------------ */
 #define MYSLAM_MAP_AFTER_INSERT 0
 #define MYSLAM_MAP_AFTER_OPTIMIZE 1
@@ -1377,6 +1377,57 @@ int myslam_map_loop_inputs_batch(myslam_map* h, const int64_t* d_kf_id, const in
 int myslam_map_write_backend_batch(myslam_map* h, const int64_t* d_kf_id, double* d_kf_pose, const int32_t* d_n_kf, int be_kf_cap, const int64_t* d_mp_id,
                                    double* d_mp_pos, const int32_t* d_n_mp, int be_mp_cap, const uint8_t* d_select, int batch);
 int myslam_map_feature_slots_batch(myslam_map* h, const int64_t* d_feat_mp_id, const int32_t* d_n_feat, int feat_cap, int batch, int32_t* d_feat_landmark);
+
+/* ------------------------------------------------------------------------------------------
+ * LINK UPKEEP — a key-frame feature's mpMapPoint.lock() that goes null after the key-frame was made, on the device.  Two things do that:
+ *   CULLED  Backend::OptimizeActiveMap removes an outlier edge and resets the feature's map point (src/backend.cpp:236-247).  KeyFrame shares its
+ *           Feature objects with its Frame (src/keyframe.cpp:21): the next TrackLastFrame (src/frontend.cpp:127-171) sees the reset when the last
+ *           frame is that key-frame's frame, and ComputeCorrectPose (src/loopclosing.cpp:218-237) sees it when the key-frame is a loop key-frame.
+ *   ERASED  Map::RemoveAllOutlierMapPoints (src/map.cpp:166-175) drops the map's only shared_ptr: every feature that pointed at the point locks null.
+ * Order of one key-frame:  ... optimise -> update(AFTER_OPTIMIZE) -> culled_view's lists -> myslam_loop_store_clear_links_batch (pending = the turn's
+ * feature-slot table, which is put afterwards: the AddToDatabase order, src/loopclosing.cpp:73-75) + myslam_tracker_clear_links_batch -> put -> ...
+ * -> detect -> myslam_map_filter_landmarks_batch on d_loop_feat_landmark -> match.  Filtering erased points at use is exact: an erased id never
+ * returns, and ComputeCorrectPose asks lock() at that same moment.  Erased points need no tracker rule: the frontend resets the feature that made
+ * it list a point (src/frontend.cpp:267).
+ * Each of the three batch calls is ONE launch, one workgroup per item, on its handle's stream; nothing is allocated or synchronised, no device memory
+ * is read from the host, no global atomics; an item's bytes depend neither on its slot nor on its neighbours; all are recordable between
+ * myslam_graph_begin / _end (myslam_loop_store_clear_links_batch too: unlike put_batch it does no host bookkeeping, and it reads the ids and the
+ * number of key-frames held on the device, so a replay sees what was put after the recording).
+ *
+ * myslam_backend_culled_view — the device pointers of the list k_backend_write_back writes with every myslam_backend_optimize_batch (still three
+ * launches), valid until destroy, stride obs_cap:  d_kf_id (max_batch x obs_cap i64) = d_kf_id[b][d_obs_kf[row]] and d_tag (i32) = d_obs_tag[row] of
+ * every INPUT row with d_obs_report == 1, in input row order (a removed edge row is ACTIVE, so d_obs_kf >= 0; the turn and the init write the
+ * feature's index into d_feat_tag);  d_n_culled (max_batch i32) their number = d_n_outlier_edges.  A refused or EMPTY item: 0.  Items from the call's
+ * batch on keep their bytes; entries from the count on are unspecified; before the first call every count is 0.
+ *
+ * myslam_loop_store_clear_links_batch — item b's list at d_kf_id / d_tag + b * list_cap, d_n[b] entries (clamped to [0, list_cap]).  An entry with
+ * id >= 0 and tag >= 0:  the pending pointers are given, id == d_pending_kf_id[b] and tag < feat_cap -> d_pending_feat_landmark[b][tag] = -1;
+ * otherwise the id is searched among the ids held: found and tag < that slot's stored feature count -> that entry of the slot's table = -1.  Anything
+ * else (an id not held — key-frames that closed a loop and the five after it are never stored, src/loopclosing.cpp:671-681 —, a negative id, a
+ * tag out of range) is ignored.  d_n_cleared[b] (may be NULL) = the entries that named a stored or pending feature: entries, not distinct features
+ * (the writes are idempotent).  Call level, nothing enqueued: a required pointer NULL, exactly one pending pointer NULL, list_cap <= 0 or
+ * batch <= 0 -> MYSLAM_ERR_INVALID; batch > 65535 -> MYSLAM_ERR_CAPACITY.
+ *
+ * myslam_map_filter_landmarks_batch — the whole row of d_feat_landmark (batch x feat_cap; the matcher indexes it by class_id without a count): an
+ * entry e with 0 <= e < n_mp[b] and mp_state[b][e] == 2 becomes -1; every other value (-1 and out-of-range values included, which the matcher
+ * reports itself) keeps its bits.  d_n_dropped[b] (may be NULL) = the entries changed.  NULL table or feat_cap <= 0 -> MYSLAM_ERR_INVALID; batch
+ * beyond the handle's -> MYSLAM_ERR_CAPACITY.
+ *
+ * myslam_tracker_clear_links_batch — item s = stream s, lists strided by list_cap.  A stream is touched only when its ids are valid and
+ * ref_frame_id == next_frame_id - 1 (the last frame is the reference key-frame's frame; frozen or not): every entry with d_kf_id == ref_kf_id and
+ * 0 <= tag < n_feat sets that feature's landmark slot to -1.  The landmark table, ids, outlier list and everything else keep their bytes (the next
+ * turn's rebuild drops landmarks nothing names).  Any other stream keeps every byte and reports 0 in d_n_cleared (S, may be NULL).
+ * ------------------------------------------------------------------------------------------ */
+/* src/backend.cpp:236-247: the features whose edge the solve removed */
+int myslam_backend_culled_view(const myslam_backend* h, const int64_t** d_kf_id, const int32_t** d_tag, const int32_t** d_n_culled);
+/* src/backend.cpp:236-247 as ComputeCorrectPose (src/loopclosing.cpp:218-237) sees it in a stored key-frame */
+int myslam_loop_store_clear_links_batch(myslam_loop_store* h, const int64_t* d_kf_id, const int32_t* d_tag, const int32_t* d_n, int list_cap, int batch,
+                                        const int64_t* d_pending_kf_id, int32_t* d_pending_feat_landmark, int32_t* d_n_cleared);
+/* src/map.cpp:166-175 as src/loopclosing.cpp:218-237 sees it */
+int myslam_map_filter_landmarks_batch(myslam_map* h, int32_t* d_feat_landmark, int feat_cap, int batch, int32_t* d_n_dropped);
+/* src/backend.cpp:236-247 as TrackLastFrame (src/frontend.cpp:127-171) sees it through src/keyframe.cpp:21 */
+int myslam_tracker_clear_links_batch(myslam_tracker* h, const int64_t* d_kf_id, const int32_t* d_tag, const int32_t* d_n, int list_cap,
+                                     int32_t* d_n_cleared);
 
 /* ------------------------------------------------------------------------------------------
  * Host-side formats of the reference's runner — plain host code, no device needed; the C++ forms live in
