@@ -1340,6 +1340,84 @@ class MapArchive:
                                                        C.c_void_p(d_n_dropped or None)), "myslam_map_filter_landmarks_batch")
 
 
+class ObsArchive:
+    """MapPoint::GetObservations() of every map point of `max_batch` streams that is alive and not in the back end's table (myslam_obs_archive_*):
+    the source of insert_keyframe_batch's prior rows.  `map_archive` is the MapArchive of the same streams (kept alive by this object), `be_obs_cap`
+    the back end's obs_cap, `row_cap` the stored rows one item holds.  Order of a key-frame, one stream: prior_rows_batch -> insert ->
+    MapArchive.update_batch -> update_batch -> optimise -> MapArchive.update_batch -> update_batch(d_obs_report).  Batch calls take device pointers
+    as ints, enqueue one launch and return."""
+
+    def __init__(self, map_archive, max_batch, be_obs_cap, row_cap, stream=None):
+        self.map, self.max_batch, self.be_obs_cap, self.row_cap = map_archive, int(max_batch), int(be_obs_cap), int(row_cap)
+        self.be_mp_cap = map_archive.backend_mp_cap
+        self._h = C.c_void_p()
+        _check(lib().myslam_obs_archive_create(C.byref(self._h), map_archive._h, self.max_batch, self.be_obs_cap, self.row_cap), "myslam_obs_archive_create")
+        if stream is not None:
+            self.set_stream(stream)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and self._h.value and _lib is not None:
+            lib().myslam_obs_archive_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def set_stream(self, stream):
+        _check(lib().myslam_obs_archive_set_stream(self._h, C.c_void_p(stream)), "myslam_obs_archive_set_stream")
+
+    def launches_per_update(self):
+        return lib().myslam_obs_archive_launches_per_update(self._h)
+
+    def load(self, item, seg_mp_id, seg_count, row_kf_id, row_uv, row_tag, row_flags, table_mp_id=(), table_mp_rows=(), table_kf_id=(), table_uv=(),
+             table_tag=(), table_flags=()):
+        """one item from host arrays (synchronous): the live segments and the mirror of the back end's current table; clears the sticky error.
+        MyslamError(INVALID / CAPACITY) on what the header lists, the item then keeps every byte"""
+        a = [np.ascontiguousarray(seg_mp_id, np.int64), np.ascontiguousarray(seg_count, np.int32), np.ascontiguousarray(row_kf_id, np.int64),
+             np.ascontiguousarray(row_uv, np.float32).reshape(-1, 2), np.ascontiguousarray(row_tag, np.int32), np.ascontiguousarray(row_flags, np.uint8),
+             np.ascontiguousarray(table_mp_id, np.int64), np.ascontiguousarray(table_mp_rows, np.int32), np.ascontiguousarray(table_kf_id, np.int64),
+             np.ascontiguousarray(table_uv, np.float32).reshape(-1, 2), np.ascontiguousarray(table_tag, np.int32), np.ascontiguousarray(table_flags, np.uint8)]
+        assert len(a[0]) == len(a[1]) and len(a[2]) == len(a[3]) == len(a[4]) == len(a[5]) and len(a[6]) == len(a[7]) and len(a[8]) == len(a[9]) == len(a[10]) == len(a[11])
+        _check(lib().myslam_obs_archive_load(self._h, int(item), _p(a[0]), _p(a[1]), len(a[0]), _p(a[2]), _p(a[3]), _p(a[4]), _p(a[5]), len(a[2]), _p(a[6]),
+                                             _p(a[7]), len(a[6]), _p(a[8]), _p(a[9]), _p(a[10]), _p(a[11]), len(a[8])), "myslam_obs_archive_load")
+
+    def get(self, item):
+        """one item as a dict of numpy arrays cut to their counts (synchronises): the live segments in ascending id order (seg_mp_id, seg_count and the
+        rows row_kf_id / row_uv / row_tag / row_flags), the mirror (table_*), rows_in_use, n_reclaims and the sticky error (0 = none)"""
+        R, M, O = self.row_cap, self.be_mp_cap, self.be_obs_cap
+        a = dict(seg_mp_id=np.zeros(R, np.int64), seg_count=np.zeros(R, np.int32), row_kf_id=np.zeros(R, np.int64), row_uv=np.zeros((R, 2), np.float32),
+                 row_tag=np.zeros(R, np.int32), row_flags=np.zeros(R, np.uint8), table_mp_id=np.zeros(M, np.int64), table_mp_rows=np.zeros(M, np.int32),
+                 table_kf_id=np.zeros(O, np.int64), table_uv=np.zeros((O, 2), np.float32), table_tag=np.zeros(O, np.int32), table_flags=np.zeros(O, np.uint8))
+        n = [C.c_int() for _ in range(7)]
+        _check(lib().myslam_obs_archive_get(self._h, int(item), _p(a["seg_mp_id"]), _p(a["seg_count"]), C.byref(n[0]), _p(a["row_kf_id"]), _p(a["row_uv"]),
+                                            _p(a["row_tag"]), _p(a["row_flags"]), C.byref(n[1]), _p(a["table_mp_id"]), _p(a["table_mp_rows"]), C.byref(n[2]),
+                                            _p(a["table_kf_id"]), _p(a["table_uv"]), _p(a["table_tag"]), _p(a["table_flags"]), C.byref(n[3]), C.byref(n[4]),
+                                            C.byref(n[5]), C.byref(n[6])), "myslam_obs_archive_get")
+        ns, nr, ntm, ntr = (v.value for v in n[:4])
+        cut = dict(seg_mp_id=ns, seg_count=ns, row_kf_id=nr, row_uv=nr, row_tag=nr, row_flags=nr, table_mp_id=ntm, table_mp_rows=ntm, table_kf_id=ntr,
+                   table_uv=ntr, table_tag=ntr, table_flags=ntr)
+        out = {k: v[:cut[k]].copy() for k, v in a.items()}
+        out.update(rows_in_use=n[4].value, n_reclaims=n[5].value, error=n[6].value)
+        return out
+
+    def update_batch(self, mode, d_kf_id, d_kf_pose, d_n_kf, d_mp_id, d_mp_pos, d_mp_outlier, d_n_mp, d_obs_mp, d_obs_kf, d_obs_flags, d_obs_uv, d_obs_tag,
+                     d_n_obs, be_kf_cap, be_mp_cap, be_obs_cap, d_backend_status, d_map_status, d_obs_report, batch, d_status):
+        """after each MapArchive.update_batch: the back end's thirteen tables as they stand (optimize_batch's order) and its caps, the back-end call's
+        and the map update's d_status, and after an optimise its d_obs_report (None / 0 after an insert); d_status batch i32 = MAP_UPDATED /
+        MAP_SKIPPED or a negative, sticky error"""
+        vp = lambda p: C.c_void_p(p or None)
+        _check(lib().myslam_obs_archive_update_batch(self._h, int(mode), vp(d_kf_id), vp(d_kf_pose), vp(d_n_kf), vp(d_mp_id), vp(d_mp_pos), vp(d_mp_outlier),
+                                                     vp(d_n_mp), vp(d_obs_mp), vp(d_obs_kf), vp(d_obs_flags), vp(d_obs_uv), vp(d_obs_tag), vp(d_n_obs),
+                                                     int(be_kf_cap), int(be_mp_cap), int(be_obs_cap), vp(d_backend_status), vp(d_map_status),
+                                                     vp(d_obs_report), int(batch), vp(d_status)), "myslam_obs_archive_update_batch")
+
+    def prior_rows_batch(self, d_feat_mp_id, d_n_feat, feat_cap, d_mp_id, d_n_mp, be_mp_cap, batch, d_prior_mp_id, d_prior_kf_id, d_prior_uv, d_prior_tag,
+                         d_prior_flags, d_n_prior, prior_cap, d_status):
+        """before the insert: the stored rows of every distinct stored point a feature names, ids ascending, in insert_keyframe_batch's prior arrays
+        (batch x prior_cap); d_status batch i32 = 0, ERR_CAPACITY (more rows than prior_cap: n_prior 0) or the item's sticky error"""
+        vp = lambda p: C.c_void_p(p or None)
+        _check(lib().myslam_obs_archive_prior_rows_batch(self._h, vp(d_feat_mp_id), vp(d_n_feat), int(feat_cap), vp(d_mp_id), vp(d_n_mp), int(be_mp_cap),
+                                                         int(batch), vp(d_prior_mp_id), vp(d_prior_kf_id), vp(d_prior_uv), vp(d_prior_tag), vp(d_prior_flags),
+                                                         vp(d_n_prior), int(prior_cap), vp(d_status)), "myslam_obs_archive_prior_rows_batch")
+
+
 LOOP_DETECT_CANDIDATE, LOOP_DETECT_NO_LOOP = 0, 1      # MYSLAM_LOOP_DETECT_*
 
 

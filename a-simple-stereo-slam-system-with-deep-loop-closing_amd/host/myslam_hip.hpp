@@ -743,6 +743,57 @@ public:
     void FilterLandmarksBatch(int32_t* d_featureLandmark, int featCap, int batch, int32_t* d_nDropped = nullptr) {
         check(myslam_map_filter_landmarks_batch(h_, d_featureLandmark, featCap, batch, d_nDropped), "myslam_map_filter_landmarks_batch");
     }
+    const myslam_map* handle() const { return h_; }
+};
+
+// MapPoint::GetObservations() (src/mappoint.cpp:19-44) of every map point that is alive and not in the back end's table, per stream, on the device
+// (myslam_obs_archive_*, include/myslam_hip.h): the source of Backend::InsertKeyFrameBatch's prior rows, so that a map point that comes back is the
+// fixed landmark src/backend.cpp:175-177 makes of it.  `map` is the MapArchive of the same streams and must outlive this object.  Order of a key-frame
+// on one stream: PriorRowsBatch -> InsertKeyFrameBatch (with those arrays) -> MapArchive::UpdateBatch -> UpdateBatch -> OptimizeBatch ->
+// MapArchive::UpdateBatch -> UpdateBatch (with OptimizeBatch's d_obsReport).  Errors of an item are sticky until Load.
+class ObsArchive {
+    myslam_obs_archive* h_ = nullptr;
+public:
+    ObsArchive(const MapArchive& map, int maxBatch, int backendObsCap, int rowCap) {
+        check(myslam_obs_archive_create(&h_, map.handle(), maxBatch, backendObsCap, rowCap), "myslam_obs_archive_create");
+    }
+    ~ObsArchive() { if (h_) myslam_obs_archive_destroy(h_); }
+    ObsArchive(const ObsArchive&) = delete; ObsArchive& operator=(const ObsArchive&) = delete;
+    void SetStream(void* hipStream) { check(myslam_obs_archive_set_stream(h_, hipStream), "myslam_obs_archive_set_stream"); }
+    int LaunchesPerUpdate() const { return myslam_obs_archive_launches_per_update(h_); }
+    // one item from / to host arrays (synchronous): the live segments (ids ascending) with their rows, and the mirror of the back end's current table
+    void Load(int item, const int64_t* segMPId, const int32_t* segCount, int nSeg, const int64_t* rowKFId, const float* rowUV, const int32_t* rowTag,
+              const uint8_t* rowFlags, int nRows, const int64_t* tableMPId = nullptr, const int32_t* tableMPRows = nullptr, int nTableMP = 0,
+              const int64_t* tableKFId = nullptr, const float* tableUV = nullptr, const int32_t* tableTag = nullptr, const uint8_t* tableFlags = nullptr,
+              int nTableRows = 0) {
+        check(myslam_obs_archive_load(h_, item, segMPId, segCount, nSeg, rowKFId, rowUV, rowTag, rowFlags, nRows, tableMPId, tableMPRows, nTableMP, tableKFId,
+                                      tableUV, tableTag, tableFlags, nTableRows), "myslam_obs_archive_load");
+    }
+    // seg and row arrays sized rowCap, table arrays by the back end's mpCap / obsCap; any pointer may be nullptr
+    void Get(int item, int64_t* segMPId, int32_t* segCount, int* nSeg, int64_t* rowKFId, float* rowUV, int32_t* rowTag, uint8_t* rowFlags, int* nRows,
+             int64_t* tableMPId = nullptr, int32_t* tableMPRows = nullptr, int* nTableMP = nullptr, int64_t* tableKFId = nullptr, float* tableUV = nullptr,
+             int32_t* tableTag = nullptr, uint8_t* tableFlags = nullptr, int* nTableRows = nullptr, int* rowsInUse = nullptr, int* nReclaims = nullptr,
+             int* error = nullptr) {
+        check(myslam_obs_archive_get(h_, item, segMPId, segCount, nSeg, rowKFId, rowUV, rowTag, rowFlags, nRows, tableMPId, tableMPRows, nTableMP, tableKFId,
+                                     tableUV, tableTag, tableFlags, nTableRows, rowsInUse, nReclaims, error), "myslam_obs_archive_get");
+    }
+    // after EACH MapArchive::UpdateBatch: the back end's tables as they stand, the back-end call's and the map update's status, and after an optimise
+    // its d_obsReport (nullptr after an insert); status[b] = MYSLAM_MAP_UPDATED / _SKIPPED or a negative, sticky error
+    void UpdateBatch(int mode, const Backend& be, const int64_t* d_kfId, const int32_t* d_nKF, const int64_t* d_mpId, const int32_t* d_nMP,
+                     const int32_t* d_obsMP, const int32_t* d_obsKF, const uint8_t* d_obsFlags, const float* d_obsUV, const int32_t* d_obsTag,
+                     const int32_t* d_nObs, const int32_t* d_backendStatus, const int32_t* d_mapStatus, const uint8_t* d_obsReport, int batch,
+                     int32_t* d_status) {
+        check(myslam_obs_archive_update_batch(h_, mode, d_kfId, nullptr, d_nKF, d_mpId, nullptr, nullptr, d_nMP, d_obsMP, d_obsKF, d_obsFlags, d_obsUV, d_obsTag,
+                                              d_nObs, be.kfCap(), be.mpCap(), be.obsCap(), d_backendStatus, d_mapStatus, d_obsReport, batch, d_status),
+              "myslam_obs_archive_update_batch");
+    }
+    // before the insert: the stored rows of every distinct stored point a feature names, ids ascending, in InsertKeyFrameBatch's prior arrays
+    void PriorRowsBatch(const Backend& be, const int64_t* d_featMPId, const int32_t* d_nFeat, int featCap, const int64_t* d_mpId, const int32_t* d_nMP,
+                        int batch, int64_t* d_priorMPId, int64_t* d_priorKFId, float* d_priorUV, int32_t* d_priorTag, uint8_t* d_priorFlags,
+                        int32_t* d_nPrior, int priorCap, int32_t* d_status) {
+        check(myslam_obs_archive_prior_rows_batch(h_, d_featMPId, d_nFeat, featCap, d_mpId, d_nMP, be.mpCap(), batch, d_priorMPId, d_priorKFId, d_priorUV,
+                                                  d_priorTag, d_priorFlags, d_nPrior, priorCap, d_status), "myslam_obs_archive_prior_rows_batch");
+    }
 };
 
 // What ProcessNewKF leaves in a KeyFrame (mvPyramidKeyPoints, mORBDescriptors, which features still name a map point), resident on the device for up to

@@ -1430,6 +1430,99 @@ int myslam_tracker_clear_links_batch(myslam_tracker* h, const int64_t* d_kf_id, 
                                      int32_t* d_n_cleared);
 
 /* ------------------------------------------------------------------------------------------
+ * OBSERVATION ARCHIVE — MapPoint::GetObservations() (src/mappoint.cpp:19-44) of every map point that is alive and NOT in the active set, per stream,
+ * on the device.  The reference keeps that list in the MapPoint object for as long as the point lives; a point that Map::RemoveOldActiveMapPoints
+ * (src/map.cpp:126-140) took out of the active set and that a feature of a later key-frame names again comes back with it, and since its front
+ * observer is outside the window, src/backend.cpp:175-177 makes it a FIXED landmark.  The back end's tables hold a point's rows only while it is
+ * active and myslam_map holds no rows at all: this handle is the source of the prior rows of myslam_backend_insert_keyframe_batch (d_prior_*,
+ * d_n_prior).  The tracker keeps such a point by design (myslam_tracker_update_from_map_batch: absent ids keep their values) and the next turn names
+ * it in d_feat_mp_id.
+ * Order of one key-frame, all on one stream:  turn -> prior_rows -> insert (with those arrays) -> myslam_map_update_batch(AFTER_INSERT) ->
+ * update(AFTER_INSERT) -> optimise -> myslam_map_update_batch(AFTER_OPTIMIZE) -> update(AFTER_OPTIMIZE, the optimise's d_obs_report) -> ...
+ * CONTRACT, the map archive's: exactly one back-end call on an item lies between two updates of it, and the map's update of that call comes first.
+ *
+ * create: `map` is the map archive of the same streams (its tables are read through myslam_map_view; it must outlive this handle; max_batch at most
+ * its own; the back end's mp_cap is its backend_mp_cap), be_obs_cap the back end's obs_cap, row_cap the stored rows one item can hold.  The handle
+ * owns, per item: two POOLS of row_cap rows, one of which holds the segments; per map-point slot of `map` (offset, count); the MIRROR, two copies of
+ * be_obs_cap rows with the ids and segment starts of the table's map points; and the counters.  Nothing moves after create.
+ * A stored row is (observer's mnKFId i64, uv 2 x f32, tag i32, flags u8): uv and tag bit for bit what the back end's table held, flags only
+ * MYSLAM_BACKEND_OBS_OUTLIER as the table held it (ACTIVE is never stored), a point's rows in its GetObservations() order = the table's order
+ * within the segment.
+ *
+ * myslam_obs_archive_update_batch — device pointers, ONE launch (k_obs_update, one workgroup per item), after EACH myslam_map_update_batch.  It reads
+ * the back end's thirteen tables as they stand after the call in myslam_backend_optimize_batch's order (d_kf_pose, d_mp_pos and d_mp_outlier are not
+ * read and may be NULL) with that handle's three caps, d_backend_status = the back-end call's d_status, d_map_status = the map update's d_status, and
+ * after an optimise its d_obs_report (by INPUT row: the row of the table as it stood at the previous update).  Per item everything is decided
+ * before anything is written:
+ *   1. d_backend_status[b] != 0 or d_map_status[b] == MYSLAM_MAP_SKIPPED: MYSLAM_MAP_SKIPPED, every byte kept.
+ *   2. a point that was in the table at the previous update, is not in it now and has mp_state != 2 in the map LEAVES ALIVE: its rows are stored,
+ *      after an insert all the rows it had, after an optimise those whose d_obs_report is not 1.
+ *   3. a table row with d_obs_kf = -1 no longer says whose it is, and the compacted table no longer holds a leaving point's rows at all, so the
+ *      mirror holds every row of the table whole, with the observer's mnKFId, and follows the rows through both compactions: at an insert a point's
+ *      old rows stay in order at the front of its segment and the new key-frame's (the highest id's) rows follow; at an optimise the kept rows keep
+ *      their order.  A point NEW to the table has its prior rows first: the number of its leading rows that are not the new key-frame's must equal
+ *      the number of rows stored for it (0 for a point that is not stored or erased), and their ids come from the store.  If the number differs the
+ *      caller did not pass this handle's rows: MYSLAM_ERR_INVALID.
+ *   4. a point that is in the table now has no stored rows any more (it RETURNED); when it leaves again it is stored afresh.
+ *   5. a point erased while outside the table (Map::RemoveAllOutlierMapPoints empties the whole list, src/map.cpp:166-175) has dead rows: mp_state
+ *      is read at use, nothing runs at the erasure.
+ *   6. dead rows are reclaimed: segments are bump-allocated; when the rows in use plus the rows to store exceed row_cap, the live segments go to the
+ *      other pool in slot order first, in the same launch.  MYSLAM_ERR_CAPACITY comes when, and only when, the rows of the points alive and outside
+ *      the table exceed row_cap.
+ *   7. errors are STICKY: a map update that answered an error (the table moved on without this item), rule 3's mismatch, a table that does not
+ *      continue the mirror or a count out of range (MYSLAM_ERR_INVALID) and rule 6's MYSLAM_ERR_CAPACITY.  The item keeps every byte, and every
+ *      later update and prior_rows of it reports the same error (d_n_prior[b] = 0) until a load.
+ *   otherwise MYSLAM_MAP_UPDATED.
+ *
+ * myslam_obs_archive_prior_rows_batch — ONE launch (k_obs_prior_rows), before the insert: d_feat_mp_id / d_n_feat (batch x feat_cap) of the turn and
+ * the back end's d_mp_id / d_n_mp as they stand -> the insert's prior arrays (batch x prior_cap) and d_n_prior.  A row-set is written for every
+ * DISTINCT id >= 0 among the item's features that is not in the table and that the map holds with state 0 or 1 (a listed point is still alive) and
+ * that has stored rows; ids ascend and a point's rows are in stored order (what the insert demands of d_prior_mp_id).  Ids the map does not hold,
+ * erased ids and ids in the table give no rows.  More rows than prior_cap: MYSLAM_ERR_CAPACITY for that item and d_n_prior[b] = 0, nothing is
+ * truncated, not sticky; a count out of range: MYSLAM_ERR_INVALID, likewise.  Output slots from the count on keep their bytes.  d_status MYSLAM_OK else.
+ *
+ * myslam_obs_archive_load / _get — one item, host pointers, synchronous as myslam_map_load / _get (MYSLAM_ERR_UNSUPPORTED while the stream is
+ * recorded); both read the map's ids and states of the item.  load takes the live segments (ids strictly ascending, each held by the map with
+ * state 0 or 1 and not in the table, counts >= 1 summing to n_rows) with their rows, and the mirror: the ids of the back end's current table
+ * (strictly ascending), the rows of each, and for every row of that table the observer's mnKFId with uv, tag and flags; flags with a bit other than
+ * OUTLIER, or anything else above -> MYSLAM_ERR_INVALID, counts beyond the caps -> MYSLAM_ERR_CAPACITY, the item then keeps every byte.  It clears
+ * the sticky error and the reclaim count.  get: the live segments concatenated in ascending id order with per-point counts (dead rows are never
+ * visible; seg and row arrays sized row_cap), the mirror (sized mp_cap / obs_cap), the rows in use in the pool, the reclaims so far and the sticky
+ * error; any pointer may be NULL.
+ *
+ * Both batch calls allocate nothing, never synchronise, read no device memory from the host, use no global atomics and are recordable between
+ * myslam_graph_begin / _end; an item's bytes depend neither on its slot nor on its neighbours.  Call level, nothing enqueued: NULL required
+ * pointers, an unknown mode, d_obs_report missing AFTER_OPTIMIZE, caps that do not match the handle or the map -> MYSLAM_ERR_INVALID; a batch beyond
+ * the handle's -> MYSLAM_ERR_CAPACITY.
+ * OUT OF SCOPE, as above: LoopLocalFusion's re-linking (src/loopclosing.cpp:509-532), which appends a point's observations to a point that is
+ * usually not active; this store is where they would be appended.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct myslam_obs_archive myslam_obs_archive;
+int myslam_obs_archive_create(myslam_obs_archive** out, const myslam_map* map, int max_batch, int be_obs_cap, int row_cap);
+int myslam_obs_archive_destroy(myslam_obs_archive* h);
+int myslam_obs_archive_set_stream(myslam_obs_archive* h, void* hip_stream);
+int myslam_obs_archive_load(myslam_obs_archive* h, int item, const int64_t* seg_mp_id, const int32_t* seg_count, int n_seg, const int64_t* row_kf_id,
+                            const float* row_uv, const int32_t* row_tag, const uint8_t* row_flags, int n_rows, const int64_t* table_mp_id,
+                            const int32_t* table_mp_rows, int n_table_mp, const int64_t* table_kf_id, const float* table_uv, const int32_t* table_tag,
+                            const uint8_t* table_flags, int n_table_rows);
+int myslam_obs_archive_get(myslam_obs_archive* h, int item, int64_t* seg_mp_id, int32_t* seg_count, int* n_seg, int64_t* row_kf_id, float* row_uv,
+                           int32_t* row_tag, uint8_t* row_flags, int* n_rows, int64_t* table_mp_id, int32_t* table_mp_rows, int* n_table_mp,
+                           int64_t* table_kf_id, float* table_uv, int32_t* table_tag, uint8_t* table_flags, int* n_table_rows, int* rows_in_use,
+                           int* n_reclaims, int* error);
+/* src/map.cpp:126-140 and src/mappoint.cpp:19-56 as the stored lists see them, as described above */
+int myslam_obs_archive_update_batch(myslam_obs_archive* h, int mode, const int64_t* d_kf_id, const double* d_kf_pose, const int32_t* d_n_kf,
+                                    const int64_t* d_mp_id, const double* d_mp_pos, const uint8_t* d_mp_outlier, const int32_t* d_n_mp,
+                                    const int32_t* d_obs_mp, const int32_t* d_obs_kf, const uint8_t* d_obs_flags, const float* d_obs_uv,
+                                    const int32_t* d_obs_tag, const int32_t* d_n_obs, int be_kf_cap, int be_mp_cap, int be_obs_cap,
+                                    const int32_t* d_backend_status, const int32_t* d_map_status, const uint8_t* d_obs_report, int batch, int32_t* d_status);
+/* kernel launches one myslam_obs_archive_update_batch enqueues (1) */
+int myslam_obs_archive_launches_per_update(const myslam_obs_archive* h);
+/* GetObservations() of the returning map points (src/keyframe.cpp:39-47 finds them in the objects the features hold) */
+int myslam_obs_archive_prior_rows_batch(myslam_obs_archive* h, const int64_t* d_feat_mp_id, const int32_t* d_n_feat, int feat_cap, const int64_t* d_mp_id,
+                                        const int32_t* d_n_mp, int be_mp_cap, int batch, int64_t* d_prior_mp_id, int64_t* d_prior_kf_id, float* d_prior_uv,
+                                        int32_t* d_prior_tag, uint8_t* d_prior_flags, int32_t* d_n_prior, int prior_cap, int32_t* d_status);
+
+/* ------------------------------------------------------------------------------------------
  * Host-side formats of the reference's runner — plain host code, no device needed; the C++ forms live in
  * host/myslam_io.hpp and host/myslam_png.hpp.
  * ------------------------------------------------------------------------------------------ */
