@@ -913,6 +913,15 @@ class Tracker:
         _check(lib().myslam_tracker_clear_links_batch(self._h, C.c_void_p(d_kf_id or None), C.c_void_p(d_tag or None), C.c_void_p(d_n or None),
                                                       int(list_cap), C.c_void_p(d_n_cleared or None)), "myslam_tracker_clear_links_batch")
 
+    def relink_batch(self, d_kf_id, d_tag, d_slot, d_n, list_cap, map_archive, d_n_relinked=None, d_status=None):
+        """device pointers, asynchronous: Relink.view()'s link lists (stream s at + s * list_cap) against `map_archive` (item s = stream s).  Guard of
+        clear_links_batch; the landmark of every listed feature of the reference key-frame takes the target's id, position and outlier flag
+        (src/loopclosing.cpp:524, :529), a feature without one gets the slot that carries the id or a new one, slot -1 drops the landmark.
+        d_status `streams` i32 = 0 / ERR_INVALID / ERR_CAPACITY (the stream then keeps every byte); d_n_relinked `streams` i32 or None."""
+        vp = lambda p: C.c_void_p(p or None)
+        _check(lib().myslam_tracker_relink_batch(self._h, vp(d_kf_id), vp(d_tag), vp(d_slot), vp(d_n), int(list_cap), map_archive._h if map_archive else None,
+                                                 vp(d_n_relinked), vp(d_status)), "myslam_tracker_relink_batch")
+
     def set_image_batch(self, d_imgs, step, stride, d_select):
         """device pointers, asynchronous: the stored previous left image of every selected stream <- d_imgs[s], pyramid rebuilt"""
         _check(lib().myslam_tracker_set_image_batch(self._h, C.c_void_p(d_imgs), int(step), C.c_size_t(stride), C.c_void_p(d_select)),
@@ -1226,6 +1235,7 @@ class Backend:
 
 MAP_AFTER_INSERT, MAP_AFTER_OPTIMIZE = 0, 1            # MYSLAM_MAP_AFTER_*
 MAP_UPDATED, MAP_SKIPPED = 0, 1                        # MYSLAM_MAP_*
+MAP_AFTER_RELINK = 2                                   # MYSLAM_MAP_AFTER_RELINK
 
 
 class MapTables(C.Structure):                          # myslam_map_tables
@@ -1339,6 +1349,13 @@ class MapArchive:
         _check(lib().myslam_map_filter_landmarks_batch(self._h, C.c_void_p(d_feat_landmark or None), int(feat_cap), int(batch),
                                                        C.c_void_p(d_n_dropped or None)), "myslam_map_filter_landmarks_batch")
 
+    def relink_batch(self, d_merge, d_n_merge, merge_cap, d_plan_status, batch, d_status):
+        """Relink.view()'s merge list (stride merge_cap = its out_cap) and Relink.plan_batch's d_status: every merged point is erased (state 2,
+        src/loopclosing.cpp:527 with src/map.cpp:144-155); d_status batch i32 = MAP_UPDATED / MAP_SKIPPED / ERR_INVALID.  One launch, recordable."""
+        vp = lambda p: C.c_void_p(p or None)
+        _check(lib().myslam_map_relink_batch(self._h, vp(d_merge), vp(d_n_merge), int(merge_cap), vp(d_plan_status), int(batch), vp(d_status)),
+               "myslam_map_relink_batch")
+
 
 class ObsArchive:
     """MapPoint::GetObservations() of every map point of `max_batch` streams that is alive and not in the back end's table (myslam_obs_archive_*):
@@ -1418,6 +1435,96 @@ class ObsArchive:
                                                          vp(d_n_prior), int(prior_cap), vp(d_status)), "myslam_obs_archive_prior_rows_batch")
 
 
+RELINK_DONE, RELINK_SKIPPED, RELINK_REPORT_INTS = 0, 1, 6      # MYSLAM_RELINK_*
+
+
+class RelinkLists(C.Structure):                        # myslam_relink_lists
+    _fields_ = [(n, C.c_void_p) for n in ("merge", "n_merge", "adopt", "n_adopt", "target", "link_kf_id", "link_tag", "link_slot", "n_link", "report",
+                                          "row_kf_id", "row_uv", "row_tag", "row_flags", "row_root_id", "row_slot", "row_place", "n_rows",
+                                          "merge_from_id", "merge_root_id", "merge_rows", "merge_place", "n_staged_merges", "table_mp", "table_rows",
+                                          "work_size")] + \
+               [(n, C.c_int32) for n in ("max_batch", "out_cap", "feat_cap", "point_cap", "stage_cap")]
+
+
+class Relink:
+    """The plan of LoopLocalFusion's re-linking (src/loopclosing.cpp:509-532) for `max_batch` streams (myslam_relink_*): which point of the current
+    key-frame is merged into which point of the loop key-frame, which feature adopts, where every archive slot's features end.  `map_archive` is
+    the MapArchive of the same streams (kept alive by this object), `out_cap` the matcher's / verifier's cap, `feat_cap` the stride of the feature
+    tables.  After plan_batch: MapArchive.relink_batch(view().merge ...), LoopKeyFrameStore.set_links_batch / Tracker.relink_batch with
+    view().link_*.  Device pointers as ints; one launch per call."""
+
+    def __init__(self, map_archive, max_batch, out_cap, feat_cap, stage_cap, stream=None):
+        self.map, self.max_batch, self.out_cap, self.feat_cap, self.stage_cap = map_archive, int(max_batch), int(out_cap), int(feat_cap), int(stage_cap)
+        self._h = C.c_void_p()
+        _check(lib().myslam_relink_create(C.byref(self._h), map_archive._h, self.max_batch, self.out_cap, self.feat_cap, self.stage_cap),
+               "myslam_relink_create")
+        if stream is not None:
+            self.set_stream(stream)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and self._h.value and _lib is not None:
+            lib().myslam_relink_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def set_stream(self, stream):
+        _check(lib().myslam_relink_set_stream(self._h, C.c_void_p(stream)), "myslam_relink_set_stream")
+
+    def launches_per_plan(self):
+        return lib().myslam_relink_launches_per_plan(self._h)
+
+    def view(self):
+        """device pointers (ints, None never) and caps of the plan's outputs: merge / adopt (max_batch x out_cap x 2 i32) with n_merge / n_adopt,
+        target (max_batch x point_cap i32), link_kf_id / link_tag / link_slot (max_batch x feat_cap) with n_link, report (max_batch x 6 i32)"""
+        v = RelinkLists()
+        _check(lib().myslam_relink_view(self._h, C.byref(v)), "myslam_relink_view")
+        return v
+
+    def plan_batch(self, d_valid_pairs, d_counts, d_outlier, d_correct_status, d_cur_feat_landmark, d_loop_feat_landmark, d_cur_kf_id, batch, d_status):
+        """loop_match_batch's pairs and counts, verify_batch's outlier flags, LoopCorrector.correct_batch's status, the current key-frame's feature ->
+        slot table (batch x feat_cap i32, IN/OUT), the gathered loop table and the current mnKFId (batch i64) -> the handle's lists; d_status batch
+        i32 = RELINK_DONE / RELINK_SKIPPED / ERR_INVALID"""
+        vp = lambda p: C.c_void_p(p or None)
+        _check(lib().myslam_loop_relink_plan_batch(self._h, vp(d_valid_pairs), vp(d_counts), vp(d_outlier), vp(d_correct_status), vp(d_cur_feat_landmark),
+                                                   vp(d_loop_feat_landmark), vp(d_cur_kf_id), int(batch), vp(d_status)), "myslam_loop_relink_plan_batch")
+
+
+    # ---- the rows (src/loopclosing.cpp:521-527): stage -> back end -> MapArchive.relink_batch -> MapArchive.update_batch(MAP_AFTER_RELINK) -> obs update ----
+    def stage_batch(self, obs_archive, d_plan_status, batch, d_status):
+        """GetObservations() of every merged point, read from `obs_archive` (nothing of it changes), into view().row_* with the place of every row in the
+        list of the point it ends on; d_status batch i32 = RELINK_DONE / RELINK_SKIPPED / ERR_INVALID / ERR_CAPACITY (row_cap, the back end's obs_cap
+        or stage_cap) or the archive's sticky error.  view().row_kf_id / row_tag / row_slot with n_rows are the link list of the moved rows."""
+        vp = lambda p: C.c_void_p(p or None)
+        _check(lib().myslam_relink_stage_batch(obs_archive._h if obs_archive else None, self._h, vp(d_plan_status), int(batch), vp(d_status)),
+               "myslam_relink_stage_batch")
+
+    def backend_batch(self, backend, d_kf_id, d_kf_pose, d_n_kf, d_mp_id, d_mp_pos, d_mp_outlier, d_n_mp, d_obs_mp, d_obs_kf, d_obs_flags, d_obs_uv, d_obs_tag,
+                      d_n_obs, d_stage_status, batch, d_mp_new_row, d_status):
+        """the back end's thirteen tables, in/out: merged points leave with their rows, a target in the table gets the staged rows at the end of its
+        segment (ACTIVE 0); d_mp_new_row batch x mp_cap i32 by INPUT row; d_status batch i32 = 0, the stage's status when that is not 0,
+        ERR_INVALID or ERR_CAPACITY (obs_cap) with every byte kept.  It is the one back-end call before the next updates."""
+        vp = lambda p: C.c_void_p(p or None)
+        _check(lib().myslam_relink_backend_batch(backend._h if backend else None, self._h, vp(d_kf_id), vp(d_kf_pose), vp(d_n_kf), vp(d_mp_id), vp(d_mp_pos),
+                                                 vp(d_mp_outlier), vp(d_n_mp), vp(d_obs_mp), vp(d_obs_kf), vp(d_obs_flags), vp(d_obs_uv), vp(d_obs_tag), vp(d_n_obs),
+                                                 vp(d_stage_status), int(batch), vp(d_mp_new_row), vp(d_status)), "myslam_relink_backend_batch")
+
+    def obs_update_batch(self, obs_archive, d_kf_id, d_n_kf, d_mp_id, d_n_mp, d_obs_mp, d_obs_kf, d_obs_flags, d_obs_uv, d_obs_tag, d_n_obs, be_kf_cap, be_mp_cap,
+                         be_obs_cap, d_backend_status, d_map_status, batch, d_status):
+        """ObsArchive.update_batch's place after a re-link: the mirror follows the table, targets outside the table get the moved rows appended;
+        d_status batch i32 = MAP_UPDATED / MAP_SKIPPED or a negative, sticky error"""
+        vp = lambda p: C.c_void_p(p or None)
+        _check(lib().myslam_relink_obs_update_batch(obs_archive._h if obs_archive else None, self._h, vp(d_kf_id), vp(d_n_kf), vp(d_mp_id), vp(d_n_mp), vp(d_obs_mp),
+                                                    vp(d_obs_kf), vp(d_obs_flags), vp(d_obs_uv), vp(d_obs_tag), vp(d_n_obs), int(be_kf_cap), int(be_mp_cap),
+                                                    int(be_obs_cap), vp(d_backend_status), vp(d_map_status), int(batch), vp(d_status)),
+               "myslam_relink_obs_update_batch")
+
+    @staticmethod
+    def first_kf_batch(obs_archive, batch, d_first_kf):
+        """LoopCorrector.correct_batch's d_first_kf (batch x point_cap i32) in LIST order: the archive row of the front observer, -1 without a row or
+        for an erased point; what a stream that re-links passes instead of MapArchive.loop_inputs_batch's d_first_kf"""
+        _check(lib().myslam_relink_first_kf_batch(obs_archive._h if obs_archive else None, int(batch), C.c_void_p(d_first_kf or None)),
+               "myslam_relink_first_kf_batch")
+
+
 LOOP_DETECT_CANDIDATE, LOOP_DETECT_NO_LOOP = 0, 1      # MYSLAM_LOOP_DETECT_*
 
 
@@ -1470,6 +1577,14 @@ class LoopKeyFrameStore:
         vp = lambda p: C.c_void_p(p or None)
         _check(lib().myslam_loop_store_clear_links_batch(self._h, vp(d_kf_id), vp(d_tag), vp(d_n), int(list_cap), int(batch), vp(d_pending_kf_id),
                                                          vp(d_pending_feat_landmark), vp(d_n_cleared)), "myslam_loop_store_clear_links_batch")
+
+    def set_links_batch(self, d_kf_id, d_tag, d_slot, d_n, list_cap, batch, d_pending_kf_id=None, d_pending_feat_landmark=None, d_n_set=None):
+        """clear_links_batch with a value per entry: Relink.view()'s link lists (item b at + b * list_cap); the named feature of a key-frame held, or
+        of the pending key-frame, points at d_slot (>= -1) afterwards (src/loopclosing.cpp:524, :529).  d_n_set batch i32 or None.  One launch,
+        recordable."""
+        vp = lambda p: C.c_void_p(p or None)
+        _check(lib().myslam_loop_store_set_links_batch(self._h, vp(d_kf_id), vp(d_tag), vp(d_slot), vp(d_n), int(list_cap), int(batch),
+                                                       vp(d_pending_kf_id), vp(d_pending_feat_landmark), vp(d_n_set)), "myslam_loop_store_set_links_batch")
 
     def detect_batch(self, d_best_id, d_max_score, d_cnt, nq, d_loop_desc, d_n_loop, d_loop_pyr, d_loop_feat_landmark, d_loop_slot, d_status,
                      thr_high=0.94, max_suspected=3):

@@ -39,6 +39,7 @@ UNITS = {
     "loop_store.hip": [],                  # copies and two compares: nothing a contraction could change
     "map_archive.hip": EXACT,              # the odometry edge's measurement is the hosts' f64 arithmetic, operation by operation
     "obs_archive.hip": [],                 # integer code and copies
+    "relink.hip": [],                      # integer code and copies
     "prof.hip": [],
     "io.hip": [],
     "graph.hip": [],

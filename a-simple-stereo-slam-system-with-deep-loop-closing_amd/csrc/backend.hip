@@ -518,6 +518,101 @@ __global__ __launch_bounds__(BE_NT) void k_backend_insert(InsTables T, InsIn I, 
     }
 }
 
+// k_backend_relink: LoopLocalFusion's re-linking (src/loopclosing.cpp:521-527) on the tables, from the rows myslam_relink_stage_batch staged.  A merged
+// point leaves with all its rows (Map::RemoveMapPoint, src/map.cpp:144-155); a point the rows end on that is in the table gets them at the END of its
+// segment, each at the place the stage gave it, ACTIVE cleared (AddObservation alone runs), OUTLIER kept, its key-frame found by id.  The tables are
+// rebuilt from the handle's copy, as the insert does; everything is decided before anything is written.
+__global__ __launch_bounds__(BE_NT) void k_backend_relink(InsTables T, InsWork W, myslam_relink_lists R, const int32_t* stage_status, int32_t* mp_new_row,
+                                                          int32_t* status) {
+    __shared__ int s_w[BE_NW];
+    __shared__ int s_bad;
+    const int b = blockIdx.x, t = threadIdx.x;
+    const int nk = T.n_kf[b], nm = T.n_mp[b], no = T.n_obs[b];
+    int32_t* const new_row = mp_new_row + (size_t)b * T.mp_cap;
+    auto refuse = [&](int st) {                                             // the tables keep every byte
+        for (int m = t; m < clamped_count(nm, T.mp_cap); m += BE_NT) new_row[m] = -1;
+        if (t == 0) status[b] = st;
+    };
+    const int ss = stage_status[b];
+    if (ss != 0) { refuse(ss); return; }                                    // uniform: skipped, or the stage's refusal
+    const int nmg = R.n_staged_merges[b], nst = R.n_rows[b];
+    if (nk < 0 || nk > T.kf_cap || nm < 0 || nm > T.mp_cap || no < 0 || no > T.obs_cap || nmg < 0 || nmg > R.out_cap || nst < 0 || nst > R.stage_cap ||
+        R.table_mp[b] != nm || R.table_rows[b] != no) {                     // uniform: the rows were not staged for this table
+        refuse(MYSLAM_ERR_INVALID);
+        return;
+    }
+    const auto tb = T.item(b);
+    const auto w = W.item(b, T.mp_cap, T.obs_cap);
+    int32_t* const old_off = w.dmp; int32_t* const new_off = w.drows;      // mp_cap + 1 each
+    int32_t* const fin = w.mp_fin; int32_t* const add = w.mp_shift;        // final row of an input point (-1: it leaves); the rows it receives
+    const int64_t* const mg_from = R.merge_from_id + (size_t)b * R.out_cap;
+    const int64_t* const mg_root = R.merge_root_id + (size_t)b * R.out_cap;
+    const int32_t* const mg_rows = R.merge_rows + (size_t)b * R.out_cap;
+    const size_t sb = (size_t)b * R.stage_cap;
+    if (t == 0) s_bad = 0;
+    __syncthreads();
+    bool bad = be_tables_bad<true>(tb, nk, nm, no, w);
+    for (int m = t; m < nm; m += BE_NT) { fin[m] = 0; add[m] = 0; }
+    if (bad) s_bad = 1;
+    __syncthreads();
+    if (s_bad) { refuse(MYSLAM_ERR_INVALID); return; }
+    for (int r = t; r <= no; r += BE_NT) {                                  // where every segment starts (obs_mp is in range and non-decreasing)
+        const int prev = r ? w.obs_mp[r - 1] : -1, cur = r < no ? w.obs_mp[r] : nm;
+        for (int m = prev + 1; m <= cur; m++) old_off[m] = r;
+    }
+    __syncthreads();
+    if (t == 0)
+        for (int i = 0; i < nmg; i++) {
+            const int fr = find_row(w.mp_id, nm, mg_from[i]), rr = find_row(w.mp_id, nm, mg_root[i]);
+            if (fr >= 0) { fin[fr] = -1; if (old_off[fr + 1] - old_off[fr] != mg_rows[i]) s_bad = 1; }
+            if (rr >= 0) add[rr] += mg_rows[i];
+        }
+    __syncthreads();
+    int n_rows = 0, n_pts = 0;
+    for (int m0 = 0; m0 < nm; m0 += BE_NT) {                                // uniform: the new places, in the table's order
+        const int m = m0 + t;
+        const bool keep = m < nm && fin[m] == 0;
+        if (m < nm && !keep && add[m]) s_bad = 1;                           // rows never end on a point that was merged away
+        const int len = keep ? old_off[m + 1] - old_off[m] + add[m] : 0;
+        int tot, totp;
+        const int pos = n_rows + block_exsum<BE_NW>(len, s_w, tot);
+        const int row = n_pts + block_rank<BE_NW>(keep, s_w, totp);
+        if (m < nm) { new_off[m] = pos; fin[m] = keep ? row : -1; }
+        n_rows += tot; n_pts += totp;
+    }
+    for (int d = t; d < nst; d += BE_NT) {                                  // a staged row stands behind the rows its point had, within what it receives
+        const int rr = find_row(w.mp_id, nm, R.row_root_id[sb + d]);
+        if (rr < 0) continue;
+        const int place = R.row_place[sb + d], len = old_off[rr + 1] - old_off[rr];
+        if (place < len || place >= len + add[rr] || (R.row_flags[sb + d] & ~BE_OUTLIER)) s_bad = 1;
+    }
+    __syncthreads();
+    if (s_bad || n_rows > T.obs_cap) { refuse(s_bad ? MYSLAM_ERR_INVALID : MYSLAM_ERR_CAPACITY); return; }      // uniform
+    // ---- from here on the item is written ----
+    for (int r = t; r < no; r += BE_NT) {
+        const int m = w.obs_mp[r];
+        if (fin[m] < 0) continue;
+        const int q = new_off[m] + (r - old_off[m]);
+        tb.obs_mp[q] = fin[m]; tb.obs_kf[q] = w.obs_kf[r]; tb.obs_flags[q] = w.obs_flags[r];
+        tb.obs_uv[2 * q] = w.obs_uv[2 * r]; tb.obs_uv[2 * q + 1] = w.obs_uv[2 * r + 1]; tb.obs_tag[q] = w.obs_tag[r];
+    }
+    for (int d = t; d < nst; d += BE_NT) {
+        const int rr = find_row(w.mp_id, nm, R.row_root_id[sb + d]);
+        if (rr < 0) continue;
+        const int q = new_off[rr] + R.row_place[sb + d];
+        tb.obs_mp[q] = fin[rr]; tb.obs_kf[q] = find_row(tb.kf_id, nk, R.row_kf_id[sb + d]); tb.obs_flags[q] = R.row_flags[sb + d] & BE_OUTLIER;
+        tb.obs_uv[2 * q] = R.row_uv[2 * (sb + d)]; tb.obs_uv[2 * q + 1] = R.row_uv[2 * (sb + d) + 1]; tb.obs_tag[q] = R.row_tag[sb + d];
+    }
+    for (int m = t; m < nm; m += BE_NT) {
+        const int q = fin[m];
+        new_row[m] = q;
+        if (q < 0) continue;
+        tb.mp_id[q] = w.mp_id[m]; tb.mp_outlier[q] = w.mp_outlier[m];
+        tb.mp_pos[3 * q] = w.mp_pos[3 * m]; tb.mp_pos[3 * q + 1] = w.mp_pos[3 * m + 1]; tb.mp_pos[3 * q + 2] = w.mp_pos[3 * m + 2];
+    }
+    if (t == 0) { T.n_mp[b] = n_pts; T.n_obs[b] = n_rows; status[b] = MYSLAM_OK; }
+}
+
 }  // namespace myslam_hip
 
 using namespace myslam_hip;
@@ -705,6 +800,24 @@ int myslam_backend_debug_solved(myslam_backend* h, int item, double* poses, doub
         if (E && ((rc = be_fetch(rounds_outliers2, w.rounds + b, sizeof(int32_t))) || (rc = be_fetch(rounds_outliers2 + 1, w.nout + b, sizeof(int32_t)))))
             return rc;
     }
+    return MYSLAM_OK;
+}
+
+int myslam_relink_backend_batch(myslam_backend* h, const myslam_relink* rl, int64_t* d_kf_id, double* d_kf_pose, int32_t* d_n_kf, int64_t* d_mp_id,
+                                double* d_mp_pos, uint8_t* d_mp_outlier, int32_t* d_n_mp, int32_t* d_obs_mp, int32_t* d_obs_kf, uint8_t* d_obs_flags,
+                                float* d_obs_uv, int32_t* d_obs_tag, int32_t* d_n_obs, const int32_t* d_stage_status, int batch, int32_t* d_mp_new_row,
+                                int32_t* d_status) {
+    if (!h || !rl || batch < 0 || !d_kf_id || !d_kf_pose || !d_n_kf || !d_mp_id || !d_mp_pos || !d_mp_outlier || !d_n_mp || !d_obs_mp || !d_obs_kf ||
+        !d_obs_flags || !d_obs_uv || !d_obs_tag || !d_n_obs || !d_stage_status || !d_mp_new_row || !d_status)
+        return MYSLAM_ERR_INVALID;
+    myslam_relink_lists v;
+    if (myslam_relink_view(rl, &v) != MYSLAM_OK) return MYSLAM_ERR_INVALID;
+    if (batch > h->max_batch || batch > v.max_batch) return MYSLAM_ERR_CAPACITY;
+    if (batch == 0) return MYSLAM_OK;
+    const InsTables T{d_kf_id, d_kf_pose, d_n_kf, d_mp_id, d_mp_pos, d_mp_outlier, d_n_mp, d_obs_mp, d_obs_kf, d_obs_flags, d_obs_uv, d_obs_tag, d_n_obs,
+                      h->kf_cap, h->mp_cap, h->obs_cap};
+    hipLaunchKernelGGL(k_backend_relink, dim3(batch), dim3(BE_NT), 0, h->stream, T, h->iw, v, d_stage_status, d_mp_new_row, d_status);
+    MYSLAM_HIP_CHECK(hipGetLastError());
     return MYSLAM_OK;
 }
 

@@ -7,7 +7,8 @@
 // launch stays valid; ids, row counts, feature counts and the number of key-frames held are read ON THE DEVICE, so a replay sees what was put after
 // the recording.  Slot strides are rounded up to 4 key-points / 4 landmark entries: every slot starts on a 16-byte boundary.
 //
-// k_loop_store_clear_links (one workgroup per item) sets single entries of stored landmark tables to -1: the features the optimiser reset.
+// k_loop_store_clear_links (one workgroup per item) sets single entries of stored landmark tables to -1: the features the optimiser reset; with
+// a value column (set_links) to the slot a re-linked feature points at.
 // The other kernels are copies and nothing else: a 2-D grid (chunk x item), every workgroup repeats its item's decision (two compares and a binary search
 // over the ids, all wave-uniform) and then moves its share of the item's three arrays, 16 bytes per lane where source and destination of the item are
 // 16-byte aligned (a key-point is 28 bytes: item b of a caller's table starts aligned only when b * cap is a multiple of 4), a dword per lane
@@ -130,9 +131,13 @@ __global__ void __launch_bounds__(LS_THREADS) k_loop_detect(const LsStore st, co
 // clear_links: one workgroup per item.  Entry j of item b's list names a feature (key-frame id, feature index) whose mpMapPoint the optimiser
 // reset (src/backend.cpp:236-247); its link becomes -1 in the pending table (a key-frame that is not put yet) or in the slot that holds the id.
 // The number of key-frames held is read here, as k_loop_detect reads it.  Two entries that name one feature store the same -1.
+// set_links is the same walk with a value per entry (`value`, nullptr = -1 for all): the slot a re-linked feature points at afterwards
+// (src/loopclosing.cpp:521-530); an entry whose value is below -1 is ignored.  Two entries that name one feature with different values have no
+// order: the re-link's lists name a feature once.
 struct LsClear {
     const int64_t* kf_id; const int32_t* tag; const int32_t* n; int list_cap;
     const int64_t* pending_kf_id; int32_t* pending_lm; int32_t* n_cleared;
+    const int32_t* value;
 };
 __global__ void __launch_bounds__(LS_THREADS) k_loop_store_clear_links(const LsStore st, const LsClear c) {
     __shared__ int s_w[LS_THREADS / WAVE];
@@ -140,6 +145,7 @@ __global__ void __launch_bounds__(LS_THREADS) k_loop_store_clear_links(const LsS
     const int n = ls_clamp(c.n[b], c.list_cap), held = *st.size;
     const int64_t* const ids = c.kf_id + (size_t)b * c.list_cap;
     const int32_t* const tags = c.tag + (size_t)b * c.list_cap;
+    const int32_t* const values = c.value ? c.value + (size_t)b * c.list_cap : nullptr;
     const bool pending = c.pending_kf_id != nullptr;
     const int64_t pend_id = pending ? c.pending_kf_id[b] : -1;
     int cleared = 0;
@@ -149,15 +155,16 @@ __global__ void __launch_bounds__(LS_THREADS) k_loop_store_clear_links(const LsS
         if (j < n) {
             const int64_t id = ids[j];
             const int tag = tags[j];
-            if (id >= 0 && tag >= 0) {
+            const int v = values ? values[j] : -1;
+            if (id >= 0 && tag >= 0 && v >= -1) {
                 if (pending && id == pend_id && tag < st.feat_cap) {
-                    c.pending_lm[(size_t)b * st.feat_cap + tag] = -1;
+                    c.pending_lm[(size_t)b * st.feat_cap + tag] = v;
                     hit = true;
                 } else {
                     // a key-frame that closed a loop, and the five after it, are not held (:671-681)
                     const int slot = lower_row(st.ids, held, (uint64_t)id);
                     if (slot < held && st.ids[slot] == (uint64_t)id && tag < st.nfeat[slot]) {
-                        st.lm[(size_t)slot * st.feat_st + tag] = -1;
+                        st.lm[(size_t)slot * st.feat_st + tag] = v;
                         hit = true;
                     }
                 }
@@ -308,7 +315,19 @@ int myslam_loop_store_clear_links_batch(myslam_loop_store* h, const int64_t* d_k
     if (batch > LS_MAX_GRID_Y) return MYSLAM_ERR_CAPACITY;
     std::lock_guard<std::mutex> lk(h->mu);
     // no host bookkeeping: the ids and their number are read on the device, so the launch may be recorded
-    const LsClear c{d_kf_id, d_tag, d_n, list_cap, d_pending_kf_id, d_pending_feat_landmark, d_n_cleared};
+    const LsClear c{d_kf_id, d_tag, d_n, list_cap, d_pending_kf_id, d_pending_feat_landmark, d_n_cleared, nullptr};
+    hipLaunchKernelGGL(k_loop_store_clear_links, dim3(batch), dim3(LS_THREADS), 0, h->stream, h->view, c);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    return MYSLAM_OK;
+}
+
+int myslam_loop_store_set_links_batch(myslam_loop_store* h, const int64_t* d_kf_id, const int32_t* d_tag, const int32_t* d_slot, const int32_t* d_n,
+                                      int list_cap, int batch, const int64_t* d_pending_kf_id, int32_t* d_pending_feat_landmark, int32_t* d_n_set) {
+    if (!h || !d_kf_id || !d_tag || !d_slot || !d_n || list_cap <= 0 || batch <= 0 || (d_pending_kf_id == nullptr) != (d_pending_feat_landmark == nullptr))
+        return MYSLAM_ERR_INVALID;
+    if (batch > LS_MAX_GRID_Y) return MYSLAM_ERR_CAPACITY;
+    std::lock_guard<std::mutex> lk(h->mu);
+    const LsClear c{d_kf_id, d_tag, d_n, list_cap, d_pending_kf_id, d_pending_feat_landmark, d_n_set, d_slot};
     hipLaunchKernelGGL(k_loop_store_clear_links, dim3(batch), dim3(LS_THREADS), 0, h->stream, h->view, c);
     MYSLAM_HIP_CHECK(hipGetLastError());
     return MYSLAM_OK;

@@ -6,7 +6,8 @@
 //   k_map_loop_inputs    the per-loop index inputs of myslam_loop_correct_batch;
 //   k_map_write_backend  the corrected poses and positions back into the back end's rows;
 //   k_map_feature_slots  map-point id -> archive slot per feature (myslam_loop_store_put_batch's d_feat_landmark);
-//   k_map_filter_landmarks  the links of a gathered table to points erased since (one workgroup per item, a block scan for its count).
+//   k_map_filter_landmarks  the links of a gathered table to points erased since (one workgroup per item, a block scan for its count);
+//   k_map_relink         the points a re-link plan merged away are erased (state 2), one workgroup per item.
 // Ids ascend in every table, so a row is found by binary search (sorted_rows.h) and a new row's slot is a closed form: no scans, no atomics; an item's bytes depend
 // neither on its slot nor on its neighbours.  The edge measurement uses se3_chain.h (chain.py's arithmetic, built with -ffp-contract=off).
 // See include/myslam_hip.h for the contract.
@@ -282,6 +283,37 @@ __global__ __launch_bounds__(MA_NT) void k_map_filter_landmarks(MaTables A, int3
     if (t == 0 && n_dropped) n_dropped[b] = dropped;
 }
 
+// One workgroup per item: Map::RemoveMapPoint (src/map.cpp:144-155) for every point the re-link plan merged away (src/loopclosing.cpp:526).  The
+// list is validated whole before the first state is written; targets keep their state, no position is touched.
+__global__ __launch_bounds__(MA_NT) void k_map_relink(MaTables A, const int32_t* merge, const int32_t* n_merge, int merge_cap, const int32_t* plan_status,
+                                                      int32_t* status) {
+    __shared__ int s_bad;
+    const int b = blockIdx.x, t = threadIdx.x;
+    if (plan_status[b] != MYSLAM_RELINK_DONE) {                             // uniform: skipped or refused, nothing was merged
+        if (t == 0) status[b] = MYSLAM_MAP_SKIPPED;
+        return;
+    }
+    const int n = n_merge[b], aM = A.n_mp[b];
+    const int32_t* const list = merge + (size_t)b * merge_cap * 2;
+    uint8_t* const state = A.mp_state + (size_t)b * A.point_cap;
+    if (t == 0) s_bad = 0;
+    __syncthreads();
+    bool bad = n < 0 || n > merge_cap || aM < 0 || aM > A.point_cap;
+    if (!bad)
+        for (int i = t; i < n; i += MA_NT) {
+            const int from = list[2 * i], to = list[2 * i + 1];
+            bad |= from < 0 || from >= aM || to < 0 || to >= aM || from == to;
+        }
+    if (bad) s_bad = 1;
+    __syncthreads();
+    if (s_bad) {                                                            // uniform; every byte kept
+        if (t == 0) status[b] = MYSLAM_ERR_INVALID;
+        return;
+    }
+    for (int i = t; i < n; i += MA_NT) state[list[2 * i]] = 2;
+    if (t == 0) status[b] = MYSLAM_MAP_UPDATED;
+}
+
 }  // namespace myslam_hip
 
 using namespace myslam_hip;
@@ -441,7 +473,10 @@ int myslam_map_update_batch(myslam_map* h, int mode, const int64_t* d_kf_id, con
                             const int32_t* d_obs_kf, const uint8_t* d_obs_flags, const int32_t* d_n_obs, int be_obs_cap, const int32_t* d_backend_status,
                             const int64_t* d_outlier_mp_id, const int32_t* d_n_outlier_mp, int outlier_cap, const uint8_t* d_mp_report, int batch,
                             int32_t* d_status) {
-    if (!h || batch < 0 || (mode != MYSLAM_MAP_AFTER_INSERT && mode != MYSLAM_MAP_AFTER_OPTIMIZE)) return MYSLAM_ERR_INVALID;
+    if (!h || batch < 0 || (mode != MYSLAM_MAP_AFTER_INSERT && mode != MYSLAM_MAP_AFTER_OPTIMIZE && mode != MYSLAM_MAP_AFTER_RELINK)) return MYSLAM_ERR_INVALID;
+    if (mode == MYSLAM_MAP_AFTER_RELINK) {      // the re-link neither makes a key-frame nor a point: an insert's update without an outlier list
+        mode = MYSLAM_MAP_AFTER_INSERT; d_n_outlier_mp = nullptr;
+    }
     if (!d_kf_id || !d_kf_pose || !d_n_kf || !d_mp_id || !d_mp_pos || !d_n_mp || !d_obs_mp || !d_obs_kf || !d_obs_flags || !d_n_obs || !d_backend_status ||
         !d_status || be_obs_cap < 1 || ma_backend_args_bad(h, be_kf_cap, be_mp_cap))
         return MYSLAM_ERR_INVALID;
@@ -508,6 +543,16 @@ int myslam_map_filter_landmarks_batch(myslam_map* h, int32_t* d_feat_landmark, i
     if (batch > h->max_batch) return MYSLAM_ERR_CAPACITY;
     if (batch == 0) return MYSLAM_OK;
     hipLaunchKernelGGL(k_map_filter_landmarks, dim3(batch), dim3(MA_NT), 0, h->stream, h->t, d_feat_landmark, feat_cap, d_n_dropped);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    return MYSLAM_OK;
+}
+
+int myslam_map_relink_batch(myslam_map* h, const int32_t* d_merge, const int32_t* d_n_merge, int merge_cap, const int32_t* d_plan_status, int batch,
+                            int32_t* d_status) {
+    if (!h || batch < 0 || !d_merge || !d_n_merge || !d_plan_status || !d_status || merge_cap < 1) return MYSLAM_ERR_INVALID;
+    if (batch > h->max_batch) return MYSLAM_ERR_CAPACITY;
+    if (batch == 0) return MYSLAM_OK;
+    hipLaunchKernelGGL(k_map_relink, dim3(batch), dim3(MA_NT), 0, h->stream, h->t, d_merge, d_n_merge, merge_cap, d_plan_status, d_status);
     MYSLAM_HIP_CHECK(hipGetLastError());
     return MYSLAM_OK;
 }

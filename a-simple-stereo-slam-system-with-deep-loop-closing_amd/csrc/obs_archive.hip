@@ -307,6 +307,311 @@ __global__ __launch_bounds__(OA_NT) void k_obs_prior_rows(OaTables A, OaPriorIn 
     }
 }
 
+// ---- RE-LINK (include/myslam_hip.h): LoopLocalFusion's moved rows (reference src/loopclosing.cpp:521-525) as far as this handle holds them ----
+// k_relink_stage       reads the archive (nothing of it is written): GetObservations() of every merged point — the mirror's rows for a point of the
+//                      table, the stored segment else — goes to the plan handle's staging with the place each row takes in the list of the point it
+//                      ends on.  The final list of a point that stands is its own rows, then for every merge into it, in order, the whole list the
+//                      merged point had by then; so a merged point's OWN rows stand at one place, which one lane finds with two passes over the merge
+//                      list (sizes forwards, places backwards).  Both capacities (row_cap, the back end's obs_cap) are decided here.
+// k_relink_obs_update  after the back end's tables and the map's states moved: the mirror follows the table (appended rows take their observer's id
+//                      from the staging), a target outside the table has its list written afresh (stored rows, then the moved ones) by update rule 6.
+// k_relink_first_kf    the front observer of every point in LIST order.
+struct OaSeg { int p, n; };             // row of a point in the recorded table (-1: outside) and the rows of its list, n < 0: inconsistent
+
+__device__ __forceinline__ OaSeg oa_own(const OaTables& A, int b, int mc, int pn, int pno, int s) {
+    const int64_t* const pid = A.t_mp_id[mc] + (size_t)b * A.be_mp_cap;
+    const int32_t* const po = A.t_off[mc] + (size_t)b * (A.be_mp_cap + 1);
+    const int p = find_row(pid, pn, A.map_mp_id[(size_t)b * A.point_cap + s]);
+    if (p >= 0) {
+        const int o0 = po[p], o1 = po[p + 1];
+        return {p, (o0 >= 0 && o0 <= o1 && o1 <= pno) ? o1 - o0 : -1};
+    }
+    const int c = A.seg_cnt[(size_t)b * A.point_cap + s], o = A.seg_off[(size_t)b * A.point_cap + s];
+    return {-1, (c < 0 || (c > 0 && (o < 0 || o > A.row_cap - c))) ? -1 : c};
+}
+
+__global__ __launch_bounds__(OA_NT) void k_relink_stage(OaTables A, myslam_relink_lists R, const int32_t* plan_status, int32_t* status) {
+    __shared__ int s_bad, s_live, s_code, s_total;
+    const int b = blockIdx.x, t = threadIdx.x;
+    const auto none = [&](int code) { if (t == 0) { R.n_rows[b] = 0; R.n_staged_merges[b] = 0; status[b] = code; } };
+    const int err = A.err[b];
+    if (err) { none(err); return; }
+    if (plan_status[b] != MYSLAM_RELINK_DONE) { none(MYSLAM_RELINK_SKIPPED); return; }
+    const int nmg = R.n_merge[b], aM = A.map_n_mp[b];
+    const int mc = A.mcur[b] & 1, pc = A.pcur[b] & 1;
+    const int pn = A.t_n_mp[mc][b];
+    const int32_t* const po = A.t_off[mc] + (size_t)b * (A.be_mp_cap + 1);
+    const int pno = (pn >= 0 && pn <= A.be_mp_cap) ? po[pn] : -1;
+    if (nmg < 0 || nmg > R.out_cap || aM < 0 || aM > A.point_cap || pno < 0 || pno > A.be_obs_cap) { none(MYSLAM_ERR_INVALID); return; }      // uniform
+    const int32_t* const merge = R.merge + (size_t)b * R.out_cap * 2;
+    const int32_t* const target = R.target + (size_t)b * R.point_cap;
+    const int64_t* const map_id = A.map_mp_id + (size_t)b * A.point_cap;
+    const uint8_t* const state = A.map_state + (size_t)b * A.point_cap;
+    const int32_t* const seg_off = A.seg_off + (size_t)b * A.point_cap;
+    const int32_t* const seg_cnt = A.seg_cnt + (size_t)b * A.point_cap;
+    const int64_t* const pid = A.t_mp_id[mc] + (size_t)b * A.be_mp_cap;
+    int32_t* const wsz = R.work_size + (size_t)b * R.point_cap;
+    int64_t* const mg_from = R.merge_from_id + (size_t)b * R.out_cap;
+    int64_t* const mg_root = R.merge_root_id + (size_t)b * R.out_cap;
+    int32_t* const mg_rows = R.merge_rows + (size_t)b * R.out_cap;
+    int32_t* const mg_place = R.merge_place + (size_t)b * R.out_cap;
+    if (t == 0) { s_bad = 0; s_live = 0; s_code = 0; s_total = 0; }
+    __syncthreads();
+    bool bad = false;
+    for (int i = t; i < nmg; i += OA_NT) {                                  // every slot in range and alive, every merged point's end a point that stands
+        const int x = merge[2 * i], y = merge[2 * i + 1];
+        if (x < 0 || x >= aM || y < 0 || y >= aM || x == y || state[x] == 2 || state[y] == 2) { bad = true; continue; }
+        const int r = target[x];
+        if (r < 0 || r >= aM || target[r] != r || state[r] == 2) { bad = true; continue; }
+        const OaSeg ox = oa_own(A, b, mc, pn, pno, x), oy = oa_own(A, b, mc, pn, pno, y);
+        if (ox.n < 0 || oy.n < 0) { bad = true; continue; }
+        wsz[x] = ox.n; wsz[y] = oy.n;                                       // (whoever writes a slot writes the same number)
+        mg_from[i] = map_id[x]; mg_root[i] = map_id[r]; mg_rows[i] = ox.n;
+    }
+    int live = 0;
+    for (int s = t; s < aM; s += OA_NT) {
+        const int c = seg_cnt[s];
+        if (c <= 0 || state[s] == 2) continue;
+        if (seg_off[s] < 0 || seg_off[s] > A.row_cap - c) { bad = true; continue; }
+        live += c;
+    }
+    if (bad) s_bad = 1;
+    if (live) atomicAdd(&s_live, live);                                     // LDS
+    __syncthreads();
+    if (s_bad) { none(MYSLAM_ERR_INVALID); return; }                        // uniform
+    if (t == 0) {
+        for (int i = 0; i < nmg; i++) {                                     // sizes forwards: where the merged point's list starts in its target's
+            const int x = merge[2 * i], y = merge[2 * i + 1];
+            mg_place[i] = wsz[y]; wsz[y] += wsz[x];
+        }
+        long long n_table = pno, out_rows = s_live, total = 0;
+        for (int i = nmg - 1; i >= 0; i--) {                                // places backwards: a target that was merged later has its own place by now
+            const int x = merge[2 * i], y = merge[2 * i + 1];
+            const int place = mg_place[i] + (target[y] == y ? 0 : wsz[y]);
+            wsz[x] = place; mg_place[i] = place;
+            const int c = mg_rows[i];
+            const bool from_in = find_row(pid, pn, mg_from[i]) >= 0, root_in = find_row(pid, pn, mg_root[i]) >= 0;
+            n_table += (root_in ? c : 0) - (from_in ? c : 0);
+            out_rows += (root_in ? 0 : c) - (from_in ? 0 : c);
+            total += c;
+        }
+        if (total > R.stage_cap || n_table > A.be_obs_cap || out_rows > A.row_cap) s_code = MYSLAM_ERR_CAPACITY;
+        s_total = (int)(total > R.stage_cap ? 0 : total);
+    }
+    __syncthreads();
+    if (s_code) { none(s_code); return; }                                   // uniform; nothing of any table was written
+    const OaRows mir = A.mir[mc].at((size_t)b * A.be_obs_cap), pool = A.pool[pc].at((size_t)b * A.row_cap);
+    const OaRows dst{R.row_kf_id + (size_t)b * R.stage_cap, R.row_uv + (size_t)b * R.stage_cap * 2, R.row_tag + (size_t)b * R.stage_cap,
+                     R.row_flags + (size_t)b * R.stage_cap};
+    int base = 0;
+    for (int i = 0; i < nmg; i++) {                                         // uniform: the own rows of every merged point, merge by merge
+        const int x = merge[2 * i], c = mg_rows[i];
+        const int p = find_row(pid, pn, mg_from[i]);
+        const int src0 = p >= 0 ? po[p] : seg_off[x];
+        for (int j = t; j < c; j += OA_NT) {
+            const size_t d = (size_t)base + j;
+            dst.copy_from((int)d, p >= 0 ? mir : pool, src0 + j);
+            R.row_root_id[(size_t)b * R.stage_cap + d] = mg_root[i]; R.row_slot[(size_t)b * R.stage_cap + d] = target[x];
+            R.row_place[(size_t)b * R.stage_cap + d] = mg_place[i] + j;
+        }
+        base += c;
+    }
+    if (t == 0) { R.n_rows[b] = s_total; R.n_staged_merges[b] = nmg; R.table_mp[b] = pn; R.table_rows[b] = pno; status[b] = MYSLAM_RELINK_DONE; }
+}
+
+__global__ __launch_bounds__(OA_NT) void k_relink_obs_update(OaTables A, BeTablesRead B, myslam_relink_lists R, const int32_t* be_status, const int32_t* map_status,
+                                                             int32_t* status) {
+    __shared__ int s_w[OA_NW];
+    __shared__ int s_bad, s_keep, s_new, s_lo, s_hi;
+    const int b = blockIdx.x, t = threadIdx.x;
+    const int err = A.err[b];
+    if (err) { if (t == 0) status[b] = err; return; }
+    const int ms = map_status[b];
+    if (be_status[b] != 0 || ms == MYSLAM_MAP_SKIPPED) { if (t == 0) status[b] = MYSLAM_MAP_SKIPPED; return; }
+    const int nk = B.n_kf[b], nm = B.n_mp[b], no = B.n_obs[b], aM = A.map_n_mp[b];
+    const int mc = A.mcur[b] & 1, pc = A.pcur[b] & 1, used = A.used[b];
+    const int pn = A.t_n_mp[mc][b];
+    const int32_t* const po = A.t_off[mc] + (size_t)b * (A.be_mp_cap + 1);
+    const int pno = (pn >= 0 && pn <= A.be_mp_cap) ? po[pn] : -1;
+    const int nmg = R.n_staged_merges[b], nst = R.n_rows[b];
+    if (ms != MYSLAM_MAP_UPDATED || nk < 1 || nk > B.kf_cap || nm < 0 || nm > B.mp_cap || no < 0 || no > B.obs_cap || aM < 0 || aM > A.point_cap || pno < 0 ||
+        pno > A.be_obs_cap || used < 0 || used > A.row_cap || nmg < 0 || nmg > R.out_cap || nst < 0 || nst > R.stage_cap || R.table_mp[b] != pn ||
+        R.table_rows[b] != pno) {                                           // uniform: the staging is not of this mirror
+        if (t == 0) { A.err[b] = MYSLAM_ERR_INVALID; status[b] = MYSLAM_ERR_INVALID; }                          // sticky, every byte kept
+        return;
+    }
+    const auto be = B.item(b);
+    const int64_t* const map_id = A.map_mp_id + (size_t)b * A.point_cap;
+    const uint8_t* const state = A.map_state + (size_t)b * A.point_cap;
+    int32_t* const seg_off = A.seg_off + (size_t)b * A.point_cap;
+    int32_t* const seg_cnt = A.seg_cnt + (size_t)b * A.point_cap;
+    uint8_t* const named = A.named + (size_t)b * A.point_cap;
+    const int64_t* const pid = A.t_mp_id[mc] + (size_t)b * A.be_mp_cap;
+    const OaRows old_mir = A.mir[mc].at((size_t)b * A.be_obs_cap), new_mir = A.mir[mc ^ 1].at((size_t)b * A.be_obs_cap);
+    const OaRows old_pool = A.pool[pc].at((size_t)b * A.row_cap);
+    int64_t* const nid = A.t_mp_id[mc ^ 1] + (size_t)b * A.be_mp_cap;
+    int32_t* const noff = A.t_off[mc ^ 1] + (size_t)b * (A.be_mp_cap + 1);
+    int32_t* const w_p = A.w_p + (size_t)b * A.be_mp_cap;                   // per table point: its row in the recorded table, the rows it received
+    int32_t* const w_add = A.w_lk + (size_t)b * A.be_mp_cap;
+    int32_t* const wsz = R.work_size + (size_t)b * R.point_cap;             // per target outside the table: the rows it receives
+    const int32_t* const merge = R.merge + (size_t)b * R.out_cap * 2;
+    const int32_t* const target = R.target + (size_t)b * R.point_cap;
+    const int64_t* const mg_root = R.merge_root_id + (size_t)b * R.out_cap;
+    const int32_t* const mg_rows = R.merge_rows + (size_t)b * R.out_cap;
+    const size_t sb = (size_t)b * R.stage_cap;
+    if (t == 0) { s_bad = 0; s_keep = 0; s_new = 0; s_lo = aM; s_hi = -1; }
+    __syncthreads();
+    bool bad = false;
+    for (int r = t; r <= no; r += OA_NT) {                                  // segment starts, as k_obs_update
+        const int prev = r ? be.obs_mp[r - 1] : -1, cur = r < no ? be.obs_mp[r] : nm;
+        if (prev < -1 || cur < prev || cur > nm || (r < no && cur == nm)) { bad = true; continue; }
+        for (int m = prev + 1; m <= cur; m++) noff[m] = r;
+    }
+    for (int m = t; m < nm; m += OA_NT) w_add[m] = 0;
+    for (int i = t; i < nmg; i += OA_NT) {                                  // the slots the merged rows end on
+        const int x = merge[2 * i];
+        const int r = (x >= 0 && x < aM) ? target[x] : -1;
+        if (r < 0 || r >= aM || state[r] == 2) { bad = true; continue; }
+        wsz[r] = 0;
+    }
+    if (bad) s_bad = 1;
+    __syncthreads();
+    if (s_bad) {                                                            // uniform
+        if (t == 0) { A.err[b] = MYSLAM_ERR_INVALID; status[b] = MYSLAM_ERR_INVALID; }
+        return;
+    }
+    if (t == 0)
+        for (int i = 0; i < nmg; i++) {                                     // rows received, by table row or by slot
+            const int rr = find_row(be.mp_id, nm, mg_root[i]);
+            if (rr >= 0) w_add[rr] += mg_rows[i]; else wsz[target[merge[2 * i]]] += mg_rows[i];
+        }
+    __syncthreads();
+    // ---- decide ----
+    for (int m = t; m < nm; m += OA_NT) {                                   // every point of the table was in it, and holds what it held plus what it received
+        const int p = find_row(pid, pn, be.mp_id[m]);
+        w_p[m] = p;
+        if (p < 0 || find_row(map_id, aM, be.mp_id[m]) < 0) { bad = true; continue; }
+        const int o0 = po[p], o1 = po[p + 1];
+        bad |= !(o0 >= 0 && o0 <= o1 && o1 <= pno) || noff[m + 1] - noff[m] != o1 - o0 + w_add[m];
+    }
+    for (int p = t; p < pn; p += OA_NT)                                     // a recorded point that is gone was merged away: erased by now
+        if (find_row(be.mp_id, nm, pid[p]) < 0) { const int s = find_row(map_id, aM, pid[p]); bad |= s < 0 || state[s] != 2; }
+    for (int i = t; i < nmg; i += OA_NT) {                                  // the targets outside the table: marked, whoever names them
+        const int r = target[merge[2 * i]];
+        if (find_row(be.mp_id, nm, mg_root[i]) >= 0 || wsz[r] <= 0) continue;
+        named[r] = 1;
+        atomicMin(&s_lo, r); atomicMax(&s_hi, r);                           // LDS
+    }
+    for (int d = t; d < nst; d += OA_NT) {                                  // a staged row of a table point stands behind the rows the point had
+        const int rr = find_row(be.mp_id, nm, R.row_root_id[sb + d]);
+        const int place = R.row_place[sb + d];
+        if (rr < 0) {                                                       // of a point outside the table: behind its stored rows, within what it receives
+            const int s = R.row_slot[sb + d];
+            if (s < 0 || s >= aM || state[s] == 2) { bad = true; continue; }
+            const int c = seg_cnt[s] > 0 ? seg_cnt[s] : 0;
+            bad |= place < c || place - c >= wsz[s] || (R.row_flags[sb + d] & ~MYSLAM_BACKEND_OBS_OUTLIER);
+            continue;
+        }
+        const int p = find_row(pid, pn, be.mp_id[rr]);
+        bad |= p < 0 || place < po[p + 1] - po[p] || place >= noff[rr + 1] - noff[rr];
+    }
+    if (bad) s_bad = 1;
+    __syncthreads();
+    const int lo = s_lo, hi = s_hi;
+    int keep = 0, fresh = 0;
+    for (int s = t; s < aM; s += OA_NT) {
+        const int c = (seg_cnt[s] > 0 && state[s] != 2) ? seg_cnt[s] : 0;
+        if (c && (seg_off[s] < 0 || seg_off[s] > A.row_cap - c)) { s_bad = 1; continue; }
+        if (s >= lo && s <= hi && named[s]) fresh += c + wsz[s]; else keep += c;
+    }
+    if (keep) atomicAdd(&s_keep, keep);
+    if (fresh) atomicAdd(&s_new, fresh);
+    __syncthreads();
+    const int n_new = s_new;
+    if (s_bad || s_keep + n_new > A.row_cap) {                              // uniform; sticky, every byte kept (the marks go)
+        for (int s = lo + t; s <= hi; s += OA_NT) named[s] = 0;
+        const int e = s_bad ? MYSLAM_ERR_INVALID : MYSLAM_ERR_CAPACITY;
+        if (t == 0) { A.err[b] = e; status[b] = e; }
+        return;
+    }
+    // ---- from here on the item is written: the other mirror, the free rows of the pool (or the other pool), the slots ----
+    for (int r = t; r < no; r += OA_NT) {
+        const int m = be.obs_mp[r], p = w_p[m], j = r - noff[m];
+        if (j < po[p + 1] - po[p]) new_mir.kf[r] = old_mir.kf[po[p] + j];
+        new_mir.uv[2 * r] = be.obs_uv[2 * r]; new_mir.uv[2 * r + 1] = be.obs_uv[2 * r + 1];
+        new_mir.tag[r] = be.obs_tag[r]; new_mir.flags[r] = be.obs_flags[r] & MYSLAM_BACKEND_OBS_OUTLIER;
+    }
+    for (int d = t; d < nst; d += OA_NT) {                                  // the appended rows' observers
+        const int rr = find_row(be.mp_id, nm, R.row_root_id[sb + d]);
+        if (rr >= 0) new_mir.kf[noff[rr] + R.row_place[sb + d]] = R.row_kf_id[sb + d];
+    }
+    for (int m = t; m < nm; m += OA_NT) nid[m] = be.mp_id[m];
+    if (t == 0) A.t_n_mp[mc ^ 1][b] = nm;
+    int base = used, npc = pc;
+    if (used + n_new > A.row_cap) {                                         // reclaim: the live segments that are not written afresh, in slot order
+        const OaRows dst = A.pool[pc ^ 1].at((size_t)b * A.row_cap);
+        base = 0; npc = pc ^ 1;
+        for (int s0 = 0; s0 < aM; s0 += OA_NT) {                            // uniform
+            const int s = s0 + t;
+            const int c = (s < aM && seg_cnt[s] > 0 && state[s] != 2 && !(s >= lo && s <= hi && named[s])) ? seg_cnt[s] : 0;
+            int tot;
+            const int pos = base + block_exsum<OA_NW>(c, s_w, tot);
+            if (c) {
+                const int o = seg_off[s];
+                for (int j = 0; j < c; j++) dst.copy_from(pos + j, old_pool, o + j);
+                seg_off[s] = pos;
+            }
+            base += tot;
+        }
+    }
+    const OaRows dst = A.pool[npc].at((size_t)b * A.row_cap);
+    for (int s0 = lo; s0 <= hi; s0 += OA_NT) {                              // uniform: the targets outside the table, in slot order
+        const int s = s0 + t;
+        const bool on = s <= hi && named[s];
+        const int c = (on && seg_cnt[s] > 0) ? seg_cnt[s] : 0, k = on ? c + wsz[s] : 0;
+        int tot;
+        const int pos = base + block_exsum<OA_NW>(k, s_w, tot);
+        if (on) {
+            const int o = seg_off[s];
+            for (int j = 0; j < c; j++) dst.copy_from(pos + j, old_pool, o + j);
+            seg_off[s] = pos; seg_cnt[s] = k;
+        }
+        base += tot;
+    }
+    __syncthreads();
+    const OaRows stg{R.row_kf_id + sb, R.row_uv + sb * 2, R.row_tag + sb, R.row_flags + sb};
+    for (int d = t; d < nst; d += OA_NT) {                                  // the moved rows behind them, each at its place
+        const int s = R.row_slot[sb + d];
+        if (s >= lo && s <= hi && named[s]) dst.copy_from(seg_off[s] + R.row_place[sb + d], stg, d);
+    }
+    __syncthreads();
+    for (int s = lo + t; s <= hi; s += OA_NT) named[s] = 0;
+    if (t == 0) {
+        A.mcur[b] = mc ^ 1; A.pcur[b] = npc; A.used[b] = base;
+        if (npc != pc) A.n_reclaim[b] += 1;
+        status[b] = MYSLAM_MAP_UPDATED;
+    }
+}
+
+__global__ __launch_bounds__(OA_NT) void k_relink_first_kf(OaTables A, const int64_t* map_kf_id, const int32_t* map_n_kf, int kf_cap, int32_t* first_kf) {
+    const int b = blockIdx.y, s = blockIdx.x * OA_NT + threadIdx.x;
+    const int aM = clamped_count(A.map_n_mp, b, A.point_cap);
+    if (s >= aM) return;
+    int out = -1;
+    const int mc = A.mcur[b] & 1, pc = A.pcur[b] & 1;
+    const int pn = A.t_n_mp[mc][b];
+    const int32_t* const po = A.t_off[mc] + (size_t)b * (A.be_mp_cap + 1);
+    const int pno = (pn >= 0 && pn <= A.be_mp_cap) ? po[pn] : -1;
+    if (!A.err[b] && pno >= 0 && pno <= A.be_obs_cap && A.map_state[(size_t)b * A.point_cap + s] != 2) {
+        const OaSeg o = oa_own(A, b, mc, pn, pno, s);
+        if (o.n > 0) {
+            const int64_t kf = o.p >= 0 ? A.mir[mc].kf[(size_t)b * A.be_obs_cap + po[o.p]] : A.pool[pc].kf[(size_t)b * A.row_cap + A.seg_off[(size_t)b * A.point_cap + s]];
+            out = find_row(map_kf_id + (size_t)b * kf_cap, clamped_count(map_n_kf, b, kf_cap), kf);
+        }
+    }
+    first_kf[(size_t)b * A.point_cap + s] = out;
+}
+
 }  // namespace myslam_hip
 
 using namespace myslam_hip;
@@ -547,6 +852,45 @@ int myslam_obs_archive_prior_rows_batch(myslam_obs_archive* h, const int64_t* d_
     const OaPriorIn I{d_feat_mp_id, d_n_feat, feat_cap, d_mp_id, d_n_mp, be_mp_cap};
     const OaPriorOut O{d_prior_mp_id, {d_prior_kf_id, d_prior_uv, d_prior_tag, d_prior_flags}, d_n_prior, prior_cap};
     hipLaunchKernelGGL(k_obs_prior_rows, dim3(batch), dim3(OA_NT), 0, h->stream, h->t, I, O, d_status);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    return MYSLAM_OK;
+}
+
+int myslam_relink_stage_batch(myslam_obs_archive* oa, myslam_relink* h, const int32_t* d_plan_status, int batch, int32_t* d_status) {
+    if (!oa || !h || !d_plan_status || !d_status || batch < 0) return MYSLAM_ERR_INVALID;
+    myslam_relink_lists v;
+    if (myslam_relink_view(h, &v) != MYSLAM_OK || v.point_cap != oa->t.point_cap) return MYSLAM_ERR_INVALID;
+    if (batch > oa->max_batch || batch > v.max_batch) return MYSLAM_ERR_CAPACITY;
+    if (batch == 0) return MYSLAM_OK;
+    hipLaunchKernelGGL(k_relink_stage, dim3(batch), dim3(OA_NT), 0, oa->stream, oa->t, v, d_plan_status, d_status);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    return MYSLAM_OK;
+}
+
+int myslam_relink_obs_update_batch(myslam_obs_archive* oa, myslam_relink* h, const int64_t* d_kf_id, const int32_t* d_n_kf, const int64_t* d_mp_id,
+                                   const int32_t* d_n_mp, const int32_t* d_obs_mp, const int32_t* d_obs_kf, const uint8_t* d_obs_flags, const float* d_obs_uv,
+                                   const int32_t* d_obs_tag, const int32_t* d_n_obs, int be_kf_cap, int be_mp_cap, int be_obs_cap,
+                                   const int32_t* d_backend_status, const int32_t* d_map_status, int batch, int32_t* d_status) {
+    if (!oa || !h || batch < 0 || !d_kf_id || !d_n_kf || !d_mp_id || !d_n_mp || !d_obs_mp || !d_obs_kf || !d_obs_flags || !d_obs_uv || !d_obs_tag || !d_n_obs ||
+        !d_backend_status || !d_map_status || !d_status || be_kf_cap < 1 || be_mp_cap != oa->t.be_mp_cap || be_obs_cap != oa->t.be_obs_cap)
+        return MYSLAM_ERR_INVALID;
+    myslam_relink_lists v;
+    if (myslam_relink_view(h, &v) != MYSLAM_OK || v.point_cap != oa->t.point_cap) return MYSLAM_ERR_INVALID;
+    if (batch > oa->max_batch || batch > v.max_batch) return MYSLAM_ERR_CAPACITY;
+    if (batch == 0) return MYSLAM_OK;
+    const BeTablesRead B{d_kf_id, nullptr, d_n_kf, d_mp_id, nullptr, nullptr, d_n_mp, d_obs_mp, d_obs_kf, d_obs_flags, d_obs_uv, d_obs_tag, d_n_obs,
+                         be_kf_cap, be_mp_cap, be_obs_cap};
+    hipLaunchKernelGGL(k_relink_obs_update, dim3(batch), dim3(OA_NT), 0, oa->stream, oa->t, B, v, d_backend_status, d_map_status, d_status);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    return MYSLAM_OK;
+}
+
+int myslam_relink_first_kf_batch(myslam_obs_archive* oa, int batch, int32_t* d_first_kf) {
+    if (!oa || batch < 0 || !d_first_kf) return MYSLAM_ERR_INVALID;
+    if (batch > oa->max_batch) return MYSLAM_ERR_CAPACITY;
+    if (batch == 0) return MYSLAM_OK;
+    hipLaunchKernelGGL(k_relink_first_kf, dim3((oa->t.point_cap + OA_NT - 1) / OA_NT, batch), dim3(OA_NT), 0, oa->stream, oa->t, oa->map.kf_id, oa->map.n_kf,
+                       oa->map.kf_cap, d_first_kf);
     MYSLAM_HIP_CHECK(hipGetLastError());
     return MYSLAM_OK;
 }

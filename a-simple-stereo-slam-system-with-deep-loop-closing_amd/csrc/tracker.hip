@@ -522,6 +522,94 @@ __global__ __launch_bounds__(TRK_NT) void k_trk_clear_links(TrkArgs a, const int
     if (t == 0 && n_cleared) n_cleared[s] = cleared;
 }
 
+// ---- LoopLocalFusion re-linked features of the reference key-frame (src/loopclosing.cpp:521-530).  Same sharing and same guard as above: while
+//      the last frame is that key-frame's frame, feature `tag` names the point its list entry gives (an archive slot of the map, -1 = none).  A
+//      feature that has a landmark keeps its slot, and the slot takes the target's id, position and outlier flag (every feature of the frame that
+//      shared the slot observed the same point and moved with it); a feature without one takes the slot that carries the target's id, else a new
+//      one.  The entries are walked in list order on copies (the turn's scratch: kfId, kfMap = the archive slot a landmark slot takes its values
+//      from, kfSlot = the features' slots), the landmark search of an entry is the block's; nothing of the stream is written before the walk has
+//      shown that every slot is in range and the table holds the new landmarks ----
+struct TrkRelink {
+    const int64_t* kf_id; const int32_t* tag; const int32_t* slot; const int32_t* n; int list_cap;
+    const int64_t* mp_id; const double* mp_pos; const uint8_t* mp_state; const int32_t* n_mp; int point_cap;
+    int32_t* n_relinked; int32_t* status;
+};
+__global__ __launch_bounds__(TRK_NT) void k_trk_relink(TrkArgs a, TrkRelink r) {
+    __shared__ int s_found, s_bad;
+    const int s = blockIdx.x, t = threadIdx.x;
+    TrkState& st = a.st[s];
+    if (st.idsValid == 0 || st.ref_frame_id != st.next_frame_id - 1) {     // uniform: the frame has moved on, every byte kept
+        if (t == 0) { r.status[s] = MYSLAM_OK; if (r.n_relinked) r.n_relinked[s] = 0; }
+        return;
+    }
+    const int cnt = clamped_count(r.n, s, r.list_cap), nFeat = clamped_count(st.n_feat, a.cap), nLm = clamped_count(st.n_lm, a.lmCap);
+    const int aM = clamped_count(r.n_mp, s, r.point_cap);
+    const int64_t ref = a.ids[(size_t)s * 3];
+    const size_t fb = (size_t)s * a.cap, lb = (size_t)s * a.lmCap, lo = (size_t)s * r.list_cap, pb = (size_t)s * r.point_cap;
+    const auto names = [&](int j) { const int f = r.tag[lo + j]; return r.kf_id[lo + j] == ref && f >= 0 && f < nFeat; };
+    if (t == 0) { s_found = 0x7fffffff; s_bad = 0; }
+    __syncthreads();
+    bool bad = false;
+    for (int j = t; j < cnt; j += TRK_NT)
+        if (names(j)) { const int v = r.slot[lo + j]; bad |= v < -1 || v >= aM; }
+    if (bad) s_bad = 1;
+    for (int l = t; l < nLm; l += TRK_NT) { a.kfId[lb + l] = a.lmId[lb + l]; a.kfMap[lb + l] = -1; }
+    for (int f = t; f < nFeat; f += TRK_NT) a.kfSlot[fb + f] = a.lm[fb + f];
+    __syncthreads();
+    if (s_bad) {                                                            // uniform; every byte of the stream kept
+        if (t == 0) { r.status[s] = MYSLAM_ERR_INVALID; if (r.n_relinked) r.n_relinked[s] = 0; }
+        return;
+    }
+    int nNew = 0, hits = 0;
+    bool full = false;
+    for (int j = 0; j < cnt; j++) {                                         // uniform: every thread reads the same entry
+        __syncthreads();                                                    // what the entry before wrote
+        if (!names(j)) continue;
+        hits++;
+        const int f = r.tag[lo + j], v = r.slot[lo + j];
+        if (v < 0) { if (t == 0) a.kfSlot[fb + f] = -1; continue; }
+        const int64_t id = r.mp_id[pb + v];
+        const int L = a.kfSlot[fb + f];
+        if (L >= 0 && L < nLm + nNew) {                                     // an observation moved with its point: the slot is the target's now
+            if (t == 0) { a.kfId[lb + L] = id; a.kfMap[lb + L] = v; }
+            continue;
+        }
+        int mine = 0x7fffffff;
+        for (int l = t; l < nLm + nNew; l += TRK_NT)
+            if (a.kfId[lb + l] == id) { mine = l; break; }
+        if (mine != 0x7fffffff) atomicMin(&s_found, mine);                 // LDS
+        __syncthreads();
+        const int found = s_found;
+        __syncthreads();
+        const bool opens = found == 0x7fffffff;
+        if (opens && nLm + nNew >= a.lmCap) { full = true; continue; }      // uniform
+        const int slot = opens ? nLm + nNew : found;
+        if (t == 0) {
+            s_found = 0x7fffffff;
+            a.kfSlot[fb + f] = slot; a.kfId[lb + slot] = id; a.kfMap[lb + slot] = v;
+        }
+        nNew += opens;
+    }
+    __syncthreads();
+    if (full) {                                                             // uniform; only the scratch was written
+        if (t == 0) { r.status[s] = MYSLAM_ERR_CAPACITY; if (r.n_relinked) r.n_relinked[s] = 0; }
+        return;
+    }
+    // ---- commit ----
+    for (int l = t; l < nLm + nNew; l += TRK_NT) {
+        const int v = a.kfMap[lb + l];
+        if (v < 0) continue;
+        a.lmId[lb + l] = a.kfId[lb + l]; a.lmOutl[lb + l] = r.mp_state[pb + v] == 1;
+        for (int c = 0; c < 3; c++) a.lmPos[(lb + l) * 3 + c] = r.mp_pos[(pb + v) * 3 + c];
+    }
+    for (int f = t; f < nFeat; f += TRK_NT) a.lm[fb + f] = a.kfSlot[fb + f];
+    if (t == 0) {
+        st.n_lm = nLm + nNew;
+        r.status[s] = MYSLAM_OK;
+        if (r.n_relinked) r.n_relinked[s] = hits;
+    }
+}
+
 // ---- the stored previous left image of the selected streams <- imgs (the pyramid follows in lk_bank_pyramid) ----
 __global__ __launch_bounds__(TRK_NT) void k_kf_set_image(TrkArgs a, const uint8_t* imgs, int step, size_t stride, const uint8_t* select) {
     const int s = blockIdx.y, t = threadIdx.x;
@@ -1022,6 +1110,18 @@ int myslam_tracker_update_from_map_batch(myslam_tracker* h, const int64_t* d_kf_
 int myslam_tracker_clear_links_batch(myslam_tracker* h, const int64_t* d_kf_id, const int32_t* d_tag, const int32_t* d_n, int list_cap, int32_t* d_n_cleared) {
     if (!h || !d_kf_id || !d_tag || !d_n || list_cap <= 0) return MYSLAM_ERR_INVALID;
     hipLaunchKernelGGL(k_trk_clear_links, dim3(h->S), dim3(TRK_NT), 0, h->stream, h->a, d_kf_id, d_tag, d_n, list_cap, d_n_cleared);
+    MYSLAM_HIP_CHECK(hipGetLastError());
+    return MYSLAM_OK;
+}
+
+int myslam_tracker_relink_batch(myslam_tracker* h, const int64_t* d_kf_id, const int32_t* d_tag, const int32_t* d_slot, const int32_t* d_n, int list_cap,
+                                const myslam_map* map, int32_t* d_n_relinked, int32_t* d_status) {
+    if (!h || !d_kf_id || !d_tag || !d_slot || !d_n || list_cap <= 0 || !map || !d_status) return MYSLAM_ERR_INVALID;
+    myslam_map_tables mv;
+    if (myslam_map_view(map, &mv) != MYSLAM_OK) return MYSLAM_ERR_INVALID;
+    if (h->S > mv.max_batch) return MYSLAM_ERR_INVALID;                       // item s of the map is stream s
+    const TrkRelink r{d_kf_id, d_tag, d_slot, d_n, list_cap, mv.mp_id, mv.mp_pos, mv.mp_state, mv.n_mp, mv.point_cap, d_n_relinked, d_status};
+    hipLaunchKernelGGL(k_trk_relink, dim3(h->S), dim3(TRK_NT), 0, h->stream, h->a, r);
     MYSLAM_HIP_CHECK(hipGetLastError());
     return MYSLAM_OK;
 }

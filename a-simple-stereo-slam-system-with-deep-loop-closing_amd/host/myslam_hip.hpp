@@ -448,6 +448,13 @@ public:
     void ClearLinksBatch(const int64_t* d_kfId, const int32_t* d_tag, const int32_t* d_n, int listCap, int32_t* d_nCleared = nullptr) {
         check(myslam_tracker_clear_links_batch(h_, d_kfId, d_tag, d_n, listCap, d_nCleared), "myslam_tracker_clear_links_batch");
     }
+    // Relink::View()'s link lists against the map archive of the same streams (MapArchive::handle()): under ClearLinksBatch's guard the landmark of every
+    // listed feature of the reference key-frame takes the target's id, position and outlier flag (src/loopclosing.cpp:524, :529), a feature without one
+    // gets the slot that carries the id or a new one; status[s] = MYSLAM_OK, or MYSLAM_ERR_INVALID / _CAPACITY with every byte of the stream kept
+    void RelinkBatch(const int64_t* d_kfId, const int32_t* d_tag, const int32_t* d_slot, const int32_t* d_n, int listCap, const myslam_map* map,
+                     int32_t* d_nRelinked, int32_t* d_status) {
+        check(myslam_tracker_relink_batch(h_, d_kfId, d_tag, d_slot, d_n, listCap, map, d_nRelinked, d_status), "myslam_tracker_relink_batch");
+    }
     // the stored previous left image of the selected streams <- d_imgs[s] (a key-frame's image after DeepLCD blurred it)
     void SetImageBatch(const uint8_t* d_imgs, int step, size_t stride, const uint8_t* d_select) {
         check(myslam_tracker_set_image_batch(h_, d_imgs, step, stride, d_select), "myslam_tracker_set_image_batch");
@@ -612,6 +619,7 @@ class Backend {
     myslam_backend* h_ = nullptr;
     int maxBatch_, kfCap_, mpCap_, obsCap_;
 public:
+    myslam_backend* handle() { return h_; }
     Backend(int maxBatch, int kfCap, int mpCap, int obsCap) : maxBatch_(maxBatch), kfCap_(kfCap), mpCap_(mpCap), obsCap_(obsCap) {
         check(myslam_backend_create(&h_, maxBatch, kfCap, mpCap, obsCap), "myslam_backend_create");
     }
@@ -678,7 +686,7 @@ public:
 // LoopCorrector::CorrectBatch's tables (View() gives the device pointers).  Order of a key-frame: InsertKeyFrameBatch -> UpdateBatch(AFTER_INSERT) ->
 // OptimizeBatch -> UpdateBatch(AFTER_OPTIMIZE) -> Backend::CulledView's lists into LoopKeyFrameStore::ClearLinksBatch and TrackerBank::ClearLinksBatch
 // -> ... -> DetectBatch -> FilterLandmarksBatch -> MatchFeaturesBatch -> ... -> LoopInputsBatch -> CorrectBatch -> WriteBackendBatch ->
-// Tracker::UpdateFromMap.  Left with the caller: LoopLocalFusion's re-linking of observations.
+// Relink (below: PlanBatch ... ObsUpdateBatch, with RelinkBatch and UpdateBatch(MYSLAM_MAP_AFTER_RELINK) of this class) -> Tracker::UpdateFromMap.
 class MapArchive {
     myslam_map* h_ = nullptr;
 public:
@@ -743,7 +751,63 @@ public:
     void FilterLandmarksBatch(int32_t* d_featureLandmark, int featCap, int batch, int32_t* d_nDropped = nullptr) {
         check(myslam_map_filter_landmarks_batch(h_, d_featureLandmark, featCap, batch, d_nDropped), "myslam_map_filter_landmarks_batch");
     }
+    // Relink::View()'s merge list (stride mergeCap = its outCap) and Relink::PlanBatch's status: the merged points are erased (src/loopclosing.cpp:527)
+    void RelinkBatch(const int32_t* d_merge, const int32_t* d_nMerge, int mergeCap, const int32_t* d_planStatus, int batch, int32_t* d_status) {
+        check(myslam_map_relink_batch(h_, d_merge, d_nMerge, mergeCap, d_planStatus, batch, d_status), "myslam_map_relink_batch");
+    }
     const myslam_map* handle() const { return h_; }
+};
+
+// The plan of LoopClosing::LoopLocalFusion's re-linking (src/loopclosing.cpp:509-532) for a batch of corrected loops on the device (myslam_relink_*,
+// include/myslam_hip.h, RE-LINK): which map point of the current key-frame is merged into which point of the loop key-frame, which feature adopts a loop
+// point, where every archive slot's features end; and the moved observation rows, staged in this handle and carried into the back end's tables and
+// the two archives.  `map` is the MapArchive of the same streams and must outlive this object.  Order of one loop: CorrectBatch -> WriteBackendBatch ->
+// PlanBatch -> StageBatch -> BackendBatch -> MapArchive::RelinkBatch (View().merge, BackendBatch's status) -> MapArchive::UpdateBatch
+// (MYSLAM_MAP_AFTER_RELINK) -> ObsUpdateBatch -> LoopKeyFrameStore::SetLinksBatch (View().row_kf_id / row_tag / row_slot, then View().link_*) and
+// TrackerBank::RelinkBatch (View().link_*) -> TrackerBank::UpdateFromMap; FirstKfBatch before the next CorrectBatch.
+class Relink {
+    myslam_relink* h_ = nullptr;
+public:
+    Relink(const MapArchive& map, int maxBatch, int outCap, int featCap, int stageCap) {
+        check(myslam_relink_create(&h_, map.handle(), maxBatch, outCap, featCap, stageCap), "myslam_relink_create");
+    }
+    ~Relink() { if (h_) myslam_relink_destroy(h_); }
+    Relink(const Relink&) = delete; Relink& operator=(const Relink&) = delete;
+    void SetStream(void* hipStream) { check(myslam_relink_set_stream(h_, hipStream), "myslam_relink_set_stream"); }
+    int LaunchesPerPlan() const { return myslam_relink_launches_per_plan(h_); }
+    // device pointers and caps of the plan's outputs, valid until destruction
+    myslam_relink_lists View() const {
+        myslam_relink_lists v;
+        check(myslam_relink_view(h_, &v), "myslam_relink_view");
+        return v;
+    }
+    // MatchFeaturesBatch's pairs and counts, VerifyBatch's outlier flags, CorrectBatch's status, the current key-frame's feature -> slot table (in/out),
+    // the gathered loop table, the current mnKFId; status[b] = MYSLAM_RELINK_DONE / _SKIPPED or MYSLAM_ERR_INVALID
+    void PlanBatch(const int32_t* d_validPairs, const int32_t* d_counts, const uint8_t* d_outlier, const int32_t* d_correctStatus,
+                   int32_t* d_curFeatureLandmark, const int32_t* d_loopFeatureLandmark, const int64_t* d_curKfId, int batch, int32_t* d_status) {
+        check(myslam_loop_relink_plan_batch(h_, d_validPairs, d_counts, d_outlier, d_correctStatus, d_curFeatureLandmark, d_loopFeatureLandmark, d_curKfId,
+                                            batch, d_status), "myslam_loop_relink_plan_batch");
+    }
+    // the rows (src/loopclosing.cpp:521-527): StageBatch -> BackendBatch -> MapArchive::RelinkBatch -> MapArchive::UpdateBatch(MYSLAM_MAP_AFTER_RELINK) ->
+    // ObsUpdateBatch; FirstKfBatch gives CorrectBatch's d_firstKF in list order from then on.  The raw handles come from ObsArchive::handle() / Backend::handle()
+    void StageBatch(myslam_obs_archive* obs, const int32_t* d_planStatus, int batch, int32_t* d_status) {
+        check(myslam_relink_stage_batch(obs, h_, d_planStatus, batch, d_status), "myslam_relink_stage_batch");
+    }
+    void BackendBatch(myslam_backend* be, int64_t* d_kfId, double* d_kfPose, int32_t* d_nKF, int64_t* d_mpId, double* d_mpPos, uint8_t* d_mpOutlier, int32_t* d_nMP,
+                      int32_t* d_obsMP, int32_t* d_obsKF, uint8_t* d_obsFlags, float* d_obsUV, int32_t* d_obsTag, int32_t* d_nObs, const int32_t* d_stageStatus,
+                      int batch, int32_t* d_mpNewRow, int32_t* d_status) {
+        check(myslam_relink_backend_batch(be, h_, d_kfId, d_kfPose, d_nKF, d_mpId, d_mpPos, d_mpOutlier, d_nMP, d_obsMP, d_obsKF, d_obsFlags, d_obsUV, d_obsTag, d_nObs,
+                                          d_stageStatus, batch, d_mpNewRow, d_status), "myslam_relink_backend_batch");
+    }
+    void ObsUpdateBatch(myslam_obs_archive* obs, const int64_t* d_kfId, const int32_t* d_nKF, const int64_t* d_mpId, const int32_t* d_nMP, const int32_t* d_obsMP,
+                        const int32_t* d_obsKF, const uint8_t* d_obsFlags, const float* d_obsUV, const int32_t* d_obsTag, const int32_t* d_nObs, int kfCap, int mpCap,
+                        int obsCap, const int32_t* d_backendStatus, const int32_t* d_mapStatus, int batch, int32_t* d_status) {
+        check(myslam_relink_obs_update_batch(obs, h_, d_kfId, d_nKF, d_mpId, d_nMP, d_obsMP, d_obsKF, d_obsFlags, d_obsUV, d_obsTag, d_nObs, kfCap, mpCap, obsCap,
+                                             d_backendStatus, d_mapStatus, batch, d_status), "myslam_relink_obs_update_batch");
+    }
+    static void FirstKfBatch(myslam_obs_archive* obs, int batch, int32_t* d_firstKF) {
+        check(myslam_relink_first_kf_batch(obs, batch, d_firstKF), "myslam_relink_first_kf_batch");
+    }
 };
 
 // MapPoint::GetObservations() (src/mappoint.cpp:19-44) of every map point that is alive and not in the back end's table, per stream, on the device
@@ -760,6 +824,7 @@ public:
     ~ObsArchive() { if (h_) myslam_obs_archive_destroy(h_); }
     ObsArchive(const ObsArchive&) = delete; ObsArchive& operator=(const ObsArchive&) = delete;
     void SetStream(void* hipStream) { check(myslam_obs_archive_set_stream(h_, hipStream), "myslam_obs_archive_set_stream"); }
+    myslam_obs_archive* handle() { return h_; }
     int LaunchesPerUpdate() const { return myslam_obs_archive_launches_per_update(h_); }
     // one item from / to host arrays (synchronous): the live segments (ids ascending) with their rows, and the mirror of the back end's current table
     void Load(int item, const int64_t* segMPId, const int32_t* segCount, int nSeg, const int64_t* rowKFId, const float* rowUV, const int32_t* rowTag,
@@ -830,6 +895,12 @@ public:
                          int32_t* d_pendingFeatureLandmark = nullptr, int32_t* d_nCleared = nullptr) {
         check(myslam_loop_store_clear_links_batch(h_, d_kfId, d_tag, d_n, listCap, batch, d_pendingKfId, d_pendingFeatureLandmark, d_nCleared),
               "myslam_loop_store_clear_links_batch");
+    }
+    // ClearLinksBatch with a value per entry (Relink::View()'s link lists): the named feature points at d_slot (>= -1) afterwards (src/loopclosing.cpp:524, :529)
+    void SetLinksBatch(const int64_t* d_kfId, const int32_t* d_tag, const int32_t* d_slot, const int32_t* d_n, int listCap, int batch,
+                       const int64_t* d_pendingKfId = nullptr, int32_t* d_pendingFeatureLandmark = nullptr, int32_t* d_nSet = nullptr) {
+        check(myslam_loop_store_set_links_batch(h_, d_kfId, d_tag, d_slot, d_n, listCap, batch, d_pendingKfId, d_pendingFeatureLandmark, d_nSet),
+              "myslam_loop_store_set_links_batch");
     }
     void DetectBatch(const uint64_t* d_bestId, const float* d_maxScore, const int32_t* d_cntSuspected, int nq, uint8_t* d_loopDescriptors, int32_t* d_nLoop,
                      KeyPoint* d_loopPyramidKeyPoints, int32_t* d_loopFeatureLandmark, int32_t* d_loopSlot, int32_t* d_status, float thrHigh = 0.94f /*:147*/,

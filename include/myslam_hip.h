@@ -1056,7 +1056,9 @@ int myslam_loop_verify_batch(myslam_pnp* h, const float* d_pts3d, const float* d
  *                                                       in/out: T[v0] * T[v1]^-1 as measured;  d_n_edges batch i32, in/out
  *   d_points           batch x point_cap x 3 f64, in/out   map points;  d_n_points batch i32
  *   d_first_active     batch x point_cap i32            slot IN THE ITEM'S ACTIVE LIST of the active key-frame that first observes the point; < 0: not an active map point
- *   d_first_kf         batch x point_cap i32            row of the key-frame that first observed the point; < 0: the skip of :627-631
+ *   d_first_kf         batch x point_cap i32            row of the key-frame that first observed the point; < 0: the skip of :627-631.  A stream that
+ *                                                       re-links (RE-LINK, below) passes myslam_relink_first_kf_batch's array here: GetObservations().front()
+ *                                                       in LIST order, which myslam_map_loop_inputs_batch's d_first_kf is not for a merged target
  * correct_threshold = 1.0 (:285), max_iters = 20 (:606) at the call site.  Per item, in this order:
  *   1. d_verify_status[b] != MYSLAM_VERIFY_CONFIRMED -> MYSLAM_LOOP_CORRECT_SKIPPED, nothing of the item's tables is touched;
  *   2. the edge (cur, loop) with the measurement Tcc * Tloop^-1 (:328-330; Tloop = the loop key-frame's pose as given) is appended at slot d_n_edges[b]
@@ -1078,7 +1080,9 @@ int myslam_loop_verify_batch(myslam_pnp* h, const float* d_pts3d, const float* d
  * order makes its LATER endpoint a separator of a dense Schur system (chosen on the device, no greedy pass).  A map that needs more than
  * MYSLAM_LOOP_CORRECT_MAX_SEPARATORS of them (one per closed loop, 17 over KITTI 00) gets MYSLAM_LOOP_CORRECT_FUSED_ONLY: steps 2 to 4 are done, poses
  * outside the active window and non-active points are untouched, d_iters[b] = 0 — the caller finishes that map with myslam_pose_graph_optimize +
- * myslam_correct_map_points.  Re-linking observations (:509-532) stays with the caller, as for myslam_loop_local_fusion.
+ * myslam_correct_map_points.  Re-linking observations (:509-532) is not part of this call: for tables that live on the device it is RE-LINK, below,
+ * which runs after this call and myslam_map_write_backend_batch on this call's d_status (DONE and FUSED_ONLY re-link, every other status skips); for
+ * host maps it is the caller's, as for myslam_loop_local_fusion.
  * batch beyond the handle's -> MYSLAM_ERR_CAPACITY, nothing enqueued.
  * ------------------------------------------------------------------------------------------ */
 #define MYSLAM_LOOP_CORRECT_DONE 0
@@ -1325,12 +1329,17 @@ int myslam_backend_insert_launches_per_call(const myslam_backend* h);
  * All batch calls allocate nothing, never synchronise, read no device memory from the host, are recordable between myslam_graph_begin / _end and use no
  * global atomics; an item's bytes depend neither on its slot nor on its neighbours.  Call level, nothing enqueued: NULL pointers, an unknown mode, a
  * back-end cap that does not match (be_kf_cap beyond MYSLAM_BA_MAX_WINDOW_POSES included) -> MYSLAM_ERR_INVALID; batch beyond the handle's -> MYSLAM_ERR_CAPACITY.
- * OUT OF SCOPE, left with the caller: LoopLocalFusion's re-linking of observations (src/loopclosing.cpp:509-532) with its effect on the back end's
- * tables and the tracker's landmark ids.  Culled and erased links: LINK UPKEEP, below; whole tables from a host map:
- * myslam_loop_store_set_landmarks_batch.
+ * OUT OF SCOPE for the modes above: LoopLocalFusion's re-linking of observations (src/loopclosing.cpp:509-532) is not done by an insert's or an optimise's
+ * update; it is RE-LINK's, below, on the device: the plan, the moved rows in the back end's tables and in the observation archive, the erased states
+ * (myslam_map_relink_batch) and mode MYSLAM_MAP_AFTER_RELINK of myslam_map_update_batch, which is an insert's update without an outlier list (the
+ * re-link makes neither a key-frame nor a point): refresh, snapshot, masks and window record follow the re-linked table.  mp_first_kf is NOT exact for
+ * a point a re-link has touched (its list is no longer in key-frame order): a stream that re-links passes myslam_relink_first_kf_batch's array to
+ * myslam_loop_correct_batch instead of myslam_map_loop_inputs_batch's d_first_kf.  Culled and erased links: LINK UPKEEP, below; whole tables from
+ * a host map: myslam_loop_store_set_landmarks_batch.
  * ------------------------------------------------------------------------------------------ */
 #define MYSLAM_MAP_AFTER_INSERT 0
 #define MYSLAM_MAP_AFTER_OPTIMIZE 1
+#define MYSLAM_MAP_AFTER_RELINK 2     /* RE-LINK, below */
 #define MYSLAM_MAP_UPDATED 0
 #define MYSLAM_MAP_SKIPPED 1
 typedef struct myslam_map myslam_map;
@@ -1494,8 +1503,10 @@ int myslam_tracker_clear_links_batch(myslam_tracker* h, const int64_t* d_kf_id, 
  * myslam_graph_begin / _end; an item's bytes depend neither on its slot nor on its neighbours.  Call level, nothing enqueued: NULL required
  * pointers, an unknown mode, d_obs_report missing AFTER_OPTIMIZE, caps that do not match the handle or the map -> MYSLAM_ERR_INVALID; a batch beyond
  * the handle's -> MYSLAM_ERR_CAPACITY.
- * OUT OF SCOPE, as above: LoopLocalFusion's re-linking (src/loopclosing.cpp:509-532), which appends a point's observations to a point that is
- * usually not active; this store is where they would be appended.
+ * OUT OF SCOPE for the two calls above: the rows that LoopLocalFusion's re-linking moves (src/loopclosing.cpp:509-532; :521-525 appends a point's
+ * observations to a point that is usually not active, so this store is where they are appended).  RE-LINK, below, does it on this handle:
+ * myslam_relink_stage_batch reads the lists, myslam_relink_obs_update_batch is this handle's update after a re-link (myslam_obs_archive_update_batch
+ * keeps its two modes), myslam_relink_first_kf_batch gives the front observers in list order.
  * ------------------------------------------------------------------------------------------ */
 typedef struct myslam_obs_archive myslam_obs_archive;
 int myslam_obs_archive_create(myslam_obs_archive** out, const myslam_map* map, int max_batch, int be_obs_cap, int row_cap);
@@ -1521,6 +1532,160 @@ int myslam_obs_archive_launches_per_update(const myslam_obs_archive* h);
 int myslam_obs_archive_prior_rows_batch(myslam_obs_archive* h, const int64_t* d_feat_mp_id, const int32_t* d_n_feat, int feat_cap, const int64_t* d_mp_id,
                                         const int32_t* d_n_mp, int be_mp_cap, int batch, int64_t* d_prior_mp_id, int64_t* d_prior_kf_id, float* d_prior_uv,
                                         int32_t* d_prior_tag, uint8_t* d_prior_flags, int32_t* d_n_prior, int prior_cap, int32_t* d_status);
+
+/* ------------------------------------------------------------------------------------------
+ * RE-LINK — the second half of LoopClosing::LoopLocalFusion (src/loopclosing.cpp:509-532) on the device: for every surviving feature match the
+ * current key-frame's map point is merged into the loop key-frame's (:521-525 move its observations and point their features at the loop point,
+ * :527 erases it with Map::RemoveMapPoint, src/map.cpp:144-155), and a feature without a point adopts the loop point (:529).  What this section
+ * does on the device: the PLAN of the walk (which point goes where), the moved ROWS (the back end's thirteen tables, the observation archive's
+ * segments and mirror), the erased states and the snapshot in the map archive, the front observers in list order, the features of EVERY key-frame that
+ * observed a merged point (loop store) and the tracker's landmarks.  A device-resident stream needs no host map for it.
+ * Order of one loop:  ... -> verify -> loop_inputs -> myslam_loop_correct_batch -> write_backend -> myslam_loop_relink_plan_batch ->
+ * myslam_relink_stage_batch -> myslam_relink_backend_batch -> myslam_map_relink_batch -> myslam_map_update_batch(MYSLAM_MAP_AFTER_RELINK) ->
+ * myslam_relink_obs_update_batch -> myslam_loop_store_set_links_batch (the moved rows' list, then the plan's) + myslam_tracker_relink_batch ->
+ * myslam_tracker_update_from_map_batch -> the next key-frame's prior_rows / insert; myslam_relink_first_kf_batch before the next myslam_loop_correct_batch.
+ * The re-link counts as the ONE back-end call between two updates.
+ * Every batch call is ONE launch, one workgroup per item, on its handle's stream: device pointers, nothing allocated or synchronised, no device
+ * memory read from the host, no global atomics, recordable between myslam_graph_begin / _end.  Per item everything is decided before anything is
+ * written: an item with an error keeps every byte of every table (the plan's own lists of it are empty); an item's bytes depend neither on its
+ * slot nor on its neighbours.
+ *
+ * myslam_relink_create — `map` is the map archive of the same streams (read through myslam_map_view for mp_state / n_mp; it must outlive this
+ * handle; max_batch at most its own), out_cap the matcher's and verifier's cap (<= 4096), feat_cap the stride of the feature tables (<= 65536);
+ * beyond those limits MYSLAM_ERR_CAPACITY.  The handle owns the lists of myslam_relink_view; nothing moves after create.
+ *
+ * myslam_loop_relink_plan_batch — per item: d_valid_pairs (batch x out_cap x 2: current feature, loop feature) and d_counts of
+ * myslam_loop_match_batch, d_outlier (batch x out_cap) of myslam_loop_verify_batch, d_correct_status = myslam_loop_correct_batch's d_status,
+ * d_cur_feat_landmark (batch x feat_cap, IN/OUT) the current key-frame's feature -> archive-slot table as myslam_map_feature_slots_batch wrote it with
+ * link upkeep applied, d_loop_feat_landmark (batch x feat_cap) after myslam_map_filter_landmarks_batch, d_cur_kf_id (batch i64) the current
+ * key-frame's mnKFId.  A status that is neither MYSLAM_LOOP_CORRECT_DONE nor MYSLAM_LOOP_CORRECT_FUSED_ONLY: MYSLAM_RELINK_SKIPPED, the lists are
+ * empty (the reference returns at :438-442 before LoopLocalFusion).  Otherwise the pairs with d_outlier == 0 are walked serially, in their order
+ * (_msetValidFeatureMatches after :423-428).  lock() of a slot is null for a slot < 0 or a point in state 2; states 0 and 1 are alive.
+ *   loop_mp = lock(d_loop_feat_landmark[lf]), followed through the merges this walk has made (the loop feature is an observation of its point and
+ *             moved with it); null: the pair is skipped (:514-517; a slot >= 0 in state 2 is counted as a dead loop point).
+ *   cur_mp  = lock(the current table's entry for cf) AS THE WALK HAS LEFT IT: an observation follows the merges of its point ((c, l1) then (c, l2)
+ *             merges L1 into L2); an adopted feature is no observation (:529 sets the pointer only), so when the point it adopted is merged
+ *             away later its entry is null again.
+ *   cur_mp null: ADOPT, the entry for cf becomes loop_mp.  cur_mp == loop_mp: skipped — a DECLARED DEVIATION (the reference would append a
+ *   point's observations to itself and erase it; chain.py and host/myslam_system.hpp skip as well).  Otherwise MERGE cur_mp -> loop_mp.
+ * After the walk every entry of the whole row of d_cur_feat_landmark (as myslam_map_filter_landmarks_batch, without a count) that names a merged
+ * point names the point its features ended on; values outside [0, n_mp) keep their bits.  Outputs (myslam_relink_view, valid until destroy):
+ *   merge / n_merge    max_batch x out_cap x 2 / max_batch i32   (from slot, to slot) in walk order
+ *   adopt / n_adopt    max_batch x out_cap x 2 / max_batch i32   (feature, slot) in walk order
+ *   target             max_batch x point_cap i32                 per archive slot below n_mp the slot its features end on (itself for a point
+ *                                                                that only received), -1 = untouched
+ *   link_kf_id / link_tag / link_slot / n_link   max_batch x feat_cap i64 / i32 / i32, max_batch i32   (d_cur_kf_id, feature, final slot; -1 = its
+ *                      point is gone) of every feature of the current key-frame whose entry the walk changed, in feature order: the lists of
+ *                      myslam_loop_store_set_links_batch and myslam_tracker_relink_batch
+ *   report             max_batch x MYSLAM_RELINK_REPORT_INTS i32: pairs walked, merges, adopts, same-point skips, dead loop points, links
+ * Slots from a count on keep their bytes.  MYSLAM_ERR_INVALID per item: d_counts outside [0, out_cap], n_mp outside [0, point_cap], a negative
+ * d_cur_kf_id, a feature id of a walked pair outside [0, feat_cap), a slot those pairs name (either table) outside [-1, n_mp) — all found before
+ * the first write; the item's lists are then empty and its target row -1.
+ * DECLARED DEVIATION, order: the plan runs after the corrector, the reference's loop runs between the fusion and the pose-graph step.  Positions
+ * are not touched here, so the only observable difference is a merge target without a single observation, which :623 asserts does not exist.
+ *
+ * myslam_map_relink_batch — Map::RemoveMapPoint (src/map.cpp:144-155, called at src/loopclosing.cpp:527) for a plan's merge list (d_merge /
+ * d_n_merge with stride merge_cap = the plan's out_cap, d_plan_status = the plan's d_status): every from-slot gets state 2 wherever the point
+ * was; targets keep their state, positions are not touched.  d_status: MYSLAM_MAP_UPDATED; MYSLAM_MAP_SKIPPED for a plan status other than
+ * MYSLAM_RELINK_DONE; MYSLAM_ERR_INVALID (every byte kept) for a count outside [0, merge_cap] or a slot outside [0, n_mp).  d_plan_status is the
+ * status of myslam_relink_backend_batch in the order above (0 = MYSLAM_RELINK_DONE: the rows moved), the plan's own where no rows are kept on the device.
+ *
+ * THE ROWS.  For each merge, in order, the reference appends GetObservations() of the merged point to the END of the target's list, in list order
+ * (:521-525; AddObservation alone: the target's active list does not change).  So the final list of a point that stands is its own rows, then for
+ * every merge into it, in order, the whole list the merged point had by then, and the OWN rows of every merged point stand at one place of one list.
+ * myslam_relink_stage_batch (obs_archive.hip; `oa` is read, nothing of it is written; before the merged points are erased) finds that place with two
+ * passes of one lane over the merge list and writes, into the plan's handle (myslam_relink_view, stage_cap rows per item): row_kf_id / row_uv /
+ * row_tag / row_flags = the own rows of every merged point, merge by merge, in list order — the mirror's rows for a point of the back end's table (all
+ * rows of its segment, with the observer's mnKFId and the OUTLIER bit), the stored segment for a point outside it (a chain merge) —, row_root_id /
+ * row_slot = mnId and archive slot of the point the row ends on, row_place = its index in that point's list; per merge merge_from_id, merge_root_id,
+ * merge_rows, merge_place.  (row_kf_id, row_tag, row_slot) with n_rows IS the link list of the moved rows for myslam_loop_store_set_links_batch: every
+ * moved row once, with its final slot.  d_status: MYSLAM_RELINK_DONE; MYSLAM_RELINK_SKIPPED for a plan status other than DONE; the archive's sticky
+ * error; MYSLAM_ERR_INVALID (a slot out of range, an erased point, a target that does not stand, an inconsistent mirror or segment);
+ * MYSLAM_ERR_CAPACITY when, and only when, the rows of the points alive and outside the table after the re-link would exceed row_cap, or the table's
+ * rows the back end's obs_cap, or the moved rows stage_cap — not sticky, nothing was written.
+ * myslam_relink_backend_batch (backend.hip, that handle's copy of the tables): d_stage_status != 0 -> d_status = that value, every byte kept, d_mp_new_row
+ * -1.  Else the merged points leave the map-point and observation tables with all their rows; a target in the table gets its rows at the end of its
+ * segment, each at row_place: ACTIVE cleared, OUTLIER kept, uv and tag bit for bit, d_obs_kf found by id in the key-frame table, -1 when absent
+ * (the rows with ACTIVE = 0 whose key-frame is in the window that myslam_backend_optimize_batch's section announces).  Both tables are compacted in
+ * their order, d_obs_mp renumbered, the counts stored; rows from a new count on keep their bytes; d_mp_new_row (batch x mp_cap) by INPUT row, -1 for a
+ * point that left.  MYSLAM_ERR_INVALID: the table checks of myslam_backend_optimize_batch, counts that are not the ones the rows were staged for, a
+ * place outside what its point receives; MYSLAM_ERR_CAPACITY: more rows than obs_cap.
+ * myslam_relink_obs_update_batch (after myslam_map_relink_batch and the map's update): d_backend_status != 0 or a skipped map update -> MYSLAM_MAP_SKIPPED.
+ * The mirror follows the table, the appended rows with their observers' ids; a target outside the table has its list written afresh (stored rows,
+ * then the moved ones) by update rule 6 (bump allocation, reclaim into the other pool in the same launch); the merged points' segments are dead rows.
+ * Errors are STICKY as in myslam_obs_archive_update_batch.  (It uses the plan handle's work_size column as scratch: the handle is not const.)
+ * myslam_relink_first_kf_batch: d_first_kf (batch x point_cap) with the meaning of myslam_map_loop_inputs_batch's output, but in LIST order: the archive
+ * row of the observer of the first row of the mirror's segment (a point of the table) or of the stored segment, -1 without a row, for an erased point
+ * and for an item with a sticky error.  A merged target's list is own rows ++ moved rows, and the moved rows may be of older key-frames: when its
+ * front is culled later (src/backend.cpp:236-247) front() is the next row in list order, not the lowest observer.
+ * LIMIT, adoptions across loops: whether a feature adopted its point (:529) is known within one walk only.  A feature that adopted a point in an
+ * EARLIER loop is treated as an observation of it afterwards: it follows a later merge of that point where the reference's pointer would go null.
+ *
+ * myslam_loop_store_set_links_batch — myslam_loop_store_clear_links_batch with a value: entry j (d_kf_id, d_tag, d_slot) of item b, with id >= 0,
+ * tag >= 0 and slot >= -1, sets that entry of the pending table or of the stored key-frame's table to d_slot, by exactly clear_links' lookup and
+ * ignore rules (src/loopclosing.cpp:524, :529 as ComputeCorrectPose, :218-237, sees them in a stored key-frame); d_n_set[b] (may be NULL) = the
+ * entries that named a stored or pending feature.  Call level as clear_links.
+ *
+ * myslam_tracker_relink_batch — item s = stream s = item s of `map`, lists strided by list_cap.  Guard and conditions of
+ * myslam_tracker_clear_links_batch: a stream is touched only when its ids are valid and ref_frame_id == next_frame_id - 1, and only by entries
+ * with d_kf_id == ref_kf_id and 0 <= tag < n_feat (src/loopclosing.cpp:524, :529 through src/keyframe.cpp:21).  slot -1: the feature loses its
+ * landmark.  Otherwise the landmark of feature `tag` takes the target's mnId (map mp_id), its position (mp_pos) and outlier flag = (mp_state == 1);
+ * a feature without a landmark gets the slot that already carries the target's id, else a new one at the end of the table.  next_mp_id and the
+ * other counters are untouched.  d_status (S): MYSLAM_OK; MYSLAM_ERR_INVALID for a naming entry with a slot outside [-1, n_mp);
+ * MYSLAM_ERR_CAPACITY when the landmark table is full — in both cases the stream keeps every byte.  d_n_relinked (S, may be NULL) = naming entries.
+ * (The walk runs on the key-frame turn's scratch columns, which a refused stream leaves overwritten; list_cap is the caller's stride, checked against nothing.)
+ * ------------------------------------------------------------------------------------------ */
+#define MYSLAM_RELINK_DONE 0
+#define MYSLAM_RELINK_SKIPPED 1
+#define MYSLAM_RELINK_REPORT_INTS 6
+typedef struct myslam_relink myslam_relink;
+typedef struct myslam_relink_lists {
+    int32_t* merge; int32_t* n_merge; int32_t* adopt; int32_t* n_adopt; int32_t* target;
+    int64_t* link_kf_id; int32_t* link_tag; int32_t* link_slot; int32_t* n_link; int32_t* report;
+    /* the moved rows, written by myslam_relink_stage_batch: max_batch x stage_cap */
+    int64_t* row_kf_id; float* row_uv; int32_t* row_tag; uint8_t* row_flags; int64_t* row_root_id; int32_t* row_slot; int32_t* row_place; int32_t* n_rows;
+    /* and per merge, max_batch x out_cap: the merged point's id, the id of the point its rows end on, its own rows, their place in that point's list */
+    int64_t* merge_from_id; int64_t* merge_root_id; int32_t* merge_rows; int32_t* merge_place; int32_t* n_staged_merges;
+    int32_t* table_mp; int32_t* table_rows;   /* max_batch: the back end's counts the rows were staged for */
+    int32_t* work_size;                       /* max_batch x point_cap: the stage's scratch */
+    int32_t max_batch, out_cap, feat_cap, point_cap, stage_cap;
+} myslam_relink_lists;
+int myslam_relink_create(myslam_relink** out, const myslam_map* map, int max_batch, int out_cap, int feat_cap, int stage_cap);
+int myslam_relink_destroy(myslam_relink* h);
+int myslam_relink_set_stream(myslam_relink* h, void* hip_stream);
+/* the device pointers and caps of the plan's outputs: valid until destroy */
+int myslam_relink_view(const myslam_relink* h, myslam_relink_lists* out);
+/* kernel launches one myslam_loop_relink_plan_batch enqueues (1) */
+int myslam_relink_launches_per_plan(const myslam_relink* h);
+/* src/loopclosing.cpp:509-532: which point is merged into which, which feature adopts, as described above */
+int myslam_loop_relink_plan_batch(myslam_relink* h, const int32_t* d_valid_pairs, const int32_t* d_counts, const uint8_t* d_outlier,
+                                  const int32_t* d_correct_status, int32_t* d_cur_feat_landmark, const int32_t* d_loop_feat_landmark,
+                                  const int64_t* d_cur_kf_id, int batch, int32_t* d_status);
+/* src/loopclosing.cpp:521-525: GetObservations() of every merged point, read from the observation archive, staged in the plan's handle */
+int myslam_relink_stage_batch(myslam_obs_archive* oa, myslam_relink* h, const int32_t* d_plan_status, int batch, int32_t* d_status);
+/* src/loopclosing.cpp:521-527 on the back end's tables: moved rows appended (AddObservation alone), merged points out (src/map.cpp:144-155) */
+int myslam_relink_backend_batch(myslam_backend* be, const myslam_relink* h, int64_t* d_kf_id, double* d_kf_pose, int32_t* d_n_kf, int64_t* d_mp_id,
+                                double* d_mp_pos, uint8_t* d_mp_outlier, int32_t* d_n_mp, int32_t* d_obs_mp, int32_t* d_obs_kf, uint8_t* d_obs_flags,
+                                float* d_obs_uv, int32_t* d_obs_tag, int32_t* d_n_obs, const int32_t* d_stage_status, int batch, int32_t* d_mp_new_row,
+                                int32_t* d_status);
+/* src/loopclosing.cpp:521-525 as the stored lists see them: the observation archive after the re-link, in the place of myslam_obs_archive_update_batch
+ * (which keeps its two modes): after myslam_map_update_batch
+ * (MYSLAM_MAP_AFTER_RELINK) of the same call; the tables and caps as there */
+int myslam_relink_obs_update_batch(myslam_obs_archive* oa, myslam_relink* h, const int64_t* d_kf_id, const int32_t* d_n_kf, const int64_t* d_mp_id,
+                                   const int32_t* d_n_mp, const int32_t* d_obs_mp, const int32_t* d_obs_kf, const uint8_t* d_obs_flags, const float* d_obs_uv,
+                                   const int32_t* d_obs_tag, const int32_t* d_n_obs, int be_kf_cap, int be_mp_cap, int be_obs_cap,
+                                   const int32_t* d_backend_status, const int32_t* d_map_status, int batch, int32_t* d_status);
+/* GetObservations().front()->mpKF of every map point in LIST order (src/loopclosing.cpp:625-629 after :521-525 appended rows out of key-frame order) */
+int myslam_relink_first_kf_batch(myslam_obs_archive* oa, int batch, int32_t* d_first_kf);
+/* src/loopclosing.cpp:527 with src/map.cpp:144-155: the merged points are erased */
+int myslam_map_relink_batch(myslam_map* h, const int32_t* d_merge, const int32_t* d_n_merge, int merge_cap, const int32_t* d_plan_status, int batch,
+                            int32_t* d_status);
+/* src/loopclosing.cpp:524 and :529 as src/loopclosing.cpp:218-237 sees them in a stored key-frame */
+int myslam_loop_store_set_links_batch(myslam_loop_store* h, const int64_t* d_kf_id, const int32_t* d_tag, const int32_t* d_slot, const int32_t* d_n,
+                                      int list_cap, int batch, const int64_t* d_pending_kf_id, int32_t* d_pending_feat_landmark, int32_t* d_n_set);
+/* src/loopclosing.cpp:524 and :529 as TrackLastFrame (src/frontend.cpp:127-171) sees them through src/keyframe.cpp:21 */
+int myslam_tracker_relink_batch(myslam_tracker* h, const int64_t* d_kf_id, const int32_t* d_tag, const int32_t* d_slot, const int32_t* d_n, int list_cap,
+                                const myslam_map* map, int32_t* d_n_relinked, int32_t* d_status);
 
 /* ------------------------------------------------------------------------------------------
  * Host-side formats of the reference's runner — plain host code, no device needed; the C++ forms live in
