@@ -557,6 +557,88 @@ class LoopQueryContext(_LoopQueries):
         self._h = C.c_void_p()
 
 
+LCDBANK_SCANNED, LCDBANK_GATED, LCDBANK_IDLE, LCDBANK_ADDED = 0, 1, 2, 3
+
+
+class LoopDatabaseBank:
+    """S loop databases in one device allocation (myslam_lcdbank_*), item s = stream s: the gate of src/loopclosing.cpp:62, DetectLoop's scan
+    (:126-143) and AddToDatabase (:651-659) per stream, with ids, counts and row limits on the device.  query / append / clear take device
+    pointers as ints, enqueue on the handle's stream and return (recordable, StepGraph); load / get / sizes are synchronous and take numpy arrays."""
+
+    def __init__(self, streams, rows_per_stream, stream=None):
+        self.streams, self.rows_per_stream = int(streams), int(rows_per_stream)
+        self._h = C.c_void_p()
+        _check(lib().myslam_lcdbank_create(C.byref(self._h), self.streams, self.rows_per_stream), "myslam_lcdbank_create")
+        if stream is not None:
+            self.set_stream(stream)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and self._h.value and _lib is not None:
+            _lib.myslam_lcdbank_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def set_stream(self, stream):
+        _check(lib().myslam_lcdbank_set_stream(self._h, C.c_void_p(stream)), "myslam_lcdbank_set_stream")
+
+    @staticmethod
+    def row_tile():
+        """rows of one stream that one workgroup of the scan owns"""
+        return lib().myslam_lcdbank_row_tile()
+
+    @staticmethod
+    def launches_per_query():
+        return lib().myslam_lcdbank_launches_per_query()
+
+    def query_batch(self, d_q, d_cur_id, d_active, d_best_id, d_max_score, d_cnt, d_best_row, d_status, thr_low=0.92, min_size=0):
+        """d_q S x 1064 f32, d_cur_id S u64, d_active S i32 or None -> S each: best id u64, max score f32, cnt i32 (LoopKeyFrameStore.detect_batch's
+        inputs), best row i32 (-1: nothing above 0), status i32 (LCDBANK_SCANNED / _GATED: n <= min_size / _IDLE)"""
+        vp = lambda p: C.c_void_p(p or None)
+        _check(lib().myslam_lcdbank_query_batch(self._h, vp(d_q), vp(d_cur_id), vp(d_active), C.c_float(thr_low), int(min_size), vp(d_best_id),
+                                                vp(d_max_score), vp(d_cnt), vp(d_best_row), vp(d_status)), "myslam_lcdbank_query_batch")
+
+    def append_batch(self, d_descr, d_id, d_add, d_status):
+        """d_descr S x 1064 f32, d_id S u64, d_add S i32 or None -> d_status S i32: LCDBANK_ADDED / _IDLE / ERR_CAPACITY (stream full) / ERR_INVALID
+        (id not above the last one held)"""
+        vp = lambda p: C.c_void_p(p or None)
+        _check(lib().myslam_lcdbank_append_batch(self._h, vp(d_descr), vp(d_id), vp(d_add), vp(d_status)), "myslam_lcdbank_append_batch")
+
+    def clear_batch(self, d_clear):
+        """d_clear S i32: the streams with a non-zero entry are empty afterwards"""
+        _check(lib().myslam_lcdbank_clear_batch(self._h, C.c_void_p(d_clear or None)), "myslam_lcdbank_clear_batch")
+
+    def view(self):
+        """device pointers as ints: rows (S x rows_per_stream x 1064 f32), ids (S x rows_per_stream u64), n (S i32)"""
+        r, i, n = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(lib().myslam_lcdbank_view(self._h, C.byref(r), C.byref(i), C.byref(n)), "myslam_lcdbank_view")
+        return r.value, i.value, n.value
+
+    def read_view(self):
+        """the whole allocation behind view() as numpy arrays (rows, ids, n), bytes behind the counts included; waits for nothing but its own copies"""
+        S, R = self.streams, self.rows_per_stream
+        out = (np.empty((S, R, LCD_DIM), np.float32), np.empty((S, R), np.uint64), np.empty(S, np.int32))
+        for ptr, a in zip(self.view(), out):
+            _check(lib().myslam_debug_peek(C.c_void_p(ptr), _p(a), a.nbytes), "myslam_debug_peek")
+        return out
+
+    def load(self, s, ids, rows):
+        """replaces stream s with len(ids) rows (host arrays); ids ascend strictly (MyslamError(INVALID)), at most rows_per_stream (CAPACITY)"""
+        ids = np.ascontiguousarray(ids, np.uint64); rows = np.ascontiguousarray(rows, np.float32).reshape(-1, LCD_DIM) if len(ids) else np.zeros((0, LCD_DIM), np.float32)
+        assert len(rows) == len(ids)
+        _check(lib().myslam_lcdbank_load(self._h, int(s), _p(ids) if len(ids) else None, _p(rows) if len(ids) else None, len(ids)), "myslam_lcdbank_load")
+
+    def get(self, s):
+        """(ids u64, rows f32) of stream s"""
+        ids = np.zeros(self.rows_per_stream, np.uint64); rows = np.zeros((self.rows_per_stream, LCD_DIM), np.float32)
+        n = C.c_int()
+        _check(lib().myslam_lcdbank_get(self._h, int(s), _p(ids), _p(rows), self.rows_per_stream, C.byref(n)), "myslam_lcdbank_get")
+        return ids[:n.value].copy(), rows[:n.value].copy()
+
+    def sizes(self):
+        n = np.zeros(self.streams, np.int32)
+        _check(lib().myslam_lcdbank_sizes(self._h, _p(n)), "myslam_lcdbank_sizes")
+        return n
+
+
 class StepGraph:
     """One batched step recorded into a HIP graph (myslam_graph_begin / _end) and replayed with one launch.
         g = StepGraph.record(origin_stream, [side streams...], body)      # body() issues the step's *_batch calls on those streams

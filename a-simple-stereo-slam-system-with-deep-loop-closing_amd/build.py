@@ -30,6 +30,7 @@ UNITS = {
     "match_tri.hip": EXACT + ["-mllvm", "-amdgpu-mfma-vgpr-form"],     # MFMA accumulators in VGPRs: the arg-max reads them directly
     "calc.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
     "lcddb.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],
+    "lcd_bank.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"],     # the loop database's flags: one rule for both scans
     "ba.hip": [],
     "lk.hip": EXACT,
     "pgo.hip": [],

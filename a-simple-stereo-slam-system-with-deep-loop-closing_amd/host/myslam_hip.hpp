@@ -7,6 +7,7 @@
 //   myslam::BFMatcherHamming::match                                 (cv::BFMatcher use at src/loopclosing.cpp:33,172)
 //   myslam::triangulation  include/myslam/algorithm.h:16-33        (stereo rig form)
 //   myslam::LoopDatabase   LoopClosing::DetectLoop / AddToDatabase  src/loopclosing.cpp:124-161, 651-659
+//   myslam::LoopDatabaseBank   the same per stream of a bank, ids and counts on the device   src/loopclosing.cpp:62, 126-143, 651-659
 //   myslam::LocalBA::{Build,Optimize,OptimizeActiveMap}  Backend::OptimizeActiveMap  src/backend.cpp:126-243
 //   myslam::PyrLKTracker::calcOpticalFlowPyrLK        cv::calcOpticalFlowPyrLK call sites        src/frontend.cpp:150-153, 358-361
 //   myslam::EstimateCurrentPose                       g2o stage of Frontend::EstimateCurrentPose src/frontend.cpp:176-276
@@ -236,6 +237,58 @@ class LoopDatabase {           // LoopClosing::_mvDatabase + DetectLoop + AddToD
    private:
     myslam_lcddb* h_ = nullptr;
     float th1_, th2_;
+};
+
+// S LoopDatabases in one device allocation, item s = stream s of a TrackerBank: each stream's _mvDatabase with its ids, row count and scan limits on the
+// device.  QueryBatch is the gate of LoopClosing::Run (src/loopclosing.cpp:62) and DetectLoop's scan (:126-143) per stream, and writes
+// LoopKeyFrameStore::DetectBatch's three inputs; AppendBatch is AddToDatabase (:651-659) for the streams the caller selects.  Device pointers; every
+// batch call enqueues on the handle's stream and returns, and can be recorded.  Load / Get / Sizes take host memory and wait.
+class LoopDatabaseBank {
+    myslam_lcdbank* h_ = nullptr;
+    int streams_, rowsPerStream_;
+public:
+    LoopDatabaseBank(int streams, int rowsPerStream, float thresLow = 0.92f, int databaseMinSize = 0)
+        : streams_(streams), rowsPerStream_(rowsPerStream), th2_(thresLow), minSize_(databaseMinSize) {
+        check(myslam_lcdbank_create(&h_, streams, rowsPerStream), "myslam_lcdbank_create");
+    }
+    ~LoopDatabaseBank() { if (h_) myslam_lcdbank_destroy(h_); }
+    LoopDatabaseBank(const LoopDatabaseBank&) = delete; LoopDatabaseBank& operator=(const LoopDatabaseBank&) = delete;
+    int streams() const { return streams_; }
+    int rowsPerStream() const { return rowsPerStream_; }
+    static int rowTile() { return myslam_lcdbank_row_tile(); }
+    static int launchesPerQuery() { return myslam_lcdbank_launches_per_query(); }
+    void SetStream(void* hipStream) { check(myslam_lcdbank_set_stream(h_, hipStream), "myslam_lcdbank_set_stream"); }
+    // status[s] = MYSLAM_LCDBANK_SCANNED / _GATED / _IDLE; d_active may be nullptr (every stream)
+    void QueryBatch(const float* d_descr, const uint64_t* d_curKFId, const int32_t* d_active, uint64_t* d_bestId, float* d_maxScore,
+                    int32_t* d_cntSuspected, int32_t* d_bestRow, int32_t* d_status) {
+        check(myslam_lcdbank_query_batch(h_, d_descr, d_curKFId, d_active, th2_, minSize_, d_bestId, d_maxScore, d_cntSuspected, d_bestRow, d_status),
+              "myslam_lcdbank_query_batch");
+    }
+    // status[s] = MYSLAM_LCDBANK_ADDED / _IDLE / MYSLAM_ERR_CAPACITY / MYSLAM_ERR_INVALID; d_add may be nullptr (every stream)
+    void AppendBatch(const float* d_descr, const uint64_t* d_kfId, const int32_t* d_add, int32_t* d_status) {
+        check(myslam_lcdbank_append_batch(h_, d_descr, d_kfId, d_add, d_status), "myslam_lcdbank_append_batch");
+    }
+    void ClearBatch(const int32_t* d_clear) { check(myslam_lcdbank_clear_batch(h_, d_clear), "myslam_lcdbank_clear_batch"); }
+    void View(const float** d_rows, const uint64_t** d_ids, const int32_t** d_n) const { check(myslam_lcdbank_view(h_, d_rows, d_ids, d_n), "myslam_lcdbank_view"); }
+    void Load(int stream, const std::vector<uint64_t>& ids, const std::vector<float>& rows) {
+        if (rows.size() != ids.size() * MYSLAM_LCD_DIM) throw std::runtime_error("LoopDatabaseBank::Load: rows and ids differ in length");
+        check(myslam_lcdbank_load(h_, stream, ids.data(), rows.data(), (int)ids.size()), "myslam_lcdbank_load");
+    }
+    void Get(int stream, std::vector<uint64_t>& ids, std::vector<float>& rows) {
+        ids.assign(rowsPerStream_, 0); rows.assign((size_t)rowsPerStream_ * MYSLAM_LCD_DIM, 0.f);
+        int n = 0;
+        check(myslam_lcdbank_get(h_, stream, ids.data(), rows.data(), rowsPerStream_, &n), "myslam_lcdbank_get");
+        ids.resize(n); rows.resize((size_t)n * MYSLAM_LCD_DIM);
+    }
+    std::vector<int32_t> Sizes() {
+        std::vector<int32_t> n(streams_);
+        check(myslam_lcdbank_sizes(h_, n.data()), "myslam_lcdbank_sizes");
+        return n;
+    }
+
+private:
+    float th2_;
+    int minSize_;
 };
 
 struct LocalBA {               // flat-array form of the graph Backend::OptimizeActiveMap builds (backend.cpp:139-206)

@@ -311,8 +311,9 @@ int myslam_loop_match_batch(
  *      copied.  Output slots from the counts on are left as they were.
  * A rejected item carries n_loop = 0: myslam_loop_match_batch answers MYSLAM_LOOP_MATCH_FEW_PAIRS for it, myslam_loop_verify_batch
  * MYSLAM_VERIFY_FEW_MATCHES and myslam_loop_correct_batch MYSLAM_LOOP_CORRECT_SKIPPED, so the chain needs no compaction between its stages.
- * The gate `_mvDatabase.size() > _mnDatabaseMinSize` (:62) stays with the caller (see thr_high = +inf above), as does AddToDatabase for the items
- * that end unconfirmed.
+ * The gate `_mvDatabase.size() > _mnDatabaseMinSize` (:62) and AddToDatabase for the items that end unconfirmed are on the device for a bank of
+ * streams: myslam_lcdbank_query_batch gates each stream by its own row count (a gated or idle item carries a score of 0 and ends NO_LOOP here) and
+ * myslam_lcdbank_append_batch adds the rows the caller selects.  With the single myslam_lcddb both stay with the caller (see thr_high = +inf above).
  *
  * Call level, nothing enqueued: NULL pointers (d_kf_status excepted), nq / batch / n / kf_capacity / cap / feat_cap <= 0 -> MYSLAM_ERR_INVALID;
  * cap > 16384, feat_cap > 65536 (myslam_loop_match_batch's limits) or nq > 65535 -> MYSLAM_ERR_CAPACITY; create out of device memory ->
@@ -547,6 +548,75 @@ int myslam_lcddb_ctx_query_batch_owned(myslam_lcddb_query_ctx* c, const float* d
 int myslam_lcd_merge_owned_candidates(const myslam_lcd_owned_candidate* gathered, int nshards, int nq, uint64_t* best_id, float* max_score, int32_t* cnt);
 int myslam_lcd_merge_owned_candidates_device(const myslam_lcd_owned_candidate* d_gathered, int nshards, int nq, uint64_t* d_best_id,
                                              float* d_max_score, int32_t* d_cnt, void* hip_stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Loop database bank — S loop databases in one device allocation, item s = stream s as in the tracker, the back end and the archives.  A bank of S
+ * streams is S reference Systems, so S LoopClosing::_mvDatabase maps (include/myslam/loopclosing.h:120) whose key-frame ids all start at 0
+ * (myslam_tracker's new_kf_id).  Per stream it replaces the gate of LoopClosingRun (src/loopclosing.cpp:62), the scan of DetectLoop (:126-143) and
+ * AddToDatabase (:651-659).
+ *
+ * Layout, fixed at create: rows [S][rows_per_stream][1064] f32, ids [S][rows_per_stream] u64 ascending per stream, count [S] i32 — all in device
+ * memory; nothing grows and nothing moves, so a recorded step (myslam_graph_begin / _end) that names the bank stays valid for ever and a replay sees
+ * the rows appended since the recording.  After create no call changes host state but set_stream.  query / append / clear enqueue on the handle's
+ * stream and return: they read no device memory from the host, allocate nothing, never synchronise and use no global atomics.  One stream of calls per
+ * bank (the query's scratch is the handle's).  load / get / sizes are the synchronous test and resume path: host pointers, they wait for the
+ * handle's stream (MYSLAM_ERR_UNSUPPORTED while it is being recorded).
+ *
+ * query_batch (d_q S x 1064, 16-byte aligned; d_cur_id S; d_active S or NULL = every item; outputs S each), per item s —
+ * LoopClosing::DetectLoop's loop, src/loopclosing.cpp:126-143, behind the gate at :62:
+ *   1. d_active[s] == 0: d_status[s] = MYSLAM_LCDBANK_IDLE, (d_best_id, d_max_score, d_cnt)[s] = (0, 0.0f, 0), d_best_row[s] = -1; d_q and
+ *      d_cur_id of the item are not read;
+ *   2. n[s] <= min_size: MYSLAM_LCDBANK_GATED with the same outputs (`_mvDatabase.size() > _mnDatabaseMinSize`, :62);
+ *   3. else MYSLAM_LCDBANK_SCANNED: rows 0 .. n[s]-1 of the stream in ascending order, ending at the first row with (cur - id) mod 2^64 < 20 (:133;
+ *      the window wraps for cur < 19); the maximum starts at 0 with best id 0 (:128-129), '>' is strict for the maximum (the lowest row wins ties)
+ *      and for cnt = #{score > thr_low}; NaN never wins and is never counted.  d_best_row[s] = the winning row's index inside its stream, -1 when
+ *      nothing scored above 0.
+ * The three outputs are myslam_loop_detect_batch's inputs: an idle or gated item carries a score of 0 and ends MYSLAM_LOOP_DETECT_NO_LOOP there.
+ * A score is an f32 sum whose order depends on the entry's place in its row only: the same row and query give the same bits in every stream and slot.
+ * At most myslam_lcdbank_launches_per_query() = 3 launches; a workgroup scans MYSLAM_LCDBANK_ROW_TILE rows of one stream (myslam_lcdbank_row_tile()).
+ *
+ * append_batch (d_descr S x 1064, d_id S, d_add S or NULL = every item), one launch, one workgroup per stream — AddToDatabase, :651-659:
+ *   d_add[s] == 0                               MYSLAM_LCDBANK_IDLE, nothing read or written but the status
+ *   the stream holds rows_per_stream rows       MYSLAM_ERR_CAPACITY, nothing stored
+ *   n[s] > 0 and d_id[s] <= the last id held    MYSLAM_ERR_INVALID, nothing stored (std::map order, as myslam_lcddb_append_batch's rule on the host)
+ *   otherwise                                   MYSLAM_LCDBANK_ADDED: row and id written at n[s], then n[s] incremented
+ * A query enqueued behind it on the same stream sees the row.
+ *
+ * clear_batch: n[s] = 0 where d_clear[s] != 0 (a stream that starts again, myslam_tracker_reset_stream, has an empty database).
+ * load replaces stream s: rows and ids below n and the count are written, bytes behind n are kept; ids must ascend strictly (MYSLAM_ERR_INVALID),
+ * n > rows_per_stream: MYSLAM_ERR_CAPACITY; the stream keeps every byte then.  get: *n = the count; more than cap: MYSLAM_ERR_CAPACITY, nothing copied
+ * (ids / rows may be NULL).
+ *
+ * Call level, nothing enqueued: NULL required pointers, a d_q that is not 16-byte aligned, sizes <= 0, a stream index out of range ->
+ * MYSLAM_ERR_INVALID; streams > 65535 or rows_per_stream > 2^24 -> MYSLAM_ERR_CAPACITY; create out of device memory -> MYSLAM_ERR_CAPACITY, any
+ * other HIP failure -> MYSLAM_ERR_HIP.
+ *
+ * Out of scope: a per-stream key-frame store (myslam_loop_store stays one map; d_best_row is the key a banked one would use), the decision of which
+ * items end unconfirmed (the caller's d_add), the five-key-frames rule of LoopClosing::InsertNewKeyFrame, the wiring into a bank of trackers, and
+ * sharding a bank over several GPUs.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct myslam_lcdbank myslam_lcdbank;
+#define MYSLAM_LCDBANK_SCANNED 0
+#define MYSLAM_LCDBANK_GATED   1
+#define MYSLAM_LCDBANK_IDLE    2
+#define MYSLAM_LCDBANK_ADDED   3
+#define MYSLAM_LCDBANK_ROW_TILE 32
+int myslam_lcdbank_create(myslam_lcdbank** out, int streams, int rows_per_stream);
+int myslam_lcdbank_destroy(myslam_lcdbank* h);
+int myslam_lcdbank_set_stream(myslam_lcdbank* h, void* hip_stream);
+int myslam_lcdbank_row_tile(void);
+int myslam_lcdbank_launches_per_query(void);
+int myslam_lcdbank_query_batch(myslam_lcdbank* h, const float* d_q /*S x 1064*/, const uint64_t* d_cur_id /*S*/, const int32_t* d_active /*S, NULL = all*/,
+        float thr_low, int min_size,
+        uint64_t* d_best_id, float* d_max_score, int32_t* d_cnt,     /* S each: myslam_loop_detect_batch's inputs */
+        int32_t* d_best_row, int32_t* d_status);                     /* S each */
+int myslam_lcdbank_append_batch(myslam_lcdbank* h, const float* d_descr /*S x 1064*/, const uint64_t* d_id /*S*/, const int32_t* d_add /*S, NULL = all*/,
+        int32_t* d_status);
+int myslam_lcdbank_clear_batch(myslam_lcdbank* h, const int32_t* d_clear /*S*/);
+int myslam_lcdbank_view(const myslam_lcdbank* h, const float** d_rows, const uint64_t** d_ids, const int32_t** d_n);
+int myslam_lcdbank_load(myslam_lcdbank* h, int s, const uint64_t* ids, const float* rows, int n);   /* host pointers, synchronous, replaces stream s */
+int myslam_lcdbank_get(myslam_lcdbank* h, int s, uint64_t* ids, float* rows, int cap, int* n);      /* host pointers, synchronous */
+int myslam_lcdbank_sizes(myslam_lcdbank* h, int32_t* n /*S, host*/);
 
 /* ------------------------------------------------------------------------------------------
  * Local BA linear-system build — replaces the per-edge work g2o does for
