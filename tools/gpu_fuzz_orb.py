@@ -6,7 +6,10 @@ import __graft_entry__ as g
 pkg = g.load_package(); api, synth = pkg.api, pkg.synth
 sys.path.insert(0, "oracle")
 from pyoracle import Oracle
+sys.path.insert(0, "tests")
+import orb_cases
 o = Oracle()
+corpus = [c.img for c in orb_cases.all_cases()]      # hand-made edge images (tests/orb_cases.py) under random parameters
 rng = np.random.default_rng(int(sys.argv[1]) if len(sys.argv) > 1 else 0)
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 40
 bad = 0
@@ -15,7 +18,9 @@ for it in range(N):
     nf = int(rng.choice([60, 200, 500, 1000, 2000])); nl = int(rng.choice([1, 3, 5, 8])); sf = float(rng.choice([1.1, 1.2, 1.2, 1.3]))
     u = rng.random()
     kind = "noise" if u < 0.2 else ("texture" if u < 0.55 else "sparse")
-    if kind == "sparse":      # a scene with few rectangles: a few % of FAST corners, the regime of the two-phase FAST path
+    if u > 0.9:
+        img = corpus[int(rng.integers(len(corpus)))]; h, w = img.shape; kind = "case"
+    elif kind == "sparse":      # a scene with few rectangles: a few % of FAST corners, the regime of the two-phase FAST path
         img = np.ascontiguousarray(synth.stereo_batch(1, stream_id=int(rng.integers(1000)), n_rect=int(rng.integers(20, 1500)), h=h, w=w)[0, 0])
     else:
         img = np.ascontiguousarray(synth.random_image(int(rng.integers(1 << 30)), h, w, kind))
