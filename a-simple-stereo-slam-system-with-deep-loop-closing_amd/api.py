@@ -1517,6 +1517,96 @@ class ObsArchive:
                                                          vp(d_n_prior), int(prior_cap), vp(d_status)), "myslam_obs_archive_prior_rows_batch")
 
 
+MAPPER_IDLE, MAPPER_STATUS_WORDS = 3, 8                 # MYSLAM_MAPPER_*
+MAPPER_STAGES = ("prior_rows", "insert", "map_after_insert", "obs_after_insert", "optimize", "map_after_optimize", "obs_after_optimize")
+BE_TABLES = ("kf_id", "kf_pose", "n_kf", "mp_id", "mp_pos", "mp_outlier", "n_mp", "obs_mp", "obs_kf", "obs_flags", "obs_uv", "obs_tag", "n_obs")
+
+
+class MapperTables(C.Structure):                       # myslam_mapper_tables
+    _fields_ = [(n, C.c_void_p) for n in BE_TABLES + ("prior_mp_id", "prior_kf_id", "prior_uv", "prior_tag", "prior_flags", "n_prior", "feat_row",
+                                                      "mp_new_row", "removed_kf_id", "removed_kf_row", "dis", "obs_report", "mp_report", "new_outlier_mp",
+                                                      "n_new_outlier_mp", "obs_chi2", "rounds", "n_outlier_edges", "n_cleared", "gate", "fault")] + \
+               [("stage_status", C.c_void_p * 7)] + [(n, C.c_void_p) for n in ("backend", "map", "obs")] + \
+               [(n, C.c_int32) for n in ("streams", "kf_cap", "mp_cap", "obs_cap", "feat_cap", "prior_cap")]
+
+
+class _Borrowed:
+    """a handle the Mapper owns, seen through the class of its unit: same methods, never destroyed from here"""
+
+    def __del__(self):
+        pass
+
+
+class Mapper:
+    """The Backend thread's work for a bank of `streams` streams behind one handle (myslam_mapper_*): Backend::ProcessNewKeyFrame + OptimizeActiveMap
+    (src/backend.cpp:82-121, :126-266) and Map::InsertKeyFrame (src/map.cpp:17-48) for exactly the streams that made a key-frame in the turn or
+    StereoInit whose outputs the call is given; the decision is taken on the device.  The handle owns a Backend, a MapArchive (solve attached) and an
+    ObsArchive (`.backend`, `.map`, `.obs`: borrowed views with their classes' methods), the back end's 13 tables and every array between the stages.
+    keyframe_batch takes device pointers, enqueues launches_per_call() launches on the handle's stream and returns."""
+
+    def __init__(self, streams, kf_cap, mp_cap, obs_cap, feat_cap, archive_kf_cap, archive_edge_cap, archive_point_cap, obs_row_cap, prior_cap, stream=None):
+        self.streams = int(streams)
+        self._h = C.c_void_p()
+        _check(lib().myslam_mapper_create(C.byref(self._h), self.streams, int(kf_cap), int(mp_cap), int(obs_cap), int(feat_cap), int(archive_kf_cap),
+                                          int(archive_edge_cap), int(archive_point_cap), int(obs_row_cap), int(prior_cap)), "myslam_mapper_create")
+        if stream is not None:
+            self.set_stream(stream)
+        t = self.view()
+        self.kf_cap, self.mp_cap, self.obs_cap, self.feat_cap, self.prior_cap = t.kf_cap, t.mp_cap, t.obs_cap, t.feat_cap, t.prior_cap
+
+        def borrow(cls, handle, **attrs):
+            o = object.__new__(type("Borrowed" + cls.__name__, (_Borrowed, cls), {}))
+            o._h = C.c_void_p(handle)
+            o.__dict__.update(attrs)
+            return o
+        self.backend = borrow(Backend, t.backend, max_batch=self.streams, kf_cap=t.kf_cap, mp_cap=t.mp_cap, obs_cap=t.obs_cap)
+        self.map = borrow(MapArchive, t.map, max_batch=self.streams, kf_cap=int(archive_kf_cap), edge_cap=int(archive_edge_cap),
+                          point_cap=int(archive_point_cap), backend_mp_cap=t.mp_cap)
+        self.obs = borrow(ObsArchive, t.obs, map=self.map, max_batch=self.streams, be_obs_cap=t.obs_cap, row_cap=int(obs_row_cap), be_mp_cap=t.mp_cap)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and self._h.value and _lib is not None:
+            lib().myslam_mapper_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def set_stream(self, stream):
+        """the handle's stream, and that of the three owned handles"""
+        _check(lib().myslam_mapper_set_stream(self._h, C.c_void_p(stream)), "myslam_mapper_set_stream")
+
+    def launches_per_call(self, with_tracker=True):
+        return lib().myslam_mapper_launches_per_call(self._h, int(bool(with_tracker)))
+
+    def view(self):
+        """MapperTables: the device pointers (ints or None), caps and owned handles"""
+        t = MapperTables()
+        _check(lib().myslam_mapper_view(self._h, C.byref(t)), "myslam_mapper_view")
+        return t
+
+    def keyframe_batch(self, trk, outs, window, K, d_status, min_dis_th=0.2, delta=5.991, chi2_th=5.991, rounds=5, iters=10):
+        """outs: the dict of device pointers a turn or an init wrote (Tracker.TURN_OUTPUTS; StreamBank._turn_buffers builds it), trk the Tracker of the same
+        streams or None, window = Map.activeMap.size, K = (fx, fy, cx, cy), d_status streams x MAPPER_STATUS_WORDS i32.  Asynchronous, recordable."""
+        o = [C.c_void_p(outs.get(k) or None) for k in Tracker.TURN_OUTPUTS]
+        _check(lib().myslam_mapper_keyframe_batch(self._h, trk._h if trk is not None else None, *o, int(window), C.c_double(min_dis_th), C.c_double(K[0]),
+                                                  C.c_double(K[1]), C.c_double(K[2]), C.c_double(K[3]), C.c_double(delta), C.c_double(chi2_th), int(rounds),
+                                                  int(iters), C.c_void_p(d_status or None)), "myslam_mapper_keyframe_batch")
+
+    def status(self, d_status):
+        """the status words of the last call as a (streams, MAPPER_STATUS_WORDS) array (synchronises): [:, 0] overall, [:, 1:] MAPPER_STAGES"""
+        out = np.zeros((self.streams, MAPPER_STATUS_WORDS), np.int32)
+        _check(lib().myslam_debug_peek(C.c_void_p(d_status), _p(out), out.nbytes), "myslam_debug_peek")
+        return out
+
+    def reset_item(self, s):
+        """host call, synchronous: stream s's tables, map-archive item and observation-archive item empty, its sticky fault cleared"""
+        _check(lib().myslam_mapper_reset_item(self._h, int(s)), "myslam_mapper_reset_item")
+
+    def get(self, s):
+        """stream s's whole map from the owned archive (synchronises): key-frame ids and poses, map-point ids, positions and states (0 alive, 1 listed
+        as an outlier, 2 erased)"""
+        a = self.map.get(s)
+        return {k: a[k] for k in ("kf_id", "kf_pose", "mp_id", "mp_pos", "mp_state")}
+
+
 RELINK_DONE, RELINK_SKIPPED, RELINK_REPORT_INTS = 0, 1, 6      # MYSLAM_RELINK_*
 
 

@@ -41,6 +41,7 @@ UNITS = {
     "map_archive.hip": EXACT,              # the odometry edge's measurement is the hosts' f64 arithmetic, operation by operation
     "obs_archive.hip": [],                 # integer code and copies
     "relink.hip": [],                      # integer code and copies
+    "mapper.hip": [],                      # the gate and the status words: integers; every stage is its own unit's kernel
     "prof.hip": [],
     "io.hip": [],
     "graph.hip": [],

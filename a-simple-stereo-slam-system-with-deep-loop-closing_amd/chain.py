@@ -772,6 +772,7 @@ class StreamBank:
     brings the S result records back, and only a stream whose record says needs_host (key-frame by the reference's rule or kf_every, or
     LOST) takes the existing Chain methods (detect_features ... insert_keyframe, back end, loop closer) between get_frame and set_frame.
     Stereo initialisation stays on Chain.grab() unless self.device_init is set: then every INITING stream starts on the device (device_init_turn).
+    With device_map (and device_turns, device_init) the back end's work stays on the device too (api.Mapper): see advance() and map_of().
     Device buffers are torch tensors (plumbing only).  Chain itself is the one-camera form."""
 
     device_init = False                                               # advance(): INITING streams take StereoInit through device_init_turn
@@ -1008,11 +1009,102 @@ class StreamBank:
         outl = np.array([post["lm"][j] < 0 for j, l in enumerate(kept) if not pre["lm_outlier"][l]], bool)
         c.rec("pose_only", rec["pose7"], outl, np.array([int(rec["n_inliers"])]))
 
+    # -- device_map: the Backend thread's work for the bank behind api.Mapper (myslam_mapper_*) ------------------------------------------------
+    device_map = False      # with device_turns and device_init: the map of every stream lives on the device, the chains keep no objects
+    map_caps = None         # overrides of _mapper()'s caps, by the names of api.Mapper's arguments
+
+    def _mapper(self):
+        if getattr(self, "mapper", None) is None:
+            c0, S, cap = self.chains[0], len(self.chains), self.trk.cap
+            if any(c.window != c0.window or c.K != c0.K or c.n_init_good != c0.n_init_good for c in self.chains):
+                raise ValueError("the streams of a bank with device_map share Map.activeMap.size, the camera and numFeatures.initGood")
+            if c0.window + 1 > self.api.BA_MAX_WINDOW_POSES:
+                raise ValueError("Map.activeMap.size + 1 key-frames do not fit the back end's window")
+            caps = dict(kf_cap=c0.window + 1, mp_cap=4 * cap, obs_cap=(c0.window + 1) * cap, feat_cap=cap, archive_kf_cap=512, archive_edge_cap=512,
+                        archive_point_cap=16 * cap, obs_row_cap=16 * cap, prior_cap=cap)
+            caps.update(self.map_caps or {})
+            self.mapper = self.api.Mapper(S, **caps)
+            z = lambda: self.torch.zeros((S, self.api.MAPPER_STATUS_WORDS), dtype=self.torch.int32, device="cuda")
+            self.d_map_status = {"init": z(), "turn": z()}
+            self.stopped = [None] * S                                     # why a stream stopped: "LOST", or the error it met
+            self.map_status = []                                          # (frame, "init" / "turn", the S x 8 status words) of every mapper call
+        return self.mapper
+
+    def _enqueue_map(self, which):
+        """the mapper call on the output set enqueue_init / enqueue_turn has just written, then the ONE download of it: the S x 8 status words"""
+        c0 = self.chains[0]
+        self.mapper.keyframe_batch(self.trk, {k: v.data_ptr() for k, v in self.turn_buf.items()}, c0.window, c0.Kt, self.d_map_status[which].data_ptr())
+        words = self.d_map_status[which].cpu().numpy()
+        self.map_status.append((self.t, which, words.copy()))
+        return words
+
+    def map_of(self, s):
+        """stream s's whole map, read from the mapper's archive: kf_id, kf_pose, mp_id, mp_pos, mp_state (0 alive, 1 listed as an outlier, 2 erased)"""
+        return self._mapper().get(s)
+
+    def _advance_mapped(self, t):
+        """advance() with device_map: step -> records; init -> mapper -> status words; turn -> mapper -> status words.  No key-frame is downloaded,
+        no stream is handed over; c.poses, c.status, c.next_frame_id and c.kf_frames follow the records and the status words (a key-frame's entry
+        of c.poses is the tracker's estimate, the record's pose7: the pose the optimise leaves is in map_of(s))."""
+        self._mapper()
+        self.upload(t)
+        S, idle = len(self.chains), self.api.MAPPER_IDLE
+        if getattr(self, "armed", None) is None:
+            self.armed = [False] * S
+        stepped = [s for s in range(S) if self.on_device[s] and self.stopped[s] is None]
+        turns = []
+        if stepped:
+            self.step()
+            res = self.results()
+            for s in stepped:
+                c, rec = self.chains[s], res[s]
+                c.status, c.next_frame_id = int(rec["status"]), int(rec["frame_id"]) + 1
+                c.poses.append(rec["pose7"].copy())
+                if c.status < 0:
+                    self.stopped[s] = "tracker tables too small (%d)" % c.status
+                elif c.status == LOST:                                    # the reference quits (src/frontend.cpp:64-68)
+                    self.stopped[s] = "LOST"
+                elif rec["needs_host"]:
+                    turns.append((s, int(rec["frame_id"])))
+        inits = [s for s, c in enumerate(self.chains) if not self.on_device[s] and self.stopped[s] is None and c.status == INITING]
+        if inits:
+            for s in inits:
+                c = self.chains[s]
+                if not self.armed[s]:
+                    self.trk.reset_stream(s, c.next_frame_id, c.next_kf_id, c.next_mp_id, max(int(c.kf_every), 0))
+                    self.armed[s] = True
+            self.enqueue_init()
+            words = self._enqueue_map("init")
+            for s in inits:
+                c = self.chains[s]
+                frame_id = c.next_frame_id
+                c.next_frame_id += 1                                      # the Frame was constructed, StereoInit or retry
+                c.poses.append(IDENT.copy())
+                if words[s, 0] == 0:
+                    c.kf_frames.append(frame_id)
+                    c.status, self.on_device[s], self.armed[s] = TRACKING_GOOD, True, False
+                elif words[s, 0] != idle:
+                    self.stopped[s] = "mapper status %d" % words[s, 0]
+        if turns:
+            self.enqueue_turn()
+            words = self._enqueue_map("turn")
+            for s, frame_id in turns:
+                if words[s, 0] == 0:
+                    self.chains[s].kf_frames.append(frame_id)
+                else:                                                     # the turn was refused (capacity: the stream stays frozen), or the map faulted
+                    self.stopped[s] = "no key-frame turn" if words[s, 0] == idle else "mapper status %d" % words[s, 0]
+        return [s for s, c in enumerate(self.chains) if self.stopped[s] is None and c.status in (INITING, TRACKING_GOOD, TRACKING_BAD)]
+
     def advance(self, t):
         """one frame of every stream; returns the streams that are still tracking.  self.device_turns (default False): frozen streams take their
         key-frame turn through device_turn instead of host_turn.  self.device_init (default False): INITING streams start through
         device_init_turn (one masks -> detect_batch -> init_batch -> download for all of them) instead of Chain.grab() + hand_off, handed over
-        again afterwards unless self.resync_init is False"""
+        again afterwards unless self.resync_init is False.  self.device_map (default False) with both of them: the key-frames never leave the
+        device (_advance_mapped): no adopt_keyframe, hand_off, host_turn or Chain.backend_new_keyframe; bank.map_of(s) reads the maps"""
+        if self.device_map:
+            if not (getattr(self, "device_turns", False) and self.device_init):
+                raise ValueError("device_map needs device_turns and device_init")
+            return self._advance_mapped(t)
         self.upload(t)
         stepped = [s for s, c in enumerate(self.chains) if self.on_device[s]]
         logged = {s: self.trk.get_frame(s) for s in stepped if self.chains[s].keep_log}       # (a logging chain pays two more downloads per frame)

@@ -131,10 +131,15 @@ __device__ __forceinline__ bool be_tables_bad(const TablesItem& tb, int nk, int 
     return bad;
 }
 
-__global__ __launch_bounds__(BE_NT) void k_backend_flatten(BeTables T, BeWork W) {
+// gate (NULL = every item runs): an item whose entry is not 0 leaves with MYSLAM_MAPPER_IDLE before any of its tables is read (mapper.hip)
+__global__ __launch_bounds__(BE_NT) void k_backend_flatten(BeTables T, BeWork W, const int32_t* gate) {
     __shared__ int s_w[BE_NW];
     __shared__ int s_bad;
     const int b = blockIdx.x, t = threadIdx.x;
+    if (gate && gate[b] != 0) {                                             // uniform: the solve skips on W.st, the write-back zeroes the reports
+        if (t == 0) { W.st[b] = MYSLAM_MAPPER_IDLE; int32_t* const sz = W.sizes + 3 * (size_t)b; sz[0] = 0; sz[1] = 0; sz[2] = 0; }
+        return;
+    }
     const int nk = T.n_kf[b], nm = T.n_mp[b], no = T.n_obs[b];
     const auto w = W.item(b, T.kf_cap, T.mp_cap, T.obs_cap);
     auto refuse = [&](int st) {                                             // nothing to solve: the item's final status, an empty window
@@ -295,7 +300,8 @@ __global__ __launch_bounds__(BE_NT) void k_backend_write_back(BeTables T, BeWork
 //   merged map-point row  = rows of the table below the id + distinct new ids below it
 //   merged observation row = the segment's old position + feature rows of smaller ids + prior rows that entered before it
 // minus what RemoveOldActiveMapPoints takes out below it.  The rank sort of the features is quadratic in their number (a key-frame has hundreds).
-__global__ __launch_bounds__(BE_NT) void k_backend_insert(InsTables T, InsIn I, InsWork W, InsOut O) {
+// gate: as k_backend_flatten's
+__global__ __launch_bounds__(BE_NT) void k_backend_insert(InsTables T, InsIn I, InsWork W, InsOut O, const int32_t* gate) {
     __shared__ int s_w[BE_NW];
     __shared__ int s_bad, s_victim;
     __shared__ long long s_kfid[MYSLAM_BA_MAX_WINDOW_POSES + 1];
@@ -311,6 +317,7 @@ __global__ __launch_bounds__(BE_NT) void k_backend_insert(InsTables T, InsIn I, 
         if (t < T.kf_cap) o.dis[t] = -1.0;
         if (t == 0) { O.removed_kf_id[b] = -1; O.removed_kf_row[b] = -1; O.status[b] = st; }
     };
+    if (gate && gate[b] != 0) { refuse(MYSLAM_MAPPER_IDLE); return; }      // uniform: only the counts were read
     if (nk < 0 || nk > T.kf_cap || nm < 0 || nm > T.mp_cap || no < 0 || no > T.obs_cap || nf < 0 || nf > I.feat_cap || np < 0 || np > I.prior_cap ||
         nx < 0 || nx > I.outlier_cap || I.window < 1) {                     // uniform
         refuse(MYSLAM_ERR_INVALID);
@@ -702,6 +709,19 @@ int myslam_backend_optimize_batch(myslam_backend* h, const int64_t* d_kf_id, dou
                                   double chi2_th, int max_rounds, int iters_per_round, uint8_t* d_obs_report, uint8_t* d_mp_report,
                                   int32_t* d_new_outlier_mp, int32_t* d_n_new_outlier_mp, double* d_obs_chi2, int32_t* d_rounds,
                                   int32_t* d_n_outlier_edges, int32_t* d_status) {
+    return backend_optimize_launch(h, d_kf_id, d_kf_pose, d_n_kf, d_mp_id, d_mp_pos, d_mp_outlier, d_n_mp, d_obs_mp, d_obs_kf, d_obs_flags, d_obs_uv, d_obs_tag,
+                                   d_n_obs, batch, fx, fy, cx, cy, huber_delta, chi2_th, max_rounds, iters_per_round, d_obs_report, d_mp_report,
+                                   d_new_outlier_mp, d_n_new_outlier_mp, d_obs_chi2, d_rounds, d_n_outlier_edges, d_status, nullptr);
+}
+
+}  // extern "C"
+
+int myslam_hip::backend_optimize_launch(myslam_backend* h, const int64_t* d_kf_id, double* d_kf_pose, const int32_t* d_n_kf, int64_t* d_mp_id, double* d_mp_pos,
+                                        uint8_t* d_mp_outlier, int32_t* d_n_mp, int32_t* d_obs_mp, int32_t* d_obs_kf, uint8_t* d_obs_flags, float* d_obs_uv,
+                                        int32_t* d_obs_tag, int32_t* d_n_obs, int batch, double fx, double fy, double cx, double cy, double huber_delta,
+                                        double chi2_th, int max_rounds, int iters_per_round, uint8_t* d_obs_report, uint8_t* d_mp_report,
+                                        int32_t* d_new_outlier_mp, int32_t* d_n_new_outlier_mp, double* d_obs_chi2, int32_t* d_rounds,
+                                        int32_t* d_n_outlier_edges, int32_t* d_status, const int32_t* d_gate) {
     if (!h || batch < 0 || max_rounds < 1 || iters_per_round < 1) return MYSLAM_ERR_INVALID;
     if (batch > h->max_batch) return MYSLAM_ERR_CAPACITY;
     if (batch == 0) return MYSLAM_OK;
@@ -714,7 +734,7 @@ int myslam_backend_optimize_batch(myslam_backend* h, const int64_t* d_kf_id, dou
     const BeWork& W = h->w;
     const BeOut O{d_obs_report, d_mp_report, d_new_outlier_mp, d_n_new_outlier_mp, d_obs_chi2, d_rounds, d_n_outlier_edges, d_status,
                   h->culled_kf_id, h->culled_tag, h->n_culled};
-    hipLaunchKernelGGL(k_backend_flatten, dim3(batch), dim3(BE_NT), 0, h->stream, T, W);
+    hipLaunchKernelGGL(k_backend_flatten, dim3(batch), dim3(BE_NT), 0, h->stream, T, W, d_gate);
     MYSLAM_HIP_CHECK(hipGetLastError());
     const int rc = ba_active_map_launch(W.poses, W.pts, W.ep, W.el, W.obs, W.fixed, W.sizes, W.st, batch, h->kf_cap, h->mp_cap, h->obs_cap, fx, fy, cx, cy,
                                         huber_delta, chi2_th, max_rounds, iters_per_round, h->scratch, h->wstride, W.chi2, W.out, W.rounds, W.nout,
@@ -724,6 +744,8 @@ int myslam_backend_optimize_batch(myslam_backend* h, const int64_t* d_kf_id, dou
     MYSLAM_HIP_CHECK(hipGetLastError());
     return MYSLAM_OK;
 }
+
+extern "C" {
 
 int myslam_backend_insert_launches_per_call(const myslam_backend* h) { return h ? 1 : MYSLAM_ERR_INVALID; }
 
@@ -736,6 +758,23 @@ int myslam_backend_insert_keyframe_batch(myslam_backend* h, int64_t* d_kf_id, do
                                          const int32_t* d_n_prior, int prior_cap, const int64_t* d_outlier_mp_id, const int32_t* d_n_outlier_mp,
                                          int outlier_cap, int batch, int window, double min_dis_th, int32_t* d_feat_row, int32_t* d_mp_new_row,
                                          int64_t* d_removed_kf_id, int32_t* d_removed_kf_row, double* d_dis, int32_t* d_status) {
+    return backend_insert_launch(h, d_kf_id, d_kf_pose, d_n_kf, d_mp_id, d_mp_pos, d_mp_outlier, d_n_mp, d_obs_mp, d_obs_kf, d_obs_flags, d_obs_uv, d_obs_tag, d_n_obs,
+                                 d_new_kf_id, d_new_kf_pose, d_feat_mp_id, d_feat_mp_pos, d_feat_uv, d_feat_tag, d_feat_flags, d_n_feat, feat_cap, d_prior_mp_id,
+                                 d_prior_kf_id, d_prior_uv, d_prior_tag, d_prior_flags, d_n_prior, prior_cap, d_outlier_mp_id, d_n_outlier_mp, outlier_cap, batch,
+                                 window, min_dis_th, d_feat_row, d_mp_new_row, d_removed_kf_id, d_removed_kf_row, d_dis, d_status, nullptr);
+}
+
+}  // extern "C"
+
+int myslam_hip::backend_insert_launch(myslam_backend* h, int64_t* d_kf_id, double* d_kf_pose, int32_t* d_n_kf, int64_t* d_mp_id, double* d_mp_pos,
+                                         uint8_t* d_mp_outlier, int32_t* d_n_mp, int32_t* d_obs_mp, int32_t* d_obs_kf, uint8_t* d_obs_flags,
+                                         float* d_obs_uv, int32_t* d_obs_tag, int32_t* d_n_obs, const int64_t* d_new_kf_id, const double* d_new_kf_pose,
+                                         const int64_t* d_feat_mp_id, const double* d_feat_mp_pos, const float* d_feat_uv, const int32_t* d_feat_tag,
+                                         const uint8_t* d_feat_flags, const int32_t* d_n_feat, int feat_cap, const int64_t* d_prior_mp_id,
+                                         const int64_t* d_prior_kf_id, const float* d_prior_uv, const int32_t* d_prior_tag, const uint8_t* d_prior_flags,
+                                         const int32_t* d_n_prior, int prior_cap, const int64_t* d_outlier_mp_id, const int32_t* d_n_outlier_mp,
+                                         int outlier_cap, int batch, int window, double min_dis_th, int32_t* d_feat_row, int32_t* d_mp_new_row,
+                                         int64_t* d_removed_kf_id, int32_t* d_removed_kf_row, double* d_dis, int32_t* d_status, const int32_t* d_gate) {
     if (!h || batch < 0 || feat_cap < 0) return MYSLAM_ERR_INVALID;
     if (!d_kf_id || !d_kf_pose || !d_n_kf || !d_mp_id || !d_mp_pos || !d_mp_outlier || !d_n_mp || !d_obs_mp || !d_obs_kf || !d_obs_flags || !d_obs_uv ||
         !d_obs_tag || !d_n_obs || !d_new_kf_id || !d_new_kf_pose || !d_feat_mp_id || !d_feat_mp_pos || !d_feat_uv || !d_feat_tag || !d_feat_flags ||
@@ -752,10 +791,12 @@ int myslam_backend_insert_keyframe_batch(myslam_backend* h, int64_t* d_kf_id, do
                   d_prior_mp_id, d_prior_kf_id, d_prior_uv, d_prior_tag, d_prior_flags, d_n_prior, d_n_prior ? prior_cap : 0,
                   d_outlier_mp_id, d_n_outlier_mp, d_n_outlier_mp ? outlier_cap : 0, window, min_dis_th};
     const InsOut O{d_feat_row, d_mp_new_row, d_removed_kf_id, d_removed_kf_row, d_dis, d_status};
-    hipLaunchKernelGGL(k_backend_insert, dim3(batch), dim3(BE_NT), 0, h->stream, T, I, h->iw, O);
+    hipLaunchKernelGGL(k_backend_insert, dim3(batch), dim3(BE_NT), 0, h->stream, T, I, h->iw, O, d_gate);
     MYSLAM_HIP_CHECK(hipGetLastError());
     return MYSLAM_OK;
 }
+
+extern "C" {
 
 // device -> host, complete on return; on this thread's non-blocking stream, never the legacy stream (common.h).  The caller has waited for h->stream.
 static int be_fetch(void* dst, const void* src, size_t bytes) {

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "dev_tables.h"
+#include "backend_launch.h"
 #include "frontend_launch.h"
 #include "se3_chain.h"
 #include "tri_solve.h"
@@ -477,10 +478,11 @@ __global__ __launch_bounds__(TRK_NT) void k_kf_tail(TrkArgs a, KfArgs k) {
 
 // ---- the map moved under the tracker (back end, loop closer): landmarks and the reference pose follow their ids ----
 // (g: dev_tables.h's view of the back end's tables; the observation columns are not given)
-__global__ __launch_bounds__(TRK_NT) void k_kf_update(TrkArgs a, BeTablesRead g) {
+// (gate, NULL = none: a stream whose entry is not 0 keeps every byte — the mapper's idle items, backend_launch.h)
+__global__ __launch_bounds__(TRK_NT) void k_kf_update(TrkArgs a, BeTablesRead g, const int32_t* gate) {
     const int s = blockIdx.x, t = threadIdx.x;
     TrkState& st = a.st[s];
-    if (st.frozen != 0 || st.idsValid == 0) return;
+    if (st.frozen != 0 || st.idsValid == 0 || (gate && gate[s] != 0)) return;
     const size_t lb = (size_t)s * a.lmCap;
     const int nMp = clamped_count(g.n_mp, s, g.mp_cap), nKf = clamped_count(g.n_kf, s, g.kf_cap);
     const auto m = g.item(s);
@@ -1100,12 +1102,24 @@ int myslam_tracker_debug_freeze(myslam_tracker* h, int s, int why) {
 
 int myslam_tracker_update_from_map_batch(myslam_tracker* h, const int64_t* d_kf_id, const double* d_kf_pose, const int32_t* d_n_kf, int kf_cap,
                                          const int64_t* d_mp_id, const double* d_mp_pos, const uint8_t* d_mp_outlier, const int32_t* d_n_mp, int mp_cap) {
+    return tracker_update_from_map_launch(h, d_kf_id, d_kf_pose, d_n_kf, kf_cap, d_mp_id, d_mp_pos, d_mp_outlier, d_n_mp, mp_cap, nullptr);
+}
+
+}  // extern "C"
+
+void myslam_hip::tracker_shape(const myslam_tracker* h, hipStream_t* stream, int* streams, int* cap) { *stream = h->stream; *streams = h->S; *cap = h->cap; }
+
+int myslam_hip::tracker_update_from_map_launch(myslam_tracker* h, const int64_t* d_kf_id, const double* d_kf_pose, const int32_t* d_n_kf, int kf_cap,
+                                               const int64_t* d_mp_id, const double* d_mp_pos, const uint8_t* d_mp_outlier, const int32_t* d_n_mp, int mp_cap,
+                                               const int32_t* d_gate) {
     if (!h || !d_kf_id || !d_kf_pose || !d_n_kf || kf_cap < 1 || !d_mp_id || !d_mp_pos || !d_mp_outlier || !d_n_mp || mp_cap < 1) return MYSLAM_ERR_INVALID;
     const BeTablesRead g{d_kf_id, d_kf_pose, d_n_kf, d_mp_id, d_mp_pos, d_mp_outlier, d_n_mp, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, kf_cap, mp_cap, 0};
-    hipLaunchKernelGGL(k_kf_update, dim3(h->S), dim3(TRK_NT), 0, h->stream, h->a, g);
+    hipLaunchKernelGGL(k_kf_update, dim3(h->S), dim3(TRK_NT), 0, h->stream, h->a, g, d_gate);
     MYSLAM_HIP_CHECK(hipGetLastError());
     return MYSLAM_OK;
 }
+
+extern "C" {
 
 int myslam_tracker_clear_links_batch(myslam_tracker* h, const int64_t* d_kf_id, const int32_t* d_tag, const int32_t* d_n, int list_cap, int32_t* d_n_cleared) {
     if (!h || !d_kf_id || !d_tag || !d_n || list_cap <= 0) return MYSLAM_ERR_INVALID;

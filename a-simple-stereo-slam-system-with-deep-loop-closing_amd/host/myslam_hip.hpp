@@ -440,6 +440,7 @@ public:
     ~TrackerBank() { if (h_) myslam_tracker_destroy(h_); }
     TrackerBank(const TrackerBank&) = delete; TrackerBank& operator=(const TrackerBank&) = delete;
     int streams() const { return streams_; }
+    myslam_tracker* handle() const { return h_; }
     int launchesPerStep() const { return myslam_tracker_launches_per_step(h_); }
     void SetStream(void* hipStream) { check(myslam_tracker_set_stream(h_, hipStream), "myslam_tracker_set_stream"); }
     // prevImage: the image the next step tracks FROM (a key-frame's image after DeepLCD blurred it in place); nullptr keeps the last step's
@@ -960,6 +961,50 @@ public:
                      int maxSuspected = 3 /*:147*/) {
         check(myslam_loop_detect_batch(h_, d_bestId, d_maxScore, d_cntSuspected, nq, thrHigh, maxSuspected, d_loopDescriptors, d_nLoop,
                                        d_loopPyramidKeyPoints, d_loopFeatureLandmark, d_loopSlot, d_status), "myslam_loop_detect_batch");
+    }
+};
+
+// The Backend thread for a bank of streams (src/backend.cpp:30-37, :82-121, :126-266 with Map::InsertKeyFrame, src/map.cpp:17-48): one enqueue maps
+// exactly the streams that made a key-frame in the turn or the StereoInit whose outputs it is given; the others keep every byte.  The handle owns the
+// back end, the map archive, the observation archive and every table between them (View()).  Device pointers; KeyFrameBatch enqueues on the
+// handle's stream and returns, and can be recorded.  ResetItem / Status take host memory and wait.
+class Mapper {
+    myslam_mapper* h_ = nullptr;
+    int streams_;
+public:
+    struct TurnOutputs {            // what myslam_tracker_keyframe_batch / _init_batch wrote (feature stride = featCap, outlier stride = 2 featCap)
+        const int64_t* newKFId; const double* newKFPose; const int64_t* featMapPointId; const double* featMapPointPos; const float* featPixels;
+        const int32_t* featTag; const uint8_t* featFlags; const int32_t* nFeat; const int64_t* outlierMapPointId; const int32_t* nOutlierMapPoint;
+        const float* rightPixels; const uint8_t* rightOk; const int32_t* report;
+    };
+    Mapper(int streams, int kfCap, int mpCap, int obsCap, int featCap, int archiveKFCap, int archiveEdgeCap, int archivePointCap, int obsRowCap,
+           int priorCap) : streams_(streams) {
+        check(myslam_mapper_create(&h_, streams, kfCap, mpCap, obsCap, featCap, archiveKFCap, archiveEdgeCap, archivePointCap, obsRowCap, priorCap),
+              "myslam_mapper_create");
+    }
+    ~Mapper() { if (h_) myslam_mapper_destroy(h_); }
+    Mapper(const Mapper&) = delete; Mapper& operator=(const Mapper&) = delete;
+    int streams() const { return streams_; }
+    int launchesPerCall(bool withTracker = true) const { return myslam_mapper_launches_per_call(h_, withTracker ? 1 : 0); }
+    void SetStream(void* hipStream) { check(myslam_mapper_set_stream(h_, hipStream), "myslam_mapper_set_stream"); }
+    myslam_mapper_tables View() const {
+        myslam_mapper_tables t;
+        check(myslam_mapper_view(h_, &t), "myslam_mapper_view");
+        return t;
+    }
+    // d_status: streams x MYSLAM_MAPPER_STATUS_WORDS; [0] = 0 mapped / MYSLAM_MAPPER_IDLE / the stream's (sticky) error.  tracker may be nullptr
+    void KeyFrameBatch(TrackerBank* tracker, const TurnOutputs& o, int window, double fx, double fy, double cx, double cy, int32_t* d_status,
+                       double minDisTh = 0.2, double huberDelta = 5.991, double chi2Th = 5.991, int maxRounds = 5, int itersPerRound = 10) {
+        check(myslam_mapper_keyframe_batch(h_, tracker ? tracker->handle() : nullptr, o.newKFId, o.newKFPose, o.featMapPointId, o.featMapPointPos, o.featPixels,
+                                           o.featTag, o.featFlags, o.nFeat, o.outlierMapPointId, o.nOutlierMapPoint, o.rightPixels, o.rightOk, o.report, window,
+                                           minDisTh, fx, fy, cx, cy, huberDelta, chi2Th, maxRounds, itersPerRound, d_status),
+              "myslam_mapper_keyframe_batch");
+    }
+    void ResetItem(int stream) { check(myslam_mapper_reset_item(h_, stream), "myslam_mapper_reset_item"); }
+    std::vector<int32_t> Status(const int32_t* d_status) const {
+        std::vector<int32_t> w((size_t)streams_ * MYSLAM_MAPPER_STATUS_WORDS);
+        check(myslam_debug_peek(d_status, w.data(), w.size() * sizeof(int32_t)), "myslam_debug_peek");
+        return w;
     }
 };
 

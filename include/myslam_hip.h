@@ -896,7 +896,8 @@ int myslam_tracker_debug_last_step(myslam_tracker* h, int stream, float* p0, flo
  * What myslam_backend_insert_keyframe_batch does with a no-turn item (d_new_kf_id = -1, d_n_feat = 0): on a table that holds a key-frame the id
  * is not above the last one -> that item is refused with MYSLAM_ERR_INVALID and keeps every byte.  On an EMPTY key-frame table there is no last
  * id to compare with and the row (-1, pose) WOULD BE APPENDED: a stream's table holds its StereoInit key-frame before any turn can happen, and a
- * caller that batches other tables must take such items out itself.
+ * caller that batches other tables must take such items out itself (myslam_mapper_keyframe_batch, MAPPER below, does so on the device: its gate
+ * idles every item without a key-frame before the insert reads a table).
  *
  * myslam_tracker_update_from_map_batch — 1 launch.  In the reference the frontend holds the MapPoint / KeyFrame objects the back end and the loop
  * closer move.  Item s = stream s: d_kf_id S x kf_cap ascending / d_kf_pose x 7 / d_n_kf, d_mp_id S x mp_cap ascending / d_mp_pos x 3 /
@@ -1756,6 +1757,91 @@ int myslam_loop_store_set_links_batch(myslam_loop_store* h, const int64_t* d_kf_
 /* src/loopclosing.cpp:524 and :529 as TrackLastFrame (src/frontend.cpp:127-171) sees them through src/keyframe.cpp:21 */
 int myslam_tracker_relink_batch(myslam_tracker* h, const int64_t* d_kf_id, const int32_t* d_tag, const int32_t* d_slot, const int32_t* d_n, int list_cap,
                                 const myslam_map* map, int32_t* d_n_relinked, int32_t* d_status);
+
+/* ------------------------------------------------------------------------------------------
+ * MAPPER — the Backend thread's work for a bank of S streams behind one handle: Backend::ProcessNewKeyFrame + OptimizeActiveMap
+ * (src/backend.cpp:82-121, :126-266; the thread loop BackendRun, :30-37, optimises only after InsertKeyFrame) and Map::InsertKeyFrame
+ * (src/map.cpp:17-48) for every stream of the bank that made a key-frame in the turn (or the StereoInit) just taken, and for no other.  The decision
+ * is taken on the device: one call is one asynchronous, recordable enqueue, whatever mix of turning and tracking streams the frame holds.
+ * The handle owns one myslam_backend, one myslam_map (with the solve attached, myslam_map_attach_solve) and one myslam_obs_archive for S items, the
+ * back end's 13 tables (zeroed: every table starts empty) and every prior, report and status array its stages hand to each other.  Nothing moves
+ * after create; myslam_mapper_view gives the pointers, so the loop-closing units work on the same state.
+ *
+ * Order of one call, all on the handle's stream, one workgroup per item in every stage, item s = stream s:
+ *   gate -> prior_rows -> insert (those priors, the turn's outlier list) -> myslam_map_update_batch(AFTER_INSERT) ->
+ *   myslam_obs_archive_update_batch(AFTER_INSERT) -> optimise (flatten, solve, write-back) -> myslam_map_update_batch(AFTER_OPTIMIZE) ->
+ *   myslam_obs_archive_update_batch(AFTER_OPTIMIZE, the optimise's d_obs_report) -> myslam_tracker_clear_links_batch on the back end's culled view ->
+ *   myslam_tracker_update_from_map_batch -> status
+ * so both contracts of the map archive hold by construction (one back-end call between two updates of an item, the map's update first).
+ * myslam_mapper_launches_per_call = 13 with a tracker (the sum of the units' own counts + 2), 11 with trk == NULL (the two tracker launches are left out).
+ *
+ * THE GATE (k_mapper_gate, the first launch, one i32 per item): item s takes the key-frame iff its sticky fault is 0 && d_report[s][0] == 0 &&
+ * d_new_kf_id[s] >= 0.  Everything else is MYSLAM_MAPPER_IDLE: MYSLAM_TRACKER_NO_TURN, MYSLAM_TRACKER_INIT_RETRY, a turn refused with
+ * MYSLAM_ERR_CAPACITY, id -1, a faulted item.  For an IDLE item no byte of its tables, of its map-archive item or of its observation-archive item
+ * changes (the (-1, pose) row that myslam_backend_insert_keyframe_batch would append to an EMPTY table is never appended), the solve does not run for
+ * it, its culled count is 0 and the tracker's stream keeps every byte (the outlier flags its steps have set are not in the table yet).  The insert and
+ * the flatten leave with MYSLAM_MAPPER_IDLE before they read a table (csrc/backend_launch.h; the public entry points pass no gate and write what
+ * they always wrote); the solve skips through its d_skip path, the write-back's status branch zeroes the reports, the two archives skip on
+ * d_backend_status != 0.  The optimise is gated on the INSERT's status: an item whose insert was refused is not re-optimised either.
+ *
+ * d_status: S x MYSLAM_MAPPER_STATUS_WORDS i32 (k_mapper_status, the last launch).  Item that passed the gate:
+ *   [0] overall: 0 mapped, or the first negative of [1..7]      [1] prior_rows      [2] insert      [3] map update after the insert
+ *   [4] obs update after the insert      [5] optimise (MYSLAM_BACKEND_DONE / MYSLAM_BACKEND_EMPTY — no error: the reference returns early and the
+ *   later updates skip — / an error / MYSLAM_MAPPER_IDLE after a refused insert)      [6] map update after the optimise      [7] obs update after it
+ * IDLE item: [0] = MYSLAM_MAPPER_IDLE, or the item's sticky fault; [1..7] = MYSLAM_MAPPER_IDLE.
+ * A negative overall status is STICKY per stream: the tracker has taken the turn, so the stream's map no longer follows it.  Every later call idles
+ * the item and reports the same error until myslam_mapper_reset_item; its neighbours are served as if it were not there.
+ *
+ * myslam_mapper_keyframe_batch: device pointers; the thirteen outputs of myslam_tracker_keyframe_batch / _init_batch in their layout (feature stride =
+ * feat_cap, outlier stride = 2 x feat_cap; d_right_xy / d_right_ok are not read and may be NULL), window = Map.activeMap.size (src/map.cpp:44),
+ * min_dis_th 0.2 (:101), the solve's arguments as myslam_backend_optimize_batch takes them.  Asynchronous, never synchronises, allocates nothing,
+ * recordable between myslam_graph_begin / _end.  trk: the tracker of the same S streams and feature cap on the same stream, or NULL.
+ * Call level, nothing enqueued: NULL required pointers, window < 1, max_rounds < 1, iters_per_round < 1, a tracker on another stream, of another bank
+ * size or feature cap -> MYSLAM_ERR_INVALID.  create: streams / caps < 1 -> MYSLAM_ERR_INVALID, feat_cap or prior_cap beyond obs_cap ->
+ * MYSLAM_ERR_CAPACITY, else whatever the owned units answer to their caps (kf_cap > MYSLAM_BA_MAX_WINDOW_POSES -> MYSLAM_ERR_UNSUPPORTED ...).
+ * ONE CALL CONSUMES ONE OUTPUT SET.  A frame in which some streams start and others turn is init -> mapper, then turn -> mapper: the two tracker calls
+ * never share an eligible stream, but each rewrites all S output items, so they must not share buffers across one mapper call.
+ *
+ * myslam_mapper_reset_item — host call, synchronous; MYSLAM_ERR_UNSUPPORTED while the stream is being recorded.  Empties the stream's tables, its
+ * map-archive item and its observation-archive item and clears its sticky fault: a restart after LOST, together with myslam_tracker_reset_stream.
+ * myslam_mapper_set_stream sets the stream of the three owned handles too.
+ * OUT OF SCOPE: loop closing — the five-key-frame skip of src/loopclosing.cpp:671-681, the store's put and everything after it — and DeepLCD's
+ * in-place blur of the key-frame image (src/deeplcd.cpp:46), which belongs with it.
+ * ------------------------------------------------------------------------------------------ */
+#define MYSLAM_MAPPER_IDLE 3           /* no key-frame of this item in this call: nothing of it was touched */
+#define MYSLAM_MAPPER_STATUS_WORDS 8
+typedef struct myslam_mapper myslam_mapper;
+typedef struct myslam_mapper_tables {
+    /* the back end's 13 tables, strided by kf_cap / mp_cap / obs_cap */
+    int64_t* kf_id; double* kf_pose; int32_t* n_kf; int64_t* mp_id; double* mp_pos; uint8_t* mp_outlier; int32_t* n_mp;
+    int32_t* obs_mp; int32_t* obs_kf; uint8_t* obs_flags; float* obs_uv; int32_t* obs_tag; int32_t* n_obs;
+    /* prior_rows' outputs (S x prior_cap) */
+    int64_t* prior_mp_id; int64_t* prior_kf_id; float* prior_uv; int32_t* prior_tag; uint8_t* prior_flags; int32_t* n_prior;
+    /* the insert's reports */
+    int32_t* feat_row; int32_t* mp_new_row; int64_t* removed_kf_id; int32_t* removed_kf_row; double* dis;
+    /* the optimise's reports */
+    uint8_t* obs_report; uint8_t* mp_report; int32_t* new_outlier_mp; int32_t* n_new_outlier_mp; double* obs_chi2; int32_t* rounds; int32_t* n_outlier_edges;
+    int32_t* n_cleared;                 /* myslam_tracker_clear_links_batch's */
+    /* per item: the gate (0 = takes the key-frame), the sticky fault, the seven stage statuses in the order of d_status[1..7] */
+    int32_t* gate; int32_t* fault; int32_t* stage_status[7];
+    myslam_backend* backend; myslam_map* map; myslam_obs_archive* obs;
+    int32_t streams, kf_cap, mp_cap, obs_cap, feat_cap, prior_cap;
+} myslam_mapper_tables;
+int myslam_mapper_create(myslam_mapper** out, int streams, int kf_cap, int mp_cap, int obs_cap, int feat_cap, int archive_kf_cap, int archive_edge_cap,
+                         int archive_point_cap, int obs_row_cap, int prior_cap);
+int myslam_mapper_destroy(myslam_mapper* h);
+int myslam_mapper_set_stream(myslam_mapper* h, void* hip_stream);
+/* the device pointers, caps and owned handles: valid until destroy */
+int myslam_mapper_view(const myslam_mapper* h, myslam_mapper_tables* out);
+/* src/backend.cpp:82-121, :126-266 and src/map.cpp:17-48 for the streams that made a key-frame, as described above */
+int myslam_mapper_keyframe_batch(myslam_mapper* h, myslam_tracker* trk, const int64_t* d_new_kf_id, const double* d_new_kf_pose, const int64_t* d_feat_mp_id,
+                                 const double* d_feat_mp_pos, const float* d_feat_uv, const int32_t* d_feat_tag, const uint8_t* d_feat_flags,
+                                 const int32_t* d_n_feat, const int64_t* d_outlier_mp_id, const int32_t* d_n_outlier_mp, const float* d_right_xy,
+                                 const uint8_t* d_right_ok, const int32_t* d_report, int window, double min_dis_th, double fx, double fy, double cx, double cy,
+                                 double huber_delta, double chi2_th, int max_rounds, int iters_per_round, int32_t* d_status);
+/* kernel launches one myslam_mapper_keyframe_batch enqueues: 13, or 11 with with_tracker == 0 */
+int myslam_mapper_launches_per_call(const myslam_mapper* h, int with_tracker);
+int myslam_mapper_reset_item(myslam_mapper* h, int stream);
 
 /* ------------------------------------------------------------------------------------------
  * Host-side formats of the reference's runner — plain host code, no device needed; the C++ forms live in
