@@ -121,7 +121,6 @@ __device__ __forceinline__ double bcast_lane(double v, int srcLane) {       // s
 //   window per key-frame: every landmark's lane pair then exists at once).
 template <int NT, bool LISTS>
 __global__ __launch_bounds__(NT) void k_ba_build(BaArgs a) {
-    MYSLAM_SIDE_PRIO();
     constexpr int NW = NT / 64;
     extern __shared__ __attribute__((aligned(16))) double s_d[];
     const int w = blockIdx.x, t = threadIdx.x, wv = t >> 6;
@@ -1107,11 +1106,7 @@ __global__ __launch_bounds__(NT) void k_pose_only(PoseOnlyArgs a) {
     // registers: the H pass of an iteration always follows an evaluation at exactly its state (the round's first, or the accepted trial's), so
     // it reads them back instead of evaluating again (the same doubles; two f64 divisions per edge and iteration less on a chain of ~45
     // dependent steps).  Eight-wave blocks of large batches keep their registers for occupancy and evaluate again.
-#ifdef MYSLAM_POSE_ONLY_NO_KEEP                              // A/B builds only
-    constexpr bool KEEP = false;
-#else
     constexpr bool KEEP = NT <= 128;
-#endif
     constexpr int NK = KEEP ? PO_EPT : 1;
     double ke0[NK], ke1[NK], kx[NK], ky[NK], kz[NK];
     auto active_chi2 = [&]() -> double {                   // computeActiveErrors + activeRobustChi2
@@ -1150,9 +1145,6 @@ __global__ __launch_bounds__(NT) void k_pose_only(PoseOnlyArgs a) {
                 // a new iteration normally follows an accepted trial; the one exception (a NaN gain ratio leaves the trial loop with the state
                 // restored and no exit condition met) evaluates again, as g2o does at the start of every iteration
                 if (!fresh) { currentChi = active_chi2(); fresh = true; }
-#ifdef MYSLAM_POSE_ONLY_RECOMPUTE_CHI                         // A/B builds only (tools/build_variants.sh): the round-4 form, one more evaluation per iteration
-                if (it > 0) currentChi = active_chi2();
-#endif
                 // ---- H (upper triangle, 21) and b (6) ----
                 double h[32];
 #pragma unroll
@@ -1179,17 +1171,8 @@ __global__ __launch_bounds__(NT) void k_pose_only(PoseOnlyArgs a) {
                         for (int r = 0; r < 6; r++) h[21 + r] += -w * (J[r] * e0 + J[6 + r] * e1);
                     }
                 }
-#ifdef MYSLAM_POSE_ONLY_SUM_PER_VALUE                        // A/B builds only: 27 six-step wave sums (the form up to round 5)
-#pragma unroll
-                for (int u = 0; u < 27; u++) h[u] = wave_sum_lane63(h[u]);
-                if (lane == 63) {
-#pragma unroll
-                    for (int u = 0; u < 27; u++) s_part[wv][u] = h[u];
-                }
-#else
                 wave_sum32_halving(h, lane);
                 if (!(lane & 1) && (lane >> 1) < 27) s_part[wv][lane >> 1] = h[0];
-#endif
                 __syncthreads();
                 if (t < 27) { double s = 0; for (int w2 = 0; w2 < NW; w2++) s += s_part[w2][t]; sH[t] = s; }
                 __syncthreads();
@@ -1299,14 +1282,8 @@ static size_t ba_lds(int maxP, int maxL, int maxE, int nwaves) {
     return sizeof(double) * ((size_t)maxP * (12 + nwaves * 27) + staged) + sizeof(int) * (3 * (size_t)maxL + lists);
 }
 
-#ifndef MYSLAM_BA_WIDE_BELOW           // A/B builds (tools/build_variants.sh)
-#define MYSLAM_BA_WIDE_BELOW 32
-#endif
-#ifndef MYSLAM_BA_LISTS_BELOW
-#define MYSLAM_BA_LISTS_BELOW 32
-#endif
-constexpr int BA_WIDE_BELOW = MYSLAM_BA_WIDE_BELOW;      // fewer windows than this per call: 1024 threads per window (latency), else 256 (throughput)
-constexpr int BA_LISTS_BELOW = MYSLAM_BA_LISTS_BELOW;    // fewer windows than this per call: the staged pose-list form when it fits LDS
+constexpr int BA_WIDE_BELOW = 32;      // fewer windows than this per call: 1024 threads per window (latency), else 256 (throughput)
+constexpr int BA_LISTS_BELOW = 32;     // fewer windows than this per call: the staged pose-list form when it fits LDS
 
 // the six inputs every BA host form stages: poses and points (written back when `solve`), observations, the two edge tables, the fixed flags (optional)
 struct BaHostIn { int p, x, o, ep, el, f; };

@@ -31,10 +31,7 @@ namespace myslam_hip {
 constexpr int HQ_TILES = 4;                       // query tiles of 32 per wave -> 512 queries per block
 constexpr int HQ_BLOCK = 4 * HQ_TILES * 32;
 constexpr int HQ_NARROW_BELOW = 16;               // fewer pairs than this per call: one query tile per wave (k_hamming_fp4<1, HQ_SPLIT>)
-#ifndef MYSLAM_HQ_SPLIT                           // A/B builds (tools/build_variants.sh)
-#define MYSLAM_HQ_SPLIT 4
-#endif
-constexpr int HQ_SPLIT = MYSLAM_HQ_SPLIT;         // ... and this many wave groups per block, each on every HQ_SPLIT-th train chunk
+constexpr int HQ_SPLIT = 4;                       // ... and this many wave groups per block, each on every HQ_SPLIT-th train chunk
 
 // The product runs on the FP4 path of the matrix cores (v_mfma_scale_f32_32x32x64_f8f6f4, K = 64 per instruction, twice the int8
 // rate): E2M1 represents +-1 exactly (0x2 / 0xA), the factor 32 of the query operand is its E8M0 block scale (2^5), sums of at most
@@ -64,7 +61,6 @@ __global__ __launch_bounds__(256 * SPLIT) void k_hamming_fp4(const uint8_t* __re
                                                      const uint8_t* __restrict__ tr, const int32_t* __restrict__ ntv,
                                                      int cap, int nq_single, int nt_single,
                                                      int32_t* __restrict__ out_idx, int32_t* __restrict__ out_dist, TriTail tt) {
-    MYSLAM_SIDE_PRIO();
     __shared__ __attribute__((aligned(16))) uint8_t s_exp[SPLIT][2][32 * HF_ROWB];
     __shared__ uint32_t s_key[SPLIT > 1 ? SPLIT : 1][SPLIT > 1 ? 128 * TILES : 1];
     __shared__ int32_t s_match[TRI ? 128 * TILES : 1];
@@ -201,7 +197,6 @@ __global__ __launch_bounds__(256) void k_triangulate(const float* __restrict__ x
                                                      const int32_t* __restrict__ match, const int32_t* __restrict__ nlv,
                                                      int cap, int n_single, double fx, double fy, double cx, double cy,
                                                      double baseline, double* __restrict__ xyz, uint8_t* __restrict__ ok) {
-    MYSLAM_SIDE_PRIO();
     const int p = blockIdx.y;
     const int i = blockIdx.x * 256 + threadIdx.x;
     const int n = nlv ? min(nlv[p], cap) : n_single;
@@ -242,7 +237,6 @@ struct LoopPairsArgs {
 };
 
 __global__ __launch_bounds__(1024) void k_loop_pairs(LoopPairsArgs a) {
-    MYSLAM_SIDE_PRIO();
     extern __shared__ uint32_t s_keys[];                     // next power of two >= cap keys
     __shared__ int s_w[16], s_red[16];
     const int b = blockIdx.x, tid = threadIdx.x, nt = blockDim.x, wv = tid >> 6, nw = nt >> 6;

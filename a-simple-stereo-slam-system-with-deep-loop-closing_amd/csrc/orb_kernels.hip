@@ -215,14 +215,8 @@ __global__ __launch_bounds__(256) void k_resize_chain(ResizeChain c) { rc_block(
 // (before: bands of 8 rows that fetched 12 row slots and interpolated 10-11 of them — 1.5 loads and 1.31 horizontal passes per
 // destination row where the scale factor needs 1.2 —, ~84 registers of row cache, and the coordinates of 4 columns and 16 rows
 // recomputed through f64 by every wave of every launch.)
-#ifndef MYSLAM_RS_BAND                 // A/B builds (tools/build_variants.sh): destination rows a wave walks (>= the level's height = the whole strip)
-#define MYSLAM_RS_BAND 64
-#endif
-#ifndef MYSLAM_RS_PF
-#define MYSLAM_RS_PF 4
-#endif
-constexpr int RS_BAND = MYSLAM_RS_BAND;
-constexpr int RS_PF = MYSLAM_RS_PF;          // raw source rows in flight ahead of the horizontal pass
+constexpr int RS_BAND = 64;        // destination rows a wave walks (>= the level's height = the whole strip)
+constexpr int RS_PF = 4;           // raw source rows in flight ahead of the horizontal pass
 
 typedef uint32_t rs_u32x3 __attribute__((ext_vector_type(3)));
 typedef uint32_t rs_u32x2 __attribute__((ext_vector_type(2)));
@@ -315,7 +309,6 @@ __device__ __forceinline__ void resize_strip_walk(const ResizeArgs& a, const uin
 }
 
 __global__ __launch_bounds__(256) void k_resize_strip(ResizeArgs a, int nstrips, int nbands, int band) {
-    MYSLAM_SIDE_PRIO();
     MYSLAM_BT(1);
     const int lane = threadIdx.x & 63;
     const int wid = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));   // scalar: row addressing goes to the SALU
@@ -622,7 +615,6 @@ __device__ __forceinline__ void blur7_strip_wave(const BlurMulti& M, int gw, int
     if (interior) run(std::false_type{}); else run(std::true_type{});
 }
 __global__ __launch_bounds__(256) void k_blur7_strip(BlurMulti M) {
-    MYSLAM_SIDE_PRIO();
     MYSLAM_BT(3);
     __shared__ __attribute__((aligned(16))) uint8_t s_tl[4][16 * B3_TS];
     blur7_strip_wave(M, __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6))), blockIdx.z, s_tl[threadIdx.x >> 6]);      // scalar wave id: row addressing goes to the SALU
@@ -838,15 +830,6 @@ void blur_mfma_ident(std::vector<uint4>& tab, size_t& offI) {
 #define FAST_RING_X {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1}
 #define FAST_RING_Y {3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1, 0, 1, 2, 3}
 
-// Profiling builds only (tools/fast_phase_pmc.sh): MYSLAM_FAST_PHASE = n truncates the DENSE path of the strip kernel after phase n so that
-// the hardware counters of consecutive builds difference into per-phase instruction counts.  1: block decode + staging + score-map
-// clearing; 2: + the scoring loop's control and window loads (score replaced by an XOR over the 24 window dwords); 3: + the byte-pair
-// picks (score = XOR over the 17 picks of a pixel pair); 4: + the min / max network (= the whole scoring phase); 5: + NMS and the
-// strip's record list; 0 (the product): + path statistics, filter and global append.
-#ifndef MYSLAM_FAST_PHASE
-#define MYSLAM_FAST_PHASE 0
-#endif
-
 typedef short s16x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ s16x2 pmin(s16x2 a, s16x2 b) { return __builtin_elementwise_min(a, b); }
 __device__ __forceinline__ s16x2 pmax(s16x2 a, s16x2 b) { return __builtin_elementwise_max(a, b); }
@@ -885,9 +868,6 @@ __device__ __forceinline__ s16x2 fast9_score_pair(const uint32_t (&r)[NR][3], s1
     s16x2 p[16];
 #pragma unroll
     for (int i = 0; i < 16; i++) p[i] = pick(ROW + 3 + RY[i], xc + RX[i]);
-#if MYSLAM_FAST_PHASE == 3
-    { s16x2 x = vv ^ thv; for (int i = 0; i < 16; i++) x = x ^ p[i]; return x; }
-#endif
     s16x2 n2[8], x2[8], n4[8], x4[8], ub[8], ud[8];
 #pragma unroll
     for (int k = 0; k < 8; k++) { n2[k] = pmin(p[2 * k], p[2 * k + 1]); x2[k] = pmax(p[2 * k], p[2 * k + 1]); }
@@ -1025,44 +1005,25 @@ struct FastCtl { const uint32_t* prev; uint32_t* cur; int force; };
 //                    separable form; every 4-pixel row with a strict maximum leaves one list record, expanded by the append phase.
 // Blocks are handed out XCD-aware: consecutive strips (which share halo rows and columns) go to the same XCD's L2.
 // CW / CH = the widest / tallest grid cell of the plan (columns cost LDS in 16-byte steps, rows one by one)
-#ifndef MYSLAM_FAST_LDS_BLOCK                                  // A/B builds (tools/build_variants.sh): another block footprint, e.g. 24300 = just over 160 KB / 7
-#define MYSLAM_FAST_LDS_BLOCK (163840 / 6 - 128)
-#endif
-#ifndef MYSLAM_FAST_BLOCKS_PER_CU                              // A/B builds that set another MYSLAM_FAST_LDS_BLOCK say how many blocks it is meant to admit
-#define MYSLAM_FAST_BLOCKS_PER_CU 6
-#endif
+constexpr int FAST_LDS_BLOCK = 163840 / 6 - 128;              // a block's LDS footprint (the measured history of this value: in the kernel, below)
+constexpr int FAST_BLOCKS_PER_CU = 6;                          // blocks per CU that footprint is meant to admit
+constexpr int FAST_WAVES_PER_EU = 6;
 // LDS a block of k_fast_strip<CW, G, CH> declares (an upper estimate: the arrays below plus their alignment) and the PAD that brings the block to
-// MYSLAM_FAST_LDS_BLOCK.  The pad is DYNAMIC LDS, passed by the launcher (round 6): as a static array it made the compiler conclude "six waves per SIMD at
+// FAST_LDS_BLOCK.  The pad is DYNAMIC LDS, passed by the launcher (round 6): as a static array it made the compiler conclude "six waves per SIMD at
 // most" and — to honour that bound by registers as well — raise the kernel's register allocation from its 68 to 73, i.e. from 72 to 80 registers per lane
 // in the hardware's granules of 8.  Alone that costs nothing (LDS admits six blocks either way); under the pipeline the blocks of the other streams hold
 // part of every CU's register file and the 8 registers decide how many FAST blocks fit beside them (beside two descriptor blocks: 5 instead of 4).
-// NS > 1 (round 6, the multi-strip form): a second tile buffer and a second set of the strip's counters; such blocks are sized for MYSLAM_FAST_MS_BLOCKS_PER_CU per CU
-#ifndef MYSLAM_FAST_MS_BLOCKS_PER_CU
-#define MYSLAM_FAST_MS_BLOCKS_PER_CU 5
-#endif
-template <int CW, int G, int CH, int NS = 1>
+template <int CW, int G, int CH>
 struct FastLds {
     static constexpr int CP = (CW + 6 + 15) & ~15, TP = G * CP, TROWS = CH + 6 + 1, SP = (CW + 4 + 8 + 3) & ~3, SROWS = CH + 2 + 4;
     static constexpr int NPAIR = G * CH * ((CW + 1) / 2);
-    static constexpr int EST = (NS > 1 ? 2 : 1) * (TROWS * TP + 16) + G * (SROWS * SP + 16) + 2 * NPAIR + (NS > 1 ? 128 : 64);
-    static constexpr int BLOCKS = NS > 1 ? MYSLAM_FAST_MS_BLOCKS_PER_CU : MYSLAM_FAST_BLOCKS_PER_CU;
-    static constexpr int BLOCK = NS > 1 ? 163840 / MYSLAM_FAST_MS_BLOCKS_PER_CU - 128 : MYSLAM_FAST_LDS_BLOCK;
-    static constexpr int PAD = (CW <= 32 && EST < (NS > 1 ? BLOCK : 163840 / 7)) ? BLOCK - EST : 0;
+    static constexpr int EST = (TROWS * TP + 16) + G * (SROWS * SP + 16) + 2 * NPAIR + 64;
+    static constexpr int BLOCKS = FAST_BLOCKS_PER_CU;
+    static constexpr int PAD = (CW <= 32 && EST < 163840 / 7) ? FAST_LDS_BLOCK - EST : 0;
     static_assert(CW > 32 || (BLOCKS * (EST + PAD) <= 163840 && (BLOCKS + 1) * (EST + PAD) > 163840), "exactly BLOCKS blocks per CU");
 };
-#ifndef MYSLAM_FAST_WAVES_PER_EU
-#define MYSLAM_FAST_WAVES_PER_EU 6
-#endif
-#ifndef MYSLAM_FAST_NS                                          // strips per block of the grid-FAST kernel (1 = one block per strip; > 1 = the multi-strip form for large launches)
-#define MYSLAM_FAST_NS 1
-#endif
-#ifdef MYSLAM_FAST_NUM_VGPR
-#define MYSLAM_FAST_VGPR_ATTR __attribute__((amdgpu_num_vgpr(MYSLAM_FAST_NUM_VGPR)))
-#else
-#define MYSLAM_FAST_VGPR_ATTR
-#endif
-template <int CW, int G, int CH = CW, int NS = 1>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CW <= 40 ? MYSLAM_FAST_WAVES_PER_EU : 3))) MYSLAM_FAST_VGPR_ATTR void k_fast_strip(OrbPlan P, const uint8_t* __restrict__ pyr, size_t pyrStride,
+template <int CW, int G, int CH = CW>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CW <= 40 ? FAST_WAVES_PER_EU : 3))) void k_fast_strip(OrbPlan P, const uint8_t* __restrict__ pyr, size_t pyrStride,
                                                     const uint8_t* __restrict__ maskPyr,
                                                     uint32_t* __restrict__ cand, int32_t* __restrict__ candCount, FastCtl ctl, int batch) {
     constexpr int T = 256;
@@ -1075,14 +1036,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CW <= 40 ? 
     constexpr int NLIST = G * ((CW + 1) / 2) * ((CH + 1) / 2);         // a cell of a x b pixels holds at most ceil(a/2) ceil(b/2) strict maxima
     constexpr int NPAIR = G * CH * ((CW + 1) / 2);                     // pixel pairs of a strip
     static_assert(CW <= 63 && CH <= 63 && G <= 4, "pair list entry = cell << 11 | row << 5 | pair index");
-    // NS > 1 (the multi-strip form, see the loop below): two tile buffers — the next strip's tile lands in one by LDS-DMA while the current strip is worked on in the
-    // other — and two sets of the strip's small state (a wave that has nothing to append runs ahead into the next strip's set-up)
-    constexpr int NB2 = NS > 1 ? 2 : 1;
-    static_assert(NS == 1 || (CW <= 32 && G == 4 && MYSLAM_FAST_PHASE == 0), "the multi-strip form exists for the usual plans' instance only");
     __shared__ __attribute__((aligned(16))) uint8_t s_tile0[TROWS * TP + 16];
-    // (the second tile buffer of the multi-strip form is DYNAMIC LDS, as the pad is: the compiler sizes the kernel's register allocation by the occupancy its STATIC
-    // LDS admits — with 31 KB declared it concludes "five waves per SIMD at most" and spends 83 registers where the block's co-runners leave room for 72)
-    extern __shared__ __attribute__((aligned(16))) uint8_t s_dyn[];
     __shared__ __attribute__((aligned(16))) uint8_t s_score[G][SROWS * SP + 16];
     __shared__ uint16_t s_pairs[NPAIR];
     // strict maxima of the strip (py<<20 | px<<8 | z) and their cells: the list lives in the tile's LDS, which is dead once the
@@ -1092,7 +1046,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CW <= 40 ? 
     // row's (cell << 10 | row << 4 | group) (s_pairs, which only the two-phase path uses otherwise).  A cell of a x b pixels has at
     // most ceil(a/2) ceil(b/2) strict maxima, hence at most NLIST such rows.
     static_assert(NLIST * 4 <= TROWS * TP && NLIST <= NPAIR, "row records must fit");
-    __shared__ int s_ini2[NB2][G], s_wc2[NB2][G], s_cnt2[NB2][4];      // [.][0] = records / maxima listed, [1] = pairs listed, [2] = corner rows (the path statistic)
+    __shared__ int s_ini[G], s_wc[G], s_cnt[4];                        // s_cnt[0] = records / maxima listed, [1] = pairs listed, [2] = corner rows (the path statistic)
     // LDS footprint on purpose (1241 x 376: cells of at most 32 x 40 pixels): a block of this instance needs 22.4 KB, seven would fit a CU — and
     // with seven waves per SIMD FAST holds 504 of the 512 registers per lane (measured: FAST alone 3 % faster, the pipelined step 1 % slower).
     // Six blocks it is; the question is what the remaining LDS of a CU is open to.  History: 25.1 KB per block (9 KB free: only blur / resize
@@ -1101,7 +1055,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CW <= 40 ? 
     // kernel runs as a limited grid and the oct-tree kernel no longer ends on its long blocks, the kernels of the other streams find their
     // CUs where FAST blocks retire; a block that squeezes in beside six FAST blocks only slows the launch the whole step waits for
     // (block size 27.2 / 26.0 / 25.0 / 24.4 / 23.7 KB: 75.0 / 74.3 / 74.5 / 73.9 / 74.3 k frames/s, two runs each on one box).
-    static_assert(FastLds<CW, G, CH, NS>::CP == CP && FastLds<CW, G, CH, NS>::TROWS == TROWS && FastLds<CW, G, CH, NS>::SP == SP && FastLds<CW, G, CH, NS>::SROWS == SROWS && FastLds<CW, G, CH, NS>::NPAIR == NPAIR,
+    static_assert(FastLds<CW, G, CH>::CP == CP && FastLds<CW, G, CH>::TROWS == TROWS && FastLds<CW, G, CH>::SP == SP && FastLds<CW, G, CH>::SROWS == SROWS && FastLds<CW, G, CH>::NPAIR == NPAIR,
                   "FastLds restates this kernel's LDS arrays");            // (the pad itself: dynamic LDS of FastLds<>::PAD bytes, see there)
 
     // XCD-aware block order (bijective remap of the 1-D grid): the dispatcher places block i on XCD i % 8 and every XCD has a private
@@ -1124,12 +1078,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CW <= 40 ? 
     asm volatile("" : "+s"(a_nstrips), "+s"(a_batch), "+s"(a_ext0N), "+s"(a_ext0Pitch), "+s"(a_ext0Stride), "+s"(a_pyrStride), "+s"(a_ext0i), "+s"(a_pyri), "+s"(a_tabi));
     typedef const uint8_t __attribute__((address_space(1))) * GlobalU8;
     const GlobalU8 a_ext0 = (GlobalU8)a_ext0i, a_pyr = (GlobalU8)a_pyri;
-    // ---- the strips of this block: one (NS == 1), or NS consecutive ones (the multi-strip form, round 6) ----
-    // Multi-strip form: a FAST block lives ~8.3 us of which ~2.2 are the latency of its tile's global loads, and under the pipeline FAST holds only 2 - 3 blocks per CU
-    // (the co-runners' registers), too few to hide it.  Here a block walks NS consecutive strips and the NEXT strip's tile lands in a second LDS buffer by LDS-DMA
-    // (global_load_lds_dwordx4: no registers for the data) while the current strip is scored: only the first strip of a block waits for memory.
+    // ---- the strip of this block ----
     const int total_strips = a_nstrips * a_batch;
-    const int gs_first = logical * NS, gs_end = min(gs_first + NS, total_strips);
+    const int gs_first = logical, gs_end = min(gs_first + 1, total_strips);
     if (gs_first >= total_strips) return;
     typedef const uint32_t __attribute__((address_space(4))) * ConstU32;
     // strip gs -> its image and the 8 dwords of its record in the plan's per-strip table (scalar: ONE s_load_dwordx8 through the constant address space)
@@ -1144,54 +1095,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CW <= 40 ? 
         r.t[0] = t0; r.t[1] = t1; r.t[2] = t2; r.t[3] = t3; r.t[4] = t4; r.t[5] = t5; r.t[6] = t6; r.t[7] = t7;
         return r;
     };
-    // multi-strip form: the tile of strip `rec` -> tile buffer q by LDS-DMA.  Lane i of a load writes LDS at (wave-uniform base) + 16 i, and a tile row is 12 pieces of
-    // 16 bytes (4 cells x 3), so piece p = 256 j + thread lies at 16 p: row p / 12, cell (p % 12) / 3, 16-byte group p % 3 — the global address is per lane.  Rows below the
-    // ROI, cells the strip does not have and columns past the row are CLAMPED to valid memory instead of staged as zeros: nothing ever reads them unmasked.
-    auto issue_tile = [&](const StripRec& r, int q, int tid) __attribute__((always_inline)) {
-        const int level = (int)(r.t[0] & 0xffu), hr = (int)(r.t[1] >> 16), iniY = (int)(r.t[1] & 0xffffu), iniX0 = (int)(r.t[2] & 0xffffu), wCell = (int)(r.t[2] >> 16);
-        const bool ext = level == 0 && r.b < a_ext0N;
-        const uint8_t* img = (const uint8_t*)(ext ? a_ext0 + (size_t)r.b * a_ext0Stride : a_pyr + (size_t)r.b * a_pyrStride + ((size_t)r.t[6] | ((size_t)r.t[7] << 32)));
-        const int ipitch = ext ? a_ext0Pitch : (int)r.t[4];
-        const uint32_t lds = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)(q ? &s_dyn[0] : &s_tile0[0])) + 1024u * (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6);
-#pragma unroll
-        for (int j = 0; j < (TROWS * 12 + 255) / 256; j++) {
-            const int pc = 256 * j + tid;
-            const int rr = pc / 12, col = pc - 12 * rr, c = col / 3, k = col - 3 * c;
-            const int x = min(iniX0 + c * wCell + 16 * k, ipitch - 16);
-            const uint8_t* src = img + (size_t)(iniY + min(rr, hr - 1)) * ipitch + x;
-            const uint32_t d = lds + 4096u * (uint32_t)j;
-            uint32_t keep;
-            if (pc < TROWS * 12)
-                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(src), "s"(d) : "memory");
-        }
-    };
     StripRec rec = load_rec(gs_first);
-    if constexpr (NS > 1) {
-        static_assert(NS == 1 || (G * ((CW + 6 + 15) / 16) == 12), "a tile row of the multi-strip form is 12 pieces");
-        if ((rec.t[0] >> 24) != 0) issue_tile(rec, 0, (int)threadIdx.x);
-    }
-    int par = 0;                                                       // tile buffer / state set of the current strip (NS > 1)
-    bool fresh = true;                                                 // the current strip's tile was issued after this wave's last wait for its loads (NS > 1, wave-uniform)
   for (int gs = gs_first; gs < gs_end; gs++) {
-    int tid_ = threadIdx.x;
-    if constexpr (NS > 1) asm volatile("" : "+v"(tid_));               // (inside a loop the compiler would hoist every lane-dependent invariant of the body into registers of its own)
-    const int tid = tid_;
-    uint8_t* const s_tile = (NS > 1 && par) ? s_dyn : s_tile0;
+    const int tid = threadIdx.x;
+    uint8_t* const s_tile = s_tile0;
     uint32_t* const s_list = reinterpret_cast<uint32_t*>(s_tile);
     uint8_t* const s_listc = s_tile + 4 * NLIST;
     uint32_t* const s_recz = reinterpret_cast<uint32_t*>(s_tile);
-    int* const s_ini = s_ini2[par];
-    int* const s_wc = s_wc2[par];
-    int& s_nlist = s_cnt2[par][0]; int& s_npair = s_cnt2[par][1]; int& s_ncorner = s_cnt2[par][2];
+    int& s_nlist = s_cnt[0]; int& s_npair = s_cnt[1]; int& s_ncorner = s_cnt[2];
     const int b = rec.b;
-    StripRec rec_next = rec;
-    if constexpr (NS > 1) { if (gs + 1 < gs_end) rec_next = load_rec(gs + 1); }      // scalar loads, in flight under this strip's work
+    const StripRec rec_next = rec;
     // what the next launch of this handle decides on is reported by a SAMPLE of the strips (a ratio of sums needs no more, and a few thousand
     // same-address atomics per launch cost nothing where 300 k of them serialise into milliseconds)
     const bool sampled = gs % max(1, total_strips >> 12) == 0;
     const uint4 e0 = make_uint4(rec.t[0], rec.t[1], rec.t[2], rec.t[3]), e1 = make_uint4(rec.t[4], rec.t[5], rec.t[6], rec.t[7]);
     const int level = (int)(e0.x & 0xffu), ci = (int)((e0.x >> 8) & 0xffu), cj0 = (int)((e0.x >> 16) & 0xffu), ncell = (int)(e0.x >> 24);
-    if (ncell == 0) { rec = rec_next; if constexpr (NS > 1) { if (gs + 1 < gs_end && (rec.t[0] >> 24) != 0) { issue_tile(rec, par, tid); fresh = true; } } continue; }      // :843 / :852 (decided when the plan was made); nothing of this strip was in flight
+    if (ncell == 0) continue;                                          // :843 / :852 (decided when the plan was made)
     const int iniY = (int)(e0.y & 0xffffu), hr = (int)(e0.y >> 16), hc = hr - 6;
     const int iniX0 = (int)(e0.z & 0xffffu), t_wCell = (int)(e0.z >> 16);
     const int pairs_total = (int)e1.y;
@@ -1225,14 +1144,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CW <= 40 ? 
         }
     };
     MYSLAM_BT_MARK(3);                                                 // (trace builds: the block's decode is done, its tile loads start here)
-    if constexpr (NS > 1) {
-        // this strip's tile is in flight (the block's first) or has landed (every wave waited for its own pieces before the previous strip's append)
-        prep();
-        if (fresh) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); fresh = false; }
-        __syncthreads();
-        // the next strip's tile -> the other buffer: the strip before this one kept its record list there, and every wave has left that strip (the barrier)
-        if (gs + 1 < gs_end && (rec_next.t[0] >> 24) != 0) issue_tile(rec_next, par ^ 1, tid);
-    } else if constexpr (G * NQC <= 16) {
+    if constexpr (G * NQC <= 16) {
         // all loads of a thread are issued before its LDS stores.  Unaligned 16-byte loads (a cell starts at any column); a load may run up
         // to 15 bytes past its row or, in the last row of the last plane, into the slack behind the pyramid block — those bytes are never used.
         // 16 lanes per tile row (G * NQC of them busy): (row, cell, 16-byte group) of a lane are bit fields of the thread index and its rows
@@ -1281,9 +1193,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CW <= 40 ? 
         __syncthreads();
     }
     MYSLAM_BT_MARK(0);
-#if MYSLAM_FAST_PHASE == 1
-    if (dense) return;
-#endif
 
     const s16x2 thv = {(short)P.minTh, (short)P.minTh};
     const int zoff = P.minTh - 1;                                      // the score map holds z = score - zoff
@@ -1443,15 +1352,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CW <= 40 ? 
                 const uint32_t* rp = reinterpret_cast<const uint32_t*>(&s_tile[(cy + j) * TP + c * CP + cx]);
                 r[j][0] = rp[0]; r[j][1] = rp[1]; r[j][2] = rp[2];
             }
-#if MYSLAM_FAST_PHASE == 2
-            {
-                uint32_t x = 0;
-                for (int j = 0; j < 8; j++) x ^= r[j][0] ^ r[j][1] ^ r[j][2];
-                *reinterpret_cast<uint32_t*>(&s_score[c][(cy + 1) * SP + 4 + cx]) = x & keepm;
-                if (cy + 1 < hc) *reinterpret_cast<uint32_t*>(&s_score[c][(cy + 2) * SP + 4 + cx]) = ~x & keepm;
-                return;
-            }
-#endif
             {
                 const s16x2 za = fast9_score_pair<0, 0, 8>(r, thv), zb = fast9_score_pair<1, 0, 8>(r, thv);
                 uint32_t ua, ub;
@@ -1494,9 +1394,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CW <= 40 ? 
         }
         __syncthreads();
         MYSLAM_BT_MARK(1);
-#if MYSLAM_FAST_PHASE >= 2 && MYSLAM_FAST_PHASE <= 4
-        return;
-#endif
         int nquad = 0;                     // 4-pixel rows that hold a corner: counted on the scalar unit (ballot + s_bcnt1), the statistic of this path
         // NMS on 4 x 4 pixel blocks (6 score-map rows x 3 dwords per lane, separable 3x3 maximum).  Every 4-pixel row that holds a strict
         // maximum leaves ONE record (its filtered z dword) in the strip's list — four ballots and one LDS atomic per wave and
@@ -1573,15 +1470,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CW <= 40 ? 
             }
         }
         if (lane == 0 && nquad) atomicAdd(&s_ncorner, nquad);
-#if MYSLAM_FAST_PHASE == 5
-        return;
-#endif
     }
     __syncthreads();
     MYSLAM_BT_MARK(2);
-    // multi-strip form: the next strip's tile was requested a whole scoring pass ago — this wave's pieces have landed by now; waiting for them HERE, in front of the
-    // append's own memory operations, keeps the wait from ever covering this strip's candidate stores
-    if constexpr (NS > 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if ((unsigned)tid == 0 && sampled) {                                 // the path statistics of this launch (see `sampled` above)
         atomicAdd(&ctl.cur[level * 4], (uint32_t)(dense ? s_ncorner : min(s_npair, NPAIR)));
         atomicAdd(&ctl.cur[level * 4 + 1], (uint32_t)pairs_total);
@@ -1657,7 +1548,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(CW <= 40 ? 
         }
     }
     }
-    rec = rec_next; par ^= (NS > 1 ? 1 : 0);
+    rec = rec_next;
   }
 }
 
@@ -1811,7 +1702,6 @@ __global__ __launch_bounds__(OT) void k_octree(OrbPlan P, const uint32_t* __rest
                                                const uint32_t* __restrict__ octTab,
                                                uint32_t* __restrict__ selOut, int32_t* __restrict__ selCount,
                                                int32_t* __restrict__ status, int NCmax, uint16_t* __restrict__ order, BlurMulti BM) {
-    MYSLAM_SIDE_PRIO();
     MYSLAM_BT(2);
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int t = threadIdx.x;
@@ -2382,9 +2272,7 @@ constexpr int DB_IT = 3;                                                        
 //   C  wave per keypoint  : blurred 37x37 window -> LDS, 4 steered BRIEF tests per lane
 
 constexpr int KD_KPB = 64;                                       // keypoints per block
-#ifndef MYSLAM_KD_GLDS                                              // windows a wave of the descriptor kernel keeps in flight in phase C (direct-to-LDS loads); 0 = the register-staged form
-#define MYSLAM_KD_GLDS 2
-#endif
+constexpr int KD_GLDS = 2;                                       // windows a wave of the descriptor kernel keeps in flight in phase C (direct-to-LDS loads)
 
 // Processing order of the descriptor kernel: the selected keys of a level in Z-order of small pixel tiles (a counting sort over
 // <= 1024 tile bins per (image, level); 32 x 32 pixels at 1241 x 376).  The oct-tree's list order scatters consecutive key-points all over the level; in tile order
@@ -2430,13 +2318,9 @@ __device__ __forceinline__ void describe_block(const OrbPlan& P, const uint8_t* 
                                                const uint16_t* __restrict__ order, const int logical_in MYSLAM_BT_PARAM) {
     const int logical = __builtin_amdgcn_readfirstlane(logical_in);      // block-uniform: everything derived from it stays on the scalar unit
     // per wave: phase A parks the 32 x 32 patches of four key-points here (4 x 64 pieces of 16 bytes), phase C the 37-row BRIEF window
-#if MYSLAM_KD_GLDS
-    // phase C keeps KD_NBUF windows per wave in flight (direct-to-LDS loads, below): KD_NBUF x 148 pieces per wave, and no less than phase A's 256
-    constexpr int KD_WB = DB_N * MYSLAM_KD_GLDS > 256 ? DB_N * MYSLAM_KD_GLDS : 256;
+    // phase C keeps KD_GLDS windows per wave in flight (direct-to-LDS loads, below): KD_GLDS x 148 pieces per wave, and no less than phase A's 256
+    constexpr int KD_WB = DB_N * KD_GLDS > 256 ? DB_N * KD_GLDS : 256;
     __shared__ __attribute__((aligned(16))) uint4 s_b[4][KD_WB];
-#else
-    __shared__ __attribute__((aligned(16))) uint4 s_b[4][256];
-#endif
     static_assert(DB_N <= 256, "the BRIEF window must fit the per-wave buffer");
     __shared__ int s_x[KD_KPB], s_y[KD_KPB], s_lv[KD_KPB], s_m10[KD_KPB], s_m01[KD_KPB], s_out[KD_KPB];
     __shared__ float s_ca[KD_KPB], s_sb[KD_KPB];
@@ -2587,119 +2471,63 @@ __device__ __forceinline__ void describe_block(const OrbPlan& P, const uint8_t* 
     for (int q = 0; q < 16; q++) pat[q] = (float)c_pattern[lane * 16 + q];
 #pragma unroll
     for (int q = 0; q < 16; q++) asm volatile("" : "+v"(pat[q]));      // kept as floats: the compiler otherwise re-converts the packed int8 pattern for every key-point
-#if MYSLAM_KD_GLDS
-    // Direct-to-LDS form (global_load_lds_dwordx4): a wave keeps the windows of its next MYSLAM_KD_GLDS - 1 key-points in flight while it tests the current one.  Under
+    // Direct-to-LDS form (global_load_lds_dwordx4): a wave keeps the windows of its next KD_GLDS - 1 key-points in flight while it tests the current one.  Under
     // the pipeline this kernel runs two blocks per CU and a key-point costs its wave one memory latency (~1.5 us on the loaded chip: 25 of an item's 39 us); a
     // register prefetch one window deep hid nothing of that (profiles/r06_ab_describe_prefetch.json) and cost 14 registers, i.e. FAST blocks.  The LDS-DMA load
     // needs no registers for its data: lane i of a load writes LDS at (wave-uniform base) + 16 i, so the ROW-MAJOR window (row r at 64 r, as the test points
     // address it) is had by letting lane i fetch piece (row i >> 2, 16-byte column i & 3) from the TILED plane — the global address is per lane, any pattern.
     // Three loads per window as before: rows 0-15, 16-31, 32-36 (20 lanes).  Completion: vmcnt, waited for by hand (the compiler does not see the asm loads);
     // loads retire in order among themselves, so `3 x (windows issued after this one)` outstanding operations prove this window landed whatever the stores do.
-    {
-        constexpr int NBUF = MYSLAM_KD_GLDS, NJ = KD_KPB / 4;
-        static_assert(NBUF >= 2 && NBUF <= 4, "windows in flight per wave");
-        const uint32_t lds0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)&s_b[0][0]) + (uint32_t)wave * (uint32_t)sizeof(s_b[0]);
-        auto level_of = [&](int j) -> int { return j < NJ ? __builtin_amdgcn_readfirstlane(s_lv[4 * j + wave]) : -1; };
-        auto issue = [&](int j, int level) __attribute__((always_inline)) {            // window of key-point 4 j + wave -> buffer j % NBUF (level >= 0, wave-uniform)
-            const int k = 4 * j + wave;
-            const LevelGeom& g = P.lv[level];
-            const int x = __builtin_amdgcn_readfirstlane(s_x[k]), y = __builtin_amdgcn_readfirstlane(s_y[k]);
-            const int xb0 = (x - DB_R) & ~15, y0 = y - DB_R, pitch8 = g.pitch * 8;
-            const uint8_t* base = blur + (size_t)b * pyrStride + g.imgOff + (size_t)(xb0 >> 4) * 128;
-            const int yy = y0 + (lane >> 2);                                           // this lane's row of the first load; the others are 16 and 32 rows = 2 and 4 tile rows below
-            const uint32_t voff = (uint32_t)__mul24(yy >> 3, pitch8) + (uint32_t)((yy & 7) << 4) + (uint32_t)((lane & 3) << 7);
-            const uint32_t dst = lds0 + (uint32_t)(j % NBUF) * (uint32_t)(DB_N * 16);
-#pragma unroll
-            for (int q = 0; q < DB_IT; q++) {
-                const uint8_t* src = base + (size_t)voff + (size_t)q * 2 * (size_t)pitch8;
-                const uint32_t d = dst + 1024u * (uint32_t)q;
-                uint32_t keep;
-                if (q < 2 || lane < DB_N - 128)
-                    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(src), "s"(d) : "memory");
-            }
-        };
-        int lv_cur = level_of(0);
-        int lv_n[NBUF - 1];
-#pragma unroll
-        for (int u = 0; u < NBUF - 1; u++) { lv_n[u] = level_of(u + 1); }
-        if (lv_cur >= 0) issue(0, lv_cur);
-#pragma unroll
-        for (int u = 0; u + 1 < NBUF - 1; u++) if (lv_n[u] >= 0) issue(u + 1, lv_n[u]);
-        for (int j = 0; j < NJ; j++) {
-            // the window NBUF - 1 key-points ahead goes into the buffer key-point j - 1 has just been tested from
-            if (lv_n[NBUF - 2] >= 0) issue(j + NBUF - 1, lv_n[NBUF - 2]);
-            int newer = 0;
-#pragma unroll
-            for (int u = 0; u < NBUF - 1; u++) newer += lv_n[u] >= 0 ? 1 : 0;
-            const int level = lv_cur;
-            lv_cur = lv_n[0];
-#pragma unroll
-            for (int u = 0; u + 1 < NBUF - 1; u++) lv_n[u] = lv_n[u + 1];
-            lv_n[NBUF - 2] = level_of(j + NBUF);
-            if (level < 0) continue;
-            if (newer == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if (newer == 1) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-            else if (newer == 2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-            const int k = 4 * j + wave;
-            const int x = __builtin_amdgcn_readfirstlane(s_x[k]);
-            const float ca = s_ca[k], sb = s_sb[k];
-            const int offB = (x - DB_R) & 15;
-            const uint8_t* center = reinterpret_cast<const uint8_t*>(s_b[wave]) + (j % NBUF) * (DB_N * 16) + DB_R * DB_P + offB + DB_R;
-            uint32_t nib = 0;
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const float x0 = pat[4 * q], y0 = pat[4 * q + 1], x1 = pat[4 * q + 2], y1 = pat[4 * q + 3];
-                constexpr float RM = 12582912.f; constexpr uint32_t RK = 0x4B400000u;            // cvRound by the magic-number add, as in the register-staged form below
-                const uint32_t r0 = __float_as_uint(__fadd_rn(__fadd_rn(__fmul_rn(x0, sb), __fmul_rn(y0, ca)), RM));
-                const uint32_t c0 = __float_as_uint(__fadd_rn(__fsub_rn(__fmul_rn(x0, ca), __fmul_rn(y0, sb)), RM));
-                const uint32_t r1 = __float_as_uint(__fadd_rn(__fadd_rn(__fmul_rn(x1, sb), __fmul_rn(y1, ca)), RM));
-                const uint32_t c1 = __float_as_uint(__fadd_rn(__fsub_rn(__fmul_rn(x1, ca), __fmul_rn(y1, sb)), RM));
-                static_assert(DB_P == 64, "row pitch of the LDS window as a shift");
-                const int t0 = center[(int)((r0 << 6) + c0 - 65u * RK)], t1 = center[(int)((r1 << 6) + c1 - 65u * RK)];
-                nib |= (uint32_t)(t0 < t1) << q;
-            }
-            const uint32_t byte = nib | (__shfl_down(nib, 1, 64) << 4);
-            uint32_t w = byte | (__shfl_down(byte, 2, 64) << 8);
-            w |= (__shfl_down(byte, 4, 64) << 16) | (__shfl_down(byte, 6, 64) << 24);
-            if ((lane & 7) == 0) reinterpret_cast<uint32_t*>(desc + ((size_t)b * cap + s_out[k]) * 32)[lane >> 3] = w;
-        }
-    }
-    return;
-#endif
-    for (int j = 0; j < KD_KPB / 4; j++) {
-        const int k = 4 * j + wave;                                   // the four waves work on neighbouring key-points of the tile order: their windows overlap in L1
-        const int level = __builtin_amdgcn_readfirstlane(s_lv[k]);
-        if (level < 0) continue;
+    constexpr int NBUF = KD_GLDS, NJ = KD_KPB / 4;
+    static_assert(NBUF >= 2 && NBUF <= 4, "windows in flight per wave");
+    const uint32_t lds0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)&s_b[0][0]) + (uint32_t)wave * (uint32_t)sizeof(s_b[0]);
+    auto level_of = [&](int j) -> int { return j < NJ ? __builtin_amdgcn_readfirstlane(s_lv[4 * j + wave]) : -1; };
+    auto issue = [&](int j, int level) __attribute__((always_inline)) {            // window of key-point 4 j + wave -> buffer j % NBUF (level >= 0, wave-uniform)
+        const int k = 4 * j + wave;
         const LevelGeom& g = P.lv[level];
         const int x = __builtin_amdgcn_readfirstlane(s_x[k]), y = __builtin_amdgcn_readfirstlane(s_y[k]);
+        const int xb0 = (x - DB_R) & ~15, y0 = y - DB_R, pitch8 = g.pitch * 8;
+        const uint8_t* base = blur + (size_t)b * pyrStride + g.imgOff + (size_t)(xb0 >> 4) * 128;
+        const int yy = y0 + (lane >> 2);                                           // this lane's row of the first load; the others are 16 and 32 rows = 2 and 4 tile rows below
+        const uint32_t voff = (uint32_t)__mul24(yy >> 3, pitch8) + (uint32_t)((yy & 7) << 4) + (uint32_t)((lane & 3) << 7);
+        const uint32_t dst = lds0 + (uint32_t)(j % NBUF) * (uint32_t)(DB_N * 16);
+#pragma unroll
+        for (int q = 0; q < DB_IT; q++) {
+            const uint8_t* src = base + (size_t)voff + (size_t)q * 2 * (size_t)pitch8;
+            const uint32_t d = dst + 1024u * (uint32_t)q;
+            uint32_t keep;
+            if (q < 2 || lane < DB_N - 128)
+                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "v"(src), "s"(d) : "memory");
+        }
+    };
+    int lv_cur = level_of(0);
+    int lv_n[NBUF - 1];
+#pragma unroll
+    for (int u = 0; u < NBUF - 1; u++) { lv_n[u] = level_of(u + 1); }
+    if (lv_cur >= 0) issue(0, lv_cur);
+#pragma unroll
+    for (int u = 0; u + 1 < NBUF - 1; u++) if (lv_n[u] >= 0) issue(u + 1, lv_n[u]);
+    for (int j = 0; j < NJ; j++) {
+        // the window NBUF - 1 key-points ahead goes into the buffer key-point j - 1 has just been tested from
+        if (lv_n[NBUF - 2] >= 0) issue(j + NBUF - 1, lv_n[NBUF - 2]);
+        int newer = 0;
+#pragma unroll
+        for (int u = 0; u < NBUF - 1; u++) newer += lv_n[u] >= 0 ? 1 : 0;
+        const int level = lv_cur;
+        lv_cur = lv_n[0];
+#pragma unroll
+        for (int u = 0; u + 1 < NBUF - 1; u++) lv_n[u] = lv_n[u + 1];
+        lv_n[NBUF - 2] = level_of(j + NBUF);
+        if (level < 0) continue;
+        if (newer == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        else if (newer == 1) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
+        else if (newer == 2) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
+        const int k = 4 * j + wave;
+        const int x = __builtin_amdgcn_readfirstlane(s_x[k]);
         const float ca = s_ca[k], sb = s_sb[k];
-        const int xb0 = (x - DB_R) & ~15, offB = (x - DB_R) - xb0;
-        // The window in the TILED blurred plane: 4 tile columns (64 bytes at a 16-byte aligned column) x the 5 or 6 tile rows that hold
-        // image rows y - 18 .. y + 18; chunk i = lane + 64 q in memory order (tile row i >> 5, tile column (i >> 3) & 3, row of the tile
-        // i & 7): lanes 0-31 and 32-63 of a load each read 512 contiguous bytes = 4 whole cache lines; chunks of rows outside the window
-        // are not requested.  The fourth tile column may lie past the image width (row padding or the next tile row): never read by a
-        // test point.  The chunks land in LDS in row-major order (DB_P bytes per window row), where the test points address them.
-        const int y0 = y - DB_R;
-        const uint8_t* bl = blur + (size_t)b * pyrStride + g.imgOff + (size_t)(y0 >> 3) * g.pitch * 8 + (size_t)(xb0 >> 4) * 128;
-        uint4 rb[DB_IT];
-#pragma unroll
-        for (int q = 0; q < DB_IT; q++) {
-            const int i = lane + 64 * q;
-            const int wr = ((i >> 5) << 3) + (i & 7) - (y0 & 7);              // window row of the chunk
-            rb[q] = (wr >= 0 && wr < DB_ROWS) ? *reinterpret_cast<const uint4*>(bl + (uint32_t)(__mul24(i >> 5, g.pitch * 8) + 16 * (i & 31))) : make_uint4(0, 0, 0, 0);
-        }
-        __builtin_amdgcn_wave_barrier();                                  // previous keypoint's window reads are done (same wave)
-#pragma unroll
-        for (int q = 0; q < DB_IT; q++) {
-            const int i = lane + 64 * q;
-            const int wr = ((i >> 5) << 3) + (i & 7) - (y0 & 7);
-            if (wr >= 0 && wr < DB_ROWS) s_b[wave][wr * 4 + ((i >> 3) & 3)] = rb[q];
-        }
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        const uint8_t* center = reinterpret_cast<const uint8_t*>(s_b[wave]) + DB_R * DB_P + offB + DB_R;
+        const int offB = (x - DB_R) & 15;
+        const uint8_t* center = reinterpret_cast<const uint8_t*>(s_b[wave]) + (j % NBUF) * (DB_N * 16) + DB_R * DB_P + offB + DB_R;
         uint32_t nib = 0;
 #pragma unroll
         for (int q = 0; q < 4; q++) {
@@ -2715,9 +2543,9 @@ __device__ __forceinline__ void describe_block(const OrbPlan& P, const uint8_t* 
             const int t0 = center[(int)((r0 << 6) + c0 - 65u * RK)], t1 = center[(int)((r1 << 6) + c1 - 65u * RK)];
             nib |= (uint32_t)(t0 < t1) << q;
         }
-        const uint32_t byte = nib | (__shfl_down(nib, 1, 64) << 4);            // valid on even lanes
+        const uint32_t byte = nib | (__shfl_down(nib, 1, 64) << 4);
         uint32_t w = byte | (__shfl_down(byte, 2, 64) << 8);
-        w |= (__shfl_down(byte, 4, 64) << 16) | (__shfl_down(byte, 6, 64) << 24);   // valid on lanes % 8 == 0
+        w |= (__shfl_down(byte, 4, 64) << 16) | (__shfl_down(byte, 6, 64) << 24);
         if ((lane & 7) == 0) reinterpret_cast<uint32_t*>(desc + ((size_t)b * cap + s_out[k]) * 32)[lane >> 3] = w;
     }
 }
@@ -2740,7 +2568,6 @@ __global__ __launch_bounds__(256) void k_describe2(OrbPlan P, const uint8_t* __r
                                                    uint8_t* __restrict__ desc, int32_t* __restrict__ counts,
                                                    int32_t* __restrict__ status, int cap, int nchunk, int batch, int detectOnly,
                                                    const uint16_t* __restrict__ order) {
-    MYSLAM_SIDE_PRIO();
     const int total = nchunk * batch, nwg = gridDim.x, bid = blockIdx.x;
     const int xcd = bid & 7, j = bid >> 3, per = (nwg + 7 - xcd) >> 3;              // blocks of this XCD: ids xcd, xcd + 8, ...
     const int tq = total >> 3, tr = total & 7;
@@ -2995,10 +2822,8 @@ bool resize_uses_strips(const ResizeArgs& a) { return a.scale_y >= 1.0 && a.scal
 
 bool resize_is_little(const ResizeArgs& a, int batch) { return a.n0 == 0 && (size_t)batch * a.dw * a.dh < (size_t)1500000; }
 
-#ifndef MYSLAM_RESIZE_CHAIN_MAX        // A/B builds (tools/build_variants.sh): levels per launch of the small-batch pyramid (1 = a launch per level)
-#define MYSLAM_RESIZE_CHAIN_MAX 3
-#endif
-int resize_chain_max() { return MYSLAM_RESIZE_CHAIN_MAX < RC_MAX ? MYSLAM_RESIZE_CHAIN_MAX : RC_MAX; }
+constexpr int RESIZE_CHAIN_MAX = 3;    // levels per launch of the small-batch pyramid (1 = a launch per level)
+int resize_chain_max() { return RESIZE_CHAIN_MAX < RC_MAX ? RESIZE_CHAIN_MAX : RC_MAX; }
 
 static ResizeChain make_chain(const ResizeArgs* lv, int n) {
     ResizeChain c;
@@ -3028,10 +2853,8 @@ void launch_pyr_head(const ResizeArgs* lv, int n, int rows, int cols, uint8_t* d
 // (measured at 1 pair x 16 lanes, tools/ab_stream_mode.sh, us per step / graph nodes: no head launch, chains of 3: 89.3 / 18; head of 2 levels + chains of 3:
 // 85.2 / 17; head of 3 + chains of 2: 86.9 / 17; head of 3 + one chain of 4: 86.5 / 16 — a node costs ~4.6 us, and the 21 / 85 interpolations per
 // pixel of a third / fourth chained level begin to cost as much)
-#ifndef MYSLAM_PYR_HEAD_LEVELS         // A/B builds: levels the head launch of a small batch produces (0 = no head launch)
-#define MYSLAM_PYR_HEAD_LEVELS 2
-#endif
-int pyr_head_levels() { return MYSLAM_PYR_HEAD_LEVELS < 3 ? MYSLAM_PYR_HEAD_LEVELS : 3; }
+constexpr int PYR_HEAD_LEVELS = 2;     // levels the head launch of a small batch produces (0 = no head launch)
+int pyr_head_levels() { return PYR_HEAD_LEVELS < 3 ? PYR_HEAD_LEVELS : 3; }
 
 void launch_resize(const ResizeArgs& a, int batch, hipStream_t s) {
     // register strips cover pyramid scale factors up to 1.25 (rows) / 1.6 (columns); larger steps take the generic kernel — and so do
@@ -3087,14 +2910,11 @@ void launch_blur_levels(const BlurArgs* lv, int n, int batch, hipStream_t s) {
     if (X.n) hipLaunchKernelGGL(k_blur7_mfma, dim3((X.wave0[X.n] + 3) / 4, 1, batch), dim3(256), 0, s, X);
 }
 
-#ifndef MYSLAM_BLUR_WITH_OCTREE        // A/B builds (tools/build_variants.sh): 0 = the Gaussian keeps its own launch
-#define MYSLAM_BLUR_WITH_OCTREE 1
-#endif
 // small batches: all levels as register strips in the oct-tree's launch — possible when every level takes the strip form (no matrix-core option, aligned planes)
 static bool blur_multi_for_octree(const BlurArgs* lv, int n, int batch, BlurMulti& M) {
     // (up to 4 pairs per call: +5 % frames/s at 1 - 2 pairs, even at 4; at 8 and 16 pairs the bands, which then wait for 512-thread blocks with the
     // oct-tree's LDS, cost 1 - 3 %: profiles/r05_ab_pairs_8_16.log)
-    if (!MYSLAM_BLUR_WITH_OCTREE || batch >= OCT_WIDE_BELOW || batch >= 16) return false;
+    if (batch >= OCT_WIDE_BELOW || batch >= 16) return false;
     M.n = 0; M.wave0[0] = 0;
     for (int i = 0; i < n; i++) {
         if (blur_form(lv[i]) != BlurForm::Strip) return false;
@@ -3110,15 +2930,6 @@ void launch_fast(const OrbPlan& P, const uint8_t* pyr, size_t pyrStride, const u
     const FastCtl ctl{statPrev, statCur, forceMode};
     const dim3 grid((unsigned)P.nstrips * (unsigned)batch);
     constexpr int pad = FastLds<32, 4, 40>::PAD;                          // dynamic LDS: see FastLds
-#if MYSLAM_FAST_NS > 1
-    // the multi-strip form (blocks of MYSLAM_FAST_NS consecutive strips, the next strip's tile prefetched by LDS-DMA) for launches that fill the chip several times over
-    if (cw <= 32 && ch <= 40 && (size_t)P.nstrips * batch >= (size_t)MYSLAM_FAST_NS * 256 * 6 * 4) {
-        const dim3 gridms((unsigned)(((size_t)P.nstrips * batch + MYSLAM_FAST_NS - 1) / MYSLAM_FAST_NS));
-        constexpr int padms = FastLds<32, 4, 40, MYSLAM_FAST_NS>::PAD + FastLds<32, 4, 40, MYSLAM_FAST_NS>::TROWS * FastLds<32, 4, 40, MYSLAM_FAST_NS>::TP + 16;      // the second tile buffer + the pad
-        hipLaunchKernelGGL((k_fast_strip<32, 4, 40, MYSLAM_FAST_NS>), gridms, dim3(256), padms, s, P, pyr, pyrStride, maskPyr, cand, candCount, ctl, batch);
-        return;
-    }
-#endif
     if (cw <= 32 && ch <= 40) hipLaunchKernelGGL((k_fast_strip<32, 4, 40>), grid, dim3(256), pad, s, P, pyr, pyrStride, maskPyr, cand, candCount, ctl, batch);
     else if (max(cw, ch) <= 40) hipLaunchKernelGGL((k_fast_strip<40, 4>), grid, dim3(256), 0, s, P, pyr, pyrStride, maskPyr, cand, candCount, ctl, batch);
     else hipLaunchKernelGGL((k_fast_strip<MAX_CELL, 4>), grid, dim3(256), 0, s, P, pyr, pyrStride, maskPyr, cand, candCount, ctl, batch);

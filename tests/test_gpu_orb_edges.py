@@ -68,6 +68,24 @@ def test_single_image(api, oracle, case, fast_mode):
     assert k0.tobytes() == r0.tobytes(), (case.name, "oct-tree (Detect)", _explain(k0, r0))
 
 
+@pytest.mark.parametrize("fast_mode", [0, 1])
+def test_strip_without_cells(api, oracle, fast_mode):
+    """62 x 903 at one level, the smallest image whose plan holds a strip of no cell: the FAST area is 871 px wide, its 29 grid columns of
+    ceil(871 / 29) = 31 px overshoot it, the last column starts past the area (ORBextractor.cpp:852 skips it) and is the only cell of the
+    row's eighth strip of four — that strip's block of k_fast_strip returns as soon as it has read its record"""
+    h, w = 62, 903
+    ncols = (w - 32) // 30
+    wcell = -(-(w - 32) // ncols)
+    assert ncols % 4 == 1 and 16 + (ncols - 1) * wcell >= w - 16 - 6
+    img = _fillers(h, w)[1]
+    ext = api.ORBextractor(300, 1.2, 1)
+    ext.set_option(ext.OPT_FAST_MODE, fast_mode)
+    xs, ys, sc = ext.debug_candidates(img, 0)
+    rx, ry, rs = oracle.grid_fast(img, 20, 7)
+    assert sorted(zip(xs.tolist(), ys.tolist(), sc.tolist())) == sorted(zip(rx.tolist(), ry.tolist(), rs.tolist())) and len(rx) > 0
+    _assert_same(ext.DetectAndCompute(img), _want(oracle, img, (300, 1.2, 1, 20, 7)), "DetectAndCompute")
+
+
 # ------------------------------------------------------------------------------------------------------------------------ batches
 def _fillers(h, w):
     rng = np.random.default_rng(h * 1000 + w)

@@ -9,7 +9,7 @@ for rep in 1 2; do
 for f in $D/lib*.so; do
   n=$(basename $f .so)
   cp $f $P/libmyslam_hip.so
-  python bench.py --full --no-cpu-baseline "$@" > $OUT/ab_${n}_$rep.json 2> $OUT/ab_${n}_$rep.err
+  timeout -k 10 ${BENCH_TIMEOUT:-900} python bench.py --full --no-cpu-baseline "$@" > $OUT/ab_${n}_$rep.json 2> $OUT/ab_${n}_$rep.err || { echo "$n rep $rep: bench rc=$?, stopping"; tail -3 $OUT/ab_${n}_$rep.err; cp /tmp/orig_lib.so $P/libmyslam_hip.so; exit 1; }
   python - <<PY
 import json
 try:

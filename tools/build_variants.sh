@@ -1,6 +1,6 @@
 #!/bin/bash
 # Builds A/B variants of the library into tools/build/ab/<name>/lib<name>.so from -D switches of ONE translation unit (the others are
-# taken from the in-tree build):   tools/build_variants.sh <unit.hip> name1:"-DX=1" name2:"-DX=2 -DY" ...
+# taken from the in-tree build):   tools/build_variants.sh <unit.hip> name1:"-DX" name2:"-DX -DY=2" ...   (e.g. orb_kernels.hip bt:-DMYSLAM_BLOCK_TRACE, the trace build)
 # (cross-compiles here; the .so files travel to the GPU box with the snapshot; tools/build is git-ignored)
 set -e
 P=a-simple-stereo-slam-system-with-deep-loop-closing_amd

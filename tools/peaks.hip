@@ -1,7 +1,7 @@
 // tools/peaks.hip — measures the peaks bench.py's roofline objects are normalised against, on the box the bench runs on.
 //
 //   hipcc --offload-arch=gfx950 -O3 -o tools/build/peaks tools/peaks.hip && tools/build/peaks > profiles/r03_peaks.json
-//   (tools/peaks.py does both and is what tools/gpu_round.sh calls)
+//   (tools/peaks.py does both)
 //
 // What it measures (all on one MI355X, default stream, HIP-event timed, best of `REPS` launches):
 //   * hbm:   float4 copy / read-only / write-only GB/s on buffers far beyond the 256 MiB Infinity Cache
