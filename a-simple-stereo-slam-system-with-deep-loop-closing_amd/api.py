@@ -1771,6 +1771,124 @@ class LoopKeyFrameStore:
 
 LoopStore = LoopKeyFrameStore                          # the handle's name in the C ABI (myslam_loop_store)
 
+LOOP_BANK_TURN, LOOP_BANK_SKIPPED, LOOP_BANK_IDLE, LOOP_BANK_CLOSED, LOOP_BANK_STORED = 0, 1, 2, 3, 4      # MYSLAM_LOOP_BANK_*
+
+
+class LoopBankArrays(C.Structure):                     # myslam_loop_bank_arrays
+    _fields_ = [(k, C.c_void_p) for k in ("kps", "desc", "feat_landmark", "rows", "n_feat", "ids", "n", "last_closed", "put_slot")] + \
+               [(k, C.c_int32) for k in ("streams", "kfs_per_stream", "cap", "feat_cap")] + [("cap_stride", C.c_int64), ("feat_stride", C.c_int64)]
+
+
+class LoopStoreBank:
+    """S per-stream loop key-frame stores in device memory (myslam_loop_bank_*), item s = stream s, with LoopClosing::InsertNewKeyFrame's
+    five-key-frames rule (src/loopclosing.cpp:671-681), DetectLoop's decision and lookup (:147, :151) by LoopDatabaseBank.query_batch's best row,
+    `if(!bConfirmedLoopKF) AddToDatabase()` (:73-75) and _mpLastClosedKF (:331) on the device.  gate / detect / finish / set_links / clear take device
+    pointers as ints, enqueue on the handle's stream and return (recordable, StepGraph); load / get / sizes are synchronous and take numpy arrays."""
+
+    def __init__(self, streams, kfs_per_stream, cap, feat_cap, stream=None):
+        self.streams, self.kfs_per_stream, self.cap, self.feat_cap = int(streams), int(kfs_per_stream), int(cap), int(feat_cap)
+        self._h = C.c_void_p()
+        _check(lib().myslam_loop_bank_create(C.byref(self._h), self.streams, self.kfs_per_stream, self.cap, self.feat_cap), "myslam_loop_bank_create")
+        if stream is not None:
+            self.set_stream(stream)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and self._h.value and _lib is not None:
+            _lib.myslam_loop_bank_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def set_stream(self, stream):
+        _check(lib().myslam_loop_bank_set_stream(self._h, C.c_void_p(stream)), "myslam_loop_bank_set_stream")
+
+    @staticmethod
+    def launches_per_finish():
+        return lib().myslam_loop_bank_launches_per_finish()
+
+    def gate_batch(self, d_new_kf_id, d_item_status, status_stride, d_active, d_status):
+        """d_new_kf_id S i64 (-1: none), d_item_status None or Mapper's d_status with its stride -> d_active S i32 (LoopDatabaseBank.query_batch's),
+        d_status S i32: LOOP_BANK_TURN / _SKIPPED (one of the five behind a closed loop) / _IDLE"""
+        vp = lambda p: C.c_void_p(p or None)
+        _check(lib().myslam_loop_bank_gate_batch(self._h, vp(d_new_kf_id), vp(d_item_status), int(status_stride), vp(d_active), vp(d_status)),
+               "myslam_loop_bank_gate_batch")
+
+    def detect_batch(self, d_best_id, d_best_row, d_max_score, d_cnt, d_loop_desc, d_n_loop, d_loop_pyr, d_loop_feat_landmark, d_loop_slot, d_status,
+                     thr_high=0.94, max_suspected=3):
+        """LoopKeyFrameStore.detect_batch per stream over LoopDatabaseBank.query_batch's four outputs; the key-frame is the one at d_best_row, which
+        must carry d_best_id (else ERR_INVALID for that stream).  One launch."""
+        vp = lambda p: C.c_void_p(p or None)
+        _check(lib().myslam_loop_bank_detect_batch(self._h, vp(d_best_id), vp(d_best_row), vp(d_max_score), vp(d_cnt), C.c_float(thr_high),
+                                                   int(max_suspected), vp(d_loop_desc), vp(d_n_loop), vp(d_loop_pyr), vp(d_loop_feat_landmark),
+                                                   vp(d_loop_slot), vp(d_status)), "myslam_loop_bank_detect_batch")
+
+    def finish_batch(self, d_cur_kf_id, d_active, d_verify_status, d_pyr_kps, d_desc, d_counts, d_kf_status, d_feat_landmark, d_n_feat, d_add, d_status):
+        """per stream: idle / VERIFY_CONFIRMED -> LOOP_BANK_CLOSED (last_closed moves, nothing stored) / ERR_CAPACITY / ERR_INVALID (id not above the
+        last one held) / LOOP_BANK_STORED (item s of LoopKeyFrameStore.put_batch's inputs goes into the stream's next slot).  d_add S i32 is
+        LoopDatabaseBank.append_batch's.  Two launches."""
+        vp = lambda p: C.c_void_p(p or None)
+        _check(lib().myslam_loop_bank_finish_batch(self._h, vp(d_cur_kf_id), vp(d_active), vp(d_verify_status), vp(d_pyr_kps), vp(d_desc), vp(d_counts),
+                                                   vp(d_kf_status), vp(d_feat_landmark), vp(d_n_feat), vp(d_add), vp(d_status)),
+               "myslam_loop_bank_finish_batch")
+
+    def set_links_batch(self, d_kf_id, d_tag, d_value, d_n, list_cap, d_pending_kf_id=None, d_pending_feat_landmark=None, d_n_set=None):
+        """LoopKeyFrameStore.set_links_batch (d_value None: clear_links_batch) with item s walked against stream s's key-frames only.  One launch."""
+        vp = lambda p: C.c_void_p(p or None)
+        _check(lib().myslam_loop_bank_links_batch(self._h, vp(d_kf_id), vp(d_tag), vp(d_value), vp(d_n), int(list_cap), vp(d_pending_kf_id),
+                                                      vp(d_pending_feat_landmark), vp(d_n_set)), "myslam_loop_bank_links_batch")
+
+    def clear_batch(self, d_reset):
+        """d_reset S i32: the streams with a non-zero entry hold nothing and have closed no loop afterwards"""
+        _check(lib().myslam_loop_bank_clear_batch(self._h, C.c_void_p(d_reset or None)), "myslam_loop_bank_clear_batch")
+
+    def view(self):
+        """LoopBankArrays: the device pointers (ints) and shapes"""
+        v = LoopBankArrays()
+        _check(lib().myslam_loop_bank_view(self._h, C.byref(v)), "myslam_loop_bank_view")
+        return v
+
+    def read_view(self):
+        """the whole allocation as numpy arrays, bytes behind the counts included: dict(kps [S, K, cap_st], desc [S, K, cap_st, 32], lm [S, K, feat_st],
+        rows, nfeat, ids [S, K], n, last_closed, put_slot [S]); waits for nothing but its own copies"""
+        v = self.view()
+        S, K, cs, fs = v.streams, v.kfs_per_stream, v.cap_stride, v.feat_stride
+        out = dict(kps=np.empty((S, K, cs), KP_DTYPE), desc=np.empty((S, K, cs, 32), np.uint8), lm=np.empty((S, K, fs), np.int32),
+                   rows=np.empty((S, K), np.int32), nfeat=np.empty((S, K), np.int32), ids=np.empty((S, K), np.uint64), n=np.empty(S, np.int32),
+                   last_closed=np.empty(S, np.int64), put_slot=np.empty(S, np.int32))
+        ptr = dict(kps=v.kps, desc=v.desc, lm=v.feat_landmark, rows=v.rows, nfeat=v.n_feat, ids=v.ids, n=v.n, last_closed=v.last_closed, put_slot=v.put_slot)
+        for k, a in out.items():
+            _check(lib().myslam_debug_peek(C.c_void_p(ptr[k]), _p(a), a.nbytes), "myslam_debug_peek")
+        return out
+
+    def load(self, s, ids, kps, desc, rows, feat_landmark, n_feat, last_closed=-1):
+        """replaces stream s (host arrays): ids [n] ascending, kps [n, cap] KP_DTYPE, desc [n, cap, 32] u8, rows [n], feat_landmark [n, feat_cap] i32,
+        n_feat [n]; MyslamError(INVALID / CAPACITY) as the header says, the stream keeps every byte then"""
+        ids = np.ascontiguousarray(ids, np.uint64)
+        n = len(ids)
+        if n == 0:                  # an empty stream: only the count and last_closed are written
+            _check(lib().myslam_loop_bank_load(self._h, int(s), None, None, None, None, None, None, 0, int(last_closed)), "myslam_loop_bank_load")
+            return
+        kps = np.ascontiguousarray(kps, KP_DTYPE).reshape(n, self.cap); desc = np.ascontiguousarray(desc, np.uint8).reshape(n, self.cap, 32)
+        lm = np.ascontiguousarray(feat_landmark, np.int32).reshape(n, self.feat_cap)
+        rows = np.ascontiguousarray(rows, np.int32).reshape(n); n_feat = np.ascontiguousarray(n_feat, np.int32).reshape(n)
+        a = [_p(x) if n else None for x in (ids, kps, desc, rows, lm, n_feat)]
+        _check(lib().myslam_loop_bank_load(self._h, int(s), *a, n, int(last_closed)), "myslam_loop_bank_load")
+
+    def get(self, s):
+        """the whole of stream s: dict(ids [n], kps [n, cap], desc [n, cap, 32], rows [n], lm [n, feat_cap], nfeat [n], last_closed)"""
+        K = self.kfs_per_stream
+        ids = np.zeros(K, np.uint64); kps = np.zeros((K, self.cap), KP_DTYPE); desc = np.zeros((K, self.cap, 32), np.uint8)
+        rows = np.zeros(K, np.int32); lm = np.zeros((K, self.feat_cap), np.int32); nf = np.zeros(K, np.int32)
+        n, last = C.c_int(), C.c_int64()
+        _check(lib().myslam_loop_bank_get(self._h, int(s), _p(ids), _p(kps), _p(desc), _p(rows), _p(lm), _p(nf), K, C.byref(n), C.byref(last)),
+               "myslam_loop_bank_get")
+        k = n.value
+        return dict(ids=ids[:k].copy(), kps=kps[:k].copy(), desc=desc[:k].copy(), rows=rows[:k].copy(), lm=lm[:k].copy(), nfeat=nf[:k].copy(),
+                    last_closed=last.value)
+
+    def sizes(self):
+        n = np.zeros(self.streams, np.int32)
+        _check(lib().myslam_loop_bank_sizes(self._h, _p(n)), "myslam_loop_bank_sizes")
+        return n
+
 
 def loop_correct_structure(n_kf, active, loop, edge_v0, edge_v1):
     """The separator rule of LoopCorrector.correct_batch for one map, on the host -> (separators, chain length, supported)"""

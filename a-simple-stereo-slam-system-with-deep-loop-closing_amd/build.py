@@ -38,6 +38,7 @@ UNITS = {
     "loop_correct.hip": [],
     "backend.hip": [],                     # integer scans and copies; the solve stays in ba.hip
     "loop_store.hip": [],                  # copies and two compares: nothing a contraction could change
+    "loop_bank.hip": [],                   # the store's copies and integer decisions per stream
     "map_archive.hip": EXACT,              # the odometry edge's measurement is the hosts' f64 arithmetic, operation by operation
     "obs_archive.hip": [],                 # integer code and copies
     "relink.hip": [],                      # integer code and copies

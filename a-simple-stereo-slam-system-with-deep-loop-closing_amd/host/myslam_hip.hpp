@@ -964,6 +964,80 @@ public:
     }
 };
 
+// One LoopKeyFrameStore per stream of a bank, in device memory, with the decisions of LoopClosingRun between the batched units on the device:
+// LoopClosing::InsertNewKeyFrame's five-key-frames rule (src/loopclosing.cpp:671-681), DetectLoop's decision and `_mvDatabase.at(bestId)` (:147, :151) by
+// the row LoopDatabaseBank::QueryBatch found, `if(!bConfirmedLoopKF) AddToDatabase()` (:73-75) and `_mpLastClosedKF = _mpCurrentKF` (:331).  Device
+// pointers, S entries each; every Batch call enqueues on the handle's stream and returns, and can be recorded.  Load / Get / Sizes take host memory and wait.
+class LoopKeyFrameStoreBank {
+    myslam_loop_bank* h_ = nullptr;
+    int streams_, kfsPerStream_, cap_, featCap_;
+public:
+    struct Stream {                 // one stream in host memory: whole slots, kps n x cap, desc n x cap x 32, featureLandmark n x featCap
+        std::vector<uint64_t> ids; std::vector<KeyPoint> kps; std::vector<uint8_t> desc; std::vector<int32_t> rows, featureLandmark, nFeatures;
+        int64_t lastClosedKFId = -1;        // _mpLastClosedKF->mnKFId, -1 = nullptr
+    };
+    LoopKeyFrameStoreBank(int streams, int kfsPerStream, int cap, int featCap) : streams_(streams), kfsPerStream_(kfsPerStream), cap_(cap), featCap_(featCap) {
+        check(myslam_loop_bank_create(&h_, streams, kfsPerStream, cap, featCap), "myslam_loop_bank_create");
+    }
+    ~LoopKeyFrameStoreBank() { if (h_) myslam_loop_bank_destroy(h_); }
+    LoopKeyFrameStoreBank(const LoopKeyFrameStoreBank&) = delete; LoopKeyFrameStoreBank& operator=(const LoopKeyFrameStoreBank&) = delete;
+    int streams() const { return streams_; }
+    int kfsPerStream() const { return kfsPerStream_; }
+    int cap() const { return cap_; }
+    int featCap() const { return featCap_; }
+    static int launchesPerFinish() { return myslam_loop_bank_launches_per_finish(); }
+    void SetStream(void* hipStream) { check(myslam_loop_bank_set_stream(h_, hipStream), "myslam_loop_bank_set_stream"); }
+    myslam_loop_bank_arrays View() const { myslam_loop_bank_arrays v; check(myslam_loop_bank_view(h_, &v), "myslam_loop_bank_view"); return v; }
+    // status[s] = MYSLAM_LOOP_BANK_TURN / _SKIPPED / _IDLE; d_itemStatus (Mapper's d_status, stride MYSLAM_MAPPER_STATUS_WORDS) may be nullptr
+    void GateBatch(const int64_t* d_newKFId, const int32_t* d_itemStatus, int statusStride, int32_t* d_active, int32_t* d_status) {
+        check(myslam_loop_bank_gate_batch(h_, d_newKFId, d_itemStatus, statusStride, d_active, d_status), "myslam_loop_bank_gate_batch");
+    }
+    void DetectBatch(const uint64_t* d_bestId, const int32_t* d_bestRow, const float* d_maxScore, const int32_t* d_cntSuspected, uint8_t* d_loopDescriptors,
+                     int32_t* d_nLoop, KeyPoint* d_loopPyramidKeyPoints, int32_t* d_loopFeatureLandmark, int32_t* d_loopSlot, int32_t* d_status,
+                     float thrHigh = 0.94f /*:147*/, int maxSuspected = 3 /*:147*/) {
+        check(myslam_loop_bank_detect_batch(h_, d_bestId, d_bestRow, d_maxScore, d_cntSuspected, thrHigh, maxSuspected, d_loopDescriptors, d_nLoop,
+                                            d_loopPyramidKeyPoints, d_loopFeatureLandmark, d_loopSlot, d_status), "myslam_loop_bank_detect_batch");
+    }
+    // status[s] = MYSLAM_LOOP_BANK_IDLE / _CLOSED / _STORED / MYSLAM_ERR_CAPACITY / MYSLAM_ERR_INVALID; d_add is LoopDatabaseBank::AppendBatch's
+    void FinishBatch(const uint64_t* d_curKFId, const int32_t* d_active, const int32_t* d_verifyStatus, const KeyPoint* d_pyramidKeyPoints,
+                     const uint8_t* d_descriptors, const int32_t* d_counts, const int32_t* d_kfStatus /*may be nullptr*/, const int32_t* d_featureLandmark,
+                     const int32_t* d_nFeatures, int32_t* d_add, int32_t* d_status) {
+        check(myslam_loop_bank_finish_batch(h_, d_curKFId, d_active, d_verifyStatus, d_pyramidKeyPoints, d_descriptors, d_counts, d_kfStatus,
+                                            d_featureLandmark, d_nFeatures, d_add, d_status), "myslam_loop_bank_finish_batch");
+    }
+    // LoopKeyFrameStore::SetLinksBatch per stream (d_value nullptr: ClearLinksBatch); item s names key-frames of stream s only
+    void SetLinksBatch(const int64_t* d_kfId, const int32_t* d_tag, const int32_t* d_value, const int32_t* d_n, int listCap,
+                       const int64_t* d_pendingKfId = nullptr, int32_t* d_pendingFeatureLandmark = nullptr, int32_t* d_nSet = nullptr) {
+        check(myslam_loop_bank_links_batch(h_, d_kfId, d_tag, d_value, d_n, listCap, d_pendingKfId, d_pendingFeatureLandmark, d_nSet),
+              "myslam_loop_bank_links_batch");
+    }
+    void ClearBatch(const int32_t* d_reset) { check(myslam_loop_bank_clear_batch(h_, d_reset), "myslam_loop_bank_clear_batch"); }
+    void Load(int stream, const Stream& s) {
+        const size_t n = s.ids.size();
+        if (s.kps.size() != n * cap_ || s.desc.size() != n * cap_ * 32 || s.rows.size() != n || s.featureLandmark.size() != n * featCap_ || s.nFeatures.size() != n)
+            throw std::runtime_error("LoopKeyFrameStoreBank::Load: the arrays do not hold ids.size() whole slots");
+        check(myslam_loop_bank_load(h_, stream, s.ids.data(), s.kps.data(), s.desc.data(), s.rows.data(), s.featureLandmark.data(), s.nFeatures.data(), (int)n,
+                                    s.lastClosedKFId), "myslam_loop_bank_load");
+    }
+    Stream Get(int stream) {
+        Stream s;
+        const size_t K = kfsPerStream_;
+        s.ids.assign(K, 0); s.kps.assign(K * cap_, KeyPoint{}); s.desc.assign(K * cap_ * 32, 0); s.rows.assign(K, 0); s.featureLandmark.assign(K * featCap_, 0);
+        s.nFeatures.assign(K, 0);
+        int n = 0;
+        check(myslam_loop_bank_get(h_, stream, s.ids.data(), s.kps.data(), s.desc.data(), s.rows.data(), s.featureLandmark.data(), s.nFeatures.data(),
+                                   kfsPerStream_, &n, &s.lastClosedKFId), "myslam_loop_bank_get");
+        s.ids.resize(n); s.kps.resize((size_t)n * cap_); s.desc.resize((size_t)n * cap_ * 32); s.rows.resize(n); s.featureLandmark.resize((size_t)n * featCap_);
+        s.nFeatures.resize(n);
+        return s;
+    }
+    std::vector<int32_t> Sizes() {
+        std::vector<int32_t> n(streams_);
+        check(myslam_loop_bank_sizes(h_, n.data()), "myslam_loop_bank_sizes");
+        return n;
+    }
+};
+
 // The Backend thread for a bank of streams (src/backend.cpp:30-37, :82-121, :126-266 with Map::InsertKeyFrame, src/map.cpp:17-48): one enqueue maps
 // exactly the streams that made a key-frame in the turn or the StereoInit whose outputs it is given; the others keep every byte.  The handle owns the
 // back end, the map archive, the observation archive and every table between them (View()).  Device pointers; KeyFrameBatch enqueues on the

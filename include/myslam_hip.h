@@ -591,9 +591,9 @@ int myslam_lcd_merge_owned_candidates_device(const myslam_lcd_owned_candidate* d
  * MYSLAM_ERR_INVALID; streams > 65535 or rows_per_stream > 2^24 -> MYSLAM_ERR_CAPACITY; create out of device memory -> MYSLAM_ERR_CAPACITY, any
  * other HIP failure -> MYSLAM_ERR_HIP.
  *
- * Out of scope: a per-stream key-frame store (myslam_loop_store stays one map; d_best_row is the key a banked one would use), the decision of which
- * items end unconfirmed (the caller's d_add), the five-key-frames rule of LoopClosing::InsertNewKeyFrame, the wiring into a bank of trackers, and
- * sharding a bank over several GPUs.
+ * The per-stream key-frame store (d_best_row is its key), the decision of which items end unconfirmed (d_add) and the five-key-frames rule of
+ * LoopClosing::InsertNewKeyFrame (d_active) are myslam_loop_bank's, below.  Out of scope: the wiring into a bank of trackers, and sharding a bank over
+ * several GPUs.
  * ------------------------------------------------------------------------------------------ */
 typedef struct myslam_lcdbank myslam_lcdbank;
 #define MYSLAM_LCDBANK_SCANNED 0
@@ -617,6 +617,110 @@ int myslam_lcdbank_view(const myslam_lcdbank* h, const float** d_rows, const uin
 int myslam_lcdbank_load(myslam_lcdbank* h, int s, const uint64_t* ids, const float* rows, int n);   /* host pointers, synchronous, replaces stream s */
 int myslam_lcdbank_get(myslam_lcdbank* h, int s, uint64_t* ids, float* rows, int cap, int* n);      /* host pointers, synchronous */
 int myslam_lcdbank_sizes(myslam_lcdbank* h, int32_t* n /*S, host*/);
+
+/* ------------------------------------------------------------------------------------------
+ * Loop key-frame store BANK: S per-stream key-frame stores in device memory, with the three decisions of LoopClosingRun that sit between the batched
+ * units — which key-frames the loop closer takes at all (LoopClosing::InsertNewKeyFrame, src/loopclosing.cpp:671-681), which ones end unconfirmed and
+ * are kept (`if(!bConfirmedLoopKF) AddToDatabase()`, :73-75, the store half of :651-659) and `_mpLastClosedKF = _mpCurrentKF` (:331) — taken on the
+ * device.  Stream s is one reference System: its own _mvDatabase (include/myslam/loopclosing.h:120) as far as key-frames go, its own _mpLastClosedKF,
+ * ids that start at 0.  myslam_lcdbank holds the same streams' image descriptors; a bank and an lcdbank created with the same number of rows per stream
+ * and fed the same ids and the same d_add make the same refusals, so row r of stream s names the same key-frame in both, and the scan's d_best_row is
+ * the slot detect reads.  If the two are driven apart (different ids, different d_add, one of them cleared alone), detect answers MYSLAM_ERR_INVALID
+ * for that stream: the id at the row is compared with d_best_id.
+ *
+ * Layout, fixed at create (K = kfs_per_stream; strides cap_st / feat_st = cap / feat_cap rounded up to 4, as in myslam_loop_store): key-points
+ * [S][K][cap_st] (28 bytes each), descriptors [S][K][cap_st x 32], landmark tables [S][K][feat_st] i32, rows [S][K] i32, n_feat [S][K] i32, ids [S][K] u64
+ * ascending per stream, n [S] i32, last_closed [S] i64 (-1 = no loop closed yet), put_slot [S] i32 (finish's plan, below).  Nothing grows and nothing
+ * moves, so a recorded step (myslam_graph_begin / _end) that names the bank stays valid and a replay sees the key-frames stored since the recording.
+ * After create no call changes host state but set_stream.  gate / detect / finish / links / clear take DEVICE pointers, enqueue on the handle's
+ * stream and return: they read no device memory from the host, allocate nothing, never synchronise and use no global atomics.  One stream of calls per
+ * bank.  Key-frame ids are below 2^63 (the gate's id is the tracker's signed new_kf_id).
+ *
+ * gate_batch — InsertNewKeyFrame, :671-681 — one launch.  Stream s is a candidate iff d_new_kf_id[s] >= 0 and (d_item_status == NULL or
+ * d_item_status[s * status_stride] == 0): pass myslam_mapper_keyframe_batch's d_status with stride MYSLAM_MAPPER_STATUS_WORDS, whose word 0 is 0 for a
+ * mapped stream.  A candidate is taken iff last_closed[s] < 0 || (uint64)(id - last_closed[s]) > 5, the reference's unsigned expression as written
+ * (:674-675).  d_active[s] = 1 / 0 (what myslam_lcdbank_query_batch takes as d_active); d_status[s] = MYSLAM_LOOP_BANK_TURN, _SKIPPED (one of the
+ * five key-frames behind a closed loop: neither processed nor stored) or _IDLE (no candidate).
+ *
+ * detect_batch — :147 and `_mpLoopKF = _mvDatabase.at(bestId)` (:151) — one launch, grid (chunks, S).  d_best_id / d_best_row / d_max_score / d_cnt are
+ * myslam_lcdbank_query_batch's outputs.  The decision is myslam_loop_detect_batch's, literally (`d_max_score[s] < thr_high || d_cnt[s] >
+ * max_suspected` -> MYSLAM_LOOP_DETECT_NO_LOOP; a NaN score is not "less"; thr_high = +inf rejects every finite score).  The lookup is the row the scan
+ * found: slot = d_best_row[s], valid iff 0 <= slot < n[s] and ids[s][slot] == d_best_id[s] — one load, no search; otherwise MYSLAM_ERR_INVALID with
+ * d_n_loop[s] = 0, d_loop_slot[s] = -1.  Status values, the output layout (item s at + s*cap / + s*feat_cap) and "no other byte of a rejected item is
+ * written" are myslam_loop_detect_batch's.
+ *
+ * finish_batch — :73-75 with :331 and AddToDatabase's store half (:651-659) — myslam_loop_bank_launches_per_finish() = 2 launches.
+ *   a. the decision, one workgroup, per stream s:
+ *        d_active[s] == 0                                      MYSLAM_LOOP_BANK_IDLE, d_add[s] = 0
+ *        d_verify_status[s] == MYSLAM_VERIFY_CONFIRMED         last_closed[s] = d_cur_kf_id[s], d_add[s] = 0, MYSLAM_LOOP_BANK_CLOSED: the key-frame is
+ *                                                              not stored, as in the reference
+ *        n[s] == K                                             MYSLAM_ERR_CAPACITY, d_add[s] = 0, every byte of the stream kept
+ *        n[s] > 0 and d_cur_kf_id[s] <= the last id held       MYSLAM_ERR_INVALID, d_add[s] = 0, every byte of the stream kept (std::map order)
+ *        otherwise                                             put_slot[s] = n[s], d_add[s] = 1, MYSLAM_LOOP_BANK_STORED
+ *      put_slot[s] = -1 in every case but the last.
+ *   b. the copy, grid (chunks, S): a workgroup reads put_slot[s], which nothing writes during this launch, and returns when it is -1; otherwise it moves
+ *      its share of the stream's item (d_pyr_kps / d_desc / d_counts / d_kf_status / d_feat_landmark / d_n_feat: item s of
+ *      myslam_orb_process_keyframes_batch's outputs and the landmark table, in myslam_loop_store_put_batch's layout and with its clamping rules: counts
+ *      clamped to [0, cap] / [0, feat_cap], d_kf_status[s] != 0 stores 0 rows) into slot put_slot[s]; chunk 0 writes rows, n_feat, the id and
+ *      n[s] = put_slot[s] + 1.  No workgroup reads n[s] in this launch: the count changes at a launch boundary, with no flag, atomic or fence inside a
+ *      launch.
+ *   d_add is myslam_lcdbank_append_batch's d_add.
+ *
+ * links_batch — myslam_loop_store_clear_links_batch / _set_links_batch per stream, entry for entry (LINK UPKEEP below; d_value NULL = -1
+ * for every entry: clear_links): item s walks its list against stream s's ids only; the pending key-frame's table and the skipping of ids that are not held
+ * included.  One launch of S workgroups.
+ *
+ * clear_batch: n[s] = 0 and last_closed[s] = -1 where d_reset[s] != 0 (a stream that starts again, myslam_tracker_reset_stream).  One launch.
+ *
+ * load / get / sizes are the synchronous resume and test path: HOST pointers, they wait for the handle's stream (MYSLAM_ERR_UNSUPPORTED while it is being
+ * recorded).  load replaces stream s: n key-frames, kps n x cap, desc n x cap x 32, feat_landmark n x feat_cap, whole slots; ids ascend strictly,
+ * rows in [0, cap], n_feat in [0, feat_cap], last_closed >= -1, else MYSLAM_ERR_INVALID; n > K: MYSLAM_ERR_CAPACITY; the stream keeps every byte then.
+ * get: *n = the count, *last_closed; more than kf_room key-frames: MYSLAM_ERR_CAPACITY, nothing copied; array pointers may be NULL.
+ *
+ * Call level, nothing enqueued: NULL required pointers (d_item_status, d_kf_status, d_value, d_n_set and both pending pointers may be NULL; the
+ * pending pointers both or neither), sizes <= 0, a stream index out of range -> MYSLAM_ERR_INVALID; cap > 16384, feat_cap > 65536
+ * (myslam_loop_match_batch's limits) or streams > 65535 -> MYSLAM_ERR_CAPACITY; create out of device memory -> MYSLAM_ERR_CAPACITY, any other HIP
+ * failure -> MYSLAM_ERR_HIP.
+ *
+ * Out of scope: the wiring into a bank of trackers, skipping ProcessNewKF's work for the streams the gate rejects, DeepLCD's in-place blur hand-back,
+ * sharding a bank over several GPUs.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct myslam_loop_bank myslam_loop_bank;
+#define MYSLAM_LOOP_BANK_TURN    0
+#define MYSLAM_LOOP_BANK_SKIPPED 1
+#define MYSLAM_LOOP_BANK_IDLE    2
+#define MYSLAM_LOOP_BANK_CLOSED  3
+#define MYSLAM_LOOP_BANK_STORED  4
+typedef struct myslam_loop_bank_arrays {      /* device pointers and shapes, as laid out above */
+    myslam_keypoint* kps; uint8_t* desc; int32_t* feat_landmark;
+    int32_t* rows; int32_t* n_feat; uint64_t* ids; int32_t* n; int64_t* last_closed; int32_t* put_slot;
+    int32_t streams, kfs_per_stream, cap, feat_cap;
+    int64_t cap_stride, feat_stride;          /* key-points / landmark entries per slot */
+} myslam_loop_bank_arrays;
+int myslam_loop_bank_create(myslam_loop_bank** out, int streams, int kfs_per_stream, int cap, int feat_cap);
+int myslam_loop_bank_destroy(myslam_loop_bank* h);
+int myslam_loop_bank_set_stream(myslam_loop_bank* h, void* hip_stream);
+int myslam_loop_bank_view(const myslam_loop_bank* h, myslam_loop_bank_arrays* out);
+int myslam_loop_bank_launches_per_finish(void);
+int myslam_loop_bank_gate_batch(myslam_loop_bank* h, const int64_t* d_new_kf_id /*S*/, const int32_t* d_item_status /*may be NULL*/, int status_stride,
+        int32_t* d_active /*out S*/, int32_t* d_status /*out S*/);
+int myslam_loop_bank_detect_batch(myslam_loop_bank* h,
+        const uint64_t* d_best_id, const int32_t* d_best_row, const float* d_max_score, const int32_t* d_cnt,   /* myslam_lcdbank_query_batch's outputs, S each */
+        float thr_high, int max_suspected,                                                                      /* 0.94f and 3 at loopclosing.cpp:147 */
+        uint8_t* d_loop_desc, int32_t* d_n_loop, myslam_keypoint* d_loop_pyr, int32_t* d_loop_feat_landmark,    /* loop_match_batch's inputs, item s at + s*cap (+ s*feat_cap) */
+        int32_t* d_loop_slot, int32_t* d_status);                                                               /* S each */
+int myslam_loop_bank_finish_batch(myslam_loop_bank* h, const uint64_t* d_cur_kf_id /*S*/, const int32_t* d_active /*S*/, const int32_t* d_verify_status /*S*/,
+        const myslam_keypoint* d_pyr_kps, const uint8_t* d_desc, const int32_t* d_counts, const int32_t* d_kf_status /*may be NULL*/,
+        const int32_t* d_feat_landmark, const int32_t* d_n_feat,
+        int32_t* d_add /*out S*/, int32_t* d_status /*out S*/);
+int myslam_loop_bank_links_batch(myslam_loop_bank* h, const int64_t* d_kf_id, const int32_t* d_tag, const int32_t* d_value /*NULL = -1 for all*/,
+        const int32_t* d_n, int list_cap, const int64_t* d_pending_kf_id, int32_t* d_pending_feat_landmark, int32_t* d_n_set);
+int myslam_loop_bank_clear_batch(myslam_loop_bank* h, const int32_t* d_reset /*S*/);
+int myslam_loop_bank_load(myslam_loop_bank* h, int s, const uint64_t* ids, const myslam_keypoint* kps, const uint8_t* desc, const int32_t* rows,
+        const int32_t* feat_landmark, const int32_t* n_feat, int n, int64_t last_closed);      /* host pointers, synchronous, replaces stream s */
+int myslam_loop_bank_get(myslam_loop_bank* h, int s, uint64_t* ids, myslam_keypoint* kps, uint8_t* desc, int32_t* rows, int32_t* feat_landmark,
+        int32_t* n_feat, int kf_room, int* n, int64_t* last_closed);                           /* host pointers, synchronous */
+int myslam_loop_bank_sizes(myslam_loop_bank* h, int32_t* n /*S, host*/);
 
 /* ------------------------------------------------------------------------------------------
  * Local BA linear-system build — replaces the per-edge work g2o does for
@@ -1805,8 +1909,9 @@ int myslam_tracker_relink_batch(myslam_tracker* h, const int64_t* d_kf_id, const
  * myslam_mapper_reset_item — host call, synchronous; MYSLAM_ERR_UNSUPPORTED while the stream is being recorded.  Empties the stream's tables, its
  * map-archive item and its observation-archive item and clears its sticky fault: a restart after LOST, together with myslam_tracker_reset_stream.
  * myslam_mapper_set_stream sets the stream of the three owned handles too.
- * OUT OF SCOPE: loop closing — the five-key-frame skip of src/loopclosing.cpp:671-681, the store's put and everything after it — and DeepLCD's
- * in-place blur of the key-frame image (src/deeplcd.cpp:46), which belongs with it.
+ * OUT OF SCOPE: loop closing — the five-key-frame skip of src/loopclosing.cpp:671-681, the store's put and everything after it (for a bank they are
+ * myslam_loop_bank_gate_batch, which reads this handle's d_status, and myslam_loop_bank_finish_batch) — and DeepLCD's in-place blur of the key-frame
+ * image (src/deeplcd.cpp:46), which belongs with it.
  * ------------------------------------------------------------------------------------------ */
 #define MYSLAM_MAPPER_IDLE 3           /* no key-frame of this item in this call: nothing of it was touched */
 #define MYSLAM_MAPPER_STATUS_WORDS 8
